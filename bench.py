@@ -10,6 +10,11 @@ metric / value : aggregate AGBNP-force-limited ns/day over all replicas at the 1
 multi-GPU      : replicas only (the force evaluation does not shard).  One process per
                  GPU, independent geometries, no data-path collective; RCCL carries only the job's
                  decisions (MAX of {failed, withheld, elapsed}) and the gather of the per-rank records.
+plain run      : set-up, warm-up, the timed steps, --dump-outputs DIR if given (forces and energy of the last timed
+                 step), the JSON line with the headline.  Everything below runs with --full only.
+--full         : a per-kernel pass after the headline (kernel_avg_us, roofline, rooflines_issue), the CPU baseline on a
+                 sample of the timed geometries (cpu_baseline, parity_on_sample; with N > 1 every rank checks its own
+                 sample) and, on one GPU, the optional records below.
 secondary      : on one GPU the same JSON line also carries BASELINE.json's other configurations (trpcage
                  GaussVol, trpcage AGBNP1 with CutoffNonPeriodic 1.2 nm, the 16 608-atom HIV-RT stand-in),
                  each with its own parity-on-sample figure, under "other_modes" the timings of the fast
@@ -18,6 +23,7 @@ secondary      : on one GPU the same JSON line also carries BASELINE.json's othe
                  2000-step random walk ("drift").  --secondary 0 skips them.
 
   python bench.py --gpus 1 --steps 200 --warmup 20
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full  # + per-kernel split, CPU baseline, optional records
   python bench.py --gpus N --steps K --warmup W          # no launcher: this process starts the N ranks itself
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
@@ -314,6 +320,9 @@ class Replica:
             self.geoms, self.d_pos = None, geometries
         self.d_force = dev.zeros((self.n, 3), torch.float64)
         self.d_energy = dev.zeros((1,), torch.float64)
+        # the LAST evaluation of a timed pass adds into buffers of its own: what that step computed, for --dump-outputs
+        self.d_force_last = dev.zeros((self.n, 3), torch.float64)
+        self.d_energy_last = dev.zeros((1,), torch.float64)
         self.stream = dev.current_stream() if stream is None else stream.cuda_stream
         self.step_bytes = self.n * 3 * 8
         self.n_geoms = int(self.d_pos.shape[0])
@@ -323,13 +332,16 @@ class Replica:
         self.in_timed_pass, self.timed_calls = False, 0
 
     def run(self, first, count):
-        base = self.d_pos.data_ptr()
+        base, d_force, d_energy = self.d_pos.data_ptr(), self.d_force.data_ptr(), self.d_energy.data_ptr()
+        last = first + count - 1 if self.in_timed_pass else -1
         for s in range(first, first + count):
             if self.in_timed_pass:  # (tests of the N > 1 path on real GPUs: a rank that dies between the barriers)
                 self.timed_calls += 1
                 if self.timed_calls == self.fail_at:
                     raise RuntimeError(f"injected failure at evaluation {self.timed_calls} of this rank's timed pass (AGBNP_BENCH_FAIL_AT)")
-            self.kernel.execute_device(base + s * self.step_bytes, self.d_force.data_ptr(), self.d_energy.data_ptr(), self.stream)
+            if s == last:
+                d_force, d_energy = self.d_force_last.data_ptr(), self.d_energy_last.data_ptr()
+            self.kernel.execute_device(base + s * self.step_bytes, d_force, d_energy, self.stream)
 
     def state(self):
         """What the engine says about its capacity negotiation right now (for the message of a pass that would not settle):
@@ -403,8 +415,8 @@ class Replica:
         for k in range(tries):
             self.tries += 1
             self.report["tries"] = self.tries
-            self.d_force.zero_()
-            self.d_energy.zero_()
+            for buf in (self.d_force, self.d_energy, self.d_force_last, self.d_energy_last):
+                buf.zero_()
             self.dev.synchronize()
             barrier()
             self.dev.synchronize()
@@ -879,7 +891,7 @@ def worker(args):
     record = {"rank": rank, "local_rank": local_rank, **dev.identity(),
               "ms_per_eval": 1e3 * elapsed_local / K, "ns_day": 86.4 / (1e3 * elapsed_local / K), "pid": os.getpid(),
               "timed_tries": rep.tries, "clock_warm_evals": warm_evals}
-    if mdist is not None and args.cpu_evals > 0:
+    if args.full and mdist is not None and args.cpu_evals > 0:
         # N > 1: EVERY rank checks the first of its own timed geometries against the CPU oracle (the ranks run different
         # geometries on different devices; rank 0's sample says nothing about rank 5's GPU).  All ranks at once, one host
         # core each, outside the timed region; a rank that disagrees ends the job.
@@ -910,6 +922,8 @@ def worker(args):
         dist.destroy_process_group()
     if rank != 0:
         return 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rep)
 
     slots = int(kernel.scalar("total_nodes")) + (n - system.nheavy) + 1  # + hydrogen slots + root, as the reference counts
     b_eval, b_kernel = algorithmic_bytes(n, slots)
@@ -1086,20 +1100,31 @@ def worker(args):
 
     line = Line(result)
     try:
-        # `roofline` and `cpu_baseline` belong to the contract: a failure there is reported in the line (and on stderr) and
-        # the line is still printed -- a line without one of them says why
-        r = line.optional("roofline", roofline_section)
-        if "error" in r:
-            line.put("roofline_error", r)
-        r = line.optional("cpu_baseline", cpu_baseline_section)
-        if "error" in r:
-            line.put("cpu_baseline_error", r)
-        if world == 1 and args.secondary and mode is None and args.system == "1dwc":
-            line.watchdog(args.secondary_budget_s)
-            optional_records()
+        # everything behind the headline runs with --full only: a plain run prints the headline and nothing else
+        if args.full:
+            # `roofline` and `cpu_baseline` belong to the full line: a failure there is reported in the line (and on stderr)
+            # and the line is still printed -- a line without one of them says why
+            r = line.optional("roofline", roofline_section)
+            if "error" in r:
+                line.put("roofline_error", r)
+            r = line.optional("cpu_baseline", cpu_baseline_section)
+            if "error" in r:
+                line.put("cpu_baseline_error", r)
+            if world == 1 and args.secondary and mode is None and args.system == "1dwc":
+                line.watchdog(args.secondary_budget_s)
+                optional_records()
     finally:
         line.emit()
     return 0
+
+
+def dump_outputs(directory, rep):
+    """--dump-outputs: what the last timed evaluation of this rank handed its caller -- forces (N x 3, kJ/mol/nm) and energy
+    (kJ/mol), float64 -- as DIR/forces.npy and DIR/energy.npy.  Its geometry is the seeded jitter number warmup + steps - 1,
+    the same in every run with the same arguments."""
+    os.makedirs(directory, exist_ok=True)
+    for name, buf in (("forces", rep.d_force_last), ("energy", rep.d_energy_last)):
+        np.save(os.path.join(directory, name + ".npy"), buf.cpu().numpy().astype(np.float64))
 
 
 def launch_replicas(args, argv):
@@ -1182,8 +1207,14 @@ def parse_args(argv):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--system", default="1dwc")
-    ap.add_argument("--cpu-evals", type=int, default=20, help="size of the CPU-baseline sample (0 disables the leg; at most 5 when N > 1)")
-    ap.add_argument("--secondary", type=int, default=1, help="also time BASELINE.json's other configurations (one GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the per-kernel (roofline) pass, the CPU baseline and parity samples and the "
+                         "optional records (--secondary); without it the line carries the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the forces and energy of the last timed evaluation (rank 0) to DIR/forces.npy and DIR/energy.npy")
+    ap.add_argument("--cpu-evals", type=int, default=20,
+                    help="with --full: size of the CPU-baseline sample (0 disables the leg; at most 5 when N > 1)")
+    ap.add_argument("--secondary", type=int, default=1, help="with --full: also time BASELINE.json's other configurations (one GPU only)")
     ap.add_argument("--secondary-budget-s", type=float, default=300.0,
                     help="time budget of the optional records behind the headline; when it runs out the line is printed with what it has")
     ap.add_argument("--mode", default="reference", choices=["reference", "fast", "fast+single", "deterministic"],

@@ -3,7 +3,7 @@
 # than the effects looked for).  Usage: scripts/abx.sh <rounds> "<tag>|<lib or ->|VAR=v VAR=v" ...   [BENCH_ARGS="..."]
 rounds=$1; shift
 mkdir -p gpurun_out
-args=${BENCH_ARGS:---steps 300 --cpu-evals 0 --secondary 0}
+args=${BENCH_ARGS:---full --steps 300 --cpu-evals 0 --secondary 0}
 for i in $(seq 1 $rounds); do
   for spec in "$@"; do
     IFS='|' read -r tag lib envs <<< "$spec"

@@ -13,11 +13,11 @@ import json, os, time
 from openmm_agbnp_plugin_amd import _lib
 head = open("profiles/.git_head").read().strip() if os.path.exists("profiles/.git_head") else None
 print(json.dumps({"library_build_id": _lib.build_id(), "git_head": head, "taken": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
-                  "command": "python3 bench.py --steps 100 --warmup 10 --cpu-evals 0 --secondary 0 under rocprofv3 (scripts/profile_round.sh)"}, indent=1))
+                  "command": "python3 bench.py --full --steps 100 --warmup 10 --cpu-evals 0 --secondary 0 under rocprofv3 (scripts/profile_round.sh)"}, indent=1))
 PY
 cat profiles/$tag/profile_head.json
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-BENCH="python3 bench.py --steps 100 --warmup 10 --cpu-evals 0 --secondary 0"
+BENCH="python3 bench.py --full --steps 100 --warmup 10 --cpu-evals 0 --secondary 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o bench -- $BENCH > $out/stats_bench.log 2>&1
 echo "stats pass done"
 for c in FETCH_SIZE WRITE_SIZE; do

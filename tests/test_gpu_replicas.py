@@ -40,10 +40,10 @@ def _gone(pid):
 
 
 def test_two_ranks_share_the_gpu_through_the_self_launcher(gpu_required):
-    """`python3 bench.py --gpus 2` with no launcher around it, on the real engine: two fresh processes, two contexts on the
-    device, one JSON line from rank 0 with the whole-job figure, roofline and cpu_baseline, and EVERY rank's own sample
+    """`python3 bench.py --gpus 2 --full` with no launcher around it, on the real engine: two fresh processes, two contexts on
+    the device, one JSON line from rank 0 with the whole-job figure, roofline and cpu_baseline, and EVERY rank's own sample
     against the CPU oracle."""
-    p, lines, pids, took = _bench({"AGBNP_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--steps", "5", "--warmup", "2", "--secondary", "0",
+    p, lines, pids, took = _bench({"AGBNP_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--secondary", "0",
                                   "--cpu-evals", "1", "--preheat-ms", "50")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout
@@ -68,7 +68,7 @@ def test_two_ranks_share_the_gpu_through_the_self_launcher(gpu_required):
 def test_one_rank_sends_every_collective_through_rccl(gpu_required):
     """The RCCL plumbing on the one GPU there is: a one-rank process group on backend nccl, every Job.sync and the gather
     of the records through it."""
-    p, lines, pids, took = _bench({"AGBNP_BENCH_FORCE_DIST": "1"}, "--gpus", "1", "--steps", "5", "--warmup", "2", "--secondary", "0",
+    p, lines, pids, took = _bench({"AGBNP_BENCH_FORCE_DIST": "1"}, "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--secondary", "0",
                                   "--cpu-evals", "1", "--preheat-ms", "50")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout
@@ -106,11 +106,11 @@ def _errors(node, path="line"):
 
 
 def test_the_drivers_own_command_line_prints_a_complete_line(gpu_required):
-    """The driver's exact command -- `python3 bench.py --gpus 1 --steps 20 --warmup 5`, a fresh child process, every optional
-    record behind the headline included (BENCH_r05 died in one of them: no `-m gpu` test ran this command line): exit code 0,
+    """The driver's command with --full -- `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`, a fresh child process,
+    every optional record behind the headline included (BENCH_r05 died in one of them: no `-m gpu` test ran this command line): exit code 0,
     ONE JSON line with `roofline` and `cpu_baseline`, BASELINE.json's configurations in `secondary`, and no record that
     reports an error or was cut off by the watchdog."""
-    p, lines, pids, took = _bench({}, "--gpus", "1", "--steps", "20", "--warmup", "5", timeout=500)
+    p, lines, pids, took = _bench({}, "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", timeout=500)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout[-2000:]
     r = lines[0]
@@ -129,3 +129,29 @@ def test_the_drivers_own_command_line_prints_a_complete_line(gpu_required):
     assert "did not settle" not in p.stderr
     assert all(_gone(pid) for pid in pids)
     assert took < 240, took
+
+
+def test_the_plain_command_line_times_the_steps_and_dumps_the_last_one(gpu_required, tmp_path):
+    """`python3 bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR` without --full: exit code 0, one line with the
+    headline and nothing measured behind it, and in DIR the forces and energy of the LAST timed evaluation alone (geometry
+    warmup + steps - 1 of rank 0's seeded jitter) at the parity bar of the one-GPU tests against the CPU oracle."""
+    import numpy as np
+
+    import openmm_agbnp_plugin_amd as P
+    from oracle import Oracle
+
+    out = tmp_path / "outputs"
+    p, lines, pids, took = _bench({}, "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out))
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = lines[0]
+    assert r["n_gpus"] == 1 and r["steps"] == 20 and r["warmup"] == 5 and r["unit"] == "ns/day" and r["dtype"] == "f64"
+    assert 0.02 < r["ms_per_step"] < 5.0 and abs(r["value"] - 86.4 / r["ms_per_step"]) < 1e-9 * r["value"]
+    assert not {"roofline", "cpu_baseline", "parity_on_sample", "kernel_avg_us", "secondary", "drift"} & set(r), sorted(r)
+    s = P.load_system("1dwc")
+    eo, fo = Oracle(*s.params(), version=1).execute(s.jittered(5 + 20 - 1))
+    forces, energy = np.load(out / "forces.npy"), np.load(out / "energy.npy")
+    assert forces.shape == (s.n, 3) and forces.dtype == np.float64 and energy.shape == (1,)
+    assert abs(energy[0] - eo) <= 1e-6 and float(np.abs(forces - fo).max()) <= 1e-7, (energy[0] - eo, float(np.abs(forces - fo).max()))
+    assert all(_gone(pid) for pid in pids)
+    assert took < 90, took

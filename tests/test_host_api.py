@@ -116,10 +116,9 @@ def test_structure_parser_units(systems):
 
 @pytest.mark.parametrize("name,dms", [("trpcage", "trpcage_agbnp1.dms"), ("1dwc", "1dwc_agbnp1.dms")])
 def test_dms_loader_matches_exported_fixture(systems, name, dms):
-    """Build-container only: the reference's example/*.dms files exist only there (never on the GPU box)."""
-    path = os.path.join("/root/reference/example", dms)
-    if not os.path.exists(path):
-        pytest.skip("reference examples are not present on this machine")
+    """The reference's example/*.dms structures, trimmed to the tables and columns the loader reads (tests/golden/,
+    made by tests/golden/make_dms_fixtures.py), load to the bundled .dat fixtures exported from the full files."""
+    path = os.path.join(ROOT, "tests", "golden", dms)
     a, b = P.load_dms(path), systems(name)
     assert a.n == b.n
     for x, y in ((a.pos, b.pos), (a.radius, b.radius), (a.gamma, b.gamma), (a.alpha, b.alpha), (a.charge, b.charge)):

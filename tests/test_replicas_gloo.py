@@ -93,6 +93,7 @@ def _fake_replica(bench, torch, script, raise_at=0):
     rep = bench.Replica.__new__(bench.Replica)  # the real settle / preheat / timed logic, no device
     rep.dev, rep.kernel, rep.stream = _Dev, _FakeKernel(script), None
     rep.d_force, rep.d_energy = torch.zeros(3), torch.zeros(1)
+    rep.d_force_last, rep.d_energy_last = torch.zeros(3), torch.zeros(1)
     rep.runs = 0
 
     def run(first, count):
@@ -193,10 +194,10 @@ def _self_launch(extra_env, *flags, timeout=300):
 def test_bench_main_self_launches_two_ranks_end_to_end():
     """The driver's invocation for N > 1 -- `python3 bench.py --gpus N`, no torch.distributed.run -- must work: the parent
     (which imports neither torch nor the engine) starts the ranks, rank 0's ONE JSON line comes back through it, and the
-    line carries roofline and cpu_baseline like the one-GPU line.  Rank 1 has one evaluation withheld in its first timed try:
+    line carries roofline and cpu_baseline (--full) like the one-GPU line.  Rank 1 has one evaluation withheld in its first timed try:
     both ranks repeat."""
     pytest.importorskip("torch")
-    p, lines = _self_launch({"AGBNP_FAKE_WITHHELD_1": "0,0,1"}, "--cpu-evals", "2")
+    p, lines = _self_launch({"AGBNP_FAKE_WITHHELD_1": "0,0,1"}, "--full", "--cpu-evals", "2")
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, p.stdout
     r = lines[0]
@@ -255,7 +256,7 @@ def test_bench_main_under_torch_distributed_run():
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--system", "trpcage", "--steps", "6",
-                        "--warmup", "2", "--preheat-ms", "0", "--cpu-evals", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+                        "--warmup", "2", "--preheat-ms", "0", "--full", "--cpu-evals", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -291,7 +292,7 @@ def test_an_optional_record_that_fails_becomes_an_error_entry_and_the_line_is_pr
 
 
 def test_bench_main_prints_the_line_when_the_optional_records_overrun_their_budget():
-    """The driver's one-GPU command shape on the CPU double: headline, roofline and cpu_baseline are in the line, the optional
+    """The one-GPU command shape with --full on the CPU double: headline, roofline and cpu_baseline are in the line, the optional
     records behind them get 0.2 s and are cut off by the watchdog -- exit code 0, one line, which says so."""
     pytest.importorskip("torch")
     import json
@@ -301,7 +302,7 @@ def test_bench_main_prints_the_line_when_the_optional_records_overrun_their_budg
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat-ms", "0",
-                        "--cpu-evals", "1", "--secondary-budget-s", "0.2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+                        "--full", "--cpu-evals", "1", "--secondary-budget-s", "0.2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -322,7 +323,7 @@ def test_bench_main_reports_a_failed_optional_record_inside_the_line():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat-ms", "0",
-                        "--cpu-evals", "1", "--secondary-budget-s", "6"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+                        "--full", "--cpu-evals", "1", "--secondary-budget-s", "6"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -331,3 +332,31 @@ def test_bench_main_reports_a_failed_optional_record_inside_the_line():
     assert r["drift"]["error"].startswith("SystemExit: injected failure of the record 'drift'")
     assert "record 'drift' failed and is reported inside the line" in p.stderr
     assert "secondary" in r  # (the records behind the failed one were started)
+
+
+def test_plain_bench_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing measured behind it, --steps sets the timed steps, and
+    --dump-outputs writes the last timed evaluation's forces and energy as float64 .npy files."""
+    pytest.importorskip("torch")
+    import json
+    import subprocess
+
+    import numpy as np
+
+    env = dict(os.environ, AGBNP_BENCH_BACKEND="gloo", AGBNP_BENCH_BACKEND_MODULE="tests.fake_bench_backend")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--system", "trpcage", "--steps", "7", "--warmup", "2",
+                        "--preheat-ms", "0", "--dump-outputs", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    r = lines[0]
+    assert r["steps"] == 7 and r["warmup"] == 2 and r["unit"] == "ns/day" and r["higher_is_better"] is True and r["dtype"] == "f64"
+    assert r["ms_per_step"] > 0 and abs(r["value"] - 86.4 / r["ms_per_step"]) < 1e-9 * r["value"]
+    assert not {"roofline", "cpu_baseline", "parity_on_sample", "kernel_avg_us", "secondary", "drift"} & set(r), sorted(r)
+    assert "parity_on_sample" not in r["ranks"][0]
+    forces, energy = np.load(out / "forces.npy"), np.load(out / "energy.npy")
+    assert forces.shape == (272, 3) and forces.dtype == np.float64
+    assert energy.shape == (1,) and energy.dtype == np.float64
