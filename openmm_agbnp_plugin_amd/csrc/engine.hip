@@ -76,11 +76,70 @@ struct DevBuf {
 constexpr int kGlobalVariant = 4;  // tree_kernels.hip: 0 (432, 64), 1 (512, 64), 2 (1024, 128), 3 (2048, 256) in LDS, 4 in HBM scratch
 constexpr int kGlobalGrid = 256;  // persistent workgroups of the global-scratch variant
 
+// Engine settings from the environment, read once by agbnp_hip_create (a change takes effect in the next context).  "Used
+// by" names bench.py and the GPU tests tests/test_gpu_{five_launches,healing,parity}.py by their last word.
+//
+//   AGBNP_HIP_...      default               values, clamp                                           used by
+//   FIVE_LAUNCHES      on (versions 0, 1)    0: the k_prep launch stays                              bench.py, five_launches, healing, parity
+//   ROWS               the row form          0: the tile kernels everywhere                          five_launches, parity
+//   HEAL               on                    0: an overgrown forest voids the evaluation             healing, parity
+//   SPLIT_FIT          on                    0: a lone subtree beyond the store climbs a variant     parity
+//   GB_FAR             more than 8192 atoms  0 / 1: the far-strip test off / on                      parity
+//   ROUND_PERMILLE     1000                  >= 100                                                  healing, parity
+//   REPLAN_EVERY       16                    >= 1                                                    parity
+//   ADAPTER_LAUNCH     off                   nonzero: execute_openmm through the adapter launch      parity
+//   NO_PINNED_STAGING  unset                 set: pageable host-facing transfers                     parity
+//   SKIN               0.1 nm                [0, 1]                                                  parity
+//   ROW_MOVE           half the skin         >= 0, at most half the skin (0: rebuild every geometry) bench.py
+//   ROW_SLICE          tuned on the device   > 0: fixed, [256, 512] in steps of 64                   parity
+//   ROW_FILL           1.5                   >= 0.01                                                 parity
+//   ROW_STRIDE         from the system       >= 128                                                  parity
+//   MASK_SKIN          0.08 nm               [0, 0.5]                                                include/agbnp_hip.h documents it
+// SKIN and the ROW_* settings take effect only in a context that can run the row form (allocate_rows).
+struct EngineSettings {
+  bool five_launches = true;
+  int rows = -1;    // -1: unset
+  bool heal = true;
+  bool split_fit = true;
+  int gb_far = -1;  // -1: unset
+  int round_permille = 1000;
+  int replan_every = 16;
+  bool adapter_launch = false;
+  bool pinned_staging = true;
+  double skin = 0.1;
+  double row_move = -1.0;   // < 0: unset
+  int row_slice = 0;        // 0: unset
+  double row_fill = 1.5;
+  int row_stride = 0;       // 0: unset
+  double mask_skin = 0.08;  // (0.06 and 0.08 cost the cavity launch the same; 0.04 renews the masks at every other evaluation of the headline's jitter)
+};
+
+EngineSettings read_settings() {
+  EngineSettings s;
+  if (const char* v = getenv("AGBNP_HIP_FIVE_LAUNCHES")) s.five_launches = atoi(v) != 0;
+  if (const char* v = getenv("AGBNP_HIP_ROWS")) s.rows = atoi(v) != 0 ? 1 : 0;
+  if (const char* v = getenv("AGBNP_HIP_HEAL")) s.heal = atoi(v) != 0;
+  if (const char* v = getenv("AGBNP_HIP_SPLIT_FIT")) s.split_fit = atoi(v) != 0;
+  if (const char* v = getenv("AGBNP_HIP_GB_FAR")) s.gb_far = atoi(v) != 0 ? 1 : 0;
+  if (const char* v = getenv("AGBNP_HIP_ROUND_PERMILLE")) s.round_permille = std::max(100, atoi(v));
+  if (const char* v = getenv("AGBNP_HIP_REPLAN_EVERY")) s.replan_every = std::max(1, atoi(v));
+  if (const char* v = getenv("AGBNP_HIP_ADAPTER_LAUNCH")) s.adapter_launch = atoi(v) != 0;
+  if (getenv("AGBNP_HIP_NO_PINNED_STAGING")) s.pinned_staging = false;
+  if (const char* v = getenv("AGBNP_HIP_SKIN")) s.skin = std::min(1.0, std::max(0.0, atof(v)));
+  if (const char* v = getenv("AGBNP_HIP_ROW_MOVE")) s.row_move = std::max(atof(v), 0.0);
+  if (const char* v = getenv("AGBNP_HIP_ROW_SLICE")) s.row_slice = atoi(v);
+  if (const char* v = getenv("AGBNP_HIP_ROW_FILL")) s.row_fill = std::max(0.01, atof(v));
+  if (const char* v = getenv("AGBNP_HIP_ROW_STRIDE")) s.row_stride = std::max(128, atoi(v));
+  if (const char* v = getenv("AGBNP_HIP_MASK_SKIN")) s.mask_skin = std::min(0.5, std::max(0.0, atof(v)));
+  return s;
+}
+
 }  // namespace
 
 struct agbnp_hip_context {
   int n = 0, nh = 0, version = 1, method = 0, device = 0;
   double cutoff = 1.0;
+  EngineSettings cfg;  // read_settings() at agbnp_hip_create
   std::string err;
   // host copies of the parameters (reference: ReferenceAGBNPKernels.h:60-91)
   std::vector<double> r_vdw, gamma, alpha, charge;
@@ -114,7 +173,6 @@ struct agbnp_hip_context {
   int five_evals = 0;          // evaluations enqueued in the mode so far: evaluation k works on set k & 1
   bool five_device = false;    // the device names the set (from the context's first stream capture on: see PairArgs::five)
   bool masks_valid = false;
-  double mask_skin = 0.08;     // nm; AGBNP_HIP_MASK_SKIN (0.06 and 0.08 cost the cavity launch the same; 0.04 renews the masks at every other evaluation of the headline's jitter)
   DevBuf<int> d_estatus, d_row_atoms, d_epoch;  // d_epoch[0]: evaluations the device has been through in that mode (its parity names the set)
   DevBuf<double> d_mask_ref;
   double* htable(int p) const { return d_heavy.p + (size_t)p * kHvRows * hstride; }
@@ -133,8 +191,6 @@ struct agbnp_hip_context {
   DevBuf<unsigned> d_nl_items;
   int nl_items_cap = 0;
   DevBuf<double> d_egb_rows;   // per-wave energy partials of the GB rows
-  int rows_policy = -1;        // AGBNP_HIP_ROWS: 0 = the tile kernels everywhere; unset or 1 = the row form wherever it can run (reference
-                               // and fast mode; the deterministic and single-precision modes keep the tiles)
   int nlg_stride = 0;
   double row_fill = 1.5;       // AGBNP_HIP_ROW_FILL: the density bound behind the walked part of a list, in protein-interior densities
   int row_boost = 1;           // widens the part of a list that the row launches walk (doubles when a list has outgrown it)
@@ -142,11 +198,10 @@ struct agbnp_hip_context {
   DevBuf<double4> d_rec_h, d_hrow, d_grec, d_hrec;
   DevBuf<double2> d_pw;        // four arrays of nti * ntj * 15 entries: {c0, c1} / {c2, c3} by [screened][screener], the same by [screener][screened]
   int forests_hint = 0;        // forests of the last evaluation the host has read the status of (0: none yet); reset by a fallback packing
-  bool fused_outputs = true;   // version 1: the pseudo-volume launch adds the forces itself (AGBNP_HIP_OUTPUT_LAUNCH=1: k_outputs does)
   bool rows_capable = false;   // the buffers above exist
   bool rows_disabled = false;  // a neighbour row outgrew its stride once: the tile kernels from then on
   double skin = 0.1;           // nm; AGBNP_HIP_SKIN
-  double row_move = -1.0;      // nm; AGBNP_HIP_ROW_MOVE, read ONCE when the context is created (< 0: half the skin)
+  double row_move = -1.0;      // nm; AGBNP_HIP_ROW_MOVE (< 0: half the skin)
   int nlh_stride = 0, nla_stride = 0;  // entries reserved per list part
   DevBuf<int2> d_sizes;
   DevBuf<double> d_born_part, d_born, d_born_fp, d_brw, d_e_atom, d_gbf, d_dbf, d_egb_part, d_components;
@@ -170,8 +225,6 @@ struct agbnp_hip_context {
   unsigned generation = 1;     // bumped whenever kernel arguments a captured graph has frozen go stale
   int fallback_parts = 1;      // the packing an overflowed evaluation is repeated on: every subtree shared among this many work items, each
                                // alone in its slot (1, or 4 once a lone item has outgrown the store; never lowered)
-  bool heal = true;            // AGBNP_HIP_HEAL=0: a forest that outgrows its store voids the evaluation (rounds 2-5) instead of being built again in smaller sets
-  bool split_fit = true;       // AGBNP_HIP_SPLIT_FIT=0: a lone subtree that outgrows the store moves the system to the next variant at once
   int tree_slots[5] = {1280, 1024, 512, 256, 256};  // resident tree workgroups per variant (CUs x workgroups per CU by LDS)
   int slot_cap = 1024;  // work slots of the tree kernels: 4 x subtrees + resident workgroups of the smallest variant
   double last_components[4] = {0, 0, 0, 0};
@@ -204,7 +257,6 @@ struct agbnp_hip_context {
   int row_atoms_kind = 0;       // five-launch mode: what d_row_atoms holds for the packing in use -- 0 atom indices (the caller's
                                 // [3n] positions), 1 slots of an OpenMM context's order (posq), -1 stale (the context reordered)
   const int* order_ptr = nullptr;
-  bool adapter_launch = false;
   int lazy_evals = 0;           // evaluations of execute_host since the log was last read and cleared: the FIRST entries of the
                                 // running log (a device-resident entry point that follows counts on from there; nothing is
                                 // synchronised for the hand-over, so it is safe inside a graph capture)
@@ -397,11 +449,11 @@ void apply_parity(agbnp_hip_context* c) {
   P.next_sizes = (five && !c->five_device) ? c->d_sizes.p + (size_t)(1 - p) * nhp : nullptr;
   P.next_estatus = (five && !c->five_device) ? c->d_estatus.p + 16 * (1 - p) : nullptr;
   P.mask_ref = c->d_mask_ref.p;
-  P.mask_move2 = 0.25 * c->mask_skin * c->mask_skin;
+  P.mask_move2 = 0.25 * c->cfg.mask_skin * c->cfg.mask_skin;
   P.row_atoms = five ? c->d_row_atoms.p : nullptr;
   T.row_atoms = P.row_atoms;
   // the masks of that mode reach a skin further than the exact test of the level-2 search does
-  const double reach = sqrt(c->T.rcut2) + (five ? c->mask_skin : 0.0);
+  const double reach = sqrt(c->T.rcut2) + (five ? c->cfg.mask_skin : 0.0);
   P.mask_rcut2 = five ? reach * reach : c->T.rcut2;
 }
 
@@ -444,7 +496,7 @@ void wire_args(agbnp_hip_context* c) {
   P.gb_cut2 = P.fast ? c->cutoff * c->cutoff : 1e300;
   // far strips (pair_kernels.hip, gb_strip): only systems with more than 8192 atoms can have blocks some 4 nm apart in
   // numbers that pay for the test (1dwc, 4152 atoms: none; 2clr, 5983: 3-5 %); AGBNP_HIP_GB_FAR = 0 / 1 forces it (tests)
-  P.gb_far = !P.fast && (getenv("AGBNP_HIP_GB_FAR") ? atoi(getenv("AGBNP_HIP_GB_FAR")) != 0 : c->n > 8192) ? 1 : 0;
+  P.gb_far = !P.fast && (c->cfg.gb_far >= 0 ? c->cfg.gb_far != 0 : c->n > 8192) ? 1 : 0;
   P.pslot = c->d_pslot.p;
   P.nslots = (int)c->d_pslot.count;
   P.nhb = (c->nh + 63) / 64;
@@ -481,10 +533,10 @@ void wire_args(agbnp_hip_context* c) {
   {
     // Row form (reference mode only: the fast mode cuts every stage at the cutoff and the deterministic mode fixes the
     // order of its sums through the tiles' quantized totals)
-    const bool wanted = c->rows_policy != 0;  // (AGBNP_HIP_ROWS=0: the tile kernels everywhere)
+    const bool wanted = c->cfg.rows != 0;  // (AGBNP_HIP_ROWS=0: the tile kernels everywhere)
     // (the single-precision option of the fast mode lives in the GB stage: in the GB rows where they can run, else in the
     // packed-FP32 strips of the tile form)
-    const bool gb_rows_possible = P.fast && c->d_nlg.p != nullptr && getenv("AGBNP_HIP_NO_GB_ROWS") == nullptr;
+    const bool gb_rows_possible = P.fast && c->d_nlg.p != nullptr;
     P.rows_on = c->rows_capable && !c->rows_disabled && c->version == 1 && !P.det && (!P.single || gb_rows_possible) && wanted ? 1 : 0;
     P.gb_rows = P.rows_on && gb_rows_possible ? 1 : 0;
     const double reach = sqrt(P.range2) + c->skin, gb_reach = c->cutoff + c->skin;  // (fast mode: the range-limited stages stop at the cutoff too)
@@ -584,24 +636,17 @@ void wire_args(agbnp_hip_context* c) {
     P.tree_slot_cap = c->slot_cap;
     P.tree_node_cap = tree_variant_node_cap(c->variant);
     P.tree_atom_cap = tree_variant_atom_cap(c->variant);
-    const bool no_pack = getenv("AGBNP_HIP_NO_PACK") != nullptr;  // tuning knob: one subtree per work slot
-    P.pack_enabled = no_pack ? 0 : (getenv("AGBNP_HIP_ITEMS_ALONE") ? 2 : 1);
-    const int round_permille = getenv("AGBNP_HIP_ROUND_PERMILLE") ? atoi(getenv("AGBNP_HIP_ROUND_PERMILLE")) : 1000;
-    P.round_permille = std::max(100, round_permille);
-    P.replan_every = std::max(1, getenv("AGBNP_HIP_REPLAN_EVERY") ? atoi(getenv("AGBNP_HIP_REPLAN_EVERY")) : 16);
-    const int split_big = getenv("AGBNP_HIP_SPLIT_BIG") ? atoi(getenv("AGBNP_HIP_SPLIT_BIG")) : 3;
-    const int split_permille = getenv("AGBNP_HIP_SPLIT_PERMILLE") ? atoi(getenv("AGBNP_HIP_SPLIT_PERMILLE")) : 550;
+    P.pack_enabled = 1;
+    P.round_permille = c->cfg.round_permille;
+    P.replan_every = c->cfg.replan_every;
     // a full device has slot_cap = 2 x subtrees work slots: more parts per subtree than that could plan more work items
     // than forest_start / order / the topology pools hold
-    P.split_big = std::min(std::min(4, c->slot_cap / std::max(c->nh, 1)), std::max(1, split_big));
-    P.split_big = std::max(1, P.split_big);
-    P.split_permille = std::max(50, split_permille);
-    c->split_fit = !(getenv("AGBNP_HIP_SPLIT_FIT") && atoi(getenv("AGBNP_HIP_SPLIT_FIT")) == 0) && c->slot_cap >= 4 * std::max(c->nh, 1);
-    P.split_fit = c->split_fit ? 1 : 0;
+    P.split_big = std::max(1, std::min(3, c->slot_cap / std::max(c->nh, 1)));
+    P.split_permille = 550;
+    P.split_fit = c->cfg.split_fit && c->slot_cap >= 4 * std::max(c->nh, 1) ? 1 : 0;
     // (the tree launches' word: bit 0 the above, bit 1 = forests that outgrow their store are healed inside the launch -- round 6;
-    // AGBNP_HIP_HEAL=0: they void the evaluation as in rounds 2-5, for the tests of the withheld-evaluation protocol and A/B runs)
-    c->heal = !(getenv("AGBNP_HIP_HEAL") && atoi(getenv("AGBNP_HIP_HEAL")) == 0);
-    T.split_fit = P.split_fit | (c->heal ? 2 : 0);
+    // AGBNP_HIP_HEAL=0: they void the evaluation as in rounds 2-5, for the tests of the withheld-evaluation protocol)
+    T.split_fit = P.split_fit | (c->cfg.heal ? 2 : 0);
     T.packing = c->d_forest.p;
     T.slot_cap = c->slot_cap;
   }
@@ -634,15 +679,13 @@ int allocate_rows(agbnp_hip_context* c) {
   constexpr int kMaxTypes = 255;     // a row's type is one byte of its group's slice word
   constexpr size_t kMaxTableBytes = 40 * 1024;  // the power-form table lives in LDS whole (1dwc: 8 x 6 types, 23 KB)
   constexpr int kMaxParticles = 65536;
-  const char* want = getenv("AGBNP_HIP_ROWS");
-  c->rows_policy = want == nullptr ? -1 : (atoi(want) != 0 ? 1 : 0);
-  if (c->version != 1 || nh == 0 || n > kMaxParticles || c->rows_policy == 0) return AGBNP_HIP_OK;
+  if (c->version != 1 || nh == 0 || n > kMaxParticles || c->cfg.rows == 0) return AGBNP_HIP_OK;
   if (c->lut.nscreened > kMaxTypes || c->lut.nscreener > kMaxTypes) return AGBNP_HIP_OK;
   if ((size_t)c->lut.nscreened * c->lut.nscreener * (kI4Nodes - 1) * 2 * sizeof(double2) > kMaxTableBytes) return AGBNP_HIP_OK;
-  if (getenv("AGBNP_HIP_SKIN")) c->skin = std::min(1.0, std::max(0.0, atof(getenv("AGBNP_HIP_SKIN"))));
-  if (getenv("AGBNP_HIP_ROW_MOVE")) c->row_move = std::max(atof(getenv("AGBNP_HIP_ROW_MOVE")), 0.0);
-  if (getenv("AGBNP_HIP_ROW_SLICE")) c->row_slice = atoi(getenv("AGBNP_HIP_ROW_SLICE"));
-  if (getenv("AGBNP_HIP_ROW_FILL")) c->row_fill = std::max(0.01, atof(getenv("AGBNP_HIP_ROW_FILL")));  // (tests: force the walk to widen)
+  c->skin = c->cfg.skin;
+  c->row_move = c->cfg.row_move;
+  c->row_slice = c->cfg.row_slice;
+  c->row_fill = c->cfg.row_fill;
   auto sorted_by_type = [&](int count, auto type_of) {
     std::vector<unsigned> v;
     for (int k = 0; k < count; k++) v.push_back((unsigned)k | ((unsigned)type_of(k) << 24));
@@ -668,8 +711,8 @@ int allocate_rows(agbnp_hip_context* c) {
     c->nlg_stride = c->method != 0 && c->cutoff > 0.0 && c->cutoff < 3.0
                         ? std::max(256, std::min(part_stride(aperm.size(), kGbParts), (int)((most + 255) / 256) * 256)) : 0;
   }
-  if (getenv("AGBNP_HIP_ROW_STRIDE")) {  // (tests: force an overflow)
-    c->nlh_stride = c->nla_stride = std::max(128, atoi(getenv("AGBNP_HIP_ROW_STRIDE")));
+  if (c->cfg.row_stride > 0) {  // (tests: force an overflow)
+    c->nlh_stride = c->nla_stride = c->cfg.row_stride;
     if (c->nlg_stride) c->nlg_stride = c->nlh_stride;
   }
   const size_t born_lists = (size_t)((n + kRowGroup - 1) / kRowGroup) * kBornParts, chain_lists = (size_t)((nh + kRowGroup - 1) / kRowGroup) * kChainParts;
@@ -757,15 +800,9 @@ int allocate_work(agbnp_hip_context* c) {
     constexpr int kStrip = 1 << 24;
     std::vector<int> items;
     items.reserve((size_t)nblk * nblk / 2 + 4);
-    const bool strips = getenv("AGBNP_HIP_NO_GB_STRIPS") == nullptr;
-    if (strips) {
-      for (int p2 = 0; 2 * p2 + 1 < nblk; p2++)
-        for (int J = 2 * p2 + 2; J < nblk; J++) items.push_back((2 * p2) | (J << 12) | kStrip);
-      for (int p2 = 0; 2 * p2 + 1 < nblk; p2++) items.push_back((2 * p2) | ((2 * p2 + 1) << 12));
-    } else {
-      for (int I = 0; I < nblk; I++)
-        for (int J = I + 1; J < nblk; J++) items.push_back(I | (J << 12));
-    }
+    for (int p2 = 0; 2 * p2 + 1 < nblk; p2++)
+      for (int J = 2 * p2 + 2; J < nblk; J++) items.push_back((2 * p2) | (J << 12) | kStrip);
+    for (int p2 = 0; 2 * p2 + 1 < nblk; p2++) items.push_back((2 * p2) | ((2 * p2 + 1) << 12));
     for (int I = 0; I < nblk; I++) items.push_back(I | (I << 12));
     HIP_TRY(c, c->d_gb_items.upload(items));
     c->P.egb_parts = (int)items.size();
@@ -872,13 +909,12 @@ int allocate_work(agbnp_hip_context* c) {
   HIP_TRY(c, hipMemset(c->d_ctx_slot.p, 0, sizeof(int) * std::max(n, 1)));
   HIP_TRY(c, c->d_hslot.alloc(std::max(c->nh, 1)));
   HIP_TRY(c, hipMemset(c->d_hslot.p, 0, sizeof(int) * std::max(c->nh, 1)));
-  c->adapter_launch = getenv("AGBNP_HIP_ADAPTER_LAUNCH") != nullptr && atoi(getenv("AGBNP_HIP_ADAPTER_LAUNCH")) != 0;
   HIP_TRY(c, c->d_force_tmp.alloc(3 * (size_t)n + 1));  // (+ the energy of agbnp_hip_execute_host)
   HIP_TRY(c, c->d_energy_tmp.alloc(1));
   HIP_TRY(c, hipMemset(c->d_force_tmp.p, 0, sizeof(double) * (3 * (size_t)n + 1)));
   HIP_TRY(c, hipMemset(c->d_energy_tmp.p, 0, sizeof(double)));
   c->h_force_tmp.resize(3 * (size_t)n + 1);
-  const bool pinned = getenv("AGBNP_HIP_NO_PINNED_STAGING") == nullptr;  // (tests: the pageable fall-back of the host-facing paths)
+  const bool pinned = c->cfg.pinned_staging;  // (tests: the pageable fall-back of the host-facing paths)
   if (!pinned || hipHostMalloc(reinterpret_cast<void**>(&c->h_report), sizeof(agbnp_hip_context::HostReport), hipHostMallocDefault) != hipSuccess) c->h_report = nullptr;
   if (!pinned || hipHostMalloc(reinterpret_cast<void**>(&c->h_xfer), sizeof(double) * (6 * (size_t)n + 8), hipHostMallocDefault) != hipSuccess) c->h_xfer = nullptr;
   (void)hipGetLastError();  // (without pinned memory the host-facing paths fall back to pageable transfers)
@@ -969,13 +1005,12 @@ int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* 
     // (Round 4: the replay of queued forests is pipelined -- the next forest's data are asked for in front of the flush -- and
     // the forces were tried in the launch again: lattice k_tree_pseudo 51 -> 109 us once more.  On gfx9 loads, stores and
     // atomics share one in-order counter, and a wait that crosses the loop's back edge is a wait for everything, the
-    // flush's atomics included.  AGBNP_HIP_FUSE_QUEUED=1 keeps the experiment reachable.)
-    static const bool fuse_queued = getenv("AGBNP_HIP_FUSE_QUEUED") && atoi(getenv("AGBNP_HIP_FUSE_QUEUED")) != 0;
+    // flush's atomics included.)
     // (Round 5: a system with more subtrees than that whose forests nevertheless fit ONE round -- 2clr under the rounds rule of
     // the packing: 3084 subtrees in 1280 forests -- is told by the forest count of the last evaluation the host has seen;
     // a stale hint costs time, never correctness.)
     const bool one_round = c->forests_hint > 0 && c->forests_hint <= c->tree_slots[c->variant];
-    const bool fused = c->fused_outputs && c->nh > 0 && (c->nh <= 2 * c->tree_slots[c->variant] || one_round || (fuse_queued && c->variant <= 1));
+    const bool fused = c->nh > 0 && (c->nh <= 2 * c->tree_slots[c->variant] || one_round);
     O.enabled = fused ? 1 : 0;
     O.n = c->n;
     O.a2h = c->d_a2h.p;
@@ -1207,10 +1242,9 @@ int agbnp_hip_create(agbnp_hip_context** out, int n, const double* radius, const
   c->method = nonbonded_method;
   c->cutoff = cutoff;
   c->device = device;
-  c->fused_outputs = getenv("AGBNP_HIP_OUTPUT_LAUNCH") == nullptr;
-  c->five = (version == 0 || version == 1) && !(getenv("AGBNP_HIP_FIVE_LAUNCHES") && atoi(getenv("AGBNP_HIP_FIVE_LAUNCHES")) == 0);  // (default since round 5, version 0 since round 6; 0: with the k_prep launch)
+  c->cfg = read_settings();
+  c->five = (version == 0 || version == 1) && c->cfg.five_launches;  // (default since round 5, version 0 since round 6)
   c->five_active = c->five;
-  if (getenv("AGBNP_HIP_MASK_SKIN")) c->mask_skin = std::min(0.5, std::max(0.0, atof(getenv("AGBNP_HIP_MASK_SKIN"))));
   c->r_vdw.assign(radius, radius + n);
   c->gamma.resize(n);
   c->alpha.assign(vdw_alpha, vdw_alpha + n);
@@ -1333,7 +1367,7 @@ int agbnp_hip_execute_openmm(agbnp_hip_context* c, const void* d_posq, int posq_
   // (OpenmmSource): they are built when an atomIndex array is first seen (or seen again after the device has found it
   // changed), one small launch that a steady run never repeats.  AGBNP_HIP_ADAPTER_LAUNCH=1: an adapter launch per
   // evaluation instead (posq -> xyz in particle order, and the particle -> slot map for the output side).
-  const bool fused = !c->adapter_launch;
+  const bool fused = !c->cfg.adapter_launch;
   if (fused) {
     if (!c->order_valid || c->order_ptr != d_atom_index) {
       HIP_TRY(c, launch_order_maps(c->n, d_atom_index, c->d_a2h.p, c->d_ctx_slot.p, c->d_hslot.p, st));

@@ -102,7 +102,7 @@ struct PairArgs {
   int ncus;                // CUs of the device
   int tree_node_cap, tree_atom_cap, pack_enabled;  // capacity of the current tree variant; packing switch
   int tree_slots;          // tree workgroups resident on the device at once (a 'round')
-  int split_big, split_permille;  // tuning knobs: parts and node threshold (share of the capacity) for sharing on a full device
+  int split_big, split_permille;  // sharing on a full device: parts per subtree (at most 3), node threshold (550 per mille of the capacity)
   int split_fit;           // 1: subtrees whose items would not fit the store are shared among up to four items (AGBNP_HIP_SPLIT_FIT=0: off)
   int round_permille;      // share of the resident workgroups that the packing fills (tuning knob, default 1000: every resident slot)
   int tree_slot_cap;       // work slots the tree kernels are launched with (>= subtrees; bounds the sharing of subtrees)
@@ -212,10 +212,7 @@ constexpr int kRowSlice = 256, kRowWaves = 8;  // entries of the shortest slice 
 // The GB rows keep no table in LDS, so their workgroups can be small: the launch (fast mode, 1dwc: 2840 one-wave items) is
 // bound by the vector-memory pipe of the fullest CU (three gathers per step), and four-wave workgroups spread the waves more
 // evenly over the CUs than eight-wave ones (8 or 12 waves on a CU instead of 8 or 16).
-#ifndef AGBNP_GB_ROW_WAVES
-#define AGBNP_GB_ROW_WAVES 4
-#endif
-constexpr int kGbRowWaves = AGBNP_GB_ROW_WAVES;
+constexpr int kGbRowWaves = 4;
 constexpr int row_waves(int kind) { return kind == 2 ? kGbRowWaves : kRowWaves; }  // (kind: RowKind)
 constexpr int kRowSliceMax = 512;
 constexpr int kChainParts = 4;  // waves (list parts) per group of chain-rule rows

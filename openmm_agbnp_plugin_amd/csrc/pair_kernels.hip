@@ -186,12 +186,6 @@ __device__ void neighbor_tile(const PairArgs& P, int tile, bool write_ref = fals
 }
 
 __global__ __launch_bounds__(256) void k_prep(PairArgs P, int prep_blocks) {
-#ifdef AGBNP_TIMING_PREP  // timing experiment only (results wrong): 1 = an empty launch of the same grid, 2 = no neighbour-mask
-                          // tiles, 3 = the neighbour-mask tiles alone; the raw event interval of k_prep says what each part costs
-  if (AGBNP_TIMING_PREP == 1) return;
-  if (AGBNP_TIMING_PREP == 2 && (int)blockIdx.x >= prep_blocks) return;
-  if (AGBNP_TIMING_PREP == 3 && (int)blockIdx.x < prep_blocks) return;
-#endif
   if ((int)blockIdx.x >= prep_blocks) return neighbor_tile(P, blockIdx.x - prep_blocks);
   prep_atoms(P, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.x == 0, false);
 }
@@ -225,10 +219,6 @@ __device__ __forceinline__ double rot1(double v) {  // lane l <- lane l+1 (mod 6
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-
-#ifndef AGBNP_PACK_ROUNDS_RULE
-#define AGBNP_PACK_ROUNDS_RULE 1  // (0: diagnostic build without the rounds rule of packing_role)
-#endif
 constexpr size_t kRoleScratchBytes = 4352;  // LDS the two roles borrow from their host kernel's dynamic area
 // ---- two single-workgroup roles, off the critical path:
 //   energy:      fixed-order sum of every energy partial, ADDED to the caller's scalar; needs the GB stage's partials:
@@ -635,7 +625,7 @@ __device__ void packing_role(const PairArgs& P, char* scratch, int scratch_bytes
   unsigned short* ws = reinterpret_cast<unsigned short*>(lds_time + region);  // [nitems] weight by sorted position
   unsigned short* where = ws + ((nitems + 1) & ~1);                            // [nitems] forest << 3 | place by sorted position
   const bool try_rounds = forests && nc > 0 && rounds_weight < rounds_classes && F <= 8191 && P.pack_items != nullptr &&
-                          region + (nitems + 1) / 2 * 2 <= lds_forests && kRounds && AGBNP_PACK_ROUNDS_RULE;
+                          region + (nitems + 1) / 2 * 2 <= lds_forests && kRounds;
   if (!try_rounds) {
 #pragma unroll 1
     for (int f = t; f <= nf; f += 256) P.forest_start[f] = forest_first(f);
@@ -1024,9 +1014,6 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
   if (kFar) {
     const double bj = __hiloint2double(s_bmax[0], 0), bi = __hiloint2double(max(s_bmax[1], s_bmax[2]), 0);
     far = __builtin_amdgcn_readfirstlane(far_gap2 > kGbFarFactor * bj * bi ? 1 : 0) != 0;  // (the same for every lane of the workgroup)
-#ifdef AGBNP_TIMING_ALL_FAR  // timing experiment only (results wrong): what the launch costs if EVERY strip took the short walk
-    far = true;
-#endif
   }
   if (kFar && far) {
 #pragma unroll 4

@@ -22,10 +22,6 @@
 namespace agbnp {
 
 __device__ __forceinline__ void hbm_add(double* p, double v) {  // global_atomic_add_f64
-#ifdef AGBNP_TIMING_NO_ATOMICS  // timing experiment only: results are wrong
-  if (v == 1.2345e300) *p = v;
-  return;
-#endif
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

@@ -102,12 +102,9 @@ __device__ __forceinline__ int next_forest(int tid, int* lds_word, int ticket, i
   return slot;
 }
 
-// Waves per SIMD the compiler is asked to leave room for = workgroups per CU that the variant's LDS footprint allows
-// (one wave of a workgroup per SIMD): 5 for the 432-node store (<= 96 VGPRs), 4 for 512 nodes (<= 128), fewer beyond.
-constexpr int tree_waves_per_simd(int ncap, int bs) {
-  if (bs == 192) return ncap <= 512 ? 4 : 2;  // (three-wave workgroups: five per CU are 15 waves, at most four on a SIMD)
-  return bs >= 256 ? (ncap <= 432 ? 5 : (ncap <= 512 ? 4 : 2)) : (ncap <= 192 ? 3 : 2);  // (one-wave workgroups: ~10 per CU for the small store)
-}
+// Waves per SIMD the compiler is asked to leave room for, from the three-wave workgroups per CU that the variant's LDS
+// footprint allows: five for the 432-node store are 15 waves, at most four on a SIMD (<= 128 VGPRs); fewer beyond 512 nodes.
+constexpr int tree_waves_per_simd(int ncap) { return ncap <= 512 ? 4 : 2; }
 
 #ifdef AGBNP_STAMPS  // (diagnostic build: the stamps take 136 bytes of the store's last LDS granule)
 constexpr int kPendCap = 4;
@@ -385,7 +382,7 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
 }
 
 template <int NCAP, int ACAP, int BS, bool GLOBAL, bool SV1>
-__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP, BS)) void k_tree_cavity(TreeArgs A) {
+__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity(TreeArgs A) {
   cavity_forests<NCAP, ACAP, BS, GLOBAL, SV1, false>(A, (int)gridDim.x);
 }
 
@@ -399,7 +396,7 @@ static_assert(kPrepHvGx == kHvGx && kPrepHvGx + 3 == kHvSvVdw && kPrepHvSvLarge 
 // float4 + correction) at the context's slots; the trailing workgroups read it through the same maps (prep_role.h) and check
 // every particle's entry against atomIndex (kStatOrderStale: the context has reordered its atoms, the evaluation is void)
 template <int NCAP, int ACAP, int BS, bool DEVPAR = false, bool POSQ = false>
-__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP, BS)) void k_tree_cavity_five(TreeArgs A, PairArgs P, int tree_blocks) {
+__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity_five(TreeArgs A, PairArgs P, int tree_blocks) {
   if ((int)blockIdx.x >= tree_blocks) {
     const int b = (int)blockIdx.x - tree_blocks;
     if (DEVPAR) rebase_for_parity(P, 0);
@@ -466,7 +463,7 @@ __device__ __forceinline__ void outputs_role(const TreeArgs& A, int blk, int bs)
 // across the volume pass and spills one at the 128-register bound.  Launches whose forests fit one round (TreeOutputs::enabled:
 // the engine's own rule for fusing the forces) take the lean one; either handles any number of forests.
 template <int NCAP, int ACAP, int BS, bool GLOBAL, bool PIPE = true, bool DEVPAR = false>
-__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP, BS)) void k_tree_pseudo(TreeArgs A) {
+__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(TreeArgs A) {
   if (DEVPAR) rebase_tree_for_parity(A, 1);  // (five-launch mode, device-side parity: the set of this evaluation; behind the GB launch, see pair_kernels.h)
   extern __shared__ __align__(16) char smem[];
   TreeStore<NCAP, ACAP> S;
@@ -777,19 +774,11 @@ extern "C" void agbnp_debug_stamps_max(unsigned long long* out, int reset) {
 // 3 = (2048, 256), one; 4 = (32768, 256) in a per-workgroup HBM slab
 constexpr int kGlobalNodeCap = 32768;
 constexpr int kGlobalAtomCap = 256;  // one byte per atom in the path words
-constexpr int kBS = AGBNP_TREE_BLOCK;  // lanes per subtree (compile-time knob, default kTreeBlock)
+constexpr int kBS = 192;  // lanes per subtree
 static_assert(kBS <= kTreeBlock && kBS % 64 == 0, "tree block size");
 // LDS is handed out in granules of 1280 bytes on gfx950: five workgroups per CU need <= 25 granules each
 static_assert((TreeStore<432, 64>::kBytes + 16 + sizeof(int) * kPendCap + 1279) / 1280 * 5 <= 128, "five build workgroups per CU");
 static_assert((TreeStore<512, 64>::kBytes + 16 + sizeof(int) * kPendCap + 1279) / 1280 * 4 <= 128, "four build workgroups per CU");
-// Experimental build (-DAGBNP_TREE_BLOCK=64): one-wave workgroups, one subtree (or part of one) each, in a small store
-#if AGBNP_TREE_BLOCK == 64
-#define AGBNP_SMALL_STORE 192, 48
-constexpr int kSmallNodes = 192, kSmallAtoms = 48;
-#else
-#define AGBNP_SMALL_STORE 432, 64
-constexpr int kSmallNodes = 432, kSmallAtoms = 64;
-#endif
 size_t tree_variant_lds_bytes(int variant);
 int tree_variant_node_cap(int variant);
 // workgroups of the build kernel that a CU holds: LDS granules of 1280 B (128 per CU), 32 waves, the register budget
@@ -798,13 +787,13 @@ int tree_variant_wgs_per_cu(int variant) {
   if (tree_variant_lds_bytes(variant) == 0) return 1;
   const int by_lds = (int)(128 / ((bytes + 1279) / 1280));
   const int waves = kBS / 64;
-  const int by_regs = 4 * tree_waves_per_simd(tree_variant_node_cap(variant), kBS) / waves;
+  const int by_regs = 4 * tree_waves_per_simd(tree_variant_node_cap(variant)) / waves;
   return std::max(1, std::min(std::min(by_lds, by_regs), 32 / waves));
 }
 
 size_t tree_variant_lds_bytes(int variant) {
   switch (variant) {
-    case 0: return TreeStore<AGBNP_SMALL_STORE>::kBytes;
+    case 0: return TreeStore<432, 64>::kBytes;
     case 1: return TreeStore<512, 64>::kBytes;
     case 2: return TreeStore<1024, 128>::kBytes;
     case 3: return TreeStore<2048, 256>::kBytes;
@@ -815,12 +804,12 @@ size_t tree_variant_scratch_bytes(int variant) {
   return variant == 4 ? ((TreeStore<kGlobalNodeCap, kGlobalAtomCap>::kBytes + 255) / 256) * 256 : 0;
 }
 int tree_variant_node_cap(int variant) {
-  static const int caps[5] = {kSmallNodes, 512, 1024, 2048, kGlobalNodeCap};
+  static const int caps[5] = {432, 512, 1024, 2048, kGlobalNodeCap};
   return caps[variant];
 }
 
 int tree_variant_atom_cap(int variant) {
-  static const int caps[5] = {kSmallAtoms, 64, 128, 256, kGlobalAtomCap};
+  static const int caps[5] = {64, 64, 128, 256, kGlobalAtomCap};
   return caps[variant];
 }
 
@@ -837,16 +826,12 @@ static hipError_t launch_tree(K kernel, int grid, size_t lds, const TreeArgs& A,
 // slots: workgroups to launch = min(work slots that may be planned, workgroups the device keeps resident)
 hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st) {
   if (A.nh <= 0) return hipSuccess;
-#ifdef AGBNP_STAMPS  // diagnostic build only: time the largest subtrees alone (results are incomplete)
-  if (const char* env = getenv("AGBNP_DIAG_TREE_GRID"))
-    return launch_tree(k_tree_cavity<AGBNP_SMALL_STORE, kBS, false, false>, std::min(A.nh, atoi(env)), TreeStore<AGBNP_SMALL_STORE>::kBytes, A, st);
-#endif
   const bool sv1 = A.want_sv_large != 0;  // (the diagnostic self volumes of pass 1: a kernel of their own)
 #define AGBNP_CAVITY(...) (sv1 ? launch_tree(k_tree_cavity<__VA_ARGS__, true>, grid, lds, A, st) : launch_tree(k_tree_cavity<__VA_ARGS__, false>, grid, lds, A, st))
   int grid = slots;
   size_t lds = 0;
   switch (variant) {
-    case 0: lds = TreeStore<AGBNP_SMALL_STORE>::kBytes; return AGBNP_CAVITY(AGBNP_SMALL_STORE, kBS, false);
+    case 0: lds = TreeStore<432, 64>::kBytes; return AGBNP_CAVITY(432, 64, kBS, false);
     case 1: lds = TreeStore<512, 64>::kBytes; return AGBNP_CAVITY(512, 64, kBS, false);
     case 2: lds = TreeStore<1024, 128>::kBytes; return AGBNP_CAVITY(1024, 128, kBS, false);
     case 3: lds = TreeStore<2048, 256>::kBytes; return AGBNP_CAVITY(2048, 256, kBS, false);
@@ -881,7 +866,7 @@ hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, co
     return launch_five(k_tree_cavity_five<NC, AC, kBS, false, false>, grid, lds, A, P, slots, st);                     \
   } while (0)
   switch (variant) {
-    case 0: AGBNP_FIVE(kSmallNodes, kSmallAtoms);
+    case 0: AGBNP_FIVE(432, 64);
     case 1: AGBNP_FIVE(512, 64);
     case 2: AGBNP_FIVE(1024, 128);
     default: AGBNP_FIVE(2048, 256);
@@ -897,10 +882,10 @@ hipError_t launch_tree_pseudo(int variant, int global_grid, int slots, const Tre
   const int grid = A.out.forest_blocks + (A.out.enabled ? (A.out.n + kBS - 1) / kBS : 0);
   switch (variant) {
     case 0:
-      if (A.five == 2 && A.out.enabled) return launch_tree(k_tree_pseudo<AGBNP_SMALL_STORE, kBS, false, false, true>, grid, TreeStore<AGBNP_SMALL_STORE>::kReplayBytes, A, st);
-      if (A.five == 2) return launch_tree(k_tree_pseudo<AGBNP_SMALL_STORE, kBS, false, true, true>, grid, TreeStore<AGBNP_SMALL_STORE>::kReplayBytes, A, st);
-      if (A.out.enabled) return launch_tree(k_tree_pseudo<AGBNP_SMALL_STORE, kBS, false, false>, grid, TreeStore<AGBNP_SMALL_STORE>::kReplayBytes, A, st);
-      return launch_tree(k_tree_pseudo<AGBNP_SMALL_STORE, kBS, false>, grid, TreeStore<AGBNP_SMALL_STORE>::kReplayBytes, A, st);
+      if (A.five == 2 && A.out.enabled) return launch_tree(k_tree_pseudo<432, 64, kBS, false, false, true>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
+      if (A.five == 2) return launch_tree(k_tree_pseudo<432, 64, kBS, false, true, true>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
+      if (A.out.enabled) return launch_tree(k_tree_pseudo<432, 64, kBS, false, false>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
+      return launch_tree(k_tree_pseudo<432, 64, kBS, false>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
     case 1:
       if (A.five == 2 && A.out.enabled) return launch_tree(k_tree_pseudo<512, 64, kBS, false, false, true>, grid, TreeStore<512, 64>::kReplayBytes, A, st);
       if (A.five == 2) return launch_tree(k_tree_pseudo<512, 64, kBS, false, true, true>, grid, TreeStore<512, 64>::kReplayBytes, A, st);
