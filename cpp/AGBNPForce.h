@@ -111,6 +111,16 @@ class HipCalcAGBNPForceKernel {
     return energy;
   }
 
+  // Energy-only evaluation (what OpenMM asks for with includeForces = false): the energy execute() would return at these
+  // positions, without the force passes where the context allows it; no forces are written (include/agbnp_hip.h).
+  double energy(const std::vector<double>& positions) {
+    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+    if ((int)positions.size() != 3 * numParticles) throw OpenMMException("energy(): positions must hold 3N values");
+    double e = 0.0;
+    if (agbnp_hip_energy_host(ctx, positions.data(), &e) != AGBNP_HIP_OK) throw OpenMMException(agbnp_hip_last_error(ctx));
+    return e;
+  }
+
   void copyParametersToContext(const AGBNPForce& force) {
     if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
     std::vector<double> r, g, a, q;

@@ -125,6 +125,32 @@ int agbnp_hip_execute_openmm(agbnp_hip_context* ctx, const void* d_posq, int pos
                              const int* d_atom_index, int padded_num_atoms, long long* d_force_buffer, void* d_energy_buffer,
                              int energy_is_double, int energy_slot, void* stream);
 
+/* Energy-only evaluations: what OpenMM asks of CalcAGBNPForceKernel::execute(context, includeForces = false,
+ * includeEnergy = true) -- getState(getEnergy=True) without forces, reporters, Monte-Carlo tests, line searches, the energy
+ * matrices of replica exchange.  The three mirror the three execute entry points above, without force outputs:
+ *   - NOTHING is written to any force buffer of the caller;
+ *   - the energy is the one the matching execute call would produce at the same positions (agbnp_hip_energy_host returns it,
+ *     the other two ADD it to *d_energy / to element energy_slot of d_energy_buffer, which must not be NULL);
+ *   - such an evaluation is counted in the same overflow log, withheld when incomplete (a subtree that needs the next capacity
+ *     variant, a jump of more than 0.04 nm, a reordered OpenMM context), and reported by agbnp_hip_finish(),
+ *     agbnp_hip_withheld_evaluations(), agbnp_hip_poll() and agbnp_hip_wait_verdict() under its enqueue index;
+ *     agbnp_hip_energy_host() repeats withheld ones itself;
+ *   - afterwards the context is in exactly the state a full evaluation leaves (forest packing, neighbour masks and rows, the
+ *     healing counters), so full and energy-only evaluations may be interleaved in any order.
+ * Five-launch mode with the Reference semantics and the FP64 row form (the default): FOUR launches for version 1 (the cavity
+ * launch; the Born rows; the GB stage's energy-only instantiation, which drops the direct force and the Y sums; one small
+ * launch with the energy and dealing roles -- no chain-rule and no pseudo-volume launch), TWO for version 0 (the cavity launch;
+ * the output launch's role workgroups and mask tiles).  Every other configuration (deterministic, fast and fast+single modes,
+ * AGBNP_HIP_ROWS=0, AGBNP_HIP_FIVE_LAUNCHES=0, capacity variant 4, diagnostics, a context that has been stream-captured)
+ * runs the full evaluation with its forces sent to a buffer of the context's own: correct, not faster.  Scalar 18 says which.
+ * Inside a stream capture these return AGBNP_HIP_ERR_INVALID_ARGUMENT, launch nothing and leave the capture usable:
+ * energy-only evaluations are not captured into graphs. */
+int agbnp_hip_energy_host(agbnp_hip_context* ctx, const double* positions, double* energy); /* energy RETURNED; synchronous */
+int agbnp_hip_energy_device(agbnp_hip_context* ctx, const double* d_positions, double* d_energy, void* stream); /* ADDED; async */
+int agbnp_hip_energy_openmm(agbnp_hip_context* ctx, const void* d_posq, int posq_is_double, const void* d_posq_correction,
+                            const int* d_atom_index, int padded_num_atoms, void* d_energy_buffer, int energy_is_double,
+                            int energy_slot, void* stream); /* ADDED to d_energy_buffer[energy_slot]; async */
+
 /* Tells the engine that the contents of the d_atom_index array it last saw have changed (OpenMM has reordered its atoms):
  * the next agbnp_hip_execute_openmm() rebuilds its maps first, and no evaluation is lost to the check.  Optional -- without
  * it the first evaluation after a reorder is withheld and repeated, see above. */
@@ -220,7 +246,9 @@ int agbnp_hip_get_mode(const agbnp_hip_context* ctx);
  *             32 / 64 a forest of several work items outgrew its nodes / its local atoms (the two kinds of 4);
  *             bits 8.. the part count of a lone work item that asked for its subtree to be shared further
  *          16 kernel launches of an evaluation as the context runs now: version 1: 5 (five-launch mode) or 6; version 0: 2 or 3
- *          17 forests that outgrew their store and were healed inside the tree launch (built again in smaller sets: the
+ *          18 kernel launches of an energy-only evaluation as the context runs now: 4 (version 1) or 2 (version 0), 0 where it
+             runs as a full evaluation with its forces sent to a buffer of the context's own
+          17 forests that outgrew their store and were healed inside the tree launch (built again in smaller sets: the
  *             evaluation is complete, nothing is withheld for them) over the evaluations the last agbnp_hip_finish() covered
  *          14 forest packings planned so far (a packing in use is planned anew every AGBNP_HIP_REPLAN_EVERY-th evaluation,
  *             default 16, or when the trees have drifted from the shapes it was planned for)

@@ -230,6 +230,39 @@ class HipCalcAGBNPForceKernel:
         if rc != _lib.OK:
             raise OpenMMException(_lib.last_error(self._h))
 
+    def energy(self, positions):
+        """Energy-only evaluation (what OpenMM asks for with includeForces=false): the energy execute() would return at
+        these positions, computed without the force passes where the context allows it (include/agbnp_hip.h).  No forces
+        are written anywhere; withheld evaluations are repeated inside, like execute()."""
+        self._need()
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
+        if pos.size != 3 * self.numParticles:
+            raise OpenMMException("energy(): wrong number of positions")
+        e = C.c_double(0.0)
+        rc = _lib.load().agbnp_hip_energy_host(self._h, _dp(pos), C.byref(e))
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(self._h))
+        return e.value
+
+    def energy_device(self, d_positions, d_energy, stream=None):
+        """Energy-only form of execute_device(): the energy is ADDED to *d_energy on the device, nothing else is written.
+        Asynchronous, counted in the same log as full evaluations (finish(), withheld(), poll(), wait_verdict()).  Refused
+        (OpenMMException) inside a stream capture."""
+        self._need()
+        rc = _lib.load().agbnp_hip_energy_device(self._h, C.c_void_p(d_positions), C.c_void_p(d_energy), C.c_void_p(stream or 0))
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(self._h))
+
+    def energy_openmm(self, d_posq, posq_is_double, d_posq_correction, d_atom_index, padded_num_atoms, d_energy_buffer,
+                      energy_is_double, energy_slot=0, stream=None):
+        """Energy-only form of execute_openmm(): no force buffer; the energy is ADDED to d_energy_buffer[energy_slot]."""
+        self._need()
+        rc = _lib.load().agbnp_hip_energy_openmm(self._h, C.c_void_p(d_posq), int(bool(posq_is_double)), C.c_void_p(d_posq_correction or 0),
+                                                 C.c_void_p(d_atom_index or 0), int(padded_num_atoms), C.c_void_p(d_energy_buffer),
+                                                 int(bool(energy_is_double)), int(energy_slot), C.c_void_p(stream or 0))
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(self._h))
+
     def atom_order_changed(self):
         """The context has reordered its atoms (same atomIndex array, new contents): the next execute_openmm() rebuilds the
         engine's maps first instead of losing one evaluation to the check on the device."""
@@ -293,7 +326,7 @@ class HipCalcAGBNPForceKernel:
             raise OpenMMException(_lib.last_error(self._h))
 
     # ---- diagnostics (test support) -------------------------------------------------------------
-    SCALARS = dict(e_vol1=0, e_vol2=1, e_atom=2, e_gb_pair=3, max_subtree_nodes=4, total_nodes=5, variant=6, max_local_atoms=7, forests=8, rows_on=9, row_builds=10, pack_level=11, pack_age=12, row_slice=13, pack_plans=14, overflow_kinds=15, launches=16, healed_forests=17)
+    SCALARS = dict(e_vol1=0, e_vol2=1, e_atom=2, e_gb_pair=3, max_subtree_nodes=4, total_nodes=5, variant=6, max_local_atoms=7, forests=8, rows_on=9, row_builds=10, pack_level=11, pack_age=12, row_slice=13, pack_plans=14, overflow_kinds=15, launches=16, healed_forests=17, energy_only_launches=18)
     VECTORS = dict(selfvol_vdw=0, born=1, scale=2, selfvol_large=3, subtree_nodes=4, subtree_atoms=5)
 
     def scalar(self, name):
@@ -399,6 +432,15 @@ class AGBNPContext:
             return 0.0, forces
         e = self._kernel.execute(self._positions, forces, True, True)
         return e, forces
+
+    def getEnergy(self, groups=-1):
+        """The potential energy alone (getState(getEnergy=True) without forces): an energy-only evaluation.  Honours the
+        force-group mask like getState()."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        if (groups & (1 << self._force.getForceGroup())) == 0:
+            return 0.0
+        return self._kernel.energy(self._positions)
 
     def _update_parameters(self, force):
         self._kernel.copyParametersToContext(force)

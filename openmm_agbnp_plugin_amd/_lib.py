@@ -17,6 +17,7 @@ SYMBOLS = [
     "agbnp_hip_get_tables", "agbnp_hip_host_tables", "agbnp_hip_num_particles", "agbnp_hip_version",
     "agbnp_hip_last_error", "agbnp_hip_destroy", "agbnp_hip_device_count", "agbnp_hip_build_id",
     "agbnp_hip_set_mode", "agbnp_hip_get_mode", "agbnp_hip_set_diagnostics", "agbnp_hip_set_profiling", "agbnp_hip_num_kernels", "agbnp_hip_kernel_name", "agbnp_hip_get_kernel_times",
+    "agbnp_hip_energy_host", "agbnp_hip_energy_device", "agbnp_hip_energy_openmm",
 ]
 
 _lib = None
@@ -57,6 +58,9 @@ def load():
     lib.agbnp_hip_execute_host.argtypes = [vp, dp, dp, dp]
     lib.agbnp_hip_execute_device.argtypes = [vp, vp, vp, vp, vp]
     lib.agbnp_hip_execute_openmm.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]
+    lib.agbnp_hip_energy_host.argtypes = [vp, dp, dp]
+    lib.agbnp_hip_energy_device.argtypes = [vp, vp, vp, vp]
+    lib.agbnp_hip_energy_openmm.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
     lib.agbnp_hip_atom_order_changed.argtypes = [vp]
     lib.agbnp_hip_finish.argtypes = [vp, vp, ip]
     lib.agbnp_hip_poll.argtypes = [vp, ip, ip]

@@ -101,6 +101,7 @@ enum KernelId {
   kKPrep = 0, kKTreeCavity, kKBornTiles, kKGbTiles, kKDbornTiles, kKTreePseudo, kKOutputs,
   kKBornRows, kKDbornRows,  // row form of the two range-limited stages (take the place of the two tile kernels)
   kKGbRows,                 // row form of the GB stage (fast mode only)
+  kKEnergyRoles,            // energy-only evaluations: energy, dealing and the rows' close behind the GB stage (k_energy_roles)
   kKernelCount
 };
 

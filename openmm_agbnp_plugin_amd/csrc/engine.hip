@@ -213,6 +213,11 @@ struct agbnp_hip_context {
   // host-API staging
   DevBuf<double> d_pos_in, d_force_tmp, d_energy_tmp;
   std::vector<double> h_force_tmp;
+  // energy-only evaluations (agbnp_hip_energy_*): where the forces of one that runs as a full evaluation go (the fallback,
+  // energy_only_fast) -- [3n] FP64 for agbnp_hip_energy_device, fixed-point planes [3 padded] for agbnp_hip_energy_openmm
+  // (energy_role routes the energy to an OpenMM accumulator only beside a fixed-point force target); never read
+  DevBuf<double> d_eo_force;
+  DevBuf<unsigned long long> d_eo_fixed;
 
   PairArgs P{};
   TreeArgs T{};
@@ -911,6 +916,8 @@ int allocate_work(agbnp_hip_context* c) {
   HIP_TRY(c, hipMemset(c->d_hslot.p, 0, sizeof(int) * std::max(c->nh, 1)));
   HIP_TRY(c, c->d_force_tmp.alloc(3 * (size_t)n + 1));  // (+ the energy of agbnp_hip_execute_host)
   HIP_TRY(c, c->d_energy_tmp.alloc(1));
+  HIP_TRY(c, c->d_eo_force.alloc(3 * (size_t)n));
+  HIP_TRY(c, hipMemset(c->d_eo_force.p, 0, sizeof(double) * 3 * (size_t)n));
   HIP_TRY(c, hipMemset(c->d_force_tmp.p, 0, sizeof(double) * (3 * (size_t)n + 1)));
   HIP_TRY(c, hipMemset(c->d_energy_tmp.p, 0, sizeof(double)));
   c->h_force_tmp.resize(3 * (size_t)n + 1);
@@ -921,7 +928,18 @@ int allocate_work(agbnp_hip_context* c) {
   return AGBNP_HIP_OK;
 }
 
-int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, hipStream_t st) {
+// Energy-only evaluations (agbnp_hip_energy_*) run on launches of their own where the context runs the five-launch mode with the
+// host-named set, the Reference semantics and -- version 1 -- the FP64 row form of the pair stages: the cavity launch, then
+// launch_energy_only_stages (no chain-rule launch, no pseudo-volume launch).  Everywhere else (deterministic, fast, fast+single
+// modes, AGBNP_HIP_ROWS=0, AGBNP_HIP_FIVE_LAUNCHES=0, capacity variant 4, diagnostics, a context captured into a graph before)
+// they run as full evaluations whose forces go to a buffer of the context's own.
+bool energy_only_fast(const agbnp_hip_context* c) {
+  if (!c->five_active || c->five_device || c->mode != 0 || c->variant > 3 || c->diagnostics || c->nh <= 0) return false;
+  if (c->version == 0) return true;
+  return c->P.rows_on && !c->P.gb_rows && !c->P.single && !c->P.fast && !c->P.det;
+}
+
+int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, hipStream_t st, bool energy_only = false) {
   int rc = ensure_scratch(c);
   if (rc != AGBNP_HIP_OK) return rc;
   c->enqueued++;
@@ -987,6 +1005,10 @@ int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* 
     }
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
     HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st));
+    if (energy_only && energy_only_fast(c)) {
+      HIP_TRY(c, launch_energy_only_stages(c->P, c->version, d_energy, c->d_components.p, st, tl));
+      return AGBNP_HIP_OK;
+    }
   } else {
     HIP_TRY(c, launch_prep(c->P, st, tl));
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
@@ -1351,17 +1373,13 @@ int agbnp_hip_execute_device(agbnp_hip_context* c, const double* d_pos, double* 
   return enqueue(c, d_pos, d_force, d_energy, st);
 }
 
-int agbnp_hip_execute_openmm(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,
-                             const int* d_atom_index, int padded_num_atoms, long long* d_force_buffer, void* d_energy_buffer,
-                             int energy_is_double, int energy_slot, void* stream) {
-  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!d_posq || !d_force_buffer) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: null pointer");
-  if (padded_num_atoms < c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: padded atom count below the particle count");
-  if (posq_is_double && d_posq_correction)
-    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: a position correction only exists beside float positions");
-  if (energy_slot < 0) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: negative energy slot");
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+}  // extern "C"
+
+namespace {
+// agbnp_hip_execute_openmm and agbnp_hip_energy_openmm (energy_only: d_force_buffer is the context's own), arguments checked
+int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,
+                                const int* d_atom_index, int padded_num_atoms, long long* d_force_buffer, void* d_energy_buffer,
+                                int energy_is_double, int energy_slot, hipStream_t st, void* stream, bool energy_only) {
   note_stream(c, stream);
   // Input side.  Normally k_prep reads the context's posq itself, through the engine's maps of the context's atom order
   // (OpenmmSource): they are built when an atomIndex array is first seen (or seen again after the device has found it
@@ -1391,10 +1409,28 @@ int agbnp_hip_execute_openmm(agbnp_hip_context* c, const void* d_posq, int posq_
   c->P.omm.energy_buffer = d_energy_buffer;
   c->P.omm.energy_is_double = energy_is_double;
   c->P.omm.energy_slot = energy_slot;
-  const int rc = enqueue(c, c->d_pos_in.p, c->d_force_tmp.p, c->d_energy_tmp.p, st);
+  const int rc = enqueue(c, c->d_pos_in.p, c->d_force_tmp.p, c->d_energy_tmp.p, st, energy_only);
   c->P.in = OpenmmSource();
   c->P.omm = OpenmmTargets();
   return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int agbnp_hip_execute_openmm(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,
+                             const int* d_atom_index, int padded_num_atoms, long long* d_force_buffer, void* d_energy_buffer,
+                             int energy_is_double, int energy_slot, void* stream) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_posq || !d_force_buffer) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: null pointer");
+  if (padded_num_atoms < c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: padded atom count below the particle count");
+  if (posq_is_double && d_posq_correction)
+    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: a position correction only exists beside float positions");
+  if (energy_slot < 0) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: negative energy slot");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  return agbnp_hip_execute_openmm_to(c, d_posq, posq_is_double, d_posq_correction, d_atom_index, padded_num_atoms, d_force_buffer,
+                                     d_energy_buffer, energy_is_double, energy_slot, st, stream, false);
 }
 
 int agbnp_hip_atom_order_changed(agbnp_hip_context* c) {
@@ -1426,9 +1462,13 @@ int agbnp_hip_finish(agbnp_hip_context* c, void* stream, int* must_repeat) {
   return AGBNP_HIP_OK;
 }
 
-int agbnp_hip_execute_host(agbnp_hip_context* c, const double* pos, double* forces, double* energy) {
-  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!pos || !forces || !energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_host: null pointer");
+}  // extern "C"
+
+namespace {
+// agbnp_hip_execute_host and agbnp_hip_energy_host: forces == nullptr is the energy-only evaluation (nothing but the energy
+// travels back)
+int host_evaluation(agbnp_hip_context* c, const double* pos, double* forces, double* energy) {
+  const bool energy_only = forces == nullptr;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = sizeof(double) * 3 * (size_t)c->n;
   if (c->unfinished) {
@@ -1454,10 +1494,13 @@ int agbnp_hip_execute_host(agbnp_hip_context* c, const double* pos, double* forc
   for (int attempt = 0; attempt < 10; attempt++) {
     HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, h_in ? h_in : pos, bytes, hipMemcpyHostToDevice, c->stream));
     c->P.zero_out = c->d_force_tmp.p;  // (cleared by k_prep: the kernel arguments are captured by value at launch)
-    int rc = enqueue(c, c->d_pos_in.p, c->d_force_tmp.p, d_energy, c->stream);
+    int rc = enqueue(c, c->d_pos_in.p, c->d_force_tmp.p, d_energy, c->stream, energy_only);
     c->P.zero_out = nullptr;
     if (rc != AGBNP_HIP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(h_out, c->d_force_tmp.p, bytes + sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (energy_only)
+      HIP_TRY(c, hipMemcpyAsync(h_out + n3, d_energy, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    else
+      HIP_TRY(c, hipMemcpyAsync(h_out, c->d_force_tmp.p, bytes + sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (c->h_status && c->h_report && !c->timeline.enabled && c->enqueued < 1024) {
       // the short cut: the device's own word on this evaluation (pinned memory, written when its tree stage had ended).
       // The wait for the stream is a spin on its status: a blocking wait comes back 10-20 us late.
@@ -1471,7 +1514,7 @@ int agbnp_hip_execute_host(agbnp_hip_context* c, const double* pos, double* forc
       std::atomic_thread_fence(std::memory_order_acquire);
       if (judged == c->enqueued && h[1] == 0) {
         c->lazy_evals++;
-        for (size_t k = 0; k < n3; k++) forces[k] += h_out[k];
+        for (size_t k = 0; k < n3 && forces; k++) forces[k] += h_out[k];
         *energy = h_out[n3];
         return AGBNP_HIP_OK;
       }
@@ -1480,11 +1523,67 @@ int agbnp_hip_execute_host(agbnp_hip_context* c, const double* pos, double* forc
     rc = harvest(c, &repeat, c->stream);  // (its own reads follow on the stream; one wait for everything)
     if (rc != AGBNP_HIP_OK) return rc;
     if (repeat) continue;
-    for (size_t k = 0; k < n3; k++) forces[k] += h_out[k];
+    for (size_t k = 0; k < n3 && forces; k++) forces[k] += h_out[k];
     *energy = h_out[n3];
     return AGBNP_HIP_OK;
   }
-  return c->fail(AGBNP_HIP_ERR_CAPACITY, "agbnp_hip_execute_host: capacity negotiation did not converge");
+  return c->fail(AGBNP_HIP_ERR_CAPACITY, energy_only ? "agbnp_hip_energy_host: capacity negotiation did not converge"
+                                                     : "agbnp_hip_execute_host: capacity negotiation did not converge");
+}
+
+// the energy-only entry points launch nothing inside a stream capture (energy-only graphs are not supported)
+bool refuse_capture(agbnp_hip_context* c, hipStream_t st, const char* who) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap == hipStreamCaptureStatusNone) return false;
+  c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream is being captured; energy-only evaluations cannot be captured into a graph (capture agbnp_hip_execute_device instead)");
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int agbnp_hip_execute_host(agbnp_hip_context* c, const double* pos, double* forces, double* energy) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!pos || !forces || !energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_host: null pointer");
+  return host_evaluation(c, pos, forces, energy);
+}
+
+int agbnp_hip_energy_host(agbnp_hip_context* c, const double* pos, double* energy) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!pos || !energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_host: null pointer");
+  return host_evaluation(c, pos, nullptr, energy);
+}
+
+int agbnp_hip_energy_device(agbnp_hip_context* c, const double* d_pos, double* d_energy, void* stream) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_pos || !d_energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_device: null pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (refuse_capture(c, st, "agbnp_hip_energy_device")) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  note_stream(c, stream);
+  return enqueue(c, d_pos, c->d_eo_force.p, d_energy, st, true);
+}
+
+int agbnp_hip_energy_openmm(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,
+                            const int* d_atom_index, int padded_num_atoms, void* d_energy_buffer, int energy_is_double,
+                            int energy_slot, void* stream) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_posq || !d_energy_buffer) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: null pointer");
+  if (padded_num_atoms < c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: padded atom count below the particle count");
+  if (posq_is_double && d_posq_correction)
+    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: a position correction only exists beside float positions");
+  if (energy_slot < 0) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: negative energy slot");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (refuse_capture(c, st, "agbnp_hip_energy_openmm")) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  const size_t planes = 3 * (size_t)padded_num_atoms;
+  if (c->d_eo_fixed.count < planes) {  // (hipFree of a smaller one waits for the device: nothing in flight still uses it)
+    HIP_TRY(c, c->d_eo_fixed.alloc(planes));
+    HIP_TRY(c, hipMemset(c->d_eo_fixed.p, 0, sizeof(unsigned long long) * planes));
+  }
+  // the same evaluation as agbnp_hip_execute_openmm, with the context's own fixed-point planes in place of the caller's
+  return agbnp_hip_execute_openmm_to(c, d_posq, posq_is_double, d_posq_correction, d_atom_index, padded_num_atoms,
+                                     reinterpret_cast<long long*>(c->d_eo_fixed.p), d_energy_buffer, energy_is_double, energy_slot, st, stream, true);
 }
 
 int agbnp_hip_get_scalar(agbnp_hip_context* c, int which, double* value) {
@@ -1498,6 +1597,10 @@ int agbnp_hip_get_scalar(agbnp_hip_context* c, int which, double* value) {
     const int* s = c->last_status;
     *value = (s[kStatStickyNode] ? 1 : 0) | (s[kStatStickyAtom] ? 2 : 0) | (s[kStatStickyPack] ? 4 : 0) | (s[kStatStickyRow] ? 8 : 0) |
              (s[kStatStickyOrder] ? 16 : 0) | (s[kStatStickyForest] << 5) | (s[kStatStickySplit] << 8);  // (32 / 64: a forest's nodes / local atoms)
+    return AGBNP_HIP_OK;
+  }
+  if (which == 18) {  // launches of an energy-only evaluation as the context runs now (0: it runs as a full evaluation)
+    *value = energy_only_fast(c) ? (c->version == 1 ? 4 : 2) : 0;
     return AGBNP_HIP_OK;
   }
   if (which == 17) {  // forests healed inside the tree launch over the evaluations the last agbnp_hip_finish covered (none withheld for them)
@@ -1633,7 +1736,8 @@ int agbnp_hip_num_kernels(void) { return kKernelCount; }
 
 const char* agbnp_hip_kernel_name(int index) {
   static const char* names[kKernelCount] = {"k_prep",        "k_tree_cavity", "k_born_tiles", "k_gb_tiles", "k_dborn_tiles",
-                                            "k_tree_pseudo", "k_outputs",     "k_born_rows",  "k_dborn_rows",  "k_gb_rows"};
+                                            "k_tree_pseudo", "k_outputs",     "k_born_rows",  "k_dborn_rows",  "k_gb_rows",
+                                            "k_energy_roles"};
   return (index >= 0 && index < kKernelCount) ? names[index] : "";
 }
 

@@ -948,7 +948,9 @@ __device__ __forceinline__ int wave_max_hi_to_lane63(int m) {
 // sums -- about half the instructions of a pair step (ReferenceAGBNPKernels.cpp:477-499 evaluates the full formula for
 // every pair; the 16 608-atom lattice has 71 % of its tiles out there, 1dwc none).
 constexpr double kGbFarFactor = 4.0 * 60.0 * 0.69314718055994530942;
-template <bool kCut, bool kFar>
+// kEnergy: the instantiation of the energy-only evaluations (agbnp_hip_energy_*): the pair energy alone -- the direct force and
+// the Y sums (and the row form's bw shares made of them) only feed the chain rule and the forces, and are neither summed nor stored
+template <bool kCut, bool kFar, bool kEnergy = false>
 __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __restrict__ aposq, const double* __restrict__ born_part,
                                          const double* __restrict__ inv_rvdw, double* __restrict__ gb_rows, double* __restrict__ egb_out,
                                          const PairArgs& P, char* s_area, double* s_e, int* s_bmax) {
@@ -970,7 +972,7 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
   // (unconditional loads: a choice here would have to wait for them)
   const int ysa = P.a2s[min(64 * I0 + lane, n - 1)], ysc = P.a2s[min(64 * I0 + 64 + lane, n - 1)], ysj = P.a2s[min(64 * J + lane, n - 1)];
   double beta_a = 0.0, beta_c = 0.0, beta_j = 0.0;  // row form of the chain rule: wave 3 (idle here) turns its Y totals into bw shares
-  if (P.rows_on && wave == 3) {
+  if (!kEnergy && P.rows_on && wave == 3) {
     const int ka = min(64 * I0 + lane, n - 1), kc = min(64 * I0 + 64 + lane, n - 1), kj = min(64 * J + lane, n - 1);
     const double ra = inv_rvdw[ka], rc = inv_rvdw[kc], rj = inv_rvdw[kj], pa = born_part[ka], pc = born_part[kc], pj = born_part[kj];
     beta_a = bw_beta(born_radius(ra, pa));
@@ -1088,6 +1090,13 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
   PAIR_STAMP(1, 2);
   StripSums& S = *reinterpret_cast<StripSums*>(s_area);
   const int jslot = (lane + start + 16) & 63;  // whose sums the lane holds after the rotations
+  if (kEnergy) {  // (the force and Y sums of the walk are dead: the compiler drops them)
+    e = wave_sum(e);
+    if (lane == 0) s_e[wave] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) egb_out[0] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
+    return;
+  }
   S.red[wave][0][lane] = kf * fxa;
   S.red[wave][1][lane] = kf * fya;
   S.red[wave][2][lane] = kf * fza;
@@ -1248,7 +1257,9 @@ __device__ __forceinline__ void gb_strip_f32(int n, int I0, int J, const double4
 // kMasks (round 6): the instantiations of the five-launch mode where the Born stage is not the FP64 row launch that carries the
 // masks' renewal (tile kernels: deterministic mode, AGBNP_HIP_ROWS=0): the workgroups behind the last work item are the tiles that
 // lay the level-2 neighbour masks down anew when the cavity launch's trailing workgroups asked for it (k_rows, MASKS)
-template <bool kCut, bool kSingle, bool kFar, bool kMasks = false>
+// kEnergy: the instantiation of the energy-only evaluations (Reference mode, FP64; see gb_strip): the prologue (B, f', E_atom, brw)
+// and the pair energy partials, no direct force, no Y sums, no bw shares; workgroup 0 still does the packing role
+template <bool kCut, bool kSingle, bool kFar, bool kMasks = false, bool kEnergy = false>
 __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__ items, const double4* __restrict__ aposq,
                                                   const double* __restrict__ born_part, const double* __restrict__ inv_rvdw,
                                                   const double* __restrict__ alpha, double* __restrict__ born,
@@ -1291,7 +1302,7 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
   PAIR_STAMP(1, 0);
   if (item & kGbStripFlag) {
     if (kSingle) return gb_strip_f32<kCut>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (blockIdx.x - 1), P, s_area, s_e);
-    return gb_strip<kCut, kFar>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (blockIdx.x - 1), P, s_area, s_e, s_bmax);
+    return gb_strip<kCut, kFar, kEnergy>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (blockIdx.x - 1), P, s_area, s_e, s_bmax);
   }
   const bool diag = I == J;
   if (kCut && !diag) {  // fast mode: a tile whose two blocks are further apart than the cutoff has no pair to meet
@@ -1308,7 +1319,7 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
   PAIR_STAMP_WHERE(1, item);
   const int ysi = P.a2s[min(64 * I + lane, n - 1)], ysj = P.a2s[min(64 * J + lane, n - 1)];  // (the Y sums leave by pair-order slot, see gb_strip)
   double beta_i = 0.0, beta_j = 0.0;  // row form of the chain rule: see gb_strip
-  if (P.rows_on && wave == 3) {
+  if (!kEnergy && P.rows_on && wave == 3) {
     const int ki = min(64 * I + lane, n - 1), kj = min(64 * J + lane, n - 1);
     const double ri = inv_rvdw[ki], rj = inv_rvdw[kj], pi = born_part[ki], pj = born_part[kj];
     beta_i = bw_beta(born_radius(ri, pi));
@@ -1342,7 +1353,7 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
         e_atom[a] = al / bh3 + kDielFactor * pa.w * pa.w * bra.inv_br;
         brw[a] = brw_a;
         P.srec[ysi] = make_double4(bra.br, bra.fp, brw_a, pa.w);  // the chain-rule stage's copy, by slot (a = 64 I + lane here)
-        if (P.rows_on) hbm_add(&P.bw[a], bw_alpha(bra, brw_a, pa.w));
+        if (!kEnergy && P.rows_on) hbm_add(&P.bw[a], bw_alpha(bra, brw_a, pa.w));
       }
     }
   }
@@ -1398,6 +1409,13 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
   __syncthreads();  // every wave is done with the records
   PAIR_STAMP(1, 2);
   TileSums& s_sums = *reinterpret_cast<TileSums*>(s_area);
+  if (kEnergy) {  // (see gb_strip)
+    e = wave_sum(e);
+    if (lane == 0) s_e[wave] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) egb_part[blockIdx.x - 1] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
+    return;
+  }
   {
     const double vi4[4] = {kf * fxi, kf * fyi, kf * fzi, yi}, vj4[4] = {kf * fxj, kf * fyj, kf * fzj, yj_acc};
     tile_sums_store(s_sums, wave, lane, (lane + start + nsteps) & 63, vi4, vj4);  // jslot: whose sums the lane holds now
@@ -1837,6 +1855,21 @@ __global__ __launch_bounds__(256) void k_outputs(PairArgs P, int version, double
   force_out[3 * i + 2] += fz;
 }
 
+// ---- energy-only evaluations (agbnp_hip_energy_*, version 1): the close of the evaluation ---------------------------------
+// A full evaluation's chain-rule launch carries the energy role and the dealing role, and the pseudo-volume launch's output
+// workgroups close the neighbour rows' evaluation (rows_close_evaluation).  An energy-only evaluation launches neither: this
+// small launch behind its GB stage does the three, so that the context is left as a full evaluation leaves it.
+//   block 0  energy role (energy sum, sticky log, the host's window on it)
+//   block 1  dealing role (the next evaluation's packing into work slots), with the chain-rule launch's LDS: the same dealing
+//   block 2  rows_close_evaluation (one lane)
+__global__ __launch_bounds__(256) void k_energy_roles(PairArgs P, double* __restrict__ energy_out, double* __restrict__ components,
+                                                      int role_bytes) {
+  extern __shared__ double2 s_dyn[];
+  if (blockIdx.x == 0) return energy_role(P, 1, energy_out, components, reinterpret_cast<char*>(s_dyn));
+  if (blockIdx.x == 1) return dealing_role(P, reinterpret_cast<char*>(s_dyn), role_bytes);
+  if (threadIdx.x == 0 && P.rows_on) rows_close_evaluation(P.nl_flag, P.nl_nitems, P.row_target, P.gb_rows != 0);
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------
 #define AGBNP_CHECK_LAUNCH()             \
   do {                                   \
@@ -1940,6 +1973,46 @@ hipError_t launch_pair_stages(const PairArgs& P, double* energy_out, double* com
                      (const double*)P.pbox, (const double4*)P.prec, (const double4*)P.srec, (const double*)P.ys, (const double*)P.sv_vdw,
                      P.inv_vol_h, P.nh, P.lut, P.db_fx, P, energy_out, components, (int)db_lds);
   AGBNP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+// The energy-only evaluation's launches behind the cavity launch (engine.hip, energy_only_fast: five-launch mode with the
+// host-named set, Reference semantics, FP64 rows).  Version 1: the Born rows exactly as in a full evaluation (they also build the
+// chain-rule lists after a rebuild and carry the masks' renewal tiles), the GB stage's energy-only instantiation, k_energy_roles.
+// Version 0: the output launch's two role workgroups and its mask tiles, without force workgroups.
+hipError_t launch_energy_only_stages(const PairArgs& P, int version, double* energy_out, double* components, hipStream_t st,
+                                     Timeline* tl) {
+  if (version != 1) {
+    AGBNP_MARK(kKOutputs);
+    const int nh1 = std::max(P.nh, 1);  // (the roles' LDS as launch_outputs sizes it)
+    const int classes_ints = std::min(2 * nh1 + 64, 12288), rounds_ints = std::min(nh1 + P.tree_slots + nh1 + nh1 / 4 + 64, 14000);
+    const int role_bytes = (int)kRoleScratchBytes + 4 * std::max(classes_ints, rounds_ints);
+    hipLaunchKernelGGL(k_outputs, dim3(2 + P.nb_tiles), dim3(256), role_bytes, st, P, version, (double*)nullptr, energy_out, components,
+                       role_bytes, 2);
+    AGBNP_CHECK_LAUNCH();
+    AGBNP_MARK(-1);
+    return hipSuccess;
+  }
+  if (!P.rows_on || P.gb_rows || P.single || P.fast || P.det || P.five != 1) return hipErrorInvalidValue;  // (engine.hip never asks)
+  const int born_groups = (P.n + kRowGroup - 1) / kRowGroup, chain_groups = (P.nh + kRowGroup - 1) / kRowGroup;
+  auto walk_blocks = [](int lists, int cap) { return (lists + kRowWaves - 1) / kRowWaves * ((cap + kRowSlice - 1) / kRowSlice); };
+  const int born_blocks = walk_blocks(born_groups * kBornParts, P.nlh_cap);
+  const int build_blocks = (chain_groups * kChainParts + kRowWaves - 1) / kRowWaves;
+  const size_t table_lds = (size_t)2 * P.nti * P.ntj * kRowIntervals * sizeof(double2);
+  const size_t chain_lds = std::max(table_lds, sizeof(TileSums));
+  AGBNP_MARK(kKBornRows);
+  hipLaunchKernelGGL((k_rows<kBornRows, false, true>), dim3(born_blocks + build_blocks + P.nb_tiles), dim3(64 * kRowWaves), table_lds, st, P,
+                     (double*)nullptr, (double*)nullptr, born_blocks + build_blocks);
+  AGBNP_CHECK_LAUNCH();
+  AGBNP_MARK(kKGbTiles);
+  auto gb = P.gb_far ? k_gb_tiles<false, false, true, false, true> : k_gb_tiles<false, false, false, false, true>;
+  hipLaunchKernelGGL(gb, dim3(P.gb_items_count + 1), dim3(256), 0, st, P.n, P.gb_items, (const double4*)P.aposq, (const double*)P.born_part,
+                     P.inv_rvdw, P.alpha, P.born, P.born_fp, P.brw, P.e_atom, P.gb_fx, P.egb_part, P);
+  AGBNP_CHECK_LAUNCH();
+  AGBNP_MARK(kKEnergyRoles);
+  hipLaunchKernelGGL(k_energy_roles, dim3(3), dim3(256), chain_lds, st, P, energy_out, components, (int)chain_lds);
+  AGBNP_CHECK_LAUNCH();
+  AGBNP_MARK(-1);
   return hipSuccess;
 }
 

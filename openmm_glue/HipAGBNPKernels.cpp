@@ -93,7 +93,7 @@ void HipCalcAGBNPForceKernel::initialize(const System& system, const AGBNPForce&
   sinceFinish = 0;
 }
 
-void HipCalcAGBNPForceKernel::enqueue() {
+void HipCalcAGBNPForceKernel::enqueue(bool energyOnly) {
   const bool dbl = cu.getUseDoublePrecision(), mixed = cu.getUseMixedPrecision();
   // OpenMM reorders its atoms now and then (ComputeContext::reorderAtoms: same arrays, new contents).  The engine would find
   // out by itself -- and repeat one evaluation; the host copy of the order is at hand, so it is told beforehand.
@@ -101,6 +101,15 @@ void HipCalcAGBNPForceKernel::enqueue() {
   if (order != lastOrder) {
     if (!lastOrder.empty()) agbnp_hip_atom_order_changed(engine);
     lastOrder = order;
+  }
+  if (energyOnly) {  // no force buffer: the energy alone, into the same slot
+    if (agbnp_hip_energy_openmm(engine, cu.getPosq().getDevicePointer(), dbl ? 1 : 0,
+                                mixed ? cu.getPosqCorrection().getDevicePointer() : nullptr,
+                                static_cast<const int*>(cu.getAtomIndexArray().getDevicePointer()), cu.getPaddedNumAtoms(),
+                                cu.getEnergyBuffer().getDevicePointer(), (dbl || mixed) ? 1 : 0, /*energy slot*/ 0,
+                                cu.getCurrentStream()) != AGBNP_HIP_OK)
+      throw OpenMMException(agbnp_hip_last_error(engine));
+    return;
   }
   if (agbnp_hip_execute_openmm(engine, cu.getPosq().getDevicePointer(), dbl ? 1 : 0,
                                mixed ? cu.getPosqCorrection().getDevicePointer() : nullptr,
@@ -113,8 +122,11 @@ void HipCalcAGBNPForceKernel::enqueue() {
 
 double HipCalcAGBNPForceKernel::execute(ContextImpl& context, bool includeForces, bool includeEnergy) {
   if (!engine) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
-  // both are always computed, as in the reference (ReferenceAGBNPKernels.cpp:139-149 ignores the two flags)
-  enqueue();
+  // includeForces = true: forces and energy, as in the reference (ReferenceAGBNPKernels.cpp:139-149 ignores the two flags).
+  // includeForces = false (getState(getEnergy=True) without forces, reporters, Monte-Carlo tests, replica-exchange energy
+  // matrices): an energy-only evaluation -- nothing reaches the force buffer, the same per-step check follows
+  const bool energyOnly = !includeForces;
+  enqueue(energyOnly);
   if (verdictMode) {
     // the host waits for the device's word on this evaluation, not for the stream; the blocking path below is only taken
     // for a withheld evaluation (repeat it, as the reference does), without pinned memory, and once in 1024 evaluations
@@ -157,7 +169,7 @@ double HipCalcAGBNPForceKernel::execute(ContextImpl& context, bool includeForces
                               "its forces were not applied.  Restart from the last checkpoint (the capacity has been raised) "
                               "or run with AGBNP_HIP_CHECK_INTERVAL=1");
       if (attempt >= 8) throw OpenMMException("AGBNPForce (HIP): capacity negotiation did not converge");
-      enqueue();
+      enqueue(energyOnly);
     }
   }
   return 0.0;  // the energy went into the context's energy buffer (OpenCLAGBNPKernels.cpp:555)

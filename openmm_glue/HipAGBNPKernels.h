@@ -45,7 +45,7 @@ class HipCalcAGBNPForceKernel : public CalcAGBNPForceKernel {
   agbnp_hip_context* getEngine() { return engine; }
 
  private:
-  void enqueue();
+  void enqueue(bool energyOnly);  // energyOnly: agbnp_hip_energy_openmm (execute with includeForces = false)
   OpenMM::HipContext& cu;
   agbnp_hip_context* engine;
   int checkInterval, sinceCheck;
