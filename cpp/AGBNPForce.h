@@ -121,6 +121,28 @@ class HipCalcAGBNPForceKernel {
     return e;
   }
 
+  // Replica groups (agbnp_hip_execute_group_host): one evaluation of every kernel in `kernels`, the launches of the members
+  // that can share them made once for all; positions[i] (3N_i) read, forces[i] accumulated, the members' energies returned.
+  static std::vector<double> executeGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,
+                                          const std::vector<std::vector<double>>& positions, std::vector<std::vector<double>>& forces) {
+    const size_t n = kernels.size();
+    if (n < 1 || n > AGBNP_HIP_MAX_GROUP) throw OpenMMException("executeGroup(): a group has 1 to 16 members");
+    if (positions.size() != n || forces.size() != n) throw OpenMMException("executeGroup(): one position and one force array per member");
+    std::vector<agbnp_hip_context*> ctxs(n);
+    std::vector<const double*> pos(n);
+    std::vector<double*> frc(n);
+    for (size_t i = 0; i < n; i++) {
+      if (!kernels[i] || !kernels[i]->ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+      const size_t n3 = 3 * (size_t)kernels[i]->numParticles;
+      if (positions[i].size() != n3 || forces[i].size() != n3) throw OpenMMException("executeGroup(): arrays must hold 3N values");
+      ctxs[i] = kernels[i]->ctx, pos[i] = positions[i].data(), frc[i] = forces[i].data();
+    }
+    std::vector<double> energies(n, 0.0);
+    if (agbnp_hip_execute_group_host(ctxs.data(), (int)n, pos.data(), frc.data(), energies.data()) != AGBNP_HIP_OK)
+      throw OpenMMException(agbnp_hip_last_error(ctxs[0]));
+    return energies;
+  }
+
   void copyParametersToContext(const AGBNPForce& force) {
     if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
     std::vector<double> r, g, a, q;

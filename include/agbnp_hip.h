@@ -151,6 +151,44 @@ int agbnp_hip_energy_openmm(agbnp_hip_context* ctx, const void* d_posq, int posq
                             const int* d_atom_index, int padded_num_atoms, void* d_energy_buffer, int energy_is_double,
                             int energy_slot, void* stream); /* ADDED to d_energy_buffer[energy_slot]; async */
 
+/* Replica groups: ONE call that enqueues an evaluation of each of `count` existing contexts (1 .. AGBNP_HIP_MAX_GROUP), for
+ * replica exchange, multiple walkers and binding-energy schemes that run several small systems at once.  d_positions,
+ * d_forces, d_energies are HOST arrays of `count` DEVICE pointers, one per member.  For every member i the call does exactly
+ * what agbnp_hip_execute_device(ctxs[i], d_positions[i], d_forces[i], d_energies[i], stream) would do: the same numbers,
+ * forces and energy ADDED, the evaluation counted in THAT member's overflow log under its own enqueue index -- so
+ * agbnp_hip_finish(), _poll(), _wait_verdict(), _withheld_evaluations() and _generation() work per member, a withheld member
+ * (a jump of more than 0.04 nm, a subtree that needs the next capacity variant) does not affect the others, and group and
+ * single-context calls on the same contexts may be interleaved in any order.
+ * Members must be distinct contexts on one device, every pointer non-NULL, and the output buffers of different members must
+ * not overlap; otherwise AGBNP_HIP_ERR_INVALID_ARGUMENT, nothing is launched and no member changes.  A NULL `stream` means the
+ * first member's own stream: the call orders it behind every member's own stream and every member's own stream behind the
+ * group's work, so each member's agbnp_hip_finish(NULL) drains it (no member keeps a reference to another member's stream).
+ * A caller stream is noted on every member as agbnp_hip_execute_device notes it.  If the call fails with a device error, the
+ * members whose launches were not reached are left as they were; a member whose launches failed must be recreated, as after
+ * a failed agbnp_hip_execute_device.  Inside a stream capture the call is refused
+ * (AGBNP_HIP_ERR_INVALID_ARGUMENT, the capture stays usable): groups are not captured into graphs.
+ * Launches.  A member SHARES when its evaluation is exactly the default launch sequence: the five-launch mode with the
+ * host-named set (never captured), the Reference semantics, for version 1 the FP64 row form with the forces leaving with the
+ * pseudo-volume launch, capacity variant 0-3, no diagnostics, no profiling, AGBNP_HIP_GROUP_LAUNCHES not 0.  Sharing members
+ * are split into launch sets by version, capacity variant and the GB far-strip test; each launch set is FIVE launches for
+ * version 1 (cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes) or TWO for version 0 (cavity, outputs), whatever
+ * its size.  A member's one-off launches (the masks of a fresh context, the words beside the rows after the other entry point)
+ * go in front of them.  Every other member runs its ordinary launches on the same stream: correct, not faster.  Members may
+ * be different systems or the same system with different parameters.  Scalar 19 says how the last evaluation ran.
+ * Argument blocks.  What the shared launches read of a sharing member lives on the device, in the context's own argument block
+ * (one per parity of the five-launch mode's sets), rewritten by one small launch only when it changes: a new capacity variant,
+ * grown neighbour rows, the other entry point, ANOTHER POSITION BUFFER.  The force and energy pointers travel with each launch,
+ * so output buffers may change in every call at no cost; a caller that passes a different d_positions[i] than in the call two
+ * group calls before (the same parity) pays one extra small launch for that member.  Keep one position buffer per member (an
+ * MD loop does) and a steady run enqueues the five (two) shared launches and nothing else. */
+#define AGBNP_HIP_MAX_GROUP 16
+int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,
+                            double* const* d_energies, void* stream);
+/* The synchronous twin for host buffers: positions[i][3 n_i] read, forces[i][3 n_i] ACCUMULATED (+=), energies[i] RETURNED.
+ * Withheld members are repeated inside, as agbnp_hip_execute_host() does. */
+int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces,
+                                 double* energies);
+
 /* Tells the engine that the contents of the d_atom_index array it last saw have changed (OpenMM has reordered its atoms):
  * the next agbnp_hip_execute_openmm() rebuilds its maps first, and no evaluation is lost to the check.  Optional -- without
  * it the first evaluation after a reorder is withheld and repeated, see above. */
@@ -248,6 +286,8 @@ int agbnp_hip_get_mode(const agbnp_hip_context* ctx);
  *          16 kernel launches of an evaluation as the context runs now: version 1: 5 (five-launch mode) or 6; version 0: 2 or 3
  *          18 kernel launches of an energy-only evaluation as the context runs now: 4 (version 1) or 2 (version 0), 0 where it
              runs as a full evaluation with its forces sent to a buffer of the context's own
+          19 members of the launch set of agbnp_hip_execute_group whose shared launches the context's last evaluation ran in
+ *             (a group of one counts 1); 0 when it did not run through shared launches
           17 forests that outgrew their store and were healed inside the tree launch (built again in smaller sets: the
  *             evaluation is complete, nothing is withheld for them) over the evaluations the last agbnp_hip_finish() covered
  *          14 forest packings planned so far (a packing in use is planned anew every AGBNP_HIP_REPLAN_EVERY-th evaluation,

@@ -326,7 +326,7 @@ class HipCalcAGBNPForceKernel:
             raise OpenMMException(_lib.last_error(self._h))
 
     # ---- diagnostics (test support) -------------------------------------------------------------
-    SCALARS = dict(e_vol1=0, e_vol2=1, e_atom=2, e_gb_pair=3, max_subtree_nodes=4, total_nodes=5, variant=6, max_local_atoms=7, forests=8, rows_on=9, row_builds=10, pack_level=11, pack_age=12, row_slice=13, pack_plans=14, overflow_kinds=15, launches=16, healed_forests=17, energy_only_launches=18)
+    SCALARS = dict(e_vol1=0, e_vol2=1, e_atom=2, e_gb_pair=3, max_subtree_nodes=4, total_nodes=5, variant=6, max_local_atoms=7, forests=8, rows_on=9, row_builds=10, pack_level=11, pack_age=12, row_slice=13, pack_plans=14, overflow_kinds=15, launches=16, healed_forests=17, energy_only_launches=18, group_members=19)
     VECTORS = dict(selfvol_vdw=0, born=1, scale=2, selfvol_large=3, subtree_nodes=4, subtree_atoms=5)
 
     def scalar(self, name):
@@ -386,6 +386,58 @@ class HipCalcAGBNPForceKernel:
             self.release()
         except Exception:
             pass
+
+
+def _group_handles(kernels, who):
+    kernels = list(kernels)
+    if not 1 <= len(kernels) <= _lib.MAX_GROUP:
+        raise OpenMMException(f"{who}(): a group has 1 to {_lib.MAX_GROUP} members, not {len(kernels)}")
+    for k in kernels:
+        if not isinstance(k, HipCalcAGBNPForceKernel):
+            raise OpenMMException(f"{who}(): members must be HipCalcAGBNPForceKernel objects")
+        k._need()
+    return kernels, (C.c_void_p * len(kernels))(*[k._h for k in kernels])
+
+
+def execute_group(kernels, d_positions, d_forces, d_energies, stream=None):
+    """Replica groups (include/agbnp_hip.h, agbnp_hip_execute_group): one call that enqueues an evaluation of every kernel in
+    `kernels`, with the launches of the members that can share them made once for all of them.  d_positions, d_forces,
+    d_energies: lists of raw FP64 device pointers (ints), one per member; forces and energies are ADDED, as by each member's
+    execute_device().  Asynchronous; each member's finish() reports its own withheld evaluations."""
+    kernels, hs = _group_handles(kernels, "execute_group")
+    n = len(kernels)
+    for name, ptrs in (("d_positions", d_positions), ("d_forces", d_forces), ("d_energies", d_energies)):
+        if len(ptrs) != n:
+            raise OpenMMException(f"execute_group(): {name} has {len(ptrs)} entries for {n} members")
+    arr = lambda ptrs: (C.c_void_p * n)(*[int(p or 0) for p in ptrs])  # noqa: E731
+    rc = _lib.load().agbnp_hip_execute_group(hs, n, arr(d_positions), arr(d_forces), arr(d_energies), C.c_void_p(stream or 0))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(kernels[0]._h))
+
+
+def execute_group_host(kernels, positions, forces):
+    """Synchronous twin of execute_group() for host buffers: positions[i] (N_i x 3) are read, forces[i] (C-contiguous float64
+    arrays of 3 N_i values) are accumulated in place, the members' energies are returned as a list.  Withheld members are
+    repeated inside."""
+    kernels, hs = _group_handles(kernels, "execute_group_host")
+    n = len(kernels)
+    if len(positions) != n or len(forces) != n:
+        raise OpenMMException(f"execute_group_host(): {len(positions)} positions and {len(forces)} force arrays for {n} members")
+    pos = []
+    for k, p, f in zip(kernels, positions, forces):
+        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+        if p.size != 3 * k.numParticles:
+            raise OpenMMException("execute_group_host(): wrong number of positions")
+        if not (isinstance(f, np.ndarray) and f.dtype == np.float64 and f.flags.c_contiguous and f.size == 3 * k.numParticles):
+            raise OpenMMException("execute_group_host(): forces must be C-contiguous float64 arrays of 3N values")
+        pos.append(p)
+    dpp = C.POINTER(C.c_double)
+    energies = np.zeros(n)
+    rc = _lib.load().agbnp_hip_execute_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), (dpp * n)(*[_dp(f) for f in forces]),
+                                                  _dp(energies))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(kernels[0]._h))
+    return [float(e) for e in energies]
 
 
 def host_tables(radius, ishydrogen):

@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AGBNP_HIP_LIBRARY") or os.path.join(_HERE, "libagbnp_hip.so")  # override: diagnostic builds only
 
 OK, ERR_INVALID_ARGUMENT, ERR_PARAMETERS, ERR_DEVICE, ERR_CAPACITY, ERR_TIMEOUT = 0, 1, 2, 3, 4, 5
+MAX_GROUP = 16  # AGBNP_HIP_MAX_GROUP: members of one agbnp_hip_execute_group call
 
 # every symbol include/agbnp_hip.h declares
 SYMBOLS = [
@@ -18,6 +19,7 @@ SYMBOLS = [
     "agbnp_hip_last_error", "agbnp_hip_destroy", "agbnp_hip_device_count", "agbnp_hip_build_id",
     "agbnp_hip_set_mode", "agbnp_hip_get_mode", "agbnp_hip_set_diagnostics", "agbnp_hip_set_profiling", "agbnp_hip_num_kernels", "agbnp_hip_kernel_name", "agbnp_hip_get_kernel_times",
     "agbnp_hip_energy_host", "agbnp_hip_energy_device", "agbnp_hip_energy_openmm",
+    "agbnp_hip_execute_group", "agbnp_hip_execute_group_host",
 ]
 
 _lib = None
@@ -61,6 +63,8 @@ def load():
     lib.agbnp_hip_energy_host.argtypes = [vp, dp, dp]
     lib.agbnp_hip_energy_device.argtypes = [vp, vp, vp, vp]
     lib.agbnp_hip_energy_openmm.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
+    lib.agbnp_hip_execute_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
+    lib.agbnp_hip_execute_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), C.POINTER(dp), dp]
     lib.agbnp_hip_atom_order_changed.argtypes = [vp]
     lib.agbnp_hip_finish.argtypes = [vp, vp, ip]
     lib.agbnp_hip_poll.argtypes = [vp, ip, ip]

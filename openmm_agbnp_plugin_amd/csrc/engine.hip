@@ -24,6 +24,7 @@
 #include "../../include/agbnp_hip.h"
 #include "adapter_kernels.h"
 #include "agbnp_common.h"
+#include "group_args.h"
 #include "i4_tables.h"
 #include "pair_kernels.h"
 #include "tree_kernels.h"
@@ -37,6 +38,9 @@ int tree_variant_wgs_per_cu(int variant);
 hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
 hipError_t launch_tree_pseudo(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
 hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st);
+int tree_five_grid(int slots, const PairArgs& P);
+int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A);
+size_t tree_variant_replay_bytes(int variant);
 }  // namespace agbnp
 
 using namespace agbnp;
@@ -95,6 +99,7 @@ constexpr int kGlobalGrid = 256;  // persistent workgroups of the global-scratch
 //   ROW_FILL           1.5                   >= 0.01                                                 parity
 //   ROW_STRIDE         from the system       >= 128                                                  parity
 //   MASK_SKIN          0.08 nm               [0, 0.5]                                                include/agbnp_hip.h documents it
+//   GROUP_LAUNCHES     on                    0: the context runs alone inside agbnp_hip_execute_group    scripts/replica_group_timing.py
 // SKIN and the ROW_* settings take effect only in a context that can run the row form (allocate_rows).
 struct EngineSettings {
   bool five_launches = true;
@@ -111,6 +116,7 @@ struct EngineSettings {
   int row_slice = 0;        // 0: unset
   double row_fill = 1.5;
   int row_stride = 0;       // 0: unset
+  bool group_launches = true;
   double mask_skin = 0.08;  // (0.06 and 0.08 cost the cavity launch the same; 0.04 renews the masks at every other evaluation of the headline's jitter)
 };
 
@@ -131,6 +137,7 @@ EngineSettings read_settings() {
   if (const char* v = getenv("AGBNP_HIP_ROW_FILL")) s.row_fill = std::max(0.01, atof(v));
   if (const char* v = getenv("AGBNP_HIP_ROW_STRIDE")) s.row_stride = std::max(128, atoi(v));
   if (const char* v = getenv("AGBNP_HIP_MASK_SKIN")) s.mask_skin = std::min(0.5, std::max(0.0, atof(v)));
+  if (const char* v = getenv("AGBNP_HIP_GROUP_LAUNCHES")) s.group_launches = atoi(v) != 0;
   return s;
 }
 
@@ -271,6 +278,13 @@ struct agbnp_hip_context {
   int row_slice = 0;           // AGBNP_HIP_ROW_SLICE: entries per slice, fixed (0: tuned on the device, see rows_close_evaluation)
   bool have_results = false;
   bool diagnostics = false;
+  // replica groups (agbnp_hip_execute_group): the context's argument blocks of the shared launches, one per parity of the
+  // five-launch mode's sets, and what was last written to each (a block is rewritten only when it changes)
+  DevBuf<GroupMemberArgs> d_group;
+  GroupMemberArgs group_written[2];
+  bool group_valid[2] = {false, false};
+  hipEvent_t group_event = nullptr;  // joins the context's own stream and a group's stream
+  int group_members = 0;             // scalar 19: members of the launch set the last evaluation shared (0: it ran alone)
 
   int fail(int code, const std::string& msg) {
     err = msg;
@@ -939,9 +953,18 @@ bool energy_only_fast(const agbnp_hip_context* c) {
   return c->P.rows_on && !c->P.gb_rows && !c->P.single && !c->P.fast && !c->P.det;
 }
 
-int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, hipStream_t st, bool energy_only = false) {
+// What enqueue() decides before its launches (enqueue_prepare) and hands to them (enqueue_launch)
+struct EvalPlan {
+  int tree_grid = 1;   // workgroups of the tree launches
+  bool fused = false;  // version 1: the forces leave with the pseudo-volume launch
+};
+
+// The per-evaluation host logic of an evaluation: scratch, the five-launch mode's exits, its set, the one-off launches in front
+// of the evaluation (the masks of a fresh context, the words beside the rows), the decision on the outputs.
+int enqueue_prepare(agbnp_hip_context* c, const double* d_pos, hipStream_t st, EvalPlan& plan) {
   int rc = ensure_scratch(c);
   if (rc != AGBNP_HIP_OK) return rc;
+  c->group_members = 0;
   c->enqueued++;
   c->P.pos = d_pos;
   c->P.tree_node_cap = tree_variant_node_cap(c->variant);  // the packing of the next evaluation is sized for the variant in use
@@ -973,7 +996,7 @@ int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* 
   }
   // workgroups of the tree launches: what the device keeps resident for this variant (they take forests from a queue);
   // fewer if there cannot be that many forests
-  const int tree_grid = std::max(1, std::min(c->slot_cap, c->tree_slots[c->variant]));
+  plan.tree_grid = std::max(1, std::min(c->slot_cap, c->tree_slots[c->variant]));
   if (c->five_active) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (!c->five_device && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
@@ -1003,6 +1026,54 @@ int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* 
       HIP_TRY(c, launch_masks(c->P, st, tl));
       c->masks_valid = true;
     }
+  }
+  if (c->version == 1) {
+    // The forces leave with the pseudo-volume launch when that launch is one round of workgroups (1dwc: -1 us, A/B on one
+    // box).  With more forests than resident workgroups a workgroup replays several forests in a row, and the next
+    // forest's loads queue behind the force atomics of the one before (three adds on one line of the caller's [n][3]
+    // buffer retire more slowly than the heavy-atom table's separate rows: lattice of 16.6 k atoms 49 -> 99 us): there the
+    // output launch stays.  (No heavy atom: no tree launch to carry them.)
+    // (Round 4: the replay of queued forests is pipelined -- the next forest's data are asked for in front of the flush -- and
+    // the forces were tried in the launch again: lattice k_tree_pseudo 51 -> 109 us once more.  On gfx9 loads, stores and
+    // atomics share one in-order counter, and a wait that crosses the loop's back edge is a wait for everything, the
+    // flush's atomics included.)
+    // (Round 5: a system with more subtrees than that whose forests nevertheless fit ONE round -- 2clr under the rounds rule of
+    // the packing: 3084 subtrees in 1280 forests -- is told by the forest count of the last evaluation the host has seen;
+    // a stale hint costs time, never correctness.)
+    const bool one_round = c->forests_hint > 0 && c->forests_hint <= c->tree_slots[c->variant];
+    plan.fused = c->nh > 0 && (c->nh <= 2 * c->tree_slots[c->variant] || one_round);
+  }
+  return AGBNP_HIP_OK;
+}
+
+// the outputs of the pseudo-volume launch (TreeOutputs, tree_kernels.h)
+void set_outputs(agbnp_hip_context* c, double* d_force, bool fused) {
+  TreeOutputs& O = c->T.out;
+  O.enabled = fused ? 1 : 0;
+  O.n = c->n;
+  O.a2h = c->d_a2h.p;
+  O.h2a = c->d_h2a.p;
+  O.force = c->P.omm.force_fixed ? nullptr : d_force;
+  O.force_fixed = c->P.omm.force_fixed;
+  O.padded = c->P.omm.padded;
+  O.ctx_slot = c->P.omm.ctx_slot;
+  O.gb_f = c->P.gb_fx;
+  O.db_f = c->P.db_fx;
+  O.rows_on = c->P.rows_on;
+  O.bw = c->P.bw;
+  O.grec = c->P.grec;
+  O.hrec = c->P.hrec;
+  O.nl_flag = c->P.nl_flag;
+  O.nl_nitems = c->P.nl_nitems;
+  O.row_target = c->P.row_target;
+  O.gb_rows = c->P.gb_rows;
+}
+
+// The launches of an evaluation that enqueue_prepare has prepared
+int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, double* d_force, double* d_energy, hipStream_t st, bool energy_only) {
+  Timeline* tl = c->timeline.enabled ? &c->timeline : nullptr;
+  const int tree_grid = plan.tree_grid;
+  if (c->five_active) {
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
     HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st));
     if (energy_only && energy_only_fast(c)) {
@@ -1017,40 +1088,9 @@ int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* 
   if (c->version == 1) {
     HIP_TRY(c, launch_pair_stages(c->P, d_energy, c->d_components.p, st, tl));
     if (tl) HIP_TRY(c, tl->mark(kKTreePseudo, st));
-    // the forces leave with the pseudo-volume launch itself (TreeOutputs, tree_kernels.h): no output launch
-    TreeOutputs& O = c->T.out;
-    // The forces leave with the pseudo-volume launch when that launch is one round of workgroups (1dwc: -1 us, A/B on one
-    // box).  With more forests than resident workgroups a workgroup replays several forests in a row, and the next
-    // forest's loads queue behind the force atomics of the one before (three adds on one line of the caller's [n][3]
-    // buffer retire more slowly than the heavy-atom table's separate rows: lattice of 16.6 k atoms 49 -> 99 us): there the
-    // output launch stays.  (No heavy atom: no tree launch to carry them.)
-    // (Round 4: the replay of queued forests is pipelined -- the next forest's data are asked for in front of the flush -- and
-    // the forces were tried in the launch again: lattice k_tree_pseudo 51 -> 109 us once more.  On gfx9 loads, stores and
-    // atomics share one in-order counter, and a wait that crosses the loop's back edge is a wait for everything, the
-    // flush's atomics included.)
-    // (Round 5: a system with more subtrees than that whose forests nevertheless fit ONE round -- 2clr under the rounds rule of
-    // the packing: 3084 subtrees in 1280 forests -- is told by the forest count of the last evaluation the host has seen;
-    // a stale hint costs time, never correctness.)
-    const bool one_round = c->forests_hint > 0 && c->forests_hint <= c->tree_slots[c->variant];
-    const bool fused = c->nh > 0 && (c->nh <= 2 * c->tree_slots[c->variant] || one_round);
-    O.enabled = fused ? 1 : 0;
-    O.n = c->n;
-    O.a2h = c->d_a2h.p;
-    O.h2a = c->d_h2a.p;
-    O.force = c->P.omm.force_fixed ? nullptr : d_force;
-    O.force_fixed = c->P.omm.force_fixed;
-    O.padded = c->P.omm.padded;
-    O.ctx_slot = c->P.omm.ctx_slot;
-    O.gb_f = c->P.gb_fx;
-    O.db_f = c->P.db_fx;
-    O.rows_on = c->P.rows_on;
-    O.bw = c->P.bw;
-    O.grec = c->P.grec;
-    O.hrec = c->P.hrec;
-    O.nl_flag = c->P.nl_flag;
-    O.nl_nitems = c->P.nl_nitems;
-    O.row_target = c->P.row_target;
-    O.gb_rows = c->P.gb_rows;
+    // the forces leave with the pseudo-volume launch itself (TreeOutputs, tree_kernels.h): no output launch (enqueue_prepare)
+    const bool fused = plan.fused;
+    set_outputs(c, d_force, fused);
     HIP_TRY(c, launch_tree_pseudo(c->variant, kGlobalGrid, tree_grid, c->T, st));
     if (fused) {
       if (tl) HIP_TRY(c, tl->mark(-1, st));
@@ -1059,6 +1099,13 @@ int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* 
   }
   HIP_TRY(c, launch_outputs(c->P, c->version, d_force, d_energy, c->d_components.p, st, tl, c->five_active && c->version == 0));
   return AGBNP_HIP_OK;
+}
+
+int enqueue(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, hipStream_t st, bool energy_only = false) {
+  EvalPlan plan;
+  const int rc = enqueue_prepare(c, d_pos, st, plan);
+  if (rc != AGBNP_HIP_OK) return rc;
+  return enqueue_launch(c, plan, d_force, d_energy, st, energy_only);
 }
 
 // one work item per work slot (what a context starts with, and what an overflowed evaluation is repeated on): every subtree
@@ -1465,27 +1512,32 @@ int agbnp_hip_finish(agbnp_hip_context* c, void* stream, int* must_repeat) {
 }  // extern "C"
 
 namespace {
+// The sticky overflow log is about to be read and cleared by a host-facing call's own harvest.  Evaluations that the caller
+// has enqueued with agbnp_hip_execute_device and not yet finished must not lose their entries: they are harvested now and
+// carried over to the caller's next agbnp_hip_finish.
+int carry_unfinished(agbnp_hip_context* c) {
+  if (!c->unfinished) return AGBNP_HIP_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (void* st : c->user_streams) HIP_TRY(c, hipStreamSynchronize((hipStream_t)st));
+  int pending = 0;
+  int rc = harvest(c, &pending, c->stream);
+  if (rc != AGBNP_HIP_OK) return rc;
+  const int seq = c->last_device_seq;
+  for (int k : c->withheld) c->carried.push_back(k + c->carried_seq);
+  c->carried_count += pending;
+  c->carried_seq += seq;
+  c->unfinished = false;
+  return AGBNP_HIP_OK;
+}
+
 // agbnp_hip_execute_host and agbnp_hip_energy_host: forces == nullptr is the energy-only evaluation (nothing but the energy
 // travels back)
 int host_evaluation(agbnp_hip_context* c, const double* pos, double* forces, double* energy) {
   const bool energy_only = forces == nullptr;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = sizeof(double) * 3 * (size_t)c->n;
-  if (c->unfinished) {
-    // The sticky overflow log is about to be read and cleared by this call's own harvest.  Evaluations that the caller
-    // has enqueued with agbnp_hip_execute_device and not yet finished must not lose their entries: they are harvested
-    // now and carried over to the caller's next agbnp_hip_finish.
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (void* st : c->user_streams) HIP_TRY(c, hipStreamSynchronize((hipStream_t)st));
-    int pending = 0;
-    int rc = harvest(c, &pending, c->stream);
-    if (rc != AGBNP_HIP_OK) return rc;
-    const int seq = c->last_device_seq;
-    for (int k : c->withheld) c->carried.push_back(k + c->carried_seq);
-    c->carried_count += pending;
-    c->carried_seq += seq;
-    c->unfinished = false;
-  }
+  int rc0 = carry_unfinished(c);
+  if (rc0 != AGBNP_HIP_OK) return rc0;
   const size_t n3 = 3 * (size_t)c->n;
   double* const d_energy = c->d_force_tmp.p + n3;  // forces and energy leave in one buffer: one clear, one copy back
   double* const h_in = c->h_xfer ? c->h_xfer : nullptr;
@@ -1539,6 +1591,254 @@ bool refuse_capture(agbnp_hip_context* c, hipStream_t st, const char* who) {
   return true;
 }
 }  // namespace
+
+namespace {
+// ---- replica groups (agbnp_hip_execute_group) -------------------------------------------------------------------------------
+// A member shares the launches of its launch set when its evaluation is exactly the default launch sequence: the five-launch
+// mode with the host-named set, the Reference semantics and (version 1) the FP64 row form, an LDS-resident capacity variant, the
+// forces leaving with the pseudo-volume launch, no diagnostics, no profiling.  Every other member runs its own launches.
+bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan) {
+  if (!c->cfg.group_launches || c->timeline.enabled || !energy_only_fast(c)) return false;
+  if (c->P.in.posq || c->P.omm.force_fixed || c->P.five != 1) return false;
+  return c->version == 0 || plan.fused;
+}
+
+bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
+
+// the arguments of a group call, checked before anything is launched or changed; d_outputs: device buffers of every member
+// (forces [3n], energy [1]) that must not overlap those of another member
+int check_group(agbnp_hip_context* const* ctxs, int count, const void* pos, const void* forces, const void* energies,
+                double* const* d_forces, double* const* d_energies, const char* who) {
+  if (!ctxs || count < 1 || count > kMaxGroup) {
+    if (ctxs && count >= 1 && ctxs[0]) ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a group has 1 to 16 members");
+    return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  }
+  for (int i = 0; i < count; i++)
+    if (!ctxs[i]) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  agbnp_hip_context* c0 = ctxs[0];
+  if (!pos || !forces || !energies) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  for (int i = 0; i < count; i++) {
+    if (ctxs[i]->device != c0->device) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": members on different devices");
+    for (int j = 0; j < i; j++)
+      if (ctxs[j] == ctxs[i]) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the same context twice");
+  }
+  if (!d_forces) return AGBNP_HIP_OK;
+  for (int i = 0; i < count; i++) {
+    if (!static_cast<const double* const*>(pos)[i] || !d_forces[i] || !d_energies[i])
+      return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    for (int j = 0; j < i; j++) {
+      const size_t ni = 3 * (size_t)ctxs[i]->n, nj = 3 * (size_t)ctxs[j]->n;
+      if (spans_overlap(d_forces[i], ni, d_forces[j], nj) || spans_overlap(d_forces[i], ni, d_energies[j], 1) ||
+          spans_overlap(d_energies[i], 1, d_forces[j], nj) || spans_overlap(d_energies[i], 1, d_energies[j], 1))
+        return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": output buffers of two members overlap");
+    }
+  }
+  return AGBNP_HIP_OK;
+}
+
+// One launch per stage for the members set[0..m) of a launch set (same version, capacity variant and far-strip test)
+int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, double* const* d_force,
+               double* const* d_energy, hipStream_t st) {
+  agbnp_hip_context* const c0 = ctxs[set[0]];
+  const int version = c0->version, variant = c0->variant;
+  const int stages = version == 1 ? 5 : 2;  // version 1: cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes; 0: cavity, outputs
+  GroupLaunch G[5];
+  GroupOutputs out;
+  std::memset(G, 0, sizeof(G));
+  std::memset(&out, 0, sizeof(out));
+  size_t lds[5] = {tree_variant_lds_bytes(variant), 0, 0, 0, tree_variant_replay_bytes(variant)};
+  for (int k = 0; k < m; k++) {
+    const int i = set[k];
+    agbnp_hip_context* const c = ctxs[i];
+    const EvalPlan& plan = plans[i];
+    if (version == 1) set_outputs(c, d_force[i], true);
+    GroupMemberArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.P = c->P;
+    a.T = c->T;
+    a.T.out.forest_blocks = plan.tree_grid;
+    a.T.out.force = nullptr;  // (the caller's outputs travel in the launch argument: the block stays what it was)
+    a.components = c->d_components.p;
+    a.tree_blocks = plan.tree_grid;
+    a.pseudo_blocks = version == 1 ? tree_pseudo_grid(variant, kGlobalGrid, plan.tree_grid, a.T) : 0;
+    const PairGroupShape sh = pair_group_shape(c->P, version);
+    a.born_role = sh.born_role;
+    a.chain_role = (int)sh.chain_lds;
+    a.out_role_bytes = sh.out_role_bytes;
+    a.out_mask_from = sh.out_mask_from;
+    // the block of this evaluation's set, rewritten in stream order where it changed
+    const int p = (c->five_evals - 1) & 1;
+    if (c->d_group.p == nullptr) HIP_TRY(c, c->d_group.alloc(2));
+    if (!c->group_valid[p] || std::memcmp(&c->group_written[p], &a, sizeof(a)) != 0) {
+      HIP_TRY(c, launch_group_put(a, c->d_group.p + p, st));
+      std::memcpy(&c->group_written[p], &a, sizeof(a));
+      c->group_valid[p] = true;
+    }
+    const unsigned long long addr = (unsigned long long)(uintptr_t)(c->d_group.p + p);
+    const int grid1[5] = {tree_five_grid(plan.tree_grid, c->P), sh.born_blocks, sh.gb_blocks, sh.chain_blocks, a.pseudo_blocks};
+    const int grid0[2] = {grid1[0], sh.out_blocks};
+    for (int s = 0; s < stages; s++) {
+      G[s].first[k + 1] = G[s].first[k] + (version == 1 ? grid1[s] : grid0[s]);
+      G[s].args[k] = addr;
+    }
+    out.force[k] = (unsigned long long)(uintptr_t)d_force[i];
+    out.energy[k] = (unsigned long long)(uintptr_t)d_energy[i];
+    if (version == 1) {
+      lds[1] = std::max(lds[1], sh.born_lds);
+      lds[3] = std::max(lds[3], sh.chain_lds);
+    } else {
+      lds[1] = std::max(lds[1], (size_t)sh.out_role_bytes);
+    }
+    c->group_members = m;
+  }
+  for (int s = 0; s < stages; s++) G[s].count = m;
+  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st));
+  if (version == 0) {
+    HIP_TRY(c0, launch_group_outputs(G[1], out, lds[1], st));
+    return AGBNP_HIP_OK;
+  }
+  HIP_TRY(c0, launch_group_born_rows(G[1], lds[1], st));
+  HIP_TRY(c0, launch_group_gb(c0->P.gb_far, G[2], st));
+  HIP_TRY(c0, launch_group_chain_rows(G[3], out, lds[3], st));
+  HIP_TRY(c0, launch_group_pseudo(variant, G[4], out, lds[4], st));
+  return AGBNP_HIP_OK;
+}
+
+// every member's evaluation on `st`: the per-evaluation host logic of each, then one launch per stage and launch set, then the
+// members that run alone.  When something fails, the members whose launches were not reached get back the counts their
+// enqueue_prepare advanced (enqueue index, five-launch set parity), so that host and device keep counting alike; a member whose
+// launches failed half-way is in the state a failed agbnp_hip_execute_device leaves (AGBNP_HIP_ERR_DEVICE: recreate it).
+int group_enqueue(agbnp_hip_context* const* ctxs, int count, const double* const* d_pos, double* const* d_force, double* const* d_energy,
+                  hipStream_t st) {
+  EvalPlan plans[kMaxGroup];
+  bool shares[kMaxGroup], done[kMaxGroup], launched[kMaxGroup] = {};
+  int was_enqueued[kMaxGroup], was_five_evals[kMaxGroup], prepared = 0;
+  auto undo = [&](int rc) {
+    for (int i = 0; i < prepared; i++)
+      if (!launched[i]) ctxs[i]->enqueued = was_enqueued[i], ctxs[i]->five_evals = was_five_evals[i];
+    return rc;
+  };
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    was_enqueued[i] = c->enqueued;
+    was_five_evals[i] = c->five_evals;
+    const int rc = enqueue_prepare(c, d_pos[i], st, plans[i]);
+    prepared = i + 1;
+    if (rc != AGBNP_HIP_OK) return undo(rc);
+    shares[i] = group_shares(c, plans[i]);
+    done[i] = !shares[i];
+  }
+  for (int i = 0; i < count; i++) {
+    if (done[i]) continue;
+    const agbnp_hip_context* a = ctxs[i];
+    int set[kMaxGroup], m = 0;
+    for (int j = i; j < count; j++) {
+      const agbnp_hip_context* b = ctxs[j];
+      if (!done[j] && b->version == a->version && b->variant == a->variant && b->P.gb_far == a->P.gb_far) set[m++] = j, done[j] = true;
+    }
+    for (int k = 0; k < m; k++) launched[set[k]] = true;
+    // (a launch set of one makes the member's own launches: the same kernels without the look-up of its argument block, which
+    // costs a dependent scalar load in front of every launch's first use of an argument)
+    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, d_force, d_energy, st)
+                         : enqueue_launch(ctxs[set[0]], plans[set[0]], d_force[set[0]], d_energy[set[0]], st, false);
+    if (rc != AGBNP_HIP_OK) return undo(rc);
+    if (m == 1) ctxs[set[0]]->group_members = 1;
+  }
+  for (int i = 0; i < count; i++) {
+    if (shares[i]) continue;
+    launched[i] = true;
+    const int rc = enqueue_launch(ctxs[i], plans[i], d_force[i], d_energy[i], st, false);
+    if (rc != AGBNP_HIP_OK) return undo(rc);
+  }
+  return AGBNP_HIP_OK;
+}
+
+// joins a member's own stream and the group's: `to` waits for what is on `from` now
+int join_streams(agbnp_hip_context* c, hipStream_t from, hipStream_t to) {
+  if (from == to) return AGBNP_HIP_OK;
+  if (!c->group_event) HIP_TRY(c, hipEventCreateWithFlags(&c->group_event, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->group_event, from));
+  HIP_TRY(c, hipStreamWaitEvent(to, c->group_event, 0));
+  return AGBNP_HIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,
+                            double* const* d_energies, void* stream) {
+  int rc = check_group(ctxs, count, d_positions, d_forces, d_energies, d_forces, d_energies, "agbnp_hip_execute_group");
+  if (rc != AGBNP_HIP_OK) return rc;
+  agbnp_hip_context* const c0 = ctxs[0];
+  HIP_TRY(c0, hipSetDevice(c0->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c0->stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_group: the stream is being captured; groups are not captured into graphs");
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    HIP_TRY(c, hipSetDevice(c->device));
+    // (NULL: the first member's own stream, which no caller can name -- it is not noted as a caller stream; every member's own
+    // stream is joined to it on both sides instead, so that the member's agbnp_hip_finish(NULL) drains the group's work)
+    note_stream(c, stream);
+    if (!stream) {
+      rc = join_streams(c, c->stream, st);
+      if (rc != AGBNP_HIP_OK) return rc;
+    }
+  }
+  rc = group_enqueue(ctxs, count, d_positions, d_forces, d_energies, st);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count && !stream; i++) {
+    rc = join_streams(ctxs[i], st, ctxs[i]->stream);
+    if (rc != AGBNP_HIP_OK) return rc;
+  }
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces,
+                                 double* energies) {
+  int rc = check_group(ctxs, count, positions, forces, energies, nullptr, nullptr, "agbnp_hip_execute_group_host");
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++)
+    if (!positions[i] || !forces[i]) return ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_group_host: null pointer");
+  agbnp_hip_context* const c0 = ctxs[0];
+  const hipStream_t st = c0->stream;
+  const double* d_pos[kMaxGroup];
+  double *d_force[kMaxGroup], *d_energy[kMaxGroup];
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = carry_unfinished(c);  // (every member's streams are idle from here on)
+    if (rc != AGBNP_HIP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
+    c->P.zero_out = c->d_force_tmp.p;  // (cleared by the cavity launch's trailing workgroups, as in agbnp_hip_execute_host)
+    d_pos[i] = c->d_pos_in.p;
+    d_force[i] = c->d_force_tmp.p;
+    d_energy[i] = c->d_force_tmp.p + 3 * (size_t)c->n;
+  }
+  rc = group_enqueue(ctxs, count, d_pos, d_force, d_energy, st);
+  for (int i = 0; i < count; i++) ctxs[i]->P.zero_out = nullptr;
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    int repeat = 0;
+    rc = harvest(c, &repeat, st);  // (waits for the group's stream)
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (repeat) {  // withheld: repeated alone, as agbnp_hip_execute_host repeats
+      rc = host_evaluation(c, positions[i], forces[i], &energies[i]);
+      if (rc != AGBNP_HIP_OK) return rc;
+      continue;
+    }
+    const size_t n3 = 3 * (size_t)c->n;
+    c->h_force_tmp.resize(n3 + 1);
+    HIP_TRY(c, hipMemcpy(c->h_force_tmp.data(), c->d_force_tmp.p, sizeof(double) * (n3 + 1), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n3; k++) forces[i][k] += c->h_force_tmp[k];
+    energies[i] = c->h_force_tmp[n3];
+  }
+  return AGBNP_HIP_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 
@@ -1601,6 +1901,10 @@ int agbnp_hip_get_scalar(agbnp_hip_context* c, int which, double* value) {
   }
   if (which == 18) {  // launches of an energy-only evaluation as the context runs now (0: it runs as a full evaluation)
     *value = energy_only_fast(c) ? (c->version == 1 ? 4 : 2) : 0;
+    return AGBNP_HIP_OK;
+  }
+  if (which == 19) {  // members of the launch set whose shared launches the last evaluation ran in (0: it ran alone)
+    *value = c->group_members;
     return AGBNP_HIP_OK;
   }
   if (which == 17) {  // forests healed inside the tree launch over the evaluations the last agbnp_hip_finish covered (none withheld for them)
@@ -1880,6 +2184,7 @@ void agbnp_hip_destroy(agbnp_hip_context* c) {
     (void)hipStreamDestroy(c->stream);
   }
   for (hipEvent_t e : c->timeline.events) (void)hipEventDestroy(e);
+  if (c->group_event) (void)hipEventDestroy(c->group_event);
   if (c->h_status) (void)hipHostFree(c->h_status);
   if (c->h_report) (void)hipHostFree(c->h_report);
   if (c->h_xfer) (void)hipHostFree(c->h_xfer);

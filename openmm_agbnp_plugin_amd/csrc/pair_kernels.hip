@@ -26,6 +26,7 @@
 #include "agbnp_common.h"
 #include "device_math.h"
 #include "pair_kernels.h"
+#include "group_args.h"
 #include "prep_role.h"
 
 namespace agbnp {
@@ -185,13 +186,16 @@ __device__ void neighbor_tile(const PairArgs& P, int tile, bool write_ref = fals
   }
 }
 
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 __global__ __launch_bounds__(256) void k_prep(PairArgs P, int prep_blocks) {
   if ((int)blockIdx.x >= prep_blocks) return neighbor_tile(P, blockIdx.x - prep_blocks);
   prep_atoms(P, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.x == 0, false);
 }
+#endif
 
 // five-launch mode: the neighbour masks alone (a launch of its own, only when the masks in hand have gone stale), and where
 // the heavy atoms are while they are laid down
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 __global__ __launch_bounds__(256) void k_masks(PairArgs P, int ref_blocks) {
   if ((int)blockIdx.x >= ref_blocks) return neighbor_tile(P, blockIdx.x - ref_blocks);
   const int h = blockIdx.x * blockDim.x + threadIdx.x;
@@ -201,6 +205,7 @@ __global__ __launch_bounds__(256) void k_masks(PairArgs P, int ref_blocks) {
   P.mask_ref[3 * h + 1] = r.y;
   P.mask_ref[3 * h + 2] = r.z;
 }
+#endif
 
 // ---- GB pairs, symmetric 64x64 tiles (all pairs, no cutoff) ------------------------------------------------
 // A workgroup of four waves owns one tile (I <= J).  In every wave lane l keeps atom i = 64 I + l and its sums in
@@ -1260,15 +1265,15 @@ __device__ __forceinline__ void gb_strip_f32(int n, int I0, int J, const double4
 // kEnergy: the instantiation of the energy-only evaluations (Reference mode, FP64; see gb_strip): the prologue (B, f', E_atom, brw)
 // and the pair energy partials, no direct force, no Y sums, no bw shares; workgroup 0 still does the packing role
 template <bool kCut, bool kSingle, bool kFar, bool kMasks = false, bool kEnergy = false>
-__global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__ items, const double4* __restrict__ aposq,
+AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ items, const double4* __restrict__ aposq,
                                                   const double* __restrict__ born_part, const double* __restrict__ inv_rvdw,
                                                   const double* __restrict__ alpha, double* __restrict__ born,
                                                   double* __restrict__ born_fp, double* __restrict__ brw,
                                                   double* __restrict__ e_atom, double* __restrict__ gb_rows,
-                                                  double* __restrict__ egb_part, PairArgs P) {
-  if (kMasks && (int)blockIdx.x > P.gb_items_count) {
+                                                  double* __restrict__ egb_part, PairArgs P AGBNP_WG_PARAM) {
+  if (kMasks && (int)AGBNP_WG > P.gb_items_count) {
     if (((P.estatus[kStatOrderStale] & 2) | P.estatus[kStatMaskAging]) == 0) return;
-    return neighbor_tile(P, (int)blockIdx.x - 1 - P.gb_items_count, true);
+    return neighbor_tile(P, (int)AGBNP_WG - 1 - P.gb_items_count, true);
   }
   // one LDS area, two lives: the atom records during the walk, the sums of the four waves after it
   __shared__ __align__(16) char s_area[sizeof(StripSums)];
@@ -1278,7 +1283,7 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
   // hides underneath this launch, the longest of the pair stages
   __shared__ double s_e[4];
   __shared__ int s_bmax[4];  // (kFar: the blocks' largest Born radii)
-  if (blockIdx.x == 0) {
+  if (AGBNP_WG == 0) {
     PAIR_STAMP(1, 0);
     rebase_for_parity(P, 0);
     packing_role<true>(P, s_area, (int)sizeof(StripSums));
@@ -1297,12 +1302,12 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
   // instructions without one: the former run at high priority, so that a workgroup that arrives beside three that are
   // walking gets its loads out at once instead of when the SIMD has nothing else to do (when it is too late to hide them).
   __builtin_amdgcn_s_setprio(3);
-  const int item = items[blockIdx.x - 1];
+  const int item = items[AGBNP_WG - 1];
   const int I = item & 0xfff, J = (item >> 12) & 0xfff;
   PAIR_STAMP(1, 0);
   if (item & kGbStripFlag) {
-    if (kSingle) return gb_strip_f32<kCut>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (blockIdx.x - 1), P, s_area, s_e);
-    return gb_strip<kCut, kFar, kEnergy>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (blockIdx.x - 1), P, s_area, s_e, s_bmax);
+    if (kSingle) return gb_strip_f32<kCut>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (AGBNP_WG - 1), P, s_area, s_e);
+    return gb_strip<kCut, kFar, kEnergy>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (AGBNP_WG - 1), P, s_area, s_e, s_bmax);
   }
   const bool diag = I == J;
   if (kCut && !diag) {  // fast mode: a tile whose two blocks are further apart than the cutoff has no pair to meet
@@ -1312,7 +1317,7 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
       gap2 += g * g;
     }
     if (gap2 >= P.gb_cut2) {
-      if (threadIdx.x == 0) egb_part[blockIdx.x - 1] = 0.0;
+      if (threadIdx.x == 0) egb_part[AGBNP_WG - 1] = 0.0;
       return;
     }
   }
@@ -1413,7 +1418,7 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
     e = wave_sum(e);
     if (lane == 0) s_e[wave] = e;
     __syncthreads();
-    if (threadIdx.x == 0) egb_part[blockIdx.x - 1] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
+    if (threadIdx.x == 0) egb_part[AGBNP_WG - 1] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
     return;
   }
   {
@@ -1435,7 +1440,7 @@ __global__ __launch_bounds__(256) void k_gb_tiles(int n, const int* __restrict__
     if (i < n) hbm_add(wave == 3 ? &P.ys[ysi] : &row[i], quantize(tile_sums_fold(s_sums, wave, lane), qs, det));
     if (j < n) hbm_add(wave == 3 ? &P.ys[ysj] : &row[j], quantize(tile_sums_fold(s_sums, 4 + wave, lane), qs, det));
   }
-  if (threadIdx.x == 0) egb_part[blockIdx.x - 1] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
+  if (threadIdx.x == 0) egb_part[AGBNP_WG - 1] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
   PAIR_STAMP(1, 3);
 }
 
@@ -1470,6 +1475,7 @@ __device__ __forceinline__ void born_walk(double& sum_i, double& sum_j, const do
   }
 }
 
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 __global__ __launch_bounds__(256) void k_born_tiles(int nh, int nhb, int ntj, int lut_entries, const int* __restrict__ items,
                                                    const int* __restrict__ pslot, const double* __restrict__ pbox,
                                                    const double4* __restrict__ prec, const double* __restrict__ sv_vdw,
@@ -1561,6 +1567,7 @@ __global__ __launch_bounds__(256) void k_born_tiles(int nh, int nhb, int ntj, in
     PAIR_STAMP(0, 3);
   }
 }
+#endif
 
 // ---- Born-radius chain rule, 64x64 tiles in "pair order" with range culling ------------------------------
 // Reference loop (ReferenceAGBNPKernels.cpp:555-586) over ordered (i, heavy j != i, d < 2 nm):
@@ -1617,6 +1624,7 @@ __device__ __forceinline__ void dborn_walk(DbornLane& L, const double2* __restri
   }
 }
 
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 __global__ __launch_bounds__(256) void k_dborn_tiles(int n, int nhb, int ntj, int lut_entries, const int* __restrict__ items,
                                                     const int* __restrict__ pslot, const double* __restrict__ pbox,
                                                     const double4* __restrict__ prec, const double4* __restrict__ srec,
@@ -1734,6 +1742,7 @@ __global__ __launch_bounds__(256) void k_dborn_tiles(int n, int nhb, int ntj, in
   if (aj >= 0 && (both || wave < 3)) hbm_add(&row[wave == 3 ? 64 * J + lane : aj], quantize(tile_sums_fold(s_sums, 4 + wave, lane), qs, det));
   PAIR_STAMP(2, 3);
 }
+#endif
 
 // ---- row form of the pair stages: the launches (device code in row_kernels.h) -----------------------------------------
 // (launch bounds: six waves per SIMD = three workgroups per CU, 80 vector registers; the GB rows, whose pair terms and
@@ -1747,10 +1756,10 @@ __global__ __launch_bounds__(256) void k_dborn_tiles(int n, int nhb, int ntj, in
 // DEVPAR: the evaluation's set of accumulators is named by the device's own count (PairArgs::five == 2, contexts that have
 // been captured into a graph); a launch of its own instantiation, so that eager launches carry no trace of it.
 template <int KIND, bool SINGLE = false, bool MASKS = false, bool DEVPAR = false>
-__global__ __launch_bounds__(64 * row_waves(KIND), KIND == kGbRows ? 4 : 6) void k_rows(PairArgs P, double* __restrict__ energy_out, double* __restrict__ components, int role_bytes) {
+AGBNP_KERNEL AGBNP_BOUNDS(64 * row_waves(KIND), KIND == kGbRows ? 4 : 6) void k_rows(PairArgs P, double* __restrict__ energy_out, double* __restrict__ components, int role_bytes AGBNP_WG_PARAM) {
   extern __shared__ double2 s_dyn[];
 
-  int blk = blockIdx.x;
+  int blk = AGBNP_WG;
   if (MASKS && KIND == kBornRows && blk >= role_bytes) {
     if (threadIdx.x >= 256) return;
     if (DEVPAR) rebase_for_parity(P, 0);
@@ -1787,12 +1796,12 @@ __global__ __launch_bounds__(64 * row_waves(KIND), KIND == kGbRows ? 4 : 6) void
 //   block  nfb       energy: fixed-order sum of every energy partial, ADDED to the caller's scalar
 //   block  nfb+1     bookkeeping for the NEXT evaluation: tree statistics and the largest-first subtree order
 
-__global__ __launch_bounds__(256) void k_outputs(PairArgs P, int version, double* __restrict__ force_out,
+AGBNP_KERNEL AGBNP_BOUNDS(256) void k_outputs(PairArgs P, int version, double* __restrict__ force_out,
                                                  double* __restrict__ energy_out, double* __restrict__ components, int role_bytes,
-                                                 int mask_from) {
+                                                 int mask_from AGBNP_WG_PARAM) {
   // version 0 has no pair stages to carry the two single-workgroup roles: they are the first two workgroups here
   extern __shared__ char s_role[];  // role_bytes when version != 1
-  int blk = blockIdx.x;
+  int blk = AGBNP_WG;
   if (mask_from >= 0 && blk >= mask_from) {
     // version 0 in the five-launch mode (round 6): the tiles that lay the level-2 neighbour masks down anew when this evaluation's
     // trailing workgroups found a heavy atom a quarter of the masks' skin from where it was (or beyond half: the evaluation is
@@ -1862,6 +1871,7 @@ __global__ __launch_bounds__(256) void k_outputs(PairArgs P, int version, double
 //   block 0  energy role (energy sum, sticky log, the host's window on it)
 //   block 1  dealing role (the next evaluation's packing into work slots), with the chain-rule launch's LDS: the same dealing
 //   block 2  rows_close_evaluation (one lane)
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 __global__ __launch_bounds__(256) void k_energy_roles(PairArgs P, double* __restrict__ energy_out, double* __restrict__ components,
                                                       int role_bytes) {
   extern __shared__ double2 s_dyn[];
@@ -1869,6 +1879,47 @@ __global__ __launch_bounds__(256) void k_energy_roles(PairArgs P, double* __rest
   if (blockIdx.x == 1) return dealing_role(P, reinterpret_cast<char*>(s_dyn), role_bytes);
   if (threadIdx.x == 0 && P.rows_on) rows_close_evaluation(P.nl_flag, P.nl_nitems, P.row_target, P.gb_rows != 0);
 }
+#endif
+
+#ifdef AGBNP_GROUP_TU
+// ---- replica groups (group_args.h): the pair-stage launches of several contexts in one grid ---------------------------------
+// The instantiations a sharing member launches alone: the five-launch mode's Born rows with their mask tiles, the Reference GB
+// tiles, the chain-rule rows; version 0's output launch with its role workgroups and mask tiles.
+__global__ __launch_bounds__(64 * kRowWaves, 6) void k_group_born_rows(GroupLaunch G) {
+  int blk;
+  const GroupMemberArgs& g = group_member(G, blk);
+  k_rows<kBornRows, false, true, false>(g.P, nullptr, nullptr, g.born_role, (unsigned)blk, 0u);
+}
+template <bool kFar>
+__global__ __launch_bounds__(256) void k_group_gb_tiles(GroupLaunch G) {
+  int blk;
+  const GroupMemberArgs& g = group_member(G, blk);
+  const PairArgs& P = g.P;
+  k_gb_tiles<false, false, kFar, false, false>(P.n, P.gb_items, (const double4*)P.aposq, (const double*)P.born_part, P.inv_rvdw, P.alpha, P.born,
+                                               P.born_fp, P.brw, P.e_atom, P.gb_fx, P.egb_part, P, (unsigned)blk, 0u);
+}
+__global__ __launch_bounds__(64 * kRowWaves, 6) void k_group_chain_rows(GroupLaunch G, GroupOutputs O) {
+  int blk;
+  const int m = group_index(G, blk);
+  const GroupMemberArgs& g = group_args(G, m);
+  k_rows<kChainRows, false, false, false>(g.P, reinterpret_cast<double*>(O.energy[m]), g.components, g.chain_role, (unsigned)blk, 0u);
+}
+__global__ __launch_bounds__(256) void k_group_outputs(GroupLaunch G, GroupOutputs O) {
+  int blk;
+  const int m = group_index(G, blk);
+  const GroupMemberArgs& g = group_args(G, m);
+  k_outputs(g.P, 0, reinterpret_cast<double*>(O.force[m]), reinterpret_cast<double*>(O.energy[m]), g.components, g.out_role_bytes,
+            g.out_mask_from, (unsigned)blk, 0u);
+}
+// a member's argument block, rewritten in stream order (the new block travels as this launch's argument)
+static_assert(sizeof(GroupMemberArgs) % 8 == 0 && sizeof(GroupMemberArgs) + 8 <= 4096, "the block travels as a kernel argument");
+__global__ __launch_bounds__(256) void k_group_put(GroupMemberArgs a, GroupMemberArgs* __restrict__ dst) {
+  const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&a);
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(dst);
+  for (int w = threadIdx.x; w < (int)(sizeof(GroupMemberArgs) / 8); w += 256) out[w] = src[w];
+}
+
+#endif  // AGBNP_GROUP_TU
 
 // ---- launchers -----------------------------------------------------------------------------------------
 #define AGBNP_CHECK_LAUNCH()             \
@@ -1885,6 +1936,7 @@ __global__ __launch_bounds__(256) void k_energy_roles(PairArgs P, double* __rest
     }                                                \
   } while (0)
 
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 hipError_t launch_masks(const PairArgs& P, hipStream_t st, Timeline* tl) {
   AGBNP_MARK(kKPrep);  // (booked as k_prep: it takes that launch's place in the evaluations that need it)
   const int ref_blocks = (std::max(P.nh, 1) + 255) / 256;
@@ -2032,9 +2084,68 @@ hipError_t launch_outputs(const PairArgs& P, int version, double* force_out, dou
   return hipSuccess;
 }
 
+// grids and LDS of a member's pair-stage launches as launch_pair_stages / launch_outputs size them (the five-launch mode with the
+// FP64 rows; version 0: the output launch with its mask tiles)
+PairGroupShape pair_group_shape(const PairArgs& P, int version) {
+  PairGroupShape g{};
+  const int born_groups = (P.n + kRowGroup - 1) / kRowGroup, chain_groups = (P.nh + kRowGroup - 1) / kRowGroup;
+  auto walk_blocks = [](int lists, int cap) { return (lists + kRowWaves - 1) / kRowWaves * ((cap + kRowSlice - 1) / kRowSlice); };
+  if (version == 1) {
+    const int born_blocks = walk_blocks(born_groups * kBornParts, P.nlh_cap), chain_blocks = walk_blocks(chain_groups * kChainParts, P.nla_cap);
+    const int build_blocks = (chain_groups * kChainParts + (P.gb_rows ? born_groups * kGbParts : 0) + kRowWaves - 1) / kRowWaves;
+    const size_t table_lds = (size_t)2 * P.nti * P.ntj * kRowIntervals * sizeof(double2);
+    g.born_role = born_blocks + build_blocks;
+    g.born_blocks = born_blocks + build_blocks + P.nb_tiles;
+    g.born_lds = table_lds;
+    g.gb_blocks = P.gb_items_count + 1;
+    g.chain_blocks = 2 + chain_blocks;
+    g.chain_lds = std::max(table_lds, sizeof(TileSums));
+    return g;
+  }
+  const int nh1 = std::max(P.nh, 1);
+  const int classes_ints = std::min(2 * nh1 + 64, 12288), rounds_ints = std::min(nh1 + P.tree_slots + nh1 + nh1 / 4 + 64, 14000);
+  g.out_role_bytes = (int)kRoleScratchBytes + 4 * std::max(classes_ints, rounds_ints);
+  g.out_mask_from = (P.n + 255) / 256 + 2;
+  g.out_blocks = g.out_mask_from + P.nb_tiles;
+  return g;
+}
+
+#endif  // !AGBNP_GROUP_TU
+
+#ifdef AGBNP_GROUP_TU
+hipError_t launch_group_born_rows(const GroupLaunch& G, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_born_rows, dim3(G.first[G.count]), dim3(64 * kRowWaves), lds, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_gb(int gb_far, const GroupLaunch& G, hipStream_t st) {
+  if (gb_far)
+    hipLaunchKernelGGL(k_group_gb_tiles<true>, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  else
+    hipLaunchKernelGGL(k_group_gb_tiles<false>, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_chain_rows(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_chain_rows, dim3(G.first[G.count]), dim3(64 * kRowWaves), lds, st, G, O);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_outputs(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_outputs, dim3(G.first[G.count]), dim3(256), lds, st, G, O);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_put(const GroupMemberArgs& a, GroupMemberArgs* dst, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_put, dim3(1), dim3(256), 0, st, a, dst);
+  return hipGetLastError();
+}
+
+#endif  // AGBNP_GROUP_TU
+
 }  // namespace agbnp
 
-#ifdef AGBNP_PAIR_STAMPS
+#if defined(AGBNP_PAIR_STAMPS) && !defined(AGBNP_GROUP_TU)
 extern "C" void agbnp_debug_pair_log(unsigned long long* out) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(agbnp::g_pair_log), sizeof(agbnp::g_pair_log));
 }

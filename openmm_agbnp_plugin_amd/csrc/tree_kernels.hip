@@ -2,6 +2,7 @@
 #include "tree_kernels.h"
 
 #include "pair_kernels.h"
+#include "group_args.h"
 #include "prep_role.h"
 #include "row_kernels.h"
 
@@ -115,10 +116,10 @@ constexpr int kPendCap = 16;  // work items that may wait while a forest that ou
 // FIVE: the five-launch mode's instantiation (k_tree_cavity_five below): positions straight from the caller's array.
 // POSQ: FIVE with the positions in an OpenMM context's posq (TreeArgs::posq; row_atoms holds slots)
 template <int NCAP, int ACAP, int BS, bool GLOBAL, bool SV1, bool FIVE, bool POSQ = false>
-__device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree_blocks) {  // tree_blocks: forest workgroups of the launch
+__device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree_blocks AGBNP_WG_PARAM) {  // tree_blocks: forest workgroups of the launch
   extern __shared__ __align__(16) char smem[];
   TreeStore<NCAP, ACAP> S;
-  S.carve(GLOBAL ? (A.scratch + (size_t)blockIdx.x * A.scratch_stride) : smem);
+  S.carve(GLOBAL ? (A.scratch + (size_t)AGBNP_WG * A.scratch_stride) : smem);
   __shared__ int s_next;  // hand-off word of the work queue (in LDS for every variant)
   // healing (below): work items of the slot's row that wait for another set, their number, and the work slot the set in hand
   // writes its topology to -- in LDS, not in registers: the build keeps ~190 scalar values live as it is
@@ -126,21 +127,21 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
   int& s_npend = s_pend[kPendCap];
   int& s_out = s_pend[kPendCap + 1];
   const int tid = threadIdx.x;
-  // the row of the workgroup's own work slot is requested before anything is waited for (blockIdx.x < slot_cap: the
+  // the row of the workgroup's own work slot is requested before anything is waited for (AGBNP_WG < slot_cap: the
   // row exists whether or not the slot is in use)
   int first_item = -1, first_atom = 0;
-  if ((tid & 63) < kMaxRoots) first_item = A.rows[(size_t)kRowStride * blockIdx.x + (tid & 63)];
-  if (FIVE && (tid & 63) < kMaxRoots) first_atom = A.row_atoms[(size_t)kMaxItems * blockIdx.x + (tid & 63)];
+  if ((tid & 63) < kMaxRoots) first_item = A.rows[(size_t)kRowStride * AGBNP_WG + (tid & 63)];
+  if (FIVE && (tid & 63) < kMaxRoots) first_atom = A.row_atoms[(size_t)kMaxItems * AGBNP_WG + (tid & 63)];
   const int nforests = min(A.nforests()[0], A.slot_cap);  // (never above the slots the per-slot arrays hold)
-  if (blockIdx.x == 0 && tid == 0) A.cur_nforests()[0] = nforests;
-  if ((int)blockIdx.x >= nforests && tid == 0) {  // an idle work slot: k_tree_pseudo's workgroup of the same slot finds nothing to replay
-    A.hdr[blockIdx.x].nnodes = 0;
-    A.hdr[blockIdx.x].natoms = 0;
+  if (AGBNP_WG == 0 && tid == 0) A.cur_nforests()[0] = nforests;
+  if ((int)AGBNP_WG >= nforests && tid == 0) {  // an idle work slot: k_tree_pseudo's workgroup of the same slot finds nothing to replay
+    A.hdr[AGBNP_WG].nnodes = 0;
+    A.hdr[AGBNP_WG].natoms = 0;
   }
 
   const bool queued = nforests > tree_blocks;  // otherwise every forest has a workgroup of its own
   const int lane = tid & 63;
-  for (int slot = blockIdx.x; slot < nforests;) {
+  for (int slot = AGBNP_WG; slot < nforests;) {
     constexpr int kNotAsked = 0x3fffffff;  // (a forest that fails before it asks ends the workgroup's run: the evaluation is void anyway)
     int ticket = kNotAsked;  // lane 0: the queue is asked for the forest after this one ONCE per slot, however many sets it takes
     // the slot's row of work items (written in slot order by the bookkeeping of the previous evaluation: no
@@ -148,7 +149,7 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
     // (-1 = no item.  Counting the items with a ballot instead of reading the row's count word out of lane 8 makes
     // k_tree_cavity 1.6 us faster on 1dwc, A/B on one box -- same spill counts, different register allocation.)
     int my_item = first_item, my_atom = first_atom;
-    if (slot != (int)blockIdx.x) {  // (a forest from the queue)
+    if (slot != (int)AGBNP_WG) {  // (a forest from the queue)
       // (the lane number through an opaque move: otherwise the compiler forms the per-lane row address at the kernel's head, keeps
       // it for this path alone and -- at the register limit -- parks it in scratch: 8 bytes of stores per lane and launch)
       int lane_q = lane;
@@ -381,10 +382,12 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
   }
 }
 
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 template <int NCAP, int ACAP, int BS, bool GLOBAL, bool SV1>
 __global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity(TreeArgs A) {
   cavity_forests<NCAP, ACAP, BS, GLOBAL, SV1, false>(A, (int)gridDim.x);
 }
+#endif
 
 // Five-launch mode (the default for version 1; engine.hip): there is no k_prep launch.  The forest workgroups read the caller's positions
 // themselves; the workgroups BEHIND them in the grid -- dispatched when the first forests have left, done long before the last
@@ -396,14 +399,14 @@ static_assert(kPrepHvGx == kHvGx && kPrepHvGx + 3 == kHvSvVdw && kPrepHvSvLarge 
 // float4 + correction) at the context's slots; the trailing workgroups read it through the same maps (prep_role.h) and check
 // every particle's entry against atomIndex (kStatOrderStale: the context has reordered its atoms, the evaluation is void)
 template <int NCAP, int ACAP, int BS, bool DEVPAR = false, bool POSQ = false>
-__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity_five(TreeArgs A, PairArgs P, int tree_blocks) {
-  if ((int)blockIdx.x >= tree_blocks) {
-    const int b = (int)blockIdx.x - tree_blocks;
+AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity_five(TreeArgs A, PairArgs P, int tree_blocks AGBNP_WG_PARAM) {
+  if ((int)AGBNP_WG >= tree_blocks) {
+    const int b = (int)AGBNP_WG - tree_blocks;
     if (DEVPAR) rebase_for_parity(P, 0);
     return prep_atoms(P, b * BS + (int)threadIdx.x, b == 0, true);
   }
   if (DEVPAR) rebase_tree_for_parity(A, 0);
-  cavity_forests<NCAP, ACAP, BS, false, false, true, POSQ>(A, tree_blocks);
+  cavity_forests<NCAP, ACAP, BS, false, false, true, POSQ>(A, tree_blocks AGBNP_WG_ARG);
 }
 
 // ---- the forces leave with the last tree launch (TreeOutputs) ------------------------------------------------------
@@ -463,7 +466,7 @@ __device__ __forceinline__ void outputs_role(const TreeArgs& A, int blk, int bs)
 // across the volume pass and spills one at the 128-register bound.  Launches whose forests fit one round (TreeOutputs::enabled:
 // the engine's own rule for fusing the forces) take the lean one; either handles any number of forests.
 template <int NCAP, int ACAP, int BS, bool GLOBAL, bool PIPE = true, bool DEVPAR = false>
-__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(TreeArgs A) {
+AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(TreeArgs A AGBNP_WG_PARAM) {
   if (DEVPAR) rebase_tree_for_parity(A, 1);  // (five-launch mode, device-side parity: the set of this evaluation; behind the GB launch, see pair_kernels.h)
   extern __shared__ __align__(16) char smem[];
   TreeStore<NCAP, ACAP> S;
@@ -471,10 +474,10 @@ __global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(T
   const int tid = threadIdx.x;
   // forest workgroups of the launch; the output workgroups come FIRST in the grid (they only need what earlier launches
   // left, and would otherwise wait for a forest workgroup to leave before they get a slot)
-  const int grid = A.out.enabled ? A.out.forest_blocks : (int)gridDim.x;
-  const int out_blocks = (int)gridDim.x - grid;
-  if ((int)blockIdx.x < out_blocks) return outputs_role(A, blockIdx.x, BS);
-  const int block = (int)blockIdx.x - out_blocks;  // number of the forest workgroup
+  const int grid = A.out.enabled ? A.out.forest_blocks : (int)AGBNP_NWG;
+  const int out_blocks = (int)AGBNP_NWG - grid;
+  if ((int)AGBNP_WG < out_blocks) return outputs_role(A, AGBNP_WG, BS);
+  const int block = (int)AGBNP_WG - out_blocks;  // number of the forest workgroup
   S.carve_replay(GLOBAL ? (A.scratch + (size_t)block * A.scratch_stride) : smem);
   const bool write_forces = A.out.enabled != 0;
   // forests to replay: those of the packing -- and, when k_tree_cavity healed a forest that had outgrown its store (it built the
@@ -746,7 +749,29 @@ __global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(T
   }
 }
 
-#ifdef AGBNP_STAMPS
+#ifdef AGBNP_GROUP_TU
+// ---- replica groups (group_args.h): the cavity and pseudo-volume launches of several contexts in one grid --------------------
+// The instantiations of the five-launch mode with the host-named set (eager launches) and, for the pseudo-volume launch, the
+// forces leaving with it: what a sharing member would launch alone.
+template <int NCAP, int ACAP, int BS>
+__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_group_cavity_five(GroupLaunch G) {
+  int blk;
+  const GroupMemberArgs& g = group_member(G, blk);
+  k_tree_cavity_five<NCAP, ACAP, BS, false, false>(g.T, g.P, g.tree_blocks, (unsigned)blk, 0u);
+}
+template <int NCAP, int ACAP, int BS, bool PIPE>
+__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_group_pseudo(GroupLaunch G, GroupOutputs O) {
+  int blk;
+  const int m = group_index(G, blk);
+  const GroupMemberArgs& g = group_args(G, m);
+  TreeArgs A = g.T;
+  A.out.force = reinterpret_cast<double*>(O.force[m]);  // (the caller's outputs travel with the launch)
+  k_tree_pseudo<NCAP, ACAP, BS, false, PIPE, false>(A, (unsigned)blk, (unsigned)g.pseudo_blocks);
+}
+
+#endif  // AGBNP_GROUP_TU
+
+#if defined(AGBNP_STAMPS) && !defined(AGBNP_GROUP_TU)
 extern "C" void agbnp_debug_stamps(unsigned long long* out, int reset) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 16);
   if (reset) {
@@ -779,6 +804,7 @@ static_assert(kBS <= kTreeBlock && kBS % 64 == 0, "tree block size");
 // LDS is handed out in granules of 1280 bytes on gfx950: five workgroups per CU need <= 25 granules each
 static_assert((TreeStore<432, 64>::kBytes + 16 + sizeof(int) * kPendCap + 1279) / 1280 * 5 <= 128, "five build workgroups per CU");
 static_assert((TreeStore<512, 64>::kBytes + 16 + sizeof(int) * kPendCap + 1279) / 1280 * 4 <= 128, "four build workgroups per CU");
+#ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
 size_t tree_variant_lds_bytes(int variant);
 int tree_variant_node_cap(int variant);
 // workgroups of the build kernel that a CU holds: LDS granules of 1280 B (128 per CU), 32 waves, the register budget
@@ -850,6 +876,26 @@ static hipError_t launch_five(K kernel, dim3 grid, size_t lds, const TreeArgs& A
   return hipGetLastError();
 }
 
+// workgroups of the five-launch mode's cavity launch: the forest workgroups, then the prep workgroups (replica groups lay the
+// grids of several contexts side by side, engine.hip)
+int tree_five_grid(int slots, const PairArgs& P) {
+  const int work = std::max(std::max(P.n, P.nslots), (int)kStatEvalWords);
+  return slots + (work + kBS - 1) / kBS;
+}
+int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A) {
+  const int forest_blocks = variant <= 3 ? slots : (global_grid < A.nh ? global_grid : A.nh);
+  return forest_blocks + (A.out.enabled ? (A.out.n + kBS - 1) / kBS : 0);
+}
+size_t tree_variant_replay_bytes(int variant) {
+  switch (variant) {
+    case 0: return TreeStore<432, 64>::kReplayBytes;
+    case 1: return TreeStore<512, 64>::kReplayBytes;
+    case 2: return TreeStore<1024, 128>::kReplayBytes;
+    case 3: return TreeStore<2048, 256>::kReplayBytes;
+    default: return 0;
+  }
+}
+
 // (round 6: every LDS variant -- rounds 5 left the mode for good at the first store beyond (512, 64))
 hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st) {
   if (A.nh <= 0 || variant > 3) return hipErrorInvalidValue;  // (the engine leaves the mode before it gets here)
@@ -900,5 +946,52 @@ hipError_t launch_tree_pseudo(int variant, int global_grid, int slots, const Tre
     default: return launch_tree(k_tree_pseudo<kGlobalNodeCap, kGlobalAtomCap, kBS, true>, grid, 0, A, st);
   }
 }
+
+#endif  // !AGBNP_GROUP_TU
+
+#ifdef AGBNP_GROUP_TU
+// replica groups: one launch per stage for every member of a launch set (engine.hip, agbnp_hip_execute_group)
+template <class K>
+static hipError_t launch_group(K kernel, const GroupLaunch& G, size_t lds, hipStream_t st) {
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(G.first[G.count]), dim3(kBS), lds, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st) {
+  switch (variant) {
+    case 0: return launch_group(k_group_cavity_five<432, 64, kBS>, G, lds, st);
+    case 1: return launch_group(k_group_cavity_five<512, 64, kBS>, G, lds, st);
+    case 2: return launch_group(k_group_cavity_five<1024, 128, kBS>, G, lds, st);
+    case 3: return launch_group(k_group_cavity_five<2048, 256, kBS>, G, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <class K>
+static hipError_t launch_group_out(K kernel, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(G.first[G.count]), dim3(kBS), lds, st, G, O);
+  return hipGetLastError();
+}
+
+// (the instantiation launch_tree_pseudo takes where the forces leave with the launch: the lean one up to 512 nodes)
+hipError_t launch_group_pseudo(int variant, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
+  switch (variant) {
+    case 0: return launch_group_out(k_group_pseudo<432, 64, kBS, false>, G, O, lds, st);
+    case 1: return launch_group_out(k_group_pseudo<512, 64, kBS, false>, G, O, lds, st);
+    case 2: return launch_group_out(k_group_pseudo<1024, 128, kBS, true>, G, O, lds, st);
+    case 3: return launch_group_out(k_group_pseudo<2048, 256, kBS, true>, G, O, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+#endif  // AGBNP_GROUP_TU
 
 }  // namespace agbnp

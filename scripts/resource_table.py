@@ -54,7 +54,7 @@ def main():
     tmp = args.keep_asm or tempfile.mkdtemp(prefix="agbnp_asm_")
     os.makedirs(tmp, exist_ok=True)
     allrows = {}
-    for src in ("tree_kernels.hip", "pair_kernels.hip", "engine.hip"):
+    for src in ("tree_kernels.hip", "pair_kernels.hip", "group_kernels.hip", "engine.hip"):
         if not os.path.exists(os.path.join(CSRC, src)):
             continue
         out = os.path.join(tmp, src.replace(".hip", ".s"))

@@ -1,0 +1,93 @@
+"""Replica groups (include/agbnp_hip.h: agbnp_hip_execute_group / _host) at the boundaries that need no device: the library exports
+them, the group bound is mirrored in Python, the Python wrappers check their lists before they touch the library, and the C++
+mirror compiles against the header."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import openmm_agbnp_plugin_amd as P
+from openmm_agbnp_plugin_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("agbnp_hip_execute_group", "agbnp_hip_execute_group_host")
+
+
+def test_the_group_entry_points_are_declared_and_exported():
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "agbnp_hip.h")).read()
+    for name in NEW:
+        assert name in _lib.SYMBOLS
+        assert f"int {name}(" in header
+        getattr(lib, name)
+
+
+def test_the_group_bound_is_mirrored():
+    header = open(os.path.join(ROOT, "include", "agbnp_hip.h")).read()
+    m = re.search(r"#define AGBNP_HIP_MAX_GROUP (\d+)", header)
+    assert m and int(m.group(1)) == _lib.MAX_GROUP == 16
+
+
+def test_a_null_group_is_an_invalid_argument():
+    lib = _lib.load()
+    assert lib.agbnp_hip_execute_group(None, 1, None, None, None, None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.agbnp_hip_execute_group_host(None, 1, None, None, None) == _lib.ERR_INVALID_ARGUMENT
+
+
+class _Fake(P.HipCalcAGBNPForceKernel):
+    """A kernel with a handle that must never reach the library."""
+
+    def __init__(self, n):
+        super().__init__(device=0)
+        self._h = 12345
+        self.numParticles = n
+
+
+@pytest.fixture()
+def no_library(monkeypatch):
+    def refuse():
+        raise AssertionError("the wrapper reached the library")
+    monkeypatch.setattr(_lib, "load", refuse)
+
+
+def test_execute_group_checks_its_lists_first(no_library):
+    ks = [_Fake(4), _Fake(4)]
+    with pytest.raises(P.OpenMMException):
+        P.execute_group([], [], [], [])
+    with pytest.raises(P.OpenMMException):
+        P.execute_group([_Fake(4) for _ in range(17)], [1] * 17, [1] * 17, [1] * 17)
+    with pytest.raises(P.OpenMMException):
+        P.execute_group(ks, [1, 2], [3], [4, 5])
+    with pytest.raises(P.OpenMMException):
+        P.execute_group(ks, [1, 2], [3, 4], [5])
+    with pytest.raises(P.OpenMMException):
+        P.execute_group([ks[0], "not a kernel"], [1, 2], [3, 4], [5, 6])
+    with pytest.raises(P.OpenMMException):
+        P.execute_group([P.HipCalcAGBNPForceKernel()], [1], [2], [3])  # (never initialised)
+
+
+def test_execute_group_host_checks_shapes_first(no_library):
+    ks = [_Fake(4), _Fake(5)]
+    pos = [np.zeros((4, 3)), np.zeros((5, 3))]
+    frc = [np.zeros((4, 3)), np.zeros((5, 3))]
+    with pytest.raises(P.OpenMMException):
+        P.execute_group_host(ks, pos[:1], frc)
+    with pytest.raises(P.OpenMMException):
+        P.execute_group_host(ks, [np.zeros((5, 3)), np.zeros((5, 3))], frc)
+    with pytest.raises(P.OpenMMException):
+        P.execute_group_host(ks, pos, [np.zeros((4, 3), dtype=np.float32), np.zeros((5, 3))])
+    with pytest.raises(P.OpenMMException):
+        P.execute_group_host(ks, pos, [np.zeros((4, 3)), np.zeros((3, 5)).T])
+
+
+def test_the_cpp_mirror_declares_execute_group():
+    subprocess.run(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-fsyntax-only",
+                    os.path.join(ROOT, "tests", "cxx", "TestHipReplicaGroup.cpp")], check=True)
+
+
+def test_scalar_19_is_named():
+    assert P.HipCalcAGBNPForceKernel.SCALARS["group_members"] == 19
+    header = open(os.path.join(ROOT, "include", "agbnp_hip.h")).read()
+    assert re.search(r"\b19 members of the launch set", header)
