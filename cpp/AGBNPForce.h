@@ -143,6 +143,33 @@ class HipCalcAGBNPForceKernel {
     return energies;
   }
 
+  // Energy-only replica groups (agbnp_hip_energy_group_host): the energy of every kernel in `kernels` at positions[i] (3N_i),
+  // on shared energy-only launches where the members allow it; no force is written anywhere.
+  static std::vector<double> energyGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,
+                                         const std::vector<std::vector<double>>& positions) {
+    const size_t n = kernels.size();
+    if (n < 1 || n > AGBNP_HIP_MAX_GROUP) throw OpenMMException("energyGroup(): a group has 1 to 16 members");
+    if (positions.size() != n) throw OpenMMException("energyGroup(): one position array per member");
+    std::vector<agbnp_hip_context*> ctxs(n);
+    std::vector<const double*> pos(n);
+    for (size_t i = 0; i < n; i++) {
+      if (!kernels[i] || !kernels[i]->ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+      if (positions[i].size() != 3 * (size_t)kernels[i]->numParticles) throw OpenMMException("energyGroup(): arrays must hold 3N values");
+      ctxs[i] = kernels[i]->ctx, pos[i] = positions[i].data();
+    }
+    std::vector<double> energies(n, 0.0);
+    if (agbnp_hip_energy_group_host(ctxs.data(), (int)n, pos.data(), energies.data()) != AGBNP_HIP_OK)
+      throw OpenMMException(agbnp_hip_last_error(ctxs[0]));
+    return energies;
+  }
+
+  // The positions of the next evaluation are unrelated to the last ones (agbnp_hip_expect_jump): it lays the neighbour masks
+  // down at its own positions first and is not withheld for the jump.
+  void expectJump() {
+    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+    if (agbnp_hip_expect_jump(ctx) != AGBNP_HIP_OK) throw OpenMMException(agbnp_hip_last_error(ctx));
+  }
+
   void copyParametersToContext(const AGBNPForce& force) {
     if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
     std::vector<double> r, g, a, q;

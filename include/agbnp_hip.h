@@ -189,6 +189,52 @@ int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const dou
 int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces,
                                  double* energies);
 
+/* Energy-only replica groups: the conjunction of agbnp_hip_energy_device() and agbnp_hip_execute_group(), for the energy
+ * matrices of replica exchange.  d_positions and d_energies are HOST arrays of `count` DEVICE pointers.  For every member i the
+ * call does exactly what agbnp_hip_energy_device(ctxs[i], d_positions[i], d_energies[i], stream) would do: the same energy
+ * ADDED to *d_energies[i], nothing written to any force buffer of any caller, the evaluation counted in THAT member's overflow
+ * log under its own enqueue index, and the member left in the state a full evaluation leaves (forest packing, neighbour masks
+ * and rows, healing counters, set parity) -- so agbnp_hip_finish(), _poll(), _wait_verdict(), _withheld_evaluations() and
+ * _generation() work per member, a withheld member does not affect the others, and energy groups, full groups and all
+ * single-context calls on the same contexts may be interleaved in any order.
+ * Arguments as for agbnp_hip_execute_group(): 1 .. AGBNP_HIP_MAX_GROUP distinct contexts on one device, no NULL pointer, the
+ * energy words of different members must not overlap (a contiguous array of `count` doubles, one per member, is fine);
+ * otherwise AGBNP_HIP_ERR_INVALID_ARGUMENT, nothing is launched and no member changes.  Position buffers MAY be shared between
+ * members (two Hamiltonians at one replica's positions): they are inputs.  A NULL `stream`, a caller stream and a device
+ * error half-way are handled as in agbnp_hip_execute_group().  Inside a stream capture the call is refused
+ * (AGBNP_HIP_ERR_INVALID_ARGUMENT, the capture stays usable).
+ * Launches.  A member SHARES under the conditions of agbnp_hip_execute_group() except the one on the forces (no pseudo-volume
+ * launch is made, so a system with more forests than one round of tree workgroups shares here): scalar 18 is not 0, the set is
+ * named by the host, the positions are the caller's FP64 array, no profiling, AGBNP_HIP_GROUP_LAUNCHES not 0.  Sharing members
+ * are split into launch sets by version, capacity variant and the GB far-strip test; a version-1 set is FOUR launches (cavity,
+ * Born rows, the GB tiles' energy-only form, three role workgroups per member), a version-0 set TWO (cavity, the output launch
+ * without force workgroups), whatever its size; a set of one makes the member's own energy-only launches.  Every other member
+ * runs what agbnp_hip_energy_device() runs for it on the same stream: correct, not faster.  Scalars 19 and 20 say how the last
+ * evaluation ran.
+ * Argument blocks.  Energy groups and full groups build the same block for a member's parity: a steady run that mixes the two
+ * kinds of call on the same members with fixed position buffers rewrites nothing (scalar 21 counts the rewrites). */
+int agbnp_hip_energy_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_energies,
+                           void* stream); /* ADDED to *d_energies[i]; asynchronous */
+/* The synchronous twin for host buffers: positions[i][3 n_i] read, energies[i] RETURNED.  Withheld members are repeated inside,
+ * alone, as agbnp_hip_energy_host() does. */
+int agbnp_hip_energy_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* energies);
+
+/* A hint: the positions of the NEXT evaluation of this context are unrelated to those of the last one (another replica's
+ * conformation in an exchange matrix, a restart, a Monte Carlo move).  In the five-launch mode the neighbour masks carry a skin,
+ * and a heavy atom that has moved more than 0.04 nm since they were laid down makes the evaluation a jump: withheld, reported
+ * as kind 16 by scalar 15, repeated by the caller.  After this call the next evaluation enqueued through ANY entry point
+ * (groups included: a member's one-off launches go in front of the shared ones) lays the masks down at its own positions first,
+ * with one small launch in front of it exactly as a fresh context's first evaluation does, and is therefore not withheld for
+ * the jump.  The hint is consumed by that evaluation.  It costs that one launch and no host synchronisation, and it does not
+ * change agbnp_hip_generation().  Where the context does not run the five-launch mode the masks are laid down at every
+ * evaluation anyway: the call returns AGBNP_HIP_OK and does nothing.  If the next evaluation is enqueued inside a stream
+ * capture the hint stays pending and nothing of it is captured (a captured mask launch would repeat at every replay).
+ * The hint only removes the jump verdict.  The evaluation can still be withheld through the usual protocol for a subtree
+ * that needs the next capacity variant, a forest packing that the new geometry outgrows, a neighbour row beyond its walk, or
+ * a reordered OpenMM context.  Nothing else needs telling: neighbour rows rebuild on the device by themselves and forests heal
+ * by themselves. */
+int agbnp_hip_expect_jump(agbnp_hip_context* ctx);
+
 /* Tells the engine that the contents of the d_atom_index array it last saw have changed (OpenMM has reordered its atoms):
  * the next agbnp_hip_execute_openmm() rebuilds its maps first, and no evaluation is lost to the check.  Optional -- without
  * it the first evaluation after a reorder is withheld and repeated, see above. */
@@ -288,6 +334,11 @@ int agbnp_hip_get_mode(const agbnp_hip_context* ctx);
              runs as a full evaluation with its forces sent to a buffer of the context's own
           19 members of the launch set of agbnp_hip_execute_group whose shared launches the context's last evaluation ran in
  *             (a group of one counts 1); 0 when it did not run through shared launches
+ *          20 last_evaluation_kind: how the last evaluation ENQUEUED on the context ran (valid without a completed evaluation,
+ *             like 18 and 19): 0 a full evaluation, 1 an energy-only evaluation on energy-only launches (alone or shared),
+ *             2 an energy-only request that ran as a full evaluation with its forces sent to the context's own buffer
+ *          21 group_block_writes: how often the context's group argument blocks have been rewritten so far (one small launch
+ *             each); it stands still in a steady run of group calls with fixed position buffers
           17 forests that outgrew their store and were healed inside the tree launch (built again in smaller sets: the
  *             evaluation is complete, nothing is withheld for them) over the evaluations the last agbnp_hip_finish() covered
  *          14 forest packings planned so far (a packing in use is planned anew every AGBNP_HIP_REPLAN_EVERY-th evaluation,

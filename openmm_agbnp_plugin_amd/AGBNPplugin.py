@@ -269,6 +269,16 @@ class HipCalcAGBNPForceKernel:
         self._need()
         _lib.load().agbnp_hip_atom_order_changed(self._h)
 
+    def expect_jump(self):
+        """A hint: the positions of the NEXT evaluation are unrelated to the last ones (another replica's conformation, a
+        restart).  That evaluation, through any entry point, lays the neighbour masks down at its own positions first -- one
+        small launch, no synchronisation -- and is not withheld for the jump.  Consumed by that evaluation; does nothing where
+        the context does not run the five-launch mode (include/agbnp_hip.h, agbnp_hip_expect_jump)."""
+        self._need()
+        rc = _lib.load().agbnp_hip_expect_jump(self._h)
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(self._h))
+
     def finish(self, stream=None):
         """Synchronise and read the device's overflow log: returns the number of evaluations enqueued since the
         previous finish() whose forces and energy were WITHHELD on the device (0 = all complete).  Those must be
@@ -326,7 +336,7 @@ class HipCalcAGBNPForceKernel:
             raise OpenMMException(_lib.last_error(self._h))
 
     # ---- diagnostics (test support) -------------------------------------------------------------
-    SCALARS = dict(e_vol1=0, e_vol2=1, e_atom=2, e_gb_pair=3, max_subtree_nodes=4, total_nodes=5, variant=6, max_local_atoms=7, forests=8, rows_on=9, row_builds=10, pack_level=11, pack_age=12, row_slice=13, pack_plans=14, overflow_kinds=15, launches=16, healed_forests=17, energy_only_launches=18, group_members=19)
+    SCALARS = dict(e_vol1=0, e_vol2=1, e_atom=2, e_gb_pair=3, max_subtree_nodes=4, total_nodes=5, variant=6, max_local_atoms=7, forests=8, rows_on=9, row_builds=10, pack_level=11, pack_age=12, row_slice=13, pack_plans=14, overflow_kinds=15, launches=16, healed_forests=17, energy_only_launches=18, group_members=19, last_evaluation_kind=20, group_block_writes=21)
     VECTORS = dict(selfvol_vdw=0, born=1, scale=2, selfvol_large=3, subtree_nodes=4, subtree_atoms=5)
 
     def scalar(self, name):
@@ -435,6 +445,44 @@ def execute_group_host(kernels, positions, forces):
     energies = np.zeros(n)
     rc = _lib.load().agbnp_hip_execute_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), (dpp * n)(*[_dp(f) for f in forces]),
                                                   _dp(energies))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(kernels[0]._h))
+    return [float(e) for e in energies]
+
+
+def energy_group(kernels, d_positions, d_energies, stream=None):
+    """Energy-only replica groups (include/agbnp_hip.h, agbnp_hip_energy_group): one call that enqueues an energy-only
+    evaluation of every kernel in `kernels`, with the launches of the members that can share them made once for all of them.
+    d_positions, d_energies: lists of raw FP64 device pointers (ints), one per member; position buffers may be shared between
+    members, the energy words must be distinct.  The energies are ADDED, as by each member's energy_device(); no force is
+    written.  Asynchronous; each member's finish() reports its own withheld evaluations."""
+    kernels, hs = _group_handles(kernels, "energy_group")
+    n = len(kernels)
+    for name, ptrs in (("d_positions", d_positions), ("d_energies", d_energies)):
+        if len(ptrs) != n:
+            raise OpenMMException(f"energy_group(): {name} has {len(ptrs)} entries for {n} members")
+    arr = lambda ptrs: (C.c_void_p * n)(*[int(p or 0) for p in ptrs])  # noqa: E731
+    rc = _lib.load().agbnp_hip_energy_group(hs, n, arr(d_positions), arr(d_energies), C.c_void_p(stream or 0))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(kernels[0]._h))
+
+
+def energy_group_host(kernels, positions):
+    """Synchronous twin of energy_group() for host buffers: positions[i] (N_i x 3) are read, the members' energies are
+    returned as a list.  Withheld members are repeated inside."""
+    kernels, hs = _group_handles(kernels, "energy_group_host")
+    n = len(kernels)
+    if len(positions) != n:
+        raise OpenMMException(f"energy_group_host(): {len(positions)} positions for {n} members")
+    pos = []
+    for k, p in zip(kernels, positions):
+        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+        if p.size != 3 * k.numParticles:
+            raise OpenMMException("energy_group_host(): wrong number of positions")
+        pos.append(p)
+    dpp = C.POINTER(C.c_double)
+    energies = np.zeros(n)
+    rc = _lib.load().agbnp_hip_energy_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), _dp(energies))
     if rc != _lib.OK:
         raise OpenMMException(_lib.last_error(kernels[0]._h))
     return [float(e) for e in energies]

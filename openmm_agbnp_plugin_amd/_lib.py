@@ -20,6 +20,7 @@ SYMBOLS = [
     "agbnp_hip_set_mode", "agbnp_hip_get_mode", "agbnp_hip_set_diagnostics", "agbnp_hip_set_profiling", "agbnp_hip_num_kernels", "agbnp_hip_kernel_name", "agbnp_hip_get_kernel_times",
     "agbnp_hip_energy_host", "agbnp_hip_energy_device", "agbnp_hip_energy_openmm",
     "agbnp_hip_execute_group", "agbnp_hip_execute_group_host",
+    "agbnp_hip_energy_group", "agbnp_hip_energy_group_host", "agbnp_hip_expect_jump",
 ]
 
 _lib = None
@@ -65,6 +66,9 @@ def load():
     lib.agbnp_hip_energy_openmm.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
     lib.agbnp_hip_execute_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
     lib.agbnp_hip_execute_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), C.POINTER(dp), dp]
+    lib.agbnp_hip_energy_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), vp]
+    lib.agbnp_hip_energy_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp]
+    lib.agbnp_hip_expect_jump.argtypes = [vp]
     lib.agbnp_hip_atom_order_changed.argtypes = [vp]
     lib.agbnp_hip_finish.argtypes = [vp, vp, ip]
     lib.agbnp_hip_poll.argtypes = [vp, ip, ip]

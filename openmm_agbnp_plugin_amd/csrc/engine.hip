@@ -285,6 +285,9 @@ struct agbnp_hip_context {
   bool group_valid[2] = {false, false};
   hipEvent_t group_event = nullptr;  // joins the context's own stream and a group's stream
   int group_members = 0;             // scalar 19: members of the launch set the last evaluation shared (0: it ran alone)
+  int group_block_writes = 0;        // scalar 21: k_group_put launches so far
+  int last_kind = 0;                 // scalar 20: 0 a full evaluation, 1 energy-only on energy-only launches, 2 energy-only run as a full one
+  bool jump_expected = false;        // agbnp_hip_expect_jump: the next evaluation lays the neighbour masks down at its own positions first
 
   int fail(int code, const std::string& msg) {
     err = msg;
@@ -1022,11 +1025,18 @@ int enqueue_prepare(agbnp_hip_context* c, const double* d_pos, hipStream_t st, E
       HIP_TRY(c, launch_row_atoms(c->slot_cap, c->d_rows.p, want_kind ? c->d_hslot.p : c->d_h2a.p, c->d_row_atoms.p, st));
       c->row_atoms_kind = want_kind;
     }
-    if (!c->masks_valid) {  // a fresh context, or an OpenMM context that has reordered its atoms (harvest): lay them down anew
+    bool jump = false;
+    if (c->jump_expected) {  // (agbnp_hip_expect_jump; inside a stream capture it stays pending: a captured mask launch would repeat at every replay)
+      hipStreamCaptureStatus capj = hipStreamCaptureStatusNone;
+      jump = !(hipStreamIsCapturing(st, &capj) == hipSuccess && capj != hipStreamCaptureStatusNone);
+    }
+    if (!c->masks_valid || jump) {  // a fresh context, an OpenMM context that has reordered its atoms (harvest), a jump the caller has announced: lay them down anew
       HIP_TRY(c, launch_masks(c->P, st, tl));
       c->masks_valid = true;
+      if (jump) c->jump_expected = false;
     }
   }
+  if (!c->five_active) c->jump_expected = false;  // (the k_prep path lays the masks down at every evaluation)
   if (c->version == 1) {
     // The forces leave with the pseudo-volume launch when that launch is one round of workgroups (1dwc: -1 us, A/B on one
     // box).  With more forests than resident workgroups a workgroup replays several forests in a row, and the next
@@ -1073,6 +1083,7 @@ void set_outputs(agbnp_hip_context* c, double* d_force, bool fused) {
 int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, double* d_force, double* d_energy, hipStream_t st, bool energy_only) {
   Timeline* tl = c->timeline.enabled ? &c->timeline : nullptr;
   const int tree_grid = plan.tree_grid;
+  c->last_kind = !energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
   if (c->five_active) {
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
     HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st));
@@ -1597,10 +1608,11 @@ namespace {
 // A member shares the launches of its launch set when its evaluation is exactly the default launch sequence: the five-launch
 // mode with the host-named set, the Reference semantics and (version 1) the FP64 row form, an LDS-resident capacity variant, the
 // forces leaving with the pseudo-volume launch, no diagnostics, no profiling.  Every other member runs its own launches.
-bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan) {
+// (An energy-only group makes no pseudo-volume launch: the condition on the forces does not apply there.)
+bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, bool energy_only) {
   if (!c->cfg.group_launches || c->timeline.enabled || !energy_only_fast(c)) return false;
   if (c->P.in.posq || c->P.omm.force_fixed || c->P.five != 1) return false;
-  return c->version == 0 || plan.fused;
+  return c->version == 0 || plan.fused || energy_only;
 }
 
 bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
@@ -1636,12 +1648,17 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const void* pos, cons
   return AGBNP_HIP_OK;
 }
 
-// One launch per stage for the members set[0..m) of a launch set (same version, capacity variant and far-strip test)
+// One launch per stage for the members set[0..m) of a launch set (same version, capacity variant and far-strip test).
+// energy_only (agbnp_hip_energy_group; d_force is null): version 1 FOUR launches -- cavity, Born rows, the GB stage's energy-only
+// instantiation, the three role workgroups per member --, version 0 the cavity launch and the output launch in its force-less
+// shape.  Both kinds of call build the SAME argument block for a member's parity (the block holds no output pointer, and what
+// the energy-only launches read of it a full call fills too), so a run that mixes them rewrites nothing.
 int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, double* const* d_force,
-               double* const* d_energy, hipStream_t st) {
+               double* const* d_energy, hipStream_t st, bool energy_only) {
   agbnp_hip_context* const c0 = ctxs[set[0]];
   const int version = c0->version, variant = c0->variant;
-  const int stages = version == 1 ? 5 : 2;  // version 1: cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes; 0: cavity, outputs
+  // version 1: cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes (energy-only: cavity, Born rows, GB tiles, roles); 0: cavity, outputs
+  const int stages = version == 1 ? (energy_only ? 4 : 5) : 2;
   GroupLaunch G[5];
   GroupOutputs out;
   std::memset(G, 0, sizeof(G));
@@ -1651,7 +1668,7 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
     const int i = set[k];
     agbnp_hip_context* const c = ctxs[i];
     const EvalPlan& plan = plans[i];
-    if (version == 1) set_outputs(c, d_force[i], true);
+    if (version == 1) set_outputs(c, energy_only ? nullptr : d_force[i], true);  // (the block's copy carries no force pointer)
     GroupMemberArgs a;
     std::memset(&a, 0, sizeof(a));
     a.P = c->P;
@@ -1673,15 +1690,18 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       HIP_TRY(c, launch_group_put(a, c->d_group.p + p, st));
       std::memcpy(&c->group_written[p], &a, sizeof(a));
       c->group_valid[p] = true;
+      c->group_block_writes++;
     }
     const unsigned long long addr = (unsigned long long)(uintptr_t)(c->d_group.p + p);
     const int grid1[5] = {tree_five_grid(plan.tree_grid, c->P), sh.born_blocks, sh.gb_blocks, sh.chain_blocks, a.pseudo_blocks};
-    const int grid0[2] = {grid1[0], sh.out_blocks};
+    // (energy-only: three role workgroups in place of the chain-rule launch; version 0: two role workgroups and the mask tiles)
+    const int grid1e[4] = {grid1[0], sh.born_blocks, sh.gb_blocks, 3};
+    const int grid0[2] = {grid1[0], energy_only ? 2 + c->P.nb_tiles : sh.out_blocks};
     for (int s = 0; s < stages; s++) {
-      G[s].first[k + 1] = G[s].first[k] + (version == 1 ? grid1[s] : grid0[s]);
+      G[s].first[k + 1] = G[s].first[k] + (version == 1 ? (energy_only ? grid1e[s] : grid1[s]) : grid0[s]);
       G[s].args[k] = addr;
     }
-    out.force[k] = (unsigned long long)(uintptr_t)d_force[i];
+    out.force[k] = energy_only ? 0ull : (unsigned long long)(uintptr_t)d_force[i];
     out.energy[k] = (unsigned long long)(uintptr_t)d_energy[i];
     if (version == 1) {
       lds[1] = std::max(lds[1], sh.born_lds);
@@ -1690,14 +1710,23 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       lds[1] = std::max(lds[1], (size_t)sh.out_role_bytes);
     }
     c->group_members = m;
+    c->last_kind = energy_only ? 1 : 0;
   }
   for (int s = 0; s < stages; s++) G[s].count = m;
   HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st));
   if (version == 0) {
-    HIP_TRY(c0, launch_group_outputs(G[1], out, lds[1], st));
+    if (energy_only)
+      HIP_TRY(c0, launch_group_outputs_energy(G[1], out, lds[1], st));
+    else
+      HIP_TRY(c0, launch_group_outputs(G[1], out, lds[1], st));
     return AGBNP_HIP_OK;
   }
   HIP_TRY(c0, launch_group_born_rows(G[1], lds[1], st));
+  if (energy_only) {
+    HIP_TRY(c0, launch_group_gb_energy(c0->P.gb_far, G[2], st));
+    HIP_TRY(c0, launch_group_energy_roles(G[3], out, lds[3], st));
+    return AGBNP_HIP_OK;
+  }
   HIP_TRY(c0, launch_group_gb(c0->P.gb_far, G[2], st));
   HIP_TRY(c0, launch_group_chain_rows(G[3], out, lds[3], st));
   HIP_TRY(c0, launch_group_pseudo(variant, G[4], out, lds[4], st));
@@ -1708,8 +1737,10 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
 // members that run alone.  When something fails, the members whose launches were not reached get back the counts their
 // enqueue_prepare advanced (enqueue index, five-launch set parity), so that host and device keep counting alike; a member whose
 // launches failed half-way is in the state a failed agbnp_hip_execute_device leaves (AGBNP_HIP_ERR_DEVICE: recreate it).
+// energy_only (d_force is null): a member that does not share runs what agbnp_hip_energy_device runs for it.
 int group_enqueue(agbnp_hip_context* const* ctxs, int count, const double* const* d_pos, double* const* d_force, double* const* d_energy,
-                  hipStream_t st) {
+                  hipStream_t st, bool energy_only = false) {
+  auto own_force = [&](int i) { return energy_only ? ctxs[i]->d_eo_force.p : d_force[i]; };
   EvalPlan plans[kMaxGroup];
   bool shares[kMaxGroup], done[kMaxGroup], launched[kMaxGroup] = {};
   int was_enqueued[kMaxGroup], was_five_evals[kMaxGroup], prepared = 0;
@@ -1725,7 +1756,7 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const double* const
     const int rc = enqueue_prepare(c, d_pos[i], st, plans[i]);
     prepared = i + 1;
     if (rc != AGBNP_HIP_OK) return undo(rc);
-    shares[i] = group_shares(c, plans[i]);
+    shares[i] = group_shares(c, plans[i], energy_only);
     done[i] = !shares[i];
   }
   for (int i = 0; i < count; i++) {
@@ -1739,15 +1770,15 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const double* const
     for (int k = 0; k < m; k++) launched[set[k]] = true;
     // (a launch set of one makes the member's own launches: the same kernels without the look-up of its argument block, which
     // costs a dependent scalar load in front of every launch's first use of an argument)
-    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, d_force, d_energy, st)
-                         : enqueue_launch(ctxs[set[0]], plans[set[0]], d_force[set[0]], d_energy[set[0]], st, false);
+    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, d_force, d_energy, st, energy_only)
+                         : enqueue_launch(ctxs[set[0]], plans[set[0]], own_force(set[0]), d_energy[set[0]], st, energy_only);
     if (rc != AGBNP_HIP_OK) return undo(rc);
     if (m == 1) ctxs[set[0]]->group_members = 1;
   }
   for (int i = 0; i < count; i++) {
     if (shares[i]) continue;
     launched[i] = true;
-    const int rc = enqueue_launch(ctxs[i], plans[i], d_force[i], d_energy[i], st, false);
+    const int rc = enqueue_launch(ctxs[i], plans[i], own_force(i), d_energy[i], st, energy_only);
     if (rc != AGBNP_HIP_OK) return undo(rc);
   }
   return AGBNP_HIP_OK;
@@ -1838,6 +1869,86 @@ int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, cons
   return AGBNP_HIP_OK;
 }
 
+// The energy-only twin of agbnp_hip_execute_group: for every member what agbnp_hip_energy_device would do, the sharing members
+// on FOUR (version 0: two) launches per launch set (launch_set, energy_only).  Nothing is written to a force buffer of a caller.
+int agbnp_hip_energy_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_energies,
+                           void* stream) {
+  const char* who = "agbnp_hip_energy_group";
+  int rc = check_group(ctxs, count, d_positions, d_energies, d_energies, nullptr, nullptr, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  agbnp_hip_context* const c0 = ctxs[0];
+  for (int i = 0; i < count; i++) {
+    if (!d_positions[i] || !d_energies[i]) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    for (int j = 0; j < i; j++)
+      if (spans_overlap(d_energies[i], 1, d_energies[j], 1))
+        return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": energy words of two members overlap");
+  }
+  HIP_TRY(c0, hipSetDevice(c0->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c0->stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_group: the stream is being captured; groups and energy-only evaluations are not captured into graphs");
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    HIP_TRY(c, hipSetDevice(c->device));
+    note_stream(c, stream);  // (NULL: the first member's own stream, joined on both sides as in agbnp_hip_execute_group)
+    if (!stream) {
+      rc = join_streams(c, c->stream, st);
+      if (rc != AGBNP_HIP_OK) return rc;
+    }
+  }
+  rc = group_enqueue(ctxs, count, d_positions, nullptr, d_energies, st, true);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count && !stream; i++) {
+    rc = join_streams(ctxs[i], st, ctxs[i]->stream);
+    if (rc != AGBNP_HIP_OK) return rc;
+  }
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_energy_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* energies) {
+  int rc = check_group(ctxs, count, positions, energies, energies, nullptr, nullptr, "agbnp_hip_energy_group_host");
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++)
+    if (!positions[i]) return ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_group_host: null pointer");
+  agbnp_hip_context* const c0 = ctxs[0];
+  const hipStream_t st = c0->stream;
+  const double* d_pos[kMaxGroup];
+  double* d_energy[kMaxGroup];
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = carry_unfinished(c);  // (every member's streams are idle from here on)
+    if (rc != AGBNP_HIP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
+    c->P.zero_out = c->d_force_tmp.p;  // (the staging buffer's energy word is cleared with it, as in agbnp_hip_execute_group_host: the same block)
+    d_pos[i] = c->d_pos_in.p;
+    d_energy[i] = c->d_force_tmp.p + 3 * (size_t)c->n;
+  }
+  rc = group_enqueue(ctxs, count, d_pos, nullptr, d_energy, st, true);
+  for (int i = 0; i < count; i++) ctxs[i]->P.zero_out = nullptr;
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    int repeat = 0;
+    rc = harvest(c, &repeat, st);  // (waits for the group's stream)
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (repeat) {  // withheld: repeated alone, as agbnp_hip_energy_host repeats
+      rc = host_evaluation(c, positions[i], nullptr, &energies[i]);
+      if (rc != AGBNP_HIP_OK) return rc;
+      continue;
+    }
+    HIP_TRY(c, hipMemcpy(&energies[i], d_energy[i], sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_expect_jump(agbnp_hip_context* c) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (c->five_active) c->jump_expected = true;  // (elsewhere k_prep lays the masks down at every evaluation: nothing to do)
+  return AGBNP_HIP_OK;
+}
+
 }  // extern "C"
 
 extern "C" {
@@ -1905,6 +2016,14 @@ int agbnp_hip_get_scalar(agbnp_hip_context* c, int which, double* value) {
   }
   if (which == 19) {  // members of the launch set whose shared launches the last evaluation ran in (0: it ran alone)
     *value = c->group_members;
+    return AGBNP_HIP_OK;
+  }
+  if (which == 20) {  // how the last evaluation enqueued ran: 0 full, 1 energy-only launches, 2 an energy-only request run as a full evaluation
+    *value = c->last_kind;
+    return AGBNP_HIP_OK;
+  }
+  if (which == 21) {  // k_group_put launches so far: rewrites of the context's group argument blocks
+    *value = c->group_block_writes;
     return AGBNP_HIP_OK;
   }
   if (which == 17) {  // forests healed inside the tree launch over the evaluations the last agbnp_hip_finish covered (none withheld for them)

@@ -78,6 +78,10 @@ hipError_t launch_group_born_rows(const GroupLaunch& G, size_t lds, hipStream_t 
 hipError_t launch_group_gb(int gb_far, const GroupLaunch& G, hipStream_t st);
 hipError_t launch_group_chain_rows(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
 hipError_t launch_group_outputs(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
+// energy-only groups (agbnp_hip_energy_group): the launches behind the cavity and Born-rows launches, which are the full group's
+hipError_t launch_group_gb_energy(int gb_far, const GroupLaunch& G, hipStream_t st);
+hipError_t launch_group_energy_roles(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
+hipError_t launch_group_outputs_energy(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
 hipError_t launch_group_put(const GroupMemberArgs& a, GroupMemberArgs* dst, hipStream_t st);
 
 #ifdef __HIP_DEVICE_COMPILE__

@@ -1911,6 +1911,37 @@ __global__ __launch_bounds__(256) void k_group_outputs(GroupLaunch G, GroupOutpu
   k_outputs(g.P, 0, reinterpret_cast<double*>(O.force[m]), reinterpret_cast<double*>(O.energy[m]), g.components, g.out_role_bytes,
             g.out_mask_from, (unsigned)blk, 0u);
 }
+// ---- energy-only replica groups (agbnp_hip_energy_group): the launches behind the shared cavity and Born-rows launches ------
+// They read the members' argument blocks as the full group's launches do and nothing a full group call does not put there: the
+// roles' LDS bytes are those of the chain-rule launch (GroupMemberArgs::chain_role, as k_energy_roles takes them), the force-less
+// output launch of version 0 has its first mask tile behind its two role workgroups, and TreeOutputs is not read.
+// The GB stage's energy-only instantiation (the body launch_energy_only_stages launches for one context)
+template <bool kFar>
+__global__ __launch_bounds__(256) void k_group_gb_tiles_energy(GroupLaunch G) {
+  int blk;
+  const GroupMemberArgs& g = group_member(G, blk);
+  const PairArgs& P = g.P;
+  k_gb_tiles<false, false, kFar, false, true>(P.n, P.gb_items, (const double4*)P.aposq, (const double*)P.born_part, P.inv_rvdw, P.alpha, P.born,
+                                              P.born_fp, P.brw, P.e_atom, P.gb_fx, P.egb_part, P, (unsigned)blk, 0u);
+}
+// The close of a version-1 member's energy-only evaluation, three workgroups per member exactly as in k_energy_roles
+__global__ __launch_bounds__(256) void k_group_energy_roles(GroupLaunch G, GroupOutputs O) {
+  extern __shared__ double2 s_dyn[];
+  int blk;
+  const int m = group_index(G, blk);
+  const GroupMemberArgs& g = group_args(G, m);
+  const PairArgs& P = g.P;
+  if (blk == 0) return energy_role(P, 1, reinterpret_cast<double*>(O.energy[m]), g.components, reinterpret_cast<char*>(s_dyn));
+  if (blk == 1) return dealing_role(P, reinterpret_cast<char*>(s_dyn), g.chain_role);
+  if (threadIdx.x == 0 && P.rows_on) rows_close_evaluation(P.nl_flag, P.nl_nitems, P.row_target, P.gb_rows != 0);
+}
+// Version 0: the output launch in its force-less shape (two role workgroups, then the mask tiles)
+__global__ __launch_bounds__(256) void k_group_outputs_energy(GroupLaunch G, GroupOutputs O) {
+  int blk;
+  const int m = group_index(G, blk);
+  const GroupMemberArgs& g = group_args(G, m);
+  k_outputs(g.P, 0, nullptr, reinterpret_cast<double*>(O.energy[m]), g.components, g.out_role_bytes, 2, (unsigned)blk, 0u);
+}
 // a member's argument block, rewritten in stream order (the new block travels as this launch's argument)
 static_assert(sizeof(GroupMemberArgs) % 8 == 0 && sizeof(GroupMemberArgs) + 8 <= 4096, "the block travels as a kernel argument");
 __global__ __launch_bounds__(256) void k_group_put(GroupMemberArgs a, GroupMemberArgs* __restrict__ dst) {
@@ -2133,6 +2164,24 @@ hipError_t launch_group_chain_rows(const GroupLaunch& G, const GroupOutputs& O, 
 
 hipError_t launch_group_outputs(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
   hipLaunchKernelGGL(k_group_outputs, dim3(G.first[G.count]), dim3(256), lds, st, G, O);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_gb_energy(int gb_far, const GroupLaunch& G, hipStream_t st) {
+  if (gb_far)
+    hipLaunchKernelGGL(k_group_gb_tiles_energy<true>, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  else
+    hipLaunchKernelGGL(k_group_gb_tiles_energy<false>, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_energy_roles(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_energy_roles, dim3(G.first[G.count]), dim3(256), lds, st, G, O);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_outputs_energy(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_outputs_energy, dim3(G.first[G.count]), dim3(256), lds, st, G, O);
   return hipGetLastError();
 }
 
