@@ -3,12 +3,9 @@
 // Mirrors the life cycle of the reference's platform kernel
 // (platforms/reference/src/ReferenceAGBNPKernels.cpp): initialize() :58-137 -> agbnp_hip_create,
 // execute() :139-149 -> agbnp_hip_execute_{host,device}, copyParametersToContext() :1796-1815 ->
-// agbnp_hip_update_parameters.  All device work of one evaluation is enqueued on one stream:
-//
-//   k_prep -> k_tree_cavity -> [k_born_tiles -> k_gb_tiles -> k_dborn_tiles -> k_tree_pseudo] -> k_outputs
-//
-// (bracketed part only for version 1).  There is no CPU fallback: without a HIP device every entry
-// point that computes fails with AGBNP_HIP_ERR_DEVICE.
+// agbnp_hip_update_parameters.  All device work of one evaluation is enqueued on one stream (enqueue_launch; the replica
+// groups' shared launches: launch_set).  There is no CPU fallback: without a HIP device every entry point that computes fails
+// with AGBNP_HIP_ERR_DEVICE.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,20 +25,6 @@
 #include "i4_tables.h"
 #include "pair_kernels.h"
 #include "tree_kernels.h"
-
-namespace agbnp {
-size_t tree_variant_lds_bytes(int variant);
-size_t tree_variant_scratch_bytes(int variant);
-int tree_variant_node_cap(int variant);
-int tree_variant_atom_cap(int variant);
-int tree_variant_wgs_per_cu(int variant);
-hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
-hipError_t launch_tree_pseudo(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
-hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st);
-int tree_five_grid(int slots, const PairArgs& P);
-int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A);
-size_t tree_variant_replay_bytes(int variant);
-}  // namespace agbnp
 
 using namespace agbnp;
 
@@ -77,7 +60,7 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
-constexpr int kGlobalVariant = 4;  // tree_kernels.hip: 0 (432, 64), 1 (512, 64), 2 (1024, 128), 3 (2048, 256) in LDS, 4 in HBM scratch
+constexpr int kGlobalVariant = 4;  // the capacity variant whose store lives in HBM scratch (tree_kernels.hip, with_tree_variant: 0-3 in LDS)
 constexpr int kGlobalGrid = 256;  // persistent workgroups of the global-scratch variant
 
 // Engine settings from the environment, read once by agbnp_hip_create (a change takes effect in the next context).  "Used
@@ -154,7 +137,6 @@ struct agbnp_hip_context {
   I4TableSet lut;
   int variant = 0;
   hipStream_t stream = nullptr;
-  // second stream + fork/join events: the enlarged-radius cavity pass runs underneath the pair kernels
 
   // static device data
   DevBuf<int> d_a2h, d_h2a, d_status, d_order, d_ftime, d_rows, d_forest, d_pack_items, d_gb_items, d_db_items, d_pslot, d_ctx_slot;
@@ -956,6 +938,11 @@ bool energy_only_fast(const agbnp_hip_context* c) {
   return c->P.rows_on && !c->P.gb_rows && !c->P.single && !c->P.fast && !c->P.det;
 }
 
+bool is_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
+
 // What enqueue() decides before its launches (enqueue_prepare) and hands to them (enqueue_launch)
 struct EvalPlan {
   int tree_grid = 1;   // workgroups of the tree launches
@@ -985,11 +972,7 @@ int enqueue_prepare(agbnp_hip_context* c, const double* d_pos, hipStream_t st, E
     // single-precision rows of the fast mode -- stay in the mode with the host-named set: the masks' renewal rides at the tail of
     // the GB tile launch / of the single-precision Born rows; a stream capture ends the mode for them as well.)
     const bool host_set_only = c->version == 0 || !c->P.rows_on || c->P.single;
-    bool capturing = false;
-    if (host_set_only && !c->five_device) {
-      hipStreamCaptureStatus cap0 = hipStreamCaptureStatusNone;
-      capturing = hipStreamIsCapturing(st, &cap0) == hipSuccess && cap0 != hipStreamCaptureStatusNone;
-    }
+    const bool capturing = host_set_only && !c->five_device && is_capturing(st);
     if (c->variant > 3 || c->nh <= 0 || c->diagnostics || capturing || (host_set_only && c->five_device)) {
       c->five_active = false;
       c->parity = 0;
@@ -1001,8 +984,7 @@ int enqueue_prepare(agbnp_hip_context* c, const double* d_pos, hipStream_t st, E
   // fewer if there cannot be that many forests
   plan.tree_grid = std::max(1, std::min(c->slot_cap, c->tree_slots[c->variant]));
   if (c->five_active) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (!c->five_device && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+    if (!c->five_device && is_capturing(st)) {
       // a replayed graph freezes its kernel arguments: from here on the kernels take the evaluation's set from the device's own
       // count (which has kept step with the host's so far), for good -- the host cannot count replays
       c->five_device = true;
@@ -1025,11 +1007,8 @@ int enqueue_prepare(agbnp_hip_context* c, const double* d_pos, hipStream_t st, E
       HIP_TRY(c, launch_row_atoms(c->slot_cap, c->d_rows.p, want_kind ? c->d_hslot.p : c->d_h2a.p, c->d_row_atoms.p, st));
       c->row_atoms_kind = want_kind;
     }
-    bool jump = false;
-    if (c->jump_expected) {  // (agbnp_hip_expect_jump; inside a stream capture it stays pending: a captured mask launch would repeat at every replay)
-      hipStreamCaptureStatus capj = hipStreamCaptureStatusNone;
-      jump = !(hipStreamIsCapturing(st, &capj) == hipSuccess && capj != hipStreamCaptureStatusNone);
-    }
+    // (agbnp_hip_expect_jump; inside a stream capture it stays pending: a captured mask launch would repeat at every replay)
+    const bool jump = c->jump_expected && !is_capturing(st);
     if (!c->masks_valid || jump) {  // a fresh context, an OpenMM context that has reordered its atoms (harvest), a jump the caller has announced: lay them down anew
       HIP_TRY(c, launch_masks(c->P, st, tl));
       c->masks_valid = true;
@@ -1083,12 +1062,13 @@ void set_outputs(agbnp_hip_context* c, double* d_force, bool fused) {
 int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, double* d_force, double* d_energy, hipStream_t st, bool energy_only) {
   Timeline* tl = c->timeline.enabled ? &c->timeline : nullptr;
   const int tree_grid = plan.tree_grid;
+  const PairLaunchShape shape = pair_launch_shape(c->P, c->version);
   c->last_kind = !energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
   if (c->five_active) {
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
     HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st));
     if (energy_only && energy_only_fast(c)) {
-      HIP_TRY(c, launch_energy_only_stages(c->P, c->version, d_energy, c->d_components.p, st, tl));
+      HIP_TRY(c, launch_energy_only_stages(c->P, shape, c->version, d_energy, c->d_components.p, st, tl));
       return AGBNP_HIP_OK;
     }
   } else {
@@ -1097,7 +1077,7 @@ int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, double* d_force, 
     HIP_TRY(c, launch_tree_cavity(c->variant, kGlobalGrid, tree_grid, c->T, st));
   }
   if (c->version == 1) {
-    HIP_TRY(c, launch_pair_stages(c->P, d_energy, c->d_components.p, st, tl));
+    HIP_TRY(c, launch_pair_stages(c->P, shape, d_energy, c->d_components.p, st, tl));
     if (tl) HIP_TRY(c, tl->mark(kKTreePseudo, st));
     // the forces leave with the pseudo-volume launch itself (TreeOutputs, tree_kernels.h): no output launch (enqueue_prepare)
     const bool fused = plan.fused;
@@ -1108,7 +1088,8 @@ int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, double* d_force, 
       return AGBNP_HIP_OK;
     }
   }
-  HIP_TRY(c, launch_outputs(c->P, c->version, d_force, d_energy, c->d_components.p, st, tl, c->five_active && c->version == 0));
+  // (version 0 in the five-launch mode: the renewal of the level-2 neighbour masks rides at the tail of this launch)
+  HIP_TRY(c, launch_outputs(c->P, c->five_active && c->version == 0 ? shape.out_masks : shape.out, c->version, d_force, d_energy, c->d_components.p, st, tl));
   return AGBNP_HIP_OK;
 }
 
@@ -1434,6 +1415,18 @@ int agbnp_hip_execute_device(agbnp_hip_context* c, const double* d_pos, double* 
 }  // extern "C"
 
 namespace {
+// the argument check of agbnp_hip_execute_openmm and agbnp_hip_energy_openmm; d_output: the buffer the call must be given
+int check_openmm(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction, int padded_num_atoms,
+                 const void* d_output, int energy_slot, const char* who) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_posq || !d_output) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (padded_num_atoms < c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": padded atom count below the particle count");
+  if (posq_is_double && d_posq_correction)
+    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a position correction only exists beside float positions");
+  if (energy_slot < 0) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative energy slot");
+  return AGBNP_HIP_OK;
+}
+
 // agbnp_hip_execute_openmm and agbnp_hip_energy_openmm (energy_only: d_force_buffer is the context's own), arguments checked
 int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,
                                 const int* d_atom_index, int padded_num_atoms, long long* d_force_buffer, void* d_energy_buffer,
@@ -1479,12 +1472,8 @@ extern "C" {
 int agbnp_hip_execute_openmm(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,
                              const int* d_atom_index, int padded_num_atoms, long long* d_force_buffer, void* d_energy_buffer,
                              int energy_is_double, int energy_slot, void* stream) {
-  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!d_posq || !d_force_buffer) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: null pointer");
-  if (padded_num_atoms < c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: padded atom count below the particle count");
-  if (posq_is_double && d_posq_correction)
-    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: a position correction only exists beside float positions");
-  if (energy_slot < 0) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_openmm: negative energy slot");
+  const int rc = check_openmm(c, d_posq, posq_is_double, d_posq_correction, padded_num_atoms, d_force_buffer, energy_slot, "agbnp_hip_execute_openmm");
+  if (rc != AGBNP_HIP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   return agbnp_hip_execute_openmm_to(c, d_posq, posq_is_double, d_posq_correction, d_atom_index, padded_num_atoms, d_force_buffer,
@@ -1596,8 +1585,7 @@ int host_evaluation(agbnp_hip_context* c, const double* pos, double* forces, dou
 
 // the energy-only entry points launch nothing inside a stream capture (energy-only graphs are not supported)
 bool refuse_capture(agbnp_hip_context* c, hipStream_t st, const char* who) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap == hipStreamCaptureStatusNone) return false;
+  if (!is_capturing(st)) return false;
   c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream is being captured; energy-only evaluations cannot be captured into a graph (capture agbnp_hip_execute_device instead)");
   return true;
 }
@@ -1617,10 +1605,11 @@ bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, bool energy_
 
 bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
 
-// the arguments of a group call, checked before anything is launched or changed; d_outputs: device buffers of every member
-// (forces [3n], energy [1]) that must not overlap those of another member
-int check_group(agbnp_hip_context* const* ctxs, int count, const void* pos, const void* forces, const void* energies,
-                double* const* d_forces, double* const* d_energies, const char* who) {
+// The arguments of a group call, checked before anything is launched or changed.  forces is null for an energy-only call
+// (energy_only says that this was asked for).  d_energies: the device entry points' energy words, one buffer per member, which --
+// like the force buffers [3n] -- must not overlap those of another member; the host entry points pass null.
+int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* pos, double* const* forces, bool energy_only,
+                const void* energies, double* const* d_energies, const char* who) {
   if (!ctxs || count < 1 || count > kMaxGroup) {
     if (ctxs && count >= 1 && ctxs[0]) ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a group has 1 to 16 members");
     return AGBNP_HIP_ERR_INVALID_ARGUMENT;
@@ -1628,21 +1617,24 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const void* pos, cons
   for (int i = 0; i < count; i++)
     if (!ctxs[i]) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   agbnp_hip_context* c0 = ctxs[0];
-  if (!pos || !forces || !energies) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (!pos || (!forces && !energy_only) || !energies) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
   for (int i = 0; i < count; i++) {
     if (ctxs[i]->device != c0->device) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": members on different devices");
     for (int j = 0; j < i; j++)
       if (ctxs[j] == ctxs[i]) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the same context twice");
   }
-  if (!d_forces) return AGBNP_HIP_OK;
   for (int i = 0; i < count; i++) {
-    if (!static_cast<const double* const*>(pos)[i] || !d_forces[i] || !d_energies[i])
+    if (!pos[i] || (forces && !forces[i]) || (d_energies && !d_energies[i]))
       return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    for (int j = 0; j < i; j++) {
+    for (int j = 0; j < i && d_energies; j++) {
       const size_t ni = 3 * (size_t)ctxs[i]->n, nj = 3 * (size_t)ctxs[j]->n;
-      if (spans_overlap(d_forces[i], ni, d_forces[j], nj) || spans_overlap(d_forces[i], ni, d_energies[j], 1) ||
-          spans_overlap(d_energies[i], 1, d_forces[j], nj) || spans_overlap(d_energies[i], 1, d_energies[j], 1))
-        return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": output buffers of two members overlap");
+      bool clash = spans_overlap(d_energies[i], 1, d_energies[j], 1);
+      if (forces)
+        clash = clash || spans_overlap(forces[i], ni, forces[j], nj) || spans_overlap(forces[i], ni, d_energies[j], 1) ||
+                spans_overlap(d_energies[i], 1, forces[j], nj);
+      if (clash)
+        return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                        std::string(who) + (forces ? ": output buffers of two members overlap" : ": energy words of two members overlap"));
     }
   }
   return AGBNP_HIP_OK;
@@ -1654,7 +1646,8 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const void* pos, cons
 // shape.  Both kinds of call build the SAME argument block for a member's parity (the block holds no output pointer, and what
 // the energy-only launches read of it a full call fills too), so a run that mixes them rewrites nothing.
 int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, double* const* d_force,
-               double* const* d_energy, hipStream_t st, bool energy_only) {
+               double* const* d_energy, hipStream_t st) {
+  const bool energy_only = d_force == nullptr;
   agbnp_hip_context* const c0 = ctxs[set[0]];
   const int version = c0->version, variant = c0->variant;
   // version 1: cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes (energy-only: cavity, Born rows, GB tiles, roles); 0: cavity, outputs
@@ -1678,11 +1671,16 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
     a.components = c->d_components.p;
     a.tree_blocks = plan.tree_grid;
     a.pseudo_blocks = version == 1 ? tree_pseudo_grid(variant, kGlobalGrid, plan.tree_grid, a.T) : 0;
-    const PairGroupShape sh = pair_group_shape(c->P, version);
-    a.born_role = sh.born_role;
-    a.chain_role = (int)sh.chain_lds;
-    a.out_role_bytes = sh.out_role_bytes;
-    a.out_mask_from = sh.out_mask_from;
+    // the member's grids and LDS exactly as its own launches would take them (enqueue_launch): from pair_launch_shape and the
+    // tree_*_grid functions, which size those too
+    const PairLaunchShape sh = pair_launch_shape(c->P, version);
+    if (version == 1) {
+      a.born_role = sh.born_mask_from;
+      a.chain_role = (int)sh.chain_lds;
+    } else {
+      a.out_role_bytes = sh.out_masks.role_bytes;
+      a.out_mask_from = sh.out_masks.mask_from;
+    }
     // the block of this evaluation's set, rewritten in stream order where it changed
     const int p = (c->five_evals - 1) & 1;
     if (c->d_group.p == nullptr) HIP_TRY(c, c->d_group.alloc(2));
@@ -1693,12 +1691,12 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       c->group_block_writes++;
     }
     const unsigned long long addr = (unsigned long long)(uintptr_t)(c->d_group.p + p);
-    const int grid1[5] = {tree_five_grid(plan.tree_grid, c->P), sh.born_blocks, sh.gb_blocks, sh.chain_blocks, a.pseudo_blocks};
-    // (energy-only: three role workgroups in place of the chain-rule launch; version 0: two role workgroups and the mask tiles)
-    const int grid1e[4] = {grid1[0], sh.born_blocks, sh.gb_blocks, 3};
-    const int grid0[2] = {grid1[0], energy_only ? 2 + c->P.nb_tiles : sh.out_blocks};
+    // (energy-only: the roles launch in place of the chain-rule launch; version 0: the output launch in its force-less shape)
+    const int cavity_blocks = tree_five_grid(plan.tree_grid, c->P);
+    const int grid1[5] = {cavity_blocks, sh.born_blocks, sh.gb_tile_blocks, energy_only ? sh.role_blocks : sh.chain_blocks, a.pseudo_blocks};
+    const int grid0[2] = {cavity_blocks, energy_only ? sh.out_energy.blocks : sh.out_masks.blocks};
     for (int s = 0; s < stages; s++) {
-      G[s].first[k + 1] = G[s].first[k] + (version == 1 ? (energy_only ? grid1e[s] : grid1[s]) : grid0[s]);
+      G[s].first[k + 1] = G[s].first[k] + (version == 1 ? grid1[s] : grid0[s]);
       G[s].args[k] = addr;
     }
     out.force[k] = energy_only ? 0ull : (unsigned long long)(uintptr_t)d_force[i];
@@ -1707,7 +1705,7 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       lds[1] = std::max(lds[1], sh.born_lds);
       lds[3] = std::max(lds[3], sh.chain_lds);
     } else {
-      lds[1] = std::max(lds[1], (size_t)sh.out_role_bytes);
+      lds[1] = std::max(lds[1], (size_t)sh.out_masks.role_bytes);
     }
     c->group_members = m;
     c->last_kind = energy_only ? 1 : 0;
@@ -1739,7 +1737,8 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
 // launches failed half-way is in the state a failed agbnp_hip_execute_device leaves (AGBNP_HIP_ERR_DEVICE: recreate it).
 // energy_only (d_force is null): a member that does not share runs what agbnp_hip_energy_device runs for it.
 int group_enqueue(agbnp_hip_context* const* ctxs, int count, const double* const* d_pos, double* const* d_force, double* const* d_energy,
-                  hipStream_t st, bool energy_only = false) {
+                  hipStream_t st) {
+  const bool energy_only = d_force == nullptr;
   auto own_force = [&](int i) { return energy_only ? ctxs[i]->d_eo_force.p : d_force[i]; };
   EvalPlan plans[kMaxGroup];
   bool shares[kMaxGroup], done[kMaxGroup], launched[kMaxGroup] = {};
@@ -1770,7 +1769,7 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const double* const
     for (int k = 0; k < m; k++) launched[set[k]] = true;
     // (a launch set of one makes the member's own launches: the same kernels without the look-up of its argument block, which
     // costs a dependent scalar load in front of every launch's first use of an argument)
-    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, d_force, d_energy, st, energy_only)
+    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, d_force, d_energy, st)
                          : enqueue_launch(ctxs[set[0]], plans[set[0]], own_force(set[0]), d_energy[set[0]], st, energy_only);
     if (rc != AGBNP_HIP_OK) return undo(rc);
     if (m == 1) ctxs[set[0]]->group_members = 1;
@@ -1792,20 +1791,19 @@ int join_streams(agbnp_hip_context* c, hipStream_t from, hipStream_t to) {
   HIP_TRY(c, hipStreamWaitEvent(to, c->group_event, 0));
   return AGBNP_HIP_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,
-                            double* const* d_energies, void* stream) {
-  int rc = check_group(ctxs, count, d_positions, d_forces, d_energies, d_forces, d_energies, "agbnp_hip_execute_group");
+// agbnp_hip_execute_group and -- energy_only, d_forces null: for every member what agbnp_hip_energy_device would do, the sharing
+// members on FOUR (version 0: two) launches per launch set, nothing written to a force buffer of a caller -- agbnp_hip_energy_group
+int group_device(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces, bool energy_only,
+                 double* const* d_energies, void* stream, const char* who) {
+  int rc = check_group(ctxs, count, d_positions, d_forces, energy_only, d_energies, d_energies, who);
   if (rc != AGBNP_HIP_OK) return rc;
   agbnp_hip_context* const c0 = ctxs[0];
   HIP_TRY(c0, hipSetDevice(c0->device));
   hipStream_t st = stream ? (hipStream_t)stream : c0->stream;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_group: the stream is being captured; groups are not captured into graphs");
+  if (is_capturing(st))
+    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream is being captured; " +
+                                                        (energy_only ? "groups and energy-only evaluations" : "groups") + " are not captured into graphs");
   for (int i = 0; i < count; i++) {
     agbnp_hip_context* const c = ctxs[i];
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1826,14 +1824,12 @@ int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const dou
   return AGBNP_HIP_OK;
 }
 
-int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces,
-                                 double* energies) {
-  int rc = check_group(ctxs, count, positions, forces, energies, nullptr, nullptr, "agbnp_hip_execute_group_host");
+// agbnp_hip_execute_group_host and -- energy_only, forces null -- agbnp_hip_energy_group_host
+int group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces, bool energy_only,
+               double* energies, const char* who) {
+  int rc = check_group(ctxs, count, positions, forces, energy_only, energies, nullptr, who);
   if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count; i++)
-    if (!positions[i] || !forces[i]) return ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_execute_group_host: null pointer");
-  agbnp_hip_context* const c0 = ctxs[0];
-  const hipStream_t st = c0->stream;
+  const hipStream_t st = ctxs[0]->stream;
   const double* d_pos[kMaxGroup];
   double *d_force[kMaxGroup], *d_energy[kMaxGroup];
   for (int i = 0; i < count; i++) {
@@ -1842,12 +1838,13 @@ int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, cons
     rc = carry_unfinished(c);  // (every member's streams are idle from here on)
     if (rc != AGBNP_HIP_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
-    c->P.zero_out = c->d_force_tmp.p;  // (cleared by the cavity launch's trailing workgroups, as in agbnp_hip_execute_host)
+    // (cleared by the cavity launch's trailing workgroups, as in agbnp_hip_execute_host; the staging buffer's energy word with it)
+    c->P.zero_out = c->d_force_tmp.p;
     d_pos[i] = c->d_pos_in.p;
     d_force[i] = c->d_force_tmp.p;
     d_energy[i] = c->d_force_tmp.p + 3 * (size_t)c->n;
   }
-  rc = group_enqueue(ctxs, count, d_pos, d_force, d_energy, st);
+  rc = group_enqueue(ctxs, count, d_pos, energy_only ? nullptr : d_force, d_energy, st);
   for (int i = 0; i < count; i++) ctxs[i]->P.zero_out = nullptr;
   if (rc != AGBNP_HIP_OK) return rc;
   for (int i = 0; i < count; i++) {
@@ -1855,9 +1852,13 @@ int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, cons
     int repeat = 0;
     rc = harvest(c, &repeat, st);  // (waits for the group's stream)
     if (rc != AGBNP_HIP_OK) return rc;
-    if (repeat) {  // withheld: repeated alone, as agbnp_hip_execute_host repeats
-      rc = host_evaluation(c, positions[i], forces[i], &energies[i]);
+    if (repeat) {  // withheld: repeated alone, as agbnp_hip_execute_host / agbnp_hip_energy_host repeats
+      rc = host_evaluation(c, positions[i], energy_only ? nullptr : forces[i], &energies[i]);
       if (rc != AGBNP_HIP_OK) return rc;
+      continue;
+    }
+    if (energy_only) {
+      HIP_TRY(c, hipMemcpy(&energies[i], d_energy[i], sizeof(double), hipMemcpyDeviceToHost));
       continue;
     }
     const size_t n3 = 3 * (size_t)c->n;
@@ -1868,79 +1869,27 @@ int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, cons
   }
   return AGBNP_HIP_OK;
 }
+}  // namespace
 
-// The energy-only twin of agbnp_hip_execute_group: for every member what agbnp_hip_energy_device would do, the sharing members
-// on FOUR (version 0: two) launches per launch set (launch_set, energy_only).  Nothing is written to a force buffer of a caller.
+extern "C" {
+
+int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,
+                            double* const* d_energies, void* stream) {
+  return group_device(ctxs, count, d_positions, d_forces, false, d_energies, stream, "agbnp_hip_execute_group");
+}
+
+int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces,
+                                 double* energies) {
+  return group_host(ctxs, count, positions, forces, false, energies, "agbnp_hip_execute_group_host");
+}
+
 int agbnp_hip_energy_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_energies,
                            void* stream) {
-  const char* who = "agbnp_hip_energy_group";
-  int rc = check_group(ctxs, count, d_positions, d_energies, d_energies, nullptr, nullptr, who);
-  if (rc != AGBNP_HIP_OK) return rc;
-  agbnp_hip_context* const c0 = ctxs[0];
-  for (int i = 0; i < count; i++) {
-    if (!d_positions[i] || !d_energies[i]) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    for (int j = 0; j < i; j++)
-      if (spans_overlap(d_energies[i], 1, d_energies[j], 1))
-        return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": energy words of two members overlap");
-  }
-  HIP_TRY(c0, hipSetDevice(c0->device));
-  hipStream_t st = stream ? (hipStream_t)stream : c0->stream;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_group: the stream is being captured; groups and energy-only evaluations are not captured into graphs");
-  for (int i = 0; i < count; i++) {
-    agbnp_hip_context* const c = ctxs[i];
-    HIP_TRY(c, hipSetDevice(c->device));
-    note_stream(c, stream);  // (NULL: the first member's own stream, joined on both sides as in agbnp_hip_execute_group)
-    if (!stream) {
-      rc = join_streams(c, c->stream, st);
-      if (rc != AGBNP_HIP_OK) return rc;
-    }
-  }
-  rc = group_enqueue(ctxs, count, d_positions, nullptr, d_energies, st, true);
-  if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count && !stream; i++) {
-    rc = join_streams(ctxs[i], st, ctxs[i]->stream);
-    if (rc != AGBNP_HIP_OK) return rc;
-  }
-  return AGBNP_HIP_OK;
+  return group_device(ctxs, count, d_positions, nullptr, true, d_energies, stream, "agbnp_hip_energy_group");
 }
 
 int agbnp_hip_energy_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* energies) {
-  int rc = check_group(ctxs, count, positions, energies, energies, nullptr, nullptr, "agbnp_hip_energy_group_host");
-  if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count; i++)
-    if (!positions[i]) return ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_group_host: null pointer");
-  agbnp_hip_context* const c0 = ctxs[0];
-  const hipStream_t st = c0->stream;
-  const double* d_pos[kMaxGroup];
-  double* d_energy[kMaxGroup];
-  for (int i = 0; i < count; i++) {
-    agbnp_hip_context* const c = ctxs[i];
-    HIP_TRY(c, hipSetDevice(c->device));
-    rc = carry_unfinished(c);  // (every member's streams are idle from here on)
-    if (rc != AGBNP_HIP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
-    c->P.zero_out = c->d_force_tmp.p;  // (the staging buffer's energy word is cleared with it, as in agbnp_hip_execute_group_host: the same block)
-    d_pos[i] = c->d_pos_in.p;
-    d_energy[i] = c->d_force_tmp.p + 3 * (size_t)c->n;
-  }
-  rc = group_enqueue(ctxs, count, d_pos, nullptr, d_energy, st, true);
-  for (int i = 0; i < count; i++) ctxs[i]->P.zero_out = nullptr;
-  if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count; i++) {
-    agbnp_hip_context* const c = ctxs[i];
-    int repeat = 0;
-    rc = harvest(c, &repeat, st);  // (waits for the group's stream)
-    if (rc != AGBNP_HIP_OK) return rc;
-    if (repeat) {  // withheld: repeated alone, as agbnp_hip_energy_host repeats
-      rc = host_evaluation(c, positions[i], nullptr, &energies[i]);
-      if (rc != AGBNP_HIP_OK) return rc;
-      continue;
-    }
-    HIP_TRY(c, hipMemcpy(&energies[i], d_energy[i], sizeof(double), hipMemcpyDeviceToHost));
-  }
-  return AGBNP_HIP_OK;
+  return group_host(ctxs, count, positions, nullptr, true, energies, "agbnp_hip_energy_group_host");
 }
 
 int agbnp_hip_expect_jump(agbnp_hip_context* c) {
@@ -1978,12 +1927,8 @@ int agbnp_hip_energy_device(agbnp_hip_context* c, const double* d_pos, double* d
 int agbnp_hip_energy_openmm(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,
                             const int* d_atom_index, int padded_num_atoms, void* d_energy_buffer, int energy_is_double,
                             int energy_slot, void* stream) {
-  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!d_posq || !d_energy_buffer) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: null pointer");
-  if (padded_num_atoms < c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: padded atom count below the particle count");
-  if (posq_is_double && d_posq_correction)
-    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: a position correction only exists beside float positions");
-  if (energy_slot < 0) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_openmm: negative energy slot");
+  const int rc = check_openmm(c, d_posq, posq_is_double, d_posq_correction, padded_num_atoms, d_energy_buffer, energy_slot, "agbnp_hip_energy_openmm");
+  if (rc != AGBNP_HIP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   if (refuse_capture(c, st, "agbnp_hip_energy_openmm")) return AGBNP_HIP_ERR_INVALID_ARGUMENT;

@@ -64,14 +64,6 @@ struct GroupOutputs {
   unsigned long long force[kMaxGroup], energy[kMaxGroup];
 };
 
-// a member's pair-stage launches as it would make them alone
-struct PairGroupShape {
-  int born_blocks, born_role, gb_blocks, chain_blocks;
-  size_t born_lds, chain_lds;
-  int out_blocks, out_role_bytes, out_mask_from;  // version 0
-};
-PairGroupShape pair_group_shape(const PairArgs& P, int version);
-
 hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st);
 hipError_t launch_group_pseudo(int variant, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
 hipError_t launch_group_born_rows(const GroupLaunch& G, size_t lds, hipStream_t st);

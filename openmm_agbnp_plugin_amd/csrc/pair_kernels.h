@@ -240,13 +240,32 @@ struct Timeline {
   }
 };
 
+// Grids (workgroups) and dynamic LDS of a context's pair-stage and output launches, from pair_launch_shape alone
+struct OutputShape {
+  int blocks, role_bytes, mask_from;  // workgroups of the launch, the roles' LDS bytes, the first mask tile (-1: none)
+};
+struct PairLaunchShape {
+  // row form (version 1).  Born rows: the workgroups that walk the lists, those that build the later launches' lists, then --
+  // five-launch mode -- the mask tiles; without them the launch ends at born_mask_from
+  int born_walk, born_build, born_mask_from, born_blocks;
+  size_t born_lds;
+  int gb_tile_blocks, gb_row_blocks;  // the GB stage by tiles / by rows (fast mode)
+  int chain_blocks;                   // chain-rule rows: two role workgroups, then the walk
+  size_t chain_lds;
+  int role_blocks;                    // the energy-only evaluation's roles launch (LDS: chain_lds)
+  // the output launch: as it is (version 1; version 0 with the k_prep launch), version 0 with the mask tiles at its tail, and
+  // version 0 energy-only (the two role workgroups and the mask tiles)
+  OutputShape out, out_masks, out_energy;
+};
+PairLaunchShape pair_launch_shape(const PairArgs& P, int version);
+
 hipError_t launch_prep(const PairArgs& P, hipStream_t st, Timeline* tl);
 hipError_t launch_masks(const PairArgs& P, hipStream_t st, Timeline* tl);  // five-launch mode: the neighbour masks alone (with their skin) + their reference positions
-hipError_t launch_pair_stages(const PairArgs& P, double* energy_out, double* components, hipStream_t st, Timeline* tl);
-// mask_tiles: version 0 in the five-launch mode -- the renewal of the level-2 neighbour masks rides at the tail of this launch
+hipError_t launch_pair_stages(const PairArgs& P, const PairLaunchShape& S, double* energy_out, double* components, hipStream_t st, Timeline* tl);
 // energy-only evaluations (engine.hip, agbnp_hip_energy_*): the launches behind the cavity launch, no force launch among them
-hipError_t launch_energy_only_stages(const PairArgs& P, int version, double* energy_out, double* components, hipStream_t st, Timeline* tl);
-hipError_t launch_outputs(const PairArgs& P, int version, double* force_out, double* energy_out, double* components, hipStream_t st,
-                          Timeline* tl, bool mask_tiles = false);
+hipError_t launch_energy_only_stages(const PairArgs& P, const PairLaunchShape& S, int version, double* energy_out, double* components,
+                                     hipStream_t st, Timeline* tl);
+hipError_t launch_outputs(const PairArgs& P, const OutputShape& O, int version, double* force_out, double* energy_out, double* components,
+                          hipStream_t st, Timeline* tl);
 
 }  // namespace agbnp

@@ -1983,7 +1983,37 @@ hipError_t launch_prep(const PairArgs& P, hipStream_t st, Timeline* tl) {
   return hipGetLastError();
 }
 
-hipError_t launch_pair_stages(const PairArgs& P, double* energy_out, double* components, hipStream_t st, Timeline* tl) {
+// Grids and LDS of a context's pair-stage and output launches.  Every launcher below and the replica groups' launch sets
+// (engine.hip, launch_set) take their numbers from here: a group kernel finds a member's role workgroups and mask tiles by the
+// workgroup's number inside the grid the member would launch alone (group_args.h), so the two must never be sized apart.
+PairLaunchShape pair_launch_shape(const PairArgs& P, int version) {
+  PairLaunchShape s{};
+  const int born_groups = (P.n + kRowGroup - 1) / kRowGroup, chain_groups = (P.nh + kRowGroup - 1) / kRowGroup;
+  auto walk_blocks = [](int lists, int waves, int cap) { return (lists + waves - 1) / waves * ((cap + kRowSlice - 1) / kRowSlice); };
+  s.born_walk = walk_blocks(born_groups * kBornParts, kRowWaves, P.nlh_cap);
+  // the lists of the later launches are built in the Born launch
+  s.born_build = (chain_groups * kChainParts + (P.gb_rows ? born_groups * kGbParts : 0) + kRowWaves - 1) / kRowWaves;
+  s.born_mask_from = s.born_walk + s.born_build;
+  s.born_blocks = s.born_mask_from + P.nb_tiles;
+  s.born_lds = (size_t)2 * P.nti * P.ntj * kRowIntervals * sizeof(double2);
+  s.gb_tile_blocks = P.gb_items_count + 1;
+  s.gb_row_blocks = 1 + walk_blocks(born_groups * kGbParts, kGbRowWaves, P.nlg_cap);
+  s.chain_blocks = 2 + walk_blocks(chain_groups * kChainParts, kRowWaves, P.nla_cap);  // (2: the energy and the dealing workgroup lead the launch)
+  s.chain_lds = std::max(s.born_lds, sizeof(TileSums));  // (>= what the two roles borrow)
+  s.role_blocks = 3;  // k_energy_roles: the energy role, the dealing role, the close of the rows' evaluation
+  // (version 0: the roles' LDS, with room for the packed shapes and as many forest times of up to 6 k subtrees -- or, where that
+  // is more, for the rounds rule of the packing: shapes, a round of running sums, the sorted order of ~1.25 items per subtree)
+  const int nh1 = std::max(P.nh, 1);
+  const int classes_ints = std::min(2 * nh1 + 64, 12288), rounds_ints = std::min(nh1 + P.tree_slots + nh1 + nh1 / 4 + 64, 14000);
+  const int role_bytes = version == 1 ? 0 : (int)kRoleScratchBytes + 4 * std::max(classes_ints, rounds_ints);
+  const int force_blocks = (P.n + 255) / 256 + (version == 1 ? 0 : 2);
+  s.out = {force_blocks, role_bytes, -1};
+  s.out_masks = {force_blocks + P.nb_tiles, role_bytes, force_blocks};
+  s.out_energy = {2 + P.nb_tiles, role_bytes, 2};
+  return s;
+}
+
+hipError_t launch_pair_stages(const PairArgs& P, const PairLaunchShape& S, double* energy_out, double* components, hipStream_t st, Timeline* tl) {
   const size_t lds = (size_t)P.lut_entries * sizeof(double2);
   if (lds > 32 * 1024) {  // beyond the default workgroup allowance (k_dborn_tiles adds 22 KB of static tile records and sums)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_born_tiles), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1993,45 +2023,35 @@ hipError_t launch_pair_stages(const PairArgs& P, double* energy_out, double* com
   }
   if (P.rows_on) {  // row form of the two range-limited stages (and, in fast mode, of the GB stage)
     auto gb = P.fast ? k_gb_tiles<true, false, false> : (P.gb_far ? k_gb_tiles<false, false, true> : k_gb_tiles<false, false, false>);
-    const int born_groups = (P.n + kRowGroup - 1) / kRowGroup, chain_groups = (P.nh + kRowGroup - 1) / kRowGroup;
-    auto walk_blocks = [](int lists, int cap) { return (lists + kRowWaves - 1) / kRowWaves * ((cap + kRowSlice - 1) / kRowSlice); };
-    const int born_blocks = walk_blocks(born_groups * kBornParts, P.nlh_cap), chain_blocks = walk_blocks(chain_groups * kChainParts, P.nla_cap);
-    const int gb_blocks = (born_groups * kGbParts + kGbRowWaves - 1) / kGbRowWaves * ((P.nlg_cap + kRowSlice - 1) / kRowSlice);
-    // the lists of the later launches are built in the Born launch
-    const int build_blocks = (chain_groups * kChainParts + (P.gb_rows ? born_groups * kGbParts : 0) + kRowWaves - 1) / kRowWaves;
-    const size_t table_lds = (size_t)2 * P.nti * P.ntj * kRowIntervals * sizeof(double2);
-    const size_t born_lds = table_lds, chain_lds = std::max(table_lds, sizeof(TileSums));  // (>= what the two roles borrow)
+    const dim3 rows(64 * kRowWaves);
     AGBNP_MARK(kKBornRows);
     if (P.single && P.five)  // (five-launch mode, the single-precision rows of the fast mode: + the conditional mask tiles; host-named set only)
-      hipLaunchKernelGGL((k_rows<kBornRows, true, true>), dim3(born_blocks + build_blocks + P.nb_tiles), dim3(64 * kRowWaves), born_lds, st, P, (double*)nullptr,
-                         (double*)nullptr, born_blocks + build_blocks);
+      hipLaunchKernelGGL((k_rows<kBornRows, true, true>), dim3(S.born_blocks), rows, S.born_lds, st, P, (double*)nullptr, (double*)nullptr, S.born_mask_from);
     else if (P.single)
-      hipLaunchKernelGGL((k_rows<kBornRows, true>), dim3(born_blocks + build_blocks), dim3(64 * kRowWaves), born_lds, st, P, (double*)nullptr, (double*)nullptr, 0);
+      hipLaunchKernelGGL((k_rows<kBornRows, true>), dim3(S.born_mask_from), rows, S.born_lds, st, P, (double*)nullptr, (double*)nullptr, 0);
     else if (P.five == 2)  // (five-launch mode, device-side parity: + the conditional mask tiles)
-      hipLaunchKernelGGL((k_rows<kBornRows, false, true, true>), dim3(born_blocks + build_blocks + P.nb_tiles), dim3(64 * kRowWaves), born_lds, st, P,
-                         (double*)nullptr, (double*)nullptr, born_blocks + build_blocks);
+      hipLaunchKernelGGL((k_rows<kBornRows, false, true, true>), dim3(S.born_blocks), rows, S.born_lds, st, P, (double*)nullptr, (double*)nullptr, S.born_mask_from);
     else if (P.five)  // (five-launch mode: + the conditional mask tiles)
-      hipLaunchKernelGGL((k_rows<kBornRows, false, true>), dim3(born_blocks + build_blocks + P.nb_tiles), dim3(64 * kRowWaves), born_lds, st, P, (double*)nullptr,
-                         (double*)nullptr, born_blocks + build_blocks);
+      hipLaunchKernelGGL((k_rows<kBornRows, false, true>), dim3(S.born_blocks), rows, S.born_lds, st, P, (double*)nullptr, (double*)nullptr, S.born_mask_from);
     else
-      hipLaunchKernelGGL(k_rows<kBornRows>, dim3(born_blocks + build_blocks), dim3(64 * kRowWaves), born_lds, st, P, (double*)nullptr, (double*)nullptr, 0);
+      hipLaunchKernelGGL(k_rows<kBornRows>, dim3(S.born_mask_from), rows, S.born_lds, st, P, (double*)nullptr, (double*)nullptr, 0);
     AGBNP_CHECK_LAUNCH();
     if (P.gb_rows) {
       AGBNP_MARK(kKGbRows);
-      hipLaunchKernelGGL(k_rows<kGbRows>, dim3(1 + gb_blocks), dim3(64 * kGbRowWaves), sizeof(StripSums), st, P, (double*)nullptr, (double*)nullptr, (int)sizeof(StripSums));
+      hipLaunchKernelGGL(k_rows<kGbRows>, dim3(S.gb_row_blocks), dim3(64 * kGbRowWaves), sizeof(StripSums), st, P, (double*)nullptr, (double*)nullptr, (int)sizeof(StripSums));
     } else {
       AGBNP_MARK(kKGbTiles);
-      hipLaunchKernelGGL(gb, dim3(P.gb_items_count + 1), dim3(256), 0, st, P.n, P.gb_items, (const double4*)P.aposq,
+      hipLaunchKernelGGL(gb, dim3(S.gb_tile_blocks), dim3(256), 0, st, P.n, P.gb_items, (const double4*)P.aposq,
                          (const double*)P.born_part, P.inv_rvdw, P.alpha, P.born, P.born_fp, P.brw, P.e_atom, P.gb_fx, P.egb_part, P);
     }
     AGBNP_CHECK_LAUNCH();
     AGBNP_MARK(kKDbornRows);
     if (P.single)
-      hipLaunchKernelGGL((k_rows<kChainRows, true>), dim3(2 + chain_blocks), dim3(64 * kRowWaves), chain_lds, st, P, energy_out, components, (int)chain_lds);
+      hipLaunchKernelGGL((k_rows<kChainRows, true>), dim3(S.chain_blocks), rows, S.chain_lds, st, P, energy_out, components, (int)S.chain_lds);
     else if (P.five == 2)
-      hipLaunchKernelGGL((k_rows<kChainRows, false, false, true>), dim3(2 + chain_blocks), dim3(64 * kRowWaves), chain_lds, st, P, energy_out, components, (int)chain_lds);
+      hipLaunchKernelGGL((k_rows<kChainRows, false, false, true>), dim3(S.chain_blocks), rows, S.chain_lds, st, P, energy_out, components, (int)S.chain_lds);
     else
-      hipLaunchKernelGGL(k_rows<kChainRows>, dim3(2 + chain_blocks), dim3(64 * kRowWaves), chain_lds, st, P, energy_out, components, (int)chain_lds);
+      hipLaunchKernelGGL(k_rows<kChainRows>, dim3(S.chain_blocks), rows, S.chain_lds, st, P, energy_out, components, (int)S.chain_lds);
     AGBNP_CHECK_LAUNCH();
     return hipSuccess;
   }
@@ -2063,82 +2083,33 @@ hipError_t launch_pair_stages(const PairArgs& P, double* energy_out, double* com
 // host-named set, Reference semantics, FP64 rows).  Version 1: the Born rows exactly as in a full evaluation (they also build the
 // chain-rule lists after a rebuild and carry the masks' renewal tiles), the GB stage's energy-only instantiation, k_energy_roles.
 // Version 0: the output launch's two role workgroups and its mask tiles, without force workgroups.
-hipError_t launch_energy_only_stages(const PairArgs& P, int version, double* energy_out, double* components, hipStream_t st,
-                                     Timeline* tl) {
-  if (version != 1) {
-    AGBNP_MARK(kKOutputs);
-    const int nh1 = std::max(P.nh, 1);  // (the roles' LDS as launch_outputs sizes it)
-    const int classes_ints = std::min(2 * nh1 + 64, 12288), rounds_ints = std::min(nh1 + P.tree_slots + nh1 + nh1 / 4 + 64, 14000);
-    const int role_bytes = (int)kRoleScratchBytes + 4 * std::max(classes_ints, rounds_ints);
-    hipLaunchKernelGGL(k_outputs, dim3(2 + P.nb_tiles), dim3(256), role_bytes, st, P, version, (double*)nullptr, energy_out, components,
-                       role_bytes, 2);
-    AGBNP_CHECK_LAUNCH();
-    AGBNP_MARK(-1);
-    return hipSuccess;
-  }
+hipError_t launch_energy_only_stages(const PairArgs& P, const PairLaunchShape& S, int version, double* energy_out, double* components,
+                                     hipStream_t st, Timeline* tl) {
+  if (version != 1) return launch_outputs(P, S.out_energy, version, nullptr, energy_out, components, st, tl);
   if (!P.rows_on || P.gb_rows || P.single || P.fast || P.det || P.five != 1) return hipErrorInvalidValue;  // (engine.hip never asks)
-  const int born_groups = (P.n + kRowGroup - 1) / kRowGroup, chain_groups = (P.nh + kRowGroup - 1) / kRowGroup;
-  auto walk_blocks = [](int lists, int cap) { return (lists + kRowWaves - 1) / kRowWaves * ((cap + kRowSlice - 1) / kRowSlice); };
-  const int born_blocks = walk_blocks(born_groups * kBornParts, P.nlh_cap);
-  const int build_blocks = (chain_groups * kChainParts + kRowWaves - 1) / kRowWaves;
-  const size_t table_lds = (size_t)2 * P.nti * P.ntj * kRowIntervals * sizeof(double2);
-  const size_t chain_lds = std::max(table_lds, sizeof(TileSums));
   AGBNP_MARK(kKBornRows);
-  hipLaunchKernelGGL((k_rows<kBornRows, false, true>), dim3(born_blocks + build_blocks + P.nb_tiles), dim3(64 * kRowWaves), table_lds, st, P,
-                     (double*)nullptr, (double*)nullptr, born_blocks + build_blocks);
+  hipLaunchKernelGGL((k_rows<kBornRows, false, true>), dim3(S.born_blocks), dim3(64 * kRowWaves), S.born_lds, st, P, (double*)nullptr, (double*)nullptr,
+                     S.born_mask_from);
   AGBNP_CHECK_LAUNCH();
   AGBNP_MARK(kKGbTiles);
   auto gb = P.gb_far ? k_gb_tiles<false, false, true, false, true> : k_gb_tiles<false, false, false, false, true>;
-  hipLaunchKernelGGL(gb, dim3(P.gb_items_count + 1), dim3(256), 0, st, P.n, P.gb_items, (const double4*)P.aposq, (const double*)P.born_part,
+  hipLaunchKernelGGL(gb, dim3(S.gb_tile_blocks), dim3(256), 0, st, P.n, P.gb_items, (const double4*)P.aposq, (const double*)P.born_part,
                      P.inv_rvdw, P.alpha, P.born, P.born_fp, P.brw, P.e_atom, P.gb_fx, P.egb_part, P);
   AGBNP_CHECK_LAUNCH();
   AGBNP_MARK(kKEnergyRoles);
-  hipLaunchKernelGGL(k_energy_roles, dim3(3), dim3(256), chain_lds, st, P, energy_out, components, (int)chain_lds);
+  hipLaunchKernelGGL(k_energy_roles, dim3(S.role_blocks), dim3(256), S.chain_lds, st, P, energy_out, components, (int)S.chain_lds);
   AGBNP_CHECK_LAUNCH();
   AGBNP_MARK(-1);
   return hipSuccess;
 }
 
-hipError_t launch_outputs(const PairArgs& P, int version, double* force_out, double* energy_out, double* components, hipStream_t st,
-                          Timeline* tl, bool mask_tiles) {
+hipError_t launch_outputs(const PairArgs& P, const OutputShape& O, int version, double* force_out, double* energy_out, double* components,
+                          hipStream_t st, Timeline* tl) {
   AGBNP_MARK(kKOutputs);
-  // (version 0: the roles' LDS, with room for the packed shapes and as many forest times of up to 6 k subtrees -- or, where that
-  // is more, for the rounds rule of the packing: shapes, a round of running sums, the sorted order of ~1.25 items per subtree)
-  const int nh1 = std::max(P.nh, 1);
-  const int classes_ints = std::min(2 * nh1 + 64, 12288), rounds_ints = std::min(nh1 + P.tree_slots + nh1 + nh1 / 4 + 64, 14000);
-  const int role_bytes = version == 1 ? 0 : (int)kRoleScratchBytes + 4 * std::max(classes_ints, rounds_ints);
-  const int blocks = (P.n + 255) / 256 + (version == 1 ? 0 : 2);
-  hipLaunchKernelGGL(k_outputs, dim3(blocks + (mask_tiles ? P.nb_tiles : 0)), dim3(256), role_bytes, st, P, version, force_out, energy_out, components, role_bytes,
-                     mask_tiles ? blocks : -1);
+  hipLaunchKernelGGL(k_outputs, dim3(O.blocks), dim3(256), O.role_bytes, st, P, version, force_out, energy_out, components, O.role_bytes, O.mask_from);
   AGBNP_CHECK_LAUNCH();
   AGBNP_MARK(-1);
   return hipSuccess;
-}
-
-// grids and LDS of a member's pair-stage launches as launch_pair_stages / launch_outputs size them (the five-launch mode with the
-// FP64 rows; version 0: the output launch with its mask tiles)
-PairGroupShape pair_group_shape(const PairArgs& P, int version) {
-  PairGroupShape g{};
-  const int born_groups = (P.n + kRowGroup - 1) / kRowGroup, chain_groups = (P.nh + kRowGroup - 1) / kRowGroup;
-  auto walk_blocks = [](int lists, int cap) { return (lists + kRowWaves - 1) / kRowWaves * ((cap + kRowSlice - 1) / kRowSlice); };
-  if (version == 1) {
-    const int born_blocks = walk_blocks(born_groups * kBornParts, P.nlh_cap), chain_blocks = walk_blocks(chain_groups * kChainParts, P.nla_cap);
-    const int build_blocks = (chain_groups * kChainParts + (P.gb_rows ? born_groups * kGbParts : 0) + kRowWaves - 1) / kRowWaves;
-    const size_t table_lds = (size_t)2 * P.nti * P.ntj * kRowIntervals * sizeof(double2);
-    g.born_role = born_blocks + build_blocks;
-    g.born_blocks = born_blocks + build_blocks + P.nb_tiles;
-    g.born_lds = table_lds;
-    g.gb_blocks = P.gb_items_count + 1;
-    g.chain_blocks = 2 + chain_blocks;
-    g.chain_lds = std::max(table_lds, sizeof(TileSums));
-    return g;
-  }
-  const int nh1 = std::max(P.nh, 1);
-  const int classes_ints = std::min(2 * nh1 + 64, 12288), rounds_ints = std::min(nh1 + P.tree_slots + nh1 + nh1 / 4 + 64, 14000);
-  g.out_role_bytes = (int)kRoleScratchBytes + 4 * std::max(classes_ints, rounds_ints);
-  g.out_mask_from = (P.n + 255) / 256 + 2;
-  g.out_blocks = g.out_mask_from + P.nb_tiles;
-  return g;
 }
 
 #endif  // !AGBNP_GROUP_TU

@@ -1293,4 +1293,18 @@ __device__ void root_gradients_from_invariance(const TreeStore<NCAP, ACAP>& S, i
   tree_barrier<NCAP>();
 }
 
+// ---- host side (tree_kernels.hip): the capacity variants and the launches of the tree stage ----
+size_t tree_variant_lds_bytes(int variant);      // the store's LDS in the cavity launch (0: the store lives in HBM scratch)
+size_t tree_variant_replay_bytes(int variant);   // ... in the pseudo-volume launch
+size_t tree_variant_scratch_bytes(int variant);  // the per-workgroup HBM slab of the global variant
+int tree_variant_node_cap(int variant);
+int tree_variant_atom_cap(int variant);
+int tree_variant_wgs_per_cu(int variant);
+// workgroups of the five-launch mode's cavity launch and of the pseudo-volume launch, as the launchers below make them
+int tree_five_grid(int slots, const PairArgs& P);
+int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A);
+hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
+hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st);
+hipError_t launch_tree_pseudo(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
+
 }  // namespace agbnp

@@ -795,18 +795,53 @@ extern "C" void agbnp_debug_stamps_max(unsigned long long* out, int reset) {
 #endif
 
 // ---- host-side launchers -------------------------------------------------------------------------
-// variant: 0 = (432 nodes, 64 local atoms) in LDS, five workgroups per CU; 1 = (512, 64), four; 2 = (1024, 128), two;
-// 3 = (2048, 256), one; 4 = (32768, 256) in a per-workgroup HBM slab
 constexpr int kGlobalNodeCap = 32768;
 constexpr int kGlobalAtomCap = 256;  // one byte per atom in the path words
 constexpr int kBS = 192;  // lanes per subtree
 static_assert(kBS <= kTreeBlock && kBS % 64 == 0, "tree block size");
+
+// The capacity variants, here and nowhere else: 0 = (432 nodes, 64 local atoms) in LDS, five workgroups per CU; 1 = (512, 64),
+// four; 2 = (1024, 128), two; 3 = (2048, 256), one; 4 = (32768, 256) in a per-workgroup HBM slab.  with_tree_variant hands the
+// variant's capacities to a callable as a type, so that a launcher names its kernel's instantiation from them.
+template <int NCAP, int ACAP, bool GLOBAL = false>
+struct TreeVariant {
+  static constexpr int kNodeCap = NCAP, kAtomCap = ACAP;
+  static constexpr bool kGlobal = GLOBAL;  // the store lives in HBM scratch: no LDS
+  static constexpr size_t kLdsBytes = GLOBAL ? 0 : TreeStore<NCAP, ACAP>::kBytes, kReplayBytes = GLOBAL ? 0 : TreeStore<NCAP, ACAP>::kReplayBytes;
+  static constexpr size_t kScratchBytes = GLOBAL ? (TreeStore<NCAP, ACAP>::kBytes + 255) / 256 * 256 : 0;
+};
+template <class F>
+static auto with_tree_variant(int variant, F&& f) {
+  switch (variant) {
+    case 0: return f(TreeVariant<432, 64>());
+    case 1: return f(TreeVariant<512, 64>());
+    case 2: return f(TreeVariant<1024, 128>());
+    case 3: return f(TreeVariant<2048, 256>());
+    default: return f(TreeVariant<kGlobalNodeCap, kGlobalAtomCap, true>());
+  }
+}
+// where the forces leave with the pseudo-volume launch (TreeOutputs): the lean k_tree_pseudo up to 512 nodes, the pipelined one
+// (which every launch without forces runs) above
+constexpr bool pseudo_forces_lean(int node_cap) { return node_cap <= 512; }
 // LDS is handed out in granules of 1280 bytes on gfx950: five workgroups per CU need <= 25 granules each
 static_assert((TreeStore<432, 64>::kBytes + 16 + sizeof(int) * kPendCap + 1279) / 1280 * 5 <= 128, "five build workgroups per CU");
 static_assert((TreeStore<512, 64>::kBytes + 16 + sizeof(int) * kPendCap + 1279) / 1280 * 4 <= 128, "four build workgroups per CU");
 #ifndef AGBNP_GROUP_TU  // (group_kernels.hip compiles this file again for the replica groups' kernels: group_args.h)
-size_t tree_variant_lds_bytes(int variant);
-int tree_variant_node_cap(int variant);
+size_t tree_variant_lds_bytes(int variant) {
+  return with_tree_variant(variant, [](auto v) { return decltype(v)::kLdsBytes; });
+}
+size_t tree_variant_replay_bytes(int variant) {
+  return with_tree_variant(variant, [](auto v) { return decltype(v)::kReplayBytes; });
+}
+size_t tree_variant_scratch_bytes(int variant) {
+  return with_tree_variant(variant, [](auto v) { return decltype(v)::kScratchBytes; });
+}
+int tree_variant_node_cap(int variant) {
+  return with_tree_variant(variant, [](auto v) { return decltype(v)::kNodeCap; });
+}
+int tree_variant_atom_cap(int variant) {
+  return with_tree_variant(variant, [](auto v) { return decltype(v)::kAtomCap; });
+}
 // workgroups of the build kernel that a CU holds: LDS granules of 1280 B (128 per CU), 32 waves, the register budget
 int tree_variant_wgs_per_cu(int variant) {
   const size_t bytes = tree_variant_lds_bytes(variant) + 16 + sizeof(int) * kPendCap;  // (+ the kernels' static LDS)
@@ -817,179 +852,118 @@ int tree_variant_wgs_per_cu(int variant) {
   return std::max(1, std::min(std::min(by_lds, by_regs), 32 / waves));
 }
 
-size_t tree_variant_lds_bytes(int variant) {
-  switch (variant) {
-    case 0: return TreeStore<432, 64>::kBytes;
-    case 1: return TreeStore<512, 64>::kBytes;
-    case 2: return TreeStore<1024, 128>::kBytes;
-    case 3: return TreeStore<2048, 256>::kBytes;
-    default: return 0;
-  }
-}
-size_t tree_variant_scratch_bytes(int variant) {
-  return variant == 4 ? ((TreeStore<kGlobalNodeCap, kGlobalAtomCap>::kBytes + 255) / 256) * 256 : 0;
-}
-int tree_variant_node_cap(int variant) {
-  static const int caps[5] = {432, 512, 1024, 2048, kGlobalNodeCap};
-  return caps[variant];
-}
-
-int tree_variant_atom_cap(int variant) {
-  static const int caps[5] = {64, 64, 128, 256, kGlobalAtomCap};
-  return caps[variant];
-}
-
-template <class K>
-static hipError_t launch_tree(K kernel, int grid, size_t lds, const TreeArgs& A, hipStream_t st) {
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBS), lds, st, A);
-  return hipGetLastError();
-}
-
-// slots: workgroups to launch = min(work slots that may be planned, workgroups the device keeps resident)
-hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st) {
-  if (A.nh <= 0) return hipSuccess;
-  const bool sv1 = A.want_sv_large != 0;  // (the diagnostic self volumes of pass 1: a kernel of their own)
-#define AGBNP_CAVITY(...) (sv1 ? launch_tree(k_tree_cavity<__VA_ARGS__, true>, grid, lds, A, st) : launch_tree(k_tree_cavity<__VA_ARGS__, false>, grid, lds, A, st))
-  int grid = slots;
-  size_t lds = 0;
-  switch (variant) {
-    case 0: lds = TreeStore<432, 64>::kBytes; return AGBNP_CAVITY(432, 64, kBS, false);
-    case 1: lds = TreeStore<512, 64>::kBytes; return AGBNP_CAVITY(512, 64, kBS, false);
-    case 2: lds = TreeStore<1024, 128>::kBytes; return AGBNP_CAVITY(1024, 128, kBS, false);
-    case 3: lds = TreeStore<2048, 256>::kBytes; return AGBNP_CAVITY(2048, 256, kBS, false);
-    default: grid = global_grid < A.nh ? global_grid : A.nh; return AGBNP_CAVITY(kGlobalNodeCap, kGlobalAtomCap, kBS, true);
-  }
-#undef AGBNP_CAVITY
-}
-
-template <class K>
-static hipError_t launch_five(K kernel, dim3 grid, size_t lds, const TreeArgs& A, const PairArgs& P, int slots, hipStream_t st) {
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, grid, dim3(kBS), lds, st, A, P, slots);
-  return hipGetLastError();
-}
-
 // workgroups of the five-launch mode's cavity launch: the forest workgroups, then the prep workgroups (replica groups lay the
 // grids of several contexts side by side, engine.hip)
 int tree_five_grid(int slots, const PairArgs& P) {
   const int work = std::max(std::max(P.n, P.nslots), (int)kStatEvalWords);
   return slots + (work + kBS - 1) / kBS;
 }
-int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A) {
-  const int forest_blocks = variant <= 3 ? slots : (global_grid < A.nh ? global_grid : A.nh);
-  return forest_blocks + (A.out.enabled ? (A.out.n + kBS - 1) / kBS : 0);
+// ... of the six-launch cavity launch and of the pseudo-volume launch's forest part.  slots: min(work slots that may be
+// planned, workgroups the device keeps resident)
+static int tree_forest_blocks(int variant, int global_grid, int slots, const TreeArgs& A) {
+  return variant <= 3 ? slots : (global_grid < A.nh ? global_grid : A.nh);
 }
-size_t tree_variant_replay_bytes(int variant) {
-  switch (variant) {
-    case 0: return TreeStore<432, 64>::kReplayBytes;
-    case 1: return TreeStore<512, 64>::kReplayBytes;
-    case 2: return TreeStore<1024, 128>::kReplayBytes;
-    case 3: return TreeStore<2048, 256>::kReplayBytes;
-    default: return 0;
+// ... of the pseudo-volume launch: where the forces leave with it (TreeOutputs), one lane per atom follows the forest workgroups
+int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A) {
+  return tree_forest_blocks(variant, global_grid, slots, A) + (A.out.enabled ? (A.out.n + kBS - 1) / kBS : 0);
+}
+
+template <class K, class... Args>
+static hipError_t launch_tree(K kernel, int grid, size_t lds, hipStream_t st, const Args&... args) {
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
   }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBS), lds, st, args...);
+  return hipGetLastError();
+}
+
+hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st) {
+  if (A.nh <= 0) return hipSuccess;
+  const int grid = tree_forest_blocks(variant, global_grid, slots, A);
+  return with_tree_variant(variant, [&](auto v) {
+    using V = decltype(v);
+    if (A.want_sv_large)  // (the diagnostic self volumes of pass 1: a kernel of their own)
+      return launch_tree(k_tree_cavity<V::kNodeCap, V::kAtomCap, kBS, V::kGlobal, true>, grid, V::kLdsBytes, st, A);
+    return launch_tree(k_tree_cavity<V::kNodeCap, V::kAtomCap, kBS, V::kGlobal, false>, grid, V::kLdsBytes, st, A);
+  });
 }
 
 // (round 6: every LDS variant -- rounds 5 left the mode for good at the first store beyond (512, 64))
 hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st) {
   if (A.nh <= 0 || variant > 3) return hipErrorInvalidValue;  // (the engine leaves the mode before it gets here)
-  const int work = std::max(std::max(P.n, P.nslots), (int)kStatEvalWords);
-  const int prep_blocks = (work + kBS - 1) / kBS;
   const bool dev = A.five == 2, posq = A.posq != nullptr;
-  const dim3 grid(slots + prep_blocks);
-#define AGBNP_FIVE(NC, AC)                                                                                              \
-  do {                                                                                                                 \
-    const size_t lds = TreeStore<NC, AC>::kBytes;                                                                      \
-    if (dev && posq) return launch_five(k_tree_cavity_five<NC, AC, kBS, true, true>, grid, lds, A, P, slots, st);      \
-    if (dev) return launch_five(k_tree_cavity_five<NC, AC, kBS, true, false>, grid, lds, A, P, slots, st);             \
-    if (posq) return launch_five(k_tree_cavity_five<NC, AC, kBS, false, true>, grid, lds, A, P, slots, st);            \
-    return launch_five(k_tree_cavity_five<NC, AC, kBS, false, false>, grid, lds, A, P, slots, st);                     \
-  } while (0)
-  switch (variant) {
-    case 0: AGBNP_FIVE(432, 64);
-    case 1: AGBNP_FIVE(512, 64);
-    case 2: AGBNP_FIVE(1024, 128);
-    default: AGBNP_FIVE(2048, 256);
-  }
-#undef AGBNP_FIVE
+  const int grid = tree_five_grid(slots, P);
+  return with_tree_variant(variant, [&](auto v) {
+    using V = decltype(v);
+    if constexpr (V::kGlobal) {
+      return hipErrorInvalidValue;
+    } else {
+      constexpr int N = V::kNodeCap, AC = V::kAtomCap;
+      if (dev && posq) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, true>, grid, V::kLdsBytes, st, A, P, slots);
+      if (dev) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, false>, grid, V::kLdsBytes, st, A, P, slots);
+      if (posq) return launch_tree(k_tree_cavity_five<N, AC, kBS, false, true>, grid, V::kLdsBytes, st, A, P, slots);
+      return launch_tree(k_tree_cavity_five<N, AC, kBS, false, false>, grid, V::kLdsBytes, st, A, P, slots);
+    }
+  });
 }
 
 hipError_t launch_tree_pseudo(int variant, int global_grid, int slots, const TreeArgs& A0, hipStream_t st) {
   if (A0.nh <= 0) return hipSuccess;
-  // the forces leave with this launch (TreeOutputs): its forest workgroups are followed by one lane per atom
   TreeArgs A = A0;
-  A.out.forest_blocks = variant <= 3 ? slots : (global_grid < A.nh ? global_grid : A.nh);
-  const int grid = A.out.forest_blocks + (A.out.enabled ? (A.out.n + kBS - 1) / kBS : 0);
-  switch (variant) {
-    case 0:
-      if (A.five == 2 && A.out.enabled) return launch_tree(k_tree_pseudo<432, 64, kBS, false, false, true>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
-      if (A.five == 2) return launch_tree(k_tree_pseudo<432, 64, kBS, false, true, true>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
-      if (A.out.enabled) return launch_tree(k_tree_pseudo<432, 64, kBS, false, false>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
-      return launch_tree(k_tree_pseudo<432, 64, kBS, false>, grid, TreeStore<432, 64>::kReplayBytes, A, st);
-    case 1:
-      if (A.five == 2 && A.out.enabled) return launch_tree(k_tree_pseudo<512, 64, kBS, false, false, true>, grid, TreeStore<512, 64>::kReplayBytes, A, st);
-      if (A.five == 2) return launch_tree(k_tree_pseudo<512, 64, kBS, false, true, true>, grid, TreeStore<512, 64>::kReplayBytes, A, st);
-      if (A.out.enabled) return launch_tree(k_tree_pseudo<512, 64, kBS, false, false>, grid, TreeStore<512, 64>::kReplayBytes, A, st);
-      return launch_tree(k_tree_pseudo<512, 64, kBS, false>, grid, TreeStore<512, 64>::kReplayBytes, A, st);
-    case 2:
-      if (A.five == 2) return launch_tree(k_tree_pseudo<1024, 128, kBS, false, true, true>, grid, TreeStore<1024, 128>::kReplayBytes, A, st);
-      return launch_tree(k_tree_pseudo<1024, 128, kBS, false>, grid, TreeStore<1024, 128>::kReplayBytes, A, st);
-    case 3:
-      if (A.five == 2) return launch_tree(k_tree_pseudo<2048, 256, kBS, false, true, true>, grid, TreeStore<2048, 256>::kReplayBytes, A, st);
-      return launch_tree(k_tree_pseudo<2048, 256, kBS, false>, grid, TreeStore<2048, 256>::kReplayBytes, A, st);
-    default: return launch_tree(k_tree_pseudo<kGlobalNodeCap, kGlobalAtomCap, kBS, true>, grid, 0, A, st);
-  }
+  A.out.forest_blocks = tree_forest_blocks(variant, global_grid, slots, A);
+  const int grid = tree_pseudo_grid(variant, global_grid, slots, A);
+  return with_tree_variant(variant, [&](auto v) {
+    using V = decltype(v);
+    constexpr int N = V::kNodeCap, AC = V::kAtomCap;
+    if constexpr (V::kGlobal) {
+      return launch_tree(k_tree_pseudo<N, AC, kBS, true>, grid, 0, st, A);
+    } else {
+      auto launch = [&](auto pipe) {
+        constexpr bool PIPE = decltype(pipe)::value;
+        if (A.five == 2) return launch_tree(k_tree_pseudo<N, AC, kBS, false, PIPE, true>, grid, V::kReplayBytes, st, A);
+        return launch_tree(k_tree_pseudo<N, AC, kBS, false, PIPE>, grid, V::kReplayBytes, st, A);
+      };
+      if constexpr (pseudo_forces_lean(N))
+        if (A.out.enabled) return launch(std::false_type());
+      return launch(std::true_type());
+    }
+  });
 }
 
 #endif  // !AGBNP_GROUP_TU
 
 #ifdef AGBNP_GROUP_TU
 // replica groups: one launch per stage for every member of a launch set (engine.hip, agbnp_hip_execute_group)
-template <class K>
-static hipError_t launch_group(K kernel, const GroupLaunch& G, size_t lds, hipStream_t st) {
+template <class K, class... Args>
+static hipError_t launch_group(K kernel, const GroupLaunch& G, size_t lds, hipStream_t st, const Args&... args) {
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(kernel, dim3(G.first[G.count]), dim3(kBS), lds, st, G);
+  hipLaunchKernelGGL(kernel, dim3(G.first[G.count]), dim3(kBS), lds, st, G, args...);
   return hipGetLastError();
 }
 
 hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st) {
-  switch (variant) {
-    case 0: return launch_group(k_group_cavity_five<432, 64, kBS>, G, lds, st);
-    case 1: return launch_group(k_group_cavity_five<512, 64, kBS>, G, lds, st);
-    case 2: return launch_group(k_group_cavity_five<1024, 128, kBS>, G, lds, st);
-    case 3: return launch_group(k_group_cavity_five<2048, 256, kBS>, G, lds, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_tree_variant(variant, [&](auto v) {
+    using V = decltype(v);
+    if constexpr (V::kGlobal)
+      return hipErrorInvalidValue;
+    else
+      return launch_group(k_group_cavity_five<V::kNodeCap, V::kAtomCap, kBS>, G, lds, st);
+  });
 }
 
-template <class K>
-static hipError_t launch_group_out(K kernel, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3(G.first[G.count]), dim3(kBS), lds, st, G, O);
-  return hipGetLastError();
-}
-
-// (the instantiation launch_tree_pseudo takes where the forces leave with the launch: the lean one up to 512 nodes)
+// (a member's forces always leave with the launch)
 hipError_t launch_group_pseudo(int variant, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st) {
-  switch (variant) {
-    case 0: return launch_group_out(k_group_pseudo<432, 64, kBS, false>, G, O, lds, st);
-    case 1: return launch_group_out(k_group_pseudo<512, 64, kBS, false>, G, O, lds, st);
-    case 2: return launch_group_out(k_group_pseudo<1024, 128, kBS, true>, G, O, lds, st);
-    case 3: return launch_group_out(k_group_pseudo<2048, 256, kBS, true>, G, O, lds, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_tree_variant(variant, [&](auto v) {
+    using V = decltype(v);
+    if constexpr (V::kGlobal)
+      return hipErrorInvalidValue;
+    else
+      return launch_group(k_group_pseudo<V::kNodeCap, V::kAtomCap, kBS, !pseudo_forces_lean(V::kNodeCap)>, G, lds, st, O);
+  });
 }
 
 #endif  // AGBNP_GROUP_TU

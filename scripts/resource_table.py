@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Per-kernel resource table of the gfx950 code objects (no GPU needed): VGPRs, SGPRs, spills, scratch, static LDS,
-occupancy, and the number of scratch_/v_readlane/v_writelane instructions in the body.  Compiles every .hip file of
+occupancy, the number of scratch_/v_readlane/v_writelane instructions in the body, and a hash of the body's instruction
+stream (comments dropped, the function index in local labels normalised), so that "this kernel did not change" is a diff
+of two tables.  Compiles every .hip file of
 the engine to device assembly with the product's flags and reads the .amdhsa_ directives / amdhsa.kernels metadata.
 
   python scripts/resource_table.py [--out profiles/r02/resource_table.csv] [--keep-asm DIR]
 """
 import argparse
 import csv
+import hashlib
 import os
 import re
 import subprocess
@@ -39,6 +42,10 @@ def parse(asm_path):
         m = re.search(r"^" + re.escape(name) + r":[^\n]*\n(.*?)\n\.Lfunc_end\d+:", text, re.S | re.M)
         body = m.group(1) if m else ""
         ins = [l.strip() for l in body.split("\n") if l.startswith("\t") and not l.strip().startswith((".", ";"))]
+        # (comments dropped, those behind an instruction too: "in Loop: Header=BB28_4" carries the function index as well)
+        stream = "\n".join(l.split(";")[0].rstrip() for l in body.split("\n") if l.split(";")[0].strip())
+        stream = re.sub(r"\.LBB\d+_", ".LBB_", stream)
+        rows[name].update(code_hash=hashlib.sha256(stream.encode()).hexdigest()[:16])
         rows[name].update(instructions=len(ins), scratch_ins=sum(i.startswith("scratch_") for i in ins),
                           readlane=sum(i.startswith("v_readlane") for i in ins), writelane=sum(i.startswith("v_writelane") for i in ins),
                           barriers=sum(i.startswith("s_barrier") for i in ins), f64=sum("_f64" in i.split()[0] for i in ins),
@@ -62,7 +69,7 @@ def main():
         allrows.update(parse(out))
     pretty = demangle(list(allrows))
     cols = ["kernel", "vgpr", "agpr", "sgpr", "sgpr_spill", "vgpr_spill", "scratch_bytes", "static_lds", "instructions", "f64", "ds", "vmem",
-            "barriers", "scratch_ins", "readlane", "writelane"]
+            "barriers", "scratch_ins", "readlane", "writelane", "code_hash"]
     lines = []
     for name, r in sorted(allrows.items(), key=lambda kv: pretty[kv[0]]):
         short = re.sub(r"^void agbnp::", "", pretty[name])

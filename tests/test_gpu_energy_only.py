@@ -6,17 +6,14 @@ import pytest
 
 import openmm_agbnp_plugin_amd as P
 from oracle import Oracle
+from tests.gpu_helpers import SAME
+from tests.gpu_helpers import close as _close
+from tests.gpu_helpers import energy_close as _energy_close
+from tests.gpu_helpers import five  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-TIGHT = 1e-7
-SAME = 1e-9
 SENTINEL = 0x5A5A_1234_A5A5_4321
 FULL_KERNELS = {"k_tree_cavity", "k_born_rows", "k_gb_tiles", "k_dborn_rows", "k_tree_pseudo"}
-
-
-@pytest.fixture()
-def five(monkeypatch):
-    monkeypatch.setenv("AGBNP_HIP_FIVE_LAUNCHES", "1")
 
 
 def _kernel(s, version=1, mode="reference", cutoff=None):
@@ -27,15 +24,6 @@ def _kernel(s, version=1, mode="reference", cutoff=None):
         force.setCutoffDistance(cutoff)
     k.initialize(force)
     return k
-
-
-def _energy_close(e, eo, tol=TIGHT):
-    assert abs(e - eo) < tol * max(1.0, abs(eo) * 1e-3), f"energy differs by {abs(e - eo):.3e}"
-
-
-def _close(e, f, eo, fo, tol=TIGHT):
-    _energy_close(e, eo, tol)
-    assert np.abs(f - fo).max() < tol, f"forces differ by {np.abs(f - fo).max():.3e}"
 
 
 @pytest.mark.parametrize("version,name", [(1, "trpcage"), (1, "1dwc"), (1, "2clr"), (1, "fixture264"), (0, "trpcage"), (0, "fixture264")])

@@ -10,25 +10,17 @@ import pytest
 
 import openmm_agbnp_plugin_amd as P
 from oracle import Oracle
+from tests.gpu_helpers import TIGHT
+from tests.gpu_helpers import close as _close
+from tests.gpu_helpers import five  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-TIGHT = 1e-7
-
-
-@pytest.fixture()
-def five(monkeypatch):
-    monkeypatch.setenv("AGBNP_HIP_FIVE_LAUNCHES", "1")
 
 
 def _kernel(s, version=1):
     k = P.HipCalcAGBNPForceKernel(device=0)
     k.initialize(P.AGBNPForce.from_arrays(*s.params(), version=version))
     return k
-
-
-def _close(e, f, eo, fo, tol=TIGHT):
-    assert abs(e - eo) < tol * max(1.0, abs(eo) * 1e-3), f"energy differs by {abs(e - eo):.3e}"
-    assert np.abs(f - fo).max() < tol, f"forces differ by {np.abs(f - fo).max():.3e}"
 
 
 @pytest.mark.parametrize("name", ["trpcage", "1dwc", "2clr", "fixture264"])

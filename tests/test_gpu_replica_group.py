@@ -11,54 +11,14 @@ import pytest
 import openmm_agbnp_plugin_amd as P
 from openmm_agbnp_plugin_amd import _lib
 from oracle import Oracle
+from tests.gpu_helpers import SAME, TIGHT, Buffers
+from tests.gpu_helpers import close as _close
+from tests.gpu_helpers import cluster as _cluster
+from tests.gpu_helpers import execute_group as _group
+from tests.gpu_helpers import five_groups as five  # noqa: F401
+from tests.gpu_helpers import kernel_of as _kernel
 
 pytestmark = pytest.mark.gpu
-TIGHT = 1e-7
-SAME = 1e-9
-
-
-@pytest.fixture()
-def five(monkeypatch):
-    monkeypatch.setenv("AGBNP_HIP_FIVE_LAUNCHES", "1")
-    monkeypatch.delenv("AGBNP_HIP_GROUP_LAUNCHES", raising=False)
-
-
-def _kernel(params, version=1, mode="reference"):
-    k = P.HipCalcAGBNPForceKernel(device=0, mode=mode)
-    k.initialize(P.AGBNPForce.from_arrays(*params, version=version))
-    return k
-
-
-def _close(e, f, eo, fo, tol=TIGHT):
-    assert abs(e - eo) < tol * max(1.0, abs(eo) * 1e-3), f"energy differs by {abs(e - eo):.3e}"
-    assert np.abs(f - fo).max() < tol, f"forces differ by {np.abs(f - fo).max():.3e}"
-
-
-class Buffers:
-    """Device positions, forces and energy of one member (torch tensors)."""
-
-    def __init__(self, torch, n):
-        dev = torch.device("cuda:0")
-        self.torch = torch
-        self.pos = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        self.frc = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        self.ene = torch.zeros((1,), dtype=torch.float64, device=dev)
-
-    def load(self, geom):
-        self.pos.copy_(self.torch.tensor(geom, dtype=self.torch.float64))
-        self.frc.zero_()
-        self.ene.zero_()
-
-    def ptrs(self):
-        return self.pos.data_ptr(), self.frc.data_ptr(), self.ene.data_ptr()
-
-    def result(self):
-        return self.ene.item(), self.frc.cpu().numpy()
-
-
-def _group(kernels, bufs, stream):
-    P.execute_group(kernels, [b.pos.data_ptr() for b in bufs], [b.frc.data_ptr() for b in bufs], [b.ene.data_ptr() for b in bufs],
-                    stream)
 
 
 @pytest.mark.parametrize("version,name", [(1, "trpcage"), (1, "1dwc"), (1, "fixture264"), (0, "trpcage")])
@@ -294,18 +254,6 @@ def test_cpp_mirror_runs_a_group(gpu_required, systems, five, tmp_path):
         files.append(str(path))
     out = subprocess.run([exe] + files, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
-
-
-def _cluster(n, spacing, seed):
-    """A cluster denser than a protein (as tests/test_gpu_parity.py builds them): its subtrees need the larger LDS variants."""
-    from openmm_agbnp_plugin_amd.systems import vdw_alpha_from_radius
-    rng = np.random.default_rng(seed)
-    grid = np.stack(np.meshgrid(*[np.arange(6)] * 3, indexing="ij"), -1).reshape(-1, 3)[:n]
-    pos = grid * spacing + rng.normal(0, 0.02, (n, 3))
-    ish = (rng.random(n) < 0.3).astype(np.int32)
-    radius = np.where(ish == 1, 0.121, rng.choice([0.17, 0.18, 0.19, 0.2], n))
-    gamma = np.where(ish == 1, 0.0, 0.117 * 418.4)
-    return P.AGBNPSystem(f"cluster{spacing}_{seed}", pos, radius, gamma, vdw_alpha_from_radius(radius), rng.normal(0, 0.4, n), ish)
 
 
 def _group_until_complete(ks, bufs, geoms, stream, attempts=8):
