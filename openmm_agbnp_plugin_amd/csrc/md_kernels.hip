@@ -259,3 +259,276 @@ int agbnp_md_tethers(int n, const double* x, const double* x0, double* f, double
 }
 
 }  // extern "C"
+
+// ---- Replica groups (openmm_agbnp_plugin_amd/md.py::ReplicaMD) ---------------------------------------------
+// The same steps for R replicas of ONE system in one launch each, around agbnp_hip_execute_group: the grid is R times the
+// single kernels' grid, a workgroup's replica is blockIdx.x / blocks(n) (uniform), and inside a replica the partition into
+// workgroups and the fixed-order sums are the single kernels', so a replica's energies are what k_md_post / k_md_mid log
+// for the same state.  State is strided ([R][n][3], [R][blocks], [R]...): member r's buffers are fixed slices.  What differs
+// from the single kernels: the bath temperature is a device word per replica (kT[r], kJ/mol), which an exchange swaps without
+// the host, so the noise amplitude sqrt((1 - c1^2) kT[r] / m_i) is formed here and not read from a table; the Philox key is
+// seeds[r].
+//
+// Exchange (temperature replica exchange between neighbouring rungs of the ladder): k_md_exchange_decide, ONE workgroup,
+// one thread per pair (k, k + 1), k = a mod 2, a mod 2 + 2, ...: the pairs of an attempt are disjoint, so every thread reads and
+// writes its own two replicas' words; it leaves a velocity factor per replica (1 where nothing happened), and
+// k_md_exchange_apply, a launch of its own behind it, rescales -- no workgroup of the second launch can see a half-made decision.
+
+struct AgbnpMdGroup {  // (mirrored field for field by md.py::_GroupArgs)
+  int n, replicas;
+  double *x, *v, *f;                // [R][n][3]
+  const double *x0, *hdt_m, *mass;  // [n][3], [n], [n]: the one system's tether anchors, dt / 2m, m
+  const double* kT;                 // [R] bath temperatures in kJ/mol
+  const unsigned long long* seeds;  // [R] Philox keys
+  double c1, dt, ktether;           // exp(-friction dt), step, tether constant
+  double* energy;                   // [R] the words agbnp_hip_execute_group adds the AGBNP energies to
+  double* acc;                      // [R][2] kinetic-energy accumulators
+  unsigned* done;                   // [R] workgroups of the replica that have arrived
+  double *log_pe, *log_ke;          // [R][capacity]
+  long long* step;                  // [R]
+  long long capacity;
+  double* last;                     // [R][2] {potential, kinetic} energy of the last step
+};
+
+struct AgbnpMdExchangeRecord {  // (md.py::EXCHANGE_RECORD); 72 bytes, no padding
+  long long attempt, step;      // step: steps replica_lo had finished
+  int rung, replica_lo, replica_hi, accepted;
+  double u_lo, u_hi, kT_lo, kT_hi, u;  // potential energies and bath temperatures (kJ/mol) BEFORE the decision
+};
+
+struct AgbnpMdExchange {  // (md.py::_ExchangeArgs)
+  int n, replicas;
+  double* v;                 // [R][n][3]
+  double* kT;                // [R]
+  int *rung_of_replica, *replica_at_rung;  // [R] each
+  const double* last;        // [R][2]
+  const long long* step;     // [R]
+  long long* attempts;       // [1]
+  double* scale;             // [R] velocity factors of the attempt in flight
+  AgbnpMdExchangeRecord* log;
+  long long log_capacity;
+  unsigned long long seed;
+};
+
+namespace {
+
+// front_half() with the noise amplitude formed from the replica's bath temperature (the arithmetic is front_half's otherwise)
+__device__ __forceinline__ double front_half_bath(int i, int kind, double (&px)[3], double (&pv)[3], double* __restrict__ x, double* __restrict__ v,
+                                                  double* __restrict__ f, const double* __restrict__ x0, double kT, double mass, double c1,
+                                                  double dt, double ktether, unsigned long long seed, unsigned long long s) {
+  if (kind == 0) {
+    const Philox a = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const Philox b = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    double z[4];
+    box_muller(uniform53(a.c[0], a.c[1]), uniform53(a.c[2], a.c[3]), z[0], z[1]);
+    box_muller(uniform53(b.c[0], b.c[1]), uniform53(b.c[2], b.c[3]), z[2], z[3]);
+    const double cn = sqrt((1.0 - c1 * c1) * kT / mass);
+    for (int d = 0; d < 3; d++) {
+      px[d] = fma(0.5 * dt, pv[d], px[d]);
+      pv[d] = fma(c1, pv[d], cn * z[d]);
+      px[d] = fma(0.5 * dt, pv[d], px[d]);
+    }
+  } else {
+    for (int d = 0; d < 3; d++) px[d] = fma(dt, pv[d], px[d]);
+  }
+  double e = 0.0;
+  for (int d = 0; d < 3; d++) {
+    const double dd = px[d] - x0[3 * i + d];
+    x[3 * i + d] = px[d];
+    v[3 * i + d] = pv[d];
+    f[3 * i + d] = -ktether * dd;
+    e = fma(0.5 * ktether * dd, dd, e);
+  }
+  return e;
+}
+
+// the tail of k_md_post / k_md_mid per replica: the replica's last workgroup to arrive sums step s's energies into the logs
+// and hands the energy word and the accumulators back as zeros
+__device__ __forceinline__ void group_log_step(const AgbnpMdGroup& g, int r, int blocks, const double* __restrict__ part, long long s, double ke,
+                                               double* red, bool& s_last) {
+  if (threadIdx.x == 0) {
+    __hip_atomic_fetch_add(&g.acc[2 * r], ke, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+    s_last = atomicAdd(&g.done[r], 1u) == (unsigned)blocks - 1u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  double et = 0.0;
+  for (int b = threadIdx.x; b < blocks; b += kBlock) et += part[b];
+  et = block_sum(et, red);
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const double kin = __hip_atomic_load(&g.acc[2 * r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double pot = et + g.energy[r];
+    if (s < g.capacity) g.log_pe[r * g.capacity + s] = pot, g.log_ke[r * g.capacity + s] = kin;
+    g.last[2 * r] = pot, g.last[2 * r + 1] = kin;
+    g.step[r] = s + 1;
+    g.energy[r] = 0.0;
+    g.acc[2 * r] = 0.0;
+    g.done[r] = 0u;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_md_group_pre(AgbnpMdGroup g, int blocks, int kind, double* __restrict__ tether_part) {
+  __shared__ double red[kBlock / 64];
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const size_t o = (size_t)r * 3 * g.n;
+  double e = 0.0;
+  if (i < g.n) {
+    const double h = g.hdt_m[i];
+    double px[3], pv[3];
+    for (int d = 0; d < 3; d++) px[d] = g.x[o + 3 * i + d], pv[d] = fma(h, g.f[o + 3 * i + d], g.v[o + 3 * i + d]);
+    e = front_half_bath(i, kind, px, pv, g.x + o, g.v + o, g.f + o, g.x0, g.kT[r], g.mass[i], g.c1, g.dt, g.ktether, g.seeds[r],
+                        (unsigned long long)g.step[r]);
+  }
+  e = block_sum(e, red);
+  if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
+}
+
+__global__ __launch_bounds__(kBlock) void k_md_group_post(AgbnpMdGroup g, int blocks, const double* __restrict__ tether_part) {
+  __shared__ double red[kBlock / 64];
+  __shared__ bool s_last;
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const size_t o = (size_t)r * 3 * g.n;
+  const long long s = g.step[r];  // (read before this workgroup counts itself in: only the last to arrive writes it)
+  double ke = 0.0;
+  if (i < g.n) {
+    const double h = g.hdt_m[i], m = g.mass[i];
+    for (int d = 0; d < 3; d++) {
+      const double pv = fma(h, g.f[o + 3 * i + d], g.v[o + 3 * i + d]);
+      g.v[o + 3 * i + d] = pv;
+      ke = fma(0.5 * m * pv, pv, ke);
+    }
+  }
+  ke = block_sum(ke, red);
+  group_log_step(g, r, blocks, tether_part + (size_t)r * blocks, s, ke, red, s_last);
+}
+
+__global__ __launch_bounds__(kBlock) void k_md_group_mid(AgbnpMdGroup g, int blocks, int kind, const double* __restrict__ part_old,
+                                                        double* __restrict__ part_new) {
+  __shared__ double red[kBlock / 64];
+  __shared__ bool s_last;
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const size_t o = (size_t)r * 3 * g.n;
+  const long long s = g.step[r];
+  double ke = 0.0, e = 0.0;
+  if (i < g.n) {
+    const double h = g.hdt_m[i], m = g.mass[i];
+    double px[3], pv[3];
+    for (int d = 0; d < 3; d++) {
+      const double fd = g.f[o + 3 * i + d];
+      const double v1 = fma(h, fd, g.v[o + 3 * i + d]);  // end of step n
+      ke = fma(0.5 * m * v1, v1, ke);
+      pv[d] = fma(h, fd, v1);                             // first kick of step n + 1: the same force
+      px[d] = g.x[o + 3 * i + d];
+    }
+    e = front_half_bath(i, kind, px, pv, g.x + o, g.v + o, g.f + o, g.x0, g.kT[r], m, g.c1, g.dt, g.ktether, g.seeds[r],
+                        (unsigned long long)s + 1ull);
+  }
+  ke = block_sum(ke, red);
+  e = block_sum(e, red);
+  if (threadIdx.x == 0) part_new[blockIdx.x] = e;
+  group_log_step(g, r, blocks, part_old + (size_t)r * blocks, s, ke, red, s_last);
+}
+
+__global__ __launch_bounds__(kBlock) void k_md_group_tethers(AgbnpMdGroup g, int blocks, double* __restrict__ tether_part) {
+  __shared__ double red[kBlock / 64];
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const size_t o = (size_t)r * 3 * g.n;
+  double e = 0.0;
+  if (i < g.n)
+    for (int d = 0; d < 3; d++) {
+      const double dd = g.x[o + 3 * i + d] - g.x0[3 * i + d];
+      g.f[o + 3 * i + d] = -g.ktether * dd;
+      e = fma(0.5 * g.ktether * dd, dd, e);
+    }
+  e = block_sum(e, red);
+  if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
+}
+
+constexpr int kMaxReplicas = 16;  // AGBNP_HIP_MAX_GROUP
+
+// attempt a = attempts[0]: pairs of rungs (k, k + 1), k = a mod 2, a mod 2 + 2, ...; accept iff log(u) <= Delta,
+// Delta = (1 / kT_lo - 1 / kT_hi) (U_lo - U_hi), u = uniform53 of Philox(counter (k, a lo, a hi, 2), key seed).  An accepted
+// pair swaps temperatures and rungs; conformations stay.  The records of an attempt have fixed places in the log.
+__global__ __launch_bounds__(64) void k_md_exchange_decide(AgbnpMdExchange e) {
+  const int t = threadIdx.x, R = e.replicas;
+  const long long a = e.attempts[0];
+  if (t < R) e.scale[t] = 1.0;
+  __syncthreads();
+  const int parity = (int)(a & 1), k = 2 * t + parity;
+  if (k + 1 < R) {
+    const int lo = e.replica_at_rung[k], hi = e.replica_at_rung[k + 1];
+    const double kT_lo = e.kT[lo], kT_hi = e.kT[hi], u_lo = e.last[2 * lo], u_hi = e.last[2 * hi];
+    const double delta = (1.0 / kT_lo - 1.0 / kT_hi) * (u_lo - u_hi);
+    const Philox p = philox4x32((uint32_t)k, (uint32_t)a, (uint32_t)((unsigned long long)a >> 32), 2u, (uint32_t)e.seed, (uint32_t)(e.seed >> 32));
+    const double u = uniform53(p.c[0], p.c[1]);
+    const bool accepted = log(u) <= delta;
+    if (accepted) {
+      e.kT[lo] = kT_hi, e.kT[hi] = kT_lo;
+      e.rung_of_replica[lo] = k + 1, e.rung_of_replica[hi] = k;
+      e.replica_at_rung[k] = hi, e.replica_at_rung[k + 1] = lo;
+      e.scale[lo] = sqrt(kT_hi / kT_lo), e.scale[hi] = sqrt(kT_lo / kT_hi);
+    }
+    // attempts 0 .. a - 1 left (a + 1) / 2 even ones with R / 2 pairs each and a / 2 odd ones with (R - 1) / 2
+    const long long at = ((a + 1) / 2) * (R / 2) + (a / 2) * ((R - 1) / 2) + t;
+    if (at < e.log_capacity) e.log[at] = AgbnpMdExchangeRecord{a, e.step[lo], k, lo, hi, accepted ? 1 : 0, u_lo, u_hi, kT_lo, kT_hi, u};
+  }
+  __syncthreads();  // (every thread has read `a`)
+  if (t == 0) e.attempts[0] = a + 1;
+}
+
+__global__ __launch_bounds__(kBlock) void k_md_exchange_apply(AgbnpMdExchange e, int blocks) {
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const double s = e.scale[r];
+  if (s == 1.0 || i >= e.n) return;
+  double* v = e.v + (size_t)r * 3 * e.n + 3 * i;
+  for (int d = 0; d < 3; d++) v[d] *= s;
+}
+
+inline bool group_ok(const AgbnpMdGroup* g) { return g && g->n > 0 && g->replicas >= 1 && g->replicas <= kMaxReplicas; }
+
+}  // namespace
+
+extern "C" {
+
+// One launch each for all the replicas of *g (a host struct, read during the call).  tether_part / part_old / part_new:
+// [R][agbnp_md_blocks(n)].  kind 0: Langevin, 1: velocity Verlet.  Return: hipError_t of the launch, 1 for a bad *g.
+int agbnp_md_group_pre(const AgbnpMdGroup* g, int kind, double* tether_part, void* stream) {
+  if (!group_ok(g)) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(g->n);
+  hipLaunchKernelGGL(k_md_group_pre, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, kind, tether_part);
+  return (int)hipGetLastError();
+}
+
+int agbnp_md_group_mid(const AgbnpMdGroup* g, int kind, const double* part_old, double* part_new, void* stream) {
+  if (!group_ok(g)) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(g->n);
+  hipLaunchKernelGGL(k_md_group_mid, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, kind, part_old, part_new);
+  return (int)hipGetLastError();
+}
+
+int agbnp_md_group_post(const AgbnpMdGroup* g, const double* tether_part, void* stream) {
+  if (!group_ok(g)) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(g->n);
+  hipLaunchKernelGGL(k_md_group_post, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, tether_part);
+  return (int)hipGetLastError();
+}
+
+int agbnp_md_group_tethers(const AgbnpMdGroup* g, double* tether_part, void* stream) {
+  if (!group_ok(g)) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(g->n);
+  hipLaunchKernelGGL(k_md_group_tethers, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, tether_part);
+  return (int)hipGetLastError();
+}
+
+// One exchange attempt between neighbouring rungs: two launches (decide, rescale), no synchronisation, nothing read back.
+int agbnp_md_exchange(const AgbnpMdExchange* e, void* stream) {
+  if (!e || e->n <= 0 || e->replicas < 1 || e->replicas > kMaxReplicas) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(e->n);
+  hipLaunchKernelGGL(k_md_exchange_decide, dim3(1), dim3(64), 0, (hipStream_t)stream, *e);
+  hipLaunchKernelGGL(k_md_exchange_apply, dim3(e->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *e, blocks);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -292,3 +292,287 @@ class DeviceMD:
         ke = 0.5 * float((self.mass * self.v * self.v).sum())
         return 2.0 * ke / (3 * self.system.n * KB)
 
+
+# ---- replica exchange on top of the replica groups --------------------------------------------------------
+
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32(counter4, key2):
+    """Philox4x32-10 (Salmon et al., SC'11; Random123) in plain Python integers: what `philox4x32` of csrc/md_kernels.hip
+    computes.  counter4: four 32-bit words, key2: two.  Returns the four output words."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter4)
+    k0, k1 = (int(k) & _M32 for k in key2)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def uniform53(a, b):
+    """The kernels' uniform deviate in (0, 1] from two 32-bit words: 53 bits, never zero (its logarithm is taken)."""
+    u = (((int(a) & _M32) << 21) ^ ((int(b) & _M32) >> 11)) & ((1 << 53) - 1)
+    return (float(u) + 1.0) * (1.0 / 9007199254740992.0)
+
+
+def exchange_uniform(rung, attempt, exchange_seed):
+    """The deviate attempt `attempt` uses for the rung pair (rung, rung + 1): counter (k, a lo, a hi, 2), key exchange_seed."""
+    a, s = int(attempt), int(exchange_seed)
+    w = philox4x32((int(rung), a & _M32, (a >> 32) & _M32, 2), (s & _M32, (s >> 32) & _M32))
+    return uniform53(w[0], w[1])
+
+
+def exchange_delta(kT_lo, kT_hi, U_lo, U_hi):
+    """Delta of a temperature exchange between two replicas (kT in kJ/mol, potential energies in kJ/mol): the exchange is
+    accepted iff log(u) <= Delta, u uniform in (0, 1] -- min(1, exp(Delta)), the Metropolis rule for swapping the baths."""
+    return (1.0 / kT_lo - 1.0 / kT_hi) * (U_lo - U_hi)
+
+
+# one record of the exchange log (AgbnpMdExchangeRecord, csrc/md_kernels.hip); energies and kT in kJ/mol, before the decision
+EXCHANGE_RECORD = np.dtype([("attempt", "<i8"), ("step", "<i8"), ("rung", "<i4"), ("replica_lo", "<i4"), ("replica_hi", "<i4"),
+                            ("accepted", "<i4"), ("U_lo", "<f8"), ("U_hi", "<f8"), ("kT_lo", "<f8"), ("kT_hi", "<f8"), ("u", "<f8")])
+
+MAX_REPLICAS = 16  # AGBNP_HIP_MAX_GROUP
+
+
+class _GroupArgs(C.Structure):  # AgbnpMdGroup
+    _fields_ = [("n", C.c_int), ("replicas", C.c_int), ("x", C.c_void_p), ("v", C.c_void_p), ("f", C.c_void_p), ("x0", C.c_void_p),
+                ("hdt_m", C.c_void_p), ("mass", C.c_void_p), ("kT", C.c_void_p), ("seeds", C.c_void_p), ("c1", C.c_double),
+                ("dt", C.c_double), ("ktether", C.c_double), ("energy", C.c_void_p), ("acc", C.c_void_p), ("done", C.c_void_p),
+                ("log_pe", C.c_void_p), ("log_ke", C.c_void_p), ("step", C.c_void_p), ("capacity", C.c_longlong), ("last", C.c_void_p)]
+
+
+class _ExchangeArgs(C.Structure):  # AgbnpMdExchange
+    _fields_ = [("n", C.c_int), ("replicas", C.c_int), ("v", C.c_void_p), ("kT", C.c_void_p), ("rung_of_replica", C.c_void_p),
+                ("replica_at_rung", C.c_void_p), ("last", C.c_void_p), ("step", C.c_void_p), ("attempts", C.c_void_p),
+                ("scale", C.c_void_p), ("log", C.c_void_p), ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
+
+
+GROUP_SYMBOLS = ("agbnp_md_group_pre", "agbnp_md_group_mid", "agbnp_md_group_post", "agbnp_md_group_tethers", "agbnp_md_exchange")
+
+
+def _md_group_lib():
+    lib = _md_lib()
+    if not getattr(lib, "_group_ready", False):
+        vp, gp = C.c_void_p, C.POINTER(_GroupArgs)
+        lib.agbnp_md_group_pre.argtypes = [gp, C.c_int, vp, vp]
+        lib.agbnp_md_group_mid.argtypes = [gp, C.c_int, vp, vp, vp]
+        lib.agbnp_md_group_post.argtypes = [gp, vp, vp]
+        lib.agbnp_md_group_tethers.argtypes = [gp, vp, vp]
+        lib.agbnp_md_exchange.argtypes = [C.POINTER(_ExchangeArgs), vp]
+        lib._group_ready = True
+    return lib
+
+
+class ReplicaMD:
+    """Temperature replica exchange of R replicas of one system: DeviceMD's integrator and force field (tethers + AGBNP) for
+    all replicas at once -- one launch of libagbnp_md.so in front of and one behind `agbnp_hip_execute_group`, six launches a
+    step for all R -- and exchange attempts between neighbouring rungs of the temperature ladder decided on the device.
+
+    Replica r is a conformation: x[r], v[r] and kernels[r] stay together for the whole run.  An accepted exchange swaps the
+    two replicas' bath temperatures and rungs (and rescales their velocities by sqrt(T_new / T_old)); no position moves, so
+    no evaluation is withheld for it and no argument block of the group is rewritten.  Eager: group calls are not captured."""
+
+    def __init__(self, system, kernels, temperatures, seeds=None, exchange_seed=0, k_tether=2.0e4, dt=0.001, friction=1.0,
+                 device="cuda:0", log_capacity=200000):
+        kernels, temperatures = list(kernels), [float(t) for t in temperatures]
+        R = len(kernels)
+        seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
+        if len(temperatures) != R or len(seeds) != R:
+            raise ValueError(f"ReplicaMD: {R} kernels, {len(temperatures)} temperatures and {len(seeds)} seeds")
+        if not 1 <= R <= MAX_REPLICAS:
+            raise ValueError(f"ReplicaMD: a group has 1 to {MAX_REPLICAS} replicas, not {R}")
+        if any(int(k.numParticles) != int(system.n) for k in kernels):
+            raise ValueError(f"ReplicaMD: every kernel must hold the system's {int(system.n)} particles")
+        if len({id(k) for k in kernels}) != R:
+            raise ValueError("ReplicaMD: the same kernel was given twice (one context per replica)")
+        if any(not t > 0.0 for t in temperatures):
+            raise ValueError("ReplicaMD: temperatures must be positive")
+        import torch
+        self.torch = torch
+        lib = _md_group_lib()
+        self.system, self.kernels, self.R, self.n = system, kernels, R, int(system.n)
+        self.ladder = np.array(temperatures)  # the temperature of rung k; replica r starts on rung r
+        self.seeds, self.exchange_seed = seeds, int(exchange_seed)
+        self.dev = torch.device(device)
+        self.dt, self.k, self.gamma = float(dt), float(k_tether), float(friction)
+        self.c1 = float(np.exp(-self.gamma * self.dt))
+        self.log_capacity = int(log_capacity)
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        i64 = dict(dtype=torch.int64, device=self.dev)
+        n, cap = self.n, self.log_capacity
+        mass = torch.tensor(np.where(system.ishydrogen == 1, 1.008, 12.0), **f64)  # (DeviceMD's masses)
+        self.mass = mass.reshape(-1, 1)
+        self.mass1 = mass.contiguous()
+        self.hdt_m1 = ((0.5 * self.dt) / mass).contiguous()
+        self.x0 = torch.tensor(system.pos, **f64).contiguous()
+        self.x = self.x0.unsqueeze(0).repeat(R, 1, 1).contiguous()
+        self.v = torch.empty_like(self.x)
+        for r in range(R):  # replica r starts as DeviceMD(seed=seeds[r], temperature=temperatures[r]) starts
+            gen = torch.Generator(device=self.dev)
+            gen.manual_seed(seeds[r])
+            self.v[r] = torch.randn((n, 3), generator=gen, **f64) * torch.sqrt(KB * temperatures[r] / self.mass)
+        self.frc = torch.zeros_like(self.x)
+        self.kT = torch.tensor([KB * t for t in temperatures], **f64)
+        self.seed_words = torch.tensor(np.array(seeds, dtype=np.uint64).view(np.int64), **i64)
+        self.e_agbnp = torch.zeros(R, **f64)
+        self.blocks = int(lib.agbnp_md_blocks(n))
+        self.parts = (torch.zeros((R, self.blocks), **f64), torch.zeros((R, self.blocks), **f64))
+        self.acc = torch.zeros((R, 2), **f64)
+        self.done = torch.zeros(R, dtype=torch.int32, device=self.dev)
+        self.log_pe = torch.zeros((R, cap), **f64)
+        self.log_ke = torch.zeros((R, cap), **f64)
+        self.counter = torch.zeros(R, **i64)
+        self.last = torch.zeros((R, 2), **f64)  # {potential, kinetic} energy of every replica's last step
+        self.rung_of_replica = torch.arange(R, dtype=torch.int32, device=self.dev)
+        self.replica_at_rung = torch.arange(R, dtype=torch.int32, device=self.dev)
+        self.attempts = torch.zeros(1, **i64)
+        self.scale = torch.ones(R, **f64)
+        self.exchange_capacity = cap
+        self.records = torch.zeros(cap * EXCHANGE_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        p = lambda t: t.data_ptr()  # noqa: E731
+        self._g = _GroupArgs(n, R, p(self.x), p(self.v), p(self.frc), p(self.x0), p(self.hdt_m1), p(self.mass1), p(self.kT),
+                             p(self.seed_words), self.c1, self.dt, self.k, p(self.e_agbnp), p(self.acc), p(self.done), p(self.log_pe),
+                             p(self.log_ke), p(self.counter), cap, p(self.last))
+        self._e = _ExchangeArgs(n, R, p(self.v), p(self.kT), p(self.rung_of_replica), p(self.replica_at_rung), p(self.last),
+                                p(self.counter), p(self.attempts), p(self.scale), p(self.records), self.exchange_capacity,
+                                self.exchange_seed & 0xFFFFFFFFFFFFFFFF)
+        # the group call's arguments never change: member r's buffers are slices of the strided arrays
+        for k in kernels:
+            k._need()
+        vpR = C.c_void_p * R
+        self._handles = vpR(*[k._h for k in kernels])
+        self._pos = vpR(*[p(self.x[r]) for r in range(R)])
+        self._frc = vpR(*[p(self.frc[r]) for r in range(R)])
+        self._ene = vpR(*[p(self.e_agbnp[r:r + 1]) for r in range(R)])
+        self.stream = torch.cuda.Stream(device=self.dev)  # everything of this driver is enqueued here
+        self.steps_done = 0
+
+    # ---- launches
+    @staticmethod
+    def _check(rc):
+        if rc != 0:
+            raise RuntimeError(f"libagbnp_md.so: launch failed (hipError {rc})")
+
+    def _evaluate(self, st):
+        """agbnp_hip_execute_group of all members on stream `st`: forces and energies are added to frc[r], e_agbnp[r]."""
+        from . import _lib
+        rc = _lib.load().agbnp_hip_execute_group(self._handles, self.R, self._pos, self._frc, self._ene, C.c_void_p(st))
+        if rc != _lib.OK:
+            raise RuntimeError("agbnp_hip_execute_group: " + _lib.last_error(self.kernels[0]._h))
+
+    def finish(self):
+        """Every member's finish() on the driver's stream: withheld evaluations per replica since the last call."""
+        st = self.stream.cuda_stream
+        return np.array([k.finish(st) for k in self.kernels], dtype=np.int64)
+
+    def forces(self):
+        """Tethers + AGBNP of every replica at the current positions: frc[r], last[r, 0].  Waits for the result."""
+        torch = self.torch
+        lib, st = _md_group_lib(), self.stream.cuda_stream
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self.e_agbnp.zero_()
+            self._check(lib.agbnp_md_group_tethers(C.byref(self._g), self.parts[0].data_ptr(), st))
+            self._evaluate(st)
+            self.last[:, 0] = self.parts[0].sum(dim=1) + self.e_agbnp
+            self.e_agbnp.zero_()  # (a step that follows starts its own sum)
+        self.stream.synchronize()
+
+    def settle(self):
+        """Outside any timing: first evaluations (allocations, capacity negotiation, forest packing, the group's argument
+        blocks), until every member's finish() reports nothing withheld."""
+        for _ in range(8):
+            for _ in range(3):
+                self.forces()
+            if not self.finish().any():
+                break
+        else:
+            raise RuntimeError("AGBNP capacity negotiation did not converge")
+        self.torch.cuda.synchronize()
+
+    def _steps(self, kind, steps, st):
+        """`steps` consecutive steps of all replicas: front halves, then (group evaluation, back halves + next front halves in
+        one launch) between the steps, group evaluation, back halves: 5 + 1 launches per step."""
+        lib, g = _md_group_lib(), C.byref(self._g)
+        parts = (self.parts[0].data_ptr(), self.parts[1].data_ptr())
+        self._check(lib.agbnp_md_group_pre(g, kind, parts[0], st))
+        for j in range(steps):
+            self._evaluate(st)
+            if j + 1 < steps:
+                self._check(lib.agbnp_md_group_mid(g, kind, parts[j % 2], parts[(j + 1) % 2], st))
+            else:
+                self._check(lib.agbnp_md_group_post(g, parts[j % 2], st))
+
+    def exchange(self):
+        """One exchange attempt between neighbouring rungs, enqueued on the driver's stream (two launches, nothing read)."""
+        self._check(_md_group_lib().agbnp_md_exchange(C.byref(self._e), self.stream.cuda_stream))
+
+    def run(self, nsteps, kind="langevin", exchange_every=0, check_every=1000, on_report=None):
+        """`nsteps` steps of every replica, an exchange attempt after every `exchange_every` of them (0: none); every
+        `check_every` steps (and at the end) synchronises and reads every member's overflow log.  Returns, per replica, the
+        number of steps whose AGBNP contribution was withheld (all zeros in a healthy run; an exchange decided on such a step
+        used a potential energy without the AGBNP term)."""
+        torch = self.torch
+        code = {"langevin": 0, "verlet": 1}[kind]
+        exchange_every, check_every = int(exchange_every), max(1, int(check_every))
+        st = self.stream.cuda_stream
+        missed = np.zeros(self.R, dtype=np.int64)
+        done = since_exchange = since_check = 0
+        self.stream.wait_stream(torch.cuda.current_stream())
+        while done < nsteps:
+            chunk = min(nsteps - done, check_every - since_check)
+            if exchange_every > 0:
+                chunk = min(chunk, exchange_every - since_exchange)
+            self._steps(code, chunk, st)
+            done += chunk
+            since_exchange += chunk
+            since_check += chunk
+            self.steps_done += chunk
+            if exchange_every > 0 and since_exchange == exchange_every:
+                self.exchange()
+                since_exchange = 0
+            if since_check == check_every or done == nsteps:
+                missed += self.finish()
+                since_check = 0
+                if on_report:
+                    on_report(self)
+        self.stream.synchronize()
+        return missed
+
+    # ---- observables (each waits for the driver's stream)
+    def energies(self, last=None):
+        """(potential[R, steps], kinetic[R, steps]) of the recorded steps as numpy arrays."""
+        self.stream.synchronize()
+        n = min(int(self.counter.max().item()), self.log_capacity)
+        pe, ke = self.log_pe[:, :n].cpu().numpy(), self.log_ke[:, :n].cpu().numpy()
+        if last:
+            pe, ke = pe[:, -last:], ke[:, -last:]
+        return pe, ke
+
+    def temperatures(self):
+        """The current bath temperature (K) of every replica."""
+        self.stream.synchronize()
+        return self.kT.cpu().numpy() / KB
+
+    def rungs(self):
+        """rung_of_replica: the rung of the ladder every replica sits on."""
+        self.stream.synchronize()
+        return self.rung_of_replica.cpu().numpy()
+
+    def exchange_log(self):
+        """One record (EXCHANGE_RECORD) per attempted pair, in the order of the attempts."""
+        self.stream.synchronize()
+        a, R = int(self.attempts.item()), self.R
+        count = min(((a + 1) // 2) * (R // 2) + (a // 2) * ((R - 1) // 2), self.exchange_capacity)
+        raw = self.records[:count * EXCHANGE_RECORD.itemsize].cpu().numpy()
+        return raw.view(EXCHANGE_RECORD).copy()
+
+    def acceptance(self):
+        """accepted / attempted per rung pair (k, k + 1), k = 0 .. R - 2 (nan where nothing was attempted)."""
+        log = self.exchange_log()
+        tried = np.bincount(log["rung"], minlength=self.R - 1)[:max(self.R - 1, 0)].astype(float)
+        took = np.bincount(log["rung"], weights=log["accepted"], minlength=self.R - 1)[:max(self.R - 1, 0)]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(tried > 0, took / tried, np.nan)

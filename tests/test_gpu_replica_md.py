@@ -1,0 +1,261 @@
+"""GPU box: ReplicaMD (openmm_agbnp_plugin_amd/md.py) -- R replicas of trpcage (version 1) advanced by the group
+forms of the integrator kernels around agbnp_hip_execute_group, with temperature exchanges decided on the device.  Every replica
+must do what a DeviceMD of its own does; every exchange decision must be the one the host restatements give.  All tolerances
+are those of tests/test_md_examples.py."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import openmm_agbnp_plugin_amd as P
+from tests.gpu_helpers import five_groups as five  # noqa: F401
+from tests.gpu_helpers import kernel_of as _kernel
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _replicas(s, temperatures, **kw):
+    from openmm_agbnp_plugin_amd.md import ReplicaMD
+    ks = [_kernel(s.params()) for _ in temperatures]
+    rep = ReplicaMD(s, ks, temperatures, **kw)
+    rep.settle()
+    return rep, ks
+
+
+def _start(rep):
+    rep.forces()
+    assert not rep.finish().any()
+
+
+def _against_device_md(s, kind, temperatures, seeds):
+    """R = 3 replicas from distinct perturbed states against three DeviceMD runs alone, each on a context of its own, over 20
+    steps: positions to 1e-11 nm, velocities to 1e-9 nm/ps, logged energies to 1e-7 kJ/mol (the bounds of
+    test_fused_integrator_steps_are_the_torch_steps)."""
+    from openmm_agbnp_plugin_amd.md import DeviceMD
+    rep, _ = _replicas(s, temperatures, seeds=seeds)
+    torch = rep.torch
+    for r in range(rep.R):
+        rep.x[r].add_(0.002 * torch.sin(rep.x[r] * (37.0 + 3.0 * r)))  # off the tether minimum, every replica elsewhere
+    alone = []
+    for r in range(rep.R):
+        k = _kernel(s.params())
+        md = DeviceMD(s, k, k_tether=2.0e4, dt=0.001, temperature=temperatures[r], seed=seeds[r])
+        md.settle()
+        assert torch.equal(md.v, rep.v[r])  # (a replica starts as the single driver with its seed and temperature starts)
+        md.x.copy_(rep.x[r])
+        md.v.copy_(rep.v[r])
+        md.forces()
+        assert k.finish() == 0
+        e0 = float(md.ene)
+        assert md.run(20, kind, check_every=20) == 0
+        alone.append((e0, md.x.cpu().numpy(), md.v.cpu().numpy()) + md.energies())
+    _start(rep)
+    e0 = rep.last[:, 0].cpu().numpy()
+    assert not rep.run(20, kind, check_every=20).any()
+    pot, kin = rep.energies()
+    assert pot.shape == kin.shape == (rep.R, 20)
+    x, v = rep.x.cpu().numpy(), rep.v.cpu().numpy()
+    for r, (e0a, xa, va, pa, ka) in enumerate(alone):
+        dx, dv = np.abs(x[r] - xa).max(), np.abs(v[r] - va).max()
+        dp, dk = np.abs(pot[r] - pa).max(), np.abs(kin[r] - ka).max()
+        print(f"{kind} replica {r}: |dx| {dx:.2e} nm  |dv| {dv:.2e} nm/ps  |dU| {dp:.2e}  |dK| {dk:.2e} kJ/mol")
+        assert abs(e0[r] - e0a) < 1e-8 * abs(e0a)
+        assert dx < 1e-11 and dv < 1e-9
+        assert dp < 1e-7 and dk < 1e-7
+    assert np.abs(x[0] - x[1]).max() > 1e-4  # (the replicas are not copies of one another)
+
+
+def test_verlet_replicas_are_device_md_runs(gpu_required, systems):
+    pytest.importorskip("torch")
+    _against_device_md(systems("trpcage"), "verlet", [300.0, 300.0, 300.0], [5, 6, 7])
+
+
+def test_langevin_replicas_are_device_md_runs(gpu_required, systems):
+    """The same with Langevin steps against DeviceMD(seed=seeds[r], temperature=T_r): the Philox keying per replica and the noise
+    amplitude formed in the kernel from kT[r] are the single driver's up to rounding."""
+    pytest.importorskip("torch")
+    _against_device_md(systems("trpcage"), "langevin", [280.0, 300.0, 320.0], [5, 6, 7])
+
+
+def test_nve_energy_conservation_per_replica(gpu_required, systems):
+    """R = 2 from different starts: 500 Langevin steps, then 3000 velocity-Verlet steps, nothing withheld; per replica the total
+    energy fluctuates by less than 2 % and drifts by less than 0.3 % of the mean kinetic energy (the bounds of
+    test_nve_energy_conservation_trpcage)."""
+    pytest.importorskip("torch")
+    rep, _ = _replicas(systems("trpcage"), [300.0, 320.0], seeds=[3, 4])
+    _start(rep)
+    assert not rep.run(500, "langevin", check_every=500).any()
+    assert not rep.run(3000, "verlet", check_every=1000).any()
+    pot, kin = rep.energies(last=3000)
+    assert pot.shape == (2, 3000)
+    for r in range(2):
+        total = pot[r] + kin[r]
+        ke = kin[r].mean()
+        q = len(total) // 4
+        drift = abs(total[-q:].mean() - total[:q].mean())
+        fluct = np.abs(total - total[0]).max()
+        print(f"replica {r}: <K> {ke:.1f}  fluctuation {fluct:.3f}  drift {drift:.3f} kJ/mol")
+        assert ke > 300.0
+        assert fluct < 0.02 * ke, "total energy fluctuates by more than 2 % of the kinetic energy"
+        assert drift < 0.003 * ke, f"total energy drifts: {drift:.3f} kJ/mol over 3 ps"
+        assert np.ptp(pot[r]) > 10 * fluct
+
+
+def test_every_replica_holds_its_own_bath(gpu_required, systems):
+    """R = 4 on the ladder 250 / 300 / 360 / 432 K, friction 10 / ps, cold start, 2000 steps without exchanges: every replica's
+    mean kinetic temperature over the last 800 steps is within 6.7 % of its bath (the +-20 K at 300 K of
+    test_fused_langevin_holds_the_temperature), and the four means increase strictly."""
+    pytest.importorskip("torch")
+    from openmm_agbnp_plugin_amd.md import KB
+    s = systems("trpcage")
+    ladder = [250.0, 300.0, 360.0, 432.0]
+    rep, _ = _replicas(s, ladder, friction=10.0, seeds=[11, 12, 13, 14])
+    rep.v.zero_()
+    _start(rep)
+    assert not rep.run(2000, "langevin", check_every=1000).any()
+    _, kin = rep.energies(last=800)
+    temps = 2.0 * kin.mean(axis=1) / (3 * s.n * KB)
+    print("kinetic temperatures:", temps)
+    for t, bath in zip(temps, ladder):
+        assert abs(t - bath) < 0.067 * bath, f"temperature {t:.1f} K in a bath of {bath:.0f} K"
+    assert np.all(np.diff(temps) > 0.0)
+    assert np.array_equal(rep.temperatures(), np.array([KB * t for t in ladder]) / KB) and list(rep.rungs()) == [0, 1, 2, 3]
+
+
+def test_exchange_decisions_are_the_hosts(gpu_required, systems):
+    """R = 4 on a geometric ladder of ratio 1.03 from 300 K (chosen once: for trpcage's 816 tethered degrees of freedom the
+    energy distributions of neighbouring rungs then overlap widely, Delta = O(1) of either sign), an attempt every 10 steps, 200
+    attempts.  Every record names the energies the replicas logged for the step just finished, bit for bit; its deviate is the
+    host's; its verdict is log(u) <= Delta recomputed in numpy (records with |log u - Delta| < 1e-12 max(1, |Delta|) are not
+    judged, and they must be fewer than 1 %); after every attempt the rungs are a permutation and the temperatures the ladder's."""
+    pytest.importorskip("torch")
+    from openmm_agbnp_plugin_amd.md import KB, exchange_delta, exchange_uniform
+    s = systems("trpcage")
+    ladder = [300.0 * 1.03 ** k for k in range(4)]
+    kT_ladder = np.array([KB * t for t in ladder])
+    seed = 0x1234567890ABCDEF
+    rep, _ = _replicas(s, ladder, seeds=[21, 22, 23, 24], exchange_seed=seed)
+    _start(rep)
+    attempts = 200
+    for a in range(attempts):
+        assert not rep.run(10, "langevin", exchange_every=10, check_every=10).any()
+        rungs = rep.rungs()
+        assert sorted(rungs) == [0, 1, 2, 3]
+        kT = rep.kT.cpu().numpy()
+        assert np.array_equal(np.sort(kT), kT_ladder)
+        assert np.array_equal(kT, kT_ladder[rungs])  # a replica's bath is its rung's
+        assert np.array_equal(rep.replica_at_rung.cpu().numpy()[rungs], np.arange(4))
+    log = rep.exchange_log()
+    assert len(log) == (attempts // 2) * 2 + (attempts // 2) * 1  # even attempts: pairs (0,1), (2,3); odd ones: (1,2)
+    pot, _ = rep.energies()
+    assert pot.shape == (4, 10 * attempts)
+    skipped = 0
+    sitting = np.arange(4)  # replica_at_rung, replayed from the log
+    for rec in log:
+        a, k, lo, hi = int(rec["attempt"]), int(rec["rung"]), int(rec["replica_lo"]), int(rec["replica_hi"])
+        assert k % 2 == a % 2 and 0 <= k < 3
+        assert (sitting[k], sitting[k + 1]) == (lo, hi)
+        step = int(rec["step"])
+        assert step == 10 * (a + 1)
+        assert rec["U_lo"] == pot[lo, step - 1] and rec["U_hi"] == pot[hi, step - 1]
+        assert rec["kT_lo"] == kT_ladder[k] and rec["kT_hi"] == kT_ladder[k + 1]
+        assert rec["u"] == exchange_uniform(k, a, seed)
+        delta = exchange_delta(rec["kT_lo"], rec["kT_hi"], rec["U_lo"], rec["U_hi"])
+        if abs(np.log(rec["u"]) - delta) < 1e-12 * max(1.0, abs(delta)):
+            skipped += 1
+        else:
+            assert bool(rec["accepted"]) == bool(np.log(rec["u"]) <= delta)
+        if rec["accepted"]:
+            sitting[k], sitting[k + 1] = hi, lo
+    assert skipped < 0.01 * len(log)
+    assert np.array_equal(sitting, rep.replica_at_rung.cpu().numpy())
+    accepted = int(log["accepted"].sum())
+    print(f"{accepted} of {len(log)} exchanges accepted; acceptance per pair {rep.acceptance()}")
+    assert 0 < accepted < len(log)
+    acc = rep.acceptance()
+    for k in range(3):
+        sel = log["rung"] == k
+        assert acc[k] == log["accepted"][sel].sum() / sel.sum()
+
+
+def test_a_certain_exchange_swaps_baths_and_rescales(gpu_required, systems):
+    """Two replicas at 300 and 400 K, the colder one pushed up in energy: Delta > 0, the attempt is accepted whatever u is; kT and
+    rungs are swapped, every velocity is its old value times sqrt(T_new / T_old), positions and forces are untouched."""
+    pytest.importorskip("torch")
+    from openmm_agbnp_plugin_amd.md import KB, exchange_delta
+    s = systems("trpcage")
+    rep, _ = _replicas(s, [300.0, 400.0], seeds=[31, 32])
+    rep.x[0].add_(0.01 * rep.torch.sin(rep.x[0] * 37.0))  # ~400 kJ/mol of tether energy
+    _start(rep)
+    u_pot = rep.last[:, 0].cpu().numpy()
+    kT0 = rep.kT.cpu().numpy()
+    assert u_pot[0] > u_pot[1] and kT0[0] < kT0[1]
+    assert exchange_delta(kT0[0], kT0[1], u_pot[0], u_pot[1]) > 0.0
+    x0, v0, f0 = rep.x.cpu().numpy(), rep.v.cpu().numpy(), rep.frc.cpu().numpy()
+    rep.exchange()
+    log = rep.exchange_log()
+    assert len(log) == 1 and log[0]["accepted"] == 1 and (log[0]["replica_lo"], log[0]["replica_hi"]) == (0, 1)
+    assert log[0]["U_lo"] == u_pot[0] and log[0]["U_hi"] == u_pot[1]
+    kT1 = rep.kT.cpu().numpy()
+    assert np.array_equal(kT1, kT0[::-1]) and list(rep.rungs()) == [1, 0]
+    assert list(rep.replica_at_rung.cpu().numpy()) == [1, 0]
+    assert np.allclose(rep.temperatures(), [400.0, 300.0], rtol=1e-14)
+    v1 = rep.v.cpu().numpy()
+    for r in range(2):
+        want = v0[r] * np.sqrt(kT1[r] / kT0[r])
+        assert np.abs(v1[r] - want).max() <= 1e-15 * np.abs(want).max()
+        assert np.all(np.abs(v1[r] - want) <= 1e-15 * np.abs(want))
+    assert np.array_equal(rep.x.cpu().numpy(), x0) and np.array_equal(rep.frc.cpu().numpy(), f0)
+    # the next attempt (odd: pairs from rung 1 on) has no pair at R = 2 and changes nothing
+    rep.exchange()
+    assert len(rep.exchange_log()) == 1 and np.array_equal(rep.v.cpu().numpy(), v1)
+
+
+def test_equal_temperatures_accept_every_attempt(gpu_required, systems):
+    """Delta == 0 and log u <= 0: every attempt is accepted, and the velocity factor is exactly one."""
+    pytest.importorskip("torch")
+    rep, _ = _replicas(systems("trpcage"), [300.0] * 4, seeds=[41, 42, 43, 44], exchange_seed=9)
+    _start(rep)
+    assert not rep.run(100, "langevin", exchange_every=10, check_every=100).any()
+    log = rep.exchange_log()
+    assert len(log) == 15 and np.all(log["accepted"] == 1)
+    assert sorted(rep.rungs()) == [0, 1, 2, 3] and np.all(rep.temperatures() == rep.temperatures()[0])
+    assert np.all(rep.acceptance() == 1.0)
+
+
+def test_a_withheld_member_is_reported_as_that_member(gpu_required, systems, five):
+    """Replica 1 is displaced by 0.1 nm between two evaluations (the jump of test_a_jump_is_withheld_for_that_member_only): run()
+    names it and nobody else; after the repeat the next chunk is complete for everyone."""
+    pytest.importorskip("torch")
+    rep, _ = _replicas(systems("trpcage"), [300.0, 300.0, 300.0], seeds=[51, 52, 53])
+    _start(rep)
+    rep.x[1, :, 0].add_(0.1)
+    assert list(rep.run(1, "verlet", check_every=1)) == [0, 1, 0]
+    _start(rep)  # the repeat: forces at the positions the replicas now have
+    assert list(rep.run(10, "verlet", check_every=10)) == [0, 0, 0]
+
+
+def test_a_steady_run_rewrites_no_argument_block(gpu_required, systems, five):
+    """Member r's position buffer is a fixed slice: after 200 steps scalar 21 (group_block_writes) of every member reads what it
+    read after the first two, and scalar 19 says all R share one launch set."""
+    pytest.importorskip("torch")
+    R = 4
+    rep, ks = _replicas(systems("trpcage"), [300.0 * 1.03 ** k for k in range(R)])
+    _start(rep)
+    assert not rep.run(2, "langevin", check_every=2).any()
+    writes = [int(k.scalar("group_block_writes")) for k in ks]
+    assert not rep.run(198, "langevin", exchange_every=20, check_every=99).any()
+    assert [int(k.scalar("group_block_writes")) for k in ks] == writes
+    assert [int(k.scalar("group_members")) for k in ks] == [R] * R
+    assert len(rep.exchange_log()) > 0
+
+
+def test_the_example_script_runs(gpu_required):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "remd_benchmark.py"), "trpcage", "4", "1000", "50"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "ns/day aggregate" in out.stdout and "acceptance" in out.stdout
+    assert "WARNING" not in out.stdout
