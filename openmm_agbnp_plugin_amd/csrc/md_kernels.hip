@@ -1,22 +1,74 @@
-// Integrator steps for the device-resident MD driver of the example scripts (openmm_agbnp_plugin_amd/md.py; the py3
-// counterparts of the reference's example/1dwc_benchmark.py and example/test_agbnp.py).  NOT part of the drop-in boundary
-// (include/agbnp_hip.h): in the reference the integrator is OpenMM's.  A step written in torch operations is seventeen tiny
-// launches around the six of the AGBNP evaluation (0.163 ms per step of 1dwc against 0.104 for the evaluation alone); here
-// it is two: everything in front of the force evaluation, everything behind it.
+// Integrator steps for the device-resident MD drivers of the example scripts (openmm_agbnp_plugin_amd/md.py: DeviceMD and
+// ReplicaMD; the py3 counterparts of the reference's example/1dwc_benchmark.py and example/test_agbnp.py).  NOT part of the
+// drop-in boundary (include/agbnp_hip.h): in the reference the integrator is OpenMM's.  A step written in torch operations is
+// seventeen tiny launches around the six of the AGBNP evaluation (0.163 ms per step of 1dwc against 0.104 for the evaluation
+// alone); here it is two: everything in front of the force evaluation, everything behind it -- and between the steps of a run
+// both in one.
 //
-//   pre   Langevin (BAOAB, the reference's LangevinIntegrator(300 K, 1/ps, 1 fs), 1dwc_benchmark.py:20):
-//           v += dt/2m f;  x += dt/2 v;  v = c1 v + c2 xi;  x += dt/2 v
-//         velocity Verlet (the reference's NVE check, test_agbnp.py:57):   v += dt/2m f;  x += dt v
-//         then the tethers, the only force-field term besides AGBNP:  f = -k (x - x0), their energy as per-block partials
-//   post  v += dt/2m f (f now holds tethers + AGBNP);  kinetic energy;  potential = tether partials + what the engine added
-//         to the energy word;  both go into the per-step logs;  the energy word and the accumulators are handed back as zeros
+// Every kernel advances R >= 1 replicas of ONE system in one launch; a single trajectory is a group of one.
+// State is strided ([R][n][3], [R][blocks], [R]...): replica r's buffers are fixed slices, the arguments travel as one struct by
+// value (AgbnpMdGroup).  The grid is R x blocks(n) workgroups of one thread per atom; a workgroup's replica is
+// blockIdx.x / blocks (uniform), and a replica's sums are taken in a fixed order inside its own blocks(n) workgroups, so they
+// do not depend on R.
 //
-// Normal deviates: Philox4x32-10 keyed by the seed, counter = (step number on the device, atom), Box-Muller in FP64 on
-// 53-bit uniforms: the stream of a run depends on nothing but the seed (graph replays included: the step number is read
-// from device memory).
+//   pre      Langevin (BAOAB, the reference's LangevinIntegrator(300 K, 1/ps, 1 fs), 1dwc_benchmark.py:20):
+//              v += dt/2m f;  x += dt/2 v;  v = c1 v + cn xi;  x += dt/2 v,   cn = sqrt((1 - c1^2) kT[r] / m)
+//            velocity Verlet (the reference's NVE check, test_agbnp.py:57):   v += dt/2m f;  x += dt v
+//            then the tethers, the only force-field term besides AGBNP:  f = -k (x - x0), their energy as per-block partials
+//   post     v += dt/2m f (f now holds tethers + AGBNP);  kinetic energy;  potential = tether partials + what the engine added
+//            to the replica's energy word;  the replica's last workgroup to arrive writes both into the per-step logs and hands
+//            the energy word and the accumulators back as zeros
+//   mid      between two force evaluations of a run of steps: post of step n and pre of step n + 1 in ONE launch
+//   tethers  the tethers alone (the first force evaluation of a run, and the minimiser's)
+//
+// The bath temperature is a device word per replica (kT[r], kJ/mol), which an exchange swaps without the host: that is why the
+// noise amplitude is formed in the kernel.  Normal deviates: Philox4x32-10 keyed by seeds[r], counter = (atom, step number on
+// the device lo, hi, 0|1), Box-Muller in FP64 on 53-bit uniforms: the stream of a run depends on nothing but the seed (graph
+// replays included: the step number is read from device memory).
+//
+// Exchange (temperature replica exchange between neighbouring rungs of the ladder): k_md_exchange_decide, ONE workgroup,
+// one thread per pair (k, k + 1), k = a mod 2, a mod 2 + 2, ...: the pairs of an attempt are disjoint, so every thread reads and
+// writes its own two replicas' words; it leaves a velocity factor per replica (1 where nothing happened), and
+// k_md_exchange_apply, a launch of its own behind it, rescales -- no workgroup of the second launch can see a half-made decision.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+struct AgbnpMdGroup {  // (mirrored field for field by md.py::_GroupArgs)
+  int n, replicas;
+  double *x, *v, *f;                // [R][n][3]
+  const double *x0, *hdt_m, *mass;  // [n][3], [n], [n]: the one system's tether anchors, dt / 2m, m
+  const double* kT;                 // [R] bath temperatures in kJ/mol
+  const unsigned long long* seeds;  // [R] Philox keys
+  double c1, dt, ktether;           // exp(-friction dt), step, tether constant
+  double* energy;                   // [R] the words agbnp_hip_execute_group adds the AGBNP energies to
+  double* acc;                      // [R][2] kinetic-energy accumulators
+  unsigned* done;                   // [R] workgroups of the replica that have arrived
+  double *log_pe, *log_ke;          // [R][capacity]
+  long long* step;                  // [R]
+  long long capacity;
+  double* last;                     // [R][2] {potential, kinetic} energy of the last step
+};
+
+struct AgbnpMdExchangeRecord {  // (md.py::EXCHANGE_RECORD); 72 bytes, no padding
+  long long attempt, step;      // step: steps replica_lo had finished
+  int rung, replica_lo, replica_hi, accepted;
+  double u_lo, u_hi, kT_lo, kT_hi, u;  // potential energies and bath temperatures (kJ/mol) BEFORE the decision
+};
+
+struct AgbnpMdExchange {  // (md.py::_ExchangeArgs)
+  int n, replicas;
+  double* v;                 // [R][n][3]
+  double* kT;                // [R]
+  int *rung_of_replica, *replica_at_rung;  // [R] each
+  const double* last;        // [R][2]
+  const long long* step;     // [R]
+  long long* attempts;       // [1]
+  double* scale;             // [R] velocity factors of the attempt in flight
+  AgbnpMdExchangeRecord* log;
+  long long log_capacity;
+  unsigned long long seed;
+};
 
 namespace {
 
@@ -57,265 +109,11 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return r;
 }
 
-// the front half of a step for atom i, velocity pv already kicked: drift (+ OU for Langevin), tethers; returns the atom's
-// tether energy.  kind 0: Langevin (BAOAB), 1: velocity Verlet
+// the front half of a step for atom i of one replica, velocity pv already kicked: drift (+ OU for Langevin at the replica's bath
+// temperature), tethers; returns the atom's tether energy.  kind 0: Langevin (BAOAB), 1: velocity Verlet
 __device__ __forceinline__ double front_half(int i, int kind, double (&px)[3], double (&pv)[3], double* __restrict__ x, double* __restrict__ v,
-                                             double* __restrict__ f, const double* __restrict__ x0, const double* __restrict__ c2, double c1,
+                                             double* __restrict__ f, const double* __restrict__ x0, double kT, double mass, double c1,
                                              double dt, double ktether, unsigned long long seed, unsigned long long s) {
-  if (kind == 0) {
-    const Philox a = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const Philox b = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    double z[4];
-    box_muller(uniform53(a.c[0], a.c[1]), uniform53(a.c[2], a.c[3]), z[0], z[1]);
-    box_muller(uniform53(b.c[0], b.c[1]), uniform53(b.c[2], b.c[3]), z[2], z[3]);
-    const double cn = c2[i];
-    for (int d = 0; d < 3; d++) {
-      px[d] = fma(0.5 * dt, pv[d], px[d]);
-      pv[d] = fma(c1, pv[d], cn * z[d]);
-      px[d] = fma(0.5 * dt, pv[d], px[d]);
-    }
-  } else {
-    for (int d = 0; d < 3; d++) px[d] = fma(dt, pv[d], px[d]);
-  }
-  double e = 0.0;
-  for (int d = 0; d < 3; d++) {
-    const double dd = px[d] - x0[3 * i + d];
-    x[3 * i + d] = px[d];
-    v[3 * i + d] = pv[d];
-    f[3 * i + d] = -ktether * dd;
-    e = fma(0.5 * ktether * dd, dd, e);
-  }
-  return e;
-}
-
-// one thread per atom: everything in front of the force evaluation of a step
-__global__ __launch_bounds__(kBlock) void k_md_pre(int n, int kind, double* __restrict__ x, double* __restrict__ v, double* __restrict__ f,
-                                                  const double* __restrict__ x0, const double* __restrict__ hdt_m,
-                                                  const double* __restrict__ c2, double c1, double dt, double ktether,
-                                                  unsigned long long seed, const long long* __restrict__ step,
-                                                  double* __restrict__ tether_part) {
-  __shared__ double red[kBlock / 64];
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  double e = 0.0;
-  if (i < n) {
-    const double h = hdt_m[i];
-    double px[3], pv[3];
-    for (int d = 0; d < 3; d++) px[d] = x[3 * i + d], pv[d] = fma(h, f[3 * i + d], v[3 * i + d]);
-    e = front_half(i, kind, px, pv, x, v, f, x0, c2, c1, dt, ktether, seed, (unsigned long long)step[0]);
-  }
-  e = block_sum(e, red);
-  if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
-}
-
-// acc: {kinetic energy sum, -} (doubles), done: blocks that have added theirs.  The last block to arrive writes the logs.
-__global__ __launch_bounds__(kBlock) void k_md_post(int n, double* __restrict__ v, const double* __restrict__ f, const double* __restrict__ hdt_m,
-                                                   const double* __restrict__ mass, double* __restrict__ energy,
-                                                   const double* __restrict__ tether_part, double* __restrict__ acc,
-                                                   unsigned* __restrict__ done, double* __restrict__ log_pe, double* __restrict__ log_ke,
-                                                   long long* __restrict__ step, long long capacity, double* __restrict__ last) {
-  __shared__ double red[kBlock / 64];
-  __shared__ bool s_last;
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  double ke = 0.0;
-  if (i < n) {
-    const double h = hdt_m[i], m = mass[i];
-    for (int d = 0; d < 3; d++) {
-      const double pv = fma(h, f[3 * i + d], v[3 * i + d]);
-      v[3 * i + d] = pv;
-      ke = fma(0.5 * m * pv, pv, ke);
-    }
-  }
-  ke = block_sum(ke, red);
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(&acc[0], ke, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    s_last = atomicAdd(done, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  // tether energy: the pre kernel's per-block partials in fixed order (its grid is this kernel's)
-  double et = 0.0;
-  for (int b = threadIdx.x; b < (int)gridDim.x; b += kBlock) et += tether_part[b];
-  et = block_sum(et, red);
-  if (threadIdx.x == 0) {
-    __threadfence();
-    const double kin = __hip_atomic_load(&acc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double pot = et + energy[0];  // (what the AGBNP evaluation added to the word since it was last handed back as zero)
-    const long long s = step[0];
-    if (s < capacity) log_pe[s] = pot, log_ke[s] = kin;
-    last[0] = pot, last[1] = kin;
-    step[0] = s + 1;
-    energy[0] = 0.0;
-    acc[0] = 0.0;
-    *done = 0u;
-  }
-}
-
-// Between two force evaluations of a run of steps: the back half of step n (second kick, energies logged) and the front
-// half of step n + 1 in ONE launch.  The tether partials are double-buffered (the workgroup that arrives last sums step n's
-// while the others already write step n + 1's): part_old is read, part_new written.
-__global__ __launch_bounds__(kBlock) void k_md_mid(int n, int kind, double* __restrict__ x, double* __restrict__ v, double* __restrict__ f,
-                                                  const double* __restrict__ x0, const double* __restrict__ hdt_m, const double* __restrict__ mass,
-                                                  const double* __restrict__ c2, double c1, double dt, double ktether, unsigned long long seed,
-                                                  double* __restrict__ energy, const double* __restrict__ part_old, double* __restrict__ part_new,
-                                                  double* __restrict__ acc, unsigned* __restrict__ done, double* __restrict__ log_pe,
-                                                  double* __restrict__ log_ke, long long* __restrict__ step, long long capacity,
-                                                  double* __restrict__ last) {
-  __shared__ double red[kBlock / 64];
-  __shared__ bool s_last;
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  const unsigned long long s = (unsigned long long)step[0];  // (step n: read before this workgroup counts itself in)
-  double ke = 0.0, e = 0.0;
-  if (i < n) {
-    const double h = hdt_m[i], m = mass[i];
-    double px[3], pv[3];
-    for (int d = 0; d < 3; d++) {
-      const double fd = f[3 * i + d];
-      const double v1 = fma(h, fd, v[3 * i + d]);  // end of step n
-      ke = fma(0.5 * m * v1, v1, ke);
-      pv[d] = fma(h, fd, v1);                       // first kick of step n + 1: the same force
-      px[d] = x[3 * i + d];
-    }
-    e = front_half(i, kind, px, pv, x, v, f, x0, c2, c1, dt, ktether, seed, s + 1);
-  }
-  ke = block_sum(ke, red);
-  e = block_sum(e, red);
-  if (threadIdx.x == 0) {
-    part_new[blockIdx.x] = e;
-    __hip_atomic_fetch_add(&acc[0], ke, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    s_last = atomicAdd(done, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  double et = 0.0;
-  for (int b = threadIdx.x; b < (int)gridDim.x; b += kBlock) et += part_old[b];
-  et = block_sum(et, red);
-  if (threadIdx.x == 0) {
-    __threadfence();
-    const double kin = __hip_atomic_load(&acc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double pot = et + energy[0];
-    if ((long long)s < capacity) log_pe[s] = pot, log_ke[s] = kin;
-    last[0] = pot, last[1] = kin;
-    step[0] = (long long)s + 1;
-    energy[0] = 0.0;
-    acc[0] = 0.0;
-    *done = 0u;
-  }
-}
-
-// tethers alone (the first force evaluation of a run, and the minimiser's): f = -k (x - x0), partials of their energy
-__global__ __launch_bounds__(kBlock) void k_md_tethers(int n, const double* __restrict__ x, const double* __restrict__ x0, double* __restrict__ f,
-                                                      double ktether, double* __restrict__ tether_part) {
-  __shared__ double red[kBlock / 64];
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  double e = 0.0;
-  if (i < n)
-    for (int d = 0; d < 3; d++) {
-      const double dd = x[3 * i + d] - x0[3 * i + d];
-      f[3 * i + d] = -ktether * dd;
-      e = fma(0.5 * ktether * dd, dd, e);
-    }
-  e = block_sum(e, red);
-  if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
-}
-
-}  // namespace
-
-extern "C" {
-
-int agbnp_md_blocks(int n) { return (n + kBlock - 1) / kBlock; }
-
-int agbnp_md_pre(int n, int kind, double* x, double* v, double* f, const double* x0, const double* hdt_m, const double* c2, double c1,
-                 double dt, double ktether, unsigned long long seed, const long long* step, double* tether_part, void* stream) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_md_pre, dim3(agbnp_md_blocks(n)), dim3(kBlock), 0, (hipStream_t)stream, n, kind, x, v, f, x0, hdt_m, c2, c1, dt, ktether,
-                     seed, step, tether_part);
-  return (int)hipGetLastError();
-}
-
-int agbnp_md_post(int n, double* v, const double* f, const double* hdt_m, const double* mass, double* energy, const double* tether_part,
-                  double* acc, unsigned* done, double* log_pe, double* log_ke, long long* step, long long capacity, double* last,
-                  void* stream) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_md_post, dim3(agbnp_md_blocks(n)), dim3(kBlock), 0, (hipStream_t)stream, n, v, f, hdt_m, mass, energy, tether_part, acc,
-                     done, log_pe, log_ke, step, capacity, last);
-  return (int)hipGetLastError();
-}
-
-int agbnp_md_mid(int n, int kind, double* x, double* v, double* f, const double* x0, const double* hdt_m, const double* mass, const double* c2,
-                 double c1, double dt, double ktether, unsigned long long seed, double* energy, const double* part_old, double* part_new,
-                 double* acc, unsigned* done, double* log_pe, double* log_ke, long long* step, long long capacity, double* last, void* stream) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_md_mid, dim3(agbnp_md_blocks(n)), dim3(kBlock), 0, (hipStream_t)stream, n, kind, x, v, f, x0, hdt_m, mass, c2, c1, dt, ktether,
-                     seed, energy, part_old, part_new, acc, done, log_pe, log_ke, step, capacity, last);
-  return (int)hipGetLastError();
-}
-
-int agbnp_md_tethers(int n, const double* x, const double* x0, double* f, double ktether, double* tether_part, void* stream) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_md_tethers, dim3(agbnp_md_blocks(n)), dim3(kBlock), 0, (hipStream_t)stream, n, x, x0, f, ktether, tether_part);
-  return (int)hipGetLastError();
-}
-
-}  // extern "C"
-
-// ---- Replica groups (openmm_agbnp_plugin_amd/md.py::ReplicaMD) ---------------------------------------------
-// The same steps for R replicas of ONE system in one launch each, around agbnp_hip_execute_group: the grid is R times the
-// single kernels' grid, a workgroup's replica is blockIdx.x / blocks(n) (uniform), and inside a replica the partition into
-// workgroups and the fixed-order sums are the single kernels', so a replica's energies are what k_md_post / k_md_mid log
-// for the same state.  State is strided ([R][n][3], [R][blocks], [R]...): member r's buffers are fixed slices.  What differs
-// from the single kernels: the bath temperature is a device word per replica (kT[r], kJ/mol), which an exchange swaps without
-// the host, so the noise amplitude sqrt((1 - c1^2) kT[r] / m_i) is formed here and not read from a table; the Philox key is
-// seeds[r].
-//
-// Exchange (temperature replica exchange between neighbouring rungs of the ladder): k_md_exchange_decide, ONE workgroup,
-// one thread per pair (k, k + 1), k = a mod 2, a mod 2 + 2, ...: the pairs of an attempt are disjoint, so every thread reads and
-// writes its own two replicas' words; it leaves a velocity factor per replica (1 where nothing happened), and
-// k_md_exchange_apply, a launch of its own behind it, rescales -- no workgroup of the second launch can see a half-made decision.
-
-struct AgbnpMdGroup {  // (mirrored field for field by md.py::_GroupArgs)
-  int n, replicas;
-  double *x, *v, *f;                // [R][n][3]
-  const double *x0, *hdt_m, *mass;  // [n][3], [n], [n]: the one system's tether anchors, dt / 2m, m
-  const double* kT;                 // [R] bath temperatures in kJ/mol
-  const unsigned long long* seeds;  // [R] Philox keys
-  double c1, dt, ktether;           // exp(-friction dt), step, tether constant
-  double* energy;                   // [R] the words agbnp_hip_execute_group adds the AGBNP energies to
-  double* acc;                      // [R][2] kinetic-energy accumulators
-  unsigned* done;                   // [R] workgroups of the replica that have arrived
-  double *log_pe, *log_ke;          // [R][capacity]
-  long long* step;                  // [R]
-  long long capacity;
-  double* last;                     // [R][2] {potential, kinetic} energy of the last step
-};
-
-struct AgbnpMdExchangeRecord {  // (md.py::EXCHANGE_RECORD); 72 bytes, no padding
-  long long attempt, step;      // step: steps replica_lo had finished
-  int rung, replica_lo, replica_hi, accepted;
-  double u_lo, u_hi, kT_lo, kT_hi, u;  // potential energies and bath temperatures (kJ/mol) BEFORE the decision
-};
-
-struct AgbnpMdExchange {  // (md.py::_ExchangeArgs)
-  int n, replicas;
-  double* v;                 // [R][n][3]
-  double* kT;                // [R]
-  int *rung_of_replica, *replica_at_rung;  // [R] each
-  const double* last;        // [R][2]
-  const long long* step;     // [R]
-  long long* attempts;       // [1]
-  double* scale;             // [R] velocity factors of the attempt in flight
-  AgbnpMdExchangeRecord* log;
-  long long log_capacity;
-  unsigned long long seed;
-};
-
-namespace {
-
-// front_half() with the noise amplitude formed from the replica's bath temperature (the arithmetic is front_half's otherwise)
-__device__ __forceinline__ double front_half_bath(int i, int kind, double (&px)[3], double (&pv)[3], double* __restrict__ x, double* __restrict__ v,
-                                                  double* __restrict__ f, const double* __restrict__ x0, double kT, double mass, double c1,
-                                                  double dt, double ktether, unsigned long long seed, unsigned long long s) {
   if (kind == 0) {
     const Philox a = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
     const Philox b = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -342,8 +140,8 @@ __device__ __forceinline__ double front_half_bath(int i, int kind, double (&px)[
   return e;
 }
 
-// the tail of k_md_post / k_md_mid per replica: the replica's last workgroup to arrive sums step s's energies into the logs
-// and hands the energy word and the accumulators back as zeros
+// the tail of the back half per replica: the replica's last workgroup to arrive sums step s's energies into the logs and hands
+// the energy word and the accumulators back as zeros.  acc[2 r]: the kinetic-energy sum, done[r]: workgroups that have added theirs
 __device__ __forceinline__ void group_log_step(const AgbnpMdGroup& g, int r, int blocks, const double* __restrict__ part, long long s, double ke,
                                                double* red, bool& s_last) {
   if (threadIdx.x == 0) {
@@ -369,6 +167,7 @@ __device__ __forceinline__ void group_log_step(const AgbnpMdGroup& g, int r, int
   }
 }
 
+// one thread per atom: everything in front of the force evaluation of a step
 __global__ __launch_bounds__(kBlock) void k_md_group_pre(AgbnpMdGroup g, int blocks, int kind, double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
   const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
@@ -378,13 +177,14 @@ __global__ __launch_bounds__(kBlock) void k_md_group_pre(AgbnpMdGroup g, int blo
     const double h = g.hdt_m[i];
     double px[3], pv[3];
     for (int d = 0; d < 3; d++) px[d] = g.x[o + 3 * i + d], pv[d] = fma(h, g.f[o + 3 * i + d], g.v[o + 3 * i + d]);
-    e = front_half_bath(i, kind, px, pv, g.x + o, g.v + o, g.f + o, g.x0, g.kT[r], g.mass[i], g.c1, g.dt, g.ktether, g.seeds[r],
-                        (unsigned long long)g.step[r]);
+    e = front_half(i, kind, px, pv, g.x + o, g.v + o, g.f + o, g.x0, g.kT[r], g.mass[i], g.c1, g.dt, g.ktether, g.seeds[r],
+                   (unsigned long long)g.step[r]);
   }
   e = block_sum(e, red);
   if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
 }
 
+// everything behind it; the tether partials are the front half's (its grid is this kernel's)
 __global__ __launch_bounds__(kBlock) void k_md_group_post(AgbnpMdGroup g, int blocks, const double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
   __shared__ bool s_last;
@@ -404,6 +204,9 @@ __global__ __launch_bounds__(kBlock) void k_md_group_post(AgbnpMdGroup g, int bl
   group_log_step(g, r, blocks, tether_part + (size_t)r * blocks, s, ke, red, s_last);
 }
 
+// Between two force evaluations of a run of steps: the back half of step n (second kick, energies logged) and the front
+// half of step n + 1 in ONE launch.  The tether partials are double-buffered (the workgroup that arrives last sums step n's
+// while the others already write step n + 1's): part_old is read, part_new written.
 __global__ __launch_bounds__(kBlock) void k_md_group_mid(AgbnpMdGroup g, int blocks, int kind, const double* __restrict__ part_old,
                                                         double* __restrict__ part_new) {
   __shared__ double red[kBlock / 64];
@@ -422,8 +225,8 @@ __global__ __launch_bounds__(kBlock) void k_md_group_mid(AgbnpMdGroup g, int blo
       pv[d] = fma(h, fd, v1);                             // first kick of step n + 1: the same force
       px[d] = g.x[o + 3 * i + d];
     }
-    e = front_half_bath(i, kind, px, pv, g.x + o, g.v + o, g.f + o, g.x0, g.kT[r], m, g.c1, g.dt, g.ktether, g.seeds[r],
-                        (unsigned long long)s + 1ull);
+    e = front_half(i, kind, px, pv, g.x + o, g.v + o, g.f + o, g.x0, g.kT[r], m, g.c1, g.dt, g.ktether, g.seeds[r],
+                   (unsigned long long)s + 1ull);
   }
   ke = block_sum(ke, red);
   e = block_sum(e, red);
@@ -431,6 +234,7 @@ __global__ __launch_bounds__(kBlock) void k_md_group_mid(AgbnpMdGroup g, int blo
   group_log_step(g, r, blocks, part_old + (size_t)r * blocks, s, ke, red, s_last);
 }
 
+// tethers alone (the first force evaluation of a run, and the minimiser's): f = -k (x - x0), partials of their energy
 __global__ __launch_bounds__(kBlock) void k_md_group_tethers(AgbnpMdGroup g, int blocks, double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
   const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
@@ -491,6 +295,8 @@ inline bool group_ok(const AgbnpMdGroup* g) { return g && g->n > 0 && g->replica
 }  // namespace
 
 extern "C" {
+
+int agbnp_md_blocks(int n) { return (n + kBlock - 1) / kBlock; }
 
 // One launch each for all the replicas of *g (a host struct, read during the call).  tether_part / part_old / part_new:
 // [R][agbnp_md_blocks(n)].  kind 0: Langevin, 1: velocity Verlet.  Return: hipError_t of the launch, 1 for a bad *g.

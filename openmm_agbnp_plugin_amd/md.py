@@ -1,17 +1,20 @@
 """Device-resident molecular dynamics around the AGBNP engine, for the py3 counterparts of the reference's example
 scripts (example/test_agbnp.py: minimise, Langevin equilibration, NVE energy-conservation run; example/1dwc_benchmark.py:
-Langevin timing run) and for the energy-conservation test.
+Langevin timing run), for the energy-conservation test and for replica exchange (examples/remd_benchmark.py).
 
 The reference gets its bonded and Coulomb/LJ terms from OpenMM's OPLS system (DesmondDMSFile.createSystem), which is
 outside this repository; here the only force-field term besides AGBNP is a harmonic tether of every atom to its start
-position, which keeps the geometry a protein.  Everything lives on the GPU (torch tensors for the integrator state,
-`agbnp_hip_execute_device` for the force); one MD step is captured ONCE as a HIP graph and replayed, the host only
-synchronises every `check_every` steps to read the engine's overflow log (agbnp_hip_finish).
+position, which keeps the geometry a protein.  Everything lives on the GPU: torch tensors for the integrator state, the
+engine's device entry points for the force.
 
-The integrator itself is two launches of libagbnp_md.so (csrc/md_kernels.hip: everything in front of the force
-evaluation, everything behind it -- between the steps of a run both in ONE launch; Philox normal deviates) around the six
-of the AGBNP evaluation; written in torch operations it is seventeen (`fused=False`, kept as the cross-check of the
-kernels): 0.163 -> 0.11 ms per step of 1dwc.
+One state core, two drivers.  `_Replicas` holds the state of R >= 1 replicas of one system as strided arrays and makes the
+integrator's launches: two of libagbnp_md.so (csrc/md_kernels.hip: everything in front of the force evaluation, everything
+behind it -- between the steps of a run both in ONE launch; Philox normal deviates) around an evaluation its driver supplies.
+`DeviceMD` is the core at R = 1 around `agbnp_hip_execute_device`, its steps captured ONCE as a HIP graph and replayed; the
+host only synchronises every `check_every` steps to read the engine's overflow log (agbnp_hip_finish).  `ReplicaMD` is the
+core around `agbnp_hip_execute_group`, eager (group calls are not captured), plus temperature exchanges decided on the
+device.  Written in torch operations a step is seventeen launches around the six of the AGBNP evaluation
+(`DeviceMD(fused=False)`, kept as the cross-check of the kernels): 0.163 -> 0.11 ms per step of 1dwc.
 
 PyTorch is plumbing here (device arrays, the graph capture API), not the product.
 """
@@ -21,6 +24,26 @@ import os
 import numpy as np
 
 KB = 0.0083144626  # kJ/mol/K
+
+MAX_REPLICAS = 16  # AGBNP_HIP_MAX_GROUP
+
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+class _GroupArgs(C.Structure):  # AgbnpMdGroup
+    _fields_ = [("n", C.c_int), ("replicas", C.c_int), ("x", C.c_void_p), ("v", C.c_void_p), ("f", C.c_void_p), ("x0", C.c_void_p),
+                ("hdt_m", C.c_void_p), ("mass", C.c_void_p), ("kT", C.c_void_p), ("seeds", C.c_void_p), ("c1", C.c_double),
+                ("dt", C.c_double), ("ktether", C.c_double), ("energy", C.c_void_p), ("acc", C.c_void_p), ("done", C.c_void_p),
+                ("log_pe", C.c_void_p), ("log_ke", C.c_void_p), ("step", C.c_void_p), ("capacity", C.c_longlong), ("last", C.c_void_p)]
+
+
+class _ExchangeArgs(C.Structure):  # AgbnpMdExchange
+    _fields_ = [("n", C.c_int), ("replicas", C.c_int), ("v", C.c_void_p), ("kT", C.c_void_p), ("rung_of_replica", C.c_void_p),
+                ("replica_at_rung", C.c_void_p), ("last", C.c_void_p), ("step", C.c_void_p), ("attempts", C.c_void_p),
+                ("scale", C.c_void_p), ("log", C.c_void_p), ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
+
+
+GROUP_SYMBOLS = ("agbnp_md_group_pre", "agbnp_md_group_mid", "agbnp_md_group_post", "agbnp_md_group_tethers", "agbnp_md_exchange")
 
 _MD_LIB = None
 
@@ -35,18 +58,112 @@ def _md_lib():
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(path)
-        vp, dbl = C.c_void_p, C.c_double
+        vp, gp = C.c_void_p, C.POINTER(_GroupArgs)
         lib.agbnp_md_blocks.argtypes = [C.c_int]
-        lib.agbnp_md_pre.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, dbl, dbl, dbl, C.c_ulonglong, vp, vp, vp]
-        lib.agbnp_md_post.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_longlong, vp, vp]
-        lib.agbnp_md_tethers.argtypes = [C.c_int, vp, vp, vp, dbl, vp, vp]
-        lib.agbnp_md_mid.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, dbl, dbl, dbl, C.c_ulonglong, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     C.c_longlong, vp, vp]
+        lib.agbnp_md_group_pre.argtypes = [gp, C.c_int, vp, vp]
+        lib.agbnp_md_group_mid.argtypes = [gp, C.c_int, vp, vp, vp]
+        lib.agbnp_md_group_post.argtypes = [gp, vp, vp]
+        lib.agbnp_md_group_tethers.argtypes = [gp, vp, vp]
+        lib.agbnp_md_exchange.argtypes = [C.POINTER(_ExchangeArgs), vp]
         _MD_LIB = lib
     return _MD_LIB
 
 
+def _check(rc):
+    if rc != 0:
+        raise RuntimeError(f"libagbnp_md.so: launch failed (hipError {rc})")
+
+
+_KINDS = {"langevin": 0, "verlet": 1}  # the kernels' `kind`
+
+
+class _Replicas:
+    """The integrator state of R replicas of one system and the launches that advance it (csrc/md_kernels.hip).  State is
+    strided -- x, v, frc [R][n][3], everything per replica [R]... -- so replica r's buffers are fixed slices and the kernels'
+    argument struct is filled once.  Replica r starts at the system's positions with velocities drawn at temperatures[r] by a
+    generator seeded seeds[r]; seeds[r] also keys its Philox stream.  The force evaluation between the launches is the
+    driver's: `evaluate(stream)` adds forces to frc[r] and energies to e_agbnp[r]."""
+
+    def __init__(self, torch, system, temperatures, seeds, k_tether, dt, friction, device, log_capacity):
+        self.lib = lib = _md_lib()
+        self.R, self.n = R, n = len(temperatures), int(system.n)
+        self.dev = torch.device(device)
+        self.dt, self.k, self.gamma = float(dt), float(k_tether), float(friction)
+        self.c1 = float(np.exp(-self.gamma * self.dt))
+        self.log_capacity = cap = int(log_capacity)
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        i64 = dict(dtype=torch.int64, device=self.dev)
+        # masses in amu: hydrogens 1.008, heavy atoms carbon-like (the .dat fixtures carry no element)
+        self.mass1 = torch.tensor(np.where(system.ishydrogen == 1, 1.008, 12.0), **f64).contiguous()
+        self.mass = self.mass1.reshape(-1, 1)
+        self.hdt_m1 = ((0.5 * self.dt) / self.mass1).contiguous()  # dt / 2m
+        self.x0 = torch.tensor(system.pos, **f64).contiguous()
+        self.x = self.x0.unsqueeze(0).repeat(R, 1, 1).contiguous()
+        self.v = torch.empty_like(self.x)
+        for r in range(R):
+            gen = torch.Generator(device=self.dev)
+            gen.manual_seed(seeds[r])
+            self.v[r] = torch.randn((n, 3), generator=gen, **f64) * torch.sqrt(KB * temperatures[r] / self.mass)
+        self.frc = torch.zeros_like(self.x)
+        self.kT = torch.tensor([KB * t for t in temperatures], **f64)  # bath temperatures, kJ/mol: an exchange swaps them
+        self.seed_words = torch.tensor(np.array([s & _M64 for s in seeds], dtype=np.uint64).view(np.int64), **i64)
+        self.e_agbnp = torch.zeros(R, **f64)  # the words the engine adds the AGBNP energies to (handed back as zeros by every step)
+        blocks = int(lib.agbnp_md_blocks(n))
+        # the tether energy as per-block partials (a run of steps alternates between the two: k_md_group_mid)
+        self.parts = (torch.zeros((R, blocks), **f64), torch.zeros((R, blocks), **f64))
+        self.acc = torch.zeros((R, 2), **f64)  # the kinetic-energy accumulators and the arrival counters of the back half
+        self.done = torch.zeros(R, dtype=torch.int32, device=self.dev)
+        # per-step logs written by the kernels: potential and kinetic energy at index `counter`
+        self.log_pe = torch.zeros((R, cap), **f64)
+        self.log_ke = torch.zeros((R, cap), **f64)
+        self.counter = torch.zeros(R, **i64)
+        self.last = torch.zeros((R, 2), **f64)  # {potential, kinetic} energy of every replica's last step
+        p = lambda t: t.data_ptr()  # noqa: E731
+        self._g = _GroupArgs(n, R, p(self.x), p(self.v), p(self.frc), p(self.x0), p(self.hdt_m1), p(self.mass1), p(self.kT),
+                             p(self.seed_words), self.c1, self.dt, self.k, p(self.e_agbnp), p(self.acc), p(self.done), p(self.log_pe),
+                             p(self.log_ke), p(self.counter), cap, p(self.last))
+        self._parts = (p(self.parts[0]), p(self.parts[1]))
+
+    def tethers(self, st):
+        """f = -k (x - x0) of every replica, the tethers' energy as partials in parts[0]."""
+        _check(self.lib.agbnp_md_group_tethers(C.byref(self._g), self._parts[0], st))
+
+    def forces(self, torch, st, evaluate):
+        """Tethers + AGBNP of every replica at the current positions, enqueued on `st` (torch's current stream): frc[r],
+        last[r, 0]."""
+        self.e_agbnp.zero_()
+        self.tethers(st)
+        evaluate(st)
+        torch.add(self.parts[0].sum(dim=1), self.e_agbnp, out=self.last[:, 0])
+        self.e_agbnp.zero_()  # (a step that follows starts its own sum)
+
+    def steps(self, kind, steps, st, evaluate):
+        """`steps` consecutive steps of all replicas: front halves, then (evaluation, back halves + next front halves in ONE
+        launch) between the steps, evaluation, back halves: two launches around the only evaluation of a single step, one more
+        than the evaluation's for every further one."""
+        lib, g, parts = self.lib, C.byref(self._g), self._parts
+        _check(lib.agbnp_md_group_pre(g, kind, parts[0], st))
+        for j in range(steps):
+            evaluate(st)
+            if j + 1 < steps:
+                _check(lib.agbnp_md_group_mid(g, kind, parts[j % 2], parts[(j + 1) % 2], st))
+            else:
+                _check(lib.agbnp_md_group_post(g, parts[j % 2], st))
+
+
+def _settle(forces, withheld):
+    """First evaluations (allocations, capacity negotiation, forest packing), until `withheld()` reports none; bounded."""
+    for _ in range(8):
+        for _ in range(3):
+            forces()
+        if not withheld():
+            return
+    raise RuntimeError("AGBNP capacity negotiation did not converge")
+
+
 class DeviceMD:
+    """One trajectory: a replica group of one around `kernel.execute_device`, replayed as HIP graphs."""
+
     def __init__(self, system, kernel, k_tether=2.0e4, dt=0.001, temperature=300.0, friction=1.0, seed=0, device="cuda:0",
                  log_capacity=200000, fused=True):
         import torch
@@ -54,55 +171,35 @@ class DeviceMD:
         self.fused = bool(fused)
         self.seed = int(seed)
         self.system, self.kernel = system, kernel
-        self.dev = torch.device(device)
+        self.T = float(temperature)
+        self.core = core = _Replicas(torch, system, [self.T], [self.seed], k_tether, dt, friction, device, log_capacity)
+        self.dev, self.n, self.log_capacity = core.dev, core.n, core.log_capacity
+        self.dt, self.k, self.gamma, self.c1 = core.dt, core.k, core.gamma, core.c1
+        # views into the core's arrays
+        self.x, self.v, self.frc, self.x0, self.mass = core.x[0], core.v[0], core.frc[0], core.x0, core.mass
+        self.last = core.last[0]   # {potential, kinetic} energy of the last step
+        self.ene = self.last[0:1]  # potential energy of the last force evaluation (tethers + AGBNP)
+        self.log_pe, self.log_ke, self.counter = core.log_pe[0], core.log_ke[0], core.counter
+        # The step in torch operations (`fused=False`, and the minimiser's record).  Every torch op below is one tiny launch (~2 us
+        # each inside the replayed graph), so the step is written with as few of them as the arithmetic allows: fused
+        # multiply-adds, preallocated outputs, dot products for the sums.
         f64 = dict(dtype=torch.float64, device=self.dev)
-        self.dt, self.k = float(dt), float(k_tether)
-        self.T, self.gamma = float(temperature), float(friction)
-        # masses in amu: hydrogens 1.008, heavy atoms carbon-like (the .dat fixtures carry no element)
-        self.mass = torch.tensor(np.where(system.ishydrogen == 1, 1.008, 12.0)[:, None], **f64)
-        self.x0 = torch.tensor(system.pos, **f64)
-        self.x = self.x0.clone()
-        gen = torch.Generator(device=self.dev)
-        gen.manual_seed(seed)
-        self.gen = gen
-        self.v = torch.randn(self.x.shape, generator=gen, **f64) * torch.sqrt(KB * self.T / self.mass)
-        self.frc = torch.zeros_like(self.x)
-        self.last = torch.zeros(2, **f64)  # {potential, kinetic} energy of the last step
-        self.ene = self.last[0:1]          # potential energy of the last force evaluation (tethers + AGBNP)
-        self.noise = torch.empty_like(self.x)
-        self.c1 = float(np.exp(-self.gamma * self.dt))
+        self.hdt_m = core.hdt_m1.reshape(-1, 1)
         self.c2 = torch.sqrt((1.0 - self.c1 * self.c1) * KB * self.T / self.mass)
-        # per-step log written inside the graph: potential and kinetic energy at index `counter`
-        self.log_pe = torch.zeros(log_capacity, **f64)
-        self.log_ke = torch.zeros(log_capacity, **f64)
-        self.counter = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.noise = torch.empty_like(self.x)
         self.one = torch.ones(1, dtype=torch.int64, device=self.dev)
-        # Every torch op below is one tiny launch (~2 us each inside the replayed graph), so the step is written with as
-        # few of them as the arithmetic allows: fused multiply-adds, preallocated outputs, dot products for the sums.
-        self.hdt_m = (0.5 * self.dt) / self.mass  # dt / 2m
-        self.d = torch.zeros_like(self.x)           # x - x0
-        self.mv = torch.zeros_like(self.x)          # m v
+        self.d = torch.zeros_like(self.x)   # x - x0
+        self.mv = torch.zeros_like(self.x)  # m v
         self.ke = torch.zeros(1, **f64)
-        # fused integrator (csrc/md_kernels.hip): the word the engine adds the AGBNP energy to (handed back as zero by every
-        # step), the tether energy as per-block partials, the kinetic-energy accumulator and the arrival counter
-        self.n = int(system.n)
-        self.log_capacity = int(log_capacity)
-        if self.fused:
-            lib = _md_lib()
-            self.e_agbnp = torch.zeros(1, **f64)
-            self.tether_part = torch.zeros(lib.agbnp_md_blocks(self.n), **f64)
-            self.tether_part2 = torch.zeros_like(self.tether_part)  # (a run of steps alternates between the two: k_md_mid)
-            self.acc = torch.zeros(2, **f64)
-            self.done = torch.zeros(1, dtype=torch.int32, device=self.dev)
-            self.hdt_m1 = self.hdt_m.reshape(-1).contiguous()
-            self.c2_1 = self.c2.reshape(-1).contiguous()
-            self.mass1 = self.mass.reshape(-1).contiguous()
         self._eager = None
         self.graphs = {}
         self.generation = None
         self.steps_done = 0
 
     # ---- force field: tethers + AGBNP (added on the device by the engine)
+    def _evaluate(self, st):
+        self.kernel.execute_device(self.x.data_ptr(), self.frc.data_ptr(), self.core.e_agbnp.data_ptr(), st)
+
     def forces(self):
         """Tethers + AGBNP at the current positions: self.frc, self.ene.  Inside a graph capture it joins the capture; called
         eagerly on torch's default (null) stream it runs on a stream of its own and waits for it -- the engine takes a null
@@ -120,18 +217,13 @@ class DeviceMD:
 
     def _forces(self):
         torch = self.torch
+        st = torch.cuda.current_stream().cuda_stream
         if self.fused:
-            st = torch.cuda.current_stream().cuda_stream
-            self.e_agbnp.zero_()
-            self._check(_md_lib().agbnp_md_tethers(self.n, self.x.data_ptr(), self.x0.data_ptr(), self.frc.data_ptr(), self.k, self.tether_part.data_ptr(), st))
-            self.kernel.execute_device(self.x.data_ptr(), self.frc.data_ptr(), self.e_agbnp.data_ptr(), st)
-            torch.add(self.tether_part.sum().reshape(1), self.e_agbnp, out=self.ene)
-            self.e_agbnp.zero_()  # (a step that follows starts its own sum)
-            return
+            return self.core.forces(torch, st, self._evaluate)
         torch.sub(self.x, self.x0, out=self.d)
         torch.mul(self.d, -self.k, out=self.frc)
         torch.mul(torch.dot(self.d.view(-1), self.d.view(-1)).reshape(1), 0.5 * self.k, out=self.ene)
-        self.kernel.execute_device(self.x.data_ptr(), self.frc.data_ptr(), self.ene.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        self.kernel.execute_device(self.x.data_ptr(), self.frc.data_ptr(), self.ene.data_ptr(), st)
 
     def _record(self):
         torch = self.torch
@@ -141,49 +233,13 @@ class DeviceMD:
         self.log_ke.index_copy_(0, self.counter, self.ke)
         self.counter.add_(self.one)
 
-    @staticmethod
-    def _check(rc):
-        if rc != 0:
-            raise RuntimeError(f"libagbnp_md.so: launch failed (hipError {rc})")
-
-    def _step_fused(self, kind):
-        """One step in two launches around the AGBNP evaluation (csrc/md_kernels.hip)."""
-        lib, st = _md_lib(), self.torch.cuda.current_stream().cuda_stream
-        self._check(lib.agbnp_md_pre(self.n, kind, self.x.data_ptr(), self.v.data_ptr(), self.frc.data_ptr(), self.x0.data_ptr(),
-                                     self.hdt_m1.data_ptr(), self.c2_1.data_ptr(), self.c1, self.dt, self.k, self.seed, self.counter.data_ptr(),
-                                     self.tether_part.data_ptr(), st))
-        self.kernel.execute_device(self.x.data_ptr(), self.frc.data_ptr(), self.e_agbnp.data_ptr(), st)
-        self._check(lib.agbnp_md_post(self.n, self.v.data_ptr(), self.frc.data_ptr(), self.hdt_m1.data_ptr(), self.mass1.data_ptr(),
-                                      self.e_agbnp.data_ptr(), self.tether_part.data_ptr(), self.acc.data_ptr(), self.done.data_ptr(),
-                                      self.log_pe.data_ptr(), self.log_ke.data_ptr(), self.counter.data_ptr(), self.log_capacity,
-                                      self.last.data_ptr(), st))
-
-    def _steps_fused(self, kind, steps):
-        """`steps` consecutive steps: front half, then (evaluation, back half + next front half in ONE launch) between the
-        steps, evaluation, back half: 7 launches per step instead of 8."""
-        lib, st = _md_lib(), self.torch.cuda.current_stream().cuda_stream
-        parts = (self.tether_part, self.tether_part2)
-        self._check(lib.agbnp_md_pre(self.n, kind, self.x.data_ptr(), self.v.data_ptr(), self.frc.data_ptr(), self.x0.data_ptr(),
-                                     self.hdt_m1.data_ptr(), self.c2_1.data_ptr(), self.c1, self.dt, self.k, self.seed, self.counter.data_ptr(),
-                                     parts[0].data_ptr(), st))
-        for j in range(steps):
-            self.kernel.execute_device(self.x.data_ptr(), self.frc.data_ptr(), self.e_agbnp.data_ptr(), st)
-            old = parts[j % 2]
-            if j + 1 < steps:
-                self._check(lib.agbnp_md_mid(self.n, kind, self.x.data_ptr(), self.v.data_ptr(), self.frc.data_ptr(), self.x0.data_ptr(),
-                                             self.hdt_m1.data_ptr(), self.mass1.data_ptr(), self.c2_1.data_ptr(), self.c1, self.dt, self.k, self.seed,
-                                             self.e_agbnp.data_ptr(), old.data_ptr(), parts[(j + 1) % 2].data_ptr(), self.acc.data_ptr(),
-                                             self.done.data_ptr(), self.log_pe.data_ptr(), self.log_ke.data_ptr(), self.counter.data_ptr(),
-                                             self.log_capacity, self.last.data_ptr(), st))
-            else:
-                self._check(lib.agbnp_md_post(self.n, self.v.data_ptr(), self.frc.data_ptr(), self.hdt_m1.data_ptr(), self.mass1.data_ptr(),
-                                              self.e_agbnp.data_ptr(), old.data_ptr(), self.acc.data_ptr(), self.done.data_ptr(),
-                                              self.log_pe.data_ptr(), self.log_ke.data_ptr(), self.counter.data_ptr(), self.log_capacity,
-                                              self.last.data_ptr(), st))
+    def _fused_steps(self, kind, steps=1):
+        """`steps` steps of the core on the current stream (csrc/md_kernels.hip): 8 launches for one, 7 for each further one."""
+        self.core.steps(_KINDS[kind], steps, self.torch.cuda.current_stream().cuda_stream, self._evaluate)
 
     def step_verlet(self):  # velocity Verlet (the reference's NVE check uses OpenMM's VerletIntegrator, test_agbnp.py:57)
         if self.fused:
-            return self._step_fused(1)
+            return self._fused_steps("verlet")
         self.v.addcmul_(self.frc, self.hdt_m)
         self.x.add_(self.v, alpha=self.dt)
         self.forces()
@@ -192,7 +248,7 @@ class DeviceMD:
 
     def step_langevin(self):  # BAOAB (the reference uses LangevinIntegrator(300 K, 1/ps), test_agbnp.py:37, 1dwc_benchmark.py:20)
         if self.fused:
-            return self._step_fused(0)
+            return self._fused_steps("langevin")
         self.v.addcmul_(self.frc, self.hdt_m)
         self.x.add_(self.v, alpha=0.5 * self.dt)
         self.noise.normal_(generator=None)
@@ -214,13 +270,7 @@ class DeviceMD:
         torch = self.torch
         side = torch.cuda.Stream()
         with torch.cuda.stream(side):
-            for _ in range(8):
-                for _ in range(3):
-                    self.forces()
-                if self.kernel.finish(side.cuda_stream) == 0:
-                    break
-            else:
-                raise RuntimeError("AGBNP capacity negotiation did not converge")
+            _settle(self.forces, lambda: self.kernel.finish(side.cuda_stream))
         torch.cuda.synchronize()
 
     def _graph(self, kind, steps=1):
@@ -240,8 +290,8 @@ class DeviceMD:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                if self.fused and steps > 1 and kind in ("langevin", "verlet"):
-                    self._steps_fused(0 if kind == "langevin" else 1, steps)
+                if self.fused and kind in _KINDS:
+                    self._fused_steps(kind, steps)
                 else:
                     for _ in range(steps):
                         step()
@@ -333,37 +383,6 @@ def exchange_delta(kT_lo, kT_hi, U_lo, U_hi):
 EXCHANGE_RECORD = np.dtype([("attempt", "<i8"), ("step", "<i8"), ("rung", "<i4"), ("replica_lo", "<i4"), ("replica_hi", "<i4"),
                             ("accepted", "<i4"), ("U_lo", "<f8"), ("U_hi", "<f8"), ("kT_lo", "<f8"), ("kT_hi", "<f8"), ("u", "<f8")])
 
-MAX_REPLICAS = 16  # AGBNP_HIP_MAX_GROUP
-
-
-class _GroupArgs(C.Structure):  # AgbnpMdGroup
-    _fields_ = [("n", C.c_int), ("replicas", C.c_int), ("x", C.c_void_p), ("v", C.c_void_p), ("f", C.c_void_p), ("x0", C.c_void_p),
-                ("hdt_m", C.c_void_p), ("mass", C.c_void_p), ("kT", C.c_void_p), ("seeds", C.c_void_p), ("c1", C.c_double),
-                ("dt", C.c_double), ("ktether", C.c_double), ("energy", C.c_void_p), ("acc", C.c_void_p), ("done", C.c_void_p),
-                ("log_pe", C.c_void_p), ("log_ke", C.c_void_p), ("step", C.c_void_p), ("capacity", C.c_longlong), ("last", C.c_void_p)]
-
-
-class _ExchangeArgs(C.Structure):  # AgbnpMdExchange
-    _fields_ = [("n", C.c_int), ("replicas", C.c_int), ("v", C.c_void_p), ("kT", C.c_void_p), ("rung_of_replica", C.c_void_p),
-                ("replica_at_rung", C.c_void_p), ("last", C.c_void_p), ("step", C.c_void_p), ("attempts", C.c_void_p),
-                ("scale", C.c_void_p), ("log", C.c_void_p), ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
-
-
-GROUP_SYMBOLS = ("agbnp_md_group_pre", "agbnp_md_group_mid", "agbnp_md_group_post", "agbnp_md_group_tethers", "agbnp_md_exchange")
-
-
-def _md_group_lib():
-    lib = _md_lib()
-    if not getattr(lib, "_group_ready", False):
-        vp, gp = C.c_void_p, C.POINTER(_GroupArgs)
-        lib.agbnp_md_group_pre.argtypes = [gp, C.c_int, vp, vp]
-        lib.agbnp_md_group_mid.argtypes = [gp, C.c_int, vp, vp, vp]
-        lib.agbnp_md_group_post.argtypes = [gp, vp, vp]
-        lib.agbnp_md_group_tethers.argtypes = [gp, vp, vp]
-        lib.agbnp_md_exchange.argtypes = [C.POINTER(_ExchangeArgs), vp]
-        lib._group_ready = True
-    return lib
-
 
 class ReplicaMD:
     """Temperature replica exchange of R replicas of one system: DeviceMD's integrator and force field (tethers + AGBNP) for
@@ -391,53 +410,23 @@ class ReplicaMD:
             raise ValueError("ReplicaMD: temperatures must be positive")
         import torch
         self.torch = torch
-        lib = _md_group_lib()
-        self.system, self.kernels, self.R, self.n = system, kernels, R, int(system.n)
+        self.core = core = _Replicas(torch, system, temperatures, seeds, k_tether, dt, friction, device, log_capacity)
+        self.system, self.kernels, self.R, self.n, self.dev = system, kernels, R, core.n, core.dev
         self.ladder = np.array(temperatures)  # the temperature of rung k; replica r starts on rung r
         self.seeds, self.exchange_seed = seeds, int(exchange_seed)
-        self.dev = torch.device(device)
-        self.dt, self.k, self.gamma = float(dt), float(k_tether), float(friction)
-        self.c1 = float(np.exp(-self.gamma * self.dt))
-        self.log_capacity = int(log_capacity)
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        i64 = dict(dtype=torch.int64, device=self.dev)
-        n, cap = self.n, self.log_capacity
-        mass = torch.tensor(np.where(system.ishydrogen == 1, 1.008, 12.0), **f64)  # (DeviceMD's masses)
-        self.mass = mass.reshape(-1, 1)
-        self.mass1 = mass.contiguous()
-        self.hdt_m1 = ((0.5 * self.dt) / mass).contiguous()
-        self.x0 = torch.tensor(system.pos, **f64).contiguous()
-        self.x = self.x0.unsqueeze(0).repeat(R, 1, 1).contiguous()
-        self.v = torch.empty_like(self.x)
-        for r in range(R):  # replica r starts as DeviceMD(seed=seeds[r], temperature=temperatures[r]) starts
-            gen = torch.Generator(device=self.dev)
-            gen.manual_seed(seeds[r])
-            self.v[r] = torch.randn((n, 3), generator=gen, **f64) * torch.sqrt(KB * temperatures[r] / self.mass)
-        self.frc = torch.zeros_like(self.x)
-        self.kT = torch.tensor([KB * t for t in temperatures], **f64)
-        self.seed_words = torch.tensor(np.array(seeds, dtype=np.uint64).view(np.int64), **i64)
-        self.e_agbnp = torch.zeros(R, **f64)
-        self.blocks = int(lib.agbnp_md_blocks(n))
-        self.parts = (torch.zeros((R, self.blocks), **f64), torch.zeros((R, self.blocks), **f64))
-        self.acc = torch.zeros((R, 2), **f64)
-        self.done = torch.zeros(R, dtype=torch.int32, device=self.dev)
-        self.log_pe = torch.zeros((R, cap), **f64)
-        self.log_ke = torch.zeros((R, cap), **f64)
-        self.counter = torch.zeros(R, **i64)
-        self.last = torch.zeros((R, 2), **f64)  # {potential, kinetic} energy of every replica's last step
+        self.dt, self.k, self.gamma, self.c1, self.log_capacity = core.dt, core.k, core.gamma, core.c1, core.log_capacity
+        self.x, self.v, self.frc, self.x0, self.mass, self.kT = core.x, core.v, core.frc, core.x0, core.mass, core.kT
+        self.log_pe, self.log_ke, self.counter, self.last = core.log_pe, core.log_ke, core.counter, core.last
         self.rung_of_replica = torch.arange(R, dtype=torch.int32, device=self.dev)
         self.replica_at_rung = torch.arange(R, dtype=torch.int32, device=self.dev)
-        self.attempts = torch.zeros(1, **i64)
-        self.scale = torch.ones(R, **f64)
-        self.exchange_capacity = cap
-        self.records = torch.zeros(cap * EXCHANGE_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        self.attempts = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.scale = torch.ones(R, dtype=torch.float64, device=self.dev)
+        self.exchange_capacity = core.log_capacity
+        self.records = torch.zeros(self.exchange_capacity * EXCHANGE_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
         p = lambda t: t.data_ptr()  # noqa: E731
-        self._g = _GroupArgs(n, R, p(self.x), p(self.v), p(self.frc), p(self.x0), p(self.hdt_m1), p(self.mass1), p(self.kT),
-                             p(self.seed_words), self.c1, self.dt, self.k, p(self.e_agbnp), p(self.acc), p(self.done), p(self.log_pe),
-                             p(self.log_ke), p(self.counter), cap, p(self.last))
-        self._e = _ExchangeArgs(n, R, p(self.v), p(self.kT), p(self.rung_of_replica), p(self.replica_at_rung), p(self.last),
+        self._e = _ExchangeArgs(self.n, R, p(self.v), p(self.kT), p(self.rung_of_replica), p(self.replica_at_rung), p(self.last),
                                 p(self.counter), p(self.attempts), p(self.scale), p(self.records), self.exchange_capacity,
-                                self.exchange_seed & 0xFFFFFFFFFFFFFFFF)
+                                self.exchange_seed & _M64)
         # the group call's arguments never change: member r's buffers are slices of the strided arrays
         for k in kernels:
             k._need()
@@ -445,16 +434,11 @@ class ReplicaMD:
         self._handles = vpR(*[k._h for k in kernels])
         self._pos = vpR(*[p(self.x[r]) for r in range(R)])
         self._frc = vpR(*[p(self.frc[r]) for r in range(R)])
-        self._ene = vpR(*[p(self.e_agbnp[r:r + 1]) for r in range(R)])
+        self._ene = vpR(*[p(core.e_agbnp[r:r + 1]) for r in range(R)])
         self.stream = torch.cuda.Stream(device=self.dev)  # everything of this driver is enqueued here
         self.steps_done = 0
 
     # ---- launches
-    @staticmethod
-    def _check(rc):
-        if rc != 0:
-            raise RuntimeError(f"libagbnp_md.so: launch failed (hipError {rc})")
-
     def _evaluate(self, st):
         """agbnp_hip_execute_group of all members on stream `st`: forces and energies are added to frc[r], e_agbnp[r]."""
         from . import _lib
@@ -470,52 +454,28 @@ class ReplicaMD:
     def forces(self):
         """Tethers + AGBNP of every replica at the current positions: frc[r], last[r, 0].  Waits for the result."""
         torch = self.torch
-        lib, st = _md_group_lib(), self.stream.cuda_stream
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
-            self.e_agbnp.zero_()
-            self._check(lib.agbnp_md_group_tethers(C.byref(self._g), self.parts[0].data_ptr(), st))
-            self._evaluate(st)
-            self.last[:, 0] = self.parts[0].sum(dim=1) + self.e_agbnp
-            self.e_agbnp.zero_()  # (a step that follows starts its own sum)
+            self.core.forces(torch, self.stream.cuda_stream, self._evaluate)
         self.stream.synchronize()
 
     def settle(self):
         """Outside any timing: first evaluations (allocations, capacity negotiation, forest packing, the group's argument
         blocks), until every member's finish() reports nothing withheld."""
-        for _ in range(8):
-            for _ in range(3):
-                self.forces()
-            if not self.finish().any():
-                break
-        else:
-            raise RuntimeError("AGBNP capacity negotiation did not converge")
+        _settle(self.forces, lambda: self.finish().any())
         self.torch.cuda.synchronize()
-
-    def _steps(self, kind, steps, st):
-        """`steps` consecutive steps of all replicas: front halves, then (group evaluation, back halves + next front halves in
-        one launch) between the steps, group evaluation, back halves: 5 + 1 launches per step."""
-        lib, g = _md_group_lib(), C.byref(self._g)
-        parts = (self.parts[0].data_ptr(), self.parts[1].data_ptr())
-        self._check(lib.agbnp_md_group_pre(g, kind, parts[0], st))
-        for j in range(steps):
-            self._evaluate(st)
-            if j + 1 < steps:
-                self._check(lib.agbnp_md_group_mid(g, kind, parts[j % 2], parts[(j + 1) % 2], st))
-            else:
-                self._check(lib.agbnp_md_group_post(g, parts[j % 2], st))
 
     def exchange(self):
         """One exchange attempt between neighbouring rungs, enqueued on the driver's stream (two launches, nothing read)."""
-        self._check(_md_group_lib().agbnp_md_exchange(C.byref(self._e), self.stream.cuda_stream))
+        _check(self.core.lib.agbnp_md_exchange(C.byref(self._e), self.stream.cuda_stream))
 
     def run(self, nsteps, kind="langevin", exchange_every=0, check_every=1000, on_report=None):
-        """`nsteps` steps of every replica, an exchange attempt after every `exchange_every` of them (0: none); every
-        `check_every` steps (and at the end) synchronises and reads every member's overflow log.  Returns, per replica, the
-        number of steps whose AGBNP contribution was withheld (all zeros in a healthy run; an exchange decided on such a step
-        used a potential energy without the AGBNP term)."""
+        """`nsteps` steps of every replica (5 + 1 launches per step for all of them), an exchange attempt after every
+        `exchange_every` of them (0: none); every `check_every` steps (and at the end) synchronises and reads every member's
+        overflow log.  Returns, per replica, the number of steps whose AGBNP contribution was withheld (all zeros in a healthy
+        run; an exchange decided on such a step used a potential energy without the AGBNP term)."""
         torch = self.torch
-        code = {"langevin": 0, "verlet": 1}[kind]
+        code = _KINDS[kind]
         exchange_every, check_every = int(exchange_every), max(1, int(check_every))
         st = self.stream.cuda_stream
         missed = np.zeros(self.R, dtype=np.int64)
@@ -525,7 +485,7 @@ class ReplicaMD:
             chunk = min(nsteps - done, check_every - since_check)
             if exchange_every > 0:
                 chunk = min(chunk, exchange_every - since_exchange)
-            self._steps(code, chunk, st)
+            self.core.steps(code, chunk, st, self._evaluate)
             done += chunk
             since_exchange += chunk
             since_check += chunk

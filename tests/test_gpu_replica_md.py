@@ -80,6 +80,76 @@ def test_langevin_replicas_are_device_md_runs(gpu_required, systems):
     _against_device_md(systems("trpcage"), "langevin", [280.0, 300.0, 320.0], [5, 6, 7])
 
 
+def _front_half_in_numpy(md, n, x, v, f, x0, mass, kT, seed, step, c1, dt, k):
+    """The Langevin front half of one replica restated: first kick, half drift, v = c1 v + cn z, half drift; the deviates of
+    atom i are Box-Muller pairs of the Philox blocks with counter (i, step lo, step hi, 0 | 1) and key seed."""
+    z = np.empty((n, 3))
+    for i in range(n):
+        a = md.philox4x32((i, step & 0xFFFFFFFF, step >> 32, 0), (seed & 0xFFFFFFFF, seed >> 32))
+        b = md.philox4x32((i, step & 0xFFFFFFFF, step >> 32, 1), (seed & 0xFFFFFFFF, seed >> 32))
+        ra, rb = np.sqrt(-2.0 * np.log(md.uniform53(a[0], a[1]))), np.sqrt(-2.0 * np.log(md.uniform53(b[0], b[1])))
+        pa, pb = 2.0 * np.pi * md.uniform53(a[2], a[3]), 2.0 * np.pi * md.uniform53(b[2], b[3])
+        z[i] = ra * np.cos(pa), ra * np.sin(pa), rb * np.cos(pb)
+    m = mass[:, None]
+    pv = v + (0.5 * dt / m) * f
+    px = x + 0.5 * dt * pv
+    pv = c1 * pv + np.sqrt((1.0 - c1 * c1) * kT / m) * z
+    px = px + 0.5 * dt * pv
+    return px, pv, float((0.5 * k * (px - x0) ** 2).sum()), z
+
+
+def test_the_front_half_is_its_numpy_restatement(gpu_required, systems):
+    """Both drivers share the front half, so neither pins it for the other: ONE agbnp_md_group_pre launch (kind 0, Langevin) for
+    R = 2 over trpcage's atoms from given x, v, f, kT, seeds and non-zero step words (one beyond 32 bits) against the restatement
+    above on the module's own philox4x32 / uniform53.  Positions to 1e-11 nm, velocities to 1e-9 nm/ps, the sum of a replica's
+    tether partials to 1e-7 kJ/mol (the bounds of this file); forces are -k (x - x0) of the new positions to 1e-9 relative.  The
+    replicas have seeds and temperatures of their own: their deviates differ and each set is a standard normal sample (816
+    values: the mean within 4 / sqrt(816) = 0.14 of zero, the variance within 4 sqrt(2 / 816) = 0.2 of one)."""
+    torch = pytest.importorskip("torch")
+    import ctypes as C
+
+    from openmm_agbnp_plugin_amd import md
+    s = systems("trpcage")
+    n, R, dt, k, c1 = int(s.n), 2, 0.001, 2.0e4, float(np.exp(-10.0 * 0.001))
+    lib = md._md_lib()
+    blocks = int(lib.agbnp_md_blocks(n))
+    rng = np.random.default_rng(20)
+    mass = np.where(s.ishydrogen == 1, 1.008, 12.0)
+    x0 = np.ascontiguousarray(s.pos, dtype=np.float64)
+    kT = np.array([md.KB * 280.0, md.KB * 330.0])
+    seeds, steps = [0x1234567890ABCDEF, 77], [5, (1 << 32) + 3]
+    x = x0[None] + 0.002 * np.sin(x0[None] * np.array([37.0, 40.0])[:, None, None])
+    v = rng.normal(size=(R, n, 3)) * np.sqrt(kT[:, None, None] / mass[None, :, None])
+    f = rng.normal(size=(R, n, 3)) * 500.0
+    dev = torch.device("cuda:0")
+    up = lambda a, dtype=torch.float64: torch.tensor(a, dtype=dtype, device=dev).contiguous()  # noqa: E731
+    d = dict(x=up(x), v=up(v), f=up(f), x0=up(x0), hdt_m=up(0.5 * dt / mass), mass=up(mass), kT=up(kT),
+             seeds=up(np.array(seeds, dtype=np.uint64).view(np.int64), torch.int64), energy=up(np.zeros(R)), acc=up(np.zeros((R, 2))),
+             done=up(np.zeros(R), torch.int32), log_pe=up(np.zeros((R, 8))), log_ke=up(np.zeros((R, 8))), step=up(steps, torch.int64),
+             last=up(np.zeros((R, 2))), part=up(np.full((R, blocks), np.nan)))
+    p = lambda name: d[name].data_ptr()  # noqa: E731
+    g = md._GroupArgs(n, R, p("x"), p("v"), p("f"), p("x0"), p("hdt_m"), p("mass"), p("kT"), p("seeds"), c1, dt, k, p("energy"), p("acc"),
+                      p("done"), p("log_pe"), p("log_ke"), p("step"), 8, p("last"))
+    torch.cuda.synchronize()
+    assert lib.agbnp_md_group_pre(C.byref(g), 0, p("part"), torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    x1, v1, f1, part = (d[name].cpu().numpy() for name in ("x", "v", "f", "part"))
+    assert d["step"].cpu().tolist() == steps  # (the front half reads the step word; the back half advances it)
+    zs = []
+    for r in range(R):
+        px, pv, et, z = _front_half_in_numpy(md, n, x[r], v[r], f[r], x0, mass, kT[r], seeds[r], steps[r], c1, dt, k)
+        dx, dv, de = np.abs(x1[r] - px).max(), np.abs(v1[r] - pv).max(), abs(part[r].sum() - et)
+        print(f"replica {r}: |dx| {dx:.2e} nm  |dv| {dv:.2e} nm/ps  |dU tethers| {de:.2e} kJ/mol")
+        assert dx < 1e-11 and dv < 1e-9
+        assert de < 1e-7
+        want = -k * (x1[r] - x0)
+        assert np.all(np.abs(f1[r] - want) <= 1e-9 * np.abs(want))
+        assert abs(z.mean()) < 0.14 and abs(z.var() - 1.0) < 0.2
+        zs.append(z)
+    assert np.abs(zs[0] - zs[1]).max() > 1.0
+    assert np.abs(x1[0] - x1[1]).max() > 1e-4 and np.abs(v1[0] - v1[1]).max() > 1e-2
+
+
 def test_nve_energy_conservation_per_replica(gpu_required, systems):
     """R = 2 from different starts: 500 Langevin steps, then 3000 velocity-Verlet steps, nothing withheld; per replica the total
     energy fluctuates by less than 2 % and drifts by less than 0.3 % of the mean kinetic energy (the bounds of

@@ -113,8 +113,8 @@ def test_the_md_library_exports_the_group_symbols():
                                 "agbnp_md_exchange")
     for name in md.GROUP_SYMBOLS:
         getattr(lib, name)  # AttributeError if the library does not export it
-    for name in ("agbnp_md_pre", "agbnp_md_mid", "agbnp_md_post", "agbnp_md_tethers", "agbnp_md_blocks"):
-        getattr(lib, name)  # (the single-replica entry points are still there)
+    for name in ("agbnp_md_blocks",):
+        getattr(lib, name)  # (the grid of one replica: the drivers size their tether partials by it)
 
 
 def test_the_argument_structs_have_the_kernels_sizes():
