@@ -317,35 +317,70 @@ int agbnp_hip_set_mode(agbnp_hip_context* ctx, int mode);
 int agbnp_hip_get_mode(const agbnp_hip_context* ctx);
 
 /* Diagnostics of the LAST completed evaluation (test support; mirrors the quantities the reference
- * prints at verbose_level > 0, ReferenceAGBNPKernels.cpp:333-352,459-462,519).
- * scalars: 0 E_vol1  1 E_vol2  2 E_atom (vdW + GB self)  3 E_GB pair  4 max subtree nodes
- *          5 total tree nodes  6 kernel variant  7 max local atoms  8 work slots (forests) planned for the next evaluation
- *          9 1 if the range-limited pair stages run in row form (neighbour rows with a skin, rebuilt on the device when an
- *            atom has moved more than half the skin; Reference mode, version 1)  10 builds of those rows so far
- *          11 forest packing: how far the assumed store capacity is tightened (0 = not at all; one step of 15 % when healed
- *             forests keep coming or one could not be healed, given back after clean plans in a row -- more of them every time)  12 evaluations since the packing was planned
- *          13 entries per slice of a neighbour row (one wave of a row launch walks one slice; tuned on the device)
- *          15 why the last agbnp_hip_finish() withheld evaluations: 1 a subtree outgrew the store's nodes, 2 its local atoms,
- *             4 a forest packing mispredicted, 8 a neighbour row outgrew its walk, 16 the context reordered its atoms,
- *             32 / 64 a forest of several work items outgrew its nodes / its local atoms (the two kinds of 4);
- *             bits 8.. the part count of a lone work item that asked for its subtree to be shared further
- *          16 kernel launches of an evaluation as the context runs now: version 1: 5 (five-launch mode) or 6; version 0: 2 or 3
- *          18 kernel launches of an energy-only evaluation as the context runs now: 4 (version 1) or 2 (version 0), 0 where it
-             runs as a full evaluation with its forces sent to a buffer of the context's own
-          19 members of the launch set of agbnp_hip_execute_group whose shared launches the context's last evaluation ran in
- *             (a group of one counts 1); 0 when it did not run through shared launches
- *          20 last_evaluation_kind: how the last evaluation ENQUEUED on the context ran (valid without a completed evaluation,
- *             like 18 and 19): 0 a full evaluation, 1 an energy-only evaluation on energy-only launches (alone or shared),
- *             2 an energy-only request that ran as a full evaluation with its forces sent to the context's own buffer
- *          21 group_block_writes: how often the context's group argument blocks have been rewritten so far (one small launch
- *             each); it stands still in a steady run of group calls with fixed position buffers
-          17 forests that outgrew their store and were healed inside the tree launch (built again in smaller sets: the
- *             evaluation is complete, nothing is withheld for them) over the evaluations the last agbnp_hip_finish() covered
- *          14 forest packings planned so far (a packing in use is planned anew every AGBNP_HIP_REPLAN_EVERY-th evaluation,
- *             default 16, or when the trees have drifted from the shapes it was planned for)
- * vectors (length N, atom order): 0 self volume (vdW radii)  1 Born radius  2 volume scaling factor
- *          3 self volume (enlarged radii)
- *          4 / 5 nodes / local atoms of the overlap subtree rooted at the atom (tree shape, capacity planning) */
+ * prints at verbose_level > 0, ReferenceAGBNPKernels.cpp:333-352,459-462,519).  `which` of agbnp_hip_get_scalar is one of
+ * enum agbnp_hip_scalar, `which` of agbnp_hip_get_vector one of enum agbnp_hip_vector. */
+enum agbnp_hip_scalar {
+  AGBNP_HIP_SCALAR_E_VOL1 = 0,
+  AGBNP_HIP_SCALAR_E_VOL2 = 1,
+  AGBNP_HIP_SCALAR_E_ATOM = 2,             /* vdW + GB self */
+  AGBNP_HIP_SCALAR_E_GB_PAIR = 3,
+  AGBNP_HIP_SCALAR_MAX_SUBTREE_NODES = 4,
+  AGBNP_HIP_SCALAR_TOTAL_NODES = 5,        /* total tree nodes */
+  AGBNP_HIP_SCALAR_VARIANT = 6,            /* kernel variant */
+  AGBNP_HIP_SCALAR_MAX_LOCAL_ATOMS = 7,
+  AGBNP_HIP_SCALAR_FORESTS = 8,            /* work slots (forests) planned for the next evaluation */
+  AGBNP_HIP_SCALAR_ROWS_ON = 9,            /* 1 if the range-limited pair stages run in row form (neighbour rows with a skin, rebuilt on
+                                            * the device when an atom has moved more than half the skin; Reference mode, version 1) */
+  AGBNP_HIP_SCALAR_ROW_BUILDS = 10,        /* builds of those rows so far */
+  AGBNP_HIP_SCALAR_PACK_LEVEL = 11,        /* forest packing: how far the assumed store capacity is tightened (0 = not at all; one step of
+                                            * 15 % when healed forests keep coming or one could not be healed, given back after clean
+                                            * plans in a row -- more of them every time) */
+  AGBNP_HIP_SCALAR_PACK_AGE = 12,          /* evaluations since the packing was planned */
+  AGBNP_HIP_SCALAR_ROW_SLICE = 13,         /* entries per slice of a neighbour row (one wave of a row launch walks one slice; tuned on
+                                            * the device) */
+  AGBNP_HIP_SCALAR_PACK_PLANS = 14,        /* forest packings planned so far (a packing in use is planned anew every
+                                            * AGBNP_HIP_REPLAN_EVERY-th evaluation, default 16, or when the trees have drifted from the
+                                            * shapes it was planned for) */
+  AGBNP_HIP_SCALAR_OVERFLOW_KINDS = 15,    /* why the last agbnp_hip_finish() withheld evaluations: bits of enum agbnp_hip_overflow_kind */
+  AGBNP_HIP_SCALAR_LAUNCHES = 16,          /* kernel launches of an evaluation as the context runs now: version 1: 5 (five-launch mode)
+                                            * or 6; version 0: 2 or 3 */
+  AGBNP_HIP_SCALAR_HEALED_FORESTS = 17,    /* forests that outgrew their store and were healed inside the tree launch (built again in
+                                            * smaller sets: the evaluation is complete, nothing is withheld for them) over the
+                                            * evaluations the last agbnp_hip_finish() covered */
+  AGBNP_HIP_SCALAR_ENERGY_ONLY_LAUNCHES = 18,  /* kernel launches of an energy-only evaluation as the context runs now: 4 (version 1) or
+                                            * 2 (version 0), 0 where it runs as a full evaluation with its forces sent to a buffer of
+                                            * the context's own */
+  AGBNP_HIP_SCALAR_GROUP_MEMBERS = 19,     /* members of the launch set of agbnp_hip_execute_group whose shared launches the context's
+                                            * last evaluation ran in (a group of one counts 1); 0 when it did not run through shared
+                                            * launches */
+  AGBNP_HIP_SCALAR_LAST_EVALUATION_KIND = 20,  /* how the last evaluation ENQUEUED on the context ran (valid without a completed
+                                            * evaluation, like 15, 17, 18, 19 and 21): 0 a full evaluation, 1 an energy-only evaluation on
+                                            * energy-only launches (alone or shared), 2 an energy-only request that ran as a full
+                                            * evaluation with its forces sent to the context's own buffer */
+  AGBNP_HIP_SCALAR_GROUP_BLOCK_WRITES = 21 /* how often the context's group argument blocks have been rewritten so far (one small
+                                            * launch each); it stands still in a steady run of group calls with fixed position buffers */
+};
+/* the bits of AGBNP_HIP_SCALAR_OVERFLOW_KINDS */
+enum agbnp_hip_overflow_kind {
+  AGBNP_HIP_OVERFLOW_NODES = 1,            /* a subtree outgrew the store's nodes */
+  AGBNP_HIP_OVERFLOW_ATOMS = 2,            /* ... its local atoms */
+  AGBNP_HIP_OVERFLOW_PACKING = 4,          /* a forest packing mispredicted */
+  AGBNP_HIP_OVERFLOW_ROW = 8,              /* a neighbour row outgrew its walk */
+  AGBNP_HIP_OVERFLOW_REORDERED = 16,       /* the context reordered its atoms */
+  AGBNP_HIP_OVERFLOW_FOREST_NODES = 32,    /* a forest of several work items outgrew its nodes */
+  AGBNP_HIP_OVERFLOW_FOREST_ATOMS = 64,    /* ... its local atoms (the two kinds of AGBNP_HIP_OVERFLOW_PACKING) */
+  AGBNP_HIP_OVERFLOW_SPLIT_PARTS = 256     /* bits 8..: times the part count of a lone work item that asked for its subtree to be
+                                            * shared further */
+};
+/* vectors: length N, atom order */
+enum agbnp_hip_vector {
+  AGBNP_HIP_VECTOR_SELFVOL_VDW = 0,        /* self volume (vdW radii) */
+  AGBNP_HIP_VECTOR_BORN = 1,               /* Born radius */
+  AGBNP_HIP_VECTOR_SCALE = 2,              /* volume scaling factor */
+  AGBNP_HIP_VECTOR_SELFVOL_LARGE = 3,      /* self volume (enlarged radii); only collected after agbnp_hip_set_diagnostics(ctx, 1) */
+  AGBNP_HIP_VECTOR_SUBTREE_NODES = 4,      /* nodes and */
+  AGBNP_HIP_VECTOR_SUBTREE_ATOMS = 5       /* local atoms of the overlap subtree rooted at the atom (tree shape, capacity planning) */
+};
 int agbnp_hip_set_diagnostics(agbnp_hip_context* ctx, int enabled); /* vector 3 is only collected when enabled */
 int agbnp_hip_get_scalar(agbnp_hip_context* ctx, int which, double* value);
 int agbnp_hip_get_vector(agbnp_hip_context* ctx, int which, double* out);

@@ -63,8 +63,8 @@ hipError_t launch_order_maps(int n, const int* atom_index, const int* a2h, int* 
 __global__ __launch_bounds__(256) void k_row_atoms(int nwords, const int* __restrict__ rows, const int* __restrict__ map, int* __restrict__ row_atoms) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;  // item k of work slot s: w = kMaxItems * s + k
   if (w >= nwords) return;
-  const int item = rows[(size_t)kRowStride * (w / kMaxItems) + (w % kMaxItems)];
-  row_atoms[w] = item >= 0 ? map[item & 0xffffff] : 0;
+  const int item = rows[slot_row_item(w / kMaxItems, w % kMaxItems)];
+  row_atoms[w] = item >= 0 ? map[work_item_root(item)] : 0;
 }
 
 hipError_t launch_row_atoms(int nslots, const int* rows, const int* map, int* row_atoms, hipStream_t st) {

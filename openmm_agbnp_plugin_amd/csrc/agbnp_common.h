@@ -5,7 +5,16 @@
 #pragma once
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+
+// the small encoders / decoders below are shared by the host and the kernels (i4_tables.cpp reads this header as plain C++);
+// inlined before anything else runs, so that a kernel compiles to what it did with the expression written out
+#ifdef __HIPCC__
+#define AGBNP_HD __host__ __device__ __attribute__((always_inline))
+#else
+#define AGBNP_HD
+#endif
 
 namespace agbnp {
 
@@ -47,8 +56,89 @@ struct SubtreeHeader {
 // workgroup sweeping all younger positions itself moved 50 MB through the L2 per evaluation of 1dwc -- the sweep
 // was bound by that, not by its arithmetic.)
 
+// ---- Words that the host and the kernels share.  Every block of control state on the device, and every packed encoding
+// that travels between them, is defined HERE and nowhere else (tests/test_host_api.py keeps the literal spellings out of
+// the other files).  Three places in the kernels write an encoding out with the named constants below instead of calling its
+// helper (cavity_forests in tree_kernels.hip, prep_role.h, the work-item buffers of k_rows): through the helper the same
+// arithmetic reaches the optimiser in another order and the kernel leaves with another register allocation.
+
 constexpr int kMaxItems = 8;  // work items (subtrees or parts of one) per work slot = forest
 constexpr int kRowStride = 16;  // a work slot's row: kMaxItems items, their number, padding -- 64 bytes, ONE load instruction
+// a work slot's row (PairArgs::rows / TreeArgs::rows): where item k of slot s stands, and where the number of its items
+AGBNP_HD constexpr size_t slot_row_item(size_t slot, size_t k) { return (size_t)kRowStride * slot + k; }
+AGBNP_HD constexpr size_t slot_row_count(size_t slot) { return (size_t)kRowStride * slot + kMaxItems; }
+
+// work item of the tree launches = heavy index of the root | part << kWorkItemPartShift | (parts - 1) << kWorkItemPartsShift:
+// a big subtree is shared by `parts` (1..4) work items, of which this is number `part`
+constexpr int kWorkItemPartShift = 24, kWorkItemPartsShift = 26;
+AGBNP_HD constexpr int make_work_item(int root, int part, int parts) {
+  return root | (part << kWorkItemPartShift) | ((parts - 1) << kWorkItemPartsShift);
+}
+AGBNP_HD constexpr int work_item_root(int e) { return e & ((1 << kWorkItemPartShift) - 1); }
+AGBNP_HD constexpr int work_item_part(int e) { return (e >> kWorkItemPartShift) & 3; }
+AGBNP_HD constexpr int work_item_parts(int e) { return ((e >> kWorkItemPartsShift) & 3) + 1; }
+
+// tile item of the pair stages' tile kernels = I | J << 12 | flag over blocks of 64 (I <= J < 4096); kTileStripFlag: the
+// item is a strip of the two i blocks I, I + 1 against block J (gb_strip, pair_kernels.hip)
+constexpr int kTileBlocksMax = 4095;
+constexpr int kTileStripFlag = 1 << 24;
+AGBNP_HD constexpr int make_tile_item(int I, int J, int flag = 0) { return I | (J << 12) | flag; }
+AGBNP_HD constexpr int tile_I(int item) { return item & 0xfff; }
+AGBNP_HD constexpr int tile_J(int item) { return (item >> 12) & 0xfff; }
+
+// entry of a neighbour list of the row launches (and of the candidate orders hperm / aperm they are built from)
+// = index | radius type << kRowEntryTypeShift; ~0u is padding
+constexpr int kRowEntryTypeShift = 24;
+AGBNP_HD constexpr unsigned make_row_entry(unsigned index, unsigned type) { return index | (type << kRowEntryTypeShift); }
+AGBNP_HD constexpr unsigned row_entry_index(unsigned e) { return e & ((1u << kRowEntryTypeShift) - 1); }
+AGBNP_HD constexpr unsigned row_entry_type(unsigned e) { return e >> kRowEntryTypeShift; }
+// work item of a row launch = list | slice << kRowItemSliceShift (one wave walks one slice of one list)
+constexpr int kRowItemSliceShift = 24;
+AGBNP_HD constexpr unsigned make_row_item(unsigned list, unsigned slice) { return list | (slice << kRowItemSliceShift); }
+AGBNP_HD constexpr unsigned row_item_list(unsigned it) { return it & ((1u << kRowItemSliceShift) - 1); }
+AGBNP_HD constexpr unsigned row_item_slice(unsigned it) { return it >> kRowItemSliceShift; }
+
+// The packing block (one int array: agbnp_hip_context::d_forest = TreeArgs::packing = PairArgs::forest_start).  Words
+// [0, slot_cap] are forest_start: forest f of the NEXT evaluation holds the work items order[forest_start[f] ..
+// forest_start[f + 1]).  Behind them, at slot_cap + PackingWord:
+enum PackingWord {
+  kPackForestsNext = 1,  // work slots (forests) of the NEXT evaluation: rewritten by the bookkeeping while this one's pair stages run
+                         // (PairArgs::nforests)
+  kPackForestsNow = 2,   // the copy k_tree_cavity takes for THIS evaluation: energy partials are per slot (PairArgs::cur_nforests)
+  kPackState = 3,        // PairArgs::pack_state: the persistent words of the bookkeeping, indexed by PackStateWord
+};
+enum PackStateWord {
+  kPsLevel = 0,       // how far the store capacity that the packing assumes is tightened (0: not; relaxes again after kPsNeed
+                      // clean evaluations in a row)
+  kPsAge = 1,         // evaluations since the packing in use was planned (huge = it is no plan: one work item per slot, and the
+                      // next evaluation's bookkeeping plans at once)
+  kPsClean = 2,       // clean evaluations in a row since the assumed capacity was last tightened or relaxed
+  kPsPlans = 3,       // packings planned so far (a diagnostic)
+  kPsTotalNodes = 4,  // total nodes and
+  kPsMaxNodes = 5,    // largest subtree of the evaluation the packing in use was planned from (drift trigger)
+  kPsEpoch = 6,       // five-launch mode: the tree launches' copy of the device's evaluation counter (beside the forest counts
+                      // they read first: the same cache line, no cold round trip of its own)
+  kPsHeat = 7,        // leaky count of evaluations with healed forests (packing_role)
+  kPsNeed = 8,        // clean evaluations in a row that are asked for before a tightened level is given back (the level's memory)
+  kPsWords = 9,
+  kPsReported = kPsPlans + 1  // the words in front that the host reads back with every harvest
+};
+constexpr size_t packing_words(size_t slot_cap) { return slot_cap + kPackState + kPsWords; }
+
+// The row-flag block (agbnp_hip_context::d_nl_flag = PairArgs::nl_flag) of the row-form pair stages
+enum RowFlagWord {
+  kNlStale = 0,   // != 0: the neighbour rows are stale for THIS evaluation (k_prep sets it, the rows' close clears it and counts
+                  // the build; 1 on a fresh context)
+  kNlBuilds = 1,  // how often the rows have been built so far; its parity names the work-item buffers in use
+  kNlSlice = 2,   // entries per slice of a list (one wave walks a slice), tuned on the device: it only grows
+  kNlEpoch = 3,   // five-launch mode: the pair launches' copy of the device's evaluation counter (PairArgs::epoch)
+  kNlFlagWords = 4,
+  kNlReported = kNlEpoch  // the words in front that the host reads back with every harvest
+};
+// PairArgs::nl_nitems [3 kinds][kRowBuffers] and nl_items [3 kinds][kRowBuffers][nl_items_cap]: buffer `buf` (builds & 1 is
+// the one in use) of the rows of `kind` (RowKind)
+constexpr int kRowKinds = 3, kRowBuffers = 2;
+AGBNP_HD constexpr int row_items_index(int kind, int buf) { return kRowBuffers * kind + buf; }
 
 // status/overflow word indices (device int array of kStatTotalWords).
 // Words [0, kStatEvalWords) belong to ONE evaluation: k_prep clears them.  The words from kStatEvalSeq on are STICKY:
@@ -95,6 +185,10 @@ enum StatusWord {
   kStatBadBits = 2048,
   kStatTotalWords = kStatBadBitmap + kStatBadBits / 32
 };
+// five-launch mode: the words of ONE evaluation exist twice (agbnp_hip_context::d_estatus), one block of this many ints per
+// parity of the evaluation counter (an int, not an enumerator: it is multiplied by a signed parity)
+constexpr int kStatBlockStride = 16;
+static_assert(kStatEvalWords <= kStatBlockStride, "a parity's block of per-evaluation status words");
 
 // kernel ids of one evaluation, in launch order (bench/profiling support)
 enum KernelId {

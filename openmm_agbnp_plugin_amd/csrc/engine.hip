@@ -226,18 +226,21 @@ struct agbnp_hip_context {
   int carried_count = 0, carried_seq = 0;
   bool unfinished = false;      // evaluations enqueued by execute_device / execute_openmm since the last finish
   int enqueued = 0;             // ... how many: what agbnp_hip_wait_verdict waits for (the device numbers them the same way)
-  int last_pack[4] = {0, 0, 0, 0};  // {level, age, clean replans in a row, plans so far} of the forest packing as of the last harvest
+  int last_pack[kPsReported] = {0};  // the forest packing's words up to kPsPlans (PackStateWord) as of the last harvest
   int* h_status = nullptr;      // pinned, mapped: {evaluations completed, withheld} since the last finish (agbnp_hip_poll)
-  // pinned staging of the host-facing paths: what harvest() reads of the device arrives by asynchronous copies in front of
-  // ONE stream synchronisation (four blocking reads before); execute_host's positions, forces and energy travel through
-  // h_xfer ([3n] in, [3n + 1] out) instead of pageable memory
+  // what harvest() reads of the device: asynchronous copies in front of ONE stream synchronisation.  With the pinned staging
+  // of the host-facing paths the report lives in pinned memory (h_report), without it (AGBNP_HIP_NO_PINNED_STAGING) in the
+  // context (own_report); execute_host's positions, forces and energy travel through h_xfer ([3n] in, [3n + 1] out) instead
+  // of pageable memory
   struct HostReport {
     int status[kStatTotalWords];
     double components[4];
-    int rows[4], pack[4];
-    int five[36];  // five-launch mode: the two blocks of per-evaluation status words, then the device's evaluation counter
+    int rows[kNlReported], pack[kPsReported];
+    int five[2 * kStatBlockStride];  // five-launch mode: the two blocks of per-evaluation status words ...
+    int epoch;                       // ... and the device's evaluation counter
   };
   HostReport* h_report = nullptr;
+  HostReport own_report{};
   double* h_xfer = nullptr;
   // agbnp_hip_execute_host's short cut: an evaluation that the pinned status words call complete skips the reads of the
   // device (they are diagnostics) and leaves the log running; the reads are caught up with when somebody asks for a
@@ -256,7 +259,7 @@ struct agbnp_hip_context {
                                 // synchronised for the hand-over, so it is safe inside a graph capture)
   int last_device_seq = 0;      // harvest(): evaluations of the device-resident entry points that the log just read held
   std::vector<void*> user_streams;  // streams the caller has enqueued on since the last finish (drained before parameters change)
-  int last_rows[3] = {0, 0, 0};  // {stale flag, builds so far, entries per slice} of the row-form neighbour rows, as of the last harvest
+  int last_rows[kNlReported] = {0};  // the row-flag block's words up to kNlSlice (RowFlagWord) as of the last harvest
   int row_slice = 0;           // AGBNP_HIP_ROW_SLICE: entries per slice, fixed (0: tuned on the device, see rows_close_evaluation)
   bool have_results = false;
   bool diagnostics = false;
@@ -436,14 +439,14 @@ void apply_parity(agbnp_hip_context* c) {
   T.hv = c->htable(p);
   P.sizes = c->d_sizes.p + (size_t)p * nhp;
   T.sizes = P.sizes;
-  P.estatus = five ? c->d_estatus.p + 16 * p : c->d_status.p;
+  P.estatus = five ? c->d_estatus.p + kStatBlockStride * p : c->d_status.p;
   T.status = P.estatus;  // (the tree kernels only touch words of their own evaluation)
   P.five = T.five = five ? (c->five_device ? 2 : 1) : 0;
   // the counter exists twice, each copy beside what its readers read first (a cold scalar load of its own costs a launch
   // 0.1-0.3 us): the pair launches' in the neighbour rows' flag line, the tree launches' behind the forest counts; the
   // bookkeeping role advances both
-  P.epoch = c->d_nl_flag.p ? c->d_nl_flag.p + 3 : c->d_epoch.p;
-  P.epoch_tree = c->d_forest.p + (size_t)c->slot_cap + 9;
+  P.epoch = c->d_nl_flag.p ? c->d_nl_flag.p + kNlEpoch : c->d_epoch.p;
+  P.epoch_tree = c->d_forest.p + (size_t)c->slot_cap + kPackState + kPsEpoch;
   T.epoch = P.epoch_tree;
   P.table_doubles = T.table_doubles = (size_t)kHvRows * c->hstride;
   P.sizes_stride = T.sizes_stride = nhp;
@@ -451,7 +454,7 @@ void apply_parity(agbnp_hip_context* c) {
   // (five == 1: the host names the set the trailing workgroups clear, too; five == 2: rebase_for_parity does)
   P.next_hv = (five && !c->five_device) ? c->htable(1 - p) : nullptr;
   P.next_sizes = (five && !c->five_device) ? c->d_sizes.p + (size_t)(1 - p) * nhp : nullptr;
-  P.next_estatus = (five && !c->five_device) ? c->d_estatus.p + 16 * (1 - p) : nullptr;
+  P.next_estatus = (five && !c->five_device) ? c->d_estatus.p + kStatBlockStride * (1 - p) : nullptr;
   P.mask_ref = c->d_mask_ref.p;
   P.mask_move2 = 0.25 * c->cfg.mask_skin * c->cfg.mask_skin;
   P.row_atoms = five ? c->d_row_atoms.p : nullptr;
@@ -631,11 +634,11 @@ void wire_args(agbnp_hip_context* c) {
   T.nbmask = c->d_nbmask.p;
   T.nhb = nhb_c;
   {
-    const size_t nhp1 = (size_t)c->slot_cap;
+    int* const tail = c->d_forest.p + (size_t)c->slot_cap;  // (the packing block: PackingWord, agbnp_common.h)
     P.forest_start = c->d_forest.p;
-    P.nforests = c->d_forest.p + nhp1 + 1;
-    P.cur_nforests = c->d_forest.p + nhp1 + 2;
-    P.pack_state = c->d_forest.p + nhp1 + 3;
+    P.nforests = tail + kPackForestsNext;
+    P.cur_nforests = tail + kPackForestsNow;
+    P.pack_state = tail + kPackState;
     P.ncus = c->cus;
     P.tree_slot_cap = c->slot_cap;
     P.tree_node_cap = tree_variant_node_cap(c->variant);
@@ -692,8 +695,8 @@ int allocate_rows(agbnp_hip_context* c) {
   c->row_fill = c->cfg.row_fill;
   auto sorted_by_type = [&](int count, auto type_of) {
     std::vector<unsigned> v;
-    for (int k = 0; k < count; k++) v.push_back((unsigned)k | ((unsigned)type_of(k) << 24));
-    std::stable_sort(v.begin(), v.end(), [](unsigned a, unsigned b) { return (a >> 24) < (b >> 24); });
+    for (int k = 0; k < count; k++) v.push_back(make_row_entry((unsigned)k, (unsigned)type_of(k)));
+    std::stable_sort(v.begin(), v.end(), [](unsigned a, unsigned b) { return row_entry_type(a) < row_entry_type(b); });
     while (v.size() % 64 != 0) v.push_back(~0u);
     return v;
   };
@@ -747,17 +750,18 @@ int allocate_rows(agbnp_hip_context* c) {
     const size_t most = std::max(std::max(born_lists * ((c->nlh_stride + 255) / 256), chain_lists * ((c->nla_stride + 255) / 256)),
                                  gb_lists * ((c->nlg_stride + 255) / 256));
     c->nl_items_cap = (int)std::min<size_t>(most + 8, 1u << 30);
-    HIP_TRY(c, c->d_nl_items.alloc((size_t)6 * c->nl_items_cap));
-    HIP_TRY(c, hipMemset(c->d_nl_items.p, 0, sizeof(unsigned) * 6 * (size_t)c->nl_items_cap));
-    HIP_TRY(c, c->d_nl_nitems.alloc(6));
-    HIP_TRY(c, hipMemset(c->d_nl_nitems.p, 0, sizeof(int) * 6));
+    HIP_TRY(c, c->d_nl_items.alloc((size_t)kRowKinds * kRowBuffers * c->nl_items_cap));
+    HIP_TRY(c, hipMemset(c->d_nl_items.p, 0, sizeof(unsigned) * kRowKinds * kRowBuffers * (size_t)c->nl_items_cap));
+    HIP_TRY(c, c->d_nl_nitems.alloc(kRowKinds * kRowBuffers));
+    HIP_TRY(c, hipMemset(c->d_nl_nitems.p, 0, sizeof(int) * kRowKinds * kRowBuffers));
   }
   HIP_TRY(c, c->d_nlh_count.alloc(born_lists));
   HIP_TRY(c, c->d_nla_count.alloc(chain_lists));
   HIP_TRY(c, hipMemset(c->d_nlh_count.p, 0, sizeof(int) * born_lists));
   HIP_TRY(c, hipMemset(c->d_nla_count.p, 0, sizeof(int) * chain_lists));
-  // {stale: the first evaluation builds the rows; builds so far; entries per slice}
-  const std::vector<int> flag = {1, 0, c->row_slice > 0 ? std::min(std::max(c->row_slice, kRowSlice), kRowSliceMax) / 64 * 64 : kRowSlice, 0};
+  std::vector<int> flag(kNlFlagWords, 0);
+  flag[kNlStale] = 1;  // (the first evaluation builds the rows)
+  flag[kNlSlice] = c->row_slice > 0 ? std::min(std::max(c->row_slice, kRowSlice), kRowSliceMax) / 64 * 64 : kRowSlice;
   HIP_TRY(c, c->d_nl_flag.upload(flag));
   HIP_TRY(c, c->d_nl_ref.alloc(3 * (size_t)n));
   HIP_TRY(c, hipMemset(c->d_nl_ref.p, 0xff, sizeof(double) * 3 * (size_t)n));  // NaN: every atom has "moved"
@@ -798,16 +802,15 @@ int allocate_work(agbnp_hip_context* c) {
   const int nblk = (n + 63) / 64;
   {
     // work items of the symmetric GB tile kernel: one workgroup per tile, off-diagonal tiles first
-    if (nblk > 4095) return c->fail(AGBNP_HIP_ERR_CAPACITY, "more than 262080 particles are not supported by the tile index encoding");
-    // away from the diagonal: strips of two i blocks (2p, 2p + 1) against one j block (flag bit 24, see gb_strip);
+    if (nblk > kTileBlocksMax) return c->fail(AGBNP_HIP_ERR_CAPACITY, "more than 262080 particles are not supported by the tile index encoding");
+    // away from the diagonal: strips of two i blocks (2p, 2p + 1) against one j block (kTileStripFlag, see gb_strip);
     // around it: single 64 x 64 tiles
-    constexpr int kStrip = 1 << 24;
     std::vector<int> items;
     items.reserve((size_t)nblk * nblk / 2 + 4);
     for (int p2 = 0; 2 * p2 + 1 < nblk; p2++)
-      for (int J = 2 * p2 + 2; J < nblk; J++) items.push_back((2 * p2) | (J << 12) | kStrip);
-    for (int p2 = 0; 2 * p2 + 1 < nblk; p2++) items.push_back((2 * p2) | ((2 * p2 + 1) << 12));
-    for (int I = 0; I < nblk; I++) items.push_back(I | (I << 12));
+      for (int J = 2 * p2 + 2; J < nblk; J++) items.push_back(make_tile_item(2 * p2, J, kTileStripFlag));
+    for (int p2 = 0; 2 * p2 + 1 < nblk; p2++) items.push_back(make_tile_item(2 * p2, 2 * p2 + 1));
+    for (int I = 0; I < nblk; I++) items.push_back(make_tile_item(I, I));
     HIP_TRY(c, c->d_gb_items.upload(items));
     c->P.egb_parts = (int)items.size();
   }
@@ -836,11 +839,11 @@ int allocate_work(agbnp_hip_context* c) {
     // launch is one round (every workgroup resident at once) and workgroup b starts on CU b mod (number of CUs), so
     // the sorted tiles are dealt over the CUs in serpentine order: every CU gets the same mix of heavy and light ones.
     std::vector<int> sorted;
-    for (int I = 0; I < nhb; I++) sorted.push_back(I | (I << 12));
+    for (int I = 0; I < nhb; I++) sorted.push_back(make_tile_item(I, I));
     for (int I = 0; I < nhb; I++)
-      for (int J = I + 1; J < nhb; J++) sorted.push_back(I | (J << 12));
+      for (int J = I + 1; J < nhb; J++) sorted.push_back(make_tile_item(I, J));
     for (int I = 0; I < nhb; I++)
-      for (int J = nhb; J < nhb + nlb; J++) sorted.push_back(I | (J << 12));
+      for (int J = nhb; J < nhb + nlb; J++) sorted.push_back(make_tile_item(I, J));
     std::vector<int> items(sorted.size());
     {
       const size_t width = (size_t)std::max(c->cus, 1);
@@ -868,7 +871,7 @@ int allocate_work(agbnp_hip_context* c) {
   {
     // level-2 neighbour search: tiles of 64x64 heavy atoms (I <= J), one 64-bit mask per (atom, block)
     const int nhb = (nh + 63) / 64;
-    if (nhb > 4095) return c->fail(AGBNP_HIP_ERR_CAPACITY, "more than 262080 heavy atoms are not supported by the tile index encoding");
+    if (nhb > kTileBlocksMax) return c->fail(AGBNP_HIP_ERR_CAPACITY, "more than 262080 heavy atoms are not supported by the tile index encoding");
     const size_t words = (size_t)nhb * nhb * 64;
     HIP_TRY(c, c->d_nbmask.alloc(std::max<size_t>(words, 64)));
     HIP_TRY(c, hipMemset(c->d_nbmask.p, 0, sizeof(unsigned long long) * std::max<size_t>(words, 64)));
@@ -885,10 +888,9 @@ int allocate_work(agbnp_hip_context* c) {
   HIP_TRY(c, c->d_sizes.alloc((c->five ? 2 : 1) * nhp));
   HIP_TRY(c, hipMemset(c->d_sizes.p, 0, sizeof(int2) * (c->five ? 2 : 1) * nhp));
   if (c->five) {
-    HIP_TRY(c, c->d_estatus.alloc(2 * 16));
-    HIP_TRY(c, hipMemset(c->d_estatus.p, 0, sizeof(int) * 2 * 16));  // (fast mode + single keep their own Born rows: no mask tiles there, see five_active)
-    static_assert(kStatEvalWords <= 16, "a parity's block of per-evaluation status words");
-    HIP_TRY(c, c->d_epoch.upload(std::vector<int>(4, 0)));
+    HIP_TRY(c, c->d_estatus.alloc(2 * kStatBlockStride));
+    HIP_TRY(c, hipMemset(c->d_estatus.p, 0, sizeof(int) * 2 * kStatBlockStride));  // (fast mode + single keep their own Born rows: no mask tiles there, see five_active)
+    HIP_TRY(c, c->d_epoch.upload(std::vector<int>(kNlFlagWords, 0)));
     HIP_TRY(c, c->d_mask_ref.upload(std::vector<double>(3 * nhp, std::nan(""))));
     HIP_TRY(c, c->d_row_atoms.alloc((size_t)kMaxItems * nslots));
     HIP_TRY(c, hipMemset(c->d_row_atoms.p, 0, sizeof(int) * kMaxItems * nslots));
@@ -1108,8 +1110,8 @@ int upload_identity_packing(agbnp_hip_context* c) {
   std::vector<int> ident((size_t)kRowStride * nslots, -1);  // slot s: its one work item, -1 = no item, and the number 1
   for (size_t k = 0; k < nslots; k++) {
     const size_t item = std::min(k, nhp - 1);
-    ident[(size_t)kRowStride * k] = (int)(item / parts) | (int)((item % parts) << 24) | (int)((parts - 1) << 26);  // (work_item_root / _part / _parts)
-    ident[(size_t)kRowStride * k + kMaxItems] = 1;
+    ident[slot_row_item(k, 0)] = make_work_item((int)(item / parts), (int)(item % parts), (int)parts);
+    ident[slot_row_count(k)] = 1;
   }
   HIP_TRY(c, c->d_rows.upload(ident));
   if (c->five) {  // (five-launch mode: the atom of every item's root, beside the rows)
@@ -1121,30 +1123,18 @@ int upload_identity_packing(agbnp_hip_context* c) {
   HIP_TRY(c, c->d_order.upload(std::vector<int>((size_t)kMaxItems * nslots + 8, 0)));  // (the bookkeeping's working copies)
   HIP_TRY(c, c->d_ftime.upload(std::vector<int>(nslots + 1, 0)));
   if (c->d_pack_items.p == nullptr) HIP_TRY(c, c->d_pack_items.upload(std::vector<int>(2 * nslots + 2, 0)));
-  // layout: [0, slots] forest_start, [slots+1] number of forests, [slots+2] the count the running evaluation took,
-  // [slots+3] how often a packed forest has overflowed so far (kept), [slots+4] the age of the packing in evaluations
-  // (huge: this one is no plan, the next evaluation's bookkeeping plans at once)
-  std::vector<int> forest(nslots + 3);  // (+ three persistent words behind it, see below)
+  // the packing block (PackingWord, agbnp_common.h): every persistent word 0 but the age -- huge: this one is no plan
+  std::vector<int> forest(packing_words(nslots), 0);
   const int nitems = c->nh > 0 ? (int)nhp : 0;
   for (size_t k = 0; k <= nslots; k++) forest[k] = (int)std::min(k, (size_t)nitems);
-  forest[nslots + 1] = nitems;
-  forest[nslots + 2] = nitems;
-  const int no_plan = 1 << 20;
-  if (c->d_forest.p == nullptr) {
-    forest.push_back(0);
-    forest.push_back(no_plan);
-    forest.push_back(0);  // [slots+5] clean evaluations in a row since the assumed capacity was last tightened or relaxed
-    forest.push_back(0);  // [slots+6] packings planned so far (diagnostic: bench.py counts the plans inside a timed region)
-    forest.push_back(0);  // [slots+7] total nodes and
-    forest.push_back(0);  // [slots+8] largest subtree of the evaluation the packing in use was planned from (drift trigger)
-    forest.push_back(0);  // [slots+9] five-launch mode: the tree launches' copy of the device's evaluation counter (beside the
-                          // forest count they read first: the same cache line, no cold round trip of its own)
-    forest.push_back(0);  // [slots+10] the packing's `heat`: a leaky count of evaluations with healed forests (packing_role)
-    forest.push_back(0);  // [slots+11] ... and `need`: clean evaluations in a row before a tightened level is given back (its memory)
+  forest[nslots + kPackForestsNext] = nitems;
+  forest[nslots + kPackForestsNow] = nitems;
+  forest[nslots + kPackState + kPsAge] = 1 << 20;
+  if (c->d_forest.p == nullptr)
     return c->d_forest.upload(forest) == hipSuccess ? AGBNP_HIP_OK : c->fail(AGBNP_HIP_ERR_DEVICE, "upload of the forest packing failed");
-  }
-  HIP_TRY(c, hipMemcpy(c->d_forest.p, forest.data(), sizeof(int) * forest.size(), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(c->d_forest.p + nslots + 4, &no_plan, sizeof(int), hipMemcpyHostToDevice));
+  // a context that has run: the forest counts and the age in place, the other persistent words kept
+  HIP_TRY(c, hipMemcpy(c->d_forest.p, forest.data(), sizeof(int) * (nslots + kPackState), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->d_forest.p + nslots + kPackState + kPsAge, &forest[nslots + kPackState + kPsAge], sizeof(int), hipMemcpyHostToDevice));
   return AGBNP_HIP_OK;
 }
 
@@ -1152,19 +1142,19 @@ int upload_identity_packing(agbnp_hip_context* c) {
 // previous harvest whose forces and energy were withheld on the device (the caller must run those again).
 int harvest(agbnp_hip_context* c, int* repeat, hipStream_t st) {
   *repeat = 0;
-  // what is read of the device: asked for behind everything on the stream, then ONE wait
-  if (c->h_report) {
-    agbnp_hip_context::HostReport* r = c->h_report;
-    HIP_TRY(c, hipMemcpyAsync(r->status, c->d_status.p, sizeof(int) * kStatTotalWords, hipMemcpyDeviceToHost, st));
-    if (c->five_active)  // (the words of ONE evaluation live in its parity's block: both blocks come along, the counter says which)
-      HIP_TRY(c, hipMemcpyAsync(r->five, c->d_estatus.p, sizeof(int) * 32, hipMemcpyDeviceToHost, st));
-    if (c->five_active) HIP_TRY(c, hipMemcpyAsync(r->five + 32, c->P.epoch_tree, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(r->components, c->d_components.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
-    if (c->rows_capable) HIP_TRY(c, hipMemcpyAsync(r->rows, c->d_nl_flag.p, sizeof(int) * 3, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(r->pack, c->d_forest.p + c->slot_cap + 3, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    // ... and a new log starts behind the reads, in front of the same wait (an empty log is cleared to what it is)
-    HIP_TRY(c, hipMemsetAsync(c->d_status.p + kStatEvalSeq, 0, sizeof(int) * (kStatTotalWords - kStatEvalSeq), st));
+  // what is read of the device: asked for behind everything on the stream, then ONE wait (the report: in pinned memory, or
+  // -- without the pinned staging -- in the context)
+  agbnp_hip_context::HostReport* r = c->h_report ? c->h_report : &c->own_report;
+  HIP_TRY(c, hipMemcpyAsync(r->status, c->d_status.p, sizeof(r->status), hipMemcpyDeviceToHost, st));
+  if (c->five_active) {  // (the words of ONE evaluation live in its parity's block: both blocks come along, the counter says which)
+    HIP_TRY(c, hipMemcpyAsync(r->five, c->d_estatus.p, sizeof(r->five), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&r->epoch, c->P.epoch_tree, sizeof(int), hipMemcpyDeviceToHost, st));
   }
+  HIP_TRY(c, hipMemcpyAsync(r->components, c->d_components.p, sizeof(r->components), hipMemcpyDeviceToHost, st));
+  if (c->rows_capable) HIP_TRY(c, hipMemcpyAsync(r->rows, c->d_nl_flag.p, sizeof(r->rows), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(r->pack, c->d_forest.p + c->slot_cap + kPackState, sizeof(r->pack), hipMemcpyDeviceToHost, st));
+  // ... and a new log starts behind the reads, in front of the same wait (an empty log is cleared to what it is)
+  HIP_TRY(c, hipMemsetAsync(c->d_status.p + kStatEvalSeq, 0, sizeof(int) * (kStatTotalWords - kStatEvalSeq), st));
   HIP_TRY(c, hipStreamSynchronize(st));
   // per-kernel durations of everything enqueued since the last harvest
   Timeline& tl = c->timeline;
@@ -1177,37 +1167,21 @@ int harvest(agbnp_hip_context* c, int* repeat, hipStream_t st) {
     c->kernel_launches[id]++;
   }
   tl.used = 0;
-  if (c->h_report) {
-    std::memcpy(c->last_status, c->h_report->status, sizeof(int) * kStatTotalWords);
-    if (c->five_active) {
-      // (device count: the last evaluation took epoch & 1 BEFORE its bookkeeping role advanced the counter; the host's count is one ahead as well)
-      c->parity = c->five_device ? (c->h_report->five[32] + 1) & 1 : (c->five_evals + 1) & 1;
-      std::memcpy(c->last_status, c->h_report->five + 16 * c->parity, sizeof(int) * kStatEvalWords);
-    }
-    std::memcpy(c->last_components, c->h_report->components, sizeof(double) * 4);
-    if (c->rows_capable) std::memcpy(c->last_rows, c->h_report->rows, sizeof(int) * 3);
-    std::memcpy(c->last_pack, c->h_report->pack, sizeof(int) * 4);
-  } else {
-    HIP_TRY(c, hipMemcpy(c->last_status, c->d_status.p, sizeof(int) * kStatTotalWords, hipMemcpyDeviceToHost));
-    if (c->five_active) {
-      int five[33];
-      HIP_TRY(c, hipMemcpy(five, c->d_estatus.p, sizeof(int) * 32, hipMemcpyDeviceToHost));
-      HIP_TRY(c, hipMemcpy(five + 32, c->P.epoch_tree, sizeof(int), hipMemcpyDeviceToHost));
-      c->parity = c->five_device ? (five[32] + 1) & 1 : (c->five_evals + 1) & 1;  // (either count is one ahead of the last evaluation)
-      std::memcpy(c->last_status, five + 16 * c->parity, sizeof(int) * kStatEvalWords);
-    }
-    HIP_TRY(c, hipMemcpy(c->last_components, c->d_components.p, sizeof(double) * 4, hipMemcpyDeviceToHost));
-    if (c->rows_capable) HIP_TRY(c, hipMemcpy(c->last_rows, c->d_nl_flag.p, sizeof(int) * 3, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(c->last_pack, c->d_forest.p + c->slot_cap + 3, sizeof(int) * 4, hipMemcpyDeviceToHost));
+  std::memcpy(c->last_status, r->status, sizeof(r->status));
+  if (c->five_active) {
+    // (device count: the last evaluation took epoch & 1 BEFORE its bookkeeping role advanced the counter; the host's count is one ahead as well)
+    c->parity = c->five_device ? (r->epoch + 1) & 1 : (c->five_evals + 1) & 1;
+    std::memcpy(c->last_status, r->five + kStatBlockStride * c->parity, sizeof(int) * kStatEvalWords);
   }
+  std::memcpy(c->last_components, r->components, sizeof(r->components));
+  if (c->rows_capable) std::memcpy(c->last_rows, r->rows, sizeof(r->rows));
+  std::memcpy(c->last_pack, r->pack, sizeof(r->pack));
   const int* s = c->last_status;
   c->withheld.clear();
   c->withheld_count = s[kStatBadCount];
   if (s[kStatEvalSeq] > 0) c->forests_hint = s[kStatForests];  // (what the NEXT evaluation runs on, written by the last one's bookkeeping)
   // the last evaluation's own words say whether the diagnostics on the device are those of a complete evaluation
   c->have_results = s[kStatEvalSeq] > 0 ? !(s[kStatNodeOverflow] | s[kStatAtomOverflow] | s[kStatPackOverflow] | s[kStatOrderStale] | s[kStatRowOverflow]) : c->have_results;
-  if (!c->h_report && (s[kStatEvalSeq] != 0 || s[kStatBadCount] != 0))  // start a new log
-    HIP_TRY(c, hipMemset(c->d_status.p + kStatEvalSeq, 0, sizeof(int) * (kStatTotalWords - kStatEvalSeq)));
   if (c->h_status) c->h_status[0] = c->h_status[1] = 0;  // (the stream is idle: nothing writes it now)
   const int host_first = c->lazy_evals;  // the log's first entries are execute_host's own (every one of them complete)
   c->last_device_seq = std::max(0, s[kStatEvalSeq] - host_first);
@@ -1248,7 +1222,7 @@ int harvest(agbnp_hip_context* c, int* repeat, hipStream_t st) {
     } else {
       c->row_boost *= 2;
       const int stale = 1;  // (the work items were laid down for the narrower walk: rebuilt with the lists)
-      HIP_TRY(c, hipMemcpy(c->d_nl_flag.p, &stale, sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(c->d_nl_flag.p + kNlStale, &stale, sizeof(int), hipMemcpyHostToDevice));
     }
     wire_args(c);
     c->generation++;
@@ -1949,50 +1923,39 @@ int agbnp_hip_get_scalar(agbnp_hip_context* c, int which, double* value) {
     const int rc_ = catch_up(c);
     if (rc_ != AGBNP_HIP_OK) return rc_;
   }
-  if (which == 15) {  // why the last agbnp_hip_finish withheld evaluations (valid whether or not an evaluation has completed)
-    const int* s = c->last_status;
-    *value = (s[kStatStickyNode] ? 1 : 0) | (s[kStatStickyAtom] ? 2 : 0) | (s[kStatStickyPack] ? 4 : 0) | (s[kStatStickyRow] ? 8 : 0) |
-             (s[kStatStickyOrder] ? 16 : 0) | (s[kStatStickyForest] << 5) | (s[kStatStickySplit] << 8);  // (32 / 64: a forest's nodes / local atoms)
-    return AGBNP_HIP_OK;
-  }
-  if (which == 18) {  // launches of an energy-only evaluation as the context runs now (0: it runs as a full evaluation)
-    *value = energy_only_fast(c) ? (c->version == 1 ? 4 : 2) : 0;
-    return AGBNP_HIP_OK;
-  }
-  if (which == 19) {  // members of the launch set whose shared launches the last evaluation ran in (0: it ran alone)
-    *value = c->group_members;
-    return AGBNP_HIP_OK;
-  }
-  if (which == 20) {  // how the last evaluation enqueued ran: 0 full, 1 energy-only launches, 2 an energy-only request run as a full evaluation
-    *value = c->last_kind;
-    return AGBNP_HIP_OK;
-  }
-  if (which == 21) {  // k_group_put launches so far: rewrites of the context's group argument blocks
-    *value = c->group_block_writes;
-    return AGBNP_HIP_OK;
-  }
-  if (which == 17) {  // forests healed inside the tree launch over the evaluations the last agbnp_hip_finish covered (none withheld for them)
-    *value = c->last_status[kStatStickyHealed];
-    return AGBNP_HIP_OK;
+  const int* s = c->last_status;
+  switch (which) {  // what is valid whether or not an evaluation has completed
+    case AGBNP_HIP_SCALAR_OVERFLOW_KINDS:
+      *value = (s[kStatStickyNode] ? AGBNP_HIP_OVERFLOW_NODES : 0) | (s[kStatStickyAtom] ? AGBNP_HIP_OVERFLOW_ATOMS : 0) |
+               (s[kStatStickyPack] ? AGBNP_HIP_OVERFLOW_PACKING : 0) | (s[kStatStickyRow] ? AGBNP_HIP_OVERFLOW_ROW : 0) |
+               (s[kStatStickyOrder] ? AGBNP_HIP_OVERFLOW_REORDERED : 0) | (s[kStatStickyForest] * AGBNP_HIP_OVERFLOW_FOREST_NODES) |
+               (s[kStatStickySplit] * AGBNP_HIP_OVERFLOW_SPLIT_PARTS);
+      return AGBNP_HIP_OK;
+    case AGBNP_HIP_SCALAR_ENERGY_ONLY_LAUNCHES: *value = energy_only_fast(c) ? (c->version == 1 ? 4 : 2) : 0; return AGBNP_HIP_OK;
+    case AGBNP_HIP_SCALAR_GROUP_MEMBERS: *value = c->group_members; return AGBNP_HIP_OK;
+    case AGBNP_HIP_SCALAR_LAST_EVALUATION_KIND: *value = c->last_kind; return AGBNP_HIP_OK;
+    case AGBNP_HIP_SCALAR_GROUP_BLOCK_WRITES: *value = c->group_block_writes; return AGBNP_HIP_OK;
+    case AGBNP_HIP_SCALAR_HEALED_FORESTS: *value = s[kStatStickyHealed]; return AGBNP_HIP_OK;
+    default: break;
   }
   if (!c->have_results) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "no completed evaluation yet");
   switch (which) {
-    case 0: *value = c->last_components[0]; break;
-    case 1: *value = c->last_components[1]; break;
-    case 2: *value = c->last_components[2]; break;
-    case 3: *value = c->last_components[3]; break;
-    case 4: *value = c->last_status[kStatMaxNodes]; break;
-    case 5: *value = c->last_status[kStatTotalNodes]; break;
-    case 6: *value = c->variant; break;
-    case 7: *value = c->last_status[kStatMaxAtoms]; break;
-    case 8: *value = c->last_status[kStatForests]; break;
-    case 9: *value = c->P.rows_on; break;        // 1: the range-limited pair stages run in row form
-    case 10: *value = c->last_rows[1]; break;    // builds of the neighbour rows so far
-    case 13: *value = c->last_rows[2]; break;    // entries per slice of a neighbour row (one wave walks a slice)
-    case 11: *value = c->last_pack[0]; break;    // forest packing: how far the assumed store capacity is tightened (0 = not)
-    case 12: *value = c->last_pack[1]; break;    // ... evaluations since the packing in use was planned
-    case 14: *value = c->last_pack[3]; break;    // ... packings planned so far
-    case 16: *value = c->version == 1 ? (c->five_active ? 5 : 6) : (c->five_active ? 2 : 3); break;  // launches of an evaluation as the context runs now (no k_prep launch in the five-launch mode; see agbnp_hip.h)
+    case AGBNP_HIP_SCALAR_E_VOL1: *value = c->last_components[0]; break;
+    case AGBNP_HIP_SCALAR_E_VOL2: *value = c->last_components[1]; break;
+    case AGBNP_HIP_SCALAR_E_ATOM: *value = c->last_components[2]; break;
+    case AGBNP_HIP_SCALAR_E_GB_PAIR: *value = c->last_components[3]; break;
+    case AGBNP_HIP_SCALAR_MAX_SUBTREE_NODES: *value = s[kStatMaxNodes]; break;
+    case AGBNP_HIP_SCALAR_TOTAL_NODES: *value = s[kStatTotalNodes]; break;
+    case AGBNP_HIP_SCALAR_VARIANT: *value = c->variant; break;
+    case AGBNP_HIP_SCALAR_MAX_LOCAL_ATOMS: *value = s[kStatMaxAtoms]; break;
+    case AGBNP_HIP_SCALAR_FORESTS: *value = s[kStatForests]; break;
+    case AGBNP_HIP_SCALAR_ROWS_ON: *value = c->P.rows_on; break;
+    case AGBNP_HIP_SCALAR_ROW_BUILDS: *value = c->last_rows[kNlBuilds]; break;
+    case AGBNP_HIP_SCALAR_PACK_LEVEL: *value = c->last_pack[kPsLevel]; break;
+    case AGBNP_HIP_SCALAR_PACK_AGE: *value = c->last_pack[kPsAge]; break;
+    case AGBNP_HIP_SCALAR_ROW_SLICE: *value = c->last_rows[kNlSlice]; break;
+    case AGBNP_HIP_SCALAR_PACK_PLANS: *value = c->last_pack[kPsPlans]; break;
+    case AGBNP_HIP_SCALAR_LAUNCHES: *value = c->version == 1 ? (c->five_active ? 5 : 6) : (c->five_active ? 2 : 3); break;  // (no k_prep launch in the five-launch mode)
     default: return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "unknown scalar id");
   }
   return AGBNP_HIP_OK;
@@ -2021,21 +1984,21 @@ int agbnp_hip_get_vector(agbnp_hip_context* c, int which, double* out) {
     return AGBNP_HIP_OK;
   };
   switch (which) {
-    case 0: return heavy_to_atoms(c->hrow(kHvSvVdw), 1, 0, 0.0);
-    case 1:
+    case AGBNP_HIP_VECTOR_SELFVOL_VDW: return heavy_to_atoms(c->hrow(kHvSvVdw), 1, 0, 0.0);
+    case AGBNP_HIP_VECTOR_BORN:
       if (c->version != 1) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "Born radii exist for version 1 only");
       HIP_TRY(c, hipMemcpy(out, c->d_born.p, sizeof(double) * n, hipMemcpyDeviceToHost));
       return AGBNP_HIP_OK;
-    case 2: return heavy_to_atoms(c->hrow(kHvSvVdw), 1, 0, 1.0);
-    case 3:
+    case AGBNP_HIP_VECTOR_SCALE: return heavy_to_atoms(c->hrow(kHvSvVdw), 1, 0, 1.0);
+    case AGBNP_HIP_VECTOR_SELFVOL_LARGE:
       if (!c->diagnostics) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "enlarged-radius self volumes need agbnp_hip_set_diagnostics(ctx, 1) before the evaluation");
       return heavy_to_atoms(c->hrow(kHvSvLarge), 1, 0, 0.0);
-    case 4:
-    case 5: {  // overlap-tree shape: nodes / local atoms of the subtree rooted at every heavy atom (0 for hydrogens)
+    case AGBNP_HIP_VECTOR_SUBTREE_NODES:
+    case AGBNP_HIP_VECTOR_SUBTREE_ATOMS: {  // overlap-tree shape: nodes / local atoms of the subtree rooted at every heavy atom (0 for hydrogens)
       std::vector<int2> sz(std::max(nh, 1));
       HIP_TRY(c, hipMemcpy(sz.data(), c->d_sizes.p + (size_t)(c->five_active ? c->parity : 0) * std::max(nh, 1), sizeof(int2) * std::max(nh, 1), hipMemcpyDeviceToHost));
       for (int i = 0; i < n; i++) out[i] = 0.0;
-      for (int h = 0; h < nh; h++) out[c->h2a[h]] = which == 4 ? sz[h].x : sz[h].y;
+      for (int h = 0; h < nh; h++) out[c->h2a[h]] = which == AGBNP_HIP_VECTOR_SUBTREE_NODES ? sz[h].x : sz[h].y;
       return AGBNP_HIP_OK;
     }
     default: return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "unknown vector id");
@@ -2075,7 +2038,7 @@ int agbnp_hip_set_mode(agbnp_hip_context* c, int mode) {
   wire_args(c);
   if (c->rows_capable) {  // the neighbour lists were built for the reach of the mode that is being left
     const int stale = 1;
-    HIP_TRY(c, hipMemcpy(c->d_nl_flag.p, &stale, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_nl_flag.p + kNlStale, &stale, sizeof(int), hipMemcpyHostToDevice));
   }
   return AGBNP_HIP_OK;
 }
@@ -2183,7 +2146,7 @@ int agbnp_debug_get_packing(agbnp_hip_context* c, int* order, int order_cap, int
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipDeviceSynchronize());
   int nf = 0;
-  HIP_TRY(c, hipMemcpy(&nf, c->d_forest.p + c->slot_cap + 1, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(&nf, c->d_forest.p + c->slot_cap + kPackForestsNext, sizeof(int), hipMemcpyDeviceToHost));
   nf = std::min(nf, c->slot_cap);
   *nforests = nf;
   std::vector<int> rows(c->d_rows.count);
@@ -2191,7 +2154,7 @@ int agbnp_debug_get_packing(agbnp_hip_context* c, int* order, int order_cap, int
   int run = 0;
   for (int s = 0; s < nf && s + 1 < start_cap; s++) {
     forest_start[s] = run;
-    for (int k = 0; k < rows[(size_t)kRowStride * s + kMaxItems] && run < order_cap; k++) order[run++] = rows[(size_t)kRowStride * s + k];
+    for (int k = 0; k < rows[slot_row_count(s)] && run < order_cap; k++) order[run++] = rows[slot_row_item(s, k)];
     forest_start[s + 1] = run;
   }
   if (sizes) HIP_TRY(c, hipMemcpy(sizes, c->d_sizes.p + (size_t)(c->five_active ? c->parity : 0) * std::max(c->nh, 1), sizeof(int2) * std::max(c->nh, 1), hipMemcpyDeviceToHost));
@@ -2207,21 +2170,21 @@ int agbnp_debug_set_packing(agbnp_hip_context* c, const int* order, int norder, 
     std::vector<int> rows(c->d_rows.count, -1);
     for (int s = 0; s < nforests; s++) {
       const int count = std::min(forest_start[s + 1] - forest_start[s], (int)kMaxItems);
-      rows[(size_t)kRowStride * s + kMaxItems] = count;
-      for (int k = 0; k < count && forest_start[s] + k < norder; k++) rows[(size_t)kRowStride * s + k] = order[forest_start[s] + k];
+      rows[slot_row_count(s)] = count;
+      for (int k = 0; k < count && forest_start[s] + k < norder; k++) rows[slot_row_item(s, k)] = order[forest_start[s] + k];
     }
     HIP_TRY(c, hipMemcpy(c->d_rows.p, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice));
     if (c->five) {  // (five-launch mode: the roots' atoms beside the rows)
       std::vector<int> atoms((size_t)kMaxItems * c->slot_cap, 0);
       for (int s = 0; s < nforests; s++)
         for (int k = 0; k < kMaxItems; k++) {
-          const int item = rows[(size_t)kRowStride * s + k];
+          const int item = rows[slot_row_item(s, k)];
           if (item >= 0 && work_item_root(item) < c->nh) atoms[(size_t)kMaxItems * s + k] = c->h2a[work_item_root(item)];
         }
       HIP_TRY(c, hipMemcpy(c->d_row_atoms.p, atoms.data(), sizeof(int) * atoms.size(), hipMemcpyHostToDevice));
       c->row_atoms_kind = 0;
     }
-    HIP_TRY(c, hipMemcpy(c->d_forest.p + c->slot_cap + 1, &nforests, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_forest.p + c->slot_cap + kPackForestsNext, &nforests, sizeof(int), hipMemcpyHostToDevice));
   }
   c->P.pack_enabled = freeze ? 3 : c->P.pack_enabled;  // 3: the bookkeeping keeps its statistics but writes no packing
   return AGBNP_HIP_OK;

@@ -85,18 +85,13 @@ struct PairArgs {
   int* forest_start;       // [nh+1] packing of the NEXT evaluation: slot s = order[forest_start[s] .. forest_start[s+1])
   int* nforests;           // [1] work slots of the NEXT evaluation
   const int* cur_nforests; // [1] work slots of THIS evaluation (energy partials are per slot)
-  int* pack_state;         // [9] persistent: [0] the level: how often the capacity the packing assumes has been tightened (relaxes again
-                           // after clean evaluations in a row: word [2] counts them, word [8] says how many are asked for -- the
-                           // level's memory); [1] evaluations since the packing in use was planned (huge = it is no plan: one
-                           // work item per slot); [3] packings planned so far (a diagnostic); [4], [5] total nodes / largest
-                           // subtree of the evaluation the packing was planned from (drift trigger); [6] the tree launches' copy
-                           // of the evaluation counter; [7] `heat`: leaky count of evaluations with healed forests
+  int* pack_state;         // [kPsWords] the bookkeeping's persistent words (PackStateWord, agbnp_common.h)
   int replan_every;        // a healthy packing is planned anew every so many evaluations (tuning knob, default 16), or when the trees have drifted
   int2* pack_items;        // [slots] packing_role's scratch: the work items in descending weight order {item, predicted time} (rounds rule)
   int* order;              // [kMaxItems * slots] the work items by FOREST (packing_role -> dealing_role): item k of forest f at kMaxItems * f + k
   int* forest_time;        // [slots + 1] predicted time of every forest (packing_role -> dealing_role), then: are they there
   int* rows;               // [kRowStride * slots] the work items of the NEXT evaluation in WORK-SLOT order (what the tree kernel
-                           // reads: item k of slot s at kRowStride * s + k, their number at kRowStride * s + kMaxItems).  Slot s
+                           // reads: slot_row_item / slot_row_count, agbnp_common.h).  Slot s
                            // runs on CU s mod (number of CUs), so the bookkeeping ranks the forests by predicted time and deals
                            // them over the CUs in serpentine order
   int ncus;                // CUs of the device
@@ -140,7 +135,7 @@ struct PairArgs {
   double* born_part;       // [n] sum_j s_j Q (atomic sums of the tiles)
   double *born, *born_fp, *brw, *e_atom;  // [n]
   double *gb_fx, *gb_fy, *gb_fz;          // [n] GB direct force (atomic sums of the symmetric tiles); Y goes to ys
-  const int* gb_items;     // [gb_items_count] tiles of k_gb_tiles: I | J<<12 (64-atom blocks, atom order, I <= J)
+  const int* gb_items;     // [gb_items_count] tiles of k_gb_tiles: make_tile_item (64-atom blocks, atom order, I <= J)
   int gb_items_count;
   const int* db_items;     // [db_items_count] tiles of k_born_tiles / k_dborn_tiles, same encoding over blocks of pair-order slots
   int db_items_count;
@@ -155,8 +150,7 @@ struct PairArgs {
   double nl_build2;        // squared list radius: (reach + skin)^2
   double nl_move2;         // (skin / 2)^2: an atom further than this from where it was when the rows were built makes them stale
   int row_target;          // workgroups of a row launch that the device takes two per CU of (0: the slice length stays); see rows_close_evaluation
-  int* nl_flag;            // [2]: entries per slice of a list (one wave walks a slice), tuned on the device; [0] != 0: the rows are stale for THIS evaluation (k_prep sets, the output side clears and counts the build; 1 on a fresh context)
-                           // [1] how often the rows have been built so far (diagnostic)
+  int* nl_flag;            // [kNlFlagWords] the row-flag block (RowFlagWord, agbnp_common.h)
   double* nl_ref;          // [3n] positions at the last build (NaN on a fresh context)
   const unsigned* hperm;   // [hperm_n] heavy index | screener type << 24, sorted by (type, index), padded with ~0u to whole chunks of 64
   const unsigned* aperm;   // [aperm_n] atom | screened type << 24, sorted by (type, index), same padding
@@ -172,11 +166,11 @@ struct PairArgs {
   int* nlg_count;          // [groups x kGbParts]
   int nlg_stride;
   double nlg_build2;       // squared radius of those lists
-  // Work items of the row launches: (list | slice << 24) of every slice that exists, appended when the lists are built, so
+  // Work items of the row launches: one (make_row_item, agbnp_common.h) for every slice that exists, appended when the lists are built, so
   // that the workgroups with work are the FIRST of a launch and the surplus ones leave on one scalar load (a grid laid out
   // by slice number is half empty workgroups, and those ahead of a working one delay it by microseconds).  Two buffers per
   // kind: buffer (builds & 1) is the one in use, the other one is filled by the next rebuild.
-  unsigned* nl_items;      // [3 kinds][2][nl_items_cap]
+  unsigned* nl_items;      // [3 kinds][2][nl_items_cap] (row_items_index)
   int* nl_nitems;          // [3 kinds][2]
   int nl_items_cap;
   int nlh_cap, nla_cap, nlg_cap;  // entries of a list that the launches walk (multiples of 256, <= the strides): what the reach
@@ -199,12 +193,12 @@ __device__ __forceinline__ void rebase_for_parity(PairArgs& P, int after_role) {
   const size_t toff = (size_t)par * P.table_doubles, noff = (size_t)(1 - par) * P.table_doubles;
   P.next_hv = P.hx + noff;  // (hx is row 0 of set 0's table)
   P.next_sizes = P.sizes + (size_t)(1 - par) * P.sizes_stride;
-  P.next_estatus = P.estatus + 16 * (1 - par);
+  P.next_estatus = P.estatus + kStatBlockStride * (1 - par);
   P.hx += toff, P.hy += toff, P.hz += toff;
   P.gx += toff, P.gy += toff, P.gz += toff;
   P.sv_vdw += toff, P.sv_large += toff;
   P.sizes += (size_t)par * P.sizes_stride;
-  P.estatus += 16 * par;
+  P.estatus += kStatBlockStride * par;
 }
 
 constexpr int kRowGroup = 4;    // row atoms that share a neighbour list (pair_kernels.hip, k_rows)

@@ -286,7 +286,7 @@ __device__ void energy_role(const PairArgs& P, int version, double* __restrict__
         // in k_outputs the forces -- and it is entered in the sticky log that agbnp_hip_finish reports, so that
         // queued or graph-replayed evaluations cannot lose an overflow to the next evaluation's k_prep.  This
         // role runs exactly once per evaluation, after the tree stage.
-        const int* es = P.estatus + (DEVPAR ? 16 * ((epoch_now + 1) & 1) : 0);  // (behind the GB launch: the counter has moved on)
+        const int* es = P.estatus + (DEVPAR ? kStatBlockStride * ((epoch_now + 1) & 1) : 0);  // (behind the GB launch: the counter has moved on)
         const int node = es[kStatNodeOverflow], atom = es[kStatAtomOverflow], pack = es[kStatPackOverflow];
         const int rowo = es[kStatRowOverflow];  // (final before the chain-rule launch: every row is built in the Born launch)
         const int order = es[kStatOrderStale];
@@ -384,9 +384,9 @@ __device__ void packing_role(const PairArgs& P, char* scratch, int scratch_bytes
   // every control word is asked for here, together, underneath the shapes (one cold round trip for all of them)
   const int st_node = P.estatus[kStatNodeOverflow], st_atom = P.estatus[kStatAtomOverflow], st_pack = P.estatus[kStatPackOverflow];
   const int st_forest = P.estatus[kStatForestOverflow], st_spare = P.estatus[kStatSpareForests];
-  const int ps_level = P.pack_state[0], age = P.pack_state[1], ps_clean = P.pack_state[2];
-  const int tot_planned = P.pack_state[4], max_planned = P.pack_state[5];
-  const int ps_heat = P.pack_state[7], ps_need = P.pack_state[8];
+  const int ps_level = P.pack_state[kPsLevel], age = P.pack_state[kPsAge], ps_clean = P.pack_state[kPsClean];
+  const int tot_planned = P.pack_state[kPsTotalNodes], max_planned = P.pack_state[kPsMaxNodes];
+  const int ps_heat = P.pack_state[kPsHeat], ps_need = P.pack_state[kPsNeed];
   const bool overflow = (st_node | st_atom | st_pack) != 0;
   // level: how often the assumed capacity has been tightened by 15 %.  Round 6: a forest that outgrows its store is HEALED
   // inside k_tree_cavity (built again in smaller sets; kStatSpareForests counts them) and costs that one evaluation a few tens
@@ -499,14 +499,14 @@ __device__ void packing_role(const PairArgs& P, char* scratch, int scratch_bytes
     P.estatus[kStatTotalNodes] = tot_now;
     P.estatus[kStatMaxNodes] = max_now;
     P.estatus[kStatMaxAtoms] = max(max(imax[4], imax[5]), max(imax[6], imax[7]));
-    P.pack_state[0] = level;
+    P.pack_state[kPsLevel] = level;
     // (after an overflow the fallback written below is no plan: the next clean evaluation plans anew)
-    if (P.pack_enabled != 3) P.pack_state[1] = plan ? (overflow ? P.replan_every : 0) : age + 1;
-    P.pack_state[2] = (tighten || relax || st_spare != 0 || overflow) ? 0 : min(ps_clean + 1, 1 << 20);  // clean evaluations in a row
-    P.pack_state[7] = heat;
-    P.pack_state[8] = need_next;
-    if (plan) P.pack_state[3] += 1;  // (plans so far: a diagnostic)
-    if (plan && !overflow) P.pack_state[4] = tot_now, P.pack_state[5] = max_now;  // (the shapes this plan is made for)
+    if (P.pack_enabled != 3) P.pack_state[kPsAge] = plan ? (overflow ? P.replan_every : 0) : age + 1;
+    P.pack_state[kPsClean] = (tighten || relax || st_spare != 0 || overflow) ? 0 : min(ps_clean + 1, 1 << 20);  // clean evaluations in a row
+    P.pack_state[kPsHeat] = heat;
+    P.pack_state[kPsNeed] = need_next;
+    if (plan) P.pack_state[kPsPlans] += 1;  // (plans so far: a diagnostic)
+    if (plan && !overflow) P.pack_state[kPsTotalNodes] = tot_now, P.pack_state[kPsMaxNodes] = max_now;  // (the shapes this plan is made for)
     if (!plan) {
       P.estatus[kStatForests] = P.nforests[0];       // (the packing stays)
       P.forest_time[P.tree_slot_cap] = 2;           // tells dealing_role that there is nothing to deal
@@ -671,7 +671,7 @@ __device__ void packing_role(const PairArgs& P, char* scratch, int scratch_bytes
         for (int part = 0; part < parts[c]; part++) {
           int place;
           const int forest = class_place((int)(v[c] >> 32) + part, &place);  // position in descending weight order -> forest
-          P.order[kMaxItems * forest + place] = h | (part << 24) | ((parts[c] - 1) << 26);
+          P.order[kMaxItems * forest + place] = make_work_item(h, part, parts[c]);
           if (rank_by_time) atomicAdd(&lds_time[forest], tm);
         }
       }
@@ -692,7 +692,7 @@ __device__ void packing_role(const PairArgs& P, char* scratch, int scratch_bytes
     const int tm = item_time(sz, parts);
     for (int part = 0; part < parts; part++) {
       ws[first + part] = (unsigned short)w;
-      P.pack_items[first + part] = make_int2(h | (part << 24) | ((parts - 1) << 26), tm);
+      P.pack_items[first + part] = make_int2(make_work_item(h, part, parts), tm);
     }
   }
   __syncthreads();  // (also makes the global stores of this workgroup visible to its own later loads)
@@ -825,7 +825,7 @@ __device__ void dealing_role(const PairArgs& P, char* scratch, int scratch_bytes
     const int m = se.y - se.x;  // -1 behind the forest's own items (the working copy may hold older ones)
     lo.x = 0 < m ? lo.x : -1, lo.y = 1 < m ? lo.y : -1, lo.z = 2 < m ? lo.z : -1, lo.w = 3 < m ? lo.w : -1;
     hi.x = 4 < m ? hi.x : -1, hi.y = 5 < m ? hi.y : -1, hi.z = 6 < m ? hi.z : -1, hi.w = 7 < m ? hi.w : -1;
-    int4* dst = reinterpret_cast<int4*>(P.rows + (size_t)kRowStride * slot);
+    int4* dst = reinterpret_cast<int4*>(P.rows + slot_row_item(slot, 0));
     dst[0] = lo, dst[1] = hi;
     dst[2] = make_int4(m, 0, 0, 0);
     if (P.row_atoms) {  // five-launch mode: the atoms of the items' roots (the tree reads the caller's positions itself)
@@ -836,7 +836,7 @@ __device__ void dealing_role(const PairArgs& P, char* scratch, int scratch_bytes
       // entry point; the host rewrites the words when it does not, engine.hip sync_row_atoms)
       const int* __restrict__ where = P.in.posq ? P.in.hslot : P.h2a;
 #pragma unroll
-      for (int k = 0; k < kMaxItems; k++) at[k] = it[k] >= 0 ? where[it[k] & 0xffffff] : 0;
+      for (int k = 0; k < kMaxItems; k++) at[k] = it[k] >= 0 ? where[work_item_root(it[k])] : 0;
       a0 = make_int4(at[0], at[1], at[2], at[3]), a1 = make_int4(at[4], at[5], at[6], at[7]);
       int4* da = reinterpret_cast<int4*>(P.row_atoms + (size_t)kMaxItems * slot);
       da[0] = a0, da[1] = a1;
@@ -919,7 +919,6 @@ __device__ __forceinline__ double tile_sums_fold(const TileSums& T, int row, int
 struct StripSums {
   double red[4][12][64];  // per wave: rows 0-3 block I0 {fx, fy, fz, Y}, 4-7 block I0 + 1, 8-11 block J
 };
-constexpr int kGbStripFlag = 1 << 24;  // work item = I0 | J << 12 | flag
 
 // Squared gap between the bounding box of block J and the nearer of the boxes of blocks I0, I0 + 1 (atom-order boxes of k_prep)
 __device__ __forceinline__ double strip_gap2(const PairArgs& P, int I0, int J) {
@@ -971,7 +970,7 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
     }
   }
   const double far_gap2 = kFar ? strip_gap2(P, I0, J) : 0.0;  // (scalar loads, underneath the records)
-  PAIR_STAMP_WHERE(1, I0 | (J << 12) | kGbStripFlag);
+  PAIR_STAMP_WHERE(1, make_tile_item(I0, J, kTileStripFlag));
   // the Y sums leave by pair-order slot (the chain-rule stage reads them so): the wave that will add them asks for
   // the slots of its three blocks now
   // (unconditional loads: a choice here would have to wait for them)
@@ -1303,9 +1302,9 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
   // walking gets its loads out at once instead of when the SIMD has nothing else to do (when it is too late to hide them).
   __builtin_amdgcn_s_setprio(3);
   const int item = items[AGBNP_WG - 1];
-  const int I = item & 0xfff, J = (item >> 12) & 0xfff;
+  const int I = tile_I(item), J = tile_J(item);
   PAIR_STAMP(1, 0);
-  if (item & kGbStripFlag) {
+  if (item & kTileStripFlag) {
     if (kSingle) return gb_strip_f32<kCut>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (AGBNP_WG - 1), P, s_area, s_e);
     return gb_strip<kCut, kFar, kEnergy>(n, I, J, aposq, born_part, inv_rvdw, gb_rows, egb_part + (AGBNP_WG - 1), P, s_area, s_e, s_bmax);
   }
@@ -1491,7 +1490,7 @@ __global__ __launch_bounds__(256) void k_born_tiles(int nh, int nhb, int ntj, in
   PAIR_STAMP(0, 0);
   const int item = items[blockIdx.x];
   PAIR_STAMP_WAIT(0, 7, "lgkmcnt(0)");  // kernel arguments and the item are here
-  const int I = item & 0xfff, J = (item >> 12) & 0xfff;
+  const int I = tile_I(item), J = tile_J(item);
   const bool diag = I == J;
   const bool both = J < nhb;  // heavy x heavy
   // Everything the tile reads from memory is asked for here, before anything is waited for, so the workgroup's start
@@ -1643,7 +1642,7 @@ __global__ __launch_bounds__(256) void k_dborn_tiles(int n, int nhb, int ntj, in
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   PAIR_STAMP(2, 0);
   const int item = items[blockIdx.x - 2];
-  const int I = item & 0xfff, J = (item >> 12) & 0xfff;
+  const int I = tile_I(item), J = tile_J(item);
   const bool diag = I == J;
   const bool both = J < nhb;  // heavy x heavy
   // Everything the tile reads from memory is asked for here, before anything is waited for (see k_born_tiles): the

@@ -114,8 +114,8 @@ __device__ __forceinline__ void prep_atoms(const PairArgs& P, int i, bool first_
       const double rx = r.x - P.nl_ref[3 * i], ry = r.y - P.nl_ref[3 * i + 1], rz = r.z - P.nl_ref[3 * i + 2];
       moved = !(fma(rz, rz, fma(ry, ry, rx * rx)) <= P.nl_move2);
     }
-    if (__ballot(moved) != 0ull && (threadIdx.x & 63) == 0) atomicOr(&P.nl_flag[0], 1);
-    if (i < 3) P.nl_nitems[2 * i + ((P.nl_flag[1] + 1) & 1)] = 0;  // the work-item buffers that the next rebuild fills
+    if (__ballot(moved) != 0ull && (threadIdx.x & 63) == 0) atomicOr(&P.nl_flag[kNlStale], 1);
+    if (i < kRowKinds) P.nl_nitems[kRowBuffers * i + ((P.nl_flag[kNlBuilds] + 1) & 1)] = 0;  // the work-item buffers that the next rebuild fills
   }
   if (i >= P.n) return;
   if (P.zero_out) {  // (the evaluation's own outputs are added much later: the tree launch lies in between)
@@ -177,7 +177,7 @@ __device__ __forceinline__ void prep_atoms(const PairArgs& P, int i, bool first_
     if (P.rows_on) {
       P.rec_h[h] = make_double4(x, y, z, inv_vol_i);
       P.hrec[h] = make_double4(0.0, 0.0, 0.0, 0.0);  // H arrives through the chain-rule rows' atomics
-      P.hrow[h] = make_double4(x, y, z, __hiloint2double(0, i | (screener_i << 24)));
+      P.hrow[h] = make_double4(x, y, z, __hiloint2double(0, i | (screener_i << kRowEntryTypeShift)));  // (make_row_entry, written out: agbnp_common.h)
     }
   }
 }

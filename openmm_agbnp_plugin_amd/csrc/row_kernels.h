@@ -78,7 +78,7 @@ __device__ __forceinline__ double bw_alpha(const BornRadius& r, double brw, doub
 // candidate order in turn); the sums of a wave meet in a transposing butterfly, those of the parts in LDS, and leave
 // through plain stores.  Spline entries in 32-byte power form come from the slices of the group's row types in LDS.
 //
-// Neighbour lists: entries (index | type << 24) of every candidate within reach + skin of ANY row atom of the group, in
+// Neighbour lists: entries (make_row_entry, agbnp_common.h) of every candidate within reach + skin of ANY row atom of the group, in
 // the order of a static candidate list sorted by type -- the lanes of a step then mostly read consecutive entries of one
 // table row: distinct LDS banks.  The lists are rebuilt, on the device and by the waves that own them, in the evaluation
 // whose k_prep found an atom further than skin / 2 from where it was at the last build (the lists of both kinds in the
@@ -132,7 +132,7 @@ __device__ __forceinline__ RowAtoms row_atoms(const PairArgs& P, int group) {
     A.x[r] = uniform(there ? pr[r].x : 1e30);  // a row that does not exist is out of everybody's reach
     A.y[r] = uniform(pr[r].y);
     A.z[r] = uniform(pr[r].z);
-    A.self[r] = uniform(!there ? -1 : KIND == kChainRows ? (__double2loint(pr[r].w) & 0xffffff) : self[r]);
+    A.self[r] = uniform(!there ? -1 : KIND == kChainRows ? (int)row_entry_index(__double2loint(pr[r].w)) : self[r]);
   }
   return A;
 }
@@ -144,7 +144,7 @@ __device__ __forceinline__ int row_build(const RowAtoms& A, const unsigned* __re
   int cnt = 0;
   for (int base = 64 * part; base < np; base += 64 * parts) {
     const unsigned e = perm[base + lane];
-    const double4 r = rec[e != ~0u ? (int)(e & 0xffffffu) : 0];
+    const double4 r = rec[e != ~0u ? (int)row_entry_index(e) : 0];
     double dmin = 1e300;
 #pragma unroll
     for (int q = 0; q < kRowGroup; q++) {
@@ -164,25 +164,25 @@ __device__ __forceinline__ int row_build(const RowAtoms& A, const unsigned* __re
 // than four steps whatever the length of its list (the launch lasts as long as its slowest wave); item = slice * lists +
 // list, eight consecutive items per workgroup (a workgroup's items are the same slice of eight neighbouring lists: it is
 // empty as a whole, and leaves at once, or not at all).  The sums of a wave leave as one set of FP64 atomics.
-// The slice length in use lives on the device (nl_flag[2]) and only grows.  A launch whose working workgroups are a few
+// The slice length in use lives on the device (kNlSlice of the row-flag block) and only grows.  A launch whose working workgroups are a few
 // more than two per CU is as long as the workgroups on the CUs that hold three (1dwc, 596 workgroups on 256 CUs: lifetimes
 // up to 9.5 us on the CUs with two, up to 12.9 us on those with three); longer slices for a fifth fewer workgroups take
 // that tail away.  The evaluation that has rebuilt the lists looks at the work items it laid down and, if any row launch
 // has between one and two times `row_target` workgroups, asks for one more rebuild with slices of 64 entries more.
-__device__ __forceinline__ int row_slice_length(const PairArgs& P) { return min(max(P.nl_flag[2], kRowSlice), kRowSliceMax); }
+__device__ __forceinline__ int row_slice_length(const PairArgs& P) { return min(max(P.nl_flag[kNlSlice], kRowSlice), kRowSliceMax); }
 // the last launch of an evaluation (one lane): a rebuild is counted, the lists are good from here on
 __device__ __forceinline__ void rows_close_evaluation(int* nl_flag, const int* nl_nitems, int row_target, bool gb_rows) {
-  if (!nl_flag[0]) return;
-  nl_flag[1] += 1;  // (builds so far; its parity names the work-item buffers in use)
-  nl_flag[0] = 0;
+  if (!nl_flag[kNlStale]) return;
+  nl_flag[kNlBuilds] += 1;  // (its parity names the work-item buffers in use)
+  nl_flag[kNlStale] = 0;
   if (row_target <= 0) return;
-  const int buf = nl_flag[1] & 1;
-  int items = max(nl_nitems[2 * 0 + buf], nl_nitems[2 * 1 + buf]);  // (Born rows, chain-rule rows)
+  const int buf = nl_flag[kNlBuilds] & 1;
+  int items = max(nl_nitems[row_items_index(kBornRows, buf)], nl_nitems[row_items_index(kChainRows, buf)]);
   (void)gb_rows;  // (the GB rows' workgroups are small and their launch holds fewer waves than the device: left alone)
-  const int wgs = (items + kRowWaves - 1) / kRowWaves, rs = nl_flag[2];
+  const int wgs = (items + kRowWaves - 1) / kRowWaves, rs = nl_flag[kNlSlice];
   if (wgs > row_target && wgs <= 2 * row_target && rs < kRowSliceMax) {
-    nl_flag[2] = max(rs, kRowSlice) + 64;
-    nl_flag[0] = 1;
+    nl_flag[kNlSlice] = max(rs, kRowSlice) + 64;
+    nl_flag[kNlStale] = 1;
   }
 }
 
@@ -208,10 +208,10 @@ __device__ __forceinline__ void append_items(const PairArgs& P, int sub, int ent
   const int rs = row_slice_length(P);
   const int nsl = max((entries + rs - 1) / rs, at_least_one ? 1 : 0);
   if (nsl == 0) return;
-  const int buf = (P.nl_flag[1] + 1) & 1;
-  const int base = atomicAdd(&P.nl_nitems[2 * KIND + buf], nsl);
-  unsigned* items = P.nl_items + (size_t)(2 * KIND + buf) * P.nl_items_cap;
-  for (int sl = 0; sl < nsl && base + sl < P.nl_items_cap; sl++) items[base + sl] = (unsigned)sub | ((unsigned)sl << 24);
+  const int buf = (P.nl_flag[kNlBuilds] + 1) & 1;
+  const int base = atomicAdd(&P.nl_nitems[kRowBuffers * KIND + buf], nsl);
+  unsigned* items = P.nl_items + (size_t)(kRowBuffers * KIND + buf) * P.nl_items_cap;
+  for (int sl = 0; sl < nsl && base + sl < P.nl_items_cap; sl++) items[base + sl] = make_row_item((unsigned)sub, (unsigned)sl);
 }
 
 // one wave builds list `sub` of kind KIND (the lists of the later launches are built in the Born launch: both see the same
@@ -256,20 +256,20 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
   const RowLists L = row_lists<KIND>(P);
   const int NP = L.parts, stride = L.stride;
   const int nlists = L.groups * NP, lists_pad = (nlists + WAVES - 1) / WAVES * WAVES;
-  const int stale = P.nl_flag[0];
+  const int stale = P.nl_flag[kNlStale];
   const int epoch_now = PARITY ? P.epoch[0] : 0;  // (device-side parity, pair_kernels.h: in flight with the flags; else the host has moved the pointers)
   const int rs = row_slice_length(P);
   const int walk_blocks = lists_pad / WAVES * ((L.cap + kRowSlice - 1) / kRowSlice);  // (as the host lays the grid out)
-  auto flag_row_overflow = [&]() { P.estatus[(PARITY ? 16 * (epoch_now & 1) : 0) + kStatRowOverflow] = 1; };
+  auto flag_row_overflow = [&]() { P.estatus[(PARITY ? kStatBlockStride * (epoch_now & 1) : 0) + kStatRowOverflow] = 1; };
   if (KIND == kBornRows && blk >= walk_blocks) {
     // The lists of the later launches are built here, in the Born launch, by workgroups that only look at the lists'
     // lengths in an evaluation whose lists are still good.
     const int sub = (blk - walk_blocks) * WAVES + wave;
     const int chain_lists = row_lists<kChainRows>(P).groups * kChainParts;
     if (sub < chain_lists)
-      build_list<kChainRows>(P, sub, lane, stale, P.estatus + (PARITY ? 16 * (epoch_now & 1) : 0));
+      build_list<kChainRows>(P, sub, lane, stale, P.estatus + (PARITY ? kStatBlockStride * (epoch_now & 1) : 0));
     else if (P.gb_rows)
-      build_list<kGbRows>(P, sub - chain_lists, lane, stale, P.estatus + (PARITY ? 16 * (epoch_now & 1) : 0));
+      build_list<kGbRows>(P, sub - chain_lists, lane, stale, P.estatus + (PARITY ? kStatBlockStride * (epoch_now & 1) : 0));
     return;
   }
   PAIR_STAMP((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 0);
@@ -281,8 +281,8 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
   int slice, li;
   bool active;
   if (compact) {
-    const int buf = (P.nl_flag[1] + (stale ? 1 : 0)) & 1;  // (a rebuild evaluation's later launches already walk the new lists)
-    const int nitems = min(P.nl_nitems[2 * KIND + buf], P.nl_items_cap);
+    const int buf = (P.nl_flag[kNlBuilds] + (stale ? 1 : 0)) & 1;  // (a rebuild evaluation's later launches already walk the new lists)
+    const int nitems = min(P.nl_nitems[kRowBuffers * KIND + buf], P.nl_items_cap);
     if (blk * WAVES >= nitems) {
       if (KIND == kGbRows && lane == 0 && item < P.egb_parts) P.egb_part[item] = 0.0;  // (every partial is summed up)
       return;
@@ -290,10 +290,10 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
     PAIR_STAMP_HW((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0));
     PAIR_STAMP((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 10);
     active = item < nitems;
-    const unsigned it = (P.nl_items + (size_t)(2 * KIND + buf) * P.nl_items_cap)[active ? item : 0];
+    const unsigned it = (P.nl_items + (size_t)(kRowBuffers * KIND + buf) * P.nl_items_cap)[active ? item : 0];
     PAIR_STAMP_WAIT((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 11, "vmcnt(0)");
-    li = (int)(it & 0xffffffu);
-    slice = (int)(it >> 24);
+    li = (int)row_item_list(it);
+    slice = (int)row_item_slice(it);
   } else {
     slice = item / lists_pad, li = item - slice * lists_pad;  // (a workgroup's items share the slice)
     active = li < nlists;
@@ -394,8 +394,8 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
                                                           : static_cast<const double*>(P.sv_vdw) + (PARITY ? (size_t)(epoch_now & 1) * P.table_doubles : 0);
     // two steps ahead: the list entry; one step ahead: the neighbour's record and weight.  (Every load is unconditional, its
     // index clamped into the list's stride: a load under a condition makes the compiler wait for everything in flight.)
-    double4 r1 = rec[e1 & 0xffffffu];
-    double w1 = wsrc[e1 & 0xffffffu];
+    double4 r1 = rec[row_entry_index(e1)];
+    double w1 = wsrc[row_entry_index(e1)];
     __syncthreads();  // the table is in LDS
     PAIR_STAMP((KIND == kChainRows ? 2 : 0), 8);
     PAIR_STAMP_WAIT((KIND == kChainRows ? 2 : 0), 1, "vmcnt(0)");  // the first records are here
@@ -412,11 +412,11 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
         const double4 rb = r1;
         const double wb = w1;
         e1 = e2;
-        r1 = rec[e1 & 0xffffffu];
-        w1 = wsrc[e1 & 0xffffffu];
+        r1 = rec[row_entry_index(e1)];
+        w1 = wsrc[row_entry_index(e1)];
         e2 = list[min(first + 64 * (k + 2) + lane, stride - 1)];
-        const int b = (int)(e & 0xffffffu);
-        const int tent = (int)(e >> 24) * kRowIntervals;
+        const int b = (int)row_entry_index(e);
+        const int tent = (int)row_entry_type(e) * kRowIntervals;
         const float w = (float)((KIND == kChainRows ? wb : wb * rb.w) * kPerNode);
         const float cut2 = 64 * k + lane < todo ? range2f : -1.0f;  // (a lane beyond the slice meets nobody)
         const float nx = (float)(rb.x - A.x[0]), ny = (float)(rb.y - A.y[0]), nz = (float)(rb.z - A.z[0]);
@@ -448,11 +448,11 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
       const double4 rb = r1;
       const double wb = w1;
       e1 = e2;
-      r1 = rec[e1 & 0xffffffu];
-      w1 = wsrc[e1 & 0xffffffu];
+      r1 = rec[row_entry_index(e1)];
+      w1 = wsrc[row_entry_index(e1)];
       e2 = list[min(first + 64 * (k + 2) + lane, stride - 1)];
-      const int b = (int)(e & 0xffffffu);
-      const int tent = (int)(e >> 24) * kRowIntervals;
+      const int b = (int)row_entry_index(e);
+      const int tent = (int)row_entry_type(e) * kRowIntervals;
       const double w = (KIND == kChainRows ? wb : wb * rb.w) * kPerNode;  // bw_b, or s_b = selfvol_b / V_b (times the table's d(t)/d(d))
       const double range2 = 64 * k + lane < todo ? P.range2 : -1.0;  // (a lane beyond the slice meets nobody)
 #pragma unroll
@@ -510,8 +510,8 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
       P.brw[a] = brw_a;
       hbm_add(&P.bw[a], bw_alpha(br, brw_a, qv));
     }
-    double4 r1 = rec[e1 & 0xffffffu];
-    double p1 = P.born_part[e1 & 0xffffffu], v1 = P.inv_rvdw[e1 & 0xffffffu];
+    double4 r1 = rec[row_entry_index(e1)];
+    double p1 = P.born_part[row_entry_index(e1)], v1 = P.inv_rvdw[row_entry_index(e1)];
     PAIR_STAMP(1, 8);
     PAIR_STAMP_WAIT(1, 1, "vmcnt(0)");  // the first records are here
     ROWS_LOG_COUNTS(1, todo, nsteps);
@@ -534,10 +534,10 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
         const double4 rb = r1;
         const BornRadius bb_ = born_radius(v1, p1);
         e1 = e2;
-        r1 = rec[e1 & 0xffffffu];
-        p1 = P.born_part[e1 & 0xffffffu], v1 = P.inv_rvdw[e1 & 0xffffffu];
+        r1 = rec[row_entry_index(e1)];
+        p1 = P.born_part[row_entry_index(e1)], v1 = P.inv_rvdw[row_entry_index(e1)];
         e2 = list[min(first + 64 * (k + 2) + lane, stride - 1)];
-        const int b = (int)(e & 0xffffffu);
+        const int b = (int)row_entry_index(e);
         const float cut2 = 64 * k + lane < todo ? (float)P.gb_cut2 : -1.0f;  // (a lane beyond the slice meets nobody)
         const float nx = (float)(rb.x - A.x[0]), ny = (float)(rb.y - A.y[0]), nz = (float)(rb.z - A.z[0]);
         const float qb = (float)rb.w, bj = (float)bb_.br, ibj = (float)bb_.inv_br;
@@ -569,10 +569,10 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
       const double4 rb = r1;
       const BornRadius bb_ = born_radius(v1, p1);
       e1 = e2;
-      r1 = rec[e1 & 0xffffffu];
-      p1 = P.born_part[e1 & 0xffffffu], v1 = P.inv_rvdw[e1 & 0xffffffu];
+      r1 = rec[row_entry_index(e1)];
+      p1 = P.born_part[row_entry_index(e1)], v1 = P.inv_rvdw[row_entry_index(e1)];
       e2 = list[min(first + 64 * (k + 2) + lane, stride - 1)];
-      const int b = (int)(e & 0xffffffu);
+      const int b = (int)row_entry_index(e);
       const double cut2 = 64 * k + lane < todo ? P.gb_cut2 : -1.0;  // (a lane beyond the slice meets nobody)
 #pragma unroll
       for (int r = 0; r < R; r++) {

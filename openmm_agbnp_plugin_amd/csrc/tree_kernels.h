@@ -88,10 +88,8 @@ struct TreeArgs {
   int det;                     // deterministic mode: order-dependent sums only take quantized terms (device_math.h)
   int split_fit;               // bit 0: a lone work item that outgrows the store asks for its subtree to be shared (kStatSplitWanted);
                                // bit 1: a forest that outgrows its store is healed inside the launch (cavity_forests, tree_kernels.hip)
-  const int* rows;             // [kRowStride * slots] work items: item k of work slot s at kRowStride * s + k, their number at + kMaxItems
-  const int* packing;          // [slot_cap + 1] forest_start (bookkeeping's own),
-                               // [slot_cap + 1] work slots in use (rewritten for the NEXT evaluation while this one's
-                               // pair stages run), [slot_cap + 2] the copy k_tree_cavity takes for THIS evaluation
+  const int* rows;             // [kRowStride * slots] the work slots' rows (slot_row_item / slot_row_count, agbnp_common.h)
+  const int* packing;          // the packing block (PackingWord, agbnp_common.h)
   int slot_cap;
   const unsigned long long* nbmask;  // [nhb][nhb * 64] level-2 neighbour masks from the k_prep launch (agbnp_common.h)
   int nhb;                     // blocks of 64 heavy atoms
@@ -125,8 +123,8 @@ struct TreeArgs {
 
   __device__ __forceinline__ double& hvat(int row, int h) const { return hv[(unsigned)row * hstride + (unsigned)h]; }
   __device__ __forceinline__ const int* forest_start() const { return packing; }
-  __device__ __forceinline__ const int* nforests() const { return packing + slot_cap + 1; }
-  __device__ __forceinline__ int* cur_nforests() const { return const_cast<int*>(packing) + slot_cap + 2; }
+  __device__ __forceinline__ const int* nforests() const { return packing + slot_cap + kPackForestsNext; }
+  __device__ __forceinline__ int* cur_nforests() const { return const_cast<int*>(packing) + slot_cap + kPackForestsNow; }
 };
 
 // (see rebase_for_parity, pair_kernels.h)
@@ -135,7 +133,7 @@ __device__ __forceinline__ void rebase_tree_for_parity(TreeArgs& A, int after_ro
   const int par = (A.epoch[0] + after_role) & 1;
   A.hv += (size_t)par * A.table_doubles;
   A.sizes += (size_t)par * A.sizes_stride;
-  A.status += 16 * par;
+  A.status += kStatBlockStride * par;
 }
 
 constexpr int kTreeBlock = 256;  // lanes per subtree workgroup (upper bound of the BS template parameter)
@@ -155,10 +153,7 @@ enum RootWord {
   kRtOff = 5 * kMaxRoots,    // first (root, block) pair of the root in the forest's list of neighbour-mask words
   kRtNum = 6 * kMaxRoots
 };
-// work item = heavy index | part << 24 | (parts - 1) << 26
-__host__ __device__ inline int work_item_root(int e) { return e & 0xffffff; }
-__host__ __device__ inline int work_item_part(int e) { return (e >> 24) & 3; }
-__host__ __device__ inline int work_item_parts(int e) { return ((e >> 26) & 3) + 1; }
+// (work items: make_work_item / work_item_root / _part / _parts, agbnp_common.h)
 // Which work item of a subtree shared `parts` ways expands the level-2 node of sorted rank r: the parts in serpentine order
 // (0, 1, .., p-1, p-1, .., 1, 0, 0, 1, ..).  A level-2 node pairs with its YOUNGER siblings only, so the branch under rank r
 // shrinks quickly with r; plain residue classes (r mod p) give item 0 the largest branch of every group of p, the serpentine

@@ -130,7 +130,7 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
   // the row of the workgroup's own work slot is requested before anything is waited for (AGBNP_WG < slot_cap: the
   // row exists whether or not the slot is in use)
   int first_item = -1, first_atom = 0;
-  if ((tid & 63) < kMaxRoots) first_item = A.rows[(size_t)kRowStride * AGBNP_WG + (tid & 63)];
+  if ((tid & 63) < kMaxRoots) first_item = A.rows[slot_row_item(AGBNP_WG, tid & 63)];
   if (FIVE && (tid & 63) < kMaxRoots) first_atom = A.row_atoms[(size_t)kMaxItems * AGBNP_WG + (tid & 63)];
   const int nforests = min(A.nforests()[0], A.slot_cap);  // (never above the slots the per-slot arrays hold)
   if (AGBNP_WG == 0 && tid == 0) A.cur_nforests()[0] = nforests;
@@ -155,7 +155,7 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
       int lane_q = lane;
       asm volatile("" : "+v"(lane_q));
       my_item = -1;
-      if (lane_q < kMaxRoots) my_item = A.rows[(size_t)kRowStride * slot + lane_q];
+      if (lane_q < kMaxRoots) my_item = A.rows[slot_row_item(slot, lane_q)];
       if (FIVE && lane_q < kMaxRoots) my_atom = A.row_atoms[(size_t)kMaxItems * slot + lane_q];
     }
     // HEALING (round 6).  A forest that outgrows its store -- the packing was planned from an earlier geometry's shapes -- used
@@ -212,14 +212,14 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
           int mine = -1;
           if (lane < m) {
             const int pp = S.rt[kRtPart + lane];
-            mine = S.rt[kRtHeavy + lane] | ((pp & 0xff) << 24) | (((pp >> 8) - 1) << 26);
+            mine = S.rt[kRtHeavy + lane] | ((pp & 0xff) << kWorkItemPartShift) | (((pp >> 8) - 1) << kWorkItemPartsShift);  // (make_work_item, written out: agbnp_common.h)  // (make_work_item, written out: agbnp_common.h)
           }
           if (tid < 64 && lane >= keep && lane < m) s_pend[npend + lane - keep] = mine;
           my_item = lane < keep ? mine : -1;
           if (FIVE) my_atom = my_item >= 0 ? (POSQ ? A.hslot : A.out.h2a)[work_item_root(my_item)] : 0;
         } else {
           const int root = work_item_root(items[0]), p = work_item_part(items[0]);
-          auto part_of_four = [&](int q) { return root | (q << 24) | (3 << 26); };
+          auto part_of_four = [&](int q) { return make_work_item(root, q, 4); };
           if (tid == 0) {
             if (parts0 == 1) {
               s_pend[npend] = part_of_four(1), s_pend[npend + 1] = part_of_four(2), s_pend[npend + 2] = part_of_four(3);

@@ -93,8 +93,8 @@ def test_scalars_20_and_21_are_named():
     assert P.HipCalcAGBNPForceKernel.SCALARS["last_evaluation_kind"] == 20
     assert P.HipCalcAGBNPForceKernel.SCALARS["group_block_writes"] == 21
     header = open(os.path.join(ROOT, "include", "agbnp_hip.h")).read()
-    assert re.search(r"\b20 last_evaluation_kind", header)
-    assert re.search(r"\b21 group_block_writes", header)
+    assert re.search(r"\bAGBNP_HIP_SCALAR_LAST_EVALUATION_KIND = 20,\s*/\* how the last evaluation ENQUEUED", header)
+    assert re.search(r"\bAGBNP_HIP_SCALAR_GROUP_BLOCK_WRITES = 21\s*/\* how often the context's group argument blocks", header)
 
 
 def test_the_cpp_mirror_declares_energy_group_and_expect_jump():

@@ -211,3 +211,61 @@ def test_profiles_say_what_they_were_measured_on():
     assert {"k_tree_cavity", "k_gb_tiles", "k_rows<0>", "k_rows<1>", "k_tree_pseudo"} <= kernels, kernels
     counters, source = bench.counter_valu_instructions("1dwc")
     assert counters and {"k_gb_tiles", "k_born_rows", "k_dborn_rows"} <= set(counters) and os.path.basename(d) in source
+
+
+def _header_enum(header, name):
+    body = re.search(r"enum %s \{(.*?)\};" % name, header, re.S)
+    assert body, f"include/agbnp_hip.h has no enum {name}"
+    text = re.sub(r"/\*.*?\*/", "", body.group(1), flags=re.S)
+    pairs = re.findall(r"\b(AGBNP_HIP_[A-Z0-9_]+)\s*=\s*(\d+)", text)
+    assert len(pairs) == text.count("="), f"enum {name}: an enumerator without a plain decimal value"
+    return [(k, int(v)) for k, v in pairs]
+
+
+def test_diagnostic_ids_of_the_header_are_the_python_tables():
+    """The public header names every id that agbnp_hip_get_scalar / _get_vector take; the Python tables are the same names
+    (lower case, without the prefix) with the same numbers, and the ids are 0 .. count - 1 without gaps or duplicates."""
+    header = open(os.path.join(ROOT, "include", "agbnp_hip.h")).read()
+    K = P.HipCalcAGBNPForceKernel
+    for enum, prefix, table in (("agbnp_hip_scalar", "AGBNP_HIP_SCALAR_", K.SCALARS), ("agbnp_hip_vector", "AGBNP_HIP_VECTOR_", K.VECTORS)):
+        pairs = _header_enum(header, enum)
+        assert all(k.startswith(prefix) for k, _ in pairs)
+        names = [k[len(prefix):].lower() for k, _ in pairs]
+        assert len(set(names)) == len(names), f"{enum}: a name twice"
+        assert [v for _, v in pairs] == list(range(len(pairs))), f"{enum}: not 0 .. {len(pairs) - 1} in numeric order"
+        assert dict(zip(names, (v for _, v in pairs))) == dict(table)
+    # the bits of scalar 15 as the header's prose has had them: 1, 2, 4, 8, 16, 32 / 64, and the part count from bit 8 on
+    kinds = _header_enum(header, "agbnp_hip_overflow_kind")
+    assert dict(kinds) == dict(AGBNP_HIP_OVERFLOW_NODES=1, AGBNP_HIP_OVERFLOW_ATOMS=2, AGBNP_HIP_OVERFLOW_PACKING=4, AGBNP_HIP_OVERFLOW_ROW=8,
+                               AGBNP_HIP_OVERFLOW_REORDERED=16, AGBNP_HIP_OVERFLOW_FOREST_NODES=32, AGBNP_HIP_OVERFLOW_FOREST_ATOMS=64,
+                               AGBNP_HIP_OVERFLOW_SPLIT_PARTS=256)
+    assert len(kinds) == len(dict(kinds)) and all(v & (v - 1) == 0 for _, v in kinds)
+
+
+# words that the host and the kernels share are spelled by NUMBER in one file only, csrc/agbnp_common.h (and the diagnostic ids in
+# include/agbnp_hip.h): what a literal index, offset, shift or id of one of them looks like
+_SHARED_WORD_LITERALS = [
+    r"pack_state\[\d", r"last_pack\[\d", r"nl_flag\[\d", r"last_rows\[\d", r"nl_nitems\[2 \*", r"\(2 \* KIND \+ buf\)",
+    r"slot_cap \+ \d", r"\b(d_forest\.p|forest)\b[^;\n]*\b(nslots|nhp1) \+ \d+\]?", r"\bforest\.push_back\(",
+    r"16 \* \(?(par\b|p\b|1 - p|\(epoch_now)", r"\b2 \* 16\b", r"\bfive \+ \d", r"\bfive\[\d+\]", r"sizeof\(int\) \* 32\b",
+    r"d_nl_flag\.p \+ \d", r"<< 26", r"0xfff\b", r"1 << 24", r"<< 12\b", r"kRowStride \* \(?\w+\)? \+",
+    r"\(unsigned\)[\w()]+ << 24", r"screener_i << 24", r"\bit >> 24", r"\((e|a|b) >> 24\)", r"which == \d", r"case \d+: \*value", r"case \d+: return heavy_to_atoms",
+]
+
+
+def test_shared_words_are_spelled_by_number_in_one_header_only():
+    import glob
+
+    csrc = os.path.join(ROOT, "openmm_agbnp_plugin_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(ROOT, "openmm_glue", "*")))
+    files = [f for f in files if os.path.basename(f) != "agbnp_common.h"]
+    assert len(files) >= 12
+    found = []
+    for path in files:
+        code = open(path).read()
+        code = re.sub(r"/\*.*?\*/", "", code, flags=re.S)
+        code = re.sub(r"//[^\n]*", "", code)
+        for pattern in _SHARED_WORD_LITERALS:
+            for m in re.finditer(pattern, code):
+                found.append(f"{os.path.relpath(path, ROOT)}:{code.count(chr(10), 0, m.start()) + 1}: {m.group(0)!r}")
+    assert not found, "literal spellings of shared words (use the names of csrc/agbnp_common.h):\n" + "\n".join(found)

@@ -90,4 +90,4 @@ def test_the_cpp_mirror_declares_execute_group():
 def test_scalar_19_is_named():
     assert P.HipCalcAGBNPForceKernel.SCALARS["group_members"] == 19
     header = open(os.path.join(ROOT, "include", "agbnp_hip.h")).read()
-    assert re.search(r"\b19 members of the launch set", header)
+    assert re.search(r"\bAGBNP_HIP_SCALAR_GROUP_MEMBERS = 19,\s*/\* members of the launch set", header)
