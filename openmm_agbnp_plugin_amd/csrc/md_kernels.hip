@@ -8,8 +8,9 @@
 // Every kernel advances R >= 1 replicas of ONE system in one launch; a single trajectory is a group of one.
 // State is strided ([R][n][3], [R][blocks], [R]...): replica r's buffers are fixed slices, the arguments travel as one struct by
 // value (AgbnpMdGroup).  The grid is R x blocks(n) workgroups of one thread per atom; a workgroup's replica is
-// blockIdx.x / blocks (uniform), and a replica's sums are taken in a fixed order inside its own blocks(n) workgroups, so they
-// do not depend on R.
+// blockIdx.x / blocks (uniform), and a replica's sums are taken inside its own blocks(n) workgroups, so they do not depend on
+// R: the tether partials in a fixed order, the kinetic energy per workgroup in a fixed order and across workgroups by an FP64
+// atomic in the order of arrival (bit-reproducible for n <= 256, to rounding beyond).
 //
 //   pre      Langevin (BAOAB, the reference's LangevinIntegrator(300 K, 1/ps, 1 fs), 1dwc_benchmark.py:20):
 //              v += dt/2m f;  x += dt/2 v;  v = c1 v + cn xi;  x += dt/2 v,   cn = sqrt((1 - c1^2) kT[r] / m)

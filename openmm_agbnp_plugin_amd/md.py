@@ -54,7 +54,7 @@ def _md_lib():
     if _MD_LIB is None:
         from . import _lib
         _lib.load()  # (one HIP runtime per process: the engine's loader settles which)
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libagbnp_md.so")
+        path = os.environ.get("AGBNP_HIP_MD_LIBRARY") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libagbnp_md.so")  # override: diagnostic builds only
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(path)
