@@ -12,7 +12,7 @@
 //   k_adapt_positions   posq[slot] (+ correction) -> xyz[3 * atomIndex[slot]], and the inverse map particle -> slot
 //   output side         fused into the engine's own last kernel: k_outputs adds a particle's force as fixed point at its
 //                       slot and the energy workgroup adds into the context's accumulator (PairArgs::omm,
-//                       pair_kernels.hip); an evaluation that overflowed adds nothing to the context either
+//                       pair_bodies.h); an evaluation that overflowed adds nothing to the context either
 #include <hip/hip_runtime.h>
 
 #include "adapter_kernels.h"

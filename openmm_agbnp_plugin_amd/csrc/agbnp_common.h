@@ -59,7 +59,7 @@ struct SubtreeHeader {
 // ---- Words that the host and the kernels share.  Every block of control state on the device, and every packed encoding
 // that travels between them, is defined HERE and nowhere else (tests/test_host_api.py keeps the literal spellings out of
 // the other files).  Three places in the kernels write an encoding out with the named constants below instead of calling its
-// helper (cavity_forests in tree_kernels.hip, prep_role.h, the work-item buffers of k_rows): through the helper the same
+// helper (cavity_forests in tree_bodies.h, prep_role.h, the work-item buffers of k_rows): through the helper the same
 // arithmetic reaches the optimiser in another order and the kernel leaves with another register allocation.
 
 constexpr int kMaxItems = 8;  // work items (subtrees or parts of one) per work slot = forest
@@ -79,7 +79,7 @@ AGBNP_HD constexpr int work_item_part(int e) { return (e >> kWorkItemPartShift) 
 AGBNP_HD constexpr int work_item_parts(int e) { return ((e >> kWorkItemPartsShift) & 3) + 1; }
 
 // tile item of the pair stages' tile kernels = I | J << 12 | flag over blocks of 64 (I <= J < 4096); kTileStripFlag: the
-// item is a strip of the two i blocks I, I + 1 against block J (gb_strip, pair_kernels.hip)
+// item is a strip of the two i blocks I, I + 1 against block J (gb_strip, pair_bodies.h)
 constexpr int kTileBlocksMax = 4095;
 constexpr int kTileStripFlag = 1 << 24;
 AGBNP_HD constexpr int make_tile_item(int I, int J, int flag = 0) { return I | (J << 12) | flag; }

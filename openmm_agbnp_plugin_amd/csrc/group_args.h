@@ -15,8 +15,10 @@
 #include "pair_kernels.h"
 #include "tree_kernels.h"
 
-// group_kernels.hip compiles the kernels that members share a second time, as device functions that take the workgroup's number
-// (and the grid's size) inside the member's grid: the kernels of pair_kernels.hip and tree_kernels.hip name them through these
+// The kernels that members share are written once, in pair_bodies.h and tree_bodies.h, and name themselves through these.
+// pair_kernels.hip and tree_kernels.hip read the headers as they are: the bodies are __global__ kernels.  group_kernels.hip
+// sets AGBNP_GROUP_TU before it reads them: the bodies are device functions that take the workgroup's number (and the grid's
+// size) inside the member's grid, and that unit's own kernels call them.
 #ifdef AGBNP_GROUP_TU
 #define AGBNP_KERNEL __device__ __forceinline__
 #define AGBNP_BOUNDS(...)

@@ -142,7 +142,7 @@ struct PairArgs {
   double *db_fx, *db_fy, *db_fz, *db_wu;  // [n] chain-rule force by atom, W+U by heavy index (atomic sums)
   double* egb_part;        // [egb_parts]
   int egb_parts;
-  // ---- row form of the range-limited stages (k_rows, pair_kernels.hip): one wave gathers over the neighbour row of one
+  // ---- row form of the range-limited stages (k_rows, pair_bodies.h): one wave gathers over the neighbour row of one
   //      atom -- no pair is met that is out of reach, no sum leaves through an atomic.  Reference mode only; the tile
   //      kernels stay for the fast and deterministic modes, for more radius types than the per-wave table slices hold,
   //      and as the fallback when a neighbour row outgrows its stride.
@@ -201,7 +201,7 @@ __device__ __forceinline__ void rebase_for_parity(PairArgs& P, int after_role) {
   P.estatus += kStatBlockStride * par;
 }
 
-constexpr int kRowGroup = 4;    // row atoms that share a neighbour list (pair_kernels.hip, k_rows)
+constexpr int kRowGroup = 4;    // row atoms that share a neighbour list (pair_bodies.h, k_rows)
 constexpr int kRowSlice = 256, kRowWaves = 8;  // entries of the shortest slice of a list (what the launch grids are laid out for); waves per workgroup
 // The GB rows keep no table in LDS, so their workgroups can be small: the launch (fast mode, 1dwc: 2840 one-wave items) is
 // bound by the vector-memory pipe of the fullest CU (three gathers per step), and four-wave workgroups spread the waves more

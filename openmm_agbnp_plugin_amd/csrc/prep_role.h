@@ -1,5 +1,5 @@
 // The per-atom half of the preparation of an evaluation, shared by k_prep (pair_kernels.hip) and -- in the five-launch mode,
-// the default for version 1 -- by the trailing workgroups of the cavity launch (tree_kernels.hip): the caller's positions into the
+// the default for version 1 -- by the trailing workgroups of the cavity launch (tree_bodies.h): the caller's positions into the
 // heavy-atom table and the pair stages' records, the pair stages' accumulators cleared, the evaluation counted in, the
 // neighbour rows' staleness test.
 #pragma once
@@ -11,7 +11,7 @@
 namespace agbnp {
 
 // rows of the heavy-atom table that prep_atoms clears for the next evaluation (tree_kernels.h, HeavyRow: kHvGx .. kHvSvVdw are
-// consecutive; checked by a static_assert in tree_kernels.hip)
+// consecutive; checked by a static_assert in tree_bodies.h)
 constexpr int kPrepHvSvLarge = 9, kPrepHvGx = 10;
 
 // ---- where a position comes from: the caller's [3n] array, or an OpenMM context's posq (OpenmmSource) ------------------

@@ -1,5 +1,5 @@
-// Row form of the pair stages (device code of k_rows in pair_kernels.hip; rows_close_evaluation is shared with the output
-// side of k_tree_pseudo in tree_kernels.hip).  See DESIGN.md s.4e.
+// Row form of the pair stages (device code of k_rows in pair_bodies.h; rows_close_evaluation is shared with the output
+// side of k_tree_pseudo in tree_bodies.h).  See DESIGN.md s.4e.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,7 +7,7 @@
 #include "device_math.h"
 #include "pair_kernels.h"
 
-#ifndef PAIR_STAMP  // (diagnostic stamps exist in pair_kernels.hip's -DAGBNP_PAIR_STAMPS build only)
+#ifndef PAIR_STAMP  // (diagnostic stamps exist in the -DAGBNP_PAIR_STAMPS build only: pair_bodies.h)
 #define PAIR_STAMP(kern, idx)
 #define PAIR_STAMP_WAIT(kern, idx, what)
 #define PAIR_STAMP_WHERE(kern, item)

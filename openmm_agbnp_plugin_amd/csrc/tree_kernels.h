@@ -87,7 +87,7 @@ struct TreeArgs {
   int want_sv_large;           // collect the enlarged-radius self volumes too (diagnostic: extra HBM atomics)
   int det;                     // deterministic mode: order-dependent sums only take quantized terms (device_math.h)
   int split_fit;               // bit 0: a lone work item that outgrows the store asks for its subtree to be shared (kStatSplitWanted);
-                               // bit 1: a forest that outgrows its store is healed inside the launch (cavity_forests, tree_kernels.hip)
+                               // bit 1: a forest that outgrows its store is healed inside the launch (cavity_forests, tree_bodies.h)
   const int* rows;             // [kRowStride * slots] the work slots' rows (slot_row_item / slot_row_count, agbnp_common.h)
   const int* packing;          // the packing block (PackingWord, agbnp_common.h)
   int slot_cap;

@@ -269,3 +269,19 @@ def test_shared_words_are_spelled_by_number_in_one_header_only():
             for m in re.finditer(pattern, code):
                 found.append(f"{os.path.relpath(path, ROOT)}:{code.count(chr(10), 0, m.start()) + 1}: {m.group(0)!r}")
     assert not found, "literal spellings of shared words (use the names of csrc/agbnp_common.h):\n" + "\n".join(found)
+
+
+def test_every_included_engine_header_is_a_prerequisite_of_the_library():
+    """csrc/Makefile rebuilds the library, and agbnp_hip_build_id changes, when a file of SRC or HDR changes: every header of the
+    engine's own that one of those files includes must therefore be listed in HDR."""
+    csrc = os.path.join(ROOT, "openmm_agbnp_plugin_amd", "csrc")
+    make = open(os.path.join(csrc, "Makefile")).read()
+    lists = {name: re.search(r"^%s = (.*)$" % name, make, re.M).group(1).split() for name in ("SRC", "HDR")}
+    assert len(lists["SRC"]) >= 6 and "../../include/agbnp_hip.h" in lists["HDR"]
+    listed = set(lists["HDR"])
+    missing = []
+    for name in lists["SRC"] + lists["HDR"]:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+\.h)"', open(os.path.join(csrc, name)).read(), re.M):
+            if inc not in listed:
+                missing.append(f"{name} includes {inc}")
+    assert not missing, "headers that csrc/Makefile's HDR does not list:\n" + "\n".join(missing)
