@@ -31,6 +31,16 @@
 // one thread per pair (k, k + 1), k = a mod 2, a mod 2 + 2, ...: the pairs of an attempt are disjoint, so every thread reads and
 // writes its own two replicas' words; it leaves a velocity factor per replica (1 where nothing happened), and
 // k_md_exchange_apply, a launch of its own behind it, rescales -- no workgroup of the second launch can see a half-made decision.
+//
+// Hamiltonian exchange (md.py: HamiltonianReplicaMD): slot k is rung k for the whole run -- its context (the
+// parameters may differ from rung to rung), kT[k] and seed stay -- and what moves is the conformation.  The driver has added
+// the cross energies to cross[k] = A_k(x of the partner's slot) (agbnp_hip_energy_group); k_md_hamiltonian_decide, again one
+// workgroup with one thread per pair, judges
+//   Delta = ((P_lo - T_lo) - C_lo) / kT_lo + ((P_hi - T_hi) - C_hi) / kT_hi + (1 / kT_lo - 1 / kT_hi) (T_lo - T_hi)
+// (P: last[r][0], T: the slot's tether partials summed in ascending block order, C: cross[r]; a C that is 0.0 or not finite is a
+// withheld cross evaluation, and the pair is void), leaves a partner (-1: none) and a velocity factor per slot, and
+// k_md_hamiltonian_apply, a launch of its own behind it, exchanges x[lo] and x[hi] bit for bit and the velocities rescaled to
+// the bath they arrive in.  f is left alone: the driver evaluates all slots again behind the attempt.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -67,6 +77,29 @@ struct AgbnpMdExchange {  // (md.py::_ExchangeArgs)
   long long* attempts;       // [1]
   double* scale;             // [R] velocity factors of the attempt in flight
   AgbnpMdExchangeRecord* log;
+  long long log_capacity;
+  unsigned long long seed;
+};
+
+struct AgbnpMdHamiltonianRecord {  // (md.py::HAMILTONIAN_RECORD); 104 bytes, no padding
+  long long attempt, step;      // step: steps slot lo had finished
+  int rung, walker_lo, walker_hi, accepted;  // accepted: 1, 0, or -1 for a void pair (a cross energy is missing)
+  double p_lo, p_hi, t_lo, t_hi, c_lo, c_hi, kT_lo, kT_hi, u;  // potential, tether, cross energies and baths (kJ/mol) BEFORE the decision
+};
+
+struct AgbnpMdHamiltonian {  // (md.py::_HamiltonianArgs)
+  int n, replicas;
+  double *x, *v;              // [R][n][3]
+  const double* kT;           // [R] slot k's bath: never moves
+  int *walker_at_rung, *rung_of_walker;  // [R] each
+  double* last;               // [R][2] {potential, kinetic}; the kinetic word follows an accepted conformation
+  const double* tether_part;  // [R][agbnp_md_blocks(n)] the tether partials of the evaluation last[r][0] was summed from
+  double* cross;              // [R] the words agbnp_hip_energy_group added the cross energies to; handed back as zeros
+  const long long* step;      // [R]
+  long long* attempts;        // [1]
+  int* partner;               // [R] of the attempt in flight: the slot to exchange with, -1: none
+  double* scale;              // [R] of the attempt in flight: the factor of the velocities ARRIVING at the slot
+  AgbnpMdHamiltonianRecord* log;
   long long log_capacity;
   unsigned long long seed;
 };
@@ -291,6 +324,60 @@ __global__ __launch_bounds__(kBlock) void k_md_exchange_apply(AgbnpMdExchange e,
   for (int d = 0; d < 3; d++) v[d] *= s;
 }
 
+// attempt a = attempts[0] of a Hamiltonian exchange: pairs of slots (k, k + 1), k = a mod 2, a mod 2 + 2, ...; accept iff
+// log(u) <= Delta (the header comment), u = uniform53 of Philox(counter (k, a lo, a hi, 3), key seed): word 3 keeps the stream
+// apart from the temperature exchange's.  The records of an attempt have the fixed places k_md_exchange_decide uses.
+__global__ __launch_bounds__(64) void k_md_hamiltonian_decide(AgbnpMdHamiltonian h) {
+  const int t = threadIdx.x, R = h.replicas;
+  const long long a = h.attempts[0];
+  if (t < R) h.partner[t] = -1, h.scale[t] = 1.0;
+  __syncthreads();
+  const int parity = (int)(a & 1), lo = 2 * t + parity, hi = lo + 1;
+  if (hi < R) {
+    const int blocks = (h.n + kBlock - 1) / kBlock;
+    const double kT_lo = h.kT[lo], kT_hi = h.kT[hi], p_lo = h.last[2 * lo], p_hi = h.last[2 * hi];
+    const double k_lo = h.last[2 * lo + 1], k_hi = h.last[2 * hi + 1], c_lo = h.cross[lo], c_hi = h.cross[hi];
+    double t_lo = 0.0, t_hi = 0.0;
+    for (int b = 0; b < blocks; b++) t_lo += h.tether_part[(size_t)lo * blocks + b], t_hi += h.tether_part[(size_t)hi * blocks + b];
+    h.cross[lo] = 0.0, h.cross[hi] = 0.0;
+    const int w_lo = h.walker_at_rung[lo], w_hi = h.walker_at_rung[hi];
+    const double delta = ((p_lo - t_lo) - c_lo) / kT_lo + ((p_hi - t_hi) - c_hi) / kT_hi + (1.0 / kT_lo - 1.0 / kT_hi) * (t_lo - t_hi);
+    const Philox p = philox4x32((uint32_t)lo, (uint32_t)a, (uint32_t)((unsigned long long)a >> 32), 3u, (uint32_t)h.seed, (uint32_t)(h.seed >> 32));
+    const double u = uniform53(p.c[0], p.c[1]);
+    // the engine adds nothing for a withheld evaluation: a cross word that is still zero is a missing cross energy
+    const bool is_void = c_lo == 0.0 || c_hi == 0.0 || !isfinite(c_lo) || !isfinite(c_hi);
+    const bool accepted = !is_void && log(u) <= delta;
+    if (accepted) {
+      h.partner[lo] = hi, h.partner[hi] = lo;
+      h.scale[lo] = sqrt(kT_lo / kT_hi), h.scale[hi] = sqrt(kT_hi / kT_lo);
+      h.walker_at_rung[lo] = w_hi, h.walker_at_rung[hi] = w_lo;
+      if (w_lo >= 0 && w_lo < R) h.rung_of_walker[w_lo] = hi;  // (a walker is a slot number: no word outside the map is written)
+      if (w_hi >= 0 && w_hi < R) h.rung_of_walker[w_hi] = lo;
+      h.last[2 * lo + 1] = k_hi * kT_lo / kT_hi, h.last[2 * hi + 1] = k_lo * kT_hi / kT_lo;
+    }
+    const long long at = ((a + 1) / 2) * (R / 2) + (a / 2) * ((R - 1) / 2) + t;
+    if (at < h.log_capacity)
+      h.log[at] = AgbnpMdHamiltonianRecord{a, h.step[lo], lo, w_lo, w_hi, is_void ? -1 : (accepted ? 1 : 0), p_lo, p_hi, t_lo, t_hi, c_lo, c_hi,
+                                           kT_lo, kT_hi, u};
+  }
+  __syncthreads();  // (every thread has read `a`)
+  if (t == 0) h.attempts[0] = a + 1;
+}
+
+// only the workgroups of a slot whose partner is a HIGHER slot work: thread i exchanges atom i of the two conformations
+__global__ __launch_bounds__(kBlock) void k_md_hamiltonian_apply(AgbnpMdHamiltonian h, int blocks) {
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const int q = h.partner[r];
+  if (q <= r || q >= h.replicas || i >= h.n) return;
+  const double sr = h.scale[r], sq = h.scale[q];
+  const size_t o_r = (size_t)r * 3 * h.n + 3 * i, o_q = (size_t)q * 3 * h.n + 3 * i;
+  for (int d = 0; d < 3; d++) {
+    const double xr = h.x[o_r + d], xq = h.x[o_q + d], vr = h.v[o_r + d], vq = h.v[o_q + d];
+    h.x[o_r + d] = xq, h.x[o_q + d] = xr;
+    h.v[o_r + d] = vq * sr, h.v[o_q + d] = vr * sq;
+  }
+}
+
 inline bool group_ok(const AgbnpMdGroup* g) { return g && g->n > 0 && g->replicas >= 1 && g->replicas <= kMaxReplicas; }
 
 }  // namespace
@@ -335,6 +422,16 @@ int agbnp_md_exchange(const AgbnpMdExchange* e, void* stream) {
   const int blocks = agbnp_md_blocks(e->n);
   hipLaunchKernelGGL(k_md_exchange_decide, dim3(1), dim3(64), 0, (hipStream_t)stream, *e);
   hipLaunchKernelGGL(k_md_exchange_apply, dim3(e->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *e, blocks);
+  return (int)hipGetLastError();
+}
+
+// One Hamiltonian exchange attempt between neighbouring slots: two launches (decide, exchange the conformations), no
+// synchronisation, nothing read back.  The cross energies of the attempt's pairs are in h->cross when the first one runs.
+int agbnp_md_hamiltonian_exchange(const AgbnpMdHamiltonian* h, void* stream) {
+  if (!h || h->n <= 0 || h->replicas < 1 || h->replicas > kMaxReplicas) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(h->n);
+  hipLaunchKernelGGL(k_md_hamiltonian_decide, dim3(1), dim3(64), 0, (hipStream_t)stream, *h);
+  hipLaunchKernelGGL(k_md_hamiltonian_apply, dim3(h->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *h, blocks);
   return (int)hipGetLastError();
 }
 

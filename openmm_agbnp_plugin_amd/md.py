@@ -1,6 +1,7 @@
 """Device-resident molecular dynamics around the AGBNP engine, for the py3 counterparts of the reference's example
 scripts (example/test_agbnp.py: minimise, Langevin equilibration, NVE energy-conservation run; example/1dwc_benchmark.py:
-Langevin timing run), for the energy-conservation test and for replica exchange (examples/remd_benchmark.py).
+Langevin timing run), for the energy-conservation test and for replica exchange (examples/remd_benchmark.py: temperatures,
+examples/hremd_benchmark.py: Hamiltonians).
 
 The reference gets its bonded and Coulomb/LJ terms from OpenMM's OPLS system (DesmondDMSFile.createSystem), which is
 outside this repository; here the only force-field term besides AGBNP is a harmonic tether of every atom to its start
@@ -13,7 +14,8 @@ behind it -- between the steps of a run both in ONE launch; Philox normal deviat
 `DeviceMD` is the core at R = 1 around `agbnp_hip_execute_device`, its steps captured ONCE as a HIP graph and replayed; the
 host only synchronises every `check_every` steps to read the engine's overflow log (agbnp_hip_finish).  `ReplicaMD` is the
 core around `agbnp_hip_execute_group`, eager (group calls are not captured), plus temperature exchanges decided on the
-device.  Written in torch operations a step is seventeen launches around the six of the AGBNP evaluation
+device; `HamiltonianReplicaMD` is the same with contexts that differ in their parameters and conformations that
+move between them (s.4k).  Written in torch operations a step is seventeen launches around the six of the AGBNP evaluation
 (`DeviceMD(fused=False)`, kept as the cross-check of the kernels): 0.163 -> 0.11 ms per step of 1dwc.
 
 PyTorch is plumbing here (device arrays, the graph capture API), not the product.
@@ -43,7 +45,15 @@ class _ExchangeArgs(C.Structure):  # AgbnpMdExchange
                 ("scale", C.c_void_p), ("log", C.c_void_p), ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
 
 
+class _HamiltonianArgs(C.Structure):  # AgbnpMdHamiltonian
+    _fields_ = [("n", C.c_int), ("replicas", C.c_int), ("x", C.c_void_p), ("v", C.c_void_p), ("kT", C.c_void_p),
+                ("walker_at_rung", C.c_void_p), ("rung_of_walker", C.c_void_p), ("last", C.c_void_p), ("tether_part", C.c_void_p),
+                ("cross", C.c_void_p), ("step", C.c_void_p), ("attempts", C.c_void_p), ("partner", C.c_void_p), ("scale", C.c_void_p),
+                ("log", C.c_void_p), ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
+
+
 GROUP_SYMBOLS = ("agbnp_md_group_pre", "agbnp_md_group_mid", "agbnp_md_group_post", "agbnp_md_group_tethers", "agbnp_md_exchange")
+HAMILTONIAN_SYMBOLS = ("agbnp_md_hamiltonian_exchange",)
 
 _MD_LIB = None
 
@@ -65,6 +75,7 @@ def _md_lib():
         lib.agbnp_md_group_post.argtypes = [gp, vp, vp]
         lib.agbnp_md_group_tethers.argtypes = [gp, vp, vp]
         lib.agbnp_md_exchange.argtypes = [C.POINTER(_ExchangeArgs), vp]
+        lib.agbnp_md_hamiltonian_exchange.argtypes = [C.POINTER(_HamiltonianArgs), vp]
         _MD_LIB = lib
     return _MD_LIB
 
@@ -123,6 +134,7 @@ class _Replicas:
                              p(self.seed_words), self.c1, self.dt, self.k, p(self.e_agbnp), p(self.acc), p(self.done), p(self.log_pe),
                              p(self.log_ke), p(self.counter), cap, p(self.last))
         self._parts = (p(self.parts[0]), p(self.parts[1]))
+        self.part_read = 0  # the partial buffer last[:, 0] was summed from: 0 behind forces(), (s - 1) % 2 behind steps(.., s, ..)
 
     def tethers(self, st):
         """f = -k (x - x0) of every replica, the tethers' energy as partials in parts[0]."""
@@ -136,6 +148,7 @@ class _Replicas:
         evaluate(st)
         torch.add(self.parts[0].sum(dim=1), self.e_agbnp, out=self.last[:, 0])
         self.e_agbnp.zero_()  # (a step that follows starts its own sum)
+        self.part_read = 0
 
     def steps(self, kind, steps, st, evaluate):
         """`steps` consecutive steps of all replicas: front halves, then (evaluation, back halves + next front halves in ONE
@@ -149,6 +162,7 @@ class _Replicas:
                 _check(lib.agbnp_md_group_mid(g, kind, parts[j % 2], parts[(j + 1) % 2], st))
             else:
                 _check(lib.agbnp_md_group_post(g, parts[j % 2], st))
+        self.part_read = (steps - 1) % 2
 
 
 def _settle(forces, withheld):
@@ -384,52 +398,42 @@ EXCHANGE_RECORD = np.dtype([("attempt", "<i8"), ("step", "<i8"), ("rung", "<i4")
                             ("accepted", "<i4"), ("U_lo", "<f8"), ("U_hi", "<f8"), ("kT_lo", "<f8"), ("kT_hi", "<f8"), ("u", "<f8")])
 
 
-class ReplicaMD:
-    """Temperature replica exchange of R replicas of one system: DeviceMD's integrator and force field (tethers + AGBNP) for
-    all replicas at once -- one launch of libagbnp_md.so in front of and one behind `agbnp_hip_execute_group`, six launches a
-    step for all R -- and exchange attempts between neighbouring rungs of the temperature ladder decided on the device.
+class _GroupMD:
+    """What the two exchange drivers share: the core around `agbnp_hip_execute_group` on a stream of the driver's own, eager
+    (group calls are not captured).  Slot r's buffers are fixed slices of the strided arrays, so the group call's handle and
+    pointer arrays are built once.  A driver adds its exchange: `exchange()` enqueues one attempt on `self.stream`."""
 
-    Replica r is a conformation: x[r], v[r] and kernels[r] stay together for the whole run.  An accepted exchange swaps the
-    two replicas' bath temperatures and rungs (and rescales their velocities by sqrt(T_new / T_old)); no position moves, so
-    no evaluation is withheld for it and no argument block of the group is rewritten.  Eager: group calls are not captured."""
-
-    def __init__(self, system, kernels, temperatures, seeds=None, exchange_seed=0, k_tether=2.0e4, dt=0.001, friction=1.0,
-                 device="cuda:0", log_capacity=200000):
+    def __init__(self, system, kernels, temperatures, seeds, exchange_seed, k_tether, dt, friction, device, log_capacity):
+        who = type(self).__name__
         kernels, temperatures = list(kernels), [float(t) for t in temperatures]
         R = len(kernels)
         seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
         if len(temperatures) != R or len(seeds) != R:
-            raise ValueError(f"ReplicaMD: {R} kernels, {len(temperatures)} temperatures and {len(seeds)} seeds")
+            raise ValueError(f"{who}: {R} kernels, {len(temperatures)} temperatures and {len(seeds)} seeds")
         if not 1 <= R <= MAX_REPLICAS:
-            raise ValueError(f"ReplicaMD: a group has 1 to {MAX_REPLICAS} replicas, not {R}")
+            raise ValueError(f"{who}: a group has 1 to {MAX_REPLICAS} replicas, not {R}")
         if any(int(k.numParticles) != int(system.n) for k in kernels):
-            raise ValueError(f"ReplicaMD: every kernel must hold the system's {int(system.n)} particles")
+            raise ValueError(f"{who}: every kernel must hold the system's {int(system.n)} particles")
         if len({id(k) for k in kernels}) != R:
-            raise ValueError("ReplicaMD: the same kernel was given twice (one context per replica)")
-        if any(not t > 0.0 for t in temperatures):
-            raise ValueError("ReplicaMD: temperatures must be positive")
+            raise ValueError(f"{who}: the same kernel was given twice (one context per replica)")
+        if any(not 0.0 < t < float("inf") for t in temperatures):
+            raise ValueError(f"{who}: temperatures must be positive and finite")
         import torch
         self.torch = torch
         self.core = core = _Replicas(torch, system, temperatures, seeds, k_tether, dt, friction, device, log_capacity)
         self.system, self.kernels, self.R, self.n, self.dev = system, kernels, R, core.n, core.dev
-        self.ladder = np.array(temperatures)  # the temperature of rung k; replica r starts on rung r
+        self.ladder = np.array(temperatures)  # the temperature of rung k
         self.seeds, self.exchange_seed = seeds, int(exchange_seed)
         self.dt, self.k, self.gamma, self.c1, self.log_capacity = core.dt, core.k, core.gamma, core.c1, core.log_capacity
         self.x, self.v, self.frc, self.x0, self.mass, self.kT = core.x, core.v, core.frc, core.x0, core.mass, core.kT
         self.log_pe, self.log_ke, self.counter, self.last = core.log_pe, core.log_ke, core.counter, core.last
-        self.rung_of_replica = torch.arange(R, dtype=torch.int32, device=self.dev)
-        self.replica_at_rung = torch.arange(R, dtype=torch.int32, device=self.dev)
         self.attempts = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.scale = torch.ones(R, dtype=torch.float64, device=self.dev)
         self.exchange_capacity = core.log_capacity
-        self.records = torch.zeros(self.exchange_capacity * EXCHANGE_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
-        p = lambda t: t.data_ptr()  # noqa: E731
-        self._e = _ExchangeArgs(self.n, R, p(self.v), p(self.kT), p(self.rung_of_replica), p(self.replica_at_rung), p(self.last),
-                                p(self.counter), p(self.attempts), p(self.scale), p(self.records), self.exchange_capacity,
-                                self.exchange_seed & _M64)
         # the group call's arguments never change: member r's buffers are slices of the strided arrays
         for k in kernels:
             k._need()
+        p = lambda t: t.data_ptr()  # noqa: E731
         vpR = C.c_void_p * R
         self._handles = vpR(*[k._h for k in kernels])
         self._pos = vpR(*[p(self.x[r]) for r in range(R)])
@@ -447,12 +451,12 @@ class ReplicaMD:
             raise RuntimeError("agbnp_hip_execute_group: " + _lib.last_error(self.kernels[0]._h))
 
     def finish(self):
-        """Every member's finish() on the driver's stream: withheld evaluations per replica since the last call."""
+        """Every member's finish() on the driver's stream: withheld evaluations per member since the last call."""
         st = self.stream.cuda_stream
         return np.array([k.finish(st) for k in self.kernels], dtype=np.int64)
 
     def forces(self):
-        """Tethers + AGBNP of every replica at the current positions: frc[r], last[r, 0].  Waits for the result."""
+        """Tethers + AGBNP of every slot at the current positions: frc[r], last[r, 0].  Waits for the result."""
         torch = self.torch
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
@@ -465,15 +469,11 @@ class ReplicaMD:
         _settle(self.forces, lambda: self.finish().any())
         self.torch.cuda.synchronize()
 
-    def exchange(self):
-        """One exchange attempt between neighbouring rungs, enqueued on the driver's stream (two launches, nothing read)."""
-        _check(self.core.lib.agbnp_md_exchange(C.byref(self._e), self.stream.cuda_stream))
-
     def run(self, nsteps, kind="langevin", exchange_every=0, check_every=1000, on_report=None):
-        """`nsteps` steps of every replica (5 + 1 launches per step for all of them), an exchange attempt after every
+        """`nsteps` steps of every slot (5 + 1 launches per step for all of them), an exchange attempt after every
         `exchange_every` of them (0: none); every `check_every` steps (and at the end) synchronises and reads every member's
-        overflow log.  Returns, per replica, the number of steps whose AGBNP contribution was withheld (all zeros in a healthy
-        run; an exchange decided on such a step used a potential energy without the AGBNP term)."""
+        overflow log.  Returns, per member, the number of evaluations that were withheld (all zeros in a healthy run): a step
+        without the AGBNP term for that slot alone -- an exchange decided on such a step used a potential energy without it."""
         torch = self.torch
         code = _KINDS[kind]
         exchange_every, check_every = int(exchange_every), max(1, int(check_every))
@@ -511,6 +511,48 @@ class ReplicaMD:
             pe, ke = pe[:, -last:], ke[:, -last:]
         return pe, ke
 
+    def _records(self, dtype):
+        """One record per attempted pair, in the order of the attempts."""
+        self.stream.synchronize()
+        a, R = int(self.attempts.item()), self.R
+        count = min(((a + 1) // 2) * (R // 2) + (a // 2) * ((R - 1) // 2), self.exchange_capacity)
+        raw = self.records[:count * dtype.itemsize].cpu().numpy()
+        return raw.view(dtype).copy()
+
+    def acceptance(self):
+        """accepted / attempted per rung pair (k, k + 1), k = 0 .. R - 2 (nan where nothing was attempted)."""
+        log = self.exchange_log()
+        tried = np.bincount(log["rung"], minlength=self.R - 1)[:max(self.R - 1, 0)].astype(float)
+        took = np.bincount(log["rung"], weights=log["accepted"] == 1, minlength=self.R - 1)[:max(self.R - 1, 0)]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(tried > 0, took / tried, np.nan)
+
+
+class ReplicaMD(_GroupMD):
+    """Temperature replica exchange of R replicas of one system: DeviceMD's integrator and force field (tethers + AGBNP) for
+    all replicas at once -- one launch of libagbnp_md.so in front of and one behind `agbnp_hip_execute_group`, six launches a
+    step for all R -- and exchange attempts between neighbouring rungs of the temperature ladder decided on the device.
+
+    Replica r is a conformation: x[r], v[r] and kernels[r] stay together for the whole run.  An accepted exchange swaps the
+    two replicas' bath temperatures and rungs (and rescales their velocities by sqrt(T_new / T_old)); no position moves, so
+    no evaluation is withheld for it and no argument block of the group is rewritten.  Eager: group calls are not captured."""
+
+    def __init__(self, system, kernels, temperatures, seeds=None, exchange_seed=0, k_tether=2.0e4, dt=0.001, friction=1.0,
+                 device="cuda:0", log_capacity=200000):
+        super().__init__(system, kernels, temperatures, seeds, exchange_seed, k_tether, dt, friction, device, log_capacity)
+        torch, R = self.torch, self.R
+        self.rung_of_replica = torch.arange(R, dtype=torch.int32, device=self.dev)  # replica r starts on rung r
+        self.replica_at_rung = torch.arange(R, dtype=torch.int32, device=self.dev)
+        self.records = torch.zeros(self.exchange_capacity * EXCHANGE_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        p = lambda t: t.data_ptr()  # noqa: E731
+        self._e = _ExchangeArgs(self.n, R, p(self.v), p(self.kT), p(self.rung_of_replica), p(self.replica_at_rung), p(self.last),
+                                p(self.counter), p(self.attempts), p(self.scale), p(self.records), self.exchange_capacity,
+                                self.exchange_seed & _M64)
+
+    def exchange(self):
+        """One exchange attempt between neighbouring rungs, enqueued on the driver's stream (two launches, nothing read)."""
+        _check(self.core.lib.agbnp_md_exchange(C.byref(self._e), self.stream.cuda_stream))
+
     def temperatures(self):
         """The current bath temperature (K) of every replica."""
         self.stream.synchronize()
@@ -523,16 +565,103 @@ class ReplicaMD:
 
     def exchange_log(self):
         """One record (EXCHANGE_RECORD) per attempted pair, in the order of the attempts."""
-        self.stream.synchronize()
-        a, R = int(self.attempts.item()), self.R
-        count = min(((a + 1) // 2) * (R // 2) + (a // 2) * ((R - 1) // 2), self.exchange_capacity)
-        raw = self.records[:count * EXCHANGE_RECORD.itemsize].cpu().numpy()
-        return raw.view(EXCHANGE_RECORD).copy()
+        return self._records(EXCHANGE_RECORD)
 
-    def acceptance(self):
-        """accepted / attempted per rung pair (k, k + 1), k = 0 .. R - 2 (nan where nothing was attempted)."""
-        log = self.exchange_log()
-        tried = np.bincount(log["rung"], minlength=self.R - 1)[:max(self.R - 1, 0)].astype(float)
-        took = np.bincount(log["rung"], weights=log["accepted"], minlength=self.R - 1)[:max(self.R - 1, 0)]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(tried > 0, took / tried, np.nan)
+
+# ---- Hamiltonian replica exchange: the slots keep their contexts, the conformations move (DESIGN.md s.4k) -----------------------
+
+
+def hamiltonian_uniform(rung, attempt, exchange_seed):
+    """The deviate attempt `attempt` uses for the rung pair (rung, rung + 1): counter (k, a lo, a hi, 3), key exchange_seed --
+    word 3 keeps the stream apart from `exchange_uniform`'s."""
+    a, s = int(attempt), int(exchange_seed)
+    w = philox4x32((int(rung), a & _M32, (a >> 32) & _M32, 3), (s & _M32, (s >> 32) & _M32))
+    return uniform53(w[0], w[1])
+
+
+def hamiltonian_delta(kT_lo, kT_hi, P_lo, P_hi, T_lo, T_hi, C_lo, C_hi):
+    """Delta of an exchange of conformations between the rungs lo and hi: beta_lo [U_lo(x_lo) - U_lo(x_hi)] + beta_hi [U_hi(x_hi)
+    - U_hi(x_lo)] with U_k = tethers + A_k, from what the device holds: P the rung's total potential at its own conformation, T
+    the tethers' share of it, C the cross energy A_k(partner's conformation).  Accepted iff log(u) <= Delta.  For one
+    Hamiltonian (C_lo = P_hi - T_hi, C_hi = P_lo - T_lo) it is `exchange_delta`."""
+    return ((P_lo - T_lo) - C_lo) / kT_lo + ((P_hi - T_hi) - C_hi) / kT_hi + (1.0 / kT_lo - 1.0 / kT_hi) * (T_lo - T_hi)
+
+
+# one record of the Hamiltonian exchange log (AgbnpMdHamiltonianRecord, csrc/md_kernels.hip); everything BEFORE the decision;
+# accepted: 1, 0, or -1 for a void pair (a cross energy was withheld: nothing moved)
+HAMILTONIAN_RECORD = np.dtype([("attempt", "<i8"), ("step", "<i8"), ("rung", "<i4"), ("walker_lo", "<i4"), ("walker_hi", "<i4"),
+                               ("accepted", "<i4"), ("P_lo", "<f8"), ("P_hi", "<f8"), ("T_lo", "<f8"), ("T_hi", "<f8"), ("C_lo", "<f8"),
+                               ("C_hi", "<f8"), ("kT_lo", "<f8"), ("kT_hi", "<f8"), ("u", "<f8")])
+
+
+class HamiltonianReplicaMD(_GroupMD):
+    """Hamiltonian replica exchange of R rungs of one system: ReplicaMD's integrator and launches (5 + 1 per step for all R)
+    with the roles reversed.  Slot k is rung k for the whole run: kernels[k] (contexts of one system whose gamma, vdw_alpha and
+    charge may differ), kT[k], seeds[k], the buffers x[k], v[k], frc[k] and the logs of slot k never move, so log_pe / log_ke are
+    per rung.  What moves is the conformation: an accepted exchange swaps the contents of x[lo] and x[hi], and of v[lo] and
+    v[hi], each rescaled to its new bath; walker_at_rung / rung_of_walker (device, int32) follow them, walker w starting on rung
+    w.  An attempt costs a round of cross energies (agbnp_hip_energy_group with the pairs' position pointers permuted, hinted
+    with expect_jump), two launches of libagbnp_md.so and a full evaluation of all R behind them; run() counts the withheld
+    cross-round and refresh evaluations in their member's sum."""
+
+    def __init__(self, system, kernels, temperatures, seeds=None, exchange_seed=0, k_tether=2.0e4, dt=0.001, friction=1.0,
+                 device="cuda:0", log_capacity=200000):
+        super().__init__(system, kernels, temperatures, seeds, exchange_seed, k_tether, dt, friction, device, log_capacity)
+        torch, R, core, kernels = self.torch, self.R, self.core, self.kernels
+        self.walker_at_rung = torch.arange(R, dtype=torch.int32, device=self.dev)
+        self.rung_of_walker = torch.arange(R, dtype=torch.int32, device=self.dev)
+        self.partner = torch.full((R,), -1, dtype=torch.int32, device=self.dev)
+        self.cross = torch.zeros(R, dtype=torch.float64, device=self.dev)  # the kernel hands every word it read back as zero
+        self.records = torch.zeros(self.exchange_capacity * HAMILTONIAN_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        p = lambda t: t.data_ptr()  # noqa: E731
+        # one argument struct per tether-partial buffer, each filled once: the decision reads the one the last back half read
+        self._h = tuple(_HamiltonianArgs(self.n, R, p(self.x), p(self.v), p(self.kT), p(self.walker_at_rung), p(self.rung_of_walker),
+                                         p(self.last), p(part), p(self.cross), p(self.counter), p(self.attempts), p(self.partner),
+                                         p(self.scale), p(self.records), self.exchange_capacity, self.exchange_seed & _M64)
+                        for part in core.parts)
+        # the cross round of the two attempt parities: the members of the pairs (k, k + 1), k = parity, parity + 2, ..., each at
+        # the position buffer of its partner's slot, its energy added to cross[k]
+        self._cross_round = []
+        for parity in (0, 1):
+            members = [r for k in range(parity, R - 1, 2) for r in (k, k + 1)]
+            partners = [r + 1 if (r - parity) % 2 == 0 else r - 1 for r in members]
+            vpM = C.c_void_p * max(len(members), 1)
+            self._cross_round.append((members, vpM(*[kernels[r]._h for r in members]), vpM(*[p(self.x[q]) for q in partners]),
+                                      vpM(*[p(self.cross[r:r + 1]) for r in members])))
+        self._attempt = 0  # attempts enqueued: the device's counter without reading it
+
+    def exchange(self):
+        """One exchange attempt between neighbouring rungs, enqueued on the driver's stream; nothing is read and nothing waited
+        for.  Cross round (hints, one energy-only group call over the members of the attempt's pairs with the position pointers
+        permuted), decision and exchange of the conformations (two launches), refresh (hints again -- the masks sit at the
+        partner's conformation after a rejection and the host does not know the verdict -- then tethers and one full group
+        evaluation of all R: frc[k] and last[k, 0] are rung k's at what it now holds).  An attempt without a pair only counts."""
+        from . import _lib
+        torch = self.torch
+        st = self.stream.cuda_stream
+        members, handles, pos, ene = self._cross_round[self._attempt & 1]
+        self._attempt += 1
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            if not members:
+                self.attempts.add_(1)
+                return
+            for r in members:
+                self.kernels[r].expect_jump()
+            rc = _lib.load().agbnp_hip_energy_group(handles, len(members), pos, ene, C.c_void_p(st))
+            if rc != _lib.OK:
+                raise RuntimeError("agbnp_hip_energy_group: " + _lib.last_error(self.kernels[members[0]]._h))
+            _check(self.core.lib.agbnp_md_hamiltonian_exchange(C.byref(self._h[self.core.part_read]), st))
+            for r in members:
+                self.kernels[r].expect_jump()
+            self.core.forces(torch, st, self._evaluate)
+
+    def walkers(self):
+        """walker_at_rung: the walker (the conformation that started on that rung) every rung now holds."""
+        self.stream.synchronize()
+        return self.walker_at_rung.cpu().numpy()
+
+    def exchange_log(self):
+        """One record (HAMILTONIAN_RECORD) per attempted pair, in the order of the attempts; accepted = -1 marks a void pair,
+        which acceptance() counts as attempted."""
+        return self._records(HAMILTONIAN_RECORD)
