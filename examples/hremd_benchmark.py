@@ -7,7 +7,9 @@ the decision and the exchange of the conformations on the device (openmm_agbnp_p
 Prints every rung's potential energy and the walker it holds at every report, the elapsed time / aggregate ns/day and the
 acceptance per rung pair at the end.
 
-  python examples/hremd_benchmark.py [system=trpcage] [replicas=4] [steps=10000] [exchange_every=100]
+  python examples/hremd_benchmark.py [system=trpcage] [replicas=4] [steps=10000] [exchange_every=100] [minimise=0]
+
+A non-zero `minimise` relaxes every rung with FIRE (md.minimise()) before the first step.
 """
 import os
 import sys
@@ -28,6 +30,7 @@ def main():
     replicas = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     nsteps = int(sys.argv[3]) if len(sys.argv) > 3 else 10000
     exchange_every = int(sys.argv[4]) if len(sys.argv) > 4 else 100
+    minimise = bool(int(sys.argv[5])) if len(sys.argv) > 5 else False
     system = P.load_dms(name) if name.endswith(".dms") else P.load_system(name)
 
     kernels = []
@@ -46,6 +49,10 @@ def main():
     md.settle()
     md.forces()
     md.finish()
+    if minimise:
+        for r, rec in enumerate(md.minimise()):
+            print(f"rung {r}: minimised in {int(rec['iterations'])} iterations{'' if rec['converged'] else ' (not converged)'}: "
+                  f"{rec['energy']:.4f} kJ/mol, largest force {rec['fmax']:.2f} kJ/mol/nm")
     print(f"{system.name}: {system.n} atoms x {replicas} rungs, AGBNP1 + tethers, Langevin 300 K, 1 fs, charges x 1-{1.0 - CHARGE_STEP * (replicas - 1):.2f}, "
           f"exchange every {exchange_every} steps, engine on {torch.cuda.get_device_name(0)}")
     print('#"Step",' + ",".join(f'"Potential Energy {k} (kJ/mole)","Walker {k}"' for k in range(replicas)))

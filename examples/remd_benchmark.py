@@ -6,7 +6,9 @@ attempt between neighbouring rungs every `exchange_every` steps, decided on the 
 ReplicaMD).  Prints every replica's potential energy and rung at every report, the elapsed time / aggregate ns/day and
 the acceptance per rung pair at the end.
 
-  python examples/remd_benchmark.py [system=trpcage] [replicas=8] [steps=10000] [exchange_every=100]
+  python examples/remd_benchmark.py [system=trpcage] [replicas=8] [steps=10000] [exchange_every=100] [minimise=0]
+
+A non-zero `minimise` relaxes every replica with FIRE (md.minimise()) before the first step.
 """
 import os
 import sys
@@ -27,6 +29,7 @@ def main():
     replicas = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     nsteps = int(sys.argv[3]) if len(sys.argv) > 3 else 10000
     exchange_every = int(sys.argv[4]) if len(sys.argv) > 4 else 100
+    minimise = bool(int(sys.argv[5])) if len(sys.argv) > 5 else False
     system = P.load_dms(name) if name.endswith(".dms") else P.load_system(name)
 
     kernels = []
@@ -46,6 +49,10 @@ def main():
     md.settle()
     md.forces()
     md.finish()
+    if minimise:
+        for r, rec in enumerate(md.minimise()):
+            print(f"replica {r}: minimised in {int(rec['iterations'])} iterations{'' if rec['converged'] else ' (not converged)'}: "
+                  f"{rec['energy']:.4f} kJ/mol, largest force {rec['fmax']:.2f} kJ/mol/nm")
     print(f"{system.name}: {system.n} atoms x {replicas} replicas, AGBNP1 + tethers, Langevin {ladder[0]:.0f}-{ladder[-1]:.0f} K, 1 fs, "
           f"exchange every {exchange_every} steps, engine on {torch.cuda.get_device_name(0)}")
     print('#"Step",' + ",".join(f'"Potential Energy {r} (kJ/mole)","Rung {r}"' for r in range(replicas)))

@@ -41,6 +41,45 @@
 // withheld cross evaluation, and the pair is void), leaves a partner (-1: none) and a velocity factor per slot, and
 // k_md_hamiltonian_apply, a launch of its own behind it, exchanges x[lo] and x[hi] bit for bit and the velocities rescaled to
 // the bath they arrive in.  f is left alone: the driver evaluates all slots again behind the attempt.
+//
+// FIRE minimiser (fast inertial relaxation, Bitzek et al., PRL 97, 170201; md.py: _Replicas.minimise): two
+// launches per iteration around the driver's evaluation, the grid of the group kernels (R x blocks(n) workgroups, one thread per
+// atom), each replica with state and convergence of its own.  An iteration is  back, front, evaluation:  the back half judges the
+// evaluation in f and the energy word and leaves the coefficients of a move, the front half makes the move and the tethers, and
+// the evaluation adds to f.  The grid-wide dependency between judging and moving is the launch boundary: no workgroup waits for
+// another.  The minimiser's velocities are its own scratch w [R][n][3]; g.v, g.step, g.log_pe, g.log_ke, g.last, g.acc and
+// g.done are neither read nor written.  Every product below is a double operation in the order written; fma(a, b, c) is a * b + c
+// rounded once.
+//
+//   back     k_md_fire_back (f holds tethers + AGBNP, energy[r] what the engine added, tether_part the front half's partials)
+//     per atom i, over d = 0, 1, 2 in turn from zeros:  p = fma(F_d, w_d, p);  q = fma(F_d, F_d, q);  s = fma(w_d, w_d, s)
+//     per workgroup: the maximum of q, then block_sum of p, of q and of s (threads beyond n bring zeros); thread 0 stores
+//       part[r][b] = {sum p, sum q, sum s, max q} and counts the workgroup in at arrived[r]
+//     thread 0 of the replica's last workgroup to arrive, over b = 0 .. blocks - 1 in turn from zeros:
+//       P += part[r][b][0];  Q += part[r][b][1];  S += part[r][b][2];  M = max(M, part[r][b][3]);  T += tether_part[r][b]
+//     e = energy[r];  energy[r] = 0;  arrived[r] = 0   (in every case)
+//     1. e == 0.0, or e or Q not finite:  the evaluation was withheld (the engine adds nothing then) or is not a number, the
+//        iteration is void:  voids[r] += 1;  move = 0; nothing else changes -- for a converged replica too
+//     2. converged[r] != 0:          move = 0; nothing else changes
+//     3. otherwise  E = T + e,  fm = sqrt(M),  it = iterations[r];  if it < capacity: log_e[r][it] = E, log_fmax[r][it] = fm;
+//        fmax[r] = fm;  iterations[r] = it + 1;  then
+//        a. fm < tolerance:  converged[r] = 1;  move = 0
+//        b. P > 0:   npos[r] += 1;  a = 1 - alpha[r];  b = alpha[r] * sqrt(S / Q) (0 where Q is 0);  the move's dt = dt[r];  move = 1;
+//                    then, if npos[r] > n_min:  dt[r] = min(dt[r] * f_inc, dt_max);  alpha[r] = alpha[r] * f_alpha
+//        c. else:    npos[r] = 0;  dt[r] = dt[r] * f_dec;  alpha[r] = alpha0;  a = b = 0;  the move's dt = the new dt[r];  move = 1
+//     coef[r] = {a, b, the move's dt, move (0.0 or 1.0)}; where move = 0 only that word of coef[r] is written
+//
+//   front    k_md_fire_front
+//     where coef[r].move != 0, per atom i with h = dt / mass[i] (dt: the move's), over d:
+//       w_d = fma(b, F_d, a * w_d);  w_d = fma(h, F_d, w_d);  d_d = dt * w_d;      l = sqrt(fma(d_2, d_2, fma(d_1, d_1, d_0 * d_0)))
+//       if l > max_move:  c = max_move / l;  d_d = d_d * c;  w_d = w_d * c          then  x_d = x_d + d_d;  w and x are stored
+//     where it is 0, neither x nor w of the replica is written
+//     for every replica, k_md_group_tethers' lines on the stored positions:  f = -k (x - x0), the partials of the tethers' energy
+//     into tether_part
+//
+// A converged replica stays converged: its x and w are never written again, and the evaluations that follow repeat the one it
+// converged on (one of them withheld counts in voids[r] as any other).  A void iteration is repeated at the same positions
+// (the engine's contract for a withheld evaluation).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -102,6 +141,23 @@ struct AgbnpMdHamiltonian {  // (md.py::_HamiltonianArgs)
   AgbnpMdHamiltonianRecord* log;
   long long log_capacity;
   unsigned long long seed;
+};
+
+struct AgbnpMdFire {  // (md.py::_FireArgs); 176 bytes: every field at a multiple of 8 in this order, 4 bytes of padding behind n_min (at 152)
+  double* w;                 // [R][n][3] the minimiser's velocities (scratch; g.v is not used)
+  double *dt, *alpha;        // [R]
+  int* npos;                 // [R] consecutive iterations with F.w > 0
+  long long* iterations;     // [R] judged (not void) evaluations: the index of the next log slot
+  int *converged, *voids;    // [R]
+  double* fmax;              // [R] the largest per-atom force norm of the last judged evaluation
+  double* coef;              // [R][4] {a, b, dt, move} of the move in flight
+  double* part;              // [R][agbnp_md_blocks(n)][4] per-block {sum F.w, sum F.F, sum w.w, max |F_i|^2}
+  unsigned* arrived;         // [R] workgroups of the replica that have stored their partials
+  double *log_e, *log_fmax;  // [R][capacity], indexed by the iteration word
+  long long capacity;
+  double dt_max, f_inc, f_dec, alpha0, f_alpha;
+  int n_min;
+  double tolerance, max_move;  // kJ/mol/nm, nm
 };
 
 namespace {
@@ -284,6 +340,137 @@ __global__ __launch_bounds__(kBlock) void k_md_group_tethers(AgbnpMdGroup g, int
   if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
 }
 
+// ---- FIRE minimiser (the header comment states the order of every operation) ----
+
+__device__ __forceinline__ double block_max(double v, double* red) {
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = red[0];
+  for (int w = 1; w < kBlock / 64; w++) r = fmax(r, red[w]);
+  __syncthreads();
+  return r;
+}
+
+// what thread 0 of the replica's last workgroup to arrive does with the sums P = F.w, Q = F.F, S = w.w, M = max |F_i|^2, T = tethers
+__device__ __forceinline__ void fire_judge(const AgbnpMdGroup& g, const AgbnpMdFire& q, int r, double P, double Q, double S, double M, double T) {
+  const double e = g.energy[r];
+  g.energy[r] = 0.0;
+  q.arrived[r] = 0u;
+  double* coef = q.coef + 4 * r;
+  // the engine adds nothing for a withheld evaluation; a force that is not a number never reaches M (fmax drops it) but does reach Q
+  if (e == 0.0 || !isfinite(e) || !isfinite(Q)) {
+    q.voids[r] += 1;
+    coef[3] = 0.0;
+    return;
+  }
+  if (q.converged[r] != 0) {
+    coef[3] = 0.0;
+    return;
+  }
+  const double E = T + e, fm = sqrt(M);
+  const long long it = q.iterations[r];
+  if (it < q.capacity) q.log_e[r * q.capacity + it] = E, q.log_fmax[r * q.capacity + it] = fm;
+  q.fmax[r] = fm;
+  q.iterations[r] = it + 1;
+  if (fm < q.tolerance) {
+    q.converged[r] = 1;
+    coef[3] = 0.0;
+    return;
+  }
+  const double dt = q.dt[r], alpha = q.alpha[r];
+  if (P > 0.0) {
+    const int np = q.npos[r] + 1;
+    q.npos[r] = np;
+    coef[0] = 1.0 - alpha, coef[1] = Q > 0.0 ? alpha * sqrt(S / Q) : 0.0, coef[2] = dt, coef[3] = 1.0;
+    if (np > q.n_min) q.dt[r] = fmin(dt * q.f_inc, q.dt_max), q.alpha[r] = alpha * q.f_alpha;
+  } else {
+    const double cut = dt * q.f_dec;
+    q.npos[r] = 0, q.dt[r] = cut, q.alpha[r] = q.alpha0;
+    coef[0] = 0.0, coef[1] = 0.0, coef[2] = cut, coef[3] = 1.0;
+  }
+}
+
+// behind an evaluation: the four reductions per workgroup as partials; the replica's last workgroup to arrive judges.  The
+// partials cross workgroups inside the launch: agent-scope stores, a release in front of the count, an acquire behind it
+__global__ __launch_bounds__(kBlock) void k_md_fire_back(AgbnpMdGroup g, AgbnpMdFire q, int blocks, const double* __restrict__ tether_part) {
+  __shared__ double red[kBlock / 64];
+  __shared__ bool s_last;
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const size_t o = (size_t)r * 3 * g.n;
+  double p = 0.0, ff = 0.0, s = 0.0;
+  if (i < g.n)
+    for (int d = 0; d < 3; d++) {
+      const double fd = g.f[o + 3 * i + d], wd = q.w[o + 3 * i + d];
+      p = fma(fd, wd, p), ff = fma(fd, fd, ff), s = fma(wd, wd, s);
+    }
+  const double m = block_max(ff, red);
+  p = block_sum(p, red), ff = block_sum(ff, red), s = block_sum(s, red);
+  if (threadIdx.x == 0) {
+    double* mine = q.part + 4 * (size_t)blockIdx.x;
+    __hip_atomic_store(mine + 0, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + 1, ff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + 2, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + 3, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+    s_last = atomicAdd(&q.arrived[r], 1u) == (unsigned)blocks - 1u;
+  }
+  __syncthreads();
+  if (!s_last || threadIdx.x != 0) return;
+  __threadfence();
+  double P = 0.0, Q = 0.0, S = 0.0, M = 0.0, T = 0.0;
+  const double* all = q.part + 4 * (size_t)r * blocks;
+  for (int k = 0; k < blocks; k++) {  // ascending block order
+    P += __hip_atomic_load(all + 4 * k + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    Q += __hip_atomic_load(all + 4 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    S += __hip_atomic_load(all + 4 * k + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    M = fmax(M, __hip_atomic_load(all + 4 * k + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    T += tether_part[(size_t)r * blocks + k];
+  }
+  fire_judge(g, q, r, P, Q, S, M, T);
+}
+
+// in front of the next evaluation: the move the back half decided, then the tethers as k_md_group_tethers leaves them
+__global__ __launch_bounds__(kBlock) void k_md_fire_front(AgbnpMdGroup g, AgbnpMdFire q, int blocks, double* __restrict__ tether_part) {
+  __shared__ double red[kBlock / 64];
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const size_t o = (size_t)r * 3 * g.n;
+  const double ca = q.coef[4 * r], cb = q.coef[4 * r + 1], dt = q.coef[4 * r + 2];
+  const bool move = q.coef[4 * r + 3] != 0.0;
+  double e = 0.0;
+  if (i < g.n) {
+    double px[3];
+    for (int d = 0; d < 3; d++) px[d] = g.x[o + 3 * i + d];
+    if (move) {
+      const double h = dt / g.mass[i];
+      double w[3], dd[3];
+      for (int d = 0; d < 3; d++) {
+        const double fd = g.f[o + 3 * i + d];
+        w[d] = fma(cb, fd, ca * q.w[o + 3 * i + d]);
+        w[d] = fma(h, fd, w[d]);
+        dd[d] = dt * w[d];
+      }
+      const double len = sqrt(fma(dd[2], dd[2], fma(dd[1], dd[1], dd[0] * dd[0])));
+      if (len > q.max_move) {
+        const double c = q.max_move / len;
+        for (int d = 0; d < 3; d++) dd[d] *= c, w[d] *= c;
+      }
+      for (int d = 0; d < 3; d++) {
+        px[d] += dd[d];
+        q.w[o + 3 * i + d] = w[d];
+        g.x[o + 3 * i + d] = px[d];
+      }
+    }
+    for (int d = 0; d < 3; d++) {
+      const double dd = px[d] - g.x0[3 * i + d];
+      g.f[o + 3 * i + d] = -g.ktether * dd;
+      e = fma(0.5 * g.ktether * dd, dd, e);
+    }
+  }
+  e = block_sum(e, red);
+  if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
+}
+
 constexpr int kMaxReplicas = 16;  // AGBNP_HIP_MAX_GROUP
 
 // attempt a = attempts[0]: pairs of rungs (k, k + 1), k = a mod 2, a mod 2 + 2, ...; accept iff log(u) <= Delta,
@@ -413,6 +600,23 @@ int agbnp_md_group_tethers(const AgbnpMdGroup* g, double* tether_part, void* str
   if (!group_ok(g)) return (int)hipErrorInvalidValue;
   const int blocks = agbnp_md_blocks(g->n);
   hipLaunchKernelGGL(k_md_group_tethers, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, tether_part);
+  return (int)hipGetLastError();
+}
+
+// The two launches of a FIRE iteration (the header comment), one each for all the replicas of *g; *q is a host struct as *g is.
+// tether_part: [R][agbnp_md_blocks(n)], read by the back half, written by the front half.  Return: as the group entry points,
+// a null *q included.
+int agbnp_md_fire_back(const AgbnpMdGroup* g, const AgbnpMdFire* q, const double* tether_part, void* stream) {
+  if (!group_ok(g) || !q) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(g->n);
+  hipLaunchKernelGGL(k_md_fire_back, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, *q, blocks, tether_part);
+  return (int)hipGetLastError();
+}
+
+int agbnp_md_fire_front(const AgbnpMdGroup* g, const AgbnpMdFire* q, double* tether_part, void* stream) {
+  if (!group_ok(g) || !q) return (int)hipErrorInvalidValue;
+  const int blocks = agbnp_md_blocks(g->n);
+  hipLaunchKernelGGL(k_md_fire_front, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, *q, blocks, tether_part);
   return (int)hipGetLastError();
 }
 

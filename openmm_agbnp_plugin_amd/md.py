@@ -15,8 +15,11 @@ behind it -- between the steps of a run both in ONE launch; Philox normal deviat
 host only synchronises every `check_every` steps to read the engine's overflow log (agbnp_hip_finish).  `ReplicaMD` is the
 core around `agbnp_hip_execute_group`, eager (group calls are not captured), plus temperature exchanges decided on the
 device; `HamiltonianReplicaMD` is the same with contexts that differ in their parameters and conformations that
-move between them (s.4k).  Written in torch operations a step is seventeen launches around the six of the AGBNP evaluation
-(`DeviceMD(fused=False)`, kept as the cross-check of the kernels): 0.163 -> 0.11 ms per step of 1dwc.
+move between them (s.4k).  Every driver has `minimise()`: FIRE for all its replicas, each with state and convergence of its
+own, in two more launches of libagbnp_md.so around the same evaluation (back: judge and decide the move, front: move and
+tethers; s.4l), the host reading only every `check_every` iterations.  Written in torch operations a step is seventeen
+launches around the six of the AGBNP evaluation (`DeviceMD(fused=False)`, kept as the cross-check of the kernels): 0.163 ->
+0.11 ms per step of 1dwc.
 
 PyTorch is plumbing here (device arrays, the graph capture API), not the product.
 """
@@ -52,8 +55,26 @@ class _HamiltonianArgs(C.Structure):  # AgbnpMdHamiltonian
                 ("log", C.c_void_p), ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
 
 
+class _FireArgs(C.Structure):  # AgbnpMdFire
+    _fields_ = [("w", C.c_void_p), ("dt", C.c_void_p), ("alpha", C.c_void_p), ("npos", C.c_void_p), ("iterations", C.c_void_p),
+                ("converged", C.c_void_p), ("voids", C.c_void_p), ("fmax", C.c_void_p), ("coef", C.c_void_p), ("part", C.c_void_p),
+                ("arrived", C.c_void_p), ("log_e", C.c_void_p), ("log_fmax", C.c_void_p), ("capacity", C.c_longlong),
+                ("dt_max", C.c_double), ("f_inc", C.c_double), ("f_dec", C.c_double), ("alpha0", C.c_double), ("f_alpha", C.c_double),
+                ("n_min", C.c_int), ("tolerance", C.c_double), ("max_move", C.c_double)]
+
+
 GROUP_SYMBOLS = ("agbnp_md_group_pre", "agbnp_md_group_mid", "agbnp_md_group_post", "agbnp_md_group_tethers", "agbnp_md_exchange")
 HAMILTONIAN_SYMBOLS = ("agbnp_md_hamiltonian_exchange",)
+FIRE_SYMBOLS = ("agbnp_md_fire_back", "agbnp_md_fire_front")
+
+# FIRE's constants (Bitzek et al., PRL 97, 170201) and the bounds of the move
+FIRE_F_INC, FIRE_F_DEC, FIRE_ALPHA0, FIRE_F_ALPHA, FIRE_N_MIN = 1.1, 0.5, 0.1, 0.99, 5
+JUMP_THRESHOLD = 0.04     # nm: a heavy atom that moves further between two evaluations gets that evaluation withheld
+MAX_MOVE_LIMIT = 0.02     # nm: the largest `max_move` minimise() accepts, half the threshold
+
+# one record per replica of what minimise() returns; energy (kJ/mol) and fmax (kJ/mol/nm) are those of the final positions
+MINIMISE_RECORD = np.dtype([("iterations", "<i8"), ("converged", "<i4"), ("fmax", "<f8"), ("energy", "<f8"), ("voids", "<i4"),
+                            ("withheld", "<i8")])
 
 _MD_LIB = None
 
@@ -76,6 +97,8 @@ def _md_lib():
         lib.agbnp_md_group_tethers.argtypes = [gp, vp, vp]
         lib.agbnp_md_exchange.argtypes = [C.POINTER(_ExchangeArgs), vp]
         lib.agbnp_md_hamiltonian_exchange.argtypes = [C.POINTER(_HamiltonianArgs), vp]
+        lib.agbnp_md_fire_back.argtypes = [gp, C.POINTER(_FireArgs), vp, vp]
+        lib.agbnp_md_fire_front.argtypes = [gp, C.POINTER(_FireArgs), vp, vp]
         _MD_LIB = lib
     return _MD_LIB
 
@@ -86,6 +109,21 @@ def _check(rc):
 
 
 _KINDS = {"langevin": 0, "verlet": 1}  # the kernels' `kind`
+
+
+def _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move):
+    """minimise()'s arguments, judged before any device call."""
+    if not 0.0 < float(max_move) <= MAX_MOVE_LIMIT:
+        raise ValueError(f"minimise: max_move must be in (0, {MAX_MOVE_LIMIT}] nm, not {max_move}: the engine withholds an evaluation "
+                         f"whose heavy atoms moved more than {JUMP_THRESHOLD} nm since the last one, and a move is kept to half of that")
+    if not 0.0 < float(tolerance) < float("inf"):
+        raise ValueError(f"minimise: tolerance must be positive and finite (kJ/mol/nm), not {tolerance}")
+    if not 0.0 < float(dt0) < float("inf"):
+        raise ValueError(f"minimise: dt0 must be positive and finite (ps), not {dt0}")
+    if not float(dt0) <= float(dt_max) < float("inf"):
+        raise ValueError(f"minimise: dt0 = {dt0} ps exceeds dt_max = {dt_max} ps")
+    if int(max_iterations) < 1 or int(check_every) < 1:
+        raise ValueError(f"minimise: max_iterations and check_every must be at least 1, not {max_iterations} and {check_every}")
 
 
 class _Replicas:
@@ -135,6 +173,7 @@ class _Replicas:
                              p(self.log_ke), p(self.counter), cap, p(self.last))
         self._parts = (p(self.parts[0]), p(self.parts[1]))
         self.part_read = 0  # the partial buffer last[:, 0] was summed from: 0 behind forces(), (s - 1) % 2 behind steps(.., s, ..)
+        self.fire = None    # the minimiser's device words: allocated by the first minimise()
 
     def tethers(self, st):
         """f = -k (x - x0) of every replica, the tethers' energy as partials in parts[0]."""
@@ -163,6 +202,89 @@ class _Replicas:
             else:
                 _check(lib.agbnp_md_group_post(g, parts[j % 2], st))
         self.part_read = (steps - 1) % 2
+
+    def _fire_state(self, torch, capacity):
+        """The minimiser's device words, allocated at the first minimise() (the logs again when a later one asks for more)."""
+        R, n = self.R, self.n
+        fire = self.fire
+        if fire is None:
+            f64 = dict(dtype=torch.float64, device=self.dev)
+            i32 = dict(dtype=torch.int32, device=self.dev)
+            blocks = int(self.lib.agbnp_md_blocks(n))
+            fire = dict(w=torch.zeros((R, n, 3), **f64), dt=torch.zeros(R, **f64), alpha=torch.zeros(R, **f64), npos=torch.zeros(R, **i32),
+                        iterations=torch.zeros(R, dtype=torch.int64, device=self.dev), converged=torch.zeros(R, **i32),
+                        voids=torch.zeros(R, **i32), fmax=torch.zeros(R, **f64), coef=torch.zeros((R, 4), **f64),
+                        part=torch.zeros((R, blocks, 4), **f64), arrived=torch.zeros(R, **i32), capacity=0)
+            self.fire = fire
+        if capacity > fire["capacity"]:
+            fire["log_e"] = torch.zeros((R, capacity), dtype=torch.float64, device=self.dev)
+            fire["log_fmax"] = torch.zeros((R, capacity), dtype=torch.float64, device=self.dev)
+            fire["capacity"] = capacity
+        return fire
+
+    def minimise(self, torch, st, evaluate, finish, tolerance=10.0, max_iterations=1000, check_every=50, dt0=0.001, dt_max=0.005,
+                 max_move=0.01, on_check=None):
+        """FIRE (csrc/md_kernels.hip) from the current positions, every replica with state and convergence of
+        its own, enqueued on `st` (torch's current stream): tethers and an evaluation, then per iteration the back half (judge
+        the evaluation, decide the move), the front half (move, tethers) and `evaluate(st)`.  Every `check_every` iterations
+        `finish()` (withheld evaluations per member since its last call; it waits for the stream) and the `converged` words are
+        read -- the only host reads before the end -- and `on_check(converged)` is called; it stops when every replica has
+        converged or after `max_iterations`.  No atom moves more than `max_move` nm in an iteration.  v, counter, log_pe and
+        log_ke are not touched; frc, last[:, 0], e_agbnp and part_read are left as forces() leaves them.  Returns one
+        MINIMISE_RECORD per replica.  An evaluation the engine withheld (or one whose forces are not numbers) makes a void
+        iteration for that replica, converged or not: counted in `voids`, repeated in place; `withheld` is what the members'
+        finish() reported.  Where either is not zero the LAST evaluation may have been such a one: `energy`, `fmax`, frc and
+        last[:, 0] of that replica then lack the AGBNP term, and forces() puts them right."""
+        _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move)
+        max_iterations, check_every = int(max_iterations), int(check_every)
+        lib, g, part = self.lib, C.byref(self._g), self._parts[0]
+        fire = self._fire_state(torch, max_iterations)
+        for key in ("w", "npos", "iterations", "converged", "voids", "fmax", "coef", "arrived", "log_e", "log_fmax"):
+            fire[key].zero_()
+        fire["dt"].fill_(float(dt0))
+        fire["alpha"].fill_(FIRE_ALPHA0)
+        p = lambda key: fire[key].data_ptr()  # noqa: E731
+        q = _FireArgs(p("w"), p("dt"), p("alpha"), p("npos"), p("iterations"), p("converged"), p("voids"), p("fmax"), p("coef"), p("part"),
+                      p("arrived"), p("log_e"), p("log_fmax"), fire["capacity"], float(dt_max), FIRE_F_INC, FIRE_F_DEC, FIRE_ALPHA0,
+                      FIRE_F_ALPHA, FIRE_N_MIN, float(tolerance), float(max_move))
+        q = C.byref(q)
+        self.e_agbnp.zero_()
+        self.tethers(st)
+        evaluate(st)
+        withheld = np.zeros(self.R, dtype=np.int64)
+        done = 0
+        while done < max_iterations:
+            chunk = min(check_every, max_iterations - done)
+            for _ in range(chunk):
+                _check(lib.agbnp_md_fire_back(g, q, part, st))
+                _check(lib.agbnp_md_fire_front(g, q, part, st))
+                evaluate(st)
+            done += chunk
+            withheld += np.asarray(finish(), dtype=np.int64).reshape(-1)
+            converged = fire["converged"].cpu().numpy()
+            if on_check:
+                on_check(converged)
+            if converged.all():
+                break
+        # as forces() ends: every replica's last evaluation is at the positions it now holds (a converged one's repeats the
+        # evaluation it converged on)
+        torch.add(self.parts[0].sum(dim=1), self.e_agbnp, out=self.last[:, 0])
+        self.e_agbnp.zero_()
+        self.part_read = 0
+        out = np.zeros(self.R, dtype=MINIMISE_RECORD)
+        out["iterations"], out["converged"] = fire["iterations"].cpu().numpy(), fire["converged"].cpu().numpy()
+        out["fmax"] = self.frc.square().sum(dim=2).max(dim=1).values.sqrt().cpu().numpy()
+        out["energy"], out["voids"], out["withheld"] = self.last[:, 0].cpu().numpy(), fire["voids"].cpu().numpy(), withheld
+        return out
+
+    def minimisation_log(self):
+        """(energy[R][iterations], fmax[R][iterations]) of the last minimise(): what every judged evaluation logged, as numpy
+        arrays padded with zeros behind a replica's own count."""
+        fire = self.fire
+        if fire is None:
+            raise RuntimeError("minimisation_log: minimise() has not been called")
+        count = min(int(fire["iterations"].max().item()), fire["capacity"])
+        return fire["log_e"][:, :count].cpu().numpy(), fire["log_fmax"][:, :count].cpu().numpy()
 
 
 def _settle(forces, withheld):
@@ -277,6 +399,24 @@ class DeviceMD:
         self.x.add_(move)
         self.forces()
         self._record()
+
+    def minimise(self, tolerance=10.0, max_iterations=1000, check_every=50, dt0=0.001, dt_max=0.005, max_move=0.01, on_check=None):
+        """FIRE from the current positions until the largest per-atom force norm (tethers + AGBNP) is below `tolerance`
+        (kJ/mol/nm) or `max_iterations` have run (`_Replicas.minimise`): eager, on a stream of the driver's own, two launches of
+        libagbnp_md.so around `execute_device` per iteration, the host reading only every `check_every` iterations.  No atom
+        moves more than `max_move` nm between two evaluations, so none is withheld for a jump.  self.v and the step logs are
+        untouched, and the state is as forces() leaves it: run() may follow.  Returns one MINIMISE_RECORD (a numpy array of 1)."""
+        _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move)
+        torch = self.torch
+        if self._eager is None:
+            self._eager = torch.cuda.Stream(device=self.dev)
+        side = self._eager
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            out = self.core.minimise(torch, side.cuda_stream, self._evaluate, lambda: [self.kernel.finish(side.cuda_stream)], tolerance,
+                                     max_iterations, check_every, dt0, dt_max, max_move, on_check)
+        side.synchronize()
+        return out
 
     # ---- graph capture / replay
     def settle(self):
@@ -462,6 +602,21 @@ class _GroupMD:
         with torch.cuda.stream(self.stream):
             self.core.forces(torch, self.stream.cuda_stream, self._evaluate)
         self.stream.synchronize()
+
+    def minimise(self, tolerance=10.0, max_iterations=1000, check_every=50, dt0=0.001, dt_max=0.005, max_move=0.01, on_check=None):
+        """FIRE for every slot from the positions it holds, each under its own context's parameters and with convergence of
+        its own (`_Replicas.minimise`): eager on the driver's stream, two launches of libagbnp_md.so around
+        `agbnp_hip_execute_group` per iteration for all R, the host reading only every `check_every` iterations.  A slot that has
+        converged is not moved again while the others go on.  v, counter and the step logs are untouched, and the state is as
+        forces() leaves it: run() or exchange() may follow.  Returns one MINIMISE_RECORD per slot."""
+        _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move)
+        torch = self.torch
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            out = self.core.minimise(torch, self.stream.cuda_stream, self._evaluate, self.finish, tolerance, max_iterations, check_every,
+                                     dt0, dt_max, max_move, on_check)
+        self.stream.synchronize()
+        return out
 
     def settle(self):
         """Outside any timing: first evaluations (allocations, capacity negotiation, forest packing, the group's argument
