@@ -25,7 +25,8 @@
 // The bath temperature is a device word per replica (kT[r], kJ/mol), which an exchange swaps without the host: that is why the
 // noise amplitude is formed in the kernel.  Normal deviates: Philox4x32-10 keyed by seeds[r], counter = (atom, step number on
 // the device lo, hi, 0|1), Box-Muller in FP64 on 53-bit uniforms: the stream of a run depends on nothing but the seed (graph
-// replays included: the step number is read from device memory).
+// replays included: the step number is read from device memory).  The counter's last word names the stream (kNoiseWord0 ..
+// kHamiltonianWord below, md.py's PHILOX_* words): no two uses share one.
 //
 // Exchange (temperature replica exchange between neighbouring rungs of the ladder): k_md_exchange_decide, ONE workgroup,
 // one thread per pair (k, k + 1), k = a mod 2, a mod 2 + 2, ...: the pairs of an attempt are disjoint, so every thread reads and
@@ -74,8 +75,8 @@
 //       w_d = fma(b, F_d, a * w_d);  w_d = fma(h, F_d, w_d);  d_d = dt * w_d;      l = sqrt(fma(d_2, d_2, fma(d_1, d_1, d_0 * d_0)))
 //       if l > max_move:  c = max_move / l;  d_d = d_d * c;  w_d = w_d * c          then  x_d = x_d + d_d;  w and x are stored
 //     where it is 0, neither x nor w of the replica is written
-//     for every replica, k_md_group_tethers' lines on the stored positions:  f = -k (x - x0), the partials of the tethers' energy
-//     into tether_part
+//     for every replica, tether() per component on the stored positions as in k_md_group_tethers:  f = -k (x - x0), the
+//     partials of the tethers' energy into tether_part
 //
 // A converged replica stays converged: its x and w are never written again, and the evaluations that follow repeat the one it
 // converged on (one of them withheld counts in voids[r] as any other).  A void iteration is repeated at the same positions
@@ -83,6 +84,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "../../include/agbnp_hip.h"
 
 struct AgbnpMdGroup {  // (mirrored field for field by md.py::_GroupArgs)
   int n, replicas;
@@ -163,6 +166,22 @@ struct AgbnpMdFire {  // (md.py::_FireArgs); 176 bytes: every field at a multipl
 namespace {
 
 constexpr int kBlock = 256;
+constexpr int kMaxReplicas = AGBNP_HIP_MAX_GROUP;
+// the last word of a Philox counter names the stream: the two blocks of a step's noise, the two exchanges' deviates
+constexpr uint32_t kNoiseWord0 = 0u, kNoiseWord1 = 1u, kExchangeWord = 2u, kHamiltonianWord = 3u;
+
+__host__ __device__ constexpr int blocks_of(int n) { return (n + kBlock - 1) / kBlock; }
+
+// a workgroup's replica r, its thread's atom i (beyond n in the replica's last workgroup) and the offset o of replica r in an
+// [R][n][3] array; the grid is R x blocks workgroups
+struct Place {
+  int r, i;
+  size_t o;
+};
+__device__ __forceinline__ Place place(int blocks, int n) {
+  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  return Place{r, i, (size_t)r * 3 * n};
+}
 
 struct Philox {
   uint32_t c[4];
@@ -199,14 +218,34 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return r;
 }
 
+// one component of an atom's tether, the position word x in a register:  f = -k (x - x0);  returns the atom's energy so far,
+// e, with this component's k/2 (x - x0)^2 added in one fma.  Its callers take d = 0, 1, 2 in turn from e = 0
+__device__ __forceinline__ double tether(double x, double x0, double k, double& f, double e) {
+  const double dd = x - x0;
+  f = -k * dd;
+  return fma(0.5 * k * dd, dd, e);
+}
+
+// thread 0 counts its workgroup in at *counter, a release fence in front of the count; true, for every thread, in the last of
+// the `blocks` workgroups to arrive.  What a workgroup publishes in front of the call is its caller's, and so is the acquire
+// fence in front of what the last one reads
+__device__ __forceinline__ bool last_to_arrive(unsigned* counter, int blocks, bool& s_last) {
+  if (threadIdx.x == 0) {
+    __threadfence();
+    s_last = atomicAdd(counter, 1u) == (unsigned)blocks - 1u;
+  }
+  __syncthreads();
+  return s_last;
+}
+
 // the front half of a step for atom i of one replica, velocity pv already kicked: drift (+ OU for Langevin at the replica's bath
 // temperature), tethers; returns the atom's tether energy.  kind 0: Langevin (BAOAB), 1: velocity Verlet
 __device__ __forceinline__ double front_half(int i, int kind, double (&px)[3], double (&pv)[3], double* __restrict__ x, double* __restrict__ v,
                                              double* __restrict__ f, const double* __restrict__ x0, double kT, double mass, double c1,
                                              double dt, double ktether, unsigned long long seed, unsigned long long s) {
   if (kind == 0) {
-    const Philox a = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const Philox b = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const Philox a = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), kNoiseWord0, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const Philox b = philox4x32((uint32_t)i, (uint32_t)s, (uint32_t)(s >> 32), kNoiseWord1, (uint32_t)seed, (uint32_t)(seed >> 32));
     double z[4];
     box_muller(uniform53(a.c[0], a.c[1]), uniform53(a.c[2], a.c[3]), z[0], z[1]);
     box_muller(uniform53(b.c[0], b.c[1]), uniform53(b.c[2], b.c[3]), z[2], z[3]);
@@ -221,11 +260,9 @@ __device__ __forceinline__ double front_half(int i, int kind, double (&px)[3], d
   }
   double e = 0.0;
   for (int d = 0; d < 3; d++) {
-    const double dd = px[d] - x0[3 * i + d];
     x[3 * i + d] = px[d];
     v[3 * i + d] = pv[d];
-    f[3 * i + d] = -ktether * dd;
-    e = fma(0.5 * ktether * dd, dd, e);
+    e = tether(px[d], x0[3 * i + d], ktether, f[3 * i + d], e);
   }
   return e;
 }
@@ -234,13 +271,8 @@ __device__ __forceinline__ double front_half(int i, int kind, double (&px)[3], d
 // the energy word and the accumulators back as zeros.  acc[2 r]: the kinetic-energy sum, done[r]: workgroups that have added theirs
 __device__ __forceinline__ void group_log_step(const AgbnpMdGroup& g, int r, int blocks, const double* __restrict__ part, long long s, double ke,
                                                double* red, bool& s_last) {
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(&g.acc[2 * r], ke, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    s_last = atomicAdd(&g.done[r], 1u) == (unsigned)blocks - 1u;
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(&g.acc[2 * r], ke, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!last_to_arrive(&g.done[r], blocks, s_last)) return;
   double et = 0.0;
   for (int b = threadIdx.x; b < blocks; b += kBlock) et += part[b];
   et = block_sum(et, red);
@@ -260,8 +292,7 @@ __device__ __forceinline__ void group_log_step(const AgbnpMdGroup& g, int r, int
 // one thread per atom: everything in front of the force evaluation of a step
 __global__ __launch_bounds__(kBlock) void k_md_group_pre(AgbnpMdGroup g, int blocks, int kind, double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
-  const size_t o = (size_t)r * 3 * g.n;
+  const auto [r, i, o] = place(blocks, g.n);
   double e = 0.0;
   if (i < g.n) {
     const double h = g.hdt_m[i];
@@ -278,8 +309,7 @@ __global__ __launch_bounds__(kBlock) void k_md_group_pre(AgbnpMdGroup g, int blo
 __global__ __launch_bounds__(kBlock) void k_md_group_post(AgbnpMdGroup g, int blocks, const double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
   __shared__ bool s_last;
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
-  const size_t o = (size_t)r * 3 * g.n;
+  const auto [r, i, o] = place(blocks, g.n);
   const long long s = g.step[r];  // (read before this workgroup counts itself in: only the last to arrive writes it)
   double ke = 0.0;
   if (i < g.n) {
@@ -301,8 +331,7 @@ __global__ __launch_bounds__(kBlock) void k_md_group_mid(AgbnpMdGroup g, int blo
                                                         double* __restrict__ part_new) {
   __shared__ double red[kBlock / 64];
   __shared__ bool s_last;
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
-  const size_t o = (size_t)r * 3 * g.n;
+  const auto [r, i, o] = place(blocks, g.n);
   const long long s = g.step[r];
   double ke = 0.0, e = 0.0;
   if (i < g.n) {
@@ -327,15 +356,10 @@ __global__ __launch_bounds__(kBlock) void k_md_group_mid(AgbnpMdGroup g, int blo
 // tethers alone (the first force evaluation of a run, and the minimiser's): f = -k (x - x0), partials of their energy
 __global__ __launch_bounds__(kBlock) void k_md_group_tethers(AgbnpMdGroup g, int blocks, double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
-  const size_t o = (size_t)r * 3 * g.n;
+  const auto [r, i, o] = place(blocks, g.n);
   double e = 0.0;
   if (i < g.n)
-    for (int d = 0; d < 3; d++) {
-      const double dd = g.x[o + 3 * i + d] - g.x0[3 * i + d];
-      g.f[o + 3 * i + d] = -g.ktether * dd;
-      e = fma(0.5 * g.ktether * dd, dd, e);
-    }
+    for (int d = 0; d < 3; d++) e = tether(g.x[o + 3 * i + d], g.x0[3 * i + d], g.ktether, g.f[o + 3 * i + d], e);
   e = block_sum(e, red);
   if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
 }
@@ -393,11 +417,10 @@ __device__ __forceinline__ void fire_judge(const AgbnpMdGroup& g, const AgbnpMdF
 
 // behind an evaluation: the four reductions per workgroup as partials; the replica's last workgroup to arrive judges.  The
 // partials cross workgroups inside the launch: agent-scope stores, a release in front of the count, an acquire behind it
-__global__ __launch_bounds__(kBlock) void k_md_fire_back(AgbnpMdGroup g, AgbnpMdFire q, int blocks, const double* __restrict__ tether_part) {
+__global__ __launch_bounds__(kBlock) void k_md_fire_back(AgbnpMdGroup g, int blocks, AgbnpMdFire q, const double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
   __shared__ bool s_last;
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
-  const size_t o = (size_t)r * 3 * g.n;
+  const auto [r, i, o] = place(blocks, g.n);
   double p = 0.0, ff = 0.0, s = 0.0;
   if (i < g.n)
     for (int d = 0; d < 3; d++) {
@@ -412,11 +435,8 @@ __global__ __launch_bounds__(kBlock) void k_md_fire_back(AgbnpMdGroup g, AgbnpMd
     __hip_atomic_store(mine + 1, ff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(mine + 2, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(mine + 3, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    s_last = atomicAdd(&q.arrived[r], 1u) == (unsigned)blocks - 1u;
   }
-  __syncthreads();
-  if (!s_last || threadIdx.x != 0) return;
+  if (!last_to_arrive(&q.arrived[r], blocks, s_last) || threadIdx.x != 0) return;
   __threadfence();
   double P = 0.0, Q = 0.0, S = 0.0, M = 0.0, T = 0.0;
   const double* all = q.part + 4 * (size_t)r * blocks;
@@ -430,11 +450,10 @@ __global__ __launch_bounds__(kBlock) void k_md_fire_back(AgbnpMdGroup g, AgbnpMd
   fire_judge(g, q, r, P, Q, S, M, T);
 }
 
-// in front of the next evaluation: the move the back half decided, then the tethers as k_md_group_tethers leaves them
-__global__ __launch_bounds__(kBlock) void k_md_fire_front(AgbnpMdGroup g, AgbnpMdFire q, int blocks, double* __restrict__ tether_part) {
+// in front of the next evaluation: the move the back half decided, then tether() as in k_md_group_tethers
+__global__ __launch_bounds__(kBlock) void k_md_fire_front(AgbnpMdGroup g, int blocks, AgbnpMdFire q, double* __restrict__ tether_part) {
   __shared__ double red[kBlock / 64];
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
-  const size_t o = (size_t)r * 3 * g.n;
+  const auto [r, i, o] = place(blocks, g.n);
   const double ca = q.coef[4 * r], cb = q.coef[4 * r + 1], dt = q.coef[4 * r + 2];
   const bool move = q.coef[4 * r + 3] != 0.0;
   double e = 0.0;
@@ -461,33 +480,37 @@ __global__ __launch_bounds__(kBlock) void k_md_fire_front(AgbnpMdGroup g, AgbnpM
         g.x[o + 3 * i + d] = px[d];
       }
     }
-    for (int d = 0; d < 3; d++) {
-      const double dd = px[d] - g.x0[3 * i + d];
-      g.f[o + 3 * i + d] = -g.ktether * dd;
-      e = fma(0.5 * g.ktether * dd, dd, e);
-    }
+    for (int d = 0; d < 3; d++) e = tether(px[d], g.x0[3 * i + d], g.ktether, g.f[o + 3 * i + d], e);
   }
   e = block_sum(e, red);
   if (threadIdx.x == 0) tether_part[blockIdx.x] = e;
 }
 
-constexpr int kMaxReplicas = 16;  // AGBNP_HIP_MAX_GROUP
+// The schedule of exchange attempt a, shared by both decide kernels (one workgroup, thread t): thread t has the pair of rungs
+// (k, k + 1), k = pair_of(a, t) = a mod 2 + 2 t, where k + 1 < R; the pair's record has a fixed place in the log -- attempts
+// 0 .. a - 1 left (a + 1) / 2 even ones with R / 2 pairs each and a / 2 odd ones with (R - 1) / 2 --; its deviate is uniform53
+// of Philox(counter (k, a lo, a hi, word), key seed), `word` keeping the two exchanges' streams apart
+__device__ __forceinline__ int pair_of(long long a, int t) { return 2 * t + (int)(a & 1); }
+__device__ __forceinline__ long long record_place(long long a, int R, int t) { return ((a + 1) / 2) * (R / 2) + (a / 2) * ((R - 1) / 2) + t; }
+__device__ __forceinline__ double attempt_uniform(int k, long long a, uint32_t word, unsigned long long seed) {
+  const Philox p = philox4x32((uint32_t)k, (uint32_t)a, (uint32_t)((unsigned long long)a >> 32), word, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return uniform53(p.c[0], p.c[1]);
+}
 
 // attempt a = attempts[0]: pairs of rungs (k, k + 1), k = a mod 2, a mod 2 + 2, ...; accept iff log(u) <= Delta,
-// Delta = (1 / kT_lo - 1 / kT_hi) (U_lo - U_hi), u = uniform53 of Philox(counter (k, a lo, a hi, 2), key seed).  An accepted
+// Delta = (1 / kT_lo - 1 / kT_hi) (U_lo - U_hi), u = attempt_uniform with counter word kExchangeWord (2).  An accepted
 // pair swaps temperatures and rungs; conformations stay.  The records of an attempt have fixed places in the log.
 __global__ __launch_bounds__(64) void k_md_exchange_decide(AgbnpMdExchange e) {
   const int t = threadIdx.x, R = e.replicas;
   const long long a = e.attempts[0];
   if (t < R) e.scale[t] = 1.0;
   __syncthreads();
-  const int parity = (int)(a & 1), k = 2 * t + parity;
+  const int k = pair_of(a, t);
   if (k + 1 < R) {
     const int lo = e.replica_at_rung[k], hi = e.replica_at_rung[k + 1];
     const double kT_lo = e.kT[lo], kT_hi = e.kT[hi], u_lo = e.last[2 * lo], u_hi = e.last[2 * hi];
     const double delta = (1.0 / kT_lo - 1.0 / kT_hi) * (u_lo - u_hi);
-    const Philox p = philox4x32((uint32_t)k, (uint32_t)a, (uint32_t)((unsigned long long)a >> 32), 2u, (uint32_t)e.seed, (uint32_t)(e.seed >> 32));
-    const double u = uniform53(p.c[0], p.c[1]);
+    const double u = attempt_uniform(k, a, kExchangeWord, e.seed);
     const bool accepted = log(u) <= delta;
     if (accepted) {
       e.kT[lo] = kT_hi, e.kT[hi] = kT_lo;
@@ -495,8 +518,7 @@ __global__ __launch_bounds__(64) void k_md_exchange_decide(AgbnpMdExchange e) {
       e.replica_at_rung[k] = hi, e.replica_at_rung[k + 1] = lo;
       e.scale[lo] = sqrt(kT_hi / kT_lo), e.scale[hi] = sqrt(kT_lo / kT_hi);
     }
-    // attempts 0 .. a - 1 left (a + 1) / 2 even ones with R / 2 pairs each and a / 2 odd ones with (R - 1) / 2
-    const long long at = ((a + 1) / 2) * (R / 2) + (a / 2) * ((R - 1) / 2) + t;
+    const long long at = record_place(a, R, t);
     if (at < e.log_capacity) e.log[at] = AgbnpMdExchangeRecord{a, e.step[lo], k, lo, hi, accepted ? 1 : 0, u_lo, u_hi, kT_lo, kT_hi, u};
   }
   __syncthreads();  // (every thread has read `a`)
@@ -504,24 +526,24 @@ __global__ __launch_bounds__(64) void k_md_exchange_decide(AgbnpMdExchange e) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_md_exchange_apply(AgbnpMdExchange e, int blocks) {
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const auto [r, i, o] = place(blocks, e.n);
   const double s = e.scale[r];
   if (s == 1.0 || i >= e.n) return;
-  double* v = e.v + (size_t)r * 3 * e.n + 3 * i;
+  double* v = e.v + o + 3 * i;
   for (int d = 0; d < 3; d++) v[d] *= s;
 }
 
 // attempt a = attempts[0] of a Hamiltonian exchange: pairs of slots (k, k + 1), k = a mod 2, a mod 2 + 2, ...; accept iff
-// log(u) <= Delta (the header comment), u = uniform53 of Philox(counter (k, a lo, a hi, 3), key seed): word 3 keeps the stream
+// log(u) <= Delta (the header comment), u = attempt_uniform with counter word kHamiltonianWord (3): it keeps the stream
 // apart from the temperature exchange's.  The records of an attempt have the fixed places k_md_exchange_decide uses.
 __global__ __launch_bounds__(64) void k_md_hamiltonian_decide(AgbnpMdHamiltonian h) {
   const int t = threadIdx.x, R = h.replicas;
   const long long a = h.attempts[0];
   if (t < R) h.partner[t] = -1, h.scale[t] = 1.0;
   __syncthreads();
-  const int parity = (int)(a & 1), lo = 2 * t + parity, hi = lo + 1;
+  const int lo = pair_of(a, t), hi = lo + 1;
   if (hi < R) {
-    const int blocks = (h.n + kBlock - 1) / kBlock;
+    const int blocks = blocks_of(h.n);
     const double kT_lo = h.kT[lo], kT_hi = h.kT[hi], p_lo = h.last[2 * lo], p_hi = h.last[2 * hi];
     const double k_lo = h.last[2 * lo + 1], k_hi = h.last[2 * hi + 1], c_lo = h.cross[lo], c_hi = h.cross[hi];
     double t_lo = 0.0, t_hi = 0.0;
@@ -529,8 +551,7 @@ __global__ __launch_bounds__(64) void k_md_hamiltonian_decide(AgbnpMdHamiltonian
     h.cross[lo] = 0.0, h.cross[hi] = 0.0;
     const int w_lo = h.walker_at_rung[lo], w_hi = h.walker_at_rung[hi];
     const double delta = ((p_lo - t_lo) - c_lo) / kT_lo + ((p_hi - t_hi) - c_hi) / kT_hi + (1.0 / kT_lo - 1.0 / kT_hi) * (t_lo - t_hi);
-    const Philox p = philox4x32((uint32_t)lo, (uint32_t)a, (uint32_t)((unsigned long long)a >> 32), 3u, (uint32_t)h.seed, (uint32_t)(h.seed >> 32));
-    const double u = uniform53(p.c[0], p.c[1]);
+    const double u = attempt_uniform(lo, a, kHamiltonianWord, h.seed);
     // the engine adds nothing for a withheld evaluation: a cross word that is still zero is a missing cross energy
     const bool is_void = c_lo == 0.0 || c_hi == 0.0 || !isfinite(c_lo) || !isfinite(c_hi);
     const bool accepted = !is_void && log(u) <= delta;
@@ -542,7 +563,7 @@ __global__ __launch_bounds__(64) void k_md_hamiltonian_decide(AgbnpMdHamiltonian
       if (w_hi >= 0 && w_hi < R) h.rung_of_walker[w_hi] = lo;
       h.last[2 * lo + 1] = k_hi * kT_lo / kT_hi, h.last[2 * hi + 1] = k_lo * kT_hi / kT_lo;
     }
-    const long long at = ((a + 1) / 2) * (R / 2) + (a / 2) * ((R - 1) / 2) + t;
+    const long long at = record_place(a, R, t);
     if (at < h.log_capacity)
       h.log[at] = AgbnpMdHamiltonianRecord{a, h.step[lo], lo, w_lo, w_hi, is_void ? -1 : (accepted ? 1 : 0), p_lo, p_hi, t_lo, t_hi, c_lo, c_hi,
                                            kT_lo, kT_hi, u};
@@ -553,11 +574,11 @@ __global__ __launch_bounds__(64) void k_md_hamiltonian_decide(AgbnpMdHamiltonian
 
 // only the workgroups of a slot whose partner is a HIGHER slot work: thread i exchanges atom i of the two conformations
 __global__ __launch_bounds__(kBlock) void k_md_hamiltonian_apply(AgbnpMdHamiltonian h, int blocks) {
-  const int r = blockIdx.x / blocks, b = blockIdx.x - r * blocks, i = b * kBlock + threadIdx.x;
+  const auto [r, i, o] = place(blocks, h.n);
   const int q = h.partner[r];
   if (q <= r || q >= h.replicas || i >= h.n) return;
   const double sr = h.scale[r], sq = h.scale[q];
-  const size_t o_r = (size_t)r * 3 * h.n + 3 * i, o_q = (size_t)q * 3 * h.n + 3 * i;
+  const size_t o_r = o + 3 * i, o_q = (size_t)q * 3 * h.n + 3 * i;
   for (int d = 0; d < 3; d++) {
     const double xr = h.x[o_r + d], xq = h.x[o_q + d], vr = h.v[o_r + d], vq = h.v[o_q + d];
     h.x[o_r + d] = xq, h.x[o_q + d] = xr;
@@ -565,78 +586,69 @@ __global__ __launch_bounds__(kBlock) void k_md_hamiltonian_apply(AgbnpMdHamilton
   }
 }
 
-inline bool group_ok(const AgbnpMdGroup* g) { return g && g->n > 0 && g->replicas >= 1 && g->replicas <= kMaxReplicas; }
+// the entry points' two bodies.  A struct of any of the three kinds is judged by its first two words
+template <typename S>
+bool shape_ok(const S* s) { return s && s->n > 0 && s->replicas >= 1 && s->replicas <= kMaxReplicas; }
+
+// one launch of a per-atom kernel (AgbnpMdGroup, blocks, args...) for all the replicas of *g
+template <typename K, typename... A>
+int launch_group(K kernel, const AgbnpMdGroup* g, void* stream, A... args) {
+  if (!shape_ok(g)) return (int)hipErrorInvalidValue;
+  const int blocks = blocks_of(g->n);
+  hipLaunchKernelGGL(kernel, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, args...);
+  return (int)hipGetLastError();
+}
+
+// the two launches of an exchange attempt: decide (one workgroup of 64), then apply per atom
+template <typename E, typename D, typename P>
+int launch_exchange(D decide, P apply, const E* e, void* stream) {
+  if (!shape_ok(e)) return (int)hipErrorInvalidValue;
+  const int blocks = blocks_of(e->n);
+  hipLaunchKernelGGL(decide, dim3(1), dim3(64), 0, (hipStream_t)stream, *e);
+  hipLaunchKernelGGL(apply, dim3(e->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *e, blocks);
+  return (int)hipGetLastError();
+}
 
 }  // namespace
 
 extern "C" {
 
-int agbnp_md_blocks(int n) { return (n + kBlock - 1) / kBlock; }
+int agbnp_md_blocks(int n) { return blocks_of(n); }
 
 // One launch each for all the replicas of *g (a host struct, read during the call).  tether_part / part_old / part_new:
 // [R][agbnp_md_blocks(n)].  kind 0: Langevin, 1: velocity Verlet.  Return: hipError_t of the launch, 1 for a bad *g.
 int agbnp_md_group_pre(const AgbnpMdGroup* g, int kind, double* tether_part, void* stream) {
-  if (!group_ok(g)) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(g->n);
-  hipLaunchKernelGGL(k_md_group_pre, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, kind, tether_part);
-  return (int)hipGetLastError();
+  return launch_group(k_md_group_pre, g, stream, kind, tether_part);
 }
-
 int agbnp_md_group_mid(const AgbnpMdGroup* g, int kind, const double* part_old, double* part_new, void* stream) {
-  if (!group_ok(g)) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(g->n);
-  hipLaunchKernelGGL(k_md_group_mid, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, kind, part_old, part_new);
-  return (int)hipGetLastError();
+  return launch_group(k_md_group_mid, g, stream, kind, part_old, part_new);
 }
-
 int agbnp_md_group_post(const AgbnpMdGroup* g, const double* tether_part, void* stream) {
-  if (!group_ok(g)) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(g->n);
-  hipLaunchKernelGGL(k_md_group_post, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, tether_part);
-  return (int)hipGetLastError();
+  return launch_group(k_md_group_post, g, stream, tether_part);
 }
-
 int agbnp_md_group_tethers(const AgbnpMdGroup* g, double* tether_part, void* stream) {
-  if (!group_ok(g)) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(g->n);
-  hipLaunchKernelGGL(k_md_group_tethers, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, blocks, tether_part);
-  return (int)hipGetLastError();
+  return launch_group(k_md_group_tethers, g, stream, tether_part);
 }
 
 // The two launches of a FIRE iteration (the header comment), one each for all the replicas of *g; *q is a host struct as *g is.
 // tether_part: [R][agbnp_md_blocks(n)], read by the back half, written by the front half.  Return: as the group entry points,
 // a null *q included.
 int agbnp_md_fire_back(const AgbnpMdGroup* g, const AgbnpMdFire* q, const double* tether_part, void* stream) {
-  if (!group_ok(g) || !q) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(g->n);
-  hipLaunchKernelGGL(k_md_fire_back, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, *q, blocks, tether_part);
-  return (int)hipGetLastError();
+  return q ? launch_group(k_md_fire_back, g, stream, *q, tether_part) : (int)hipErrorInvalidValue;
 }
-
 int agbnp_md_fire_front(const AgbnpMdGroup* g, const AgbnpMdFire* q, double* tether_part, void* stream) {
-  if (!group_ok(g) || !q) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(g->n);
-  hipLaunchKernelGGL(k_md_fire_front, dim3(g->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *g, *q, blocks, tether_part);
-  return (int)hipGetLastError();
+  return q ? launch_group(k_md_fire_front, g, stream, *q, tether_part) : (int)hipErrorInvalidValue;
 }
 
 // One exchange attempt between neighbouring rungs: two launches (decide, rescale), no synchronisation, nothing read back.
 int agbnp_md_exchange(const AgbnpMdExchange* e, void* stream) {
-  if (!e || e->n <= 0 || e->replicas < 1 || e->replicas > kMaxReplicas) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(e->n);
-  hipLaunchKernelGGL(k_md_exchange_decide, dim3(1), dim3(64), 0, (hipStream_t)stream, *e);
-  hipLaunchKernelGGL(k_md_exchange_apply, dim3(e->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *e, blocks);
-  return (int)hipGetLastError();
+  return launch_exchange(k_md_exchange_decide, k_md_exchange_apply, e, stream);
 }
 
 // One Hamiltonian exchange attempt between neighbouring slots: two launches (decide, exchange the conformations), no
 // synchronisation, nothing read back.  The cross energies of the attempt's pairs are in h->cross when the first one runs.
 int agbnp_md_hamiltonian_exchange(const AgbnpMdHamiltonian* h, void* stream) {
-  if (!h || h->n <= 0 || h->replicas < 1 || h->replicas > kMaxReplicas) return (int)hipErrorInvalidValue;
-  const int blocks = agbnp_md_blocks(h->n);
-  hipLaunchKernelGGL(k_md_hamiltonian_decide, dim3(1), dim3(64), 0, (hipStream_t)stream, *h);
-  hipLaunchKernelGGL(k_md_hamiltonian_apply, dim3(h->replicas * blocks), dim3(kBlock), 0, (hipStream_t)stream, *h, blocks);
-  return (int)hipGetLastError();
+  return launch_exchange(k_md_hamiltonian_decide, k_md_hamiltonian_apply, h, stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ outside this repository; here the only force-field term besides AGBNP is a harmo
 position, which keeps the geometry a protein.  Everything lives on the GPU: torch tensors for the integrator state, the
 engine's device entry points for the force.
 
-One state core, two drivers.  `_Replicas` holds the state of R >= 1 replicas of one system as strided arrays and makes the
+One state core, three drivers.  `_Replicas` holds the state of R >= 1 replicas of one system as strided arrays and makes the
 integrator's launches: two of libagbnp_md.so (csrc/md_kernels.hip: everything in front of the force evaluation, everything
 behind it -- between the steps of a run both in ONE launch; Philox normal deviates) around an evaluation its driver supplies.
 `DeviceMD` is the core at R = 1 around `agbnp_hip_execute_device`, its steps captured ONCE as a HIP graph and replayed; the
@@ -28,9 +28,14 @@ import os
 
 import numpy as np
 
+from . import _lib
+
 KB = 0.0083144626  # kJ/mol/K
 
-MAX_REPLICAS = 16  # AGBNP_HIP_MAX_GROUP
+MAX_REPLICAS = _lib.MAX_GROUP  # AGBNP_HIP_MAX_GROUP
+
+# the last word of a Philox counter names the stream (csrc/md_kernels.hip: kNoiseWord0, kNoiseWord1, kExchangeWord, kHamiltonianWord)
+PHILOX_NOISE_0, PHILOX_NOISE_1, PHILOX_EXCHANGE, PHILOX_HAMILTONIAN = 0, 1, 2, 3
 
 _M64 = 0xFFFFFFFFFFFFFFFF
 
@@ -83,7 +88,6 @@ def _md_lib():
     """libagbnp_md.so (example support, not part of the drop-in boundary); built by csrc/Makefile next to the engine."""
     global _MD_LIB
     if _MD_LIB is None:
-        from . import _lib
         _lib.load()  # (one HIP runtime per process: the engine's loader settles which)
         path = os.environ.get("AGBNP_HIP_MD_LIBRARY") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libagbnp_md.so")  # override: diagnostic builds only
         if not os.path.exists(path):
@@ -109,6 +113,24 @@ def _check(rc):
 
 
 _KINDS = {"langevin": 0, "verlet": 1}  # the kernels' `kind`
+
+
+def _args(struct, **fields):
+    """An argument struct filled by field name; a device tensor stands for its address.  A name that is not a field of
+    `struct`, or a field left out, is an error here rather than a misplaced pointer in a kernel."""
+    names = {name for name, _ in struct._fields_}
+    if set(fields) != names:
+        raise TypeError(f"{struct.__name__}: not a field {sorted(set(fields) - names)}, missing {sorted(names - set(fields))}")
+    return struct(**{name: val.data_ptr() if hasattr(val, "data_ptr") else val for name, val in fields.items()})
+
+
+def _on_side(torch, side, fn):
+    """fn() enqueued on the stream `side` behind torch's current one, and waited for; returns what fn returns."""
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        out = fn()
+    side.synchronize()
+    return out
 
 
 def _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move):
@@ -167,11 +189,10 @@ class _Replicas:
         self.log_ke = torch.zeros((R, cap), **f64)
         self.counter = torch.zeros(R, **i64)
         self.last = torch.zeros((R, 2), **f64)  # {potential, kinetic} energy of every replica's last step
-        p = lambda t: t.data_ptr()  # noqa: E731
-        self._g = _GroupArgs(n, R, p(self.x), p(self.v), p(self.frc), p(self.x0), p(self.hdt_m1), p(self.mass1), p(self.kT),
-                             p(self.seed_words), self.c1, self.dt, self.k, p(self.e_agbnp), p(self.acc), p(self.done), p(self.log_pe),
-                             p(self.log_ke), p(self.counter), cap, p(self.last))
-        self._parts = (p(self.parts[0]), p(self.parts[1]))
+        self._g = _args(_GroupArgs, n=n, replicas=R, x=self.x, v=self.v, f=self.frc, x0=self.x0, hdt_m=self.hdt_m1, mass=self.mass1,
+                        kT=self.kT, seeds=self.seed_words, c1=self.c1, dt=self.dt, ktether=self.k, energy=self.e_agbnp, acc=self.acc,
+                        done=self.done, log_pe=self.log_pe, log_ke=self.log_ke, step=self.counter, capacity=cap, last=self.last)
+        self._parts = (self.parts[0].data_ptr(), self.parts[1].data_ptr())
         self.part_read = 0  # the partial buffer last[:, 0] was summed from: 0 behind forces(), (s - 1) % 2 behind steps(.., s, ..)
         self.fire = None    # the minimiser's device words: allocated by the first minimise()
 
@@ -185,6 +206,10 @@ class _Replicas:
         self.e_agbnp.zero_()
         self.tethers(st)
         evaluate(st)
+        self._evaluated(torch)
+
+    def _evaluated(self, torch):
+        """The evaluation at the current positions is complete (tethers in parts[0], AGBNP in e_agbnp): last[:, 0] is their sum."""
         torch.add(self.parts[0].sum(dim=1), self.e_agbnp, out=self.last[:, 0])
         self.e_agbnp.zero_()  # (a step that follows starts its own sum)
         self.part_read = 0
@@ -235,7 +260,7 @@ class _Replicas:
         iteration for that replica, converged or not: counted in `voids`, repeated in place; `withheld` is what the members'
         finish() reported.  Where either is not zero the LAST evaluation may have been such a one: `energy`, `fmax`, frc and
         last[:, 0] of that replica then lack the AGBNP term, and forces() puts them right."""
-        _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move)
+        _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move)  # (the drivers' too: theirs comes first)
         max_iterations, check_every = int(max_iterations), int(check_every)
         lib, g, part = self.lib, C.byref(self._g), self._parts[0]
         fire = self._fire_state(torch, max_iterations)
@@ -243,11 +268,8 @@ class _Replicas:
             fire[key].zero_()
         fire["dt"].fill_(float(dt0))
         fire["alpha"].fill_(FIRE_ALPHA0)
-        p = lambda key: fire[key].data_ptr()  # noqa: E731
-        q = _FireArgs(p("w"), p("dt"), p("alpha"), p("npos"), p("iterations"), p("converged"), p("voids"), p("fmax"), p("coef"), p("part"),
-                      p("arrived"), p("log_e"), p("log_fmax"), fire["capacity"], float(dt_max), FIRE_F_INC, FIRE_F_DEC, FIRE_ALPHA0,
-                      FIRE_F_ALPHA, FIRE_N_MIN, float(tolerance), float(max_move))
-        q = C.byref(q)
+        q = C.byref(_args(_FireArgs, **fire, dt_max=float(dt_max), f_inc=FIRE_F_INC, f_dec=FIRE_F_DEC, alpha0=FIRE_ALPHA0,
+                          f_alpha=FIRE_F_ALPHA, n_min=FIRE_N_MIN, tolerance=float(tolerance), max_move=float(max_move)))
         self.e_agbnp.zero_()
         self.tethers(st)
         evaluate(st)
@@ -268,9 +290,7 @@ class _Replicas:
                 break
         # as forces() ends: every replica's last evaluation is at the positions it now holds (a converged one's repeats the
         # evaluation it converged on)
-        torch.add(self.parts[0].sum(dim=1), self.e_agbnp, out=self.last[:, 0])
-        self.e_agbnp.zero_()
-        self.part_read = 0
+        self._evaluated(torch)
         out = np.zeros(self.R, dtype=MINIMISE_RECORD)
         out["iterations"], out["converged"] = fire["iterations"].cpu().numpy(), fire["converged"].cpu().numpy()
         out["fmax"] = self.frc.square().sum(dim=2).max(dim=1).values.sqrt().cpu().numpy()
@@ -342,14 +362,13 @@ class DeviceMD:
         stream for its context's own stream, which nothing of torch's is ordered against."""
         torch = self.torch
         if not torch.cuda.is_current_stream_capturing() and torch.cuda.current_stream().cuda_stream == 0:
-            if self._eager is None:
-                self._eager = torch.cuda.Stream(device=self.dev)
-            self._eager.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._eager):
-                self._forces()
-            self._eager.synchronize()
-            return
+            return _on_side(torch, self._side(), self._forces)
         self._forces()
+
+    def _side(self):
+        if self._eager is None:
+            self._eager = self.torch.cuda.Stream(device=self.dev)
+        return self._eager
 
     def _forces(self):
         torch = self.torch
@@ -407,16 +426,10 @@ class DeviceMD:
         moves more than `max_move` nm between two evaluations, so none is withheld for a jump.  self.v and the step logs are
         untouched, and the state is as forces() leaves it: run() may follow.  Returns one MINIMISE_RECORD (a numpy array of 1)."""
         _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move)
-        torch = self.torch
-        if self._eager is None:
-            self._eager = torch.cuda.Stream(device=self.dev)
-        side = self._eager
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            out = self.core.minimise(torch, side.cuda_stream, self._evaluate, lambda: [self.kernel.finish(side.cuda_stream)], tolerance,
-                                     max_iterations, check_every, dt0, dt_max, max_move, on_check)
-        side.synchronize()
-        return out
+        torch, side = self.torch, self._side()
+        return _on_side(torch, side, lambda: self.core.minimise(
+            torch, side.cuda_stream, self._evaluate, lambda: [self.kernel.finish(side.cuda_stream)], tolerance, max_iterations,
+            check_every, dt0, dt_max, max_move, on_check))
 
     # ---- graph capture / replay
     def settle(self):
@@ -520,11 +533,23 @@ def uniform53(a, b):
     return (float(u) + 1.0) * (1.0 / 9007199254740992.0)
 
 
+def _attempt_uniform(rung, attempt, word, exchange_seed):
+    """`attempt_uniform` of csrc/md_kernels.hip: counter (k, a lo, a hi, word), key exchange_seed."""
+    a, s = int(attempt), int(exchange_seed)
+    w = philox4x32((int(rung), a & _M32, (a >> 32) & _M32, word), (s & _M32, (s >> 32) & _M32))
+    return uniform53(w[0], w[1])
+
+
 def exchange_uniform(rung, attempt, exchange_seed):
     """The deviate attempt `attempt` uses for the rung pair (rung, rung + 1): counter (k, a lo, a hi, 2), key exchange_seed."""
-    a, s = int(attempt), int(exchange_seed)
-    w = philox4x32((int(rung), a & _M32, (a >> 32) & _M32, 2), (s & _M32, (s >> 32) & _M32))
-    return uniform53(w[0], w[1])
+    return _attempt_uniform(rung, attempt, PHILOX_EXCHANGE, exchange_seed)
+
+
+def exchange_places(attempts, R):
+    """The log place of the first record of attempt `attempts`, which is the number of records the attempts before it left:
+    (a + 1) / 2 even ones with R / 2 pairs each and a / 2 odd ones with (R - 1) / 2 (`record_place` of csrc/md_kernels.hip)."""
+    a, R = int(attempts), int(R)
+    return ((a + 1) // 2) * (R // 2) + (a // 2) * ((R - 1) // 2)
 
 
 def exchange_delta(kT_lo, kT_hi, U_lo, U_hi):
@@ -573,19 +598,17 @@ class _GroupMD:
         # the group call's arguments never change: member r's buffers are slices of the strided arrays
         for k in kernels:
             k._need()
-        p = lambda t: t.data_ptr()  # noqa: E731
         vpR = C.c_void_p * R
         self._handles = vpR(*[k._h for k in kernels])
-        self._pos = vpR(*[p(self.x[r]) for r in range(R)])
-        self._frc = vpR(*[p(self.frc[r]) for r in range(R)])
-        self._ene = vpR(*[p(core.e_agbnp[r:r + 1]) for r in range(R)])
+        self._pos = vpR(*[self.x[r].data_ptr() for r in range(R)])
+        self._frc = vpR(*[self.frc[r].data_ptr() for r in range(R)])
+        self._ene = vpR(*[core.e_agbnp[r:r + 1].data_ptr() for r in range(R)])
         self.stream = torch.cuda.Stream(device=self.dev)  # everything of this driver is enqueued here
         self.steps_done = 0
 
     # ---- launches
     def _evaluate(self, st):
         """agbnp_hip_execute_group of all members on stream `st`: forces and energies are added to frc[r], e_agbnp[r]."""
-        from . import _lib
         rc = _lib.load().agbnp_hip_execute_group(self._handles, self.R, self._pos, self._frc, self._ene, C.c_void_p(st))
         if rc != _lib.OK:
             raise RuntimeError("agbnp_hip_execute_group: " + _lib.last_error(self.kernels[0]._h))
@@ -597,11 +620,7 @@ class _GroupMD:
 
     def forces(self):
         """Tethers + AGBNP of every slot at the current positions: frc[r], last[r, 0].  Waits for the result."""
-        torch = self.torch
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            self.core.forces(torch, self.stream.cuda_stream, self._evaluate)
-        self.stream.synchronize()
+        _on_side(self.torch, self.stream, lambda: self.core.forces(self.torch, self.stream.cuda_stream, self._evaluate))
 
     def minimise(self, tolerance=10.0, max_iterations=1000, check_every=50, dt0=0.001, dt_max=0.005, max_move=0.01, on_check=None):
         """FIRE for every slot from the positions it holds, each under its own context's parameters and with convergence of
@@ -610,13 +629,9 @@ class _GroupMD:
         converged is not moved again while the others go on.  v, counter and the step logs are untouched, and the state is as
         forces() leaves it: run() or exchange() may follow.  Returns one MINIMISE_RECORD per slot."""
         _check_minimise(tolerance, max_iterations, check_every, dt0, dt_max, max_move)
-        torch = self.torch
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            out = self.core.minimise(torch, self.stream.cuda_stream, self._evaluate, self.finish, tolerance, max_iterations, check_every,
-                                     dt0, dt_max, max_move, on_check)
-        self.stream.synchronize()
-        return out
+        return _on_side(self.torch, self.stream, lambda: self.core.minimise(
+            self.torch, self.stream.cuda_stream, self._evaluate, self.finish, tolerance, max_iterations, check_every, dt0, dt_max,
+            max_move, on_check))
 
     def settle(self):
         """Outside any timing: first evaluations (allocations, capacity negotiation, forest packing, the group's argument
@@ -669,8 +684,7 @@ class _GroupMD:
     def _records(self, dtype):
         """One record per attempted pair, in the order of the attempts."""
         self.stream.synchronize()
-        a, R = int(self.attempts.item()), self.R
-        count = min(((a + 1) // 2) * (R // 2) + (a // 2) * ((R - 1) // 2), self.exchange_capacity)
+        count = min(exchange_places(self.attempts.item(), self.R), self.exchange_capacity)
         raw = self.records[:count * dtype.itemsize].cpu().numpy()
         return raw.view(dtype).copy()
 
@@ -699,10 +713,9 @@ class ReplicaMD(_GroupMD):
         self.rung_of_replica = torch.arange(R, dtype=torch.int32, device=self.dev)  # replica r starts on rung r
         self.replica_at_rung = torch.arange(R, dtype=torch.int32, device=self.dev)
         self.records = torch.zeros(self.exchange_capacity * EXCHANGE_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
-        p = lambda t: t.data_ptr()  # noqa: E731
-        self._e = _ExchangeArgs(self.n, R, p(self.v), p(self.kT), p(self.rung_of_replica), p(self.replica_at_rung), p(self.last),
-                                p(self.counter), p(self.attempts), p(self.scale), p(self.records), self.exchange_capacity,
-                                self.exchange_seed & _M64)
+        self._e = _args(_ExchangeArgs, n=self.n, replicas=R, v=self.v, kT=self.kT, rung_of_replica=self.rung_of_replica,
+                        replica_at_rung=self.replica_at_rung, last=self.last, step=self.counter, attempts=self.attempts, scale=self.scale,
+                        log=self.records, log_capacity=self.exchange_capacity, seed=self.exchange_seed & _M64)
 
     def exchange(self):
         """One exchange attempt between neighbouring rungs, enqueued on the driver's stream (two launches, nothing read)."""
@@ -729,9 +742,7 @@ class ReplicaMD(_GroupMD):
 def hamiltonian_uniform(rung, attempt, exchange_seed):
     """The deviate attempt `attempt` uses for the rung pair (rung, rung + 1): counter (k, a lo, a hi, 3), key exchange_seed --
     word 3 keeps the stream apart from `exchange_uniform`'s."""
-    a, s = int(attempt), int(exchange_seed)
-    w = philox4x32((int(rung), a & _M32, (a >> 32) & _M32, 3), (s & _M32, (s >> 32) & _M32))
-    return uniform53(w[0], w[1])
+    return _attempt_uniform(rung, attempt, PHILOX_HAMILTONIAN, exchange_seed)
 
 
 def hamiltonian_delta(kT_lo, kT_hi, P_lo, P_hi, T_lo, T_hi, C_lo, C_hi):
@@ -768,12 +779,12 @@ class HamiltonianReplicaMD(_GroupMD):
         self.partner = torch.full((R,), -1, dtype=torch.int32, device=self.dev)
         self.cross = torch.zeros(R, dtype=torch.float64, device=self.dev)  # the kernel hands every word it read back as zero
         self.records = torch.zeros(self.exchange_capacity * HAMILTONIAN_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
-        p = lambda t: t.data_ptr()  # noqa: E731
         # one argument struct per tether-partial buffer, each filled once: the decision reads the one the last back half read
-        self._h = tuple(_HamiltonianArgs(self.n, R, p(self.x), p(self.v), p(self.kT), p(self.walker_at_rung), p(self.rung_of_walker),
-                                         p(self.last), p(part), p(self.cross), p(self.counter), p(self.attempts), p(self.partner),
-                                         p(self.scale), p(self.records), self.exchange_capacity, self.exchange_seed & _M64)
-                        for part in core.parts)
+        self._h = tuple(_args(_HamiltonianArgs, n=self.n, replicas=R, x=self.x, v=self.v, kT=self.kT, walker_at_rung=self.walker_at_rung,
+                              rung_of_walker=self.rung_of_walker, last=self.last, tether_part=part, cross=self.cross, step=self.counter,
+                              attempts=self.attempts, partner=self.partner, scale=self.scale, log=self.records,
+                              log_capacity=self.exchange_capacity, seed=self.exchange_seed & _M64) for part in core.parts)
+        p = lambda t: t.data_ptr()  # noqa: E731
         # the cross round of the two attempt parities: the members of the pairs (k, k + 1), k = parity, parity + 2, ..., each at
         # the position buffer of its partner's slot, its energy added to cross[k]
         self._cross_round = []
@@ -791,7 +802,6 @@ class HamiltonianReplicaMD(_GroupMD):
         permuted), decision and exchange of the conformations (two launches), refresh (hints again -- the masks sit at the
         partner's conformation after a rejection and the host does not know the verdict -- then tethers and one full group
         evaluation of all R: frc[k] and last[k, 0] are rung k's at what it now holds).  An attempt without a pair only counts."""
-        from . import _lib
         torch = self.torch
         st = self.stream.cuda_stream
         members, handles, pos, ene = self._cross_round[self._attempt & 1]

@@ -6,27 +6,9 @@ import pytest
 
 from tests import fire_restatement as fr
 from tests import md_restatement as mr
+from tests.md_kernel_harness import CASES, assert_same_state, same_bits
 
 LD = np.longdouble
-CASES = [(1, 1), (1, 16), (63, 2), (64, 3), (65, 2), (255, 1), (256, 2), (257, 3), (513, 16)]
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def assert_same_state(a, b, but=()):
-    assert a.keys() == b.keys()
-    for key in a:
-        if key in but:
-            continue
-        if key == "parts":
-            assert all(_same_bits(p, q) for p, q in zip(a[key], b[key])), key
-        elif isinstance(a[key], np.ndarray):
-            assert _same_bits(a[key], b[key]), key
-        else:
-            assert a[key] == b[key], key
 
 
 def start(n, R):
@@ -140,7 +122,7 @@ def test_the_restatement_is_a_plain_double_fire(n, R):
                 assert np.abs(w * scale - moved["w"][r]).max() < 1e-12
                 assert np.sqrt(((moved["x"][r] - before["x"][r]) ** 2).sum(axis=1)).max() <= before["max_move"] * (1.0 + 1e-12)
             else:
-                assert _same_bits(moved["x"][r], before["x"][r]) and _same_bits(moved["w"][r], before["w"][r])
+                assert same_bits(moved["x"][r], before["x"][r]) and same_bits(moved["w"][r], before["w"][r])
             if d["E"] is not None:
                 slot = fr.FGUARD + r * fr.FCAP + int(before["iterations"][r])
                 assert abs(d["fmax"] - judged["fmax"][r]) <= bounds["fmax"][r]
@@ -155,8 +137,8 @@ def test_what_a_launch_must_not_write_stays():
     iteration's slot where it lies inside the capacity (replica 1 starts at slot 10 of 16, replica 2 beyond 2^32), the guards never."""
     for before, bounds, judged, capped, moved in sequence(257, 3):
         for key in ("v", "step", "log_pe", "log_ke", "last", "acc", "done", "x0", "mass", "hdt_m", "kT", "seeds"):
-            assert _same_bits(before[key], judged[key]) and _same_bits(before[key], moved[key]), key
-        assert _same_bits(before["parts"][1], moved["parts"][1])
+            assert same_bits(before[key], judged[key]) and same_bits(before[key], moved[key]), key
+        assert same_bits(before["parts"][1], moved["parts"][1])
         assert_same_state(before, judged, but=("energy", "arrived", "fpart", "coef", "fdt", "alpha", "npos", "iterations", "converged", "voids",
                                                "fmax", "log_e", "log_fmax"))
         assert_same_state(judged, moved, but=("x", "w", "f", "parts"))
@@ -183,18 +165,18 @@ def test_a_void_iteration_changes_nothing_but_the_count():
         assert_same_state(void, judged, but=("energy", "arrived", "fpart", "coef", "voids", "fdt", "alpha", "npos", "iterations", "fmax",
                                              "log_e", "log_fmax"))
         for key in ("fdt", "alpha", "npos", "iterations", "fmax"):
-            assert _same_bits(void[key][1:], judged[key][1:]), key
-        assert _same_bits(void["coef"][1, :3], judged["coef"][1, :3])
+            assert same_bits(void[key][1:], judged[key][1:]), key
+        assert same_bits(void["coef"][1, :3], judged["coef"][1, :3])
         moved = fr.front(judged, 0)
-        assert _same_bits(moved["x"][1], void["x"][1]) and _same_bits(moved["w"][1], void["w"][1])
-        assert not _same_bits(moved["x"][0], void["x"][0])
+        assert same_bits(moved["x"][1], void["x"][1]) and same_bits(moved["w"][1], void["w"][1])
+        assert not same_bits(moved["x"][0], void["x"][0])
     # a force that is not a number beside a finite energy word is void as well (max |F_i|^2 alone would not see it) ...
     for word in (np.nan, np.inf):
         void = fr.copy_state(state)
         void["f"][1, 3, 0] = word
         judged = fr.back(void, 0)
         assert list(judged["voids"]) == [0, 1] and judged["coef"][1, 3] == 0.0 and list(judged["converged"]) == [0, 0]
-        assert judged["iterations"][1] == void["iterations"][1] and _same_bits(judged["fmax"][1:], void["fmax"][1:])
+        assert judged["iterations"][1] == void["iterations"][1] and same_bits(judged["fmax"][1:], void["fmax"][1:])
     # ... and a converged replica counts a withheld evaluation like any other, and stays converged
     void = fr.copy_state(state)
     void["converged"][1], void["energy"][1] = 1, 0.0

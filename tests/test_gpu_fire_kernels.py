@@ -24,14 +24,13 @@ import pytest
 from tests import fire_restatement as fr
 from tests import md_restatement as mr
 from tests.gpu_helpers import energy_close
-from tests.test_gpu_md_kernels import Device, Part, _bits, _note, _same, _up, gpu  # noqa: F401
+from tests.md_kernel_harness import _OWN, CASES, Device, Part, _bits, _note, _same, _up, altered, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 _FIRE_F64 = ("w", "fdt", "alpha", "fmax", "coef", "fpart", "log_e", "log_fmax")
 _UNTOUCHED = ("v", "step", "log_pe", "log_ke", "last", "acc", "done", "x0", "hdt_m", "mass", "kT", "seeds")  # by either launch
 _WORDS = ("fdt", "alpha", "npos", "iterations", "converged", "voids")  # bit for bit behind a back half
-_OWN = object()
 
 
 class FireDevice(Device):
@@ -43,12 +42,11 @@ class FireDevice(Device):
         t = self.t
         t.update({key: _up(gpu, state[key]) for key in _FIRE_F64 + ("npos", "converged", "voids", "iterations")})
         t["arrived"] = _up(gpu, state["arrived"].view(np.int32))
-        p = lambda name: t[name].data_ptr()  # noqa: E731
         guard = 8 * state["fguard"]
-        self.q = gpu.md._FireArgs(p("w"), p("fdt"), p("alpha"), p("npos"), p("iterations"), p("converged"), p("voids"), p("fmax"), p("coef"),
-                                  p("fpart"), p("arrived"), p("log_e") + guard, p("log_fmax") + guard, state["fcap"], state["dt_max"],
-                                  state["f_inc"], state["f_dec"], state["alpha0"], state["f_alpha"], state["n_min"], state["tolerance"],
-                                  state["max_move"])
+        self.q = gpu.md._args(gpu.md._FireArgs, dt=t["fdt"], part=t["fpart"], log_e=t["log_e"].data_ptr() + guard,
+                              log_fmax=t["log_fmax"].data_ptr() + guard, capacity=state["fcap"],
+                              **{key: t[key] for key in ("w", "alpha", "npos", "iterations", "converged", "voids", "fmax", "coef", "arrived")},
+                              **{key: state[key] for key in ("dt_max", "f_inc", "f_dec", "alpha0", "f_alpha", "n_min", "tolerance", "max_move")})
         gpu.torch.cuda.synchronize()
 
     def read(self):
@@ -147,7 +145,6 @@ def _evaluate(dev, y0, void=()):
     dev.upload("energy", E)
 
 
-CASES = [(1, 1), (1, 16), (63, 2), (64, 3), (65, 2), (255, 1), (256, 2), (257, 3), (513, 16)]
 SEQUENCES = [(n, R, fr.ITERATIONS) for n, R in CASES] + [(65537, 2, 12)]  # (257 blocks per replica)
 
 
@@ -236,15 +233,9 @@ def test_bad_arguments_are_refused_and_touch_nothing(gpu):
     dev = FireDevice(gpu, mr.evaluated(mr.tethers(base, 0), y0))
     before = dev.read()
 
-    def altered(**fields):
-        out = type(dev.g).from_buffer_copy(dev.g)
-        for key, val in fields.items():
-            setattr(out, key, val)
-        return C.byref(out)
-
     for name in ("back", "front"):
         for fields in (None, dict(n=0), dict(replicas=0), dict(replicas=17)):
-            assert dev.fire(name, 0, g=None if fields is None else altered(**fields)) != 0, (name, fields)
+            assert dev.fire(name, 0, g=None if fields is None else altered(dev.g, **fields)) != 0, (name, fields)
         assert dev.fire(name, 0, q=None) != 0, name
     after = dev.read()
     for key in before:

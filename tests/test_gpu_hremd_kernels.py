@@ -13,7 +13,6 @@ every attempt the whole state is uploaded, after it the whole state is read back
                     the slots that sit an attempt out, the tails of cross / scale / partner, the log places of other attempts, those
                     beyond the capacity and the guard records around the buffer."""
 import ctypes as C
-import types
 
 import numpy as np
 import pytest
@@ -21,58 +20,29 @@ import pytest
 from tests import hremd_restatement as hr
 from tests import md_restatement as mr
 from tests.gpu_helpers import energy_close
+from tests.md_kernel_harness import _OWN, _bits, _same, _up, altered, gpu, record_buffer, split_records  # noqa: F401
 from tests.test_hremd_api import CASES, CRAFTED, crafted_state
 
 pytestmark = pytest.mark.gpu
 
-_GUARD = 16  # records of 0xFF in front of and behind the record buffer, which must stay 0xFF
 _ARRAYS = ("x", "v", "f", "kT", "last", "step", "cross", "scale", "partner", "walker_at_rung", "rung_of_walker", "attempts")
 _EXACT = ("x", "f", "kT", "step", "cross", "partner", "walker_at_rung", "rung_of_walker", "attempts")
 _RECORD_EXACT = ("attempt", "step", "rung", "walker_lo", "walker_hi", "u")
 _RECORD_ENERGIES = ("P_lo", "P_hi", "T_lo", "T_hi", "C_lo", "C_hi", "kT_lo", "kT_hi")
 
 
-@pytest.fixture(scope="module")
-def gpu(gpu_required):
-    torch = pytest.importorskip("torch")
-    from openmm_agbnp_plugin_amd import md
-    return types.SimpleNamespace(torch=torch, md=md, lib=md._md_lib(), dev=torch.device("cuda:0"))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _up(gpu, a):
-    return gpu.torch.from_numpy(np.ascontiguousarray(a).copy()).to(gpu.dev).contiguous()
-
-
-_OWN = object()  # Device.attempt: the device's own argument struct
-
-
 class Device:
-    """A restatement state as device tensors and one argument struct per partial buffer.  The log pointer handed over is the
-    buffer's address minus `record_base` records (as tests/test_gpu_md_kernels.py::Exchange): the places of this run's attempts
-    are the buffer's 0, 1, ...; log_capacity is a log place as well, so the kernel forms no address outside the buffer."""
+    """A restatement state as device tensors, the records in a `record_buffer`, and one argument struct per partial buffer."""
 
     def __init__(self, gpu, state):
         self.gpu, self.base = gpu, state
         self.R, self.n = state["x"].shape[:2]
-        size = gpu.md.HAMILTONIAN_RECORD.itemsize
         self.t = t = {key: _up(gpu, state[key]) for key in _ARRAYS}
         self.parts = [_up(gpu, p) for p in state["parts"]]
-        guard = np.full(_GUARD * size, 0xFF, dtype=np.uint8)
-        t["records"] = _up(gpu, np.concatenate([guard, state["records"].view(np.uint8), guard]))
-        p = lambda name: t[name].data_ptr()  # noqa: E731
-        log = (p("records") + (_GUARD - state["record_base"]) * size) & 0xFFFFFFFFFFFFFFFF
-        self.h = [gpu.md._HamiltonianArgs(self.n, self.R, p("x"), p("v"), p("kT"), p("walker_at_rung"), p("rung_of_walker"), p("last"),
-                                          part.data_ptr(), p("cross"), p("step"), p("attempts"), p("partner"), p("scale"), log,
-                                          state["log_capacity"], hr.EXCHANGE_SEED) for part in self.parts]
+        words = {key: val for key, val in t.items() if key != "f"}  # (f is state the kernels must leave alone, not an argument)
+        t["records"], log = record_buffer(gpu, state, gpu.md.HAMILTONIAN_RECORD)
+        self.h = [gpu.md._args(gpu.md._HamiltonianArgs, n=self.n, replicas=self.R, tether_part=part, log=log,
+                               log_capacity=state["log_capacity"], seed=hr.EXCHANGE_SEED, **words) for part in self.parts]
         gpu.torch.cuda.synchronize()
 
     def upload(self, state):
@@ -88,11 +58,7 @@ class Device:
         out = {key: val for key, val in self.base.items() if not isinstance(val, (np.ndarray, list))}
         out.update({key: val.cpu().numpy().copy() for key, val in self.t.items()})
         out["parts"] = [p.cpu().numpy().copy() for p in self.parts]
-        size = self.gpu.md.HAMILTONIAN_RECORD.itemsize
-        raw = out["records"]
-        out["guards"] = np.concatenate([raw[:_GUARD * size], raw[-_GUARD * size:]])
-        out["records"] = raw[_GUARD * size:-_GUARD * size].view(self.gpu.md.HAMILTONIAN_RECORD).copy()
-        return out
+        return split_records(out, self.gpu.md.HAMILTONIAN_RECORD)
 
     def attempt(self, part, h=_OWN):
         torch = self.gpu.torch
@@ -231,13 +197,7 @@ def test_bad_arguments_are_refused_and_touch_nothing(gpu):
     dev = Device(gpu, hr.energies(hr.hamiltonian_state(65, 2, first_attempt=hr.FIRST_ATTEMPT + 1), 0, 0))
     before = dev.read()
     for fields in (None, dict(n=0), dict(replicas=0), dict(replicas=17)):
-        h = None
-        if fields is not None:
-            h = type(dev.h[0]).from_buffer_copy(dev.h[0])
-            for key, val in fields.items():
-                setattr(h, key, val)
-            h = C.byref(h)
-        assert dev.attempt(0, h=h) != 0, fields
+        assert dev.attempt(0, h=None if fields is None else altered(dev.h[0], **fields)) != 0, fields
     after = dev.read()
     for key in before:
         if key == "parts":

@@ -20,83 +20,13 @@ import pytest
 
 from tests import md_restatement as mr
 from tests.gpu_helpers import TIGHT, energy_close
+from tests.md_kernel_harness import CASES, Device, Part, _bits, _note, _same, _up, altered, gpu, record_buffer, split_records  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LANGEVIN, VERLET = mr.LANGEVIN, mr.VERLET
-_F64 = ("x", "v", "f", "x0", "hdt_m", "mass", "kT", "energy", "acc", "log_pe", "log_ke", "last")
 _ENERGIES = ("last", "log_pe", "log_ke")
 _EXACT = ("x0", "hdt_m", "mass", "kT", "seeds", "step", "energy", "acc", "done")
-
-
-@pytest.fixture(scope="module")
-def gpu(gpu_required):
-    torch = pytest.importorskip("torch")
-    from openmm_agbnp_plugin_amd import md
-    return types.SimpleNamespace(torch=torch, md=md, lib=md._md_lib(), dev=torch.device("cuda:0"))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _up(gpu, a):
-    return gpu.torch.from_numpy(np.ascontiguousarray(a).copy()).to(gpu.dev).contiguous()
-
-
-_OWN = object()  # Device.launch: the device's own argument struct
-
-
-class Device:
-    """A restatement state as device tensors, and the argument struct over them."""
-
-    def __init__(self, gpu, state):
-        self.gpu, self.base = gpu, state
-        self.R, self.n = state["x"].shape[:2]
-        t = {key: _up(gpu, state[key]) for key in _F64}
-        t["seeds"] = _up(gpu, state["seeds"].view(np.int64))
-        t["done"] = _up(gpu, state["done"].view(np.int32))
-        t["step"] = _up(gpu, state["step"])
-        self.t, self.parts = t, [_up(gpu, p) for p in state["parts"]]
-        p = lambda name: t[name].data_ptr()  # noqa: E731
-        self.g = gpu.md._GroupArgs(self.n, self.R, p("x"), p("v"), p("f"), p("x0"), p("hdt_m"), p("mass"), p("kT"), p("seeds"),
-                                   state["c1"], state["dt"], state["k"], p("energy"), p("acc"), p("done"), p("log_pe"), p("log_ke"),
-                                   p("step"), state["capacity"], p("last"))
-        gpu.torch.cuda.synchronize()
-
-    def read(self):
-        self.gpu.torch.cuda.synchronize()
-        out = {key: val for key, val in self.base.items() if not isinstance(val, (np.ndarray, list))}
-        out.update({key: val.cpu().numpy().copy() for key, val in self.t.items()})
-        out["seeds"], out["done"] = out["seeds"].view(np.uint64), out["done"].view(np.uint32)
-        out["parts"] = [p.cpu().numpy().copy() for p in self.parts]
-        return out
-
-    def upload(self, key, a):
-        self.t[key].copy_(self.gpu.torch.from_numpy(np.ascontiguousarray(a)))
-
-    def launch(self, name, *args, g=_OWN):
-        """One entry point on the current stream, waited for; returns its code."""
-        torch = self.gpu.torch
-        torch.cuda.synchronize()
-        args = [self.parts[a].data_ptr() if isinstance(a, Part) else a for a in args]
-        rc = getattr(self.gpu.lib, "agbnp_md_group_" + name)(C.byref(self.g) if g is _OWN else g, *args,
-                                                              torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        return rc
-
-
-class Part(int):
-    """The index of a partial buffer among a launch's arguments."""
-
-
-def _note(worst, key, value):
-    worst[key] = max(worst.get(key, 0.0), float(value))
 
 
 def _energies_close(what, before, after, want, worst):
@@ -158,7 +88,6 @@ def _check_back(what, before, after):
         assert _same(after[key][R * cap:], before[key][R * cap:]), f"{what}: the tail of {key}"
 
 
-CASES = [(1, 1), (1, 16), (63, 2), (64, 3), (65, 2), (255, 1), (256, 2), (257, 3), (513, 16)]
 SEQUENCES = [(kind, n, R) for kind in (LANGEVIN, VERLET) for n, R in CASES] + [(VERLET, 65537, 2)]  # (257 blocks per replica)
 
 
@@ -329,12 +258,6 @@ def test_bad_arguments_are_refused_and_touch_nothing(gpu):
     ex.upload_energies(np.array([-1000.0, -990.0]))
     before, ex_before = dev.read(), ex.read()
 
-    def altered(struct, **fields):
-        out = type(struct).from_buffer_copy(struct)
-        for key, val in fields.items():
-            setattr(out, key, val)
-        return C.byref(out)
-
     for fields in (None, dict(n=0), dict(replicas=0), dict(replicas=17)):
         g = None if fields is None else altered(dev.g, **fields)
         assert dev.launch("tethers", Part(0), g=g) != 0, fields
@@ -359,27 +282,16 @@ def test_bad_arguments_are_refused_and_touch_nothing(gpu):
 
 # ---- the exchange kernels alone ------------------------------------------------------------------------------------------------------
 
-_GUARD = 16  # records of 0xFF in front of and behind the record buffer, which must stay 0xFF
-
-
 class Exchange:
-    """The exchange's words as device tensors.  The records of attempt a have fixed places in the log that grow with a, and the
-    runs start at a = 2^32 - 3: the log pointer handed over is the buffer's address minus `record_base` records, so that the
-    places of this run's attempts are the buffer's 0, 1, ...; log_capacity is a log place as well, so the kernel refuses every
-    place behind the buffer's share of the log (and forms no address in front of it: the places of a run only grow)."""
+    """The exchange's words as device tensors, the records in a `record_buffer`."""
 
     def __init__(self, gpu, state):
         self.gpu, self.base = gpu, state
         self.R, self.n = state["v"].shape[:2]
-        size = gpu.md.EXCHANGE_RECORD.itemsize
-        t = {key: _up(gpu, state[key]) for key in ("v", "kT", "rung_of_replica", "replica_at_rung", "last", "step", "attempts", "scale")}
-        guard = np.full(_GUARD * size, 0xFF, dtype=np.uint8)
-        t["records"] = _up(gpu, np.concatenate([guard, state["records"].view(np.uint8), guard]))
-        self.t = t
-        p = lambda name: t[name].data_ptr()  # noqa: E731
-        log = (p("records") + (_GUARD - state["record_base"]) * size) & 0xFFFFFFFFFFFFFFFF
-        self.e = gpu.md._ExchangeArgs(self.n, self.R, p("v"), p("kT"), p("rung_of_replica"), p("replica_at_rung"), p("last"), p("step"),
-                                      p("attempts"), p("scale"), log, state["log_capacity"], mr.EXCHANGE_SEED)
+        self.t = t = {key: _up(gpu, state[key]) for key in ("v", "kT", "rung_of_replica", "replica_at_rung", "last", "step", "attempts", "scale")}
+        t["records"], log = record_buffer(gpu, state, gpu.md.EXCHANGE_RECORD)
+        self.e = gpu.md._args(gpu.md._ExchangeArgs, n=self.n, replicas=self.R, log=log, log_capacity=state["log_capacity"],
+                              seed=mr.EXCHANGE_SEED, **{key: val for key, val in t.items() if key != "records"})
         gpu.torch.cuda.synchronize()
 
     def upload_energies(self, u):
@@ -391,11 +303,7 @@ class Exchange:
         self.gpu.torch.cuda.synchronize()
         out = {key: val for key, val in self.base.items() if not isinstance(val, np.ndarray)}
         out.update({key: val.cpu().numpy().copy() for key, val in self.t.items()})
-        size = self.gpu.md.EXCHANGE_RECORD.itemsize
-        raw = out["records"]
-        out["guards"] = np.concatenate([raw[:_GUARD * size], raw[-_GUARD * size:]])
-        out["records"] = raw[_GUARD * size:-_GUARD * size].view(self.gpu.md.EXCHANGE_RECORD).copy()
-        return out
+        return split_records(out, self.gpu.md.EXCHANGE_RECORD)
 
     def attempt(self):
         torch = self.gpu.torch

@@ -5,24 +5,9 @@ import pytest
 
 from openmm_agbnp_plugin_amd import md
 from tests import md_restatement as mr
+from tests.md_kernel_harness import assert_same_state, same_bits
 
 LD = np.longdouble
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def assert_same_state(a, b):
-    assert a.keys() == b.keys()
-    for key in a:
-        if key == "parts":
-            assert all(_same_bits(p, q) for p, q in zip(a[key], b[key])), key
-        elif isinstance(a[key], np.ndarray):
-            assert _same_bits(a[key], b[key]), key
-        else:
-            assert a[key] == b[key], key
 
 
 @pytest.mark.parametrize("kind", [mr.LANGEVIN, mr.VERLET])
@@ -38,12 +23,12 @@ def test_mid_is_post_then_pre(kind):
         one = mr.mid(state, kind, old, new)
         two = mr.pre(mr.post(state, old), kind, new)
         assert_same_state(one, two)
-        assert not _same_bits(one["x"], state["x"]) and list(one["step"]) == [s + 1 for s in state["step"]]
+        assert not same_bits(one["x"], state["x"]) and list(one["step"]) == [s + 1 for s in state["step"]]
         state = one
     # the log of 8: replica 0 wrote slots 5, 6, 7; replica 1 slot 7 and was refused twice; replica 2 never wrote
     written = ~np.isnan(state["log_pe"])
     assert list(np.flatnonzero(written)) == [5, 6, 7, 8 + 7]
-    assert _same_bits(np.isnan(state["log_ke"]), ~written)
+    assert same_bits(np.isnan(state["log_ke"]), ~written)
 
 
 def test_a_function_leaves_its_argument_alone():
@@ -135,14 +120,22 @@ def test_the_exchange_inputs_are_fit_for_purpose(R, records, accepted):
     assert np.array_equal(state["kT"], (md.KB * 300.0 * 1.05 ** np.arange(R))[state["rung_of_replica"]])
 
 
+def test_the_drivers_log_places_are_the_restatements():
+    """md.exchange_places against the restatement's own copy of the formula: R = 1 (no pair), 2 (none at odd attempts), odd and
+    even R up to a full group; the first attempts and those around 2^32, where the attempt number outgrows a 32-bit word."""
+    for R in (1, 2, 3, 5, 16):
+        for a in list(range(10)) + list(range((1 << 32) - 3, (1 << 32) + 4)):
+            assert md.exchange_places(a, R) == mr.exchange_places(a, R), (a, R)
+
+
 def test_a_truncated_exchange_log_keeps_the_decisions():
     """log_capacity 40 records over a buffer of 160 at R = 5: the first 40 records are the full run's, the rest stays 0xFF, and
     temperatures and rungs end where the full run's end."""
     full, cut = _exchange_run(5), _exchange_run(5, log_capacity=40, buffer=160)
-    assert _same_bits(cut["records"][:40], full["records"][:40])
+    assert same_bits(cut["records"][:40], full["records"][:40])
     assert set(cut["records"][40:].tobytes()) == {0xFF}
     for key in ("kT", "rung_of_replica", "replica_at_rung", "attempts", "v"):
-        assert _same_bits(cut[key], full[key]), key
+        assert same_bits(cut[key], full[key]), key
 
 
 def test_one_replica_has_nobody_to_exchange_with():
