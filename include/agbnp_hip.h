@@ -281,7 +281,15 @@ int agbnp_hip_wait_verdict(const agbnp_hip_context* ctx, int evaluations, double
 /* Changes whenever kernel arguments that a captured HIP graph of agbnp_hip_execute_device has frozen go stale:
  * after a finish() that raised the capacity variant or grew the scratch pools.  A caller that replays a graph
  * compares the value at capture time with the current one after every finish() and re-captures on a difference.
- * agbnp_hip_update_parameters() does NOT change it: parameters are rewritten in place at unchanged addresses. */
+ * agbnp_hip_update_parameters() does NOT change it: parameters are rewritten in place at unchanged addresses.
+ * Mixing entry points invalidates captured graphs (five-launch mode): the tree launch finds a work item's root through words
+ * that hold the root's SLOT in the context's order for agbnp_hip_execute_openmm and its atom index for
+ * agbnp_hip_execute_device / _host, rewritten for whichever entry point enqueued last.  A graph has frozen the kernel that
+ * reads them one way, so the value also changes whenever those words change their kind: an evaluation through the other
+ * entry point (eager or captured), a reordered OpenMM context, a withheld evaluation of a context that runs through
+ * agbnp_hip_execute_openmm (the repeat's packing is laid down by the host).  Compare it after every call that enqueues through
+ * another entry point as well, BEFORE the next replay: nothing on the device catches a stale replay (slots and atom indices
+ * are both below N), its forces are simply wrong.  Read the value to keep AFTER the capture has ended. */
 unsigned agbnp_hip_generation(const agbnp_hip_context* ctx);
 
 /* Evaluation mode (default 0 = the Reference platform's semantics: the descreening sums reach as far as the tables,

@@ -324,7 +324,8 @@ class HipCalcAGBNPForceKernel:
         return [int(k) for k in idx if k >= 0]
 
     def generation(self):
-        """Changes when a captured HIP graph of execute_device has gone stale (capacity variant raised)."""
+        """Changes when a captured HIP graph of this context has gone stale (capacity variant raised; an evaluation through the
+        other device-resident entry point than the graph's: include/agbnp_hip.h)."""
         self._need()
         return int(_lib.load().agbnp_hip_generation(self._h))
 

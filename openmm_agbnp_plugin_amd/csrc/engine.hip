@@ -252,7 +252,8 @@ struct agbnp_hip_context {
   DevBuf<int> d_hslot;
   bool order_valid = false;
   int row_atoms_kind = 0;       // five-launch mode: what d_row_atoms holds for the packing in use -- 0 atom indices (the caller's
-                                // [3n] positions), 1 slots of an OpenMM context's order (posq), -1 stale (the context reordered)
+                                // [3n] positions), 1 slots of an OpenMM context's order (posq), -1 stale (the context reordered);
+                                // changed through set_row_atoms_kind only
   const int* order_ptr = nullptr;
   int lazy_evals = 0;           // evaluations of execute_host since the log was last read and cleared: the FIRST entries of the
                                 // running log (a device-resident entry point that follows counts on from there; nothing is
@@ -940,6 +941,18 @@ bool energy_only_fast(const agbnp_hip_context* c) {
   return c->P.rows_on && !c->P.gb_rows && !c->P.single && !c->P.fast && !c->P.det;
 }
 
+// The words beside the work-slot rows change their meaning (or their contents, host upload or launch, for the other entry point): a
+// graph captured through the entry point of the old kind has frozen the cavity kernel that reads them the old way -- its next
+// replay would take slots for atom indices or the reverse, both below n, nothing faults -- so it is stale, and the generation
+// says so.  Also when the change is enqueued inside a stream capture (k_row_atoms then replays with that graph, which stays
+// right; the caller reads the generation after the capture): a graph captured EARLIER through the other entry point is stale
+// from that graph's first replay on.  Host bookkeeping only: no launch, nothing in a steady run.
+void set_row_atoms_kind(agbnp_hip_context* c, int kind) {
+  if (c->row_atoms_kind == kind) return;
+  c->row_atoms_kind = kind;
+  c->generation++;
+}
+
 bool is_capturing(hipStream_t st) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
@@ -1007,7 +1020,7 @@ int enqueue_prepare(agbnp_hip_context* c, const double* d_pos, hipStream_t st, E
     c->T.hslot = c->P.in.hslot;
     if (c->row_atoms_kind != want_kind) {
       HIP_TRY(c, launch_row_atoms(c->slot_cap, c->d_rows.p, want_kind ? c->d_hslot.p : c->d_h2a.p, c->d_row_atoms.p, st));
-      c->row_atoms_kind = want_kind;
+      set_row_atoms_kind(c, want_kind);
     }
     // (agbnp_hip_expect_jump; inside a stream capture it stays pending: a captured mask launch would repeat at every replay)
     const bool jump = c->jump_expected && !is_capturing(st);
@@ -1118,7 +1131,7 @@ int upload_identity_packing(agbnp_hip_context* c) {
     std::vector<int> atoms((size_t)kMaxItems * nslots, 0);
     for (size_t k = 0; k < nslots && c->nh > 0; k++) atoms[(size_t)kMaxItems * k] = c->h2a[std::min(k, nhp - 1) / parts];
     HIP_TRY(c, c->d_row_atoms.upload(atoms));
-    c->row_atoms_kind = 0;
+    set_row_atoms_kind(c, 0);  // (a context that came through agbnp_hip_execute_openmm: its captured graphs are stale until enqueue has rewritten the words)
   }
   HIP_TRY(c, c->d_order.upload(std::vector<int>((size_t)kMaxItems * nslots + 8, 0)));  // (the bookkeeping's working copies)
   HIP_TRY(c, c->d_ftime.upload(std::vector<int>(nslots + 1, 0)));
@@ -1414,7 +1427,7 @@ int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int po
   if (fused) {
     if (!c->order_valid || c->order_ptr != d_atom_index) {
       HIP_TRY(c, launch_order_maps(c->n, d_atom_index, c->d_a2h.p, c->d_ctx_slot.p, c->d_hslot.p, st));
-      if (c->row_atoms_kind == 1) c->row_atoms_kind = -1;  // (slots of the old order: enqueue rewrites them)
+      if (c->row_atoms_kind == 1) set_row_atoms_kind(c, -1);  // (slots of the old order: enqueue rewrites them)
       c->order_valid = true;
       c->order_ptr = d_atom_index;
     }
@@ -2176,13 +2189,22 @@ int agbnp_debug_set_packing(agbnp_hip_context* c, const int* order, int norder, 
     HIP_TRY(c, hipMemcpy(c->d_rows.p, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice));
     if (c->five) {  // (five-launch mode: the roots' atoms beside the rows)
       std::vector<int> atoms((size_t)kMaxItems * c->slot_cap, 0);
+      bool roots_exist = true;
       for (int s = 0; s < nforests; s++)
         for (int k = 0; k < kMaxItems; k++) {
           const int item = rows[slot_row_item(s, k)];
           if (item >= 0 && work_item_root(item) < c->nh) atoms[(size_t)kMaxItems * s + k] = c->h2a[work_item_root(item)];
+          if (item >= 0 && work_item_root(item) >= c->nh) roots_exist = false;
         }
       HIP_TRY(c, hipMemcpy(c->d_row_atoms.p, atoms.data(), sizeof(int) * atoms.size(), hipMemcpyHostToDevice));
-      c->row_atoms_kind = 0;
+      // (a context that runs through agbnp_hip_execute_openmm keeps its kind: the slots of the new rows' roots, as enqueue would
+      // write them -- the hook replaces a packing, it does not make captured graphs stale)
+      if (c->row_atoms_kind == 1 && roots_exist) {  // (k_row_atoms reads the map at every root it is given)
+        HIP_TRY(c, launch_row_atoms(c->slot_cap, c->d_rows.p, c->d_hslot.p, c->d_row_atoms.p, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+      } else if (c->row_atoms_kind == 1) {
+        set_row_atoms_kind(c, -1);
+      }  // (-1: enqueue rewrites them anyway)
     }
     HIP_TRY(c, hipMemcpy(c->d_forest.p + c->slot_cap + kPackForestsNext, &nforests, sizeof(int), hipMemcpyHostToDevice));
   }
