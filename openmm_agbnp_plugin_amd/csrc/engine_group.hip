@@ -1,0 +1,309 @@
+// Replica groups (engine_context.h; agbnp_hip_execute_group, group_args.h): the evaluations of several contexts on one set of launches.
+#include "engine_context.h"
+
+namespace {
+// A member shares the launches of its launch set when its evaluation is exactly the default launch sequence: the five-launch
+// mode with the host-named set, the Reference semantics and (version 1) the FP64 row form, an LDS-resident capacity variant, the
+// forces leaving with the pseudo-volume launch, no diagnostics, no profiling.  Every other member runs its own launches.
+// (An energy-only group makes no pseudo-volume launch: the condition on the forces does not apply there.)
+bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest& r) {
+  if (!c->cfg.group_launches || c->timeline.enabled || !energy_only_fast(c)) return false;
+  if (r.in.posq || r.omm.force_fixed || c->P.five != 1) return false;
+  return c->version == 0 || plan.fused || r.energy_only;
+}
+
+bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
+
+// The arguments of a group call, checked before anything is launched or changed.  forces is null for an energy-only call
+// (energy_only says that this was asked for).  d_energies: the device entry points' energy words, one buffer per member, which --
+// like the force buffers [3n] -- must not overlap those of another member; the host entry points pass null.
+int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* pos, double* const* forces, bool energy_only,
+                const void* energies, double* const* d_energies, const char* who) {
+  if (!ctxs || count < 1 || count > kMaxGroup) {
+    if (ctxs && count >= 1 && ctxs[0]) ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a group has 1 to 16 members");
+    return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  }
+  for (int i = 0; i < count; i++)
+    if (!ctxs[i]) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  agbnp_hip_context* c0 = ctxs[0];
+  if (!pos || (!forces && !energy_only) || !energies) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  for (int i = 0; i < count; i++) {
+    if (ctxs[i]->device != c0->device) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": members on different devices");
+    for (int j = 0; j < i; j++)
+      if (ctxs[j] == ctxs[i]) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the same context twice");
+  }
+  for (int i = 0; i < count; i++) {
+    if (!pos[i] || (forces && !forces[i]) || (d_energies && !d_energies[i]))
+      return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    for (int j = 0; j < i && d_energies; j++) {
+      const size_t ni = 3 * (size_t)ctxs[i]->n, nj = 3 * (size_t)ctxs[j]->n;
+      bool clash = spans_overlap(d_energies[i], 1, d_energies[j], 1);
+      if (forces)
+        clash = clash || spans_overlap(forces[i], ni, forces[j], nj) || spans_overlap(forces[i], ni, d_energies[j], 1) ||
+                spans_overlap(d_energies[i], 1, forces[j], nj);
+      if (clash)
+        return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                        std::string(who) + (forces ? ": output buffers of two members overlap" : ": energy words of two members overlap"));
+    }
+  }
+  return AGBNP_HIP_OK;
+}
+
+// One launch per stage for the members set[0..m) of a launch set (same version, capacity variant and far-strip test; one kind of
+// request).  Energy-only (agbnp_hip_energy_group): version 1 FOUR launches -- cavity, Born rows, the GB stage's energy-only
+// instantiation, the three role workgroups per member --, version 0 the cavity launch and the output launch in its force-less
+// shape.  Both kinds of call build the SAME argument block for a member's parity (the block holds no output pointer, and what
+// the energy-only launches read of it a full call fills too), so a run that mixes them rewrites nothing.
+int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, const EvalRequest* reqs) {
+  const bool energy_only = reqs[set[0]].energy_only;
+  const hipStream_t st = reqs[set[0]].stream;
+  agbnp_hip_context* const c0 = ctxs[set[0]];
+  const int version = c0->version, variant = c0->variant;
+  // version 1: cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes (energy-only: cavity, Born rows, GB tiles, roles); 0: cavity, outputs
+  const int stages = version == 1 ? (energy_only ? 4 : 5) : 2;
+  GroupLaunch G[5];
+  GroupOutputs out;
+  std::memset(G, 0, sizeof(G));
+  std::memset(&out, 0, sizeof(out));
+  size_t lds[5] = {tree_variant_lds_bytes(variant), 0, 0, 0, tree_variant_replay_bytes(variant)};
+  for (int k = 0; k < m; k++) {
+    const int i = set[k];
+    agbnp_hip_context* const c = ctxs[i];
+    const EvalPlan& plan = plans[i];
+    // (the block's copy carries no force pointer; an energy-only set makes no pseudo-volume launch: no force target at all)
+    if (version == 1) set_outputs(c, energy_only ? nullptr : reqs[i].force, true);
+    GroupMemberArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.P = c->P;
+    a.T = c->T;
+    a.T.out.forest_blocks = plan.tree_grid;
+    a.T.out.force = nullptr;  // (the caller's outputs travel in the launch argument: the block stays what it was)
+    a.components = c->d_components.p;
+    a.tree_blocks = plan.tree_grid;
+    a.pseudo_blocks = version == 1 ? tree_pseudo_grid(variant, kGlobalGrid, plan.tree_grid, a.T) : 0;
+    // the member's grids and LDS exactly as its own launches would take them (enqueue_launch): from pair_launch_shape and the
+    // tree_*_grid functions, which size those too
+    const PairLaunchShape sh = pair_launch_shape(c->P, version);
+    if (version == 1) {
+      a.born_role = sh.born_mask_from;
+      a.chain_role = (int)sh.chain_lds;
+    } else {
+      a.out_role_bytes = sh.out_masks.role_bytes;
+      a.out_mask_from = sh.out_masks.mask_from;
+    }
+    // the block of this evaluation's set, rewritten in stream order where it changed
+    const int p = (c->five_evals - 1) & 1;
+    if (c->d_group.p == nullptr) HIP_TRY(c, c->d_group.alloc(2));
+    if (!c->group_valid[p] || std::memcmp(&c->group_written[p], &a, sizeof(a)) != 0) {
+      HIP_TRY(c, launch_group_put(a, c->d_group.p + p, st));
+      std::memcpy(&c->group_written[p], &a, sizeof(a));
+      c->group_valid[p] = true;
+      c->group_block_writes++;
+    }
+    const unsigned long long addr = (unsigned long long)(uintptr_t)(c->d_group.p + p);
+    // (energy-only: the roles launch in place of the chain-rule launch; version 0: the output launch in its force-less shape)
+    const int cavity_blocks = tree_five_grid(plan.tree_grid, c->P);
+    const int grid1[5] = {cavity_blocks, sh.born_blocks, sh.gb_tile_blocks, energy_only ? sh.role_blocks : sh.chain_blocks, a.pseudo_blocks};
+    const int grid0[2] = {cavity_blocks, energy_only ? sh.out_energy.blocks : sh.out_masks.blocks};
+    for (int s = 0; s < stages; s++) {
+      G[s].first[k + 1] = G[s].first[k] + (version == 1 ? grid1[s] : grid0[s]);
+      G[s].args[k] = addr;
+    }
+    out.force[k] = energy_only ? 0ull : (unsigned long long)(uintptr_t)reqs[i].force;
+    out.energy[k] = (unsigned long long)(uintptr_t)reqs[i].energy;
+    if (version == 1) {
+      lds[1] = std::max(lds[1], sh.born_lds);
+      lds[3] = std::max(lds[3], sh.chain_lds);
+    } else {
+      lds[1] = std::max(lds[1], (size_t)sh.out_masks.role_bytes);
+    }
+    c->group_members = m;
+    c->last_kind = energy_only ? 1 : 0;
+  }
+  for (int s = 0; s < stages; s++) G[s].count = m;
+  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st));
+  if (version == 0) {
+    if (energy_only)
+      HIP_TRY(c0, launch_group_outputs_energy(G[1], out, lds[1], st));
+    else
+      HIP_TRY(c0, launch_group_outputs(G[1], out, lds[1], st));
+    return AGBNP_HIP_OK;
+  }
+  HIP_TRY(c0, launch_group_born_rows(G[1], lds[1], st));
+  if (energy_only) {
+    HIP_TRY(c0, launch_group_gb_energy(c0->P.gb_far, G[2], st));
+    HIP_TRY(c0, launch_group_energy_roles(G[3], out, lds[3], st));
+    return AGBNP_HIP_OK;
+  }
+  HIP_TRY(c0, launch_group_gb(c0->P.gb_far, G[2], st));
+  HIP_TRY(c0, launch_group_chain_rows(G[3], out, lds[3], st));
+  HIP_TRY(c0, launch_group_pseudo(variant, G[4], out, lds[4], st));
+  return AGBNP_HIP_OK;
+}
+
+// every member's evaluation (one request each, all of one kind and on one stream): the per-evaluation host logic of each, then one
+// launch per stage and launch set, then the members that run alone.  When something fails, the members whose launches were not
+// reached get back the counts their enqueue_prepare advanced (enqueue index, five-launch set parity), so that host and device keep
+// counting alike; a member whose launches failed half-way is in the state a failed agbnp_hip_execute_device leaves
+// (AGBNP_HIP_ERR_DEVICE: recreate it).  A member that does not share runs what its own entry point would run for its request.
+int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* reqs) {
+  const Unbind unbind{ctxs, count};
+  EvalPlan plans[kMaxGroup];
+  bool shares[kMaxGroup], done[kMaxGroup], launched[kMaxGroup] = {};
+  int was_enqueued[kMaxGroup], was_five_evals[kMaxGroup], prepared = 0;
+  auto undo = [&](int rc) {
+    for (int i = 0; i < prepared; i++)
+      if (!launched[i]) ctxs[i]->enqueued = was_enqueued[i], ctxs[i]->five_evals = was_five_evals[i];
+    return rc;
+  };
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    was_enqueued[i] = c->enqueued;
+    was_five_evals[i] = c->five_evals;
+    const int rc = enqueue_prepare(c, reqs[i], plans[i]);
+    prepared = i + 1;
+    if (rc != AGBNP_HIP_OK) return undo(rc);
+    shares[i] = group_shares(c, plans[i], reqs[i]);
+    done[i] = !shares[i];
+  }
+  for (int i = 0; i < count; i++) {
+    if (done[i]) continue;
+    const agbnp_hip_context* a = ctxs[i];
+    int set[kMaxGroup], m = 0;
+    for (int j = i; j < count; j++) {
+      const agbnp_hip_context* b = ctxs[j];
+      if (!done[j] && b->version == a->version && b->variant == a->variant && b->P.gb_far == a->P.gb_far) set[m++] = j, done[j] = true;
+    }
+    for (int k = 0; k < m; k++) launched[set[k]] = true;
+    // (a launch set of one makes the member's own launches: the same kernels without the look-up of its argument block, which
+    // costs a dependent scalar load in front of every launch's first use of an argument)
+    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, reqs) : enqueue_launch(ctxs[set[0]], plans[set[0]], reqs[set[0]]);
+    if (rc != AGBNP_HIP_OK) return undo(rc);
+    if (m == 1) ctxs[set[0]]->group_members = 1;
+  }
+  for (int i = 0; i < count; i++) {
+    if (shares[i]) continue;
+    launched[i] = true;
+    const int rc = enqueue_launch(ctxs[i], plans[i], reqs[i]);
+    if (rc != AGBNP_HIP_OK) return undo(rc);
+  }
+  return AGBNP_HIP_OK;
+}
+
+// joins a member's own stream and the group's: `to` waits for what is on `from` now
+int join_streams(agbnp_hip_context* c, hipStream_t from, hipStream_t to) {
+  if (from == to) return AGBNP_HIP_OK;
+  if (!c->group_event) HIP_TRY(c, hipEventCreateWithFlags(&c->group_event, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->group_event, from));
+  HIP_TRY(c, hipStreamWaitEvent(to, c->group_event, 0));
+  return AGBNP_HIP_OK;
+}
+
+// agbnp_hip_execute_group and -- energy_only, d_forces null: for every member what agbnp_hip_energy_device would do, the sharing
+// members on FOUR (version 0: two) launches per launch set, nothing written to a force buffer of a caller -- agbnp_hip_energy_group
+int group_device(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces, bool energy_only,
+                 double* const* d_energies, void* stream, const char* who) {
+  int rc = check_group(ctxs, count, d_positions, d_forces, energy_only, d_energies, d_energies, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  agbnp_hip_context* const c0 = ctxs[0];
+  hipStream_t st;
+  rc = enter(c0, stream, &st);
+  if (rc != AGBNP_HIP_OK) return rc;
+  if (is_capturing(st))
+    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream is being captured; " +
+                                                        (energy_only ? "groups and energy-only evaluations" : "groups") + " are not captured into graphs");
+  EvalRequest reqs[kMaxGroup];
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    HIP_TRY(c, hipSetDevice(c->device));
+    // (NULL: the first member's own stream, which no caller can name -- it is not noted as a caller stream; every member's own
+    // stream is joined to it on both sides instead, so that the member's agbnp_hip_finish(NULL) drains the group's work)
+    note_stream(c, stream);
+    if (!stream) {
+      rc = join_streams(c, c->stream, st);
+      if (rc != AGBNP_HIP_OK) return rc;
+    }
+    reqs[i].pos = d_positions[i];
+    reqs[i].force = energy_only ? c->d_eo_force.p : d_forces[i];
+    reqs[i].energy = d_energies[i];
+    reqs[i].stream = st;
+    reqs[i].energy_only = energy_only;
+  }
+  rc = group_enqueue(ctxs, count, reqs);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count && !stream; i++) {
+    rc = join_streams(ctxs[i], st, ctxs[i]->stream);
+    if (rc != AGBNP_HIP_OK) return rc;
+  }
+  return AGBNP_HIP_OK;
+}
+
+// agbnp_hip_execute_group_host and -- energy_only, forces null -- agbnp_hip_energy_group_host
+int group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces, bool energy_only,
+               double* energies, const char* who) {
+  int rc = check_group(ctxs, count, positions, forces, energy_only, energies, nullptr, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  const hipStream_t st = ctxs[0]->stream;
+  EvalRequest reqs[kMaxGroup];
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = carry_unfinished(c);  // (every member's streams are idle from here on)
+    if (rc != AGBNP_HIP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
+    reqs[i].pos = c->d_pos_in.p;
+    reqs[i].force = energy_only ? c->d_eo_force.p : c->d_force_tmp.p;
+    reqs[i].energy = c->d_force_tmp.p + 3 * (size_t)c->n;
+    reqs[i].stream = st;
+    reqs[i].energy_only = energy_only;
+    // (cleared by the cavity launch's trailing workgroups, as in agbnp_hip_execute_host; the staging buffer's energy word with it)
+    reqs[i].zero_out = c->d_force_tmp.p;
+  }
+  rc = group_enqueue(ctxs, count, reqs);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    int repeat = 0;
+    rc = harvest(c, &repeat, st);  // (waits for the group's stream)
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (repeat) {  // withheld: repeated alone, as agbnp_hip_execute_host / agbnp_hip_energy_host repeats
+      rc = host_evaluation(c, positions[i], energy_only ? nullptr : forces[i], &energies[i]);
+      if (rc != AGBNP_HIP_OK) return rc;
+      continue;
+    }
+    if (energy_only) {
+      HIP_TRY(c, hipMemcpy(&energies[i], reqs[i].energy, sizeof(double), hipMemcpyDeviceToHost));
+      continue;
+    }
+    const size_t n3 = 3 * (size_t)c->n;
+    c->h_force_tmp.resize(n3 + 1);
+    HIP_TRY(c, hipMemcpy(c->h_force_tmp.data(), c->d_force_tmp.p, sizeof(double) * (n3 + 1), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n3; k++) forces[i][k] += c->h_force_tmp[k];
+    energies[i] = c->h_force_tmp[n3];
+  }
+  return AGBNP_HIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,
+                            double* const* d_energies, void* stream) {
+  return group_device(ctxs, count, d_positions, d_forces, false, d_energies, stream, "agbnp_hip_execute_group");
+}
+
+int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces,
+                                 double* energies) {
+  return group_host(ctxs, count, positions, forces, false, energies, "agbnp_hip_execute_group_host");
+}
+
+int agbnp_hip_energy_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_energies,
+                           void* stream) {
+  return group_device(ctxs, count, d_positions, nullptr, true, d_energies, stream, "agbnp_hip_energy_group");
+}
+
+int agbnp_hip_energy_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* energies) {
+  return group_host(ctxs, count, positions, nullptr, true, energies, "agbnp_hip_energy_group_host");
+}
+
+}  // extern "C"

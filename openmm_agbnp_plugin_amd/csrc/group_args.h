@@ -1,4 +1,4 @@
-// Replica groups (agbnp_hip_execute_group, engine.hip): the launches that several contexts share.
+// Replica groups (agbnp_hip_execute_group, engine_group.hip): the launches that several contexts share.
 //
 // Every context of a launch set keeps exactly the grid it would launch alone; the grids are laid side by side, and a
 // workgroup finds its member by its number (GroupLaunch::first) and runs the member's kernel body with its number inside

@@ -1,4 +1,4 @@
-// Replica groups (group_args.h, engine.hip agbnp_hip_execute_group): the kernels and launchers of the launches that several
+// Replica groups (group_args.h, engine_group.hip agbnp_hip_execute_group): the kernels and launchers of the launches that several
 // contexts share.  The kernel bodies are those of pair_bodies.h and tree_bodies.h, which this translation unit reads with
 // the switch below set (group_args.h): k_gb_tiles, k_rows, k_outputs, k_tree_cavity_five and k_tree_pseudo are then device functions that take the
 // workgroup's number inside a member's grid, and the kernels below call them.  A translation unit of its own, so that the
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_group_pseudo(
   k_tree_pseudo<NCAP, ACAP, BS, false, PIPE, false>(A, (unsigned)blk, (unsigned)g.pseudo_blocks);
 }
 
-// replica groups: one launch per stage for every member of a launch set (engine.hip, agbnp_hip_execute_group)
+// replica groups: one launch per stage for every member of a launch set (engine_group.hip, agbnp_hip_execute_group)
 template <class K, class... Args>
 static hipError_t launch_group(K kernel, const GroupLaunch& G, size_t lds, hipStream_t st, const Args&... args) {
   if (lds > 48 * 1024) {

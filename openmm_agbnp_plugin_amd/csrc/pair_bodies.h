@@ -815,7 +815,7 @@ __device__ void dealing_role(const PairArgs& P, char* scratch, int scratch_bytes
       int4 a0, a1;
       int at[kMaxItems];
       // (an OpenMM context's posq: the root's SLOT in the context's order -- the next evaluation is taken to come through the same
-      // entry point; the host rewrites the words when it does not, engine.hip sync_row_atoms)
+      // entry point; the host rewrites the words when it does not, engine_eval.hip enqueue_prepare)
       const int* __restrict__ where = P.in.posq ? P.in.hslot : P.h2a;
 #pragma unroll
       for (int k = 0; k < kMaxItems; k++) at[k] = it[k] >= 0 ? where[work_item_root(it[k])] : 0;

@@ -101,7 +101,7 @@ struct PairArgs {
   int split_fit;           // 1: subtrees whose items would not fit the store are shared among up to four items (AGBNP_HIP_SPLIT_FIT=0: off)
   int round_permille;      // share of the resident workgroups that the packing fills (tuning knob, default 1000: every resident slot)
   int tree_slot_cap;       // work slots the tree kernels are launched with (>= subtrees; bounds the sharing of subtrees)
-  // ---- five-launch mode (the default for version 1; AGBNP_HIP_FIVE_LAUNCHES=0 switches it off; engine.hip): no k_prep launch.  The tree accumulators, the
+  // ---- five-launch mode (the default for version 1; AGBNP_HIP_FIVE_LAUNCHES=0 switches it off; engine_context.h): no k_prep launch.  The tree accumulators, the
   //      subtree shapes and the per-evaluation status words exist TWICE and alternate with the evaluation's parity; the
   //      trailing workgroups of the cavity launch (prep_role.h) clear the other set for the next evaluation
   int five;                // 0: six launches.  1: that mode, the HOST names the evaluation's set (eager launches: the pointers of this
@@ -113,7 +113,7 @@ struct PairArgs {
   // (rebase_for_parity) -- the launches in front of the GB launch by epoch & 1, the launches behind it by (epoch + 1) & 1; the
   // GB launch's own workgroups other than the role touch nothing that exists twice.  It costs each launch one more cold scalar
   // load (+0.5-1 us per evaluation of 1dwc, A/B on one box), which is why eager contexts let the host do it.
-  int* epoch;              // (the pair launches' copy; the tree launches read epoch_tree: engine.hip, apply_parity)
+  int* epoch;              // (the pair launches' copy; the tree launches read epoch_tree: engine_setup.hip, allocate_work)
   int* epoch_tree;
   size_t table_doubles;    // doubles from one heavy-atom table to the other
   size_t sizes_stride;     // shapes from one array to the other
@@ -128,7 +128,7 @@ struct PairArgs {
                            // caller's positions itself in that mode); written with the rows
   int* status;             // [kStatTotalWords]: the STICKY words (from kStatEvalSeq on) are addressed through this one,
   int* estatus;            // the words of ONE evaluation ([0, kStatEvalWords)) through this one: the same array -- or, in the
-                           // five-launch mode, the block of the evaluation's parity (engine.hip)
+                           // five-launch mode, the block of the evaluation's parity (engine_setup.hip, apply_parity)
   volatile int* host_status;  // pinned host memory, mapped: [0] evaluations completed since the last finish, [1] of them withheld --
                               // what agbnp_hip_poll reads without touching the device (written by the energy role)
   // ---- pair-stage intermediates
@@ -256,7 +256,7 @@ PairLaunchShape pair_launch_shape(const PairArgs& P, int version);
 hipError_t launch_prep(const PairArgs& P, hipStream_t st, Timeline* tl);
 hipError_t launch_masks(const PairArgs& P, hipStream_t st, Timeline* tl);  // five-launch mode: the neighbour masks alone (with their skin) + their reference positions
 hipError_t launch_pair_stages(const PairArgs& P, const PairLaunchShape& S, double* energy_out, double* components, hipStream_t st, Timeline* tl);
-// energy-only evaluations (engine.hip, agbnp_hip_energy_*): the launches behind the cavity launch, no force launch among them
+// energy-only evaluations (engine_eval.hip, agbnp_hip_energy_*): the launches behind the cavity launch, no force launch among them
 hipError_t launch_energy_only_stages(const PairArgs& P, const PairLaunchShape& S, int version, double* energy_out, double* components,
                                      hipStream_t st, Timeline* tl);
 hipError_t launch_outputs(const PairArgs& P, const OutputShape& O, int version, double* force_out, double* energy_out, double* components,

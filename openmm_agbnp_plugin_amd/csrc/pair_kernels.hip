@@ -366,7 +366,7 @@ hipError_t launch_prep(const PairArgs& P, hipStream_t st, Timeline* tl) {
 }
 
 // Grids and LDS of a context's pair-stage and output launches.  Every launcher below and the replica groups' launch sets
-// (engine.hip, launch_set) take their numbers from here: a group kernel finds a member's role workgroups and mask tiles by the
+// (engine_group.hip, launch_set) take their numbers from here: a group kernel finds a member's role workgroups and mask tiles by the
 // workgroup's number inside the grid the member would launch alone (group_args.h), so the two must never be sized apart.
 PairLaunchShape pair_launch_shape(const PairArgs& P, int version) {
   PairLaunchShape s{};
@@ -461,14 +461,14 @@ hipError_t launch_pair_stages(const PairArgs& P, const PairLaunchShape& S, doubl
   return hipSuccess;
 }
 
-// The energy-only evaluation's launches behind the cavity launch (engine.hip, energy_only_fast: five-launch mode with the
+// The energy-only evaluation's launches behind the cavity launch (engine_eval.hip, energy_only_fast: five-launch mode with the
 // host-named set, Reference semantics, FP64 rows).  Version 1: the Born rows exactly as in a full evaluation (they also build the
 // chain-rule lists after a rebuild and carry the masks' renewal tiles), the GB stage's energy-only instantiation, k_energy_roles.
 // Version 0: the output launch's two role workgroups and its mask tiles, without force workgroups.
 hipError_t launch_energy_only_stages(const PairArgs& P, const PairLaunchShape& S, int version, double* energy_out, double* components,
                                      hipStream_t st, Timeline* tl) {
   if (version != 1) return launch_outputs(P, S.out_energy, version, nullptr, energy_out, components, st, tl);
-  if (!P.rows_on || P.gb_rows || P.single || P.fast || P.det || P.five != 1) return hipErrorInvalidValue;  // (engine.hip never asks)
+  if (!P.rows_on || P.gb_rows || P.single || P.fast || P.det || P.five != 1) return hipErrorInvalidValue;  // (the host engine never asks)
   AGBNP_MARK(kKBornRows);
   hipLaunchKernelGGL((k_rows<kBornRows, false, true>), dim3(S.born_blocks), dim3(64 * kRowWaves), S.born_lds, st, P, (double*)nullptr, (double*)nullptr,
                      S.born_mask_from);

@@ -385,7 +385,7 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
   }
 }
 
-// Five-launch mode (the default for version 1; engine.hip): there is no k_prep launch.  The forest workgroups read the caller's positions
+// Five-launch mode (the default for version 1; engine_context.h): there is no k_prep launch.  The forest workgroups read the caller's positions
 // themselves; the workgroups BEHIND them in the grid -- dispatched when the first forests have left, done long before the last
 // ones are -- do k_prep's per-atom work for the launches that follow (prep_role.h) and clear the other parity's tree
 // accumulators, subtree shapes and status words for the NEXT evaluation.

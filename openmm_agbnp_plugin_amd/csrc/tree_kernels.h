@@ -105,12 +105,12 @@ struct TreeArgs {
   int* status;                 // [kStatTotalWords]
   char* scratch;               // GLOBAL variant: per-workgroup slab
   size_t scratch_stride;
-  // five-launch mode (engine.hip): the tree reads the caller's positions itself -- no k_prep has put them into the table
+  // five-launch mode (engine_eval.hip): the tree reads the caller's positions itself -- no k_prep has put them into the table
   const double* pos;           // [3n] the caller's positions
   const int* row_atoms;        // [kMaxItems * slots] atom of the root of item k of work slot s (beside `rows`)
   // ... or an OpenMM context's posq (agbnp_hip_execute_openmm in the five-launch mode; the POSQ instantiations,
   // OpenCLAGBNPKernels.cpp:541-556 for the conventions): positions by the context's SLOT -- row_atoms then holds the slot of
-  // every item's root (engine.hip keeps it so), a candidate's slot comes through hslot
+  // every item's root (engine_eval.hip keeps it so), a candidate's slot comes through hslot
   const void* posq;            // [padded] double4, or float4 ...
   const float4* posq_corr;     // ... + float4 correction (mixed precision), or null
   int posq_double;

@@ -37,7 +37,7 @@ int tree_variant_wgs_per_cu(int variant) {
 }
 
 // workgroups of the five-launch mode's cavity launch: the forest workgroups, then the prep workgroups (replica groups lay the
-// grids of several contexts side by side, engine.hip)
+// grids of several contexts side by side, engine_group.hip)
 int tree_five_grid(int slots, const PairArgs& P) {
   const int work = std::max(std::max(P.n, P.nslots), (int)kStatEvalWords);
   return slots + (work + kBS - 1) / kBS;

@@ -61,9 +61,9 @@ def main():
     tmp = args.keep_asm or tempfile.mkdtemp(prefix="agbnp_asm_")
     os.makedirs(tmp, exist_ok=True)
     allrows = {}
-    for src in ("tree_kernels.hip", "pair_kernels.hip", "group_kernels.hip", "engine.hip"):
-        if not os.path.exists(os.path.join(CSRC, src)):
-            continue
+    # (the engine's .hip sources as csrc/Makefile lists them; a file without kernels adds no row)
+    sources = re.search(r"^SRC = (.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+    for src in (s for s in sources if s.endswith(".hip")):
         out = os.path.join(tmp, src.replace(".hip", ".s"))
         subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-o", out, src], cwd=CSRC, check=True, stderr=subprocess.DEVNULL)
         allrows.update(parse(out))

@@ -12,9 +12,9 @@ import pytest
 
 import openmm_agbnp_plugin_amd as P
 from oracle import Oracle
-from tests.gpu_helpers import TIGHT, cluster, energy_close
+from tests.gpu_helpers import TIGHT, Buffers, close, cluster, energy_close, execute_group
 from tests.gpu_helpers import five  # noqa: F401
-from tests.openmm_context import OpenMMContext, protocol_geometries
+from tests.openmm_context import ENERGY_SLOT, OpenMMContext, protocol_geometries
 from tests.test_gpu_healing import _freeze_eight_subtrees_per_forest
 
 pytestmark = pytest.mark.gpu
@@ -306,3 +306,91 @@ def test_a_long_step_and_a_reorder_are_withheld_once_and_repeat_right(gpu_requir
     assert k.finish(stream) == 0, (list(k.withheld()), int(k.scalar("overflow_kinds")))
     ctx.check(we, wf, 1, "the repeat after a reorder")
     assert int(k.scalar("launches")) == 5
+
+
+FAMILIES = ("execute_openmm", "energy_openmm", "execute_device", "energy_device", "execute", "energy", "execute_group", "energy_group",
+            "execute_group_host", "energy_group_host")
+# every family once in order, once more in another order, the first one a third time: each follows two different others
+EVERY_FAMILY_IN_TURN = FAMILIES + ("execute_device", "execute_openmm", "energy_group", "energy_openmm", "energy_group_host", "energy_device",
+                                   "execute_group", "energy", "execute_group_host", "execute", "execute_openmm")
+
+
+def test_every_entry_family_in_turn_leaves_nothing_behind(gpu_required, systems, five):
+    """What a caller asks of one evaluation -- positions, targets, energy-only, the buffer to clear first, an OpenMM context's posq
+    and planes -- must reach that evaluation's launches and no later one's.  trpcage, version 1, three contexts, the first of them
+    also behind an OpenMM context's buffers (mixed precision): the ten entry families in an irregular order in which each follows
+    at least two different others, the single-context ones on the first context, the group ones on all three, every step at fresh
+    positions.  Every result is the oracle's (TIGHT for the FP64 targets; FIXED_POINT per evaluation for the planes, through
+    OpenMMContext.check); an energy-only step leaves the caller's force buffer, or the planes, as loaded; nothing is withheld."""
+    torch = pytest.importorskip("torch")
+    sentinel, plane_sentinel = -1234.5678, 7
+    followed = {name: {a for a, b in zip(EVERY_FAMILY_IN_TURN, EVERY_FAMILY_IN_TURN[1:]) if b == name} for name in FAMILIES}
+    assert all(EVERY_FAMILY_IN_TURN.count(name) >= 2 and len(followed[name]) >= 2 for name in FAMILIES), followed
+    s = systems("trpcage")
+    assert s.n == 272
+    oracle = Oracle(*s.params(), version=1)
+    ks = [_kernel(s) for _ in range(3)]
+    ctx = OpenMMContext(torch, s.n, "mixed", oracle)
+    bufs = [Buffers(torch, s.n) for _ in ks]
+    stream = _stream(torch)
+    for step, what in enumerate(EVERY_FAMILY_IN_TURN):
+        group, energy_only = "group" in what, what.startswith("energy")
+        members = ks if group else ks[:1]
+        geoms = [s.jittered(step if m == 0 else 100 * m + step) for m in range(len(members))]
+        if "openmm" in what:
+            hi, lo, seen = ctx.host_arrays(geoms[0])
+            geoms = [seen]
+            posq, corr = torch.tensor(hi, device=ctx.dev), torch.tensor(lo, device=ctx.dev)
+            if energy_only:
+                ctx.fixed.fill_(plane_sentinel)
+        for b, g in zip(bufs, geoms):
+            b.load(g, sentinel if energy_only else 0.0)
+        torch.cuda.synchronize()
+        want = [oracle.execute(g) for g in geoms]
+        got = None  # (energy, forces or None) per member, for the families that return or accumulate FP64
+        if what == "execute_openmm":
+            ctx.enqueue(ks[0], posq, corr, stream)
+        elif what == "energy_openmm":
+            ks[0].energy_openmm(posq.data_ptr(), False, corr.data_ptr(), ctx.index.data_ptr(), ctx.padded, ctx.ebuf.data_ptr(), True,
+                                ENERGY_SLOT, stream)
+        elif what == "execute_device":
+            ks[0].execute_device(*bufs[0].ptrs(), stream)
+        elif what == "energy_device":
+            ks[0].energy_device(bufs[0].pos.data_ptr(), bufs[0].ene.data_ptr(), stream)
+        elif what == "execute":
+            f = np.zeros((s.n, 3))
+            got = [(ks[0].execute(geoms[0], f), f)]
+        elif what == "energy":
+            got = [(ks[0].energy(geoms[0]), None)]
+        elif what == "execute_group":
+            execute_group(ks, bufs, stream)
+        elif what == "energy_group":
+            P.energy_group(ks, [b.pos.data_ptr() for b in bufs], [b.ene.data_ptr() for b in bufs], stream)
+        elif what == "execute_group_host":
+            fs = [np.zeros((s.n, 3)) for _ in ks]
+            got = list(zip(P.execute_group_host(ks, geoms, fs), fs))
+        else:
+            got = [(e, None) for e in P.energy_group_host(ks, geoms)]
+        assert [k.finish(stream) for k in members] == [0] * len(members), (step, what)
+        if what == "execute_openmm":
+            ctx.check(*want[0], 1, f"step {step}, {what}")
+            continue
+        if what == "energy_openmm":
+            assert (ctx.fixed == plane_sentinel).all(), "an energy-only evaluation wrote to the fixed-point planes"
+            de = abs(ctx.energy() - want[0][0])
+            print(f"step {step}, {what}: |dE|={de:.3e}")
+            energy_close(ctx.energy(), want[0][0])
+            ctx.clear()
+            continue
+        if got is None:
+            got = [b.result() for b in bufs[: len(members)]]
+            if energy_only:
+                assert all((f == sentinel).all() for _, f in got), "an energy-only evaluation wrote to a caller's force buffer"
+                got = [(e, None) for e, _ in got]
+        for m, ((e, f), (eo, fo)) in enumerate(zip(got, want)):
+            df = 0.0 if f is None else np.abs(f - fo).max()
+            print(f"step {step}, {what}, member {m}: |dE|={abs(e - eo):.3e}  max|dF|={df:.3e}")
+            if f is None:
+                energy_close(e, eo)
+            else:
+                close(e, f, eo, fo)
