@@ -45,7 +45,7 @@ struct GroupMemberArgs {
   TreeArgs T;             // T.out: the outputs of the pseudo-volume launch (forest_blocks set)
   double* components;
   int tree_blocks;        // forest workgroups of the cavity launch (its prep workgroups follow)
-  int born_role;          // Born rows: the first mask tile (role_bytes of k_rows<kBornRows, false, true>)
+  int born_role;          // Born rows: the first mask tile (role_arg of k_rows<kBornRows, false, true>)
   int chain_role;         // chain-rule rows: the roles' LDS bytes
   int pseudo_blocks;      // workgroups of the member's pseudo-volume launch
   int out_role_bytes;     // version 0 output launch: the roles' LDS bytes

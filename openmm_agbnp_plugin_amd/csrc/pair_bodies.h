@@ -902,18 +902,26 @@ struct StripSums {
   double red[4][12][64];  // per wave: rows 0-3 block I0 {fx, fy, fz, Y}, 4-7 block I0 + 1, 8-11 block J
 };
 
-// Squared gap between the bounding box of block J and the nearer of the boxes of blocks I0, I0 + 1 (atom-order boxes of k_prep)
-__device__ __forceinline__ double strip_gap2(const PairArgs& P, int I0, int J) {
-  double gmin = 1e300;
-  for (int b = 0; b < 2; b++) {
-    double gap2 = 0.0;
-    for (int d = 0; d < 3; d++) {
-      const double g = fmax(0.0, fmax(P.abox[6 * J + d] - P.abox[6 * (I0 + b) + 3 + d], P.abox[6 * (I0 + b) + d] - P.abox[6 * J + 3 + d]));
-      gap2 += g * g;
-    }
-    gmin = fmin(gmin, gap2);
+// Squared gap between the bounding boxes of blocks I and J (box: [block][6] = {min xyz, max xyz}, as k_prep lays them down)
+__device__ __forceinline__ double box_gap2(const double* box, int I, int J) {
+  double gap2 = 0.0;
+  for (int d = 0; d < 3; d++) {
+    const double g = fmax(0.0, fmax(box[6 * J + d] - box[6 * I + 3 + d], box[6 * I + d] - box[6 * J + 3 + d]));
+    gap2 += g * g;
   }
-  return gmin;
+  return gap2;
+}
+// ... between the box of block J and the nearer of the boxes of blocks I0, I0 + 1 (atom-order boxes)
+__device__ __forceinline__ double strip_gap2(const PairArgs& P, int I0, int J) {
+  return fmin(fmin(1e300, box_gap2(P.abox, I0, J)), box_gap2(P.abox, I0 + 1, J));
+}
+// The pair energy of a workgroup of four waves (s_e: four words of LDS): a put / store pair around a barrier of the caller's
+__device__ __forceinline__ void gb_energy_put(double e, double* s_e, int lane, int wave) {
+  e = wave_sum(e);
+  if (lane == 0) s_e[wave] = e;
+}
+__device__ __forceinline__ void gb_energy_store(const double* s_e, double* out) {  // 2k times the sum, in a fixed order
+  if (threadIdx.x == 0) out[0] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
 }
 // max over the wave of the HIGH words of positive doubles (monotonic in the value): 32-bit DPP steps; lane 63 holds it
 __device__ __forceinline__ int wave_max_hi_to_lane63(int m) {
@@ -1035,28 +1043,18 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
     // pair (atom of block I0, j)
     const double dxa = xy.x - axy.x, dya = xy.y - axy.y, dza = zq.x - azq.x;
     const double d2a = fma(dza, dza, fma(dya, dya, dxa * dxa));
-    const double bba = abc.x * bj.x;
-    const double eta = exp2_nonpositive(d2a * (abc.y * bj.y));
-    const double fa = rsqrt_pos(fma(bba, eta, d2a));
     double qqa = azq.y * zq.y;
     if (kCut) qqa = d2a < P.gb_cut2 ? qqa : 0.0;
-    const double s1a = qqa * fa;
-    const double s3a = s1a * (fa * fa);
-    const double mwa = fma(-0.25, eta, 1.0) * s3a;
-    const double yta = fma(0.25, d2a, bba) * (eta * s3a);
+    const GbPairTerms<double> ta = gb_pair_terms(d2a, abc.x * bj.x, abc.y * bj.y, qqa);
+    const double mwa = ta.mw, yta = ta.ybb * ta.ets3;
     // pair (atom of block I0 + 1, j)
     const double dxc = xy.x - cxy.x, dyc = xy.y - cxy.y, dzc = zq.x - czq.x;
     const double d2c = fma(dzc, dzc, fma(dyc, dyc, dxc * dxc));
-    const double bbc = cbc.x * bj.x;
-    const double etc = exp2_nonpositive(d2c * (cbc.y * bj.y));
-    const double fc = rsqrt_pos(fma(bbc, etc, d2c));
     double qqc = czq.y * zq.y;
     if (kCut) qqc = d2c < P.gb_cut2 ? qqc : 0.0;
-    const double s1c = qqc * fc;
-    const double s3c = s1c * (fc * fc);
-    const double mwc = fma(-0.25, etc, 1.0) * s3c;
-    const double ytc = fma(0.25, d2c, bbc) * (etc * s3c);
-    e += s1a + s1c;
+    const GbPairTerms<double> tc = gb_pair_terms(d2c, cbc.x * bj.x, cbc.y * bj.y, qqc);
+    const double mwc = tc.mw, ytc = tc.ybb * tc.ets3;
+    e += ta.s1 + tc.s1;
     fxa = fma(dxa, mwa, fxa);
     fya = fma(dya, mwa, fya);
     fza = fma(dza, mwa, fza);
@@ -1077,11 +1075,9 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
   StripSums& S = *reinterpret_cast<StripSums*>(s_area);
   const int jslot = (lane + start + 16) & 63;  // whose sums the lane holds after the rotations
   if (kEnergy) {  // (the force and Y sums of the walk are dead: the compiler drops them)
-    e = wave_sum(e);
-    if (lane == 0) s_e[wave] = e;
+    gb_energy_put(e, s_e, lane, wave);
     __syncthreads();
-    if (threadIdx.x == 0) egb_out[0] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
-    return;
+    return gb_energy_store(s_e, egb_out);
   }
   S.red[wave][0][lane] = kf * fxa;
   S.red[wave][1][lane] = kf * fya;
@@ -1095,8 +1091,7 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
   S.red[wave][9][jslot] = kf * fyj;
   S.red[wave][10][jslot] = kf * fzj;
   S.red[wave][11][jslot] = yj;
-  e = wave_sum(e);
-  if (lane == 0) s_e[wave] = e;
+  gb_energy_put(e, s_e, lane, wave);
   __syncthreads();
   // thread (wave q, lane l) adds quantity q of atom l of the three blocks: rows gb_fx, gb_fy, gb_fz by atom, Y by slot
   double* __restrict__ row = gb_rows + (size_t)wave * n;
@@ -1115,7 +1110,7 @@ __device__ __forceinline__ void gb_strip(int n, int I0, int J, const double4* __
     if (ic < n) hbm_add(wave == 3 ? &P.ys[ysc] : &row[ic], quantize(fold(4 + wave), qs, det));
     if (j < n) hbm_add(wave == 3 ? &P.ys[ysj] : &row[j], quantize(fold(8 + wave), qs, det));
   }
-  if (threadIdx.x == 0) egb_out[0] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
+  gb_energy_store(s_e, egb_out);
   PAIR_STAMP(1, 3);
 }
 
@@ -1140,16 +1135,7 @@ __device__ __forceinline__ void gb_strip_f32(int n, int I0, int J, const double4
   static_assert(sizeof(StripSums) >= 128 * 16 + 128 * 8 + 128 * 16 + 128 * 8, "single-precision records fit the area of the sums");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (kCut) {  // both tiles of the strip beyond the cutoff
-    double gmin = 1e300;
-    for (int b = 0; b < 2; b++) {
-      double gap2 = 0.0;
-      for (int d = 0; d < 3; d++) {
-        const double g = fmax(0.0, fmax(P.abox[6 * J + d] - P.abox[6 * (I0 + b) + 3 + d], P.abox[6 * (I0 + b) + d] - P.abox[6 * J + 3 + d]));
-        gap2 += g * g;
-      }
-      gmin = fmin(gmin, gap2);
-    }
-    if (gmin >= P.gb_cut2) {
+    if (strip_gap2(P, I0, J) >= P.gb_cut2) {
       if (threadIdx.x == 0) egb_out[0] = 0.0;
       return;
     }
@@ -1226,8 +1212,7 @@ __device__ __forceinline__ void gb_strip_f32(int n, int I0, int J, const double4
   S.red[wave][9][jslot] = kf * (double)fyj;
   S.red[wave][10][jslot] = kf * (double)fzj;
   S.red[wave][11][jslot] = (double)yj;
-  const double e = wave_sum((double)e2.x + (double)e2.y);
-  if (lane == 0) s_e[wave] = e;
+  gb_energy_put((double)e2.x + (double)e2.y, s_e, lane, wave);
   __syncthreads();
   double* __restrict__ row = gb_rows + (size_t)wave * n;
   auto fold = [&](int r) { return (S.red[0][r][lane] + S.red[1][r][lane]) + (S.red[2][r][lane] + S.red[3][r][lane]); };
@@ -1237,7 +1222,7 @@ __device__ __forceinline__ void gb_strip_f32(int n, int I0, int J, const double4
   if (ia < n) hbm_add(wave == 3 ? &P.ys[ysa] : &row[ia], quantize(fold(wave), qs, det));
   if (ic < n) hbm_add(wave == 3 ? &P.ys[ysc] : &row[ic], quantize(fold(4 + wave), qs, det));
   if (j < n) hbm_add(wave == 3 ? &P.ys[ysj] : &row[j], quantize(fold(8 + wave), qs, det));
-  if (threadIdx.x == 0) egb_out[0] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
+  gb_energy_store(s_e, egb_out);
 }
 
 // kMasks (round 6): the instantiations of the five-launch mode where the Born stage is not the FP64 row launch that carries the
@@ -1292,12 +1277,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
   }
   const bool diag = I == J;
   if (kCut && !diag) {  // fast mode: a tile whose two blocks are further apart than the cutoff has no pair to meet
-    double gap2 = 0.0;
-    for (int d = 0; d < 3; d++) {
-      const double g = fmax(0.0, fmax(P.abox[6 * J + d] - P.abox[6 * I + 3 + d], P.abox[6 * I + d] - P.abox[6 * J + 3 + d]));
-      gap2 += g * g;
-    }
-    if (gap2 >= P.gb_cut2) {
+    if (box_gap2(P.abox, I, J) >= P.gb_cut2) {
       if (threadIdx.x == 0) egb_part[AGBNP_WG - 1] = 0.0;
       return;
     }
@@ -1330,16 +1310,9 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
       s_izq[lane] = make_double2(pa.z, qa);
       s_ibc[lane] = make_double2(bra.br, (-0.25 * 1.4426950408889634074) * bra.inv_br);
       if (diag && va) {
-        // the diagonal tile of a block publishes the per-atom results exactly once:
-        // B_i, f'_i, vdW energy + GB self energy, brw_i (ReferenceAGBNPKernels.cpp:477,513-533)
-        const double bh = bra.br + kHBRadius, bh3 = bh * bh * bh, al = alpha[a];
-        const double brw_a = -(1. / (4. * kPi)) * 3. * al * bra.br * bra.br * bra.fp / (bh3 * bh);
-        born[a] = bra.br;
-        born_fp[a] = bra.fp;
-        e_atom[a] = al / bh3 + kDielFactor * pa.w * pa.w * bra.inv_br;
-        brw[a] = brw_a;
+        // the diagonal tile of a block publishes the per-atom results exactly once
+        const double brw_a = publish_atom(a, bra, pa.w, alpha, born, born_fp, e_atom, brw, P.bw, !kEnergy && P.rows_on);
         P.srec[ysi] = make_double4(bra.br, bra.fp, brw_a, pa.w);  // the chain-rule stage's copy, by slot (a = 64 I + lane here)
-        if (!kEnergy && P.rows_on) hbm_add(&P.bw[a], bw_alpha(bra, brw_a, pa.w));
       }
     }
   }
@@ -1367,22 +1340,18 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
     const double2 xy = jxy[k], zq = jzq[k], bj = jbb[k];
     const double dx = xy.x - xi, dy = xy.y - yi_, dz = zq.x - zi;
     const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
-    const double bb = bi * bj.x;
-    const double et = exp2_nonpositive(d2 * (ci * bj.y));  // exp(-d^2 / (4 B_i B_j))
-    const double fgb = rsqrt_pos(fma(bb, et, d2));
     double qq = (k == masked_step ? qlast : qi) * zq.y;
     if (kCut) qq = d2 < P.gb_cut2 ? qq : 0.0;  // (a pair beyond the cutoff contributes to nothing: every term carries qq)
-    const double s1 = qq * fgb;
-    e += s1;
-    const double s3 = s1 * (fgb * fgb);
-    const double mw = fma(-0.25, et, 1.0) * s3;
+    const GbPairTerms<double> t = gb_pair_terms(d2, bi * bj.x, ci * bj.y, qq);
+    const double mw = t.mw;
+    e += t.s1;
     fxi = fma(dx, mw, fxi);
     fyi = fma(dy, mw, fyi);
     fzi = fma(dz, mw, fzi);
     fxj = fma(-dx, mw, fxj);
     fyj = fma(-dy, mw, fyj);
     fzj = fma(-dz, mw, fzj);
-    const double yt = fma(0.25, d2, bb) * (et * s3);
+    const double yt = t.ybb * t.ets3;
     yi += yt;
     yj_acc += yt;
     fxj = rot1(fxj);
@@ -1396,18 +1365,15 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
   PAIR_STAMP(1, 2);
   TileSums& s_sums = *reinterpret_cast<TileSums*>(s_area);
   if (kEnergy) {  // (see gb_strip)
-    e = wave_sum(e);
-    if (lane == 0) s_e[wave] = e;
+    gb_energy_put(e, s_e, lane, wave);
     __syncthreads();
-    if (threadIdx.x == 0) egb_part[AGBNP_WG - 1] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
-    return;
+    return gb_energy_store(s_e, egb_part + (AGBNP_WG - 1));
   }
   {
     const double vi4[4] = {kf * fxi, kf * fyi, kf * fzi, yi}, vj4[4] = {kf * fxj, kf * fyj, kf * fzj, yj_acc};
     tile_sums_store(s_sums, wave, lane, (lane + start + nsteps) & 63, vi4, vj4);  // jslot: whose sums the lane holds now
   }
-  e = wave_sum(e);
-  if (lane == 0) s_e[wave] = e;
+  gb_energy_put(e, s_e, lane, wave);
   __syncthreads();
   // thread (wave q, lane l) adds quantity q of atom l of block I and of block J: rows gb_fx, gb_fy, gb_fz by atom, Y by slot
   double* __restrict__ row = gb_rows + (size_t)wave * n;
@@ -1421,7 +1387,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
     if (i < n) hbm_add(wave == 3 ? &P.ys[ysi] : &row[i], quantize(tile_sums_fold(s_sums, wave, lane), qs, det));
     if (j < n) hbm_add(wave == 3 ? &P.ys[ysj] : &row[j], quantize(tile_sums_fold(s_sums, 4 + wave, lane), qs, det));
   }
-  if (threadIdx.x == 0) egb_part[AGBNP_WG - 1] = 2.0 * kDielFactor * ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3]));
+  gb_energy_store(s_e, egb_part + (AGBNP_WG - 1));
   PAIR_STAMP(1, 3);
 }
 
@@ -1429,7 +1395,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
 // (launch bounds: six waves per SIMD = three workgroups per CU, 80 vector registers; the GB rows, whose pair terms and
 // bookkeeping role need more, four)
 // SINGLE: the Born / chain-rule rows with their pair terms in single precision (row_kernels.h; fast mode + AGBNP_HIP_MODE_SINGLE)
-// MASKS (five-launch mode, Born rows only; `role_bytes` then carries the number of the first such workgroup): behind the row
+// MASKS (five-launch mode, Born rows only): behind the row
 // and list-building workgroups the grid holds one workgroup per tile of the level-2 neighbour masks.  They leave on two scalar
 // loads unless the cavity launch of this evaluation found a heavy atom a quarter of the masks' skin (or more: then the
 // evaluation is void) from where it was when the masks were laid down; then they lay them down anew from this evaluation's
@@ -1437,15 +1403,17 @@ AGBNP_KERNEL AGBNP_BOUNDS(256) void k_gb_tiles(int n, const int* __restrict__ it
 // DEVPAR: the evaluation's set of accumulators is named by the device's own count (PairArgs::five == 2, contexts that have
 // been captured into a graph); a launch of its own instantiation, so that eager launches carry no trace of it.
 template <int KIND, bool SINGLE = false, bool MASKS = false, bool DEVPAR = false>
-AGBNP_KERNEL AGBNP_BOUNDS(64 * row_waves(KIND), KIND == kGbRows ? 4 : 6) void k_rows(PairArgs P, double* __restrict__ energy_out, double* __restrict__ components, int role_bytes AGBNP_WG_PARAM) {
+AGBNP_KERNEL AGBNP_BOUNDS(64 * row_waves(KIND), KIND == kGbRows ? 4 : 6) void k_rows(PairArgs P, double* __restrict__ energy_out, double* __restrict__ components, int role_arg AGBNP_WG_PARAM) {
+  // role_arg, what the kind's roles need of the launch -- Born rows with MASKS: the number of the first mask workgroup (else
+  // unused); chain-rule rows: the LDS bytes of the launch, for the dealing role; GB rows: those for the packing role
   extern __shared__ double2 s_dyn[];
 
   int blk = AGBNP_WG;
-  if (MASKS && KIND == kBornRows && blk >= role_bytes) {
+  if (MASKS && KIND == kBornRows && blk >= role_arg) {
     if (threadIdx.x >= 256) return;
     if (DEVPAR) rebase_for_parity(P, 0);
     if (((P.estatus[kStatOrderStale] & 2) | P.estatus[kStatMaskAging]) == 0) return;
-    return neighbor_tile(P, blk - role_bytes, true);
+    return neighbor_tile(P, blk - role_arg, true);
   }
   // (five-launch mode: the Born rows read this evaluation's self volumes and write its status block -- rows_workgroup asks for
   // the device's evaluation counter with its first loads and moves the two pointers when it first needs them: a rebase HERE
@@ -1453,7 +1421,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(64 * row_waves(KIND), KIND == kGbRows ? 4 : 6) void k_
   if (KIND == kChainRows) {  // the chain-rule launch carries the two single-workgroup roles (see k_dborn_tiles): four waves each
     if (blk < 2 && threadIdx.x >= 256) return;
     if (blk == 0) return energy_role<DEVPAR>(P, 1, energy_out, components, reinterpret_cast<char*>(s_dyn));
-    if (blk == 1) return dealing_role(P, reinterpret_cast<char*>(s_dyn), role_bytes);
+    if (blk == 1) return dealing_role(P, reinterpret_cast<char*>(s_dyn), role_arg);
     blk -= 2;
   }
   if (KIND == kGbRows) {  // the GB launch carries the first half of the bookkeeping (see k_gb_tiles)
@@ -1462,7 +1430,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(64 * row_waves(KIND), KIND == kGbRows ? 4 : 6) void k_
       if (threadIdx.x >= 256) return;
       PAIR_STAMP(1, 0);
       rebase_for_parity(P, 0);
-      packing_role<false>(P, reinterpret_cast<char*>(s_dyn), role_bytes);
+      packing_role<false>(P, reinterpret_cast<char*>(s_dyn), role_arg);
       PAIR_STAMP(1, 3);
       return;
     }

@@ -77,13 +77,7 @@ __global__ __launch_bounds__(256) void k_born_tiles(int nh, int nhb, int ntj, in
   // is ONE round trip deep (records by slot: no slot -> atom indirection; a slot of a heavy block is the heavy atom
   // itself, so its self volume comes straight from the tree's row).
   auto out_of_range = [&]() {  // workgroup-uniform range test on the two bounding boxes
-    if (diag) return false;
-    double gap2 = 0.0;
-    for (int d = 0; d < 3; d++) {
-      const double g = fmax(0.0, fmax(pbox[6 * J + d] - pbox[6 * I + 3 + d], pbox[6 * I + d] - pbox[6 * J + 3 + d]));
-      gap2 += g * g;
-    }
-    return gap2 >= range2;
+    return !diag && box_gap2(pbox, I, J) >= range2;
   };
   // (a large system culls most of its tiles: there the test comes first and a culled tile costs two scalar loads; a
   // small one culls next to none: there the test waits until the tile's loads are on their way)
@@ -246,13 +240,7 @@ __global__ __launch_bounds__(256) void k_dborn_tiles(int n, int nhb, int ntj, in
     return make_double2(d.g.z + bru, slot_is_heavy ? d.sv * d.iv : 0.0);  // slot h of a heavy block is heavy atom h
   };
   auto out_of_range = [&]() {  // workgroup-uniform range test on the two bounding boxes
-    if (diag) return false;
-    double gap2 = 0.0;
-    for (int d = 0; d < 3; d++) {
-      const double g = fmax(0.0, fmax(pbox[6 * J + d] - pbox[6 * I + 3 + d], pbox[6 * I + d] - pbox[6 * J + 3 + d]));
-      gap2 += g * g;
-    }
-    return gap2 >= P.range2;
+    return !diag && box_gap2(pbox, I, J) >= P.range2;
   };
   if (P.cull_first && out_of_range()) return;  // (see k_born_tiles)
   // every slot of the tile is fetched once, block I reaches the lanes' registers through LDS (see k_born_tiles)

@@ -55,6 +55,41 @@ __device__ __forceinline__ BornRadius born_radius(double inv_rvdw, double qsum) 
 __device__ __forceinline__ double bw_beta(const BornRadius& r) { return -(1. / (4. * kPi)) * kDielFactor * r.br * r.fp; }
 __device__ __forceinline__ double bw_alpha(const BornRadius& r, double brw, double q) { return brw - (1. / (4. * kPi)) * kDielFactor * (q * q) * r.fp; }
 
+// The per-atom results, published once per atom (the diagonal tile of k_gb_tiles; the first slice of a group's first list in the
+// GB rows): B_a, f'_a, vdW + GB self energy, brw_a (ReferenceAGBNPKernels.cpp:477,513-533), alpha_a of bw_a if add_bw.  Returns brw_a.
+__device__ __forceinline__ double publish_atom(int a, const BornRadius& r, double q, const double* alpha, double* born, double* born_fp,
+                                               double* e_atom, double* brw, double* bw, bool add_bw) {
+  const double bh = r.br + kHBRadius, bh3 = bh * bh * bh, al = alpha[a];
+  const double brw_a = -(1. / (4. * kPi)) * 3. * al * r.br * r.br * r.fp / (bh3 * bh);
+  born[a] = r.br;
+  born_fp[a] = r.fp;
+  e_atom[a] = al / bh3 + kDielFactor * q * q * r.inv_br;
+  brw[a] = brw_a;
+  if (add_bw) hbm_add(&bw[a], bw_alpha(r, brw_a, q));
+  return brw_a;
+}
+// The GB pair terms, formed in one place.  Of d^2, bb = B_i B_j, c = -log2(e) / (4 B_i B_j) (as c_i / B_j) and qq = q_i q_j, with
+// et = exp(-d^2 / (4 B_i B_j)) and f = 1 / sqrt(d^2 + bb et): s1 = qq f (pair energy), mw = (1 - et/4) qq f^3 (direct force per
+// distance), and the Y term's two factors ybb = d^2/4 + bb, ets3 = et qq f^3 -- multiplied by the caller: tiles and strips round
+// the product before adding it to two sums, the rows fold it in with one fma.  float: the hardware's exp2 / rsqrt.
+template <class real>
+struct GbPairTerms {
+  real s1, mw, ybb, ets3;
+};
+__device__ __forceinline__ double gb_exp2(double y) { return exp2_nonpositive(y); }
+__device__ __forceinline__ float gb_exp2(float y) { return __builtin_amdgcn_exp2f(y); }
+__device__ __forceinline__ double gb_rsqrt(double u) { return rsqrt_pos(u); }
+__device__ __forceinline__ float gb_rsqrt(float u) { return __builtin_amdgcn_rsqf(u); }
+template <class real>
+__device__ __forceinline__ GbPairTerms<real> gb_pair_terms(real d2, real bb, real c, real qq) {
+  const real et = gb_exp2(d2 * c), fgb = gb_rsqrt(fma(bb, et, d2));
+  GbPairTerms<real> t;
+  t.s1 = qq * fgb;
+  const real s3 = t.s1 * (fgb * fgb);
+  t.mw = fma((real)-0.25, et, (real)1) * s3, t.ybb = fma((real)0.25, d2, bb), t.ets3 = et * s3;
+  return t;
+}
+
 // ---- row form of the pair stages ---------------------------------------------------------------------------------------
 // The tile kernels above meet every pair of two 64-atom blocks; on a protein of a few thousand atoms a third of those pairs
 // lie inside the tables' 2 nm reach, and a wave pays for all of them.  The row form meets (almost) only pairs in reach and
@@ -238,6 +273,30 @@ __device__ __forceinline__ void build_list(const PairArgs& P, int sub, int lane,
   }
 }
 
+template <int KIND>
+constexpr int kRowStamp = KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0;  // the kind's launch in the diagnostic stamps' log
+// The in-place rebuild of a stale Born list by the wave that walks slice `slice` of list sub = (group, part): every slice rebuilds
+// the list for itself (the same entries at the same places: the copies agree), so that no wave waits for another workgroup's.
+// Returns the length, clamped into the stride; e1, e2: the slice's first two steps, read again behind the fence.
+__device__ __forceinline__ int rebuild_born_list(const PairArgs& P, const RowLists& L, const RowAtoms& A, int sub, int group, int part, int slice, int first, int lane,
+                                                 int* estatus, unsigned& e1, unsigned& e2) {
+  const unsigned* list = P.nlh + (size_t)sub * L.stride;
+  int count = row_build(A, P.hperm, P.hperm_n, part, L.parts, static_cast<const double4*>(P.rec_h), P.nl_build2, P.nlh + (size_t)sub * L.stride, L.stride, lane);
+  if (lane == 0 && slice == 0) {
+    P.nlh_count[sub] = count;  // (untruncated, see build_list)
+    if (count > L.cap) estatus[kStatRowOverflow] = 1;
+    append_items<kBornRows>(P, sub, min(count, L.cap), false);
+  }
+  if (slice == 0 && part == 0 && lane < A.rows) {  // where the atoms were when the lists were built
+    const int a = kRowGroup * group + lane;
+    const double4 pa = static_cast<const double4*>(P.aposq)[a];
+    P.nl_ref[3 * a] = pa.x, P.nl_ref[3 * a + 1] = pa.y, P.nl_ref[3 * a + 2] = pa.z;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // (the wave's own stores, read back by other lanes)
+  e1 = list[min(first + lane, L.stride - 1)], e2 = list[min(first + 64 + lane, L.stride - 1)];
+  return min(count, L.stride);
+}
+
 // The work of one workgroup of WAVES waves of a row launch of kind KIND (blk: its number among the launch's row
 // workgroups).
 // SINGLE (Born and chain-rule rows under AGBNP_HIP_MODE_FAST | AGBNP_HIP_MODE_SINGLE): the pair terms in single precision, as
@@ -272,7 +331,7 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
       build_list<kGbRows>(P, sub - chain_lists, lane, stale, P.estatus + (PARITY ? kStatBlockStride * (epoch_now & 1) : 0));
     return;
   }
-  PAIR_STAMP((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 0);
+  PAIR_STAMP(kRowStamp<KIND>, 0);
   const int item = blk * WAVES + wave;
   // Work items.  Normally from the compact list laid down when the lists were built: the launch's first workgroups are the
   // ones with work, the rest leave here.  The Born rows of a rebuild evaluation build their lists themselves, slice by
@@ -287,11 +346,11 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
       if (KIND == kGbRows && lane == 0 && item < P.egb_parts) P.egb_part[item] = 0.0;  // (every partial is summed up)
       return;
     }
-    PAIR_STAMP_HW((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0));
-    PAIR_STAMP((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 10);
+    PAIR_STAMP_HW(kRowStamp<KIND>);
+    PAIR_STAMP(kRowStamp<KIND>, 10);
     active = item < nitems;
     const unsigned it = (P.nl_items + (size_t)(kRowBuffers * KIND + buf) * P.nl_items_cap)[active ? item : 0];
-    PAIR_STAMP_WAIT((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 11, "vmcnt(0)");
+    PAIR_STAMP_WAIT(kRowStamp<KIND>, 11, "vmcnt(0)");
     li = (int)row_item_list(it);
     slice = (int)row_item_slice(it);
   } else {
@@ -340,7 +399,7 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
   if (KIND != kGbRows && !SINGLE) tv0 = gtab[min(tx, 2 * tab - 1)], tv1 = gtab[min(kWg + tx, 2 * tab - 1)], tv2 = gtab[min(2 * kWg + tx, 2 * tab - 1)];  // (1dwc: 1440 entries)
   if (KIND != kGbRows && SINGLE)  // (1dwc: 720 entries, both halves of an entry per thread)
     tv0 = gtab[min(tx, tab - 1)], tv1 = gtab[tab + min(tx, tab - 1)], tv2 = gtab[min(kWg + tx, tab - 1)], tv3 = gtab[tab + min(kWg + tx, tab - 1)];
-  PAIR_STAMP_WAIT((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 7, "vmcnt(0) lgkmcnt(0)");
+  PAIR_STAMP_WAIT(kRowStamp<KIND>, 7, "vmcnt(0) lgkmcnt(0)");
   if (KIND != kGbRows && !SINGLE) {
     if (tx < 2 * tab) s_tab[tx] = tv0;
     if (kWg + tx < 2 * tab) s_tab[kWg + tx] = tv1;
@@ -362,22 +421,7 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
   for (int r = 0; r < R; r++) slice_at[r] = uniform((int)((types >> (8 * r)) & 0xffu) * ne);
   int count = listed;
   if (KIND == kBornRows && stale && active) {
-    // every slice of a list rebuilds the list for itself (the same entries at the same places: the copies agree), so that
-    // no wave waits for another workgroup's
-    count = row_build(A, P.hperm, P.hperm_n, part, NP, static_cast<const double4*>(P.rec_h), P.nl_build2, P.nlh + (size_t)sub * stride, stride, lane);
-    if (lane == 0 && slice == 0) {
-      P.nlh_count[sub] = count;  // (untruncated, see build_list)
-      if (count > L.cap) flag_row_overflow();
-      append_items<kBornRows>(P, sub, min(count, L.cap), false);
-    }
-    if (slice == 0 && part == 0 && lane < A.rows) {  // where the atoms were when the lists were built
-      const int a = kRowGroup * group + lane;
-      const double4 pa = static_cast<const double4*>(P.aposq)[a];
-      P.nl_ref[3 * a] = pa.x, P.nl_ref[3 * a + 1] = pa.y, P.nl_ref[3 * a + 2] = pa.z;
-    }
-    count = min(count, stride);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // (the wave's own stores, read back by other lanes)
-    e1 = list[min(first + lane, stride - 1)], e2 = list[min(first + 64 + lane, stride - 1)];
+    count = rebuild_born_list(P, L, A, sub, group, part, slice, first, lane, P.estatus + (PARITY ? kStatBlockStride * (epoch_now & 1) : 0), e1, e2);
   }
   if (KIND == kBornRows && active && slice == 0 && lane == 0 && !stale && listed_raw > L.cap) flag_row_overflow();  // (not all of it is walked)
   const int todo = active ? max(0, min(count - first, rs)) : 0;  // entries of this slice
@@ -397,9 +441,9 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
     double4 r1 = rec[row_entry_index(e1)];
     double w1 = wsrc[row_entry_index(e1)];
     __syncthreads();  // the table is in LDS
-    PAIR_STAMP((KIND == kChainRows ? 2 : 0), 8);
-    PAIR_STAMP_WAIT((KIND == kChainRows ? 2 : 0), 1, "vmcnt(0)");  // the first records are here
-    ROWS_LOG_COUNTS((KIND == kChainRows ? 2 : 0), todo, nsteps);
+    PAIR_STAMP(kRowStamp<KIND>, 8);
+    PAIR_STAMP_WAIT(kRowStamp<KIND>, 1, "vmcnt(0)");  // the first records are here
+    ROWS_LOG_COUNTS(kRowStamp<KIND>, todo, nsteps);
     if (SINGLE) {
       float ox[R], oy[R], oz[R], accf[4 * R];
 #pragma unroll
@@ -492,29 +536,20 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
       beta_r[r] = bw_beta(bra[r]);
     }
     if (active && slice == 0 && part == 0 && lane < A.rows) {
-      // the first slice of a group's first list publishes the per-atom results once (as the diagonal tile does in
-      // k_gb_tiles): B_i, f'_i, vdW energy + GB self energy, brw_i, and alpha_i of bw_i (ReferenceAGBNPKernels.cpp:477,513-533)
-      const int a = R * group + lane;
+      // the first slice of a group's first list publishes the per-atom results once (as the diagonal tile does in k_gb_tiles)
       BornRadius br = bra[0];
       double qv = row_q[0];
 #pragma unroll
       for (int r = 1; r < R; r++) {
         if (lane == r) br = bra[r], qv = row_q[r];
       }
-      const double al = P.alpha[a];
-      const double bh = br.br + kHBRadius, bh3 = bh * bh * bh;
-      const double brw_a = -(1. / (4. * kPi)) * 3. * al * br.br * br.br * br.fp / (bh3 * bh);
-      P.born[a] = br.br;
-      P.born_fp[a] = br.fp;
-      P.e_atom[a] = al / bh3 + kDielFactor * qv * qv * br.inv_br;
-      P.brw[a] = brw_a;
-      hbm_add(&P.bw[a], bw_alpha(br, brw_a, qv));
+      publish_atom(R * group + lane, br, qv, P.alpha, P.born, P.born_fp, P.e_atom, P.brw, P.bw, true);
     }
     double4 r1 = rec[row_entry_index(e1)];
     double p1 = P.born_part[row_entry_index(e1)], v1 = P.inv_rvdw[row_entry_index(e1)];
-    PAIR_STAMP(1, 8);
-    PAIR_STAMP_WAIT(1, 1, "vmcnt(0)");  // the first records are here
-    ROWS_LOG_COUNTS(1, todo, nsteps);
+    PAIR_STAMP(kRowStamp<KIND>, 8);
+    PAIR_STAMP_WAIT(kRowStamp<KIND>, 1, "vmcnt(0)");  // the first records are here
+    ROWS_LOG_COUNTS(kRowStamp<KIND>, todo, nsteps);
     if (P.single) {
       // AGBNP_HIP_MODE_SINGLE: the pair terms in single precision, the default precision of the reference's GPU platform
       // (hardware exp2 / rsqrt, a third of the instructions).  Positions are taken relative to the group's first row atom
@@ -546,17 +581,12 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
           const float dx = nx - ox[r], dy = ny - oy[r], dz = nz - oz[r];
           const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
           if (d2 < cut2 && b != A.self[r]) {
-            const float bb = bf[r] * bj;
-            const float et = __builtin_amdgcn_exp2f(d2 * (cf[r] * ibj));  // exp(-d^2 / (4 B_a B_b))
-            const float fgb = __builtin_amdgcn_rsqf(fmaf(bb, et, d2));
-            const float s1 = (qf[r] * qb) * fgb;
-            esumf += s1;
-            const float s3 = s1 * (fgb * fgb);
-            const float mw = fmaf(-0.25f, et, 1.0f) * s3;
-            accf[4 * r] = fmaf(fmaf(0.25f, d2, bb), et * s3, accf[4 * r]);  // Y
-            accf[4 * r + 1] = fmaf(dx, mw, accf[4 * r + 1]);
-            accf[4 * r + 2] = fmaf(dy, mw, accf[4 * r + 2]);
-            accf[4 * r + 3] = fmaf(dz, mw, accf[4 * r + 3]);
+            const GbPairTerms<float> t = gb_pair_terms(d2, bf[r] * bj, cf[r] * ibj, qf[r] * qb);
+            esumf += t.s1;
+            accf[4 * r] = fmaf(t.ybb, t.ets3, accf[4 * r]);  // Y
+            accf[4 * r + 1] = fmaf(dx, t.mw, accf[4 * r + 1]);
+            accf[4 * r + 2] = fmaf(dy, t.mw, accf[4 * r + 2]);
+            accf[4 * r + 3] = fmaf(dz, t.mw, accf[4 * r + 3]);
           }
         }
       }
@@ -579,6 +609,7 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
         const double dx = rb.x - A.x[r], dy = rb.y - A.y[r], dz = rb.z - A.z[r];
         const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
         if (d2 < cut2 && b != A.self[r]) {
+          // (gb_pair_terms written out: called here, the same operations cost this kernel, at 128 registers, a spill)
           const double bb = ba[r] * bb_.br;
           const double et = exp2_nonpositive(d2 * (ca_[r] * bb_.inv_br));  // exp(-d^2 / (4 B_a B_b))
           const double fgb = rsqrt_pos(fma(bb, et, d2));
@@ -596,7 +627,7 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
     esum = wave_sum(esum);
     if (lane == 0 && item < P.egb_parts) P.egb_part[item] = kDielFactor * esum;
   }
-  PAIR_STAMP((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 2);
+  PAIR_STAMP(kRowStamp<KIND>, 2);
   if (nsteps == 0) return;
   // 16 sums per lane -> one per lane: four transposing butterfly stages (a lane keeps the half of the sums that its bit of
   // the stage selects and adds its partner's copy of them; DPP moves), then the four 16-lane rows of the wave are added up
@@ -630,7 +661,7 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
       hbm_add(reinterpret_cast<double*>((KIND == kChainRows ? P.hrec : P.grec) + row) + (c - 1), total);
     }
   }
-  PAIR_STAMP((KIND == kChainRows ? 2 : KIND == kGbRows ? 1 : 0), 3);
+  PAIR_STAMP(kRowStamp<KIND>, 3);
 }
 
 }  // namespace agbnp

@@ -253,3 +253,36 @@ def test_fast_mode_on_the_born_clamp(gpu_required, five, cutoff):
             assert (oracle.vector("born") == 2.0).sum() >= 1
         print(f"born_clamp fast mode, cutoff {cutoff}, {label}: |dE|={abs(e - eo):.3e}  max|dF|={np.abs(f - fo).max():.3e}")
         assert_close(e, f, eo, fo, tol=FAST_TOL)
+
+
+ROW_EDGE_CUTOFF = 1.0  # nm
+
+
+@pytest.mark.parametrize("mode", ["fast", "fast+single"])
+@pytest.mark.parametrize("nh,n", [(65, 65), (63, 255), (129, 257)])
+def test_row_form_on_ragged_sizes(gpu_required, five, nh, n, mode):
+    """The row form of all three pair stages -- in FP64 (fast) and with single-precision pair terms (fast+single) -- at sizes
+    that leave the last row group short (65, 255 and 257 atoms: groups of four) and the last 64-atom block part filled, against
+    the oracle's cutoff switch at 1.0 nm: the file geometry, then one drawn as test_fast_single_mode_rows_against_the_cutoff_oracle
+    draws it, which rebuilds the lists.  fast at FAST_TOL; fast+single at that test's single-precision bounds, 2e-6 |E| + 2e-2
+    and 2e-4 of the largest force."""
+    s = edge_systems()[size_edge_name(nh, n)]
+    force = P.AGBNPForce.from_arrays(*s.params(), version=1)
+    force.setNonbondedMethod(P.AGBNPForce.CutoffNonPeriodic)
+    force.setCutoffDistance(ROW_EDGE_CUTOFF)
+    k = P.HipCalcAGBNPForceKernel(mode=mode)
+    k.initialize(force)
+    oracle = Oracle(*s.params(), version=1, cutoff=ROW_EDGE_CUTOFF)
+    rng = np.random.default_rng(9)
+    for label, pos in (("file", s.pos), ("drawn", s.pos + rng.normal(0.0, 0.04, s.pos.shape))):
+        f = np.zeros((s.n, 3))
+        e = k.execute(pos, f)
+        eo, fo = oracle.execute(pos)
+        de, df = abs(e - eo), float(np.abs(f - fo).max())
+        print(f"{size_edge_name(nh, n)}, {mode}, {label}: |dE|={de:.3e}  max|dF|={df:.3e}  max|F|={np.abs(fo).max():.3e}")
+        if mode == "fast":
+            close(e, f, eo, fo, FAST_TOL)
+        else:
+            assert de < 2e-6 * abs(eo) + 2e-2, (e, eo)
+            assert df < 2e-4 * np.abs(fo).max(), (df, np.abs(fo).max())
+    assert k.scalar("rows_on") == 1
