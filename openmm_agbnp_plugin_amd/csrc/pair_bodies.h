@@ -94,9 +94,12 @@ struct SplineCubic {
   double c0, c1, c2, c3, t;
 };
 __device__ __forceinline__ SplineCubic spline_cubic(const double2* __restrict__ tab, int base, double d) {
-  // callers only ask inside the table (d < kI4MaxA), so the knot index needs no clamp and the position inside the
-  // interval is the hardware fraction: one conversion instead of two (conversions issue at quarter rate)
-  const double u = d * ((kI4Nodes - 1) / kI4MaxA);
+  // callers only ask inside the table (d2 < kI4MaxA^2), and the position inside the interval is the hardware fraction: one
+  // conversion instead of two (conversions issue at quarter rate).  One or two steps of FP64 under 4, d = d2 * rsqrt_pos(d2)
+  // can still round up to 2.0 (see the FP64 rows, row_kernels.h): knot 15 with t = 0 reads the row's zero pad and gives the
+  // value of the table's end, but a derivative of zero where the force has a step.  Such a pair belongs to the END of the
+  // last interval.
+  const double u = fmin(d * ((kI4Nodes - 1) / kI4MaxA), (kI4Nodes - 1) - 0x1p-49);
   const int k = (int)u;
   const double2 lo = tab[base + k], hi = tab[base + k + 1];
   SplineCubic c;

@@ -146,9 +146,11 @@ __device__ __forceinline__ void prep_atoms(const PairArgs& P, int i, bool first_
   P.db_wu[i] = 0.0;
   const int h = P.a2h[i];
   if (h >= 0) {
-    P.hx[h] = x;
-    P.hy[h] = y;
-    P.hz[h] = z;
+    // (the trees' coordinates are relative to the first heavy atom: see build_forest, tree_kernels.h)
+    const Pos3 o = heavy_position(P, 0);
+    P.hx[h] = x - o.x;
+    P.hy[h] = y - o.y;
+    P.hz[h] = z - o.z;
     if (!five) {
       P.gx[h] = 0.0;
       P.gy[h] = 0.0;

@@ -505,7 +505,10 @@ __device__ __forceinline__ void rows_workgroup(const PairArgs& P, int blk, doubl
         const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
         if (d2 < range2 && b != A.self[r]) {
           const double rinv = rsqrt_pos(d2);
-          const double u = (d2 * rinv) * kPerNode;
+          // (rsqrt_pos is not correctly rounded -- it rounds u * y0 before it forms the residual, 2^-55 of the result -- and one
+          // or two steps of FP64 under range2 = 4 that is enough for d2 * rinv to round up to 2.0: interval 15 of a slice of 15,
+          // without padding.  Such a pair belongs to the END of the last interval: the force has a step there.)
+          const double u = fmin((d2 * rinv) * kPerNode, kRowIntervals - 0x1p-49);
           const int ent = slice_at[r] + tent + (int)u;
           const double t = __builtin_amdgcn_fract(u);
           const double2 ca = s_tab[ent], cb = s_tab[ent + tab];

@@ -45,7 +45,7 @@ namespace agbnp {
 // address it as base + (row * hstride + h): one 64-bit base in scalar registers instead of fifteen pointers (the
 // build kernel keeps ~100 scalar values live as it is; every pointer less is two fewer spilled).
 enum HeavyRow {
-  kHvX = 0, kHvY, kHvZ,        // positions (written by k_prep)
+  kHvX = 0, kHvY, kHvZ,        // positions relative to the first heavy atom (written by prep_atoms)
   kHvALarge, kHvVLarge,        // Gaussian exponent / volume, enlarged radii
   kHvAVdw, kHvVVdw,            // ... vdW radii
   kHvGam,                      // gamma / roffset (pass 1 uses +gam, pass 2 -gam)
@@ -484,12 +484,18 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
   int q_first, J_first, hq_first;
   pair_of(tid, q_first, J_first, hq_first);
   const unsigned long long bits_first = tid < npairs ? A.nbmask[(size_t)J_first * mask_stride + hq_first] : 0ull;
+  // The trees work in coordinates relative to the evaluation's first heavy atom (as prep_atoms writes them into the heavy-atom
+  // table, prep_role.h): the centres of Gaussian products are formed from coordinates, not from differences, so their rounding
+  // -- and through the stiff volume gradients the forces' -- would grow with the distance from the origin.
+  double ox = 0.0, oy = 0.0, oz = 0.0;
+  if (FIVE) tree_position<POSQ>(A, POSQ ? A.hslot[0] : A.out.h2a[0], ox, oy, oz);
   if (tid < m) {
     const int item = my_item;
     const int hi = work_item_root(item);
     double rx, ry, rz;
     if (FIVE) {
       tree_position<POSQ>(A, my_atom, rx, ry, rz);  // (POSQ: my_atom is the root's slot in the context's order)
+      rx -= ox, ry -= oy, rz -= oz;
     } else {
       rx = A.hvat(kHvX, hi), ry = A.hvat(kHvY, hi), rz = A.hvat(kHvZ, hi);
     }
@@ -582,6 +588,7 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
       const double aj = A.hvat(kHvALarge, hjn), vj = A.hvat(kHvVLarge, hjn), gj = A.hvat(kHvGam, hjn);
       if (FIVE) {
         tree_position<POSQ>(A, POSQ ? A.hslot[hjn] : A.out.h2a[hjn], xj, yj, zj);
+        xj -= ox, yj -= oy, zj -= oz;
       } else {
         xj = A.hvat(kHvX, hjn), yj = A.hvat(kHvY, hjn), zj = A.hvat(kHvZ, hjn);
       }
