@@ -121,6 +121,19 @@ class HipCalcAGBNPForceKernel {
     return e;
   }
 
+  // Per-atom decomposition of the energy at these positions (agbnp_hip_decompose_host): returns the energy; `terms` receives
+  // AGBNP_HIP_DECOMPOSITION_TERMS planes of N doubles -- cavity, vdW, GB self, GB pair (each pair shared half and half) -- whose
+  // sum over everything is the energy.  Version 0 has the cavity plane only.  No forces are written.
+  double decompose(const std::vector<double>& positions, std::vector<double>& terms) {
+    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+    if ((int)positions.size() != 3 * numParticles) throw OpenMMException("decompose(): positions must hold 3N values");
+    terms.assign((size_t)AGBNP_HIP_DECOMPOSITION_TERMS * numParticles, 0.0);
+    double e = 0.0;
+    if (agbnp_hip_decompose_host(ctx, positions.data(), terms.data(), &e) != AGBNP_HIP_OK)
+      throw OpenMMException(agbnp_hip_last_error(ctx));
+    return e;
+  }
+
   // Replica groups (agbnp_hip_execute_group_host): one evaluation of every kernel in `kernels`, the launches of the members
   // that can share them made once for all; positions[i] (3N_i) read, forces[i] accumulated, the members' energies returned.
   static std::vector<double> executeGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,

@@ -151,6 +151,43 @@ int agbnp_hip_energy_openmm(agbnp_hip_context* ctx, const void* d_posq, int posq
                             const int* d_atom_index, int padded_num_atoms, void* d_energy_buffer, int energy_is_double,
                             int energy_slot, void* stream); /* ADDED to d_energy_buffer[energy_slot]; async */
 
+/* Per-atom decomposition of an evaluation: which atoms pay the desolvation penalty, per-atom surface areas, per-residue
+ * MM-GBSA-style tables.  The energy of an evaluation is an exact sum of four per-atom terms; with nu_i = gamma_i / roffset
+ * (roffset: the enlarged-radius increment, float 0.5f * 0.1f promoted; 0 for a hydrogen), B_i the Born radius and
+ * k = -(1/2)(1 - 1/80) * 138.935...:
+ *   plane 0  "cavity"   nu_i (sv_large_i - sv_vdw_i): the self volumes with the enlarged and the vdW radii.  The plane sums to
+ *                       E_vol1 + E_vol2 (scalars 0 + 1); the GaussVol surface area of a heavy atom is A_i = term_i / gamma_i
+ *   plane 1  "vdw"      alpha_i / (B_i + 0.14 nm)^3
+ *   plane 2  "gb_self"  k q_i^2 / B_i                                        (planes 1 + 2 sum to scalar 2)
+ *   plane 3  "gb_pair"  k q_i sum_{j != i} q_j f_ij, f_ij = 1 / sqrt(d^2 + B_i B_j exp(-d^2 / (4 B_i B_j))): each pair shared half
+ *                       and half between its atoms.  The plane sums to the GB pair energy (scalar 3)
+ * Planes 0..3 summed over all atoms equal the energy the context returns at those positions in its mode.  Version 0 has plane 0
+ * only: nothing is added to planes 1..3.  per_atom is term-major: AGBNP_HIP_DECOMPOSITION_TERMS planes of N doubles, atom order.
+ *   agbnp_hip_decompose_host    synchronous; per_atom[4 N] is OVERWRITTEN, *energy RETURNED; withheld evaluations are repeated
+ *                               inside, as agbnp_hip_energy_host() does
+ *   agbnp_hip_decompose_device  asynchronous, no host synchronisation; the 4 N terms are ADDED to d_per_atom and the total to
+ *                               *d_energy (d_energy may be NULL): a caller accumulates frames and divides
+ * Nothing is written to any force buffer of the caller.  The call counts as ONE evaluation in the context's overflow log under
+ * its enqueue index; a withheld one (a jump of more than 0.04 nm, a subtree that needs the next capacity variant, a neighbour row
+ * beyond its walk) adds nothing to either output -- gated on the device like every other output -- and agbnp_hip_finish(),
+ * _poll(), _wait_verdict() and _withheld_evaluations() report it as they report any other; agbnp_hip_expect_jump() applies.
+ * Afterwards the context is in exactly the state a full evaluation leaves: the five-launch mode goes on, scalars 16 and 18 and
+ * agbnp_hip_generation() do not change, no later evaluation is withheld for it, and full, energy-only, group and decomposition
+ * calls may be interleaved in any order (agbnp_hip_set_diagnostics() is NOT involved).  Scalar 20 reports 3 for it.
+ * Launches: the context's energy-only evaluation (four launches for version 1, two for version 0 where scalar 18 is not 0; the
+ * full evaluation with its forces sent to a buffer of the context's own elsewhere) with the cavity launch's instantiation that
+ * also collects the enlarged-radius self volumes, then ONE launch of the size of the GB stage: all 64 x 64 blocks of atom pairs
+ * for plane 3, one thread per atom for planes 0..2.  Every mode is supported.  In the fast mode plane 3 meets only pairs with
+ * d^2 < cutoff^2 and the Born radii are that mode's truncated ones (with NoCutoff: the Reference mode's numbers).  In the
+ * fast+single mode the terms are FP64: the call computes what the FP64 fast mode gives, and the terms sum to THAT mode's energy
+ * (which the call returns), not to the single-precision one.  The deterministic mode gives bit-identical planes from run to run.
+ * Inside a stream capture the device call returns AGBNP_HIP_ERR_INVALID_ARGUMENT, launches nothing and leaves the capture
+ * usable.  There is no OpenMM-buffer form and no group form: decomposition is analysis, not an MD step. */
+#define AGBNP_HIP_DECOMPOSITION_TERMS 4
+int agbnp_hip_decompose_host(agbnp_hip_context* ctx, const double* positions, double* per_atom /*[4][N]*/, double* energy);
+int agbnp_hip_decompose_device(agbnp_hip_context* ctx, const double* d_positions, double* d_per_atom /*[4][N]*/,
+                               double* d_energy /*may be NULL*/, void* stream);
+
 /* Replica groups: ONE call that enqueues an evaluation of each of `count` existing contexts (1 .. AGBNP_HIP_MAX_GROUP), for
  * replica exchange, multiple walkers and binding-energy schemes that run several small systems at once.  d_positions,
  * d_forces, d_energies are HOST arrays of `count` DEVICE pointers, one per member.  For every member i the call does exactly
@@ -364,7 +401,8 @@ enum agbnp_hip_scalar {
   AGBNP_HIP_SCALAR_LAST_EVALUATION_KIND = 20,  /* how the last evaluation ENQUEUED on the context ran (valid without a completed
                                             * evaluation, like 15, 17, 18, 19 and 21): 0 a full evaluation, 1 an energy-only evaluation on
                                             * energy-only launches (alone or shared), 2 an energy-only request that ran as a full
-                                            * evaluation with its forces sent to the context's own buffer */
+                                            * evaluation with its forces sent to the context's own buffer, 3 a per-atom decomposition
+                                            * (agbnp_hip_decompose_*) */
   AGBNP_HIP_SCALAR_GROUP_BLOCK_WRITES = 21 /* how often the context's group argument blocks have been rewritten so far (one small
                                             * launch each); it stands still in a steady run of group calls with fixed position buffers */
 };

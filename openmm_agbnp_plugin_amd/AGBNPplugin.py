@@ -16,6 +16,10 @@ import numpy as np
 from . import _lib
 
 
+# the planes of an energy decomposition, in the order of include/agbnp_hip.h (agbnp_hip_decompose_*)
+DECOMPOSITION_TERMS = ("cavity", "vdw", "gb_self", "gb_pair")
+
+
 class OpenMMException(Exception):
     """Same role as OpenMM::OpenMMException in the reference: every API error surfaces as this type."""
 
@@ -260,6 +264,33 @@ class HipCalcAGBNPForceKernel:
         rc = _lib.load().agbnp_hip_energy_openmm(self._h, C.c_void_p(d_posq), int(bool(posq_is_double)), C.c_void_p(d_posq_correction or 0),
                                                  C.c_void_p(d_atom_index or 0), int(padded_num_atoms), C.c_void_p(d_energy_buffer),
                                                  int(bool(energy_is_double)), int(energy_slot), C.c_void_p(stream or 0))
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(self._h))
+
+    def decompose(self, positions):
+        """Per-atom decomposition of the energy at these positions (include/agbnp_hip.h, agbnp_hip_decompose_host): returns
+        (energy, terms) with terms a float64 array [4, N] in the order of DECOMPOSITION_TERMS -- cavity, vdW, GB self, GB pair
+        (each pair shared half and half) -- whose sum over everything is the energy.  Version 0 has the cavity plane only.  No
+        forces are written anywhere; withheld evaluations are repeated inside, like energy()."""
+        self._need()
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
+        if pos.size != 3 * self.numParticles:
+            raise OpenMMException("decompose(): wrong number of positions")
+        terms = np.zeros((len(DECOMPOSITION_TERMS), self.numParticles))
+        e = C.c_double(0.0)
+        rc = _lib.load().agbnp_hip_decompose_host(self._h, _dp(pos), _dp(terms), C.byref(e))
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(self._h))
+        return e.value, terms
+
+    def decompose_device(self, d_positions, d_per_atom, d_energy=None, stream=None):
+        """Device-resident form of decompose(): the 4 N terms are ADDED to d_per_atom (term-major planes of N doubles, atom
+        order) and the total to *d_energy when it is given; raw FP64 device pointers (ints).  Asynchronous, counted in the same
+        log as every other evaluation (finish(), withheld(), poll(), wait_verdict()); a withheld one adds nothing.  Refused
+        (OpenMMException) inside a stream capture."""
+        self._need()
+        rc = _lib.load().agbnp_hip_decompose_device(self._h, C.c_void_p(d_positions), C.c_void_p(d_per_atom), C.c_void_p(d_energy or 0),
+                                                    C.c_void_p(stream or 0))
         if rc != _lib.OK:
             raise OpenMMException(_lib.last_error(self._h))
 
@@ -542,6 +573,15 @@ class AGBNPContext:
         if (groups & (1 << self._force.getForceGroup())) == 0:
             return 0.0
         return self._kernel.energy(self._positions)
+
+    def getEnergyDecomposition(self, groups=-1):
+        """(energy, terms[4, N]) at the context's positions: the per-atom terms of DECOMPOSITION_TERMS, which sum to the energy
+        (HipCalcAGBNPForceKernel.decompose).  Honours the force-group mask like getState()."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        if (groups & (1 << self._force.getForceGroup())) == 0:
+            return 0.0, np.zeros((len(DECOMPOSITION_TERMS), self._kernel.numParticles))
+        return self._kernel.decompose(self._positions)
 
     def _update_parameters(self, force):
         self._kernel.copyParametersToContext(force)

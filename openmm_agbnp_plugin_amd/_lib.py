@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("AGBNP_HIP_LIBRARY") or os.path.join(_HERE, "libagbnp_
 
 OK, ERR_INVALID_ARGUMENT, ERR_PARAMETERS, ERR_DEVICE, ERR_CAPACITY, ERR_TIMEOUT = 0, 1, 2, 3, 4, 5
 MAX_GROUP = 16  # AGBNP_HIP_MAX_GROUP: members of one agbnp_hip_execute_group call
+DECOMPOSITION_TERMS = 4  # AGBNP_HIP_DECOMPOSITION_TERMS: planes of agbnp_hip_decompose_*
 
 # every symbol include/agbnp_hip.h declares
 SYMBOLS = [
@@ -21,6 +22,7 @@ SYMBOLS = [
     "agbnp_hip_energy_host", "agbnp_hip_energy_device", "agbnp_hip_energy_openmm",
     "agbnp_hip_execute_group", "agbnp_hip_execute_group_host",
     "agbnp_hip_energy_group", "agbnp_hip_energy_group_host", "agbnp_hip_expect_jump",
+    "agbnp_hip_decompose_host", "agbnp_hip_decompose_device",
 ]
 
 _lib = None
@@ -69,6 +71,8 @@ def load():
     lib.agbnp_hip_energy_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), vp]
     lib.agbnp_hip_energy_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp]
     lib.agbnp_hip_expect_jump.argtypes = [vp]
+    lib.agbnp_hip_decompose_host.argtypes = [vp, dp, dp, dp]
+    lib.agbnp_hip_decompose_device.argtypes = [vp, vp, vp, vp, vp]
     lib.agbnp_hip_atom_order_changed.argtypes = [vp]
     lib.agbnp_hip_finish.argtypes = [vp, vp, ip]
     lib.agbnp_hip_poll.argtypes = [vp, ip, ip]

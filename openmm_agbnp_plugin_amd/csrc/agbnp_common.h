@@ -196,6 +196,7 @@ enum KernelId {
   kKBornRows, kKDbornRows,  // row form of the two range-limited stages (take the place of the two tile kernels)
   kKGbRows,                 // row form of the GB stage (fast mode only)
   kKEnergyRoles,            // energy-only evaluations: energy, dealing and the rows' close behind the GB stage (k_energy_roles)
+  kKDecompose,              // per-atom decomposition: the launch behind its evaluation (k_decompose, decompose_kernels.hip)
   kKernelCount
 };
 

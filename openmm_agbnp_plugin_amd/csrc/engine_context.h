@@ -198,6 +198,9 @@ struct agbnp_hip_context {
   // (energy_role routes the energy to an OpenMM accumulator only beside a fixed-point force target); never read
   DevBuf<double> d_eo_force;
   DevBuf<unsigned long long> d_eo_fixed;
+  // per-atom decompositions (agbnp_hip_decompose_host): the four planes and the energy [4n + 1] on the device and on the host
+  DevBuf<double> d_decomp;
+  std::vector<double> h_decomp;
   int forests_hint = 0;        // forests of the last evaluation the host has read the status of (0: none yet); reset by a fallback packing
   std::vector<int> withheld;   // evaluations (numbered from the previous finish) that the last finish found withheld
   int withheld_count = 0;
@@ -245,7 +248,8 @@ struct agbnp_hip_context {
   hipEvent_t group_event = nullptr;  // joins the context's own stream and a group's stream
   int group_members = 0;             // scalar 19: members of the launch set the last evaluation shared (0: it ran alone)
   int group_block_writes = 0;        // scalar 21: k_group_put launches so far
-  int last_kind = 0;                 // scalar 20: 0 a full evaluation, 1 energy-only on energy-only launches, 2 energy-only run as a full one
+  int last_kind = 0;                 // scalar 20: 0 a full evaluation, 1 energy-only on energy-only launches, 2 energy-only run as a full one,
+                                     // 3 a per-atom decomposition
 
   // ---- what the last harvest read (engine_report.hip reads it back to the caller)
   Timeline timeline;
@@ -317,6 +321,7 @@ struct EvalRequest {
   double* energy = nullptr;      // [1]
   hipStream_t stream = nullptr;
   bool energy_only = false;
+  bool sv_large = false;         // the cavity launch also collects the enlarged-radius self volumes (a decomposition: row kHvSvLarge)
   double* zero_out = nullptr;    // the host entry points' staging buffer, cleared first (PairArgs::zero_out)
   OpenmmSource in;               // agbnp_hip_execute_openmm / agbnp_hip_energy_openmm: the context's posq ...
   OpenmmTargets omm;             // ... and its fixed-point planes and energy accumulator

@@ -199,7 +199,7 @@ int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest
   c->last_kind = !r.energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
   if (c->five_active) {
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
-    HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st));
+    HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st, r.sv_large));
     if (r.energy_only && energy_only_fast(c)) {
       HIP_TRY(c, launch_energy_only_stages(c->P, shape, c->version, r.energy, c->d_components.p, st, tl));
       return AGBNP_HIP_OK;
@@ -207,7 +207,7 @@ int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest
   } else {
     HIP_TRY(c, launch_prep(c->P, st, tl));
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
-    HIP_TRY(c, launch_tree_cavity(c->variant, kGlobalGrid, tree_grid, c->T, st));
+    HIP_TRY(c, launch_tree_cavity(c->variant, kGlobalGrid, tree_grid, c->T, st, r.sv_large));
   }
   if (c->version == 1) {
     HIP_TRY(c, launch_pair_stages(c->P, shape, r.energy, c->d_components.p, st, tl));
@@ -471,9 +471,91 @@ int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int po
   r.omm.energy_slot = energy_slot;
   return enqueue(c, r);
 }
+// Per-atom decomposition (agbnp_hip_decompose_*): ONE evaluation in the context's overflow log -- the energy-only evaluation of the
+// context (energy_only_fast: its four / two launches; elsewhere the full evaluation with its forces sent to d_eo_force) with the
+// cavity launch's instantiation that also collects the enlarged-radius self volumes -- and behind it, on the same stream, the one
+// launch that adds the planes (decompose_kernels.hip).  The energy leaves with the evaluation's own energy role (d_energy == NULL:
+// into the context's spare word), the planes are gated on the same verdict words.  Nothing of the context's state differs from
+// what the evaluation alone leaves: the request selects the instantiation, c->diagnostics is not touched.
+// fast+single: the terms are FP64 (header), so the evaluation runs with the single-precision option lifted for this call -- the
+// same lists and masks (the reach is the fast mode's), other pair-term arithmetic; kernel arguments travel by value, so nothing
+// enqueued before or after is affected.
+int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, double* d_per_atom, double* d_energy, hipStream_t st) {
+  EvalRequest r;
+  r.pos = d_pos;
+  r.force = c->d_eo_force.p;
+  r.energy = d_energy ? d_energy : c->d_energy_tmp.p;
+  r.stream = st;
+  r.energy_only = true;
+  r.sv_large = true;
+  const bool single = (c->mode & AGBNP_HIP_MODE_SINGLE) != 0;
+  if (single) {
+    c->mode &= ~AGBNP_HIP_MODE_SINGLE;
+    derive_args(c);
+  }
+  int rc;
+  {
+    const Unbind unbind{&c, 1};
+    EvalPlan plan;
+    rc = enqueue_prepare(c, r, plan);
+    if (rc == AGBNP_HIP_OK) rc = enqueue_launch(c, plan, r);
+    if (rc == AGBNP_HIP_OK) {
+      const hipError_t e = launch_decompose(c->P, c->version, d_per_atom, st, c->timeline.enabled ? &c->timeline : nullptr);
+      if (e != hipSuccess) rc = c->hipfail(e, "launch_decompose");
+    }
+  }
+  c->last_kind = 3;
+  if (single) {
+    c->mode |= AGBNP_HIP_MODE_SINGLE;
+    derive_args(c);
+  }
+  return rc;
+}
+
+// agbnp_hip_decompose_host: the planes and the energy travel back in one buffer; withheld evaluations are repeated
+int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int rc0 = carry_unfinished(c);
+  if (rc0 != AGBNP_HIP_OK) return rc0;
+  const size_t n4 = 4 * (size_t)c->n;
+  if (c->d_decomp.count != n4 + 1) HIP_TRY(c, c->d_decomp.alloc(n4 + 1));
+  c->h_decomp.resize(n4 + 1);
+  for (int attempt = 0; attempt < 10; attempt++) {
+    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, pos, sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_decomp.p, 0, sizeof(double) * (n4 + 1), c->stream));
+    int rc = enqueue_decomposition(c, c->d_pos_in.p, c->d_decomp.p, c->d_decomp.p + n4, c->stream);
+    if (rc != AGBNP_HIP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_decomp.data(), c->d_decomp.p, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, c->stream));
+    int repeat = 0;
+    rc = harvest(c, &repeat, c->stream);  // (its own reads follow on the stream; one wait for everything)
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (repeat) continue;
+    std::memcpy(per_atom, c->h_decomp.data(), sizeof(double) * n4);
+    *energy = c->h_decomp[n4];
+    return AGBNP_HIP_OK;
+  }
+  return c->fail(AGBNP_HIP_ERR_CAPACITY, "agbnp_hip_decompose_host: capacity negotiation did not converge");
+}
 }  // namespace
 
 extern "C" {
+
+int agbnp_hip_decompose_host(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!pos || !per_atom || !energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_decompose_host: null pointer");
+  return host_decomposition(c, pos, per_atom, energy);
+}
+
+int agbnp_hip_decompose_device(agbnp_hip_context* c, const double* d_pos, double* d_per_atom, double* d_energy, void* stream) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_pos || !d_per_atom) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_decompose_device: null pointer");
+  hipStream_t st;
+  const int rc = enter(c, stream, &st);
+  if (rc != AGBNP_HIP_OK) return rc;
+  if (refuse_capture(c, st, "agbnp_hip_decompose_device")) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  note_stream(c, stream);
+  return enqueue_decomposition(c, d_pos, d_per_atom, d_energy, st);
+}
 
 int agbnp_hip_execute_device(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, void* stream) {
   if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;

@@ -261,5 +261,8 @@ hipError_t launch_energy_only_stages(const PairArgs& P, const PairLaunchShape& S
                                      hipStream_t st, Timeline* tl);
 hipError_t launch_outputs(const PairArgs& P, const OutputShape& O, int version, double* force_out, double* energy_out, double* components,
                           hipStream_t st, Timeline* tl);
+// per-atom decomposition (decompose_kernels.hip; engine_eval.hip, agbnp_hip_decompose_*): the one launch behind its evaluation, which
+// adds the four term-major planes [4][n] to per_atom unless the evaluation was withheld
+hipError_t launch_decompose(const PairArgs& P, int version, double* per_atom, hipStream_t st, Timeline* tl);
 
 }  // namespace agbnp

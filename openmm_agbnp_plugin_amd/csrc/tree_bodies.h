@@ -394,7 +394,9 @@ static_assert(kPrepHvGx == kHvGx && kPrepHvGx + 3 == kHvSvVdw && kPrepHvSvLarge 
 // POSQ: the instantiation of agbnp_hip_execute_openmm (round 6): the forest workgroups read the context's posq (double4, float4,
 // float4 + correction) at the context's slots; the trailing workgroups read it through the same maps (prep_role.h) and check
 // every particle's entry against atomIndex (kStatOrderStale: the context has reordered its atoms, the evaluation is void)
-template <int NCAP, int ACAP, int BS, bool DEVPAR = false, bool POSQ = false>
+// SV1: the instantiation of the per-atom decomposition (agbnp_hip_decompose_*), which also collects the enlarged-radius self
+// volumes (row kHvSvLarge; the trailing workgroups clear the next evaluation's row in every instantiation)
+template <int NCAP, int ACAP, int BS, bool DEVPAR = false, bool POSQ = false, bool SV1 = false>
 AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity_five(TreeArgs A, PairArgs P, int tree_blocks AGBNP_WG_PARAM) {
   if ((int)AGBNP_WG >= tree_blocks) {
     const int b = (int)AGBNP_WG - tree_blocks;
@@ -402,7 +404,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity_five
     return prep_atoms(P, b * BS + (int)threadIdx.x, b == 0, true);
   }
   if (DEVPAR) rebase_tree_for_parity(A, 0);
-  cavity_forests<NCAP, ACAP, BS, false, false, true, POSQ>(A, tree_blocks AGBNP_WG_ARG);
+  cavity_forests<NCAP, ACAP, BS, false, SV1, true, POSQ>(A, tree_blocks AGBNP_WG_ARG);
 }
 
 // ---- the forces leave with the last tree launch (TreeOutputs) ------------------------------------------------------

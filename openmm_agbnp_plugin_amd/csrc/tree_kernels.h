@@ -1305,8 +1305,9 @@ int tree_variant_wgs_per_cu(int variant);
 // workgroups of the five-launch mode's cavity launch and of the pseudo-volume launch, as the launchers below make them
 int tree_five_grid(int slots, const PairArgs& P);
 int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A);
-hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
-hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st);
+// (sv_large: the instantiations that also collect the enlarged-radius self volumes, whatever TreeArgs::want_sv_large says)
+hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st, bool sv_large = false);
+hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st, bool sv_large = false);
 hipError_t launch_tree_pseudo(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st);
 
 }  // namespace agbnp

@@ -62,21 +62,24 @@ static hipError_t launch_tree(K kernel, int grid, size_t lds, hipStream_t st, co
   return hipGetLastError();
 }
 
-hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st) {
+hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const TreeArgs& A, hipStream_t st, bool sv_large) {
   if (A.nh <= 0) return hipSuccess;
   const int grid = tree_forest_blocks(variant, global_grid, slots, A);
   return with_tree_variant(variant, [&](auto v) {
     using V = decltype(v);
-    if (A.want_sv_large)  // (the diagnostic self volumes of pass 1: a kernel of their own)
+    if (A.want_sv_large || sv_large)  // (the self volumes of pass 1, a diagnostic or a decomposition's request: a kernel of their own)
       return launch_tree(k_tree_cavity<V::kNodeCap, V::kAtomCap, kBS, V::kGlobal, true>, grid, V::kLdsBytes, st, A);
     return launch_tree(k_tree_cavity<V::kNodeCap, V::kAtomCap, kBS, V::kGlobal, false>, grid, V::kLdsBytes, st, A);
   });
 }
 
 // (round 6: every LDS variant -- rounds 5 left the mode for good at the first store beyond (512, 64))
-hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st) {
+// sv_large: the instantiations that also collect the enlarged-radius self volumes (a decomposition's request, engine_eval.hip;
+// the caller's FP64 positions only: there is no OpenMM-buffer form of that call)
+hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, const PairArgs& P, hipStream_t st, bool sv_large) {
   if (A.nh <= 0 || variant > 3) return hipErrorInvalidValue;  // (the engine leaves the mode before it gets here)
   const bool dev = A.five == 2, posq = A.posq != nullptr;
+  if (sv_large && posq) return hipErrorInvalidValue;
   const int grid = tree_five_grid(slots, P);
   return with_tree_variant(variant, [&](auto v) {
     using V = decltype(v);
@@ -84,6 +87,8 @@ hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, co
       return hipErrorInvalidValue;
     } else {
       constexpr int N = V::kNodeCap, AC = V::kAtomCap;
+      if (sv_large && dev) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, false, true>, grid, V::kLdsBytes, st, A, P, slots);
+      if (sv_large) return launch_tree(k_tree_cavity_five<N, AC, kBS, false, false, true>, grid, V::kLdsBytes, st, A, P, slots);
       if (dev && posq) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, true>, grid, V::kLdsBytes, st, A, P, slots);
       if (dev) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, false>, grid, V::kLdsBytes, st, A, P, slots);
       if (posq) return launch_tree(k_tree_cavity_five<N, AC, kBS, false, true>, grid, V::kLdsBytes, st, A, P, slots);
