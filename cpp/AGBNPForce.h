@@ -75,6 +75,8 @@ class AGBNPForce {
   double solvent_radius;
 };
 
+class Binding;
+
 // The "HIP platform" implementation of the plugin's kernel interface.
 class HipCalcAGBNPForceKernel {
  public:
@@ -195,6 +197,7 @@ class HipCalcAGBNPForceKernel {
   agbnp_hip_context* handle() const { return ctx; }
 
  private:
+  friend class Binding;
   static void gather(const AGBNPForce& force, std::vector<double>& r, std::vector<double>& g, std::vector<double>& a,
                      std::vector<double>& q, std::vector<int>& h) {
     const int n = force.getNumParticles();
@@ -207,6 +210,86 @@ class HipCalcAGBNPForceKernel {
   }
   agbnp_hip_context* ctx;
   int device;
+  int numParticles;
+};
+
+// Binding-energy evaluations (agbnp_hip_binding_*): the complex, its receptor and its ligand in one call.  `force` holds the
+// particles of the complex, `ligandAtoms` 1 to N - 1 distinct atom indices in any order; the rest is the receptor.  With E_RL,
+// E_R, E_L the three systems' energies at the complex's positions: u = E_RL - E_R - E_L, E_lambda = E_R + E_L + lambda u,
+// F_lambda = lambda F^RL + (1 - lambda) F^{R|L}.  A binding evaluation reaches the caller's buffers only if all three members'
+// evaluations completed.  Do not evaluate or finish a member() directly between two finish() calls.
+class Binding {
+ public:
+  enum Member { Complex = 0, Receptor = 1, Ligand = 2 };
+  Binding(const AGBNPForce& force, const std::vector<int>& ligandAtoms, int device = 0, int mode = AGBNP_HIP_MODE_REFERENCE)
+      : b(nullptr), numParticles(force.getNumParticles()) {
+    std::vector<double> r, g, a, q;
+    std::vector<int> h;
+    HipCalcAGBNPForceKernel::gather(force, r, g, a, q, h);
+    if (agbnp_hip_binding_create(&b, numParticles, r.data(), g.data(), a.data(), q.data(), h.data(), ligandAtoms.data(),
+                                 (int)ligandAtoms.size(), (int)force.getVersion(), (int)force.getNonbondedMethod(),
+                                 force.getCutoffDistance(), device) != AGBNP_HIP_OK)
+      throw OpenMMException(agbnp_hip_last_error(nullptr));
+    if (mode != AGBNP_HIP_MODE_REFERENCE) setMode(mode);
+  }
+  ~Binding() { agbnp_hip_binding_destroy(b); }
+  Binding(const Binding&) = delete;
+  Binding& operator=(const Binding&) = delete;
+
+  // forces (3N) are accumulated, E_lambda is returned, u goes to `bindingEnergy`; withheld evaluations are repeated inside
+  double execute(const std::vector<double>& positions, double lambda, std::vector<double>& forces, double& bindingEnergy) {
+    if ((int)positions.size() != 3 * numParticles || (int)forces.size() != 3 * numParticles)
+      throw OpenMMException("Binding::execute(): positions and forces must hold 3N values");
+    double e = 0.0;
+    check(agbnp_hip_binding_execute_host(b, positions.data(), lambda, forces.data(), &e, &bindingEnergy));
+    return e;
+  }
+  // the same without forces: three energy-only evaluations
+  double energy(const std::vector<double>& positions, double lambda, double& bindingEnergy) {
+    if ((int)positions.size() != 3 * numParticles) throw OpenMMException("Binding::energy(): positions must hold 3N values");
+    double e = 0.0;
+    check(agbnp_hip_binding_energy_host(b, positions.data(), lambda, &e, &bindingEnergy));
+    return e;
+  }
+  // device pointers: F_lambda, E_lambda and u are ADDED -- all of them or, if a member is withheld, nothing; asynchronous
+  void executeDevice(const double* dPositions, double lambda, double* dForces, double* dEnergy, double* dBindingEnergy,
+                     void* stream = nullptr) {
+    check(agbnp_hip_binding_execute_device(b, dPositions, lambda, dForces, dEnergy, dBindingEnergy, stream));
+  }
+  void energyDevice(const double* dPositions, double lambda, double* dEnergy, double* dBindingEnergy, void* stream = nullptr) {
+    check(agbnp_hip_binding_energy_device(b, dPositions, lambda, dEnergy, dBindingEnergy, stream));
+  }
+  // binding evaluations since the previous finish() with at least one withheld member: run those again
+  int finish(void* stream = nullptr) {
+    int repeat = 0;
+    check(agbnp_hip_binding_finish(b, stream, &repeat));
+    return repeat;
+  }
+  std::vector<int> withheld() const {
+    const int n = agbnp_hip_binding_withheld_evaluations(b, nullptr, 0);
+    std::vector<int> idx(n > 0 ? n : 0, -1);
+    agbnp_hip_binding_withheld_evaluations(b, idx.data(), (int)idx.size());
+    while (!idx.empty() && idx.back() < 0) idx.pop_back();  // (beyond the log's bitmap evaluations are only counted)
+    return idx;
+  }
+  void expectJump() { check(agbnp_hip_binding_expect_jump(b)); }
+  void setMode(int mode) { check(agbnp_hip_binding_set_mode(b, mode)); }
+  // `force` holds the parameters of the COMPLEX; every member gets its subset
+  void copyParametersToContext(const AGBNPForce& force) {
+    std::vector<double> r, g, a, q;
+    std::vector<int> h;
+    HipCalcAGBNPForceKernel::gather(force, r, g, a, q, h);
+    check(agbnp_hip_binding_update_parameters(b, (int)r.size(), r.data(), g.data(), a.data(), q.data(), h.data()));
+  }
+  // a member's context, for scalars, vectors, poll and wait_verdict; the binding owns it
+  agbnp_hip_context* member(Member which) const { return agbnp_hip_binding_member(b, (int)which); }
+  agbnp_hip_binding* handle() const { return b; }
+
+ private:
+  static void check(int rc) {
+    if (rc != AGBNP_HIP_OK) throw OpenMMException(agbnp_hip_last_error(nullptr));
+  }
+  agbnp_hip_binding* b;
   int numParticles;
 };
 

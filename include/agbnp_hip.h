@@ -272,6 +272,78 @@ int agbnp_hip_energy_group_host(agbnp_hip_context* const* ctxs, int count, const
  * by themselves. */
 int agbnp_hip_expect_jump(agbnp_hip_context* ctx);
 
+/* Binding-energy evaluations: complex, receptor and ligand in ONE call, for BEDAM / single-decoupling protocols, lambda-hybrid
+ * forces and the solvation term of MM-GBSA scores.  A binding is made from the N particles of the complex and a set of ligand
+ * atoms (1 <= nL < N distinct indices, in any order in the argument and at any places in the complex).  The rest is the receptor;
+ * both sub-systems keep ascending complex order.  With x_R and x_L the complex's positions at those atoms and E_RL, E_R, E_L what
+ * a context created from the particles of the complex / the receptor / the ligand returns in the binding's mode and version:
+ *     u(x)         = E_RL(x) - E_R(x_R) - E_L(x_L)
+ *     E_lambda(x)  = E_R + E_L + lambda u = (1 - lambda)(E_R + E_L) + lambda E_RL          dE_lambda / dlambda = u
+ *     F_lambda,i   = lambda F^RL_i + (1 - lambda) F^R_r(i)    (i a receptor atom, r(i) its index in the receptor)
+ *                  = lambda F^RL_i + (1 - lambda) F^L_l(i)    (i a ligand atom)
+ * lambda = 1 is the complex's own evaluation, lambda = 0 the separated pair; lambda is any finite double (values outside [0, 1]
+ * extrapolate; NaN or infinity: AGBNP_HIP_ERR_INVALID_ARGUMENT).
+ *   agbnp_hip_binding_create             checks every argument on the host before any device call -- the ligand indices (in range,
+ *                                        distinct, 1 <= nL < N), the version (0 or 1), the method, the radii: AGBNP_HIP_ERR_INVALID_ARGUMENT
+ *                                        -- and creates the three contexts (the reference's equal-gamma error: AGBNP_HIP_ERR_PARAMETERS)
+ *   agbnp_hip_binding_execute_device     F_lambda ADDED to d_forces[3N], E_lambda to *d_energy, u to *d_binding_energy (each of the
+ *                                        two may be NULL; they must not be the same word); d_positions[3N] the complex's; asynchronous
+ *   agbnp_hip_binding_energy_device      the same without forces: NOTHING is written to any force buffer of the caller (d_energy and
+ *                                        d_binding_energy may each be NULL, not both)
+ *   agbnp_hip_binding_execute_host       synchronous, host buffers: forces ACCUMULATED (+=), the two scalars RETURNED (either pointer
+ *   agbnp_hip_binding_energy_host        may be NULL; energy_host: not both); withheld evaluations are repeated inside, as
+ *                                        agbnp_hip_execute_host does.  Device evaluations still unfinished are harvested first and
+ *                                        reported by the next agbnp_hip_binding_finish, as agbnp_hip_execute_host carries them
+ * All or nothing.  A binding evaluation adds F_lambda, E_lambda and u only if ALL THREE members' evaluations completed.  If any
+ * member is withheld, for any reason (a jump of more than 0.04 nm, a subtree that needs the next capacity variant, ...), nothing
+ * at all reaches the caller's buffers: a hybrid force that is two thirds present would be wrong.  This is decided on the device,
+ * with no host read: the launch that adds the outputs reads the three members' verdict words behind their launches.
+ * One log.  The k-th binding evaluation since the last agbnp_hip_binding_finish is the k-th evaluation of each member.
+ * agbnp_hip_binding_finish drains `stream` (NULL: the complex's own), calls agbnp_hip_finish on the three members and reports as
+ * *must_repeat the number of binding evaluations with at least one withheld member; agbnp_hip_binding_withheld_evaluations gives
+ * the union of their indices (ascending; -1: null binding).  AGBNP_HIP_ERR_CAPACITY from any member is passed through.  The
+ * caller runs the withheld evaluations again and calls finish again, as for a single context.
+ * Members.  agbnp_hip_binding_member (0 the complex, 1 the receptor, 2 the ligand; NULL for anything else) lends a member's
+ * context for agbnp_hip_get_scalar, agbnp_hip_get_vector, agbnp_hip_poll and agbnp_hip_wait_verdict.  The binding owns it: do not
+ * destroy it.  Evaluating or finishing a member directly between two agbnp_hip_binding_finish calls breaks the correspondence of
+ * the indices and is NOT ALLOWED; nothing checks for it.
+ * Forwarding.  agbnp_hip_binding_update_parameters takes the arrays of the COMPLEX and forwards each member its subset (rules and
+ * errors of agbnp_hip_update_parameters); agbnp_hip_binding_set_mode and agbnp_hip_binding_expect_jump forward to all three.
+ * Launches.  A full evaluation is ONE gather launch (one thread per receptor or ligand atom copies three doubles out of
+ * d_positions through the index map: the complex reads d_positions itself, receptor and ligand read buffers of the binding's own
+ * -- also where the ligand is one contiguous range: one rule for every partition), then ONE agbnp_hip_execute_group over
+ * {complex, receptor, ligand} whose forces and energies go to buffers of the binding's own, then ONE combine launch (one thread
+ * per atom of the complex, one of them for the scalars) that adds the outputs if the three verdicts allow it and clears the
+ * binding's buffers WHATEVER the verdict -- a withheld evaluation leaves nothing behind.  The energy-only form: the gather,
+ * agbnp_hip_energy_group, a combine of one small workgroup.  The members share launch sets exactly as the members of any group
+ * do (by version, capacity variant and far-strip test); a member that cannot share runs its own launches: correct, not faster.
+ * A steady run with one d_positions buffer rewrites no argument block (scalar 21 of every member stands still).  Any number of
+ * evaluations may be queued before agbnp_hip_binding_finish: stream order protects the binding's buffers, so use ONE stream
+ * between two finish calls.  The combine is elementwise: in the deterministic mode the outputs are bit-identical from run to run.
+ * Inside a stream capture the device calls return AGBNP_HIP_ERR_INVALID_ARGUMENT, launch nothing and leave the capture usable:
+ * they use group calls, and groups are not captured into graphs.
+ * Every failure of a binding call leaves its message with the calling thread: agbnp_hip_last_error with a NULL context.
+ * No OpenMM-buffer form and no group of several bindings. */
+typedef struct agbnp_hip_binding agbnp_hip_binding;
+int agbnp_hip_binding_create(agbnp_hip_binding** out, int num_particles, const double* radius, const double* gamma,
+                             const double* vdw_alpha, const double* charge, const int* ishydrogen, const int* ligand_atoms,
+                             int num_ligand_atoms, int version, int nonbonded_method, double cutoff_distance, int device);
+int agbnp_hip_binding_execute_device(agbnp_hip_binding* b, const double* d_positions, double lambda, double* d_forces, double* d_energy,
+                                     double* d_binding_energy, void* stream); /* F_lambda, E_lambda, u ADDED; asynchronous */
+int agbnp_hip_binding_energy_device(agbnp_hip_binding* b, const double* d_positions, double lambda, double* d_energy,
+                                    double* d_binding_energy, void* stream); /* no force written */
+int agbnp_hip_binding_execute_host(agbnp_hip_binding* b, const double* positions, double lambda, double* forces, double* energy,
+                                   double* binding_energy);
+int agbnp_hip_binding_energy_host(agbnp_hip_binding* b, const double* positions, double lambda, double* energy, double* binding_energy);
+int agbnp_hip_binding_finish(agbnp_hip_binding* b, void* stream, int* must_repeat);
+int agbnp_hip_binding_withheld_evaluations(const agbnp_hip_binding* b, int* indices, int capacity);
+int agbnp_hip_binding_expect_jump(agbnp_hip_binding* b);
+int agbnp_hip_binding_update_parameters(agbnp_hip_binding* b, int num_particles, const double* radius, const double* gamma,
+                                        const double* vdw_alpha, const double* charge, const int* ishydrogen);
+int agbnp_hip_binding_set_mode(agbnp_hip_binding* b, int mode);
+agbnp_hip_context* agbnp_hip_binding_member(agbnp_hip_binding* b, int which); /* 0 complex, 1 receptor, 2 ligand */
+void agbnp_hip_binding_destroy(agbnp_hip_binding* b);
+
 /* Tells the engine that the contents of the d_atom_index array it last saw have changed (OpenMM has reordered its atoms):
  * the next agbnp_hip_execute_openmm() rebuilds its maps first, and no evaluation is lost to the check.  Optional -- without
  * it the first evaluation after a reorder is withheld and repeated, see above. */

@@ -520,6 +520,176 @@ def energy_group_host(kernels, positions):
     return [float(e) for e in energies]
 
 
+def _ligand_indices(ligand_atoms, n):
+    """The ligand's atoms in ascending order, checked as agbnp_hip_binding_create checks them."""
+    try:
+        given = [int(a) for a in ligand_atoms]
+    except (TypeError, ValueError):
+        raise OpenMMException("BindingEnergy(): ligand_atoms must be a list of atom indices")
+    if not 1 <= len(given) < n:
+        raise OpenMMException(f"BindingEnergy(): the ligand has 1 to N - 1 = {n - 1} atoms, not {len(given)}")
+    if min(given) < 0 or max(given) >= n:
+        raise OpenMMException("BindingEnergy(): ligand atom index out of range")
+    if len(set(given)) != len(given):
+        raise OpenMMException("BindingEnergy(): a ligand atom index is given twice")
+    return np.ascontiguousarray(sorted(given), dtype=np.int32)
+
+
+class BindingEnergy:
+    """Binding-energy evaluations (include/agbnp_hip.h, agbnp_hip_binding_*): the complex, its receptor and its ligand in one
+    call.  `force` holds the particles of the complex, `ligand_atoms` the ligand's atom indices (1 to N - 1 distinct ones, any
+    order); the rest is the receptor, both in ascending complex order.  With E_RL, E_R, E_L the energies of the three systems at
+    the complex's positions,
+
+        u = E_RL - E_R - E_L,   E_lam = E_R + E_L + lam u,   F_lam = lam F_RL + (1 - lam) F_(R|L),   dE_lam / dlam = u.
+
+    A binding evaluation reaches the caller's buffers only if all three members' evaluations completed (decided on the device);
+    finish() and withheld() report the binding evaluations that are missing.  Do not evaluate or finish a member() directly
+    between two finish() calls."""
+
+    def __init__(self, force, ligand_atoms, device=0, mode="reference"):
+        self._h = None
+        n = force.getNumParticles()
+        lig = _ligand_indices(ligand_atoms, n)  # (before the library is touched)
+        mode_bits = HipCalcAGBNPForceKernel.MODES[mode]
+        lib = _lib.load()
+        r, g, a, q, h = force._arrays()
+        handle = C.c_void_p()
+        rc = lib.agbnp_hip_binding_create(C.byref(handle), n, _dp(r), _dp(g), _dp(a), _dp(q), _ip(h), _ip(lig), len(lig),
+                                          force.getVersion(), force.getNonbondedMethod(), force.getCutoffDistance(), device)
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(None))
+        self._h = handle
+        self._device = device
+        self.numParticles = n
+        self._ligand = lig
+        self._receptor = np.setdiff1d(np.arange(n, dtype=np.int32), lig).astype(np.int32)
+        self._mode = 0
+        if mode_bits:
+            self.set_mode(mode)
+
+    @property
+    def ligand_atoms(self):
+        """The ligand's atoms in the ligand context's order (ascending complex order)."""
+        return self._ligand.copy()
+
+    @property
+    def receptor_atoms(self):
+        return self._receptor.copy()
+
+    def _need(self):
+        if self._h is None:
+            raise OpenMMException("BindingEnergy: the binding has been released")
+
+    def _check(self, rc):
+        if rc != _lib.OK:
+            raise OpenMMException(_lib.last_error(None))
+
+    def _positions(self, positions, who):
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
+        if pos.size != 3 * self.numParticles:
+            raise OpenMMException(f"{who}(): wrong number of positions")
+        return pos
+
+    def execute(self, positions, lam):
+        """(E_lam, u, forces[N, 3]) at the complex's positions (N x 3, nm).  Withheld evaluations are repeated inside."""
+        self._need()
+        pos = self._positions(positions, "execute")
+        forces = np.zeros((self.numParticles, 3))
+        e, u = C.c_double(0.0), C.c_double(0.0)
+        self._check(_lib.load().agbnp_hip_binding_execute_host(self._h, _dp(pos), float(lam), _dp(forces), C.byref(e), C.byref(u)))
+        return e.value, u.value, forces
+
+    def energy(self, positions, lam):
+        """(E_lam, u) without forces: three energy-only evaluations.  Withheld evaluations are repeated inside."""
+        self._need()
+        pos = self._positions(positions, "energy")
+        e, u = C.c_double(0.0), C.c_double(0.0)
+        self._check(_lib.load().agbnp_hip_binding_energy_host(self._h, _dp(pos), float(lam), C.byref(e), C.byref(u)))
+        return e.value, u.value
+
+    def execute_device(self, d_positions, lam, d_forces, d_energy=None, d_binding_energy=None, stream=None):
+        """Raw FP64 device pointers (ints): F_lam is ADDED to d_forces[3N], E_lam to *d_energy, u to *d_binding_energy (either
+        may be None) -- all of it or, if any member's evaluation is withheld, nothing.  Asynchronous; call finish()."""
+        self._need()
+        self._check(_lib.load().agbnp_hip_binding_execute_device(self._h, C.c_void_p(d_positions), float(lam), C.c_void_p(d_forces),
+                                                                 C.c_void_p(d_energy or 0), C.c_void_p(d_binding_energy or 0),
+                                                                 C.c_void_p(stream or 0)))
+
+    def energy_device(self, d_positions, lam, d_energy=None, d_binding_energy=None, stream=None):
+        """Energy-only form of execute_device(): no force buffer is written; d_energy and d_binding_energy not both None."""
+        self._need()
+        self._check(_lib.load().agbnp_hip_binding_energy_device(self._h, C.c_void_p(d_positions), float(lam), C.c_void_p(d_energy or 0),
+                                                                C.c_void_p(d_binding_energy or 0), C.c_void_p(stream or 0)))
+
+    def finish(self, stream=None):
+        """Drains the stream, finishes the three members and returns the number of binding evaluations since the previous
+        finish() with at least one withheld member: NOTHING of those reached the caller's buffers; run them again (withheld())."""
+        self._need()
+        rep = C.c_int(0)
+        self._check(_lib.load().agbnp_hip_binding_finish(self._h, C.c_void_p(stream or 0), C.byref(rep)))
+        return int(rep.value)
+
+    def withheld(self):
+        """Indices (enqueue order since the finish() before the last one) of the binding evaluations the last finish() reported."""
+        self._need()
+        lib = _lib.load()
+        n = lib.agbnp_hip_binding_withheld_evaluations(self._h, None, 0)
+        idx = np.full(max(n, 1), -1, dtype=np.int32)
+        lib.agbnp_hip_binding_withheld_evaluations(self._h, _ip(idx), n)
+        return [int(k) for k in idx if k >= 0]
+
+    def expect_jump(self):
+        """The next evaluation's positions are unrelated to the last ones: forwarded to all three members."""
+        self._need()
+        self._check(_lib.load().agbnp_hip_binding_expect_jump(self._h))
+
+    def set_mode(self, mode):
+        self._need()
+        self._mode = HipCalcAGBNPForceKernel.MODES[mode]
+        self._check(_lib.load().agbnp_hip_binding_set_mode(self._h, self._mode))
+
+    def copyParametersToContext(self, force):
+        """`force` holds the parameters of the COMPLEX; every member gets its subset."""
+        self._need()
+        r, g, a, q, h = force._arrays()
+        self._check(_lib.load().agbnp_hip_binding_update_parameters(self._h, len(r), _dp(r), _dp(g), _dp(a), _dp(q), _ip(h)))
+
+    def member(self, which):
+        """A HipCalcAGBNPForceKernel view of a member -- 0 or "complex", 1 or "receptor", 2 or "ligand" -- for scalar(), vector(),
+        poll() and wait_verdict().  The view does not own the handle: it is valid until release()."""
+        self._need()
+        which = {"complex": 0, "receptor": 1, "ligand": 2}.get(which, which)
+        if which not in (0, 1, 2):
+            raise OpenMMException("BindingEnergy.member(): 0 the complex, 1 the receptor, 2 the ligand")
+        view = _MemberView(self._device)
+        view._h = C.c_void_p(_lib.load().agbnp_hip_binding_member(self._h, which))
+        view._mode = self._mode
+        view.numParticles = (self.numParticles, len(self._receptor), len(self._ligand))[which]
+        return view
+
+    def release(self):
+        if self._h is not None:
+            _lib.load().agbnp_hip_binding_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class _MemberView(HipCalcAGBNPForceKernel):
+    """A member of a BindingEnergy: the binding owns the handle."""
+
+    def initialize(self, force):
+        raise OpenMMException("a member of a BindingEnergy is created by the binding")
+
+    def release(self):
+        self._h = None
+
+
 def host_tables(radius, ishydrogen):
     """I4 tables from the engine's host code (no device needed)."""
     lib = _lib.load()

@@ -23,6 +23,10 @@ SYMBOLS = [
     "agbnp_hip_execute_group", "agbnp_hip_execute_group_host",
     "agbnp_hip_energy_group", "agbnp_hip_energy_group_host", "agbnp_hip_expect_jump",
     "agbnp_hip_decompose_host", "agbnp_hip_decompose_device",
+    "agbnp_hip_binding_create", "agbnp_hip_binding_execute_device", "agbnp_hip_binding_energy_device",
+    "agbnp_hip_binding_execute_host", "agbnp_hip_binding_energy_host", "agbnp_hip_binding_finish",
+    "agbnp_hip_binding_withheld_evaluations", "agbnp_hip_binding_expect_jump", "agbnp_hip_binding_update_parameters",
+    "agbnp_hip_binding_set_mode", "agbnp_hip_binding_member", "agbnp_hip_binding_destroy",
 ]
 
 _lib = None
@@ -73,6 +77,20 @@ def load():
     lib.agbnp_hip_expect_jump.argtypes = [vp]
     lib.agbnp_hip_decompose_host.argtypes = [vp, dp, dp, dp]
     lib.agbnp_hip_decompose_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.agbnp_hip_binding_create.argtypes = [C.POINTER(vp), C.c_int, dp, dp, dp, dp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
+    lib.agbnp_hip_binding_execute_device.argtypes = [vp, vp, C.c_double, vp, vp, vp, vp]
+    lib.agbnp_hip_binding_energy_device.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    lib.agbnp_hip_binding_execute_host.argtypes = [vp, dp, C.c_double, dp, dp, dp]
+    lib.agbnp_hip_binding_energy_host.argtypes = [vp, dp, C.c_double, dp, dp]
+    lib.agbnp_hip_binding_finish.argtypes = [vp, vp, ip]
+    lib.agbnp_hip_binding_withheld_evaluations.argtypes = [vp, ip, C.c_int]
+    lib.agbnp_hip_binding_expect_jump.argtypes = [vp]
+    lib.agbnp_hip_binding_update_parameters.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip]
+    lib.agbnp_hip_binding_set_mode.argtypes = [vp, C.c_int]
+    lib.agbnp_hip_binding_member.argtypes = [vp, C.c_int]
+    lib.agbnp_hip_binding_member.restype = vp
+    lib.agbnp_hip_binding_destroy.argtypes = [vp]
+    lib.agbnp_hip_binding_destroy.restype = None
     lib.agbnp_hip_atom_order_changed.argtypes = [vp]
     lib.agbnp_hip_finish.argtypes = [vp, vp, ip]
     lib.agbnp_hip_poll.argtypes = [vp, ip, ip]

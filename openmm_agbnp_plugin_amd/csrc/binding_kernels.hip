@@ -1,0 +1,103 @@
+// Binding-energy evaluations (agbnp_hip_binding_*, include/agbnp_hip.h; host side: engine_binding.hip): the two launches round
+// the group call that evaluates the complex, the receptor and the ligand.
+//   k_binding_gather   in front: the receptor's and the ligand's positions out of the complex's array, through the index map
+//   k_binding_combine  behind: F_lambda = lambda F^RL + (1 - lambda) F^{R|L}, E_lambda = (1 - lambda)(E_R + E_L) + lambda E_RL and
+//                      u = E_RL - E_R - E_L ADDED to the caller's buffers -- if and only if ALL THREE members' evaluations are
+//                      complete.  The members are gated one by one (each adds nothing when it is withheld itself); what ties the
+//                      three verdicts together is this launch, which reads every member's verdict words behind the group's
+//                      launches, the way k_decompose reads its context's.
+// The members ADD into buffers of the binding's own.  The combine launch CLEARS them whatever the verdict: a withheld binding
+// evaluation whose receptor was complete would otherwise leave the receptor's forces behind for the next one.
+// Both are streaming kernels, one thread per atom, elementwise: no order-dependent sum, so the deterministic mode's outputs are
+// bit-identical from run to run as the members' are.  The gather's indexed read is the only uncoalesced access.
+//
+// The verdict test is the engine's own (evaluation_overflowed), read as a device function as the decomposition's unit reads it:
+// this unit launches none of the kernels of pair_bodies.h.
+#define AGBNP_GROUP_TU
+#include "pair_bodies.h"
+
+#include "binding_kernels.h"
+
+namespace agbnp {
+
+__global__ __launch_bounds__(256) void k_binding_gather(int n, const double* __restrict__ pos, const int* __restrict__ sub2complex,
+                                                        double* __restrict__ sub_pos) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const size_t src = 3 * (size_t)sub2complex[t], dst = 3 * (size_t)t;
+  const double x = pos[src], y = pos[src + 1], z = pos[src + 2];
+  sub_pos[dst] = x;
+  sub_pos[dst + 1] = y;
+  sub_pos[dst + 2] = z;
+}
+
+// all three members complete?  (the same for every thread of the launch: scalar loads)
+__device__ __forceinline__ bool binding_complete(const BindingVerdicts& v) {
+  bool ok = true;
+#pragma unroll
+  for (int m = 0; m < kBindingMembers; m++) {
+    // (five == 2, a member that was once captured into a graph: its block names set 0 and the device's counter, which its GB
+    // launch has advanced, names the set -- rebase_for_parity with after_role = 1)
+    const int par = v.five[m] == 2 ? (v.epoch[m][0] + 1) & 1 : 0;
+    ok = ok && !evaluation_overflowed(v.estatus[m] + kStatBlockStride * par);
+  }
+  return ok;
+}
+
+__device__ __forceinline__ void binding_scalars(bool ok, double lambda, double* __restrict__ e, double* __restrict__ d_energy,
+                                                double* __restrict__ d_binding) {
+  // (atomic loads, so that they are VECTOR loads: the address is uniform, and as plain loads they become scalar loads, which the
+  // clears below -- vector stores with no data dependence on them -- are issued past: an energy word then reads as the zero
+  // that was about to be written.  Loads and stores of one wave through the vector pipe stay in order.)
+  const double e_rl = __hip_atomic_load(&e[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const double e_r = __hip_atomic_load(&e[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const double e_l = __hip_atomic_load(&e[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  e[0] = e[1] = e[2] = 0.0;
+  if (!ok) return;
+  if (d_energy) d_energy[0] += (1.0 - lambda) * (e_r + e_l) + lambda * e_rl;
+  if (d_binding) d_binding[0] += e_rl - e_r - e_l;
+}
+
+__global__ __launch_bounds__(256) void k_binding_combine(int n, BindingVerdicts v, double lambda, const int* __restrict__ complex2sub,
+                                                         double* __restrict__ f_complex, double* __restrict__ f_sub,
+                                                         double* __restrict__ e, double* __restrict__ d_forces,
+                                                         double* __restrict__ d_energy, double* __restrict__ d_binding) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool ok = binding_complete(v);
+  if (i == 0) binding_scalars(ok, lambda, e, d_energy, d_binding);  // the role lane
+  const size_t a = 3 * (size_t)i, s = 3 * (size_t)complex2sub[i];
+  const double w = 1.0 - lambda;
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const double f_rl = f_complex[a + d], f_own = f_sub[s + d];
+    f_complex[a + d] = 0.0;
+    f_sub[s + d] = 0.0;
+    if (ok) d_forces[a + d] += lambda * f_rl + w * f_own;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_binding_combine_energy(BindingVerdicts v, double lambda, double* __restrict__ e,
+                                                               double* __restrict__ d_energy, double* __restrict__ d_binding) {
+  if (threadIdx.x == 0) binding_scalars(binding_complete(v), lambda, e, d_energy, d_binding);
+}
+
+hipError_t launch_binding_gather(int n, const double* pos, const int* sub2complex, double* sub_pos, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, pos, sub2complex, sub_pos);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_combine(int n, const BindingVerdicts& v, double lambda, const int* complex2sub, double* f_complex,
+                                  double* f_sub, double* e, double* d_forces, double* d_energy, double* d_binding, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_combine, dim3((n + 255) / 256), dim3(256), 0, st, n, v, lambda, complex2sub, f_complex, f_sub, e,
+                     d_forces, d_energy, d_binding);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_combine_energy(const BindingVerdicts& v, double lambda, double* e, double* d_energy, double* d_binding,
+                                         hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_combine_energy, dim3(1), dim3(64), 0, st, v, lambda, e, d_energy, d_binding);
+  return hipGetLastError();
+}
+
+}  // namespace agbnp

@@ -1,0 +1,347 @@
+// Binding-energy evaluations (agbnp_hip_binding_*, include/agbnp_hip.h): one object that owns the contexts of a complex, its
+// receptor and its ligand, and one call per evaluation of
+//   u = E_RL(x) - E_R(x_R) - E_L(x_L),   E_lambda = E_R + E_L + lambda u,   F_lambda = lambda F^RL + (1 - lambda) F^{R|L}.
+// An evaluation is one gather launch (binding_kernels.hip: both sub-systems' positions out of the caller's array -- also where
+// the ligand is one contiguous range: one launch, one rule), ONE agbnp_hip_execute_group / agbnp_hip_energy_group over the three
+// members through the public entry points, so the members share launch sets exactly as any group's do, and one combine launch that
+// reads all three verdicts on the device and adds to the caller's buffers all or nothing.  The k-th binding evaluation since the
+// last agbnp_hip_binding_finish() is the k-th evaluation of every member: the binding's log is the union of the members'.
+// Messages of failed binding calls are the calling thread's agbnp_hip_last_error(NULL).
+#include "binding_kernels.h"
+#include "engine_context.h"
+
+struct agbnp_hip_binding {
+  agbnp_hip_context* m[kBindingMembers] = {nullptr, nullptr, nullptr};  // complex, receptor, ligand
+  int n = 0, nr = 0, nl = 0, device = 0;
+  std::vector<int> sub2complex;  // [n] the receptor's atoms in ascending complex order, then the ligand's
+  std::vector<int> complex2sub;  // [n] the inverse
+  DevBuf<int> d_maps;            // [2n] both, in that order
+  // [3n] the members' own positions (receptor, ligand) | [3n] the complex's forces | [3n] the receptor's and the ligand's | [3]
+  // the three energies: what the members read and ADD to, cleared by every combine launch
+  DevBuf<double> d_work;
+  // the host entry points' staging: [3n] positions | [3n] F_lambda | E_lambda, u
+  DevBuf<double> d_host;
+  std::vector<double> h_host;
+  int enqueued = 0;              // binding evaluations of the device entry points since the last finish
+  std::vector<void*> streams;    // caller streams they went to
+  std::vector<int> withheld;     // what the last finish found
+  int withheld_count = 0;
+  std::vector<int> carried;      // withheld device evaluations that a host entry point in between had to harvest
+  int carried_count = 0, carried_seq = 0;
+
+  double* sub_pos() const { return d_work.p; }
+  double* f_complex() const { return d_work.p + 3 * (size_t)n; }
+  double* f_sub() const { return d_work.p + 6 * (size_t)n; }
+  double* energies() const { return d_work.p + 9 * (size_t)n; }
+};
+
+namespace {
+int binding_fail(int code, const std::string& msg) {
+  g_create_error = msg;
+  return code;
+}
+
+// a member's call failed: its message becomes the binding's
+int member_fail(const agbnp_hip_binding* b, int code, const char* who) {
+  for (const agbnp_hip_context* c : b->m)
+    if (c && !c->err.empty()) return binding_fail(code, std::string(who) + ": " + c->err);
+  return binding_fail(code, std::string(who) + ": a member's call failed");
+}
+
+void clear_member_errors(agbnp_hip_binding* b) {
+  for (agbnp_hip_context* c : b->m) c->err.clear();
+}
+
+#define BINDING_TRY(who, call)                                                                                       \
+  do {                                                                                                               \
+    hipError_t e__ = (call);                                                                                         \
+    if (e__ != hipSuccess) return binding_fail(AGBNP_HIP_ERR_DEVICE, std::string(who) + ": " #call ": " + hipGetErrorString(e__)); \
+  } while (0)
+
+// one binding evaluation on `stream`; d_forces null: the energy-only form
+int binding_enqueue(agbnp_hip_binding* b, const double* d_pos, double lambda, double* d_forces, double* d_energy, double* d_binding,
+                    void* stream, const char* who) {
+  agbnp_hip_context* const c0 = b->m[0];
+  clear_member_errors(b);
+  hipStream_t st;
+  if (enter(c0, stream, &st) != AGBNP_HIP_OK) return member_fail(b, AGBNP_HIP_ERR_DEVICE, who);
+  if (is_capturing(st))
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                        std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
+  const int n = b->n, nr = b->nr;
+  BINDING_TRY(who, launch_binding_gather(n, d_pos, b->d_maps.p, b->sub_pos(), st));
+  const double* pos[kBindingMembers] = {d_pos, b->sub_pos(), b->sub_pos() + 3 * (size_t)nr};
+  double* frc[kBindingMembers] = {b->f_complex(), b->f_sub(), b->f_sub() + 3 * (size_t)nr};
+  double* ene[kBindingMembers] = {b->energies(), b->energies() + 1, b->energies() + 2};
+  // (a NULL stream is the complex's own: the group call joins the other members' streams to it on both sides)
+  const int rc = d_forces ? agbnp_hip_execute_group(b->m, kBindingMembers, pos, frc, ene, stream)
+                          : agbnp_hip_energy_group(b->m, kBindingMembers, pos, ene, stream);
+  if (rc != AGBNP_HIP_OK) return member_fail(b, rc, who);
+  BindingVerdicts v;
+  for (int k = 0; k < kBindingMembers; k++) {  // (the members' blocks name this evaluation's words until their next evaluation)
+    const PairArgs& P = b->m[k]->P;
+    v.estatus[k] = P.estatus;
+    v.epoch[k] = P.epoch;
+    v.five[k] = P.five;
+  }
+  if (d_forces)
+    BINDING_TRY(who, launch_binding_combine(n, v, lambda, b->d_maps.p + n, b->f_complex(), b->f_sub(), b->energies(), d_forces,
+                                            d_energy, d_binding, st));
+  else
+    BINDING_TRY(who, launch_binding_combine_energy(v, lambda, b->energies(), d_energy, d_binding, st));
+  return AGBNP_HIP_OK;
+}
+
+// drains `stream`, finishes the three members and forms the union of their logs: `out` the indices (ascending), *count their
+// number (a member that only counted evaluations beyond its log's bitmap raises it)
+int binding_harvest(agbnp_hip_binding* b, void* stream, std::vector<int>& out, int* count, const char* who) {
+  clear_member_errors(b);
+  hipStream_t st;
+  if (enter(b->m[0], stream, &st) != AGBNP_HIP_OK) return member_fail(b, AGBNP_HIP_ERR_DEVICE, who);
+  BINDING_TRY(who, hipStreamSynchronize(st));
+  out.clear();
+  int most = 0, first_rc = AGBNP_HIP_OK;
+  for (agbnp_hip_context* c : b->m) {
+    int rep = 0;
+    const int rc = agbnp_hip_finish(c, stream, &rep);
+    if (rc != AGBNP_HIP_OK && first_rc == AGBNP_HIP_OK) first_rc = rc;
+    most = std::max(most, rep);
+    out.insert(out.end(), c->withheld.begin(), c->withheld.end());
+  }
+  std::sort(out.begin(), out.end());
+  out.erase(std::unique(out.begin(), out.end()), out.end());
+  *count = std::max(most, (int)out.size());
+  if (first_rc != AGBNP_HIP_OK) return member_fail(b, first_rc, who);  // (AGBNP_HIP_ERR_CAPACITY passes through)
+  return AGBNP_HIP_OK;
+}
+
+// device evaluations that are still unfinished when a host entry point needs the log: harvested now, handed to the next finish
+int binding_carry(agbnp_hip_binding* b, const char* who) {
+  if (b->enqueued == 0) return AGBNP_HIP_OK;
+  BINDING_TRY(who, hipSetDevice(b->device));
+  for (void* s : b->streams) BINDING_TRY(who, hipStreamSynchronize((hipStream_t)s));
+  std::vector<int> bad;
+  int count = 0;
+  const int rc = binding_harvest(b, nullptr, bad, &count, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int k : bad) b->carried.push_back(k + b->carried_seq);
+  b->carried_count += count;
+  b->carried_seq += b->enqueued;
+  b->enqueued = 0;
+  return AGBNP_HIP_OK;
+}
+
+// agbnp_hip_binding_execute_host and (forces null) agbnp_hip_binding_energy_host: the device path on the binding's staging
+// buffers and the complex's own stream; a withheld evaluation is repeated here
+int binding_host(agbnp_hip_binding* b, const double* pos, double lambda, double* forces, double* energy, double* binding_energy,
+                 const char* who) {
+  int rc = binding_carry(b, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  const size_t n3 = 3 * (size_t)b->n;
+  BINDING_TRY(who, hipSetDevice(b->device));
+  if (b->d_host.p == nullptr) BINDING_TRY(who, b->d_host.alloc(2 * n3 + 2));
+  b->h_host.resize(n3 + 2);
+  const hipStream_t st = b->m[0]->stream;
+  double* const d_pos = b->d_host.p;
+  double* const d_out = b->d_host.p + n3;  // [3n] forces, E_lambda, u
+  for (int attempt = 0; attempt < 10; attempt++) {
+    BINDING_TRY(who, hipMemcpyAsync(d_pos, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
+    BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (n3 + 2), st));
+    rc = binding_enqueue(b, d_pos, lambda, forces ? d_out : nullptr, d_out + n3, d_out + n3 + 1, nullptr, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+    BINDING_TRY(who, hipMemcpyAsync(b->h_host.data(), d_out, sizeof(double) * (n3 + 2), hipMemcpyDeviceToHost, st));
+    std::vector<int> bad;
+    int count = 0;
+    rc = binding_harvest(b, nullptr, bad, &count, who);  // (waits for the stream)
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (count) continue;
+    for (size_t k = 0; k < n3 && forces; k++) forces[k] += b->h_host[k];
+    if (energy) *energy = b->h_host[n3];
+    if (binding_energy) *binding_energy = b->h_host[n3 + 1];
+    return AGBNP_HIP_OK;
+  }
+  return binding_fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
+}
+
+int binding_device(agbnp_hip_binding* b, const double* d_pos, double lambda, double* d_forces, bool energy_only, double* d_energy,
+                   double* d_binding, void* stream, const char* who) {
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_pos || (!energy_only && !d_forces) || (energy_only && !d_energy && !d_binding))
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (!std::isfinite(lambda)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": lambda must be finite");
+  const int rc = binding_enqueue(b, d_pos, lambda, energy_only ? nullptr : d_forces, d_energy, d_binding, stream, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  b->enqueued++;
+  if (stream && std::find(b->streams.begin(), b->streams.end(), stream) == b->streams.end()) b->streams.push_back(stream);
+  return AGBNP_HIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int agbnp_hip_binding_create(agbnp_hip_binding** out, int n, const double* radius, const double* gamma, const double* vdw_alpha,
+                             const double* charge, const int* ishydrogen, const int* ligand_atoms, int num_ligand_atoms, int version,
+                             int nonbonded_method, double cutoff, int device) {
+  const char* who = "agbnp_hip_binding_create";
+  if (out) *out = nullptr;
+  // every argument is checked here, on the host, before any device call
+  if (!out || n <= 0 || !radius || !gamma || !vdw_alpha || !charge || !ishydrogen || !ligand_atoms)
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer or non-positive particle count");
+  if (num_ligand_atoms < 1 || num_ligand_atoms >= n)
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the ligand has 1 to N - 1 atoms, not " + std::to_string(num_ligand_atoms));
+  if (version != 0 && version != 1)
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": illegal version number (versions 0 and 1 only)");
+  if (nonbonded_method < 0 || nonbonded_method > 2) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": illegal nonbonded method");
+  if (device < 0) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative device index");
+  std::vector<char> is_ligand(n, 0);
+  for (int k = 0; k < num_ligand_atoms; k++) {
+    const int a = ligand_atoms[k];
+    if (a < 0 || a >= n) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": ligand atom index out of range: " + std::to_string(a));
+    if (is_ligand[a]) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": ligand atom index given twice: " + std::to_string(a));
+    is_ligand[a] = 1;
+  }
+  for (int i = 0; i < n; i++)
+    if (!(radius[i] > 0.0)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": particle radius must be positive");
+
+  agbnp_hip_binding* b = new agbnp_hip_binding();
+  b->n = n;
+  b->nl = num_ligand_atoms;
+  b->nr = n - num_ligand_atoms;
+  b->device = device;
+  b->sub2complex.reserve(n);
+  for (int pass = 0; pass < 2; pass++)  // the receptor's atoms, then the ligand's, both in ascending complex order
+    for (int i = 0; i < n; i++)
+      if (is_ligand[i] == pass) b->sub2complex.push_back(i);
+  b->complex2sub.resize(n);
+  for (int t = 0; t < n; t++) b->complex2sub[b->sub2complex[t]] = t;
+
+  auto bail = [&](int code) {  // (the message is the failed agbnp_hip_create's, or already set)
+    agbnp_hip_binding_destroy(b);
+    return code;
+  };
+  // the complex first: its parameter checks (the reference's equal-gamma error among them) run on the host before its first
+  // device call, and a subset of equal gammas is equal
+  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {n, b->nr, b->nl};
+  for (int k = 0; k < kBindingMembers; k++) {
+    std::vector<double> r(count[k]), g(count[k]), a(count[k]), q(count[k]);
+    std::vector<int> h(count[k]);
+    for (int t = 0; t < count[k]; t++) {
+      const int i = k == 0 ? t : b->sub2complex[first[k] + t];
+      r[t] = radius[i], g[t] = gamma[i], a[t] = vdw_alpha[i], q[t] = charge[i], h[t] = ishydrogen[i];
+    }
+    const int rc = agbnp_hip_create(&b->m[k], count[k], r.data(), g.data(), a.data(), q.data(), h.data(), version, nonbonded_method,
+                                    cutoff, device);
+    if (rc != AGBNP_HIP_OK) return bail(rc);
+  }
+  std::vector<int> maps(b->sub2complex);
+  maps.insert(maps.end(), b->complex2sub.begin(), b->complex2sub.end());
+  hipError_t e = b->d_maps.upload(maps);
+  if (e == hipSuccess) e = b->d_work.alloc(9 * (size_t)n + 3, 0);
+  if (e != hipSuccess) {
+    binding_fail(AGBNP_HIP_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return bail(AGBNP_HIP_ERR_DEVICE);
+  }
+  *out = b;
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_binding_execute_device(agbnp_hip_binding* b, const double* d_positions, double lambda, double* d_forces, double* d_energy,
+                                     double* d_binding_energy, void* stream) {
+  return binding_device(b, d_positions, lambda, d_forces, false, d_energy, d_binding_energy, stream, "agbnp_hip_binding_execute_device");
+}
+
+int agbnp_hip_binding_energy_device(agbnp_hip_binding* b, const double* d_positions, double lambda, double* d_energy,
+                                    double* d_binding_energy, void* stream) {
+  return binding_device(b, d_positions, lambda, nullptr, true, d_energy, d_binding_energy, stream, "agbnp_hip_binding_energy_device");
+}
+
+int agbnp_hip_binding_execute_host(agbnp_hip_binding* b, const double* positions, double lambda, double* forces, double* energy,
+                                   double* binding_energy) {
+  const char* who = "agbnp_hip_binding_execute_host";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!positions || !forces) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (!std::isfinite(lambda)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": lambda must be finite");
+  return binding_host(b, positions, lambda, forces, energy, binding_energy, who);
+}
+
+int agbnp_hip_binding_energy_host(agbnp_hip_binding* b, const double* positions, double lambda, double* energy, double* binding_energy) {
+  const char* who = "agbnp_hip_binding_energy_host";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!positions || (!energy && !binding_energy)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (!std::isfinite(lambda)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": lambda must be finite");
+  return binding_host(b, positions, lambda, nullptr, energy, binding_energy, who);
+}
+
+int agbnp_hip_binding_finish(agbnp_hip_binding* b, void* stream, int* must_repeat) {
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  int count = 0;
+  std::vector<int> bad;
+  const int rc = binding_harvest(b, stream, bad, &count, "agbnp_hip_binding_finish");
+  // (evaluations that a host entry point in between had to harvest were enqueued before everything read now: they come first)
+  b->withheld = b->carried;
+  for (int k : bad) b->withheld.push_back(k + b->carried_seq);
+  b->withheld_count = b->carried_count + count;
+  b->carried.clear();
+  b->carried_count = b->carried_seq = 0;
+  b->enqueued = 0;
+  b->streams.erase(std::remove(b->streams.begin(), b->streams.end(), stream), b->streams.end());
+  if (must_repeat) *must_repeat = b->withheld_count;
+  return rc;
+}
+
+int agbnp_hip_binding_withheld_evaluations(const agbnp_hip_binding* b, int* indices, int capacity) {
+  if (!b) return -1;
+  for (int k = 0; k < capacity && k < (int)b->withheld.size() && indices; k++) indices[k] = b->withheld[k];
+  return b->withheld_count;
+}
+
+int agbnp_hip_binding_expect_jump(agbnp_hip_binding* b) {
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  for (agbnp_hip_context* c : b->m) (void)agbnp_hip_expect_jump(c);
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_binding_update_parameters(agbnp_hip_binding* b, int n, const double* radius, const double* gamma, const double* vdw_alpha,
+                                        const double* charge, const int* ishydrogen) {
+  const char* who = "agbnp_hip_binding_update_parameters";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!radius || !gamma || !vdw_alpha || !charge || !ishydrogen) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (n != b->n) return binding_fail(AGBNP_HIP_ERR_PARAMETERS, "updateParametersInContext: The number of AGBNP particles has changed");
+  // (a member drains its own stream and the caller streams it has noted; the binding's buffers are not touched)
+  clear_member_errors(b);
+  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {n, b->nr, b->nl};
+  for (int k = 0; k < kBindingMembers; k++) {
+    std::vector<double> r(count[k]), g(count[k]), a(count[k]), q(count[k]);
+    std::vector<int> h(count[k]);
+    for (int t = 0; t < count[k]; t++) {
+      const int i = k == 0 ? t : b->sub2complex[first[k] + t];
+      r[t] = radius[i], g[t] = gamma[i], a[t] = vdw_alpha[i], q[t] = charge[i], h[t] = ishydrogen[i];
+    }
+    const int rc = agbnp_hip_update_parameters(b->m[k], count[k], r.data(), g.data(), a.data(), q.data(), h.data());
+    if (rc != AGBNP_HIP_OK) return member_fail(b, rc, who);
+  }
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_binding_set_mode(agbnp_hip_binding* b, int mode) {
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  clear_member_errors(b);
+  for (agbnp_hip_context* c : b->m) {
+    const int rc = agbnp_hip_set_mode(c, mode);
+    if (rc != AGBNP_HIP_OK) return member_fail(b, rc, "agbnp_hip_binding_set_mode");
+  }
+  return AGBNP_HIP_OK;
+}
+
+agbnp_hip_context* agbnp_hip_binding_member(agbnp_hip_binding* b, int which) {
+  if (!b || which < 0 || which >= kBindingMembers) return nullptr;
+  return b->m[which];
+}
+
+void agbnp_hip_binding_destroy(agbnp_hip_binding* b) {
+  if (!b) return;
+  for (agbnp_hip_context* c : b->m) agbnp_hip_destroy(c);  // (each drains its own stream)
+  delete b;  // (hipFree waits for what is still in flight on a caller's stream)
+}
+
+}  // extern "C"

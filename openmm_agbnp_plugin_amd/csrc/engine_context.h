@@ -3,6 +3,7 @@
 //   engine_setup.hip   a context's life: create, update_parameters, destroy; its device arrays and argument blocks
 //   engine_eval.hip    one evaluation of one context: the request, its launches, the harvest, the single-context entry points
 //   engine_group.hip   replica groups: the launches that several contexts share
+//   engine_binding.hip binding-energy evaluations: three contexts behind one call, on top of the public group entry points
 //   engine_report.hip  what a caller reads back: scalars, vectors, tables, kernel times, the diagnostic hooks
 //
 // Mirrors the life cycle of the reference's platform kernel
