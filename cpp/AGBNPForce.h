@@ -284,6 +284,7 @@ class Binding {
   // a member's context, for scalars, vectors, poll and wait_verdict; the binding owns it
   agbnp_hip_context* member(Member which) const { return agbnp_hip_binding_member(b, (int)which); }
   agbnp_hip_binding* handle() const { return b; }
+  int getNumParticles() const { return numParticles; }
 
  private:
   static void check(int rc) {
@@ -292,5 +293,53 @@ class Binding {
   agbnp_hip_binding* b;
   int numParticles;
 };
+
+// Binding groups (agbnp_hip_binding_execute_group_host): one evaluation of every binding in `bindings` at its own lambda -- one
+// gather launch, the members' evaluations as replica groups, one combine launch.  positions[k] (3N_k) read, forces[k]
+// accumulated, E_lambda of every binding returned, u in `bindingEnergies`.  A binding whose evaluation was withheld is repeated
+// inside.
+inline std::vector<double> executeBindingGroup(const std::vector<Binding*>& bindings, const std::vector<std::vector<double>>& positions,
+                                               const std::vector<double>& lambdas, std::vector<std::vector<double>>& forces,
+                                               std::vector<double>& bindingEnergies) {
+  const size_t n = bindings.size();
+  if (n < 1 || n > AGBNP_HIP_MAX_BINDING_GROUP) throw OpenMMException("executeBindingGroup(): a binding group has 1 to 16 bindings");
+  if (positions.size() != n || forces.size() != n || lambdas.size() != n)
+    throw OpenMMException("executeBindingGroup(): one position array, one force array and one lambda per binding");
+  std::vector<agbnp_hip_binding*> bs(n);
+  std::vector<const double*> pos(n);
+  std::vector<double*> frc(n);
+  for (size_t i = 0; i < n; i++) {
+    if (!bindings[i]) throw OpenMMException("executeBindingGroup(): null binding");
+    const size_t n3 = 3 * (size_t)bindings[i]->getNumParticles();
+    if (positions[i].size() != n3 || forces[i].size() != n3) throw OpenMMException("executeBindingGroup(): arrays must hold 3N values");
+    bs[i] = bindings[i]->handle(), pos[i] = positions[i].data(), frc[i] = forces[i].data();
+  }
+  std::vector<double> energies(n, 0.0);
+  bindingEnergies.assign(n, 0.0);
+  if (agbnp_hip_binding_execute_group_host(bs.data(), (int)n, pos.data(), lambdas.data(), frc.data(), energies.data(),
+                                           bindingEnergies.data()) != AGBNP_HIP_OK)
+    throw OpenMMException(agbnp_hip_last_error(nullptr));
+  return energies;
+}
+
+// The same without forces (agbnp_hip_binding_energy_group_host): no force is written anywhere.
+inline std::vector<double> energyBindingGroup(const std::vector<Binding*>& bindings, const std::vector<std::vector<double>>& positions,
+                                              const std::vector<double>& lambdas, std::vector<double>& bindingEnergies) {
+  const size_t n = bindings.size();
+  if (n < 1 || n > AGBNP_HIP_MAX_BINDING_GROUP) throw OpenMMException("energyBindingGroup(): a binding group has 1 to 16 bindings");
+  if (positions.size() != n || lambdas.size() != n) throw OpenMMException("energyBindingGroup(): one position array and one lambda per binding");
+  std::vector<agbnp_hip_binding*> bs(n);
+  std::vector<const double*> pos(n);
+  for (size_t i = 0; i < n; i++) {
+    if (!bindings[i]) throw OpenMMException("energyBindingGroup(): null binding");
+    if (positions[i].size() != 3 * (size_t)bindings[i]->getNumParticles()) throw OpenMMException("energyBindingGroup(): arrays must hold 3N values");
+    bs[i] = bindings[i]->handle(), pos[i] = positions[i].data();
+  }
+  std::vector<double> energies(n, 0.0);
+  bindingEnergies.assign(n, 0.0);
+  if (agbnp_hip_binding_energy_group_host(bs.data(), (int)n, pos.data(), lambdas.data(), energies.data(), bindingEnergies.data()) != AGBNP_HIP_OK)
+    throw OpenMMException(agbnp_hip_last_error(nullptr));
+  return energies;
+}
 
 }  // namespace AGBNPPlugin

@@ -323,7 +323,7 @@ int agbnp_hip_expect_jump(agbnp_hip_context* ctx);
  * Inside a stream capture the device calls return AGBNP_HIP_ERR_INVALID_ARGUMENT, launch nothing and leave the capture usable:
  * they use group calls, and groups are not captured into graphs.
  * Every failure of a binding call leaves its message with the calling thread: agbnp_hip_last_error with a NULL context.
- * No OpenMM-buffer form and no group of several bindings. */
+ * No OpenMM-buffer form; groups of several bindings: below. */
 typedef struct agbnp_hip_binding agbnp_hip_binding;
 int agbnp_hip_binding_create(agbnp_hip_binding** out, int num_particles, const double* radius, const double* gamma,
                              const double* vdw_alpha, const double* charge, const int* ishydrogen, const int* ligand_atoms,
@@ -343,6 +343,48 @@ int agbnp_hip_binding_update_parameters(agbnp_hip_binding* b, int num_particles,
 int agbnp_hip_binding_set_mode(agbnp_hip_binding* b, int mode);
 agbnp_hip_context* agbnp_hip_binding_member(agbnp_hip_binding* b, int which); /* 0 complex, 1 receptor, 2 ligand */
 void agbnp_hip_binding_destroy(agbnp_hip_binding* b);
+
+/* Binding groups: ONE call that enqueues an evaluation of each of `count` bindings (1 .. AGBNP_HIP_MAX_BINDING_GROUP), for lambda
+ * ladders -- BEDAM and single-decoupling replica exchange over E_lambda = E_R + E_L + lambda u -- and for scoring several
+ * complexes at once.  The contract of agbnp_hip_execute_group(), carried over to bindings: for every binding k
+ * the call does exactly what agbnp_hip_binding_execute_device(bindings[k], d_positions[k], lambda_k, d_forces[k], d_energies[k],
+ * d_binding_energies[k], stream) does (the energy forms: agbnp_hip_binding_energy_device()), with the same numbers.  F_lambda,
+ * E_lambda and u are ADDED.  All or nothing holds PER BINDING: a binding with a withheld member adds nothing and leaves nothing
+ * behind, the other bindings of the call are not affected.  The evaluation is the next one of each binding's own log:
+ * agbnp_hip_binding_finish(), _withheld_evaluations, _expect_jump and _member work per binding, and group calls and single calls
+ * on the same bindings may be interleaved in any order.  The bindings need not be the same complex.
+ * Arguments.  d_positions, d_forces, d_energies, d_binding_energies are HOST arrays of `count` DEVICE pointers.  Entries of
+ * d_energies / d_binding_energies may be NULL, and so may the two arrays (every entry NULL); in the energy form the two entries of
+ * one binding may not both be NULL and may not be the same word.  Position buffers MAY be shared between bindings (two rungs
+ * scored at one conformation); the outputs of two bindings -- forces [3 N_k], energy words, u words, each against every other --
+ * must not overlap.
+ * d_lambdas is a DEVICE array of `count` doubles.  The combine launch reads it WHEN IT RUNS, in stream order: a kernel enqueued
+ * earlier on the same stream may have written it, with no host call in between (a lambda exchange decided on the device).  The
+ * values are not checked on the device.  The host forms take a host array and check every value for finiteness.
+ * Errors.  Checked on the host before anything is launched or any binding changes, AGBNP_HIP_ERR_INVALID_ARGUMENT with the message
+ * in the thread's agbnp_hip_last_error(NULL): count outside 1 .. 16, a NULL binding, the same binding twice, bindings on different
+ * devices, a NULL position or force pointer, overlapping outputs.  Inside a stream capture the call is refused, launches nothing
+ * and leaves the capture usable.
+ * Launches.  ONE gather launch over the atoms of all bindings, the members' evaluations through agbnp_hip_execute_group() /
+ * agbnp_hip_energy_group() -- ONE call over all members where 3 count <= AGBNP_HIP_MAX_GROUP, else THREE, by kind: all complexes,
+ * all receptors, all ligands (same-kind members of one system have the same version and, at related geometries, the same capacity
+ * variant: one launch set each) --, ONE combine launch over all bindings.  A ladder of 16 rungs: 1 + 3 x 5 + 1 = 17 launches
+ * where 16 single calls make 112.  With a NULL stream the work is ordered on the first binding's complex's own stream and every
+ * binding's agbnp_hip_binding_finish(b, NULL, ..) drains it.
+ * The host forms stage the inputs, run the device path and finish; forces are ACCUMULATED (+=), energies[k] and
+ * binding_energies[k] RETURNED (either array may be NULL; the energy form: not both).  A binding whose evaluation was withheld is
+ * repeated alone, as agbnp_hip_binding_execute_host() repeats; unfinished device evaluations are carried to the next finish. */
+#define AGBNP_HIP_MAX_BINDING_GROUP 16
+int agbnp_hip_binding_execute_group(agbnp_hip_binding* const* bindings, int count, const double* const* d_positions,
+                                    const double* d_lambdas, double* const* d_forces, double* const* d_energies,
+                                    double* const* d_binding_energies, void* stream);
+int agbnp_hip_binding_energy_group(agbnp_hip_binding* const* bindings, int count, const double* const* d_positions,
+                                   const double* d_lambdas, double* const* d_energies, double* const* d_binding_energies,
+                                   void* stream);
+int agbnp_hip_binding_execute_group_host(agbnp_hip_binding* const* bindings, int count, const double* const* positions,
+                                         const double* lambdas, double* const* forces, double* energies, double* binding_energies);
+int agbnp_hip_binding_energy_group_host(agbnp_hip_binding* const* bindings, int count, const double* const* positions,
+                                        const double* lambdas, double* energies, double* binding_energies);
 
 /* Tells the engine that the contents of the d_atom_index array it last saw have changed (OpenMM has reordered its atoms):
  * the next agbnp_hip_execute_openmm() rebuilds its maps first, and no evaluation is lost to the check.  Optional -- without

@@ -680,6 +680,114 @@ class BindingEnergy:
             pass
 
 
+def _binding_handles(bindings, who):
+    bindings = list(bindings)
+    if not 1 <= len(bindings) <= _lib.MAX_BINDING_GROUP:
+        raise OpenMMException(f"{who}(): a binding group has 1 to {_lib.MAX_BINDING_GROUP} bindings, not {len(bindings)}")
+    for b in bindings:
+        if not isinstance(b, BindingEnergy):
+            raise OpenMMException(f"{who}(): members must be BindingEnergy objects")
+        b._need()
+    if len({id(b) for b in bindings}) != len(bindings):
+        raise OpenMMException(f"{who}(): the same binding twice")
+    return bindings, (C.c_void_p * len(bindings))(*[b._h for b in bindings])
+
+
+def _binding_pointers(who, n, **lists):
+    """ctypes arrays of device pointers, one entry per binding; None for a list that is None (every entry NULL)."""
+    out = []
+    for name, ptrs in lists.items():
+        if ptrs is None:
+            out.append(None)
+            continue
+        if len(ptrs) != n:
+            raise OpenMMException(f"{who}(): {name} has {len(ptrs)} entries for {n} bindings")
+        out.append((C.c_void_p * n)(*[int(p or 0) for p in ptrs]))
+    return out
+
+
+def _host_lambdas(who, lambdas, n):
+    lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
+    if lam.size != n:
+        raise OpenMMException(f"{who}(): {lam.size} lambdas for {n} bindings")
+    if not np.isfinite(lam).all():
+        raise OpenMMException(f"{who}(): lambda must be finite")
+    return lam
+
+
+def binding_execute_group(bindings, d_positions, d_lambdas, d_forces, d_energies=None, d_binding_energies=None, stream=None):
+    """Binding groups (include/agbnp_hip.h, agbnp_hip_binding_execute_group): one call that enqueues an evaluation of every
+    BindingEnergy in `bindings` -- one gather launch, the members' evaluations as replica groups, one combine launch.
+    d_positions, d_forces, d_energies, d_binding_energies: lists of raw FP64 device pointers (ints), one per binding; entries of
+    the last two may be None, and so may the lists.  d_lambdas: ONE raw device pointer to len(bindings) doubles, read by the
+    combine launch when it runs -- a kernel enqueued earlier on the stream may have written them.  F_lam, E_lam and u are ADDED,
+    per binding all or nothing.  Asynchronous; each binding's finish() reports its own withheld evaluations."""
+    who = "binding_execute_group"
+    bindings, hs = _binding_handles(bindings, who)
+    n = len(bindings)
+    pos, frc, ene, u = _binding_pointers(who, n, d_positions=d_positions, d_forces=d_forces, d_energies=d_energies,
+                                         d_binding_energies=d_binding_energies)
+    if pos is None or frc is None or not d_lambdas:
+        raise OpenMMException(f"{who}(): d_positions, d_forces and d_lambdas are needed")
+    rc = _lib.load().agbnp_hip_binding_execute_group(hs, n, pos, C.c_void_p(d_lambdas), frc, ene, u, C.c_void_p(stream or 0))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(None))
+
+
+def binding_energy_group(bindings, d_positions, d_lambdas, d_energies=None, d_binding_energies=None, stream=None):
+    """Energy-only form of binding_execute_group() (agbnp_hip_binding_energy_group): no force buffer is written; of a binding's
+    two scalar pointers at least one is given, and they are different words."""
+    who = "binding_energy_group"
+    bindings, hs = _binding_handles(bindings, who)
+    n = len(bindings)
+    pos, ene, u = _binding_pointers(who, n, d_positions=d_positions, d_energies=d_energies, d_binding_energies=d_binding_energies)
+    if pos is None or not d_lambdas:
+        raise OpenMMException(f"{who}(): d_positions and d_lambdas are needed")
+    rc = _lib.load().agbnp_hip_binding_energy_group(hs, n, pos, C.c_void_p(d_lambdas), ene, u, C.c_void_p(stream or 0))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(None))
+
+
+def binding_execute_group_host(bindings, positions, lambdas, forces):
+    """Synchronous twin of binding_execute_group() for host buffers: positions[k] (N_k x 3) are read, forces[k] (C-contiguous
+    float64 arrays of 3 N_k values) are accumulated in place; returns the lists (E_lam, u).  A binding whose evaluation was
+    withheld is repeated inside."""
+    who = "binding_execute_group_host"
+    bindings, hs = _binding_handles(bindings, who)
+    n = len(bindings)
+    if len(positions) != n or len(forces) != n:
+        raise OpenMMException(f"{who}(): {len(positions)} positions and {len(forces)} force arrays for {n} bindings")
+    lam = _host_lambdas(who, lambdas, n)
+    pos = [b._positions(p, who) for b, p in zip(bindings, positions)]
+    for b, f in zip(bindings, forces):
+        if not (isinstance(f, np.ndarray) and f.dtype == np.float64 and f.flags.c_contiguous and f.size == 3 * b.numParticles):
+            raise OpenMMException(f"{who}(): forces must be C-contiguous float64 arrays of 3N values")
+    dpp = C.POINTER(C.c_double)
+    e, u = np.zeros(n), np.zeros(n)
+    rc = _lib.load().agbnp_hip_binding_execute_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), _dp(lam),
+                                                          (dpp * n)(*[_dp(f) for f in forces]), _dp(e), _dp(u))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(None))
+    return [float(x) for x in e], [float(x) for x in u]
+
+
+def binding_energy_group_host(bindings, positions, lambdas):
+    """Synchronous twin of binding_energy_group() for host buffers: returns the lists (E_lam, u)."""
+    who = "binding_energy_group_host"
+    bindings, hs = _binding_handles(bindings, who)
+    n = len(bindings)
+    if len(positions) != n:
+        raise OpenMMException(f"{who}(): {len(positions)} positions for {n} bindings")
+    lam = _host_lambdas(who, lambdas, n)
+    pos = [b._positions(p, who) for b, p in zip(bindings, positions)]
+    dpp = C.POINTER(C.c_double)
+    e, u = np.zeros(n), np.zeros(n)
+    rc = _lib.load().agbnp_hip_binding_energy_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), _dp(lam), _dp(e), _dp(u))
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(None))
+    return [float(x) for x in e], [float(x) for x in u]
+
+
 class _MemberView(HipCalcAGBNPForceKernel):
     """A member of a BindingEnergy: the binding owns the handle."""
 

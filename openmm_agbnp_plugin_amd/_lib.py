@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("AGBNP_HIP_LIBRARY") or os.path.join(_HERE, "libagbnp_
 
 OK, ERR_INVALID_ARGUMENT, ERR_PARAMETERS, ERR_DEVICE, ERR_CAPACITY, ERR_TIMEOUT = 0, 1, 2, 3, 4, 5
 MAX_GROUP = 16  # AGBNP_HIP_MAX_GROUP: members of one agbnp_hip_execute_group call
+MAX_BINDING_GROUP = 16  # AGBNP_HIP_MAX_BINDING_GROUP: bindings of one agbnp_hip_binding_execute_group call
 DECOMPOSITION_TERMS = 4  # AGBNP_HIP_DECOMPOSITION_TERMS: planes of agbnp_hip_decompose_*
 
 # every symbol include/agbnp_hip.h declares
@@ -27,6 +28,8 @@ SYMBOLS = [
     "agbnp_hip_binding_execute_host", "agbnp_hip_binding_energy_host", "agbnp_hip_binding_finish",
     "agbnp_hip_binding_withheld_evaluations", "agbnp_hip_binding_expect_jump", "agbnp_hip_binding_update_parameters",
     "agbnp_hip_binding_set_mode", "agbnp_hip_binding_member", "agbnp_hip_binding_destroy",
+    "agbnp_hip_binding_execute_group", "agbnp_hip_binding_energy_group",
+    "agbnp_hip_binding_execute_group_host", "agbnp_hip_binding_energy_group_host",
 ]
 
 _lib = None
@@ -91,6 +94,10 @@ def load():
     lib.agbnp_hip_binding_member.restype = vp
     lib.agbnp_hip_binding_destroy.argtypes = [vp]
     lib.agbnp_hip_binding_destroy.restype = None
+    lib.agbnp_hip_binding_execute_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
+    lib.agbnp_hip_binding_energy_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), vp]
+    lib.agbnp_hip_binding_execute_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp, C.POINTER(dp), dp, dp]
+    lib.agbnp_hip_binding_energy_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp, dp, dp]
     lib.agbnp_hip_atom_order_changed.argtypes = [vp]
     lib.agbnp_hip_finish.argtypes = [vp, vp, ip]
     lib.agbnp_hip_poll.argtypes = [vp, ip, ip]

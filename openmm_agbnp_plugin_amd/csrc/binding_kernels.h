@@ -29,4 +29,37 @@ hipError_t launch_binding_combine(int n, const BindingVerdicts& v, double lambda
 hipError_t launch_binding_combine_energy(const BindingVerdicts& v, double lambda, double* e, double* d_energy, double* d_binding,
                                          hipStream_t st);
 
+// ---- Binding groups (agbnp_hip_binding_execute_group / _energy_group): the same two launches, made once for up to
+// kMaxBindingGroup bindings.  Every binding keeps the grid it would launch alone; the grids lie side by side and a workgroup finds
+// its binding by its number (first[]), as the workgroups of a replica group's launches do (group_args.h: GroupLaunch::first).
+constexpr int kMaxBindingGroup = 16;  // AGBNP_HIP_MAX_BINDING_GROUP (include/agbnp_hip.h)
+
+// One binding's words of a group launch: 120 bytes.
+struct BindingGroupMember {
+  BindingVerdicts v;   // [64 bytes] the three members' verdicts on the evaluation that has just been enqueued
+  const int* maps;     // [2n] sub2complex, complex2sub
+  double* work;        // [9n + 3] the binding's own: sub-system positions | F^RL | F^{R|L} | the three energies
+  const double* pos;   // the caller's positions [3n]
+  double* forces;      // the caller's F_lambda [3n] (null: the energy-only form), E_lambda and u (either may be null)
+  double* energy;
+  double* binding;
+  int n;               // atoms of the complex
+};
+
+// The kernel argument of a group launch, by value: 72 + 16 * 120 + 8 = 2000 bytes (static_assert in binding_kernels.hip), inside
+// the 4096 bytes that a kernel's arguments may take.  Every word a workgroup reads of it is uniform: scalar loads.
+struct BindingGroupArgs {
+  int count;                        // bindings of the call
+  int first[kMaxBindingGroup + 1];  // first workgroup of every binding (256 atoms each); first[count] = the grid
+  BindingGroupMember m[kMaxBindingGroup];
+  const double* lambdas;            // [count] DEVICE words, read by the combine launch when it runs
+};
+
+// One launch for all bindings: m[k].work[3 t] = m[k].pos[3 sub2complex[t]] for t < m[k].n.
+hipError_t launch_binding_gather_group(const BindingGroupArgs& G, hipStream_t st);
+// One launch for all bindings: per binding what launch_binding_combine does, with lambda = lambdas[k].
+hipError_t launch_binding_combine_group(const BindingGroupArgs& G, hipStream_t st);
+// The energy-only form: one small workgroup per binding, the scalars alone.
+hipError_t launch_binding_combine_energy_group(const BindingGroupArgs& G, hipStream_t st);
+
 }  // namespace agbnp

@@ -10,6 +10,9 @@
 // evaluation whose receptor was complete would otherwise leave the receptor's forces behind for the next one.
 // Both are streaming kernels, one thread per atom, elementwise: no order-dependent sum, so the deterministic mode's outputs are
 // bit-identical from run to run as the members' are.  The gather's indexed read is the only uncoalesced access.
+// Binding groups (agbnp_hip_binding_execute_group) make the same two launches ONCE for up to 16 bindings:
+// k_binding_gather_group, k_binding_combine_group and k_binding_combine_energy_group below, every binding's grid side by side,
+// its words by value in the kernel argument (BindingGroupArgs) and its lambda read from device memory when the launch runs.
 //
 // The verdict test is the engine's own (evaluation_overflowed), read as a device function as the decomposition's unit reads it:
 // this unit launches none of the kernels of pair_bodies.h.
@@ -80,6 +83,85 @@ __global__ __launch_bounds__(256) void k_binding_combine(int n, BindingVerdicts 
 __global__ __launch_bounds__(64) void k_binding_combine_energy(BindingVerdicts v, double lambda, double* __restrict__ e,
                                                                double* __restrict__ d_energy, double* __restrict__ d_binding) {
   if (threadIdx.x == 0) binding_scalars(binding_complete(v), lambda, e, d_energy, d_binding);
+}
+
+// ---- binding groups: the same launches once for all bindings of a call (binding_kernels.h: BindingGroupArgs) ----
+static_assert(sizeof(BindingGroupMember) == 120 && sizeof(BindingGroupArgs) == 2000, "BindingGroupArgs: the size binding_kernels.h states");
+static_assert(sizeof(BindingGroupArgs) <= 4096, "a kernel's arguments take 4096 bytes at most");
+
+// the binding of the workgroup and the workgroup's number inside that binding's grid (both uniform; group_args.h: group_index)
+__device__ __forceinline__ int binding_group_index(const BindingGroupArgs& G, int& blk) {
+  const int b = (int)blockIdx.x;
+  int k = 0;
+#pragma unroll
+  for (int j = 1; j < kMaxBindingGroup; j++)
+    if (j < G.count && b >= G.first[j]) k = j;
+  blk = b - G.first[k];
+  return k;
+}
+
+__global__ __launch_bounds__(256) void k_binding_gather_group(const BindingGroupArgs G) {
+  int blk;
+  const BindingGroupMember& B = G.m[binding_group_index(G, blk)];
+  const int t = blk * 256 + threadIdx.x;
+  if (t >= B.n) return;
+  const double* __restrict__ pos = B.pos;
+  double* __restrict__ sub_pos = B.work;
+  const size_t src = 3 * (size_t)B.maps[t], dst = 3 * (size_t)t;
+  const double x = pos[src], y = pos[src + 1], z = pos[src + 2];
+  sub_pos[dst] = x;
+  sub_pos[dst + 1] = y;
+  sub_pos[dst + 2] = z;
+}
+
+// lambda of binding k: a device word that a kernel earlier on the stream may have written.  (An atomic load, so that it is a
+// VECTOR load like the role lane's reads of the energy words: see binding_scalars.)
+__device__ __forceinline__ double binding_group_lambda(const BindingGroupArgs& G, int k) {
+  return __hip_atomic_load(&G.lambdas[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void k_binding_combine_group(const BindingGroupArgs G) {
+  int blk;
+  const int k = binding_group_index(G, blk);
+  const BindingGroupMember& B = G.m[k];
+  const int i = blk * 256 + threadIdx.x, n = B.n;
+  if (i >= n) return;
+  const bool ok = binding_complete(B.v);
+  const double lambda = binding_group_lambda(G, k);
+  double* __restrict__ f_complex = B.work + 3 * (size_t)n;
+  double* __restrict__ f_sub = B.work + 6 * (size_t)n;
+  double* __restrict__ d_forces = B.forces;
+  if (i == 0) binding_scalars(ok, lambda, B.work + 9 * (size_t)n, B.energy, B.binding);  // the binding's role lane
+  const size_t a = 3 * (size_t)i, s = 3 * (size_t)B.maps[n + i];
+  const double w = 1.0 - lambda;
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const double f_rl = f_complex[a + d], f_own = f_sub[s + d];
+    f_complex[a + d] = 0.0;
+    f_sub[s + d] = 0.0;
+    if (ok) d_forces[a + d] += lambda * f_rl + w * f_own;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_binding_combine_energy_group(const BindingGroupArgs G) {
+  const int k = blockIdx.x;  // (one workgroup per binding)
+  const BindingGroupMember& B = G.m[k];
+  if (threadIdx.x == 0) binding_scalars(binding_complete(B.v), binding_group_lambda(G, k), B.work + 9 * (size_t)B.n, B.energy, B.binding);
+}
+
+hipError_t launch_binding_gather_group(const BindingGroupArgs& G, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_gather_group, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_combine_group(const BindingGroupArgs& G, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_combine_group, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_combine_energy_group(const BindingGroupArgs& G, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_combine_energy_group, dim3(G.count), dim3(64), 0, st, G);
+  return hipGetLastError();
 }
 
 hipError_t launch_binding_gather(int n, const double* pos, const int* sub2complex, double* sub_pos, hipStream_t st) {

@@ -6,6 +6,8 @@
 // members through the public entry points, so the members share launch sets exactly as any group's do, and one combine launch that
 // reads all three verdicts on the device and adds to the caller's buffers all or nothing.  The k-th binding evaluation since the
 // last agbnp_hip_binding_finish() is the k-th evaluation of every member: the binding's log is the union of the members'.
+// Binding groups (agbnp_hip_binding_execute_group and its kin, at the end of the unnamed namespace) evaluate up to 16 bindings on
+// one gather launch, one to three group calls and one combine launch, each binding's lambda read from device memory.
 // Messages of failed binding calls are the calling thread's agbnp_hip_last_error(NULL).
 #include "binding_kernels.h"
 #include "engine_context.h"
@@ -28,6 +30,10 @@ struct agbnp_hip_binding {
   int withheld_count = 0;
   std::vector<int> carried;      // withheld device evaluations that a host entry point in between had to harvest
   int carried_count = 0, carried_seq = 0;
+  // binding groups (below): the event that joins streams where a group call with a NULL stream runs on several, and the device
+  // words the host forms stage their lambdas in (both made on first use, by the call's first binding)
+  hipEvent_t group_event = nullptr;
+  DevBuf<double> d_group_lambdas;
 
   double* sub_pos() const { return d_work.p; }
   double* f_complex() const { return d_work.p + 3 * (size_t)n; }
@@ -175,6 +181,229 @@ int binding_device(agbnp_hip_binding* b, const double* d_pos, double lambda, dou
   if (stream && std::find(b->streams.begin(), b->streams.end(), stream) == b->streams.end()) b->streams.push_back(stream);
   return AGBNP_HIP_OK;
 }
+
+// ---- Binding groups (agbnp_hip_binding_execute_group and its kin): several bindings' evaluations on one gather launch, the
+// members' evaluations through the public group entry points -- one call over all 3 count members where they fit a group, else
+// one call per kind (complexes, receptors, ligands: same-kind members of one system share a launch set) -- and one combine
+// launch, which takes every binding's lambda from device memory.  Per binding exactly what binding_enqueue does.
+
+bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a && b && a < b + nb && b < a + na; }
+
+// what every group form checks of its bindings, before anything is launched or changed
+int check_bindings(agbnp_hip_binding* const* bs, int count, const char* who) {
+  if (!bs || count < 1 || count > kMaxBindingGroup)
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a binding group has 1 to 16 bindings, not " + std::to_string(count));
+  for (int i = 0; i < count; i++) {
+    if (!bs[i]) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null binding");
+    if (bs[i]->device != bs[0]->device) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": bindings on different devices");
+    for (int j = 0; j < i; j++)
+      if (bs[j] == bs[i]) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the same binding twice");
+  }
+  return AGBNP_HIP_OK;
+}
+
+// `to` waits for what is on `from` now (b's event: made on first use)
+int binding_join(agbnp_hip_binding* b, hipStream_t from, hipStream_t to, const char* who) {
+  if (from == to) return AGBNP_HIP_OK;
+  if (!b->group_event) BINDING_TRY(who, hipEventCreateWithFlags(&b->group_event, hipEventDisableTiming));
+  BINDING_TRY(who, hipEventRecord(b->group_event, from));
+  BINDING_TRY(who, hipStreamWaitEvent(to, b->group_event, 0));
+  return AGBNP_HIP_OK;
+}
+
+// one evaluation of every binding on `stream` (NULL: the first complex's own); the arguments have been checked.  d_forces null:
+// the energy-only form; d_energies / d_bindings null: every entry null.
+int binding_group_enqueue(agbnp_hip_binding* const* bs, int count, const double* const* d_pos, const double* d_lambdas,
+                          double* const* d_forces, double* const* d_energies, double* const* d_bindings, void* stream, const char* who) {
+  agbnp_hip_binding* const b0 = bs[0];
+  for (int k = 0; k < count; k++) clear_member_errors(bs[k]);
+  hipStream_t st;
+  if (enter(b0->m[0], stream, &st) != AGBNP_HIP_OK) return member_fail(b0, AGBNP_HIP_ERR_DEVICE, who);
+  if (is_capturing(st))
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                        std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
+  BindingGroupArgs G;
+  std::memset(&G, 0, sizeof(G));
+  G.count = count;
+  G.lambdas = d_lambdas;
+  agbnp_hip_context* ctxs[kBindingMembers * kMaxBindingGroup];
+  const double* pos[kBindingMembers * kMaxBindingGroup];
+  double *frc[kBindingMembers * kMaxBindingGroup], *ene[kBindingMembers * kMaxBindingGroup];
+  // members in one call: binding by binding; in one call per kind: kind by kind
+  const bool one_call = kBindingMembers * count <= kMaxGroup;
+  for (int k = 0; k < count; k++) {
+    agbnp_hip_binding* const b = bs[k];
+    BindingGroupMember& B = G.m[k];
+    B.maps = b->d_maps.p;
+    B.work = b->d_work.p;
+    B.pos = d_pos[k];
+    B.forces = d_forces ? d_forces[k] : nullptr;
+    B.energy = d_energies ? d_energies[k] : nullptr;
+    B.binding = d_bindings ? d_bindings[k] : nullptr;
+    B.n = b->n;
+    G.first[k + 1] = G.first[k] + (b->n + 255) / 256;
+    const double* const p[kBindingMembers] = {d_pos[k], b->sub_pos(), b->sub_pos() + 3 * (size_t)b->nr};
+    double* const f[kBindingMembers] = {b->f_complex(), b->f_sub(), b->f_sub() + 3 * (size_t)b->nr};
+    for (int m = 0; m < kBindingMembers; m++) {
+      const int at = one_call ? kBindingMembers * k + m : count * m + k;
+      ctxs[at] = b->m[m];
+      pos[at] = p[m];
+      frc[at] = f[m];
+      ene[at] = b->energies() + m;
+    }
+  }
+  // (a NULL stream: a single call on another binding runs on THAT binding's complex's stream, and the gather writes every
+  // binding's own buffers -- the group's stream waits for what those streams hold, as group_device joins its members')
+  for (int k = 1; k < count && !stream; k++) {
+    const int rc = binding_join(b0, bs[k]->m[0]->stream, st, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+  }
+  BINDING_TRY(who, launch_binding_gather_group(G, st));
+  const int calls = one_call ? 1 : kBindingMembers, per_call = one_call ? kBindingMembers * count : count;
+  for (int c = 0; c < calls; c++) {
+    const int at = c * per_call;
+    // (a NULL stream is the call's first member's own: the receptors' and the ligands' calls run on other streams than the
+    // gather and the combine, and are joined to the first complex's on both sides)
+    const hipStream_t own = stream ? st : ctxs[at]->stream;
+    int rc = binding_join(b0, st, own, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+    rc = d_forces ? agbnp_hip_execute_group(ctxs + at, per_call, pos + at, frc + at, ene + at, stream)
+                  : agbnp_hip_energy_group(ctxs + at, per_call, pos + at, ene + at, stream);
+    if (rc != AGBNP_HIP_OK) {
+      // No combine launch will read what the calls before this one added to the bindings' buffers: they are cleared here, as
+      // well as the device still allows, so that nothing stale is added to by a later evaluation.  After a failure behind the
+      // first call the members that ran have logged an evaluation the binding has not: the message says so.
+      (void)binding_join(b0, own, st, who);
+      for (int k = 0; k < count; k++)
+        (void)hipMemsetAsync(bs[k]->f_complex(), 0, sizeof(double) * (6 * (size_t)bs[k]->n + kBindingMembers), st);
+      const char* note = c > 0 ? " (members of an earlier call of this group have evaluated: finish the bindings and discard that log)" : "";
+      for (int k = 0; k < count; k++)
+        for (const agbnp_hip_context* m : bs[k]->m)
+          if (!m->err.empty()) return binding_fail(rc, std::string(who) + ": " + m->err + note);
+      return binding_fail(rc, std::string(who) + ": a member's call failed" + note);
+    }
+    rc = binding_join(b0, own, st, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+  }
+  for (int k = 0; k < count; k++)  // (the members' blocks name this evaluation's words until their next evaluation)
+    for (int m = 0; m < kBindingMembers; m++) {
+      const PairArgs& P = bs[k]->m[m]->P;
+      G.m[k].v.estatus[m] = P.estatus;
+      G.m[k].v.epoch[m] = P.epoch;
+      G.m[k].v.five[m] = P.five;
+    }
+  if (d_forces)
+    BINDING_TRY(who, launch_binding_combine_group(G, st));
+  else
+    BINDING_TRY(who, launch_binding_combine_energy_group(G, st));
+  // (a NULL stream: every other binding's agbnp_hip_binding_finish(NULL) drains its own complex's stream, which waits for the combine)
+  for (int k = 1; k < count && !stream; k++) {
+    const int rc = binding_join(b0, st, bs[k]->m[0]->stream, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+  }
+  return AGBNP_HIP_OK;
+}
+
+int binding_group_device(agbnp_hip_binding* const* bs, int count, const double* const* d_pos, const double* d_lambdas,
+                         double* const* d_forces, bool energy_only, double* const* d_energies, double* const* d_bindings, void* stream,
+                         const char* who) {
+  int rc = check_bindings(bs, count, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  if (!d_pos || !d_lambdas || (!energy_only && !d_forces)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  for (int i = 0; i < count; i++) {
+    double* const ei = d_energies ? d_energies[i] : nullptr;
+    double* const ui = d_bindings ? d_bindings[i] : nullptr;
+    if (!d_pos[i] || (!energy_only && !d_forces[i])) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (energy_only && !ei && !ui)
+      return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a binding's energy and binding-energy pointers are both null");
+    if (energy_only && ei == ui)
+      return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a binding's energy and binding-energy words are the same");
+    const size_t ni = energy_only ? 0 : 3 * (size_t)bs[i]->n;
+    double* const fi = energy_only ? nullptr : d_forces[i];
+    for (int j = 0; j < i; j++) {
+      double* const ej = d_energies ? d_energies[j] : nullptr;
+      double* const uj = d_bindings ? d_bindings[j] : nullptr;
+      const size_t nj = energy_only ? 0 : 3 * (size_t)bs[j]->n;
+      double* const fj = energy_only ? nullptr : d_forces[j];
+      const double* const a[3] = {fi, ei, ui};
+      const double* const b[3] = {fj, ej, uj};
+      const size_t na[3] = {ni, 1, 1}, nb[3] = {nj, 1, 1};
+      for (int x = 0; x < 3; x++)
+        for (int y = 0; y < 3; y++)
+          if (spans_overlap(a[x], na[x], b[y], nb[y]))
+            return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": output buffers of two bindings overlap");
+    }
+  }
+  rc = binding_group_enqueue(bs, count, d_pos, d_lambdas, energy_only ? nullptr : d_forces, d_energies, d_bindings, stream, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_binding* const b = bs[i];
+    b->enqueued++;
+    if (stream && std::find(b->streams.begin(), b->streams.end(), stream) == b->streams.end()) b->streams.push_back(stream);
+  }
+  return AGBNP_HIP_OK;
+}
+
+// agbnp_hip_binding_execute_group_host and (forces null) agbnp_hip_binding_energy_group_host: the device path on every binding's
+// staging buffers and the first complex's own stream; a binding whose evaluation was withheld is repeated alone (binding_host)
+int binding_group_host(agbnp_hip_binding* const* bs, int count, const double* const* positions, const double* lambdas,
+                       double* const* forces, bool energy_only, double* energies, double* binding_energies, const char* who) {
+  int rc = check_bindings(bs, count, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  if (!positions || !lambdas || (!energy_only && !forces) || (energy_only && !energies && !binding_energies))
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  for (int i = 0; i < count; i++) {
+    if (!positions[i] || (!energy_only && !forces[i])) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (!std::isfinite(lambdas[i])) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": lambda must be finite");
+    for (int j = 0; j < i && !energy_only; j++)
+      if (spans_overlap(forces[i], 3 * (size_t)bs[i]->n, forces[j], 3 * (size_t)bs[j]->n))
+        return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": output buffers of two bindings overlap");
+  }
+  agbnp_hip_binding* const b0 = bs[0];
+  BINDING_TRY(who, hipSetDevice(b0->device));
+  const hipStream_t st = b0->m[0]->stream;
+  const double* d_pos[kMaxBindingGroup];
+  double *d_frc[kMaxBindingGroup], *d_ene[kMaxBindingGroup], *d_u[kMaxBindingGroup];
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_binding* const b = bs[i];
+    rc = binding_carry(b, who);  // (every binding's streams are idle from here on)
+    if (rc != AGBNP_HIP_OK) return rc;
+    const size_t n3 = 3 * (size_t)b->n;
+    if (b->d_host.p == nullptr) BINDING_TRY(who, b->d_host.alloc(2 * n3 + 2));
+    b->h_host.resize(n3 + 2);
+    BINDING_TRY(who, hipMemcpyAsync(b->d_host.p, positions[i], sizeof(double) * n3, hipMemcpyHostToDevice, st));
+    BINDING_TRY(who, hipMemsetAsync(b->d_host.p + n3, 0, sizeof(double) * (n3 + 2), st));
+    d_pos[i] = b->d_host.p;
+    d_frc[i] = b->d_host.p + n3;
+    d_ene[i] = b->d_host.p + 2 * n3;
+    d_u[i] = b->d_host.p + 2 * n3 + 1;
+  }
+  if (b0->d_group_lambdas.p == nullptr) BINDING_TRY(who, b0->d_group_lambdas.alloc(kMaxBindingGroup));
+  BINDING_TRY(who, hipMemcpyAsync(b0->d_group_lambdas.p, lambdas, sizeof(double) * count, hipMemcpyHostToDevice, st));
+  rc = binding_group_enqueue(bs, count, d_pos, b0->d_group_lambdas.p, energy_only ? nullptr : d_frc, d_ene, d_u, nullptr, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++)
+    BINDING_TRY(who, hipMemcpyAsync(bs[i]->h_host.data(), d_frc[i], sizeof(double) * (3 * (size_t)bs[i]->n + 2), hipMemcpyDeviceToHost, st));
+  BINDING_TRY(who, hipStreamSynchronize(st));
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_binding* const b = bs[i];
+    const size_t n3 = 3 * (size_t)b->n;
+    std::vector<int> bad;
+    int withheld = 0;
+    rc = binding_harvest(b, nullptr, bad, &withheld, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (withheld) {  // repeated alone, as agbnp_hip_binding_execute_host / _energy_host repeats
+      rc = binding_host(b, positions[i], lambdas[i], energy_only ? nullptr : forces[i], energies ? &energies[i] : nullptr,
+                        binding_energies ? &binding_energies[i] : nullptr, who);
+      if (rc != AGBNP_HIP_OK) return rc;
+      continue;
+    }
+    for (size_t k = 0; k < n3 && !energy_only; k++) forces[i][k] += b->h_host[k];
+    if (energies) energies[i] = b->h_host[n3];
+    if (binding_energies) binding_energies[i] = b->h_host[n3 + 1];
+  }
+  return AGBNP_HIP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -272,6 +501,30 @@ int agbnp_hip_binding_energy_host(agbnp_hip_binding* b, const double* positions,
   return binding_host(b, positions, lambda, nullptr, energy, binding_energy, who);
 }
 
+int agbnp_hip_binding_execute_group(agbnp_hip_binding* const* bindings, int count, const double* const* d_positions, const double* d_lambdas,
+                                    double* const* d_forces, double* const* d_energies, double* const* d_binding_energies, void* stream) {
+  return binding_group_device(bindings, count, d_positions, d_lambdas, d_forces, false, d_energies, d_binding_energies, stream,
+                              "agbnp_hip_binding_execute_group");
+}
+
+int agbnp_hip_binding_energy_group(agbnp_hip_binding* const* bindings, int count, const double* const* d_positions, const double* d_lambdas,
+                                   double* const* d_energies, double* const* d_binding_energies, void* stream) {
+  return binding_group_device(bindings, count, d_positions, d_lambdas, nullptr, true, d_energies, d_binding_energies, stream,
+                              "agbnp_hip_binding_energy_group");
+}
+
+int agbnp_hip_binding_execute_group_host(agbnp_hip_binding* const* bindings, int count, const double* const* positions, const double* lambdas,
+                                         double* const* forces, double* energies, double* binding_energies) {
+  return binding_group_host(bindings, count, positions, lambdas, forces, false, energies, binding_energies,
+                            "agbnp_hip_binding_execute_group_host");
+}
+
+int agbnp_hip_binding_energy_group_host(agbnp_hip_binding* const* bindings, int count, const double* const* positions, const double* lambdas,
+                                        double* energies, double* binding_energies) {
+  return binding_group_host(bindings, count, positions, lambdas, nullptr, true, energies, binding_energies,
+                            "agbnp_hip_binding_energy_group_host");
+}
+
 int agbnp_hip_binding_finish(agbnp_hip_binding* b, void* stream, int* must_repeat) {
   if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   int count = 0;
@@ -341,6 +594,7 @@ agbnp_hip_context* agbnp_hip_binding_member(agbnp_hip_binding* b, int which) {
 void agbnp_hip_binding_destroy(agbnp_hip_binding* b) {
   if (!b) return;
   for (agbnp_hip_context* c : b->m) agbnp_hip_destroy(c);  // (each drains its own stream)
+  if (b->group_event) (void)hipEventDestroy(b->group_event);
   delete b;  // (hipFree waits for what is still in flight on a caller's stream)
 }
 

@@ -26,7 +26,7 @@
 // noise amplitude is formed in the kernel.  Normal deviates: Philox4x32-10 keyed by seeds[r], counter = (atom, step number on
 // the device lo, hi, 0|1), Box-Muller in FP64 on 53-bit uniforms: the stream of a run depends on nothing but the seed (graph
 // replays included: the step number is read from device memory).  The counter's last word names the stream (kNoiseWord0 ..
-// kHamiltonianWord below, md.py's PHILOX_* words): no two uses share one.
+// kLambdaWord below, md.py's PHILOX_* words): no two uses share one.
 //
 // Exchange (temperature replica exchange between neighbouring rungs of the ladder): k_md_exchange_decide, ONE workgroup,
 // one thread per pair (k, k + 1), k = a mod 2, a mod 2 + 2, ...: the pairs of an attempt are disjoint, so every thread reads and
@@ -42,6 +42,20 @@
 // withheld cross evaluation, and the pair is void), leaves a partner (-1: none) and a velocity factor per slot, and
 // k_md_hamiltonian_apply, a launch of its own behind it, exchanges x[lo] and x[hi] bit for bit and the velocities rescaled to
 // the bath they arrive in.  f is left alone: the driver evaluates all slots again behind the attempt.
+//
+// Lambda exchange (md.py: BindingReplicaMD): replica exchange over a ladder of binding Hamiltonians
+// E_lambda = E_R + E_L + lambda u.  Replica r is a conformation that keeps its binding, its bath kT[r] and its buffers; what moves
+// is lambda[r], a device word that the binding group's combine launch reads (agbnp_hip_binding_execute_group: d_lambdas).  E_lambda
+// is linear in lambda, so an exchange of lambda between two replicas needs no cross evaluation: k_md_lambda_exchange, ONE launch
+// of one workgroup with one thread per pair of rungs, judges
+//   Delta = (lambda_lo - lambda_hi) (u_lo / kT_lo - u_hi / kT_hi)
+// from the u words the last evaluation of each replica added to u[r] (u_lo / kT_lo: u[lo] / kT[lo] rounded to a double, then the
+// difference, then the product) and accepts iff log(uniform) <= Delta.  A u word that is 0.0 or not finite is a withheld
+// evaluation (the engine adds nothing then, and the word is still the zero it was handed back as): the pair is void, recorded with
+// accepted = -1, nothing swapped.  All R u words are handed back as zeros, behind a barrier: those of the replicas that sat the
+// attempt out too, which the next attempt's evaluation adds to again.  No position, velocity or force moves and no second
+// launch follows; the forces and E_lambda of a replica whose lambda changed are stale until the driver's next evaluation.
+// A binding whose u is identically zero (version 0 with a ligand without a heavy atom) makes every pair void.
 //
 // FIRE minimiser (fast inertial relaxation, Bitzek et al., PRL 97, 170201; md.py: _Replicas.minimise): two
 // launches per iteration around the driver's evaluation, the grid of the group kernels (R x blocks(n) workgroups, one thread per
@@ -146,6 +160,25 @@ struct AgbnpMdHamiltonian {  // (md.py::_HamiltonianArgs)
   unsigned long long seed;
 };
 
+struct AgbnpMdLambdaRecord {  // (md.py::LAMBDA_RECORD); 88 bytes, no padding
+  long long attempt, step;      // step: steps replica_lo had finished
+  int rung, replica_lo, replica_hi, accepted;  // accepted: 1, 0, or -1 for a void pair (a u word is missing)
+  double u_lo, u_hi, lambda_lo, lambda_hi, kT_lo, kT_hi, uniform;  // binding energies, lambdas and baths (kJ/mol) BEFORE the decision
+};
+
+struct AgbnpMdLambda {  // (md.py::_LambdaArgs); 88 bytes: 4 bytes of padding behind replicas
+  int replicas;
+  double* lambda;            // [R] the words a binding group reads as d_lambdas
+  int *rung_of_replica, *replica_at_rung;  // [R] each
+  const double* kT;          // [R] replica r's bath: never moves
+  double* u;                 // [R] the words the binding group added u to; all R are handed back as zeros
+  const long long* step;     // [R]
+  long long* attempts;       // [1]
+  AgbnpMdLambdaRecord* log;
+  long long log_capacity;
+  unsigned long long seed;
+};
+
 struct AgbnpMdFire {  // (md.py::_FireArgs); 176 bytes: every field at a multiple of 8 in this order, 4 bytes of padding behind n_min (at 152)
   double* w;                 // [R][n][3] the minimiser's velocities (scratch; g.v is not used)
   double *dt, *alpha;        // [R]
@@ -167,8 +200,8 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kMaxReplicas = AGBNP_HIP_MAX_GROUP;
-// the last word of a Philox counter names the stream: the two blocks of a step's noise, the two exchanges' deviates
-constexpr uint32_t kNoiseWord0 = 0u, kNoiseWord1 = 1u, kExchangeWord = 2u, kHamiltonianWord = 3u;
+// the last word of a Philox counter names the stream: the two blocks of a step's noise, the three exchanges' deviates
+constexpr uint32_t kNoiseWord0 = 0u, kNoiseWord1 = 1u, kExchangeWord = 2u, kHamiltonianWord = 3u, kLambdaWord = 4u;
 
 __host__ __device__ constexpr int blocks_of(int n) { return (n + kBlock - 1) / kBlock; }
 
@@ -586,6 +619,36 @@ __global__ __launch_bounds__(kBlock) void k_md_hamiltonian_apply(AgbnpMdHamilton
   }
 }
 
+// attempt a = attempts[0] of a lambda exchange (the header comment): pairs of rungs (k, k + 1), k = a mod 2, a mod 2 + 2, ...,
+// lo / hi the replicas on them; accept iff log(uniform) <= Delta, uniform = attempt_uniform with counter word kLambdaWord (4).
+// An accepted pair swaps the two replicas' lambda words and rungs; nothing else moves.  The pairs of an attempt are disjoint, so
+// every u word has at most one reader; behind a barrier all R are handed back as zeros.  The records have the fixed places k_md_exchange_decide uses.
+__global__ __launch_bounds__(64) void k_md_lambda_exchange(AgbnpMdLambda e) {
+  const int t = threadIdx.x, R = e.replicas;
+  const long long a = e.attempts[0];
+  const int k = pair_of(a, t);
+  if (k + 1 < R) {
+    const int lo = e.replica_at_rung[k], hi = e.replica_at_rung[k + 1];
+    const double l_lo = e.lambda[lo], l_hi = e.lambda[hi], kT_lo = e.kT[lo], kT_hi = e.kT[hi], u_lo = e.u[lo], u_hi = e.u[hi];
+    const double delta = (l_lo - l_hi) * (u_lo / kT_lo - u_hi / kT_hi);
+    const double uniform = attempt_uniform(k, a, kLambdaWord, e.seed);
+    // the engine adds nothing for a withheld evaluation: a u word that is still zero is a missing binding energy
+    const bool is_void = u_lo == 0.0 || u_hi == 0.0 || !isfinite(u_lo) || !isfinite(u_hi);
+    const bool accepted = !is_void && log(uniform) <= delta;
+    if (accepted) {
+      e.lambda[lo] = l_hi, e.lambda[hi] = l_lo;
+      e.rung_of_replica[lo] = k + 1, e.rung_of_replica[hi] = k;
+      e.replica_at_rung[k] = hi, e.replica_at_rung[k + 1] = lo;
+    }
+    const long long at = record_place(a, R, t);
+    if (at < e.log_capacity)
+      e.log[at] = AgbnpMdLambdaRecord{a, e.step[lo], k, lo, hi, is_void ? -1 : (accepted ? 1 : 0), u_lo, u_hi, l_lo, l_hi, kT_lo, kT_hi, uniform};
+  }
+  __syncthreads();  // (every thread has read `a` and its pair's u words)
+  if (t < R) e.u[t] = 0.0;  // all R words, those of the replicas that sat the attempt out too: the next attempt's evaluation ADDS
+  if (t == 0) e.attempts[0] = a + 1;
+}
+
 // the entry points' two bodies.  A struct of any of the three kinds is judged by its first two words
 template <typename S>
 bool shape_ok(const S* s) { return s && s->n > 0 && s->replicas >= 1 && s->replicas <= kMaxReplicas; }
@@ -649,6 +712,17 @@ int agbnp_md_exchange(const AgbnpMdExchange* e, void* stream) {
 // synchronisation, nothing read back.  The cross energies of the attempt's pairs are in h->cross when the first one runs.
 int agbnp_md_hamiltonian_exchange(const AgbnpMdHamiltonian* h, void* stream) {
   return launch_exchange(k_md_hamiltonian_decide, k_md_hamiltonian_apply, h, stream);
+}
+
+// One lambda exchange attempt between neighbouring rungs: ONE launch of one 64-thread workgroup, no synchronisation, nothing read
+// back.  The u words of the attempt's pairs are in e->u when it runs.  Return: hipError_t of the launch, 1 for a null *e, replicas
+// outside 1 .. 16 or a null array (the log's may be null where log_capacity is 0).
+int agbnp_md_lambda_exchange(const AgbnpMdLambda* e, void* stream) {
+  if (!e || e->replicas < 1 || e->replicas > kMaxReplicas) return (int)hipErrorInvalidValue;
+  if (!e->lambda || !e->rung_of_replica || !e->replica_at_rung || !e->kT || !e->u || !e->step || !e->attempts) return (int)hipErrorInvalidValue;
+  if (!e->log && e->log_capacity > 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_md_lambda_exchange, dim3(1), dim3(64), 0, (hipStream_t)stream, *e);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -15,11 +15,12 @@ behind it -- between the steps of a run both in ONE launch; Philox normal deviat
 host only synchronises every `check_every` steps to read the engine's overflow log (agbnp_hip_finish).  `ReplicaMD` is the
 core around `agbnp_hip_execute_group`, eager (group calls are not captured), plus temperature exchanges decided on the
 device; `HamiltonianReplicaMD` is the same with contexts that differ in their parameters and conformations that
-move between them (s.4k).  Every driver has `minimise()`: FIRE for all its replicas, each with state and convergence of its
-own, in two more launches of libagbnp_md.so around the same evaluation (back: judge and decide the move, front: move and
-tethers; s.4l), the host reading only every `check_every` iterations.  Written in torch operations a step is seventeen
-launches around the six of the AGBNP evaluation (`DeviceMD(fused=False)`, kept as the cross-check of the kernels): 0.163 ->
-0.11 ms per step of 1dwc.
+move between them (s.4k); `BindingReplicaMD` is the core around `agbnp_hip_binding_execute_group`, replicas on a ladder of
+binding Hamiltonians E_R + E_L + lambda u whose lambdas are exchanged on the device (s.4o).  Every driver has `minimise()`:
+FIRE for all its replicas, each with state and convergence of its own, in two more launches of libagbnp_md.so around the same
+evaluation (back: judge and decide the move, front: move and tethers; s.4l), the host reading only every `check_every`
+iterations.  Written in torch operations a step is seventeen launches around the six of the AGBNP evaluation
+(`DeviceMD(fused=False)`, kept as the cross-check of the kernels): 0.163 -> 0.11 ms per step of 1dwc.
 
 PyTorch is plumbing here (device arrays, the graph capture API), not the product.
 """
@@ -34,8 +35,9 @@ KB = 0.0083144626  # kJ/mol/K
 
 MAX_REPLICAS = _lib.MAX_GROUP  # AGBNP_HIP_MAX_GROUP
 
-# the last word of a Philox counter names the stream (csrc/md_kernels.hip: kNoiseWord0, kNoiseWord1, kExchangeWord, kHamiltonianWord)
-PHILOX_NOISE_0, PHILOX_NOISE_1, PHILOX_EXCHANGE, PHILOX_HAMILTONIAN = 0, 1, 2, 3
+# the last word of a Philox counter names the stream (csrc/md_kernels.hip: kNoiseWord0, kNoiseWord1, kExchangeWord, kHamiltonianWord,
+# kLambdaWord)
+PHILOX_NOISE_0, PHILOX_NOISE_1, PHILOX_EXCHANGE, PHILOX_HAMILTONIAN, PHILOX_LAMBDA = 0, 1, 2, 3, 4
 
 _M64 = 0xFFFFFFFFFFFFFFFF
 
@@ -60,6 +62,12 @@ class _HamiltonianArgs(C.Structure):  # AgbnpMdHamiltonian
                 ("log", C.c_void_p), ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
 
 
+class _LambdaArgs(C.Structure):  # AgbnpMdLambda
+    _fields_ = [("replicas", C.c_int), ("lambda", C.c_void_p), ("rung_of_replica", C.c_void_p), ("replica_at_rung", C.c_void_p),
+                ("kT", C.c_void_p), ("u", C.c_void_p), ("step", C.c_void_p), ("attempts", C.c_void_p), ("log", C.c_void_p),
+                ("log_capacity", C.c_longlong), ("seed", C.c_ulonglong)]
+
+
 class _FireArgs(C.Structure):  # AgbnpMdFire
     _fields_ = [("w", C.c_void_p), ("dt", C.c_void_p), ("alpha", C.c_void_p), ("npos", C.c_void_p), ("iterations", C.c_void_p),
                 ("converged", C.c_void_p), ("voids", C.c_void_p), ("fmax", C.c_void_p), ("coef", C.c_void_p), ("part", C.c_void_p),
@@ -71,6 +79,7 @@ class _FireArgs(C.Structure):  # AgbnpMdFire
 GROUP_SYMBOLS = ("agbnp_md_group_pre", "agbnp_md_group_mid", "agbnp_md_group_post", "agbnp_md_group_tethers", "agbnp_md_exchange")
 HAMILTONIAN_SYMBOLS = ("agbnp_md_hamiltonian_exchange",)
 FIRE_SYMBOLS = ("agbnp_md_fire_back", "agbnp_md_fire_front")
+LAMBDA_SYMBOLS = ("agbnp_md_lambda_exchange",)
 
 # FIRE's constants (Bitzek et al., PRL 97, 170201) and the bounds of the move
 FIRE_F_INC, FIRE_F_DEC, FIRE_ALPHA0, FIRE_F_ALPHA, FIRE_N_MIN = 1.1, 0.5, 0.1, 0.99, 5
@@ -101,6 +110,7 @@ def _md_lib():
         lib.agbnp_md_group_tethers.argtypes = [gp, vp, vp]
         lib.agbnp_md_exchange.argtypes = [C.POINTER(_ExchangeArgs), vp]
         lib.agbnp_md_hamiltonian_exchange.argtypes = [C.POINTER(_HamiltonianArgs), vp]
+        lib.agbnp_md_lambda_exchange.argtypes = [C.POINTER(_LambdaArgs), vp]
         lib.agbnp_md_fire_back.argtypes = [gp, C.POINTER(_FireArgs), vp, vp]
         lib.agbnp_md_fire_front.argtypes = [gp, C.POINTER(_FireArgs), vp, vp]
         _MD_LIB = lib
@@ -564,9 +574,11 @@ EXCHANGE_RECORD = np.dtype([("attempt", "<i8"), ("step", "<i8"), ("rung", "<i4")
 
 
 class _GroupMD:
-    """What the two exchange drivers share: the core around `agbnp_hip_execute_group` on a stream of the driver's own, eager
+    """What the exchange drivers share: the core around `agbnp_hip_execute_group` on a stream of the driver's own, eager
     (group calls are not captured).  Slot r's buffers are fixed slices of the strided arrays, so the group call's handle and
-    pointer arrays are built once.  A driver adds its exchange: `exchange()` enqueues one attempt on `self.stream`."""
+    pointer arrays are built once.  A driver adds its exchange: `exchange()` enqueues one attempt on `self.stream`.  A member
+    is whatever the driver's `_evaluate` evaluates -- a HipCalcAGBNPForceKernel, or a BindingEnergy for BindingReplicaMD --: it
+    has numParticles, a library handle behind _need() / _h, and finish(stream)."""
 
     def __init__(self, system, kernels, temperatures, seeds, exchange_seed, k_tether, dt, friction, device, log_capacity):
         who = type(self).__name__
@@ -613,6 +625,10 @@ class _GroupMD:
         if rc != _lib.OK:
             raise RuntimeError("agbnp_hip_execute_group: " + _lib.last_error(self.kernels[0]._h))
 
+    def _chunk(self, steps, attempt_follows):
+        """run() is about to enqueue `steps` steps (as many evaluations); `attempt_follows`: an exchange attempt comes right
+        behind them.  Nothing here: for a driver whose attempt uses something of the chunk's last evaluation."""
+
     def finish(self):
         """Every member's finish() on the driver's stream: withheld evaluations per member since the last call."""
         st = self.stream.cuda_stream
@@ -655,6 +671,7 @@ class _GroupMD:
             chunk = min(nsteps - done, check_every - since_check)
             if exchange_every > 0:
                 chunk = min(chunk, exchange_every - since_exchange)
+            self._chunk(chunk, exchange_every > 0 and since_exchange + chunk == exchange_every)
             self.core.steps(code, chunk, st, self._evaluate)
             done += chunk
             since_exchange += chunk
@@ -830,3 +847,131 @@ class HamiltonianReplicaMD(_GroupMD):
         """One record (HAMILTONIAN_RECORD) per attempted pair, in the order of the attempts; accepted = -1 marks a void pair,
         which acceptance() counts as attempted."""
         return self._records(HAMILTONIAN_RECORD)
+
+
+# ---- lambda replica exchange over a binding ladder: the replicas keep everything but lambda (DESIGN.md s.4o) ------------------
+
+
+def lambda_uniform(rung, attempt, exchange_seed):
+    """The deviate attempt `attempt` uses for the rung pair (rung, rung + 1): counter (k, a lo, a hi, 4), key exchange_seed --
+    word 4 keeps the stream apart from the other two exchanges'."""
+    return _attempt_uniform(rung, attempt, PHILOX_LAMBDA, exchange_seed)
+
+
+def lambda_delta(lambda_lo, lambda_hi, kT_lo, kT_hi, u_lo, u_hi):
+    """Delta of an exchange of lambda between two replicas under E_lambda = E_R + E_L + lambda u (kT, u in kJ/mol): minus the
+    change of E_lambda / kT summed over both, (lambda_lo - lambda_hi) (u_lo / kT_lo - u_hi / kT_hi).  Accepted iff
+    log(uniform) <= Delta.  Formed as the kernel forms it: each quotient a double, then the difference, then the product."""
+    return (lambda_lo - lambda_hi) * (u_lo / kT_lo - u_hi / kT_hi)
+
+
+# one record of the lambda exchange log (AgbnpMdLambdaRecord, csrc/md_kernels.hip); everything BEFORE the decision; accepted: 1,
+# 0, or -1 for a void pair (a u word was 0.0 or not finite: a withheld evaluation; nothing swapped)
+LAMBDA_RECORD = np.dtype([("attempt", "<i8"), ("step", "<i8"), ("rung", "<i4"), ("replica_lo", "<i4"), ("replica_hi", "<i4"),
+                          ("accepted", "<i4"), ("u_lo", "<f8"), ("u_hi", "<f8"), ("lambda_lo", "<f8"), ("lambda_hi", "<f8"),
+                          ("kT_lo", "<f8"), ("kT_hi", "<f8"), ("uniform", "<f8")])
+
+
+def _check_ladder(who, lambdas, R):
+    """A lambda ladder: R finite values, strictly increasing (rung k -> lambda_k)."""
+    try:
+        ladder = [float(x) for x in lambdas]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: the lambda ladder must be a list of numbers")
+    if len(ladder) != R:
+        raise ValueError(f"{who}: {R} bindings and {len(ladder)} lambdas")
+    if any(not np.isfinite(x) for x in ladder):
+        raise ValueError(f"{who}: lambdas must be finite")
+    if any(b <= a for a, b in zip(ladder, ladder[1:])):
+        raise ValueError(f"{who}: the lambda ladder must be strictly increasing")
+    return ladder
+
+
+class BindingReplicaMD(_GroupMD):
+    """Replica exchange in lambda over E_lambda = E_R + E_L + lambda u (BEDAM, single decoupling) of R replicas of one
+    complex: ReplicaMD's integrator and launches around ONE `agbnp_hip_binding_execute_group` over R BindingEnergy objects, whose
+    lambdas are a device tensor of the driver's.  Replica r is a conformation: x[r], v[r], bindings[r] and its bath kT[r] stay
+    together; an accepted exchange swaps the two replicas' lambda words and rungs, as ReplicaMD swaps baths.  frc[r] holds
+    tethers + F_lambda and e_agbnp[r] takes E_lambda, so the step kernels, minimise(), forces(), settle() and the logs work as in
+    the other drivers.
+
+    E_lambda is linear in lambda: an attempt needs no cross evaluation, only u of every replica at its own positions, and that
+    comes from the evaluation the steps made anyway -- of the steps an attempt follows, the last evaluation alone passes the u
+    pointers.  exchange() is then ONE small launch of libagbnp_md.so (decision, swap, all R u words back to zero) and a full
+    evaluation of all R as the refresh: F_lambda and last[:, 0] of a replica whose lambda changed are stale, and the
+    host does not know the verdict.  No hint is needed (nothing jumps), nothing is read.  A pair with a withheld evaluation
+    (its u word still zero) is void: recorded with accepted = -1, nothing swapped.  A binding whose u is identically zero
+    (version 0, a ligand without a heavy atom) makes every pair void.  exchange() called by hand outside run() finds no u words:
+    every pair is void -- use run(exchange_every=...)."""
+
+    def __init__(self, system, bindings, lambdas, temperatures=300.0, seeds=None, exchange_seed=0, k_tether=2.0e4, dt=0.001,
+                 friction=1.0, device="cuda:0", log_capacity=200000):
+        from .AGBNPplugin import BindingEnergy
+        who = type(self).__name__
+        bindings = list(bindings)
+        R = len(bindings)
+        if not 1 <= R <= MAX_REPLICAS:
+            raise ValueError(f"{who}: a group has 1 to {MAX_REPLICAS} replicas, not {R}")
+        if any(not isinstance(b, BindingEnergy) for b in bindings):
+            raise ValueError(f"{who}: members must be BindingEnergy objects")
+        ladder = _check_ladder(who, lambdas, R)
+        try:
+            temperatures = [float(t) for t in temperatures]
+        except TypeError:
+            temperatures = [float(temperatures)] * R
+        super().__init__(system, bindings, temperatures, seeds, exchange_seed, k_tether, dt, friction, device, log_capacity)
+        torch = self.torch
+        self.bindings = self.kernels
+        self.lambda_ladder = np.array(ladder)  # lambda of rung k
+        self.lam = torch.tensor(ladder, dtype=torch.float64, device=self.dev)  # lambda of replica r: the group's d_lambdas
+        self.u = torch.zeros(R, dtype=torch.float64, device=self.dev)  # where an attempt's evaluation adds u of replica r
+        self.rung_of_replica = torch.arange(R, dtype=torch.int32, device=self.dev)  # replica r starts on rung r
+        self.replica_at_rung = torch.arange(R, dtype=torch.int32, device=self.dev)
+        self.records = torch.zeros(self.exchange_capacity * LAMBDA_RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        self._l = _args(_LambdaArgs, replicas=R, rung_of_replica=self.rung_of_replica, replica_at_rung=self.replica_at_rung, kT=self.kT,
+                        u=self.u, step=self.counter, attempts=self.attempts, log=self.records, log_capacity=self.exchange_capacity,
+                        seed=self.exchange_seed & _M64, **{"lambda": self.lam})
+        self._u = (C.c_void_p * R)(*[self.u[r:r + 1].data_ptr() for r in range(R)])
+        self._u_in = 0  # evaluations until the one that passes the u pointers (0: none is waited for)
+
+    # ---- launches
+    def _chunk(self, steps, attempt_follows):
+        self._u_in = int(steps) if attempt_follows else 0
+
+    def _evaluate(self, st):
+        """agbnp_hip_binding_execute_group of all bindings on stream `st`: F_lambda and E_lambda are added to frc[r], e_agbnp[r];
+        u is added to u[r] by the last evaluation in front of an attempt alone."""
+        with_u = self._u_in == 1
+        self._u_in = max(self._u_in - 1, 0)
+        rc = _lib.load().agbnp_hip_binding_execute_group(self._handles, self.R, self._pos, C.c_void_p(self.lam.data_ptr()), self._frc,
+                                                         self._ene, self._u if with_u else None, C.c_void_p(st))
+        if rc != _lib.OK:
+            raise RuntimeError("agbnp_hip_binding_execute_group: " + _lib.last_error(None))
+
+    def exchange(self):
+        """One exchange attempt between neighbouring rungs, enqueued on the driver's stream; nothing is read and nothing waited
+        for: the decision (one launch, which also hands all R u words back as zeros), then tethers and one full group evaluation
+        of all R without u pointers as the refresh."""
+        torch = self.torch
+        st = self.stream.cuda_stream
+        self._u_in = 0
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            _check(self.core.lib.agbnp_md_lambda_exchange(C.byref(self._l), st))
+            self.core.forces(torch, st, self._evaluate)
+
+    # ---- observables
+    def lambdas(self):
+        """The current lambda of every replica."""
+        self.stream.synchronize()
+        return self.lam.cpu().numpy()
+
+    def rungs(self):
+        """rung_of_replica: the rung of the lambda ladder every replica sits on."""
+        self.stream.synchronize()
+        return self.rung_of_replica.cpu().numpy()
+
+    def exchange_log(self):
+        """One record (LAMBDA_RECORD) per attempted pair, in the order of the attempts; accepted = -1 marks a void pair, which
+        acceptance() counts as attempted."""
+        return self._records(LAMBDA_RECORD)
