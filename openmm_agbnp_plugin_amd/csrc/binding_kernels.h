@@ -1,5 +1,6 @@
 // Launchers of the two launches a binding evaluation puts round its group call (binding_kernels.hip; engine_binding.hip;
-// agbnp_hip_binding_*, include/agbnp_hip.h).
+// agbnp_hip_binding_*, include/agbnp_hip.h): the single-binding forms, with their short argument lists and lambda by value, and
+// the group forms.  Both are wrappers round the same device bodies; binding_enqueue picks the form by where its lambdas are.
 #pragma once
 #include <hip/hip_runtime.h>
 

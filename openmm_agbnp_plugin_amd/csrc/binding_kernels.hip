@@ -10,9 +10,13 @@
 // evaluation whose receptor was complete would otherwise leave the receptor's forces behind for the next one.
 // Both are streaming kernels, one thread per atom, elementwise: no order-dependent sum, so the deterministic mode's outputs are
 // bit-identical from run to run as the members' are.  The gather's indexed read is the only uncoalesced access.
-// Binding groups (agbnp_hip_binding_execute_group) make the same two launches ONCE for up to 16 bindings:
-// k_binding_gather_group, k_binding_combine_group and k_binding_combine_energy_group below, every binding's grid side by side,
-// its words by value in the kernel argument (BindingGroupArgs) and its lambda read from device memory when the launch runs.
+// Binding groups (agbnp_hip_binding_execute_group) make the same two launches ONCE for up to 16 bindings, every
+// binding's grid side by side, its words by value in the kernel argument (BindingGroupArgs) and its lambda read from device
+// memory when the launch runs.
+// The per-atom work stands ONCE, in the device bodies below (binding_gather_atom, binding_combine_atom, binding_complete,
+// binding_scalars).  The six kernels are wrappers, as the single and group kernels round pair_bodies.h are: each finds its
+// binding, its lambda and its pointers -- the single forms in their own short argument lists, lambda by value; the group forms in
+// BindingGroupArgs -- and calls the body.
 //
 // The verdict test is the engine's own (evaluation_overflowed), read as a device function as the decomposition's unit reads it:
 // this unit launches none of the kernels of pair_bodies.h.
@@ -23,10 +27,10 @@
 
 namespace agbnp {
 
-__global__ __launch_bounds__(256) void k_binding_gather(int n, const double* __restrict__ pos, const int* __restrict__ sub2complex,
-                                                        double* __restrict__ sub_pos) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n) return;
+// ---- the bodies ----
+// atom t of the receptor-then-ligand order: its position out of the complex's array
+__device__ __forceinline__ void binding_gather_atom(int t, const double* __restrict__ pos, const int* __restrict__ sub2complex,
+                                                    double* __restrict__ sub_pos) {
   const size_t src = 3 * (size_t)sub2complex[t], dst = 3 * (size_t)t;
   const double x = pos[src], y = pos[src + 1], z = pos[src + 2];
   sub_pos[dst] = x;
@@ -47,6 +51,7 @@ __device__ __forceinline__ bool binding_complete(const BindingVerdicts& v) {
   return ok;
 }
 
+// the role lane: the three energies read and cleared, E_lambda and u added
 __device__ __forceinline__ void binding_scalars(bool ok, double lambda, double* __restrict__ e, double* __restrict__ d_energy,
                                                 double* __restrict__ d_binding) {
   // (atomic loads, so that they are VECTOR loads: the address is uniform, and as plain loads they become scalar loads, which the
@@ -61,15 +66,11 @@ __device__ __forceinline__ void binding_scalars(bool ok, double lambda, double* 
   if (d_binding) d_binding[0] += e_rl - e_r - e_l;
 }
 
-__global__ __launch_bounds__(256) void k_binding_combine(int n, BindingVerdicts v, double lambda, const int* __restrict__ complex2sub,
-                                                         double* __restrict__ f_complex, double* __restrict__ f_sub,
-                                                         double* __restrict__ e, double* __restrict__ d_forces,
-                                                         double* __restrict__ d_energy, double* __restrict__ d_binding) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const bool ok = binding_complete(v);
-  if (i == 0) binding_scalars(ok, lambda, e, d_energy, d_binding);  // the role lane
-  const size_t a = 3 * (size_t)i, s = 3 * (size_t)complex2sub[i];
+// atom i of the complex, t = complex2sub[i] its place in the receptor-then-ligand order: its two force terms read and cleared,
+// F_lambda added.  (Plain pointers: that the buffers do not alias is the wrappers' promise, made where each names them.)
+__device__ __forceinline__ void binding_combine_atom(int i, int t, bool ok, double lambda, double* f_complex, double* f_sub,
+                                                     double* d_forces) {
+  const size_t a = 3 * (size_t)i, s = 3 * (size_t)t;
   const double w = 1.0 - lambda;
 #pragma unroll
   for (int d = 0; d < 3; d++) {
@@ -78,6 +79,24 @@ __global__ __launch_bounds__(256) void k_binding_combine(int n, BindingVerdicts 
     f_sub[s + d] = 0.0;
     if (ok) d_forces[a + d] += lambda * f_rl + w * f_own;
   }
+}
+
+// ---- one binding ----
+__global__ __launch_bounds__(256) void k_binding_gather(int n, const double* __restrict__ pos, const int* __restrict__ sub2complex,
+                                                        double* __restrict__ sub_pos) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < n) binding_gather_atom(t, pos, sub2complex, sub_pos);
+}
+
+__global__ __launch_bounds__(256) void k_binding_combine(int n, BindingVerdicts v, double lambda, const int* __restrict__ complex2sub,
+                                                         double* __restrict__ f_complex, double* __restrict__ f_sub,
+                                                         double* __restrict__ e, double* __restrict__ d_forces,
+                                                         double* __restrict__ d_energy, double* __restrict__ d_binding) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool ok = binding_complete(v);
+  if (i == 0) binding_scalars(ok, lambda, e, d_energy, d_binding);  // the role lane
+  binding_combine_atom(i, complex2sub[i], ok, lambda, f_complex, f_sub, d_forces);
 }
 
 __global__ __launch_bounds__(64) void k_binding_combine_energy(BindingVerdicts v, double lambda, double* __restrict__ e,
@@ -100,24 +119,17 @@ __device__ __forceinline__ int binding_group_index(const BindingGroupArgs& G, in
   return k;
 }
 
-__global__ __launch_bounds__(256) void k_binding_gather_group(const BindingGroupArgs G) {
-  int blk;
-  const BindingGroupMember& B = G.m[binding_group_index(G, blk)];
-  const int t = blk * 256 + threadIdx.x;
-  if (t >= B.n) return;
-  const double* __restrict__ pos = B.pos;
-  double* __restrict__ sub_pos = B.work;
-  const size_t src = 3 * (size_t)B.maps[t], dst = 3 * (size_t)t;
-  const double x = pos[src], y = pos[src + 1], z = pos[src + 2];
-  sub_pos[dst] = x;
-  sub_pos[dst + 1] = y;
-  sub_pos[dst + 2] = z;
-}
-
 // lambda of binding k: a device word that a kernel earlier on the stream may have written.  (An atomic load, so that it is a
 // VECTOR load like the role lane's reads of the energy words: see binding_scalars.)
 __device__ __forceinline__ double binding_group_lambda(const BindingGroupArgs& G, int k) {
   return __hip_atomic_load(&G.lambdas[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void k_binding_gather_group(const BindingGroupArgs G) {
+  int blk;
+  const BindingGroupMember& B = G.m[binding_group_index(G, blk)];
+  const int t = blk * 256 + threadIdx.x;
+  if (t < B.n) binding_gather_atom(t, B.pos, B.maps, B.work);
 }
 
 __global__ __launch_bounds__(256) void k_binding_combine_group(const BindingGroupArgs G) {
@@ -132,15 +144,7 @@ __global__ __launch_bounds__(256) void k_binding_combine_group(const BindingGrou
   double* __restrict__ f_sub = B.work + 6 * (size_t)n;
   double* __restrict__ d_forces = B.forces;
   if (i == 0) binding_scalars(ok, lambda, B.work + 9 * (size_t)n, B.energy, B.binding);  // the binding's role lane
-  const size_t a = 3 * (size_t)i, s = 3 * (size_t)B.maps[n + i];
-  const double w = 1.0 - lambda;
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    const double f_rl = f_complex[a + d], f_own = f_sub[s + d];
-    f_complex[a + d] = 0.0;
-    f_sub[s + d] = 0.0;
-    if (ok) d_forces[a + d] += lambda * f_rl + w * f_own;
-  }
+  binding_combine_atom(i, B.maps[n + i], ok, lambda, f_complex, f_sub, d_forces);
 }
 
 __global__ __launch_bounds__(64) void k_binding_combine_energy_group(const BindingGroupArgs G) {
@@ -149,21 +153,7 @@ __global__ __launch_bounds__(64) void k_binding_combine_energy_group(const Bindi
   if (threadIdx.x == 0) binding_scalars(binding_complete(B.v), binding_group_lambda(G, k), B.work + 9 * (size_t)B.n, B.energy, B.binding);
 }
 
-hipError_t launch_binding_gather_group(const BindingGroupArgs& G, hipStream_t st) {
-  hipLaunchKernelGGL(k_binding_gather_group, dim3(G.first[G.count]), dim3(256), 0, st, G);
-  return hipGetLastError();
-}
-
-hipError_t launch_binding_combine_group(const BindingGroupArgs& G, hipStream_t st) {
-  hipLaunchKernelGGL(k_binding_combine_group, dim3(G.first[G.count]), dim3(256), 0, st, G);
-  return hipGetLastError();
-}
-
-hipError_t launch_binding_combine_energy_group(const BindingGroupArgs& G, hipStream_t st) {
-  hipLaunchKernelGGL(k_binding_combine_energy_group, dim3(G.count), dim3(64), 0, st, G);
-  return hipGetLastError();
-}
-
+// ---- launchers ----
 hipError_t launch_binding_gather(int n, const double* pos, const int* sub2complex, double* sub_pos, hipStream_t st) {
   hipLaunchKernelGGL(k_binding_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, pos, sub2complex, sub_pos);
   return hipGetLastError();
@@ -179,6 +169,21 @@ hipError_t launch_binding_combine(int n, const BindingVerdicts& v, double lambda
 hipError_t launch_binding_combine_energy(const BindingVerdicts& v, double lambda, double* e, double* d_energy, double* d_binding,
                                          hipStream_t st) {
   hipLaunchKernelGGL(k_binding_combine_energy, dim3(1), dim3(64), 0, st, v, lambda, e, d_energy, d_binding);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_gather_group(const BindingGroupArgs& G, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_gather_group, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_combine_group(const BindingGroupArgs& G, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_combine_group, dim3(G.first[G.count]), dim3(256), 0, st, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_combine_energy_group(const BindingGroupArgs& G, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_combine_energy_group, dim3(G.count), dim3(64), 0, st, G);
   return hipGetLastError();
 }
 

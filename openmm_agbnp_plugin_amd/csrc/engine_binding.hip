@@ -6,8 +6,12 @@
 // members through the public entry points, so the members share launch sets exactly as any group's do, and one combine launch that
 // reads all three verdicts on the device and adds to the caller's buffers all or nothing.  The k-th binding evaluation since the
 // last agbnp_hip_binding_finish() is the k-th evaluation of every member: the binding's log is the union of the members'.
-// Binding groups (agbnp_hip_binding_execute_group and its kin, at the end of the unnamed namespace) evaluate up to 16 bindings on
-// one gather launch, one to three group calls and one combine launch, each binding's lambda read from device memory.
+// Binding groups (agbnp_hip_binding_execute_group and its kin) evaluate up to 16 bindings on one gather launch, one to three
+// group calls and one combine launch, each binding's lambda read from device memory.
+// Single and group calls are ONE host path: binding_enqueue takes `count` bindings and makes, for a single call (count == 1, a
+// host lambda), the single-binding launches and otherwise the group launches, as group_enqueue makes a member's own launches
+// for a launch set of one; the host entry points of both stage and deliver through binding_stage and binding_deliver.  What
+// the single and the group entry points keep of their own is their argument checks.
 // Messages of failed binding calls are the calling thread's agbnp_hip_last_error(NULL).
 #include "binding_kernels.h"
 #include "engine_context.h"
@@ -23,15 +27,15 @@ struct agbnp_hip_binding {
   DevBuf<double> d_work;
   // the host entry points' staging: [3n] positions | [3n] F_lambda | E_lambda, u
   DevBuf<double> d_host;
-  std::vector<double> h_host;
+  std::vector<double> h_host;    // [3n + 2] the outputs, read back
   int enqueued = 0;              // binding evaluations of the device entry points since the last finish
   std::vector<void*> streams;    // caller streams they went to
   std::vector<int> withheld;     // what the last finish found
   int withheld_count = 0;
   std::vector<int> carried;      // withheld device evaluations that a host entry point in between had to harvest
   int carried_count = 0, carried_seq = 0;
-  // binding groups (below): the event that joins streams where a group call with a NULL stream runs on several, and the device
-  // words the host forms stage their lambdas in (both made on first use, by the call's first binding)
+  // binding groups: the event that joins streams where a group call with a NULL stream runs on several, and the device words
+  // the host forms stage their lambdas in (both made on first use, by the call's first binding)
   hipEvent_t group_event = nullptr;
   DevBuf<double> d_group_lambdas;
 
@@ -64,38 +68,123 @@ void clear_member_errors(agbnp_hip_binding* b) {
     if (e__ != hipSuccess) return binding_fail(AGBNP_HIP_ERR_DEVICE, std::string(who) + ": " #call ": " + hipGetErrorString(e__)); \
   } while (0)
 
-// one binding evaluation on `stream`; d_forces null: the energy-only form
-int binding_enqueue(agbnp_hip_binding* b, const double* d_pos, double lambda, double* d_forces, double* d_energy, double* d_binding,
-                    void* stream, const char* who) {
-  agbnp_hip_context* const c0 = b->m[0];
-  clear_member_errors(b);
+// Where a call's lambdas are: ONE host value -- a single call: count == 1, the single-binding kernels, lambda by value in
+// their short argument lists -- or (device non-null) a device array of `count` words, which the group kernels read when the
+// combine launch runs.
+struct Lambdas {
+  double host;
+  const double* device;
+};
+
+// where the combine launch finds the three members' verdicts on the evaluation that has just been enqueued (the members' blocks
+// name this evaluation's words until their next evaluation)
+BindingVerdicts binding_verdicts(const agbnp_hip_binding* b) {
+  BindingVerdicts v;
+  for (int m = 0; m < kBindingMembers; m++) {
+    const PairArgs& P = b->m[m]->P;
+    v.estatus[m] = P.estatus;
+    v.epoch[m] = P.epoch;
+    v.five[m] = P.five;
+  }
+  return v;
+}
+
+// One evaluation of every binding on `stream` (NULL: the first complex's own); the arguments have been checked.  d_forces null:
+// the energy-only form; d_energies / d_bindings null: every entry null.  One gather launch, the members' evaluations through
+// the public group entry points -- one call over all 3 count members where they fit a group, else one call per kind
+// (complexes, receptors, ligands: same-kind members of one system share a launch set) -- and one combine launch.
+// A single call (count == 1): the loops over k = 1 .. are empty and the one group call's stream is `st` itself, so no event is
+// made or recorded.
+int binding_enqueue(agbnp_hip_binding* const* bs, int count, const double* const* d_pos, const Lambdas& lam, double* const* d_forces,
+                    double* const* d_energies, double* const* d_bindings, void* stream, const char* who) {
+  agbnp_hip_binding* const b0 = bs[0];
+  for (int k = 0; k < count; k++) clear_member_errors(bs[k]);
   hipStream_t st;
-  if (enter(c0, stream, &st) != AGBNP_HIP_OK) return member_fail(b, AGBNP_HIP_ERR_DEVICE, who);
+  if (enter(b0->m[0], stream, &st) != AGBNP_HIP_OK) return member_fail(b0, AGBNP_HIP_ERR_DEVICE, who);
   if (is_capturing(st))
     return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
                         std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
-  const int n = b->n, nr = b->nr;
-  BINDING_TRY(who, launch_binding_gather(n, d_pos, b->d_maps.p, b->sub_pos(), st));
-  const double* pos[kBindingMembers] = {d_pos, b->sub_pos(), b->sub_pos() + 3 * (size_t)nr};
-  double* frc[kBindingMembers] = {b->f_complex(), b->f_sub(), b->f_sub() + 3 * (size_t)nr};
-  double* ene[kBindingMembers] = {b->energies(), b->energies() + 1, b->energies() + 2};
-  // (a NULL stream is the complex's own: the group call joins the other members' streams to it on both sides)
-  const int rc = d_forces ? agbnp_hip_execute_group(b->m, kBindingMembers, pos, frc, ene, stream)
-                          : agbnp_hip_energy_group(b->m, kBindingMembers, pos, ene, stream);
-  if (rc != AGBNP_HIP_OK) return member_fail(b, rc, who);
-  BindingVerdicts v;
-  for (int k = 0; k < kBindingMembers; k++) {  // (the members' blocks name this evaluation's words until their next evaluation)
-    const PairArgs& P = b->m[k]->P;
-    v.estatus[k] = P.estatus;
-    v.epoch[k] = P.epoch;
-    v.five[k] = P.five;
+  BindingGroupArgs G;
+  std::memset(&G, 0, sizeof(G));
+  G.count = count;
+  G.lambdas = lam.device;
+  agbnp_hip_context* ctxs[kBindingMembers * kMaxBindingGroup];
+  const double* pos[kBindingMembers * kMaxBindingGroup];
+  double *frc[kBindingMembers * kMaxBindingGroup], *ene[kBindingMembers * kMaxBindingGroup];
+  // members in one call: binding by binding; in one call per kind: kind by kind
+  const bool one_call = kBindingMembers * count <= kMaxGroup;
+  for (int k = 0; k < count; k++) {
+    agbnp_hip_binding* const b = bs[k];
+    BindingGroupMember& B = G.m[k];
+    B.maps = b->d_maps.p;
+    B.work = b->d_work.p;
+    B.pos = d_pos[k];
+    B.forces = d_forces ? d_forces[k] : nullptr;
+    B.energy = d_energies ? d_energies[k] : nullptr;
+    B.binding = d_bindings ? d_bindings[k] : nullptr;
+    B.n = b->n;
+    G.first[k + 1] = G.first[k] + (b->n + 255) / 256;
+    const double* const p[kBindingMembers] = {d_pos[k], b->sub_pos(), b->sub_pos() + 3 * (size_t)b->nr};
+    double* const f[kBindingMembers] = {b->f_complex(), b->f_sub(), b->f_sub() + 3 * (size_t)b->nr};
+    for (int m = 0; m < kBindingMembers; m++) {
+      const int at = one_call ? kBindingMembers * k + m : count * m + k;
+      ctxs[at] = b->m[m];
+      pos[at] = p[m];
+      frc[at] = f[m];
+      ene[at] = b->energies() + m;
+    }
   }
-  if (d_forces)
-    BINDING_TRY(who, launch_binding_combine(n, v, lambda, b->d_maps.p + n, b->f_complex(), b->f_sub(), b->energies(), d_forces,
-                                            d_energy, d_binding, st));
+  const BindingGroupMember& B0 = G.m[0];  // (a single call's launches take their few words from here)
+  // (a NULL stream: a single call on another binding runs on THAT binding's complex's stream, and the gather writes every
+  // binding's own buffers -- the group's stream waits for what those streams hold, as group_device joins its members')
+  for (int k = 1; k < count && !stream; k++) BINDING_TRY(who, join_streams(b0->group_event, bs[k]->m[0]->stream, st));
+  if (lam.device)
+    BINDING_TRY(who, launch_binding_gather_group(G, st));
   else
-    BINDING_TRY(who, launch_binding_combine_energy(v, lambda, b->energies(), d_energy, d_binding, st));
+    BINDING_TRY(who, launch_binding_gather(B0.n, B0.pos, B0.maps, b0->sub_pos(), st));
+  const int calls = one_call ? 1 : kBindingMembers, per_call = one_call ? kBindingMembers * count : count;
+  for (int c = 0; c < calls; c++) {
+    const int at = c * per_call;
+    // (a NULL stream is the call's first member's own: the first call's is the first complex's, `st`; the receptors' and the
+    // ligands' calls run on other streams than the gather and the combine, and are joined to `st` on both sides)
+    const hipStream_t own = stream ? st : ctxs[at]->stream;
+    BINDING_TRY(who, join_streams(b0->group_event, st, own));
+    const int rc = d_forces ? agbnp_hip_execute_group(ctxs + at, per_call, pos + at, frc + at, ene + at, stream)
+                            : agbnp_hip_energy_group(ctxs + at, per_call, pos + at, ene + at, stream);
+    if (rc != AGBNP_HIP_OK) {
+      // No combine launch will read what the failed call, and the calls before it, added to the bindings' buffers: they are
+      // cleared here, as well as the device still allows, so that nothing stale is added to by a later evaluation.  After a
+      // failure behind the first call the members that ran have logged an evaluation the binding has not: the message says so.
+      (void)join_streams(b0->group_event, own, st);
+      for (int k = 0; k < count; k++)
+        (void)hipMemsetAsync(bs[k]->f_complex(), 0, sizeof(double) * (6 * (size_t)bs[k]->n + kBindingMembers), st);
+      const char* note = c > 0 ? " (members of an earlier call of this group have evaluated: finish the bindings and discard that log)" : "";
+      for (int k = 0; k < count; k++)
+        for (const agbnp_hip_context* m : bs[k]->m)
+          if (!m->err.empty()) return binding_fail(rc, std::string(who) + ": " + m->err + note);
+      return binding_fail(rc, std::string(who) + ": a member's call failed" + note);
+    }
+    BINDING_TRY(who, join_streams(b0->group_event, own, st));
+  }
+  for (int k = 0; k < count; k++) G.m[k].v = binding_verdicts(bs[k]);
+  if (lam.device && d_forces)
+    BINDING_TRY(who, launch_binding_combine_group(G, st));
+  else if (lam.device)
+    BINDING_TRY(who, launch_binding_combine_energy_group(G, st));
+  else if (d_forces)
+    BINDING_TRY(who, launch_binding_combine(B0.n, B0.v, lam.host, B0.maps + B0.n, b0->f_complex(), b0->f_sub(), b0->energies(), B0.forces,
+                                            B0.energy, B0.binding, st));
+  else
+    BINDING_TRY(who, launch_binding_combine_energy(B0.v, lam.host, b0->energies(), B0.energy, B0.binding, st));
+  // (a NULL stream: every other binding's agbnp_hip_binding_finish(NULL) drains its own complex's stream, which waits for the combine)
+  for (int k = 1; k < count && !stream; k++) BINDING_TRY(who, join_streams(b0->group_event, st, bs[k]->m[0]->stream));
   return AGBNP_HIP_OK;
+}
+
+// a device entry point has enqueued an evaluation of b on `stream`
+void binding_note(agbnp_hip_binding* b, void* stream) {
+  b->enqueued++;
+  if (stream && std::find(b->streams.begin(), b->streams.end(), stream) == b->streams.end()) b->streams.push_back(stream);
 }
 
 // drains `stream`, finishes the three members and forms the union of their logs: `out` the indices (ascending), *count their
@@ -137,57 +226,75 @@ int binding_carry(agbnp_hip_binding* b, const char* who) {
   return AGBNP_HIP_OK;
 }
 
+// The host entry points' evaluation, on the first complex's own stream: every binding's staging buffers made on first use, its
+// positions up, its output words zeroed (the device path ADDS), the device path, the outputs on their way back to h_host.
+int binding_stage(agbnp_hip_binding* const* bs, int count, const double* const* positions, const Lambdas& lam, bool energy_only,
+                  const char* who) {
+  const hipStream_t st = bs[0]->m[0]->stream;
+  const double* d_pos[kMaxBindingGroup];
+  double *d_frc[kMaxBindingGroup], *d_ene[kMaxBindingGroup], *d_u[kMaxBindingGroup];
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_binding* const b = bs[i];
+    const size_t n3 = 3 * (size_t)b->n;
+    if (b->d_host.p == nullptr) BINDING_TRY(who, b->d_host.alloc(2 * n3 + 2));
+    b->h_host.resize(n3 + 2);
+    d_pos[i] = b->d_host.p;
+    d_frc[i] = b->d_host.p + n3;
+    d_ene[i] = d_frc[i] + n3;
+    d_u[i] = d_ene[i] + 1;
+    BINDING_TRY(who, hipMemcpyAsync(b->d_host.p, positions[i], sizeof(double) * n3, hipMemcpyHostToDevice, st));
+    BINDING_TRY(who, hipMemsetAsync(d_frc[i], 0, sizeof(double) * (n3 + 2), st));
+  }
+  const int rc = binding_enqueue(bs, count, d_pos, lam, energy_only ? nullptr : d_frc, d_ene, d_u, nullptr, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++)
+    BINDING_TRY(who, hipMemcpyAsync(bs[i]->h_host.data(), d_frc[i], sizeof(double) * bs[i]->h_host.size(), hipMemcpyDeviceToHost, st));
+  return AGBNP_HIP_OK;
+}
+
+// ... and, once the stream is drained and the evaluation found complete, what came back: F_lambda ADDED to the caller's forces
+// (null: the energy-only form), the two scalars stored
+void binding_deliver(const agbnp_hip_binding* b, double* forces, double* energy, double* binding_energy) {
+  const size_t n3 = 3 * (size_t)b->n;
+  for (size_t k = 0; k < n3 && forces; k++) forces[k] += b->h_host[k];
+  if (energy) *energy = b->h_host[n3];
+  if (binding_energy) *binding_energy = b->h_host[n3 + 1];
+}
+
 // agbnp_hip_binding_execute_host and (forces null) agbnp_hip_binding_energy_host: the device path on the binding's staging
 // buffers and the complex's own stream; a withheld evaluation is repeated here
 int binding_host(agbnp_hip_binding* b, const double* pos, double lambda, double* forces, double* energy, double* binding_energy,
                  const char* who) {
   int rc = binding_carry(b, who);
   if (rc != AGBNP_HIP_OK) return rc;
-  const size_t n3 = 3 * (size_t)b->n;
   BINDING_TRY(who, hipSetDevice(b->device));
-  if (b->d_host.p == nullptr) BINDING_TRY(who, b->d_host.alloc(2 * n3 + 2));
-  b->h_host.resize(n3 + 2);
-  const hipStream_t st = b->m[0]->stream;
-  double* const d_pos = b->d_host.p;
-  double* const d_out = b->d_host.p + n3;  // [3n] forces, E_lambda, u
   for (int attempt = 0; attempt < 10; attempt++) {
-    BINDING_TRY(who, hipMemcpyAsync(d_pos, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
-    BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (n3 + 2), st));
-    rc = binding_enqueue(b, d_pos, lambda, forces ? d_out : nullptr, d_out + n3, d_out + n3 + 1, nullptr, who);
+    rc = binding_stage(&b, 1, &pos, Lambdas{lambda, nullptr}, forces == nullptr, who);
     if (rc != AGBNP_HIP_OK) return rc;
-    BINDING_TRY(who, hipMemcpyAsync(b->h_host.data(), d_out, sizeof(double) * (n3 + 2), hipMemcpyDeviceToHost, st));
     std::vector<int> bad;
     int count = 0;
     rc = binding_harvest(b, nullptr, bad, &count, who);  // (waits for the stream)
     if (rc != AGBNP_HIP_OK) return rc;
     if (count) continue;
-    for (size_t k = 0; k < n3 && forces; k++) forces[k] += b->h_host[k];
-    if (energy) *energy = b->h_host[n3];
-    if (binding_energy) *binding_energy = b->h_host[n3 + 1];
+    binding_deliver(b, forces, energy, binding_energy);
     return AGBNP_HIP_OK;
   }
   return binding_fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
 }
 
+// agbnp_hip_binding_execute_device and (energy_only, d_forces null) agbnp_hip_binding_energy_device: the single entry points'
+// own short checks, then a group of one with a host lambda
 int binding_device(agbnp_hip_binding* b, const double* d_pos, double lambda, double* d_forces, bool energy_only, double* d_energy,
                    double* d_binding, void* stream, const char* who) {
   if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   if (!d_pos || (!energy_only && !d_forces) || (energy_only && !d_energy && !d_binding))
     return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
   if (!std::isfinite(lambda)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": lambda must be finite");
-  const int rc = binding_enqueue(b, d_pos, lambda, energy_only ? nullptr : d_forces, d_energy, d_binding, stream, who);
+  const int rc = binding_enqueue(&b, 1, &d_pos, Lambdas{lambda, nullptr}, energy_only ? nullptr : &d_forces, &d_energy, &d_binding, stream, who);
   if (rc != AGBNP_HIP_OK) return rc;
-  b->enqueued++;
-  if (stream && std::find(b->streams.begin(), b->streams.end(), stream) == b->streams.end()) b->streams.push_back(stream);
+  binding_note(b, stream);
   return AGBNP_HIP_OK;
 }
-
-// ---- Binding groups (agbnp_hip_binding_execute_group and its kin): several bindings' evaluations on one gather launch, the
-// members' evaluations through the public group entry points -- one call over all 3 count members where they fit a group, else
-// one call per kind (complexes, receptors, ligands: same-kind members of one system share a launch set) -- and one combine
-// launch, which takes every binding's lambda from device memory.  Per binding exactly what binding_enqueue does.
-
-bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a && b && a < b + nb && b < a + na; }
 
 // what every group form checks of its bindings, before anything is launched or changed
 int check_bindings(agbnp_hip_binding* const* bs, int count, const char* who) {
@@ -202,108 +309,7 @@ int check_bindings(agbnp_hip_binding* const* bs, int count, const char* who) {
   return AGBNP_HIP_OK;
 }
 
-// `to` waits for what is on `from` now (b's event: made on first use)
-int binding_join(agbnp_hip_binding* b, hipStream_t from, hipStream_t to, const char* who) {
-  if (from == to) return AGBNP_HIP_OK;
-  if (!b->group_event) BINDING_TRY(who, hipEventCreateWithFlags(&b->group_event, hipEventDisableTiming));
-  BINDING_TRY(who, hipEventRecord(b->group_event, from));
-  BINDING_TRY(who, hipStreamWaitEvent(to, b->group_event, 0));
-  return AGBNP_HIP_OK;
-}
-
-// one evaluation of every binding on `stream` (NULL: the first complex's own); the arguments have been checked.  d_forces null:
-// the energy-only form; d_energies / d_bindings null: every entry null.
-int binding_group_enqueue(agbnp_hip_binding* const* bs, int count, const double* const* d_pos, const double* d_lambdas,
-                          double* const* d_forces, double* const* d_energies, double* const* d_bindings, void* stream, const char* who) {
-  agbnp_hip_binding* const b0 = bs[0];
-  for (int k = 0; k < count; k++) clear_member_errors(bs[k]);
-  hipStream_t st;
-  if (enter(b0->m[0], stream, &st) != AGBNP_HIP_OK) return member_fail(b0, AGBNP_HIP_ERR_DEVICE, who);
-  if (is_capturing(st))
-    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
-                        std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
-  BindingGroupArgs G;
-  std::memset(&G, 0, sizeof(G));
-  G.count = count;
-  G.lambdas = d_lambdas;
-  agbnp_hip_context* ctxs[kBindingMembers * kMaxBindingGroup];
-  const double* pos[kBindingMembers * kMaxBindingGroup];
-  double *frc[kBindingMembers * kMaxBindingGroup], *ene[kBindingMembers * kMaxBindingGroup];
-  // members in one call: binding by binding; in one call per kind: kind by kind
-  const bool one_call = kBindingMembers * count <= kMaxGroup;
-  for (int k = 0; k < count; k++) {
-    agbnp_hip_binding* const b = bs[k];
-    BindingGroupMember& B = G.m[k];
-    B.maps = b->d_maps.p;
-    B.work = b->d_work.p;
-    B.pos = d_pos[k];
-    B.forces = d_forces ? d_forces[k] : nullptr;
-    B.energy = d_energies ? d_energies[k] : nullptr;
-    B.binding = d_bindings ? d_bindings[k] : nullptr;
-    B.n = b->n;
-    G.first[k + 1] = G.first[k] + (b->n + 255) / 256;
-    const double* const p[kBindingMembers] = {d_pos[k], b->sub_pos(), b->sub_pos() + 3 * (size_t)b->nr};
-    double* const f[kBindingMembers] = {b->f_complex(), b->f_sub(), b->f_sub() + 3 * (size_t)b->nr};
-    for (int m = 0; m < kBindingMembers; m++) {
-      const int at = one_call ? kBindingMembers * k + m : count * m + k;
-      ctxs[at] = b->m[m];
-      pos[at] = p[m];
-      frc[at] = f[m];
-      ene[at] = b->energies() + m;
-    }
-  }
-  // (a NULL stream: a single call on another binding runs on THAT binding's complex's stream, and the gather writes every
-  // binding's own buffers -- the group's stream waits for what those streams hold, as group_device joins its members')
-  for (int k = 1; k < count && !stream; k++) {
-    const int rc = binding_join(b0, bs[k]->m[0]->stream, st, who);
-    if (rc != AGBNP_HIP_OK) return rc;
-  }
-  BINDING_TRY(who, launch_binding_gather_group(G, st));
-  const int calls = one_call ? 1 : kBindingMembers, per_call = one_call ? kBindingMembers * count : count;
-  for (int c = 0; c < calls; c++) {
-    const int at = c * per_call;
-    // (a NULL stream is the call's first member's own: the receptors' and the ligands' calls run on other streams than the
-    // gather and the combine, and are joined to the first complex's on both sides)
-    const hipStream_t own = stream ? st : ctxs[at]->stream;
-    int rc = binding_join(b0, st, own, who);
-    if (rc != AGBNP_HIP_OK) return rc;
-    rc = d_forces ? agbnp_hip_execute_group(ctxs + at, per_call, pos + at, frc + at, ene + at, stream)
-                  : agbnp_hip_energy_group(ctxs + at, per_call, pos + at, ene + at, stream);
-    if (rc != AGBNP_HIP_OK) {
-      // No combine launch will read what the calls before this one added to the bindings' buffers: they are cleared here, as
-      // well as the device still allows, so that nothing stale is added to by a later evaluation.  After a failure behind the
-      // first call the members that ran have logged an evaluation the binding has not: the message says so.
-      (void)binding_join(b0, own, st, who);
-      for (int k = 0; k < count; k++)
-        (void)hipMemsetAsync(bs[k]->f_complex(), 0, sizeof(double) * (6 * (size_t)bs[k]->n + kBindingMembers), st);
-      const char* note = c > 0 ? " (members of an earlier call of this group have evaluated: finish the bindings and discard that log)" : "";
-      for (int k = 0; k < count; k++)
-        for (const agbnp_hip_context* m : bs[k]->m)
-          if (!m->err.empty()) return binding_fail(rc, std::string(who) + ": " + m->err + note);
-      return binding_fail(rc, std::string(who) + ": a member's call failed" + note);
-    }
-    rc = binding_join(b0, own, st, who);
-    if (rc != AGBNP_HIP_OK) return rc;
-  }
-  for (int k = 0; k < count; k++)  // (the members' blocks name this evaluation's words until their next evaluation)
-    for (int m = 0; m < kBindingMembers; m++) {
-      const PairArgs& P = bs[k]->m[m]->P;
-      G.m[k].v.estatus[m] = P.estatus;
-      G.m[k].v.epoch[m] = P.epoch;
-      G.m[k].v.five[m] = P.five;
-    }
-  if (d_forces)
-    BINDING_TRY(who, launch_binding_combine_group(G, st));
-  else
-    BINDING_TRY(who, launch_binding_combine_energy_group(G, st));
-  // (a NULL stream: every other binding's agbnp_hip_binding_finish(NULL) drains its own complex's stream, which waits for the combine)
-  for (int k = 1; k < count && !stream; k++) {
-    const int rc = binding_join(b0, st, bs[k]->m[0]->stream, who);
-    if (rc != AGBNP_HIP_OK) return rc;
-  }
-  return AGBNP_HIP_OK;
-}
-
+// agbnp_hip_binding_execute_group and (energy_only, d_forces null) agbnp_hip_binding_energy_group
 int binding_group_device(agbnp_hip_binding* const* bs, int count, const double* const* d_pos, const double* d_lambdas,
                          double* const* d_forces, bool energy_only, double* const* d_energies, double* const* d_bindings, void* stream,
                          const char* who) {
@@ -334,13 +340,9 @@ int binding_group_device(agbnp_hip_binding* const* bs, int count, const double* 
             return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": output buffers of two bindings overlap");
     }
   }
-  rc = binding_group_enqueue(bs, count, d_pos, d_lambdas, energy_only ? nullptr : d_forces, d_energies, d_bindings, stream, who);
+  rc = binding_enqueue(bs, count, d_pos, Lambdas{0.0, d_lambdas}, energy_only ? nullptr : d_forces, d_energies, d_bindings, stream, who);
   if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count; i++) {
-    agbnp_hip_binding* const b = bs[i];
-    b->enqueued++;
-    if (stream && std::find(b->streams.begin(), b->streams.end(), stream) == b->streams.end()) b->streams.push_back(stream);
-  }
+  for (int i = 0; i < count; i++) binding_note(bs[i], stream);
   return AGBNP_HIP_OK;
 }
 
@@ -362,47 +364,44 @@ int binding_group_host(agbnp_hip_binding* const* bs, int count, const double* co
   agbnp_hip_binding* const b0 = bs[0];
   BINDING_TRY(who, hipSetDevice(b0->device));
   const hipStream_t st = b0->m[0]->stream;
-  const double* d_pos[kMaxBindingGroup];
-  double *d_frc[kMaxBindingGroup], *d_ene[kMaxBindingGroup], *d_u[kMaxBindingGroup];
   for (int i = 0; i < count; i++) {
-    agbnp_hip_binding* const b = bs[i];
-    rc = binding_carry(b, who);  // (every binding's streams are idle from here on)
+    rc = binding_carry(bs[i], who);  // (every binding's streams are idle from here on)
     if (rc != AGBNP_HIP_OK) return rc;
-    const size_t n3 = 3 * (size_t)b->n;
-    if (b->d_host.p == nullptr) BINDING_TRY(who, b->d_host.alloc(2 * n3 + 2));
-    b->h_host.resize(n3 + 2);
-    BINDING_TRY(who, hipMemcpyAsync(b->d_host.p, positions[i], sizeof(double) * n3, hipMemcpyHostToDevice, st));
-    BINDING_TRY(who, hipMemsetAsync(b->d_host.p + n3, 0, sizeof(double) * (n3 + 2), st));
-    d_pos[i] = b->d_host.p;
-    d_frc[i] = b->d_host.p + n3;
-    d_ene[i] = b->d_host.p + 2 * n3;
-    d_u[i] = b->d_host.p + 2 * n3 + 1;
   }
   if (b0->d_group_lambdas.p == nullptr) BINDING_TRY(who, b0->d_group_lambdas.alloc(kMaxBindingGroup));
   BINDING_TRY(who, hipMemcpyAsync(b0->d_group_lambdas.p, lambdas, sizeof(double) * count, hipMemcpyHostToDevice, st));
-  rc = binding_group_enqueue(bs, count, d_pos, b0->d_group_lambdas.p, energy_only ? nullptr : d_frc, d_ene, d_u, nullptr, who);
+  rc = binding_stage(bs, count, positions, Lambdas{0.0, b0->d_group_lambdas.p}, energy_only, who);
   if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count; i++)
-    BINDING_TRY(who, hipMemcpyAsync(bs[i]->h_host.data(), d_frc[i], sizeof(double) * (3 * (size_t)bs[i]->n + 2), hipMemcpyDeviceToHost, st));
   BINDING_TRY(who, hipStreamSynchronize(st));
   for (int i = 0; i < count; i++) {
     agbnp_hip_binding* const b = bs[i];
-    const size_t n3 = 3 * (size_t)b->n;
+    double* const fi = energy_only ? nullptr : forces[i];
+    double *const ei = energies ? &energies[i] : nullptr, *const ui = binding_energies ? &binding_energies[i] : nullptr;
     std::vector<int> bad;
     int withheld = 0;
     rc = binding_harvest(b, nullptr, bad, &withheld, who);
+    // (withheld: repeated alone, as agbnp_hip_binding_execute_host / _energy_host repeats)
+    if (rc == AGBNP_HIP_OK && withheld) rc = binding_host(b, positions[i], lambdas[i], fi, ei, ui, who);
     if (rc != AGBNP_HIP_OK) return rc;
-    if (withheld) {  // repeated alone, as agbnp_hip_binding_execute_host / _energy_host repeats
-      rc = binding_host(b, positions[i], lambdas[i], energy_only ? nullptr : forces[i], energies ? &energies[i] : nullptr,
-                        binding_energies ? &binding_energies[i] : nullptr, who);
-      if (rc != AGBNP_HIP_OK) return rc;
-      continue;
-    }
-    for (size_t k = 0; k < n3 && !energy_only; k++) forces[i][k] += b->h_host[k];
-    if (energies) energies[i] = b->h_host[n3];
-    if (binding_energies) binding_energies[i] = b->h_host[n3 + 1];
+    if (!withheld) binding_deliver(b, fi, ei, ui);
   }
   return AGBNP_HIP_OK;
+}
+
+// member k's subset of the complex's five parameter arrays (k = 0: all of them), in the member's own atom order
+struct MemberParams {
+  std::vector<double> r, g, a, q;
+  std::vector<int> h;
+};
+MemberParams member_params(const agbnp_hip_binding* b, int k, const double* radius, const double* gamma, const double* vdw_alpha,
+                           const double* charge, const int* ishydrogen) {
+  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {b->n, b->nr, b->nl};
+  MemberParams p;
+  for (int t = 0; t < count[k]; t++) {
+    const int i = k == 0 ? t : b->sub2complex[first[k] + t];
+    p.r.push_back(radius[i]), p.g.push_back(gamma[i]), p.a.push_back(vdw_alpha[i]), p.q.push_back(charge[i]), p.h.push_back(ishydrogen[i]);
+  }
+  return p;
 }
 }  // namespace
 
@@ -450,16 +449,10 @@ int agbnp_hip_binding_create(agbnp_hip_binding** out, int n, const double* radiu
   };
   // the complex first: its parameter checks (the reference's equal-gamma error among them) run on the host before its first
   // device call, and a subset of equal gammas is equal
-  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {n, b->nr, b->nl};
   for (int k = 0; k < kBindingMembers; k++) {
-    std::vector<double> r(count[k]), g(count[k]), a(count[k]), q(count[k]);
-    std::vector<int> h(count[k]);
-    for (int t = 0; t < count[k]; t++) {
-      const int i = k == 0 ? t : b->sub2complex[first[k] + t];
-      r[t] = radius[i], g[t] = gamma[i], a[t] = vdw_alpha[i], q[t] = charge[i], h[t] = ishydrogen[i];
-    }
-    const int rc = agbnp_hip_create(&b->m[k], count[k], r.data(), g.data(), a.data(), q.data(), h.data(), version, nonbonded_method,
-                                    cutoff, device);
+    const MemberParams p = member_params(b, k, radius, gamma, vdw_alpha, charge, ishydrogen);
+    const int rc = agbnp_hip_create(&b->m[k], (int)p.h.size(), p.r.data(), p.g.data(), p.a.data(), p.q.data(), p.h.data(), version,
+                                    nonbonded_method, cutoff, device);
     if (rc != AGBNP_HIP_OK) return bail(rc);
   }
   std::vector<int> maps(b->sub2complex);
@@ -562,15 +555,9 @@ int agbnp_hip_binding_update_parameters(agbnp_hip_binding* b, int n, const doubl
   if (n != b->n) return binding_fail(AGBNP_HIP_ERR_PARAMETERS, "updateParametersInContext: The number of AGBNP particles has changed");
   // (a member drains its own stream and the caller streams it has noted; the binding's buffers are not touched)
   clear_member_errors(b);
-  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {n, b->nr, b->nl};
   for (int k = 0; k < kBindingMembers; k++) {
-    std::vector<double> r(count[k]), g(count[k]), a(count[k]), q(count[k]);
-    std::vector<int> h(count[k]);
-    for (int t = 0; t < count[k]; t++) {
-      const int i = k == 0 ? t : b->sub2complex[first[k] + t];
-      r[t] = radius[i], g[t] = gamma[i], a[t] = vdw_alpha[i], q[t] = charge[i], h[t] = ishydrogen[i];
-    }
-    const int rc = agbnp_hip_update_parameters(b->m[k], count[k], r.data(), g.data(), a.data(), q.data(), h.data());
+    const MemberParams p = member_params(b, k, radius, gamma, vdw_alpha, charge, ishydrogen);
+    const int rc = agbnp_hip_update_parameters(b->m[k], (int)p.h.size(), p.r.data(), p.g.data(), p.a.data(), p.q.data(), p.h.data());
     if (rc != AGBNP_HIP_OK) return member_fail(b, rc, who);
   }
   return AGBNP_HIP_OK;

@@ -349,3 +349,7 @@ ENGINE_LOCAL int harvest(agbnp_hip_context* c, int* repeat, hipStream_t st);
 ENGINE_LOCAL int catch_up(agbnp_hip_context* c);
 ENGINE_LOCAL int carry_unfinished(agbnp_hip_context* c);
 ENGINE_LOCAL int host_evaluation(agbnp_hip_context* c, const double* pos, double* forces, double* energy);
+
+// ---- engine_group.hip (what replica groups and binding groups both need)
+ENGINE_LOCAL bool spans_overlap(const double* a, size_t na, const double* b, size_t nb);  // two output spans; a null one overlaps nothing
+ENGINE_LOCAL hipError_t join_streams(hipEvent_t& event, hipStream_t from, hipStream_t to);

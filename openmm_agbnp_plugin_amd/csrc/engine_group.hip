@@ -1,6 +1,18 @@
 // Replica groups (engine_context.h; agbnp_hip_execute_group, group_args.h): the evaluations of several contexts on one set of launches.
 #include "engine_context.h"
 
+// (shared with the binding groups, engine_binding.hip, whose output pointers may be null: a null span overlaps nothing)
+bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a && b && a < b + nb && b < a + na; }
+
+// joins two streams through `event` (made on first use): `to` waits for what is on `from` now
+hipError_t join_streams(hipEvent_t& event, hipStream_t from, hipStream_t to) {
+  if (from == to) return hipSuccess;
+  hipError_t e = event ? hipSuccess : hipEventCreateWithFlags(&event, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(event, from);
+  if (e == hipSuccess) e = hipStreamWaitEvent(to, event, 0);
+  return e;
+}
+
 namespace {
 // A member shares the launches of its launch set when its evaluation is exactly the default launch sequence: the five-launch
 // mode with the host-named set, the Reference semantics and (version 1) the FP64 row form, an LDS-resident capacity variant, the
@@ -11,8 +23,6 @@ bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, const EvalRe
   if (r.in.posq || r.omm.force_fixed || c->P.five != 1) return false;
   return c->version == 0 || plan.fused || r.energy_only;
 }
-
-bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
 
 // The arguments of a group call, checked before anything is launched or changed.  forces is null for an energy-only call
 // (energy_only says that this was asked for).  d_energies: the device entry points' energy words, one buffer per member, which --
@@ -190,15 +200,6 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* 
   return AGBNP_HIP_OK;
 }
 
-// joins a member's own stream and the group's: `to` waits for what is on `from` now
-int join_streams(agbnp_hip_context* c, hipStream_t from, hipStream_t to) {
-  if (from == to) return AGBNP_HIP_OK;
-  if (!c->group_event) HIP_TRY(c, hipEventCreateWithFlags(&c->group_event, hipEventDisableTiming));
-  HIP_TRY(c, hipEventRecord(c->group_event, from));
-  HIP_TRY(c, hipStreamWaitEvent(to, c->group_event, 0));
-  return AGBNP_HIP_OK;
-}
-
 // agbnp_hip_execute_group and -- energy_only, d_forces null: for every member what agbnp_hip_energy_device would do, the sharing
 // members on FOUR (version 0: two) launches per launch set, nothing written to a force buffer of a caller -- agbnp_hip_energy_group
 int group_device(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces, bool energy_only,
@@ -219,10 +220,7 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const double* const*
     // (NULL: the first member's own stream, which no caller can name -- it is not noted as a caller stream; every member's own
     // stream is joined to it on both sides instead, so that the member's agbnp_hip_finish(NULL) drains the group's work)
     note_stream(c, stream);
-    if (!stream) {
-      rc = join_streams(c, c->stream, st);
-      if (rc != AGBNP_HIP_OK) return rc;
-    }
+    if (!stream) HIP_TRY(c, join_streams(c->group_event, c->stream, st));
     reqs[i].pos = d_positions[i];
     reqs[i].force = energy_only ? c->d_eo_force.p : d_forces[i];
     reqs[i].energy = d_energies[i];
@@ -231,10 +229,7 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const double* const*
   }
   rc = group_enqueue(ctxs, count, reqs);
   if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count && !stream; i++) {
-    rc = join_streams(ctxs[i], st, ctxs[i]->stream);
-    if (rc != AGBNP_HIP_OK) return rc;
-  }
+  for (int i = 0; i < count && !stream; i++) HIP_TRY(ctxs[i], join_streams(ctxs[i]->group_event, st, ctxs[i]->stream));
   return AGBNP_HIP_OK;
 }
 

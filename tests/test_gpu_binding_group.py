@@ -14,7 +14,7 @@ import openmm_agbnp_plugin_amd as P
 from tests.binding_restatement import combine
 from tests.edge_systems import edge_systems
 from tests.gpu_helpers import five_groups  # noqa: F401
-from tests.test_gpu_binding import LAMBDAS, Buffers, _binding, _moved, check, reference
+from tests.test_gpu_binding import EDGES, LAMBDAS, Buffers, _binding, _moved, check, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -181,6 +181,44 @@ def test_deterministic_mode_is_bit_identical_to_six_single_calls(gpu_required, s
         for other, what in ((b, "run to run"), (c, "against the single call")):
             assert a[0] == other[0] and a[1] == other[1] and np.array_equal(a[2], other[2]), f"binding {k} differs {what}"
         check(a, reference(s, LIGAND, f"jitter{k % 4}", geoms[k]), lams[k], what=f"deterministic binding {k}")
+
+
+def _bits(*values):
+    return [np.ascontiguousarray(v, dtype=np.float64).reshape(-1).view(np.uint64) for v in values]
+
+
+@pytest.mark.parametrize("case", sorted(EDGES) + ["trpcage_0_15"])
+def test_a_group_of_one_is_the_single_call_bit_for_bit(gpu_required, systems, five_groups, case):
+    """The single and the group kernels are wrappers round ONE per-atom gather and ONE per-atom combine: at the shapes where a
+    wrapper could index differently (one atom in the last workgroup, a ligand at either end, a strewn ligand, a receptor without
+    a heavy atom) a group of one gives the single call's F_lambda, E_lambda and u bit for bit, in the deterministic mode (which
+    is bit-identical from run to run, so a difference is the wrappers'), and so does the energy-only form, which writes no force."""
+    torch = pytest.importorskip("torch")
+    if case == "trpcage_0_15":
+        s, ligand, version = systems("trpcage"), LIGAND, 1
+    else:
+        name, ligand, version = EDGES[case]
+        s = edge_systems()[name]
+        ligand = np.flatnonzero(s.ishydrogen == 0).tolist() if isinstance(ligand, str) else list(ligand)
+    b = _binding(s, ligand, version=version, mode="deterministic")
+    b.execute(s.pos, 0.35)  # (settles the capacity variants: the device calls below repeat nothing)
+    sentinel = -123.456
+    for form, fill in (("execute", (0.0, 0.0, 0.0)), ("energy", (0.0, 0.0, sentinel))):
+        single = Buffers(torch, s.n, fill)
+        single.load(s.pos)
+        getattr(single, form)(b, 0.35)
+        assert b.finish(single.stream) == 0
+        torch.cuda.synchronize()
+        g = Group(torch, [b], [0.35], fill)
+        g.load([s.pos])
+        getattr(g, form)()
+        assert g.finish() == [0]
+        for a, c, what in zip(_bits(*single.result()), _bits(*g.results()[0]), ("E_lambda", "u", "F_lambda")):
+            assert np.array_equal(a, c), f"{case} {form}: {what} of a group of one is not the single call's"
+        assert single.result()[0] != 0.0  # (an evaluation was added, not two withheld ones compared)
+        if form == "energy":
+            assert (single.frc == sentinel).all().item() and (g.bufs[0].frc == sentinel).all().item()
+    assert b.withheld() == []
 
 
 # ---- 4. launch sharing -----------------------------------------------------------------------------------------------
