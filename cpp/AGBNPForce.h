@@ -75,7 +75,65 @@ class AGBNPForce {
   double solvent_radius;
 };
 
-class Binding;
+// What the classes below share (not part of the mirrored interface).
+namespace detail {
+
+// a return code of the library: a failure throws with the message the library keeps for `ctx` (null: the message of the calls
+// that are not made on a context)
+inline void check(int rc, agbnp_hip_context* ctx = nullptr) {
+  if (rc != AGBNP_HIP_OK) throw OpenMMException(agbnp_hip_last_error(ctx));
+}
+
+// the particle parameters of a force as they cross the C ABI
+struct Parameters {
+  std::vector<double> r, g, a, q;
+  std::vector<int> h;
+  int n() const { return (int)r.size(); }
+};
+inline Parameters gather(const AGBNPForce& force) {
+  Parameters p;
+  const int n = force.getNumParticles();
+  p.r.resize(n), p.g.resize(n), p.a.resize(n), p.q.resize(n), p.h.resize(n);
+  for (int i = 0; i < n; i++) {
+    bool ish;
+    force.getParticleParameters(i, p.r[i], p.g[i], p.a[i], p.q[i], ish);
+    p.h[i] = ish ? 1 : 0;
+  }
+  return p;
+}
+
+// The arrays of a group call: the members' handles, their positions and, where `forces` is given, their forces.  `bound` and
+// `each` are the refusals of a wrong member count and of per-member arguments that are not one per member (`counted`: what the
+// caller has counted itself).  A member class names its handle type, its bound and its particle count, and hands out a member's
+// handle or throws (groupHandle).
+struct Group {
+  template <class Member>
+  struct Arrays {
+    std::vector<typename Member::Handle*> handles;
+    std::vector<const double*> pos;
+    std::vector<double*> frc;
+  };
+  template <class Member>
+  static Arrays<Member> collect(const std::string& who, const std::vector<Member*>& members, const char* bound, const char* each,
+                                bool counted, const std::vector<std::vector<double>>& positions,
+                                std::vector<std::vector<double>>* forces = nullptr) {
+    const size_t n = members.size();
+    if (n < 1 || n > Member::maxGroup) throw OpenMMException(who + "(): " + bound);
+    if (positions.size() != n || (forces && forces->size() != n) || !counted) throw OpenMMException(who + "(): " + each);
+    Arrays<Member> g;
+    g.handles.resize(n), g.pos.resize(n), g.frc.resize(forces ? n : 0);
+    for (size_t i = 0; i < n; i++) {
+      g.handles[i] = Member::groupHandle(members[i], who);
+      const size_t n3 = 3 * (size_t)members[i]->numParticles;
+      if (positions[i].size() != n3 || (forces && (*forces)[i].size() != n3)) throw OpenMMException(who + "(): arrays must hold 3N values");
+      g.pos[i] = positions[i].data();
+      if (forces) g.frc[i] = (*forces)[i].data();
+    }
+    return g;
+  }
+};
+
+}  // namespace detail
 
 // The "HIP platform" implementation of the plugin's kernel interface.
 class HipCalcAGBNPForceKernel {
@@ -89,13 +147,10 @@ class HipCalcAGBNPForceKernel {
   void initialize(const AGBNPForce& force) {
     agbnp_hip_destroy(ctx);
     ctx = nullptr;
-    std::vector<double> r, g, a, q;
-    std::vector<int> h;
-    gather(force, r, g, a, q, h);
-    numParticles = (int)r.size();
-    if (agbnp_hip_create(&ctx, numParticles, r.data(), g.data(), a.data(), q.data(), h.data(), (int)force.getVersion(),
-                         (int)force.getNonbondedMethod(), force.getCutoffDistance(), device) != AGBNP_HIP_OK)
-      throw OpenMMException(agbnp_hip_last_error(nullptr));
+    const detail::Parameters p = detail::gather(force);
+    numParticles = p.n();
+    detail::check(agbnp_hip_create(&ctx, p.n(), p.r.data(), p.g.data(), p.a.data(), p.q.data(), p.h.data(), (int)force.getVersion(),
+                                   (int)force.getNonbondedMethod(), force.getCutoffDistance(), device));
   }
 
   // CPU-platform data convention of the reference (ReferenceAGBNPKernels.cpp:27-35,197,794): forces are
@@ -104,22 +159,21 @@ class HipCalcAGBNPForceKernel {
                  bool includeEnergy = true) {
     (void)includeForces;
     (void)includeEnergy;
-    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+    need();
     if ((int)positions.size() != 3 * numParticles || (int)forces.size() != 3 * numParticles)
       throw OpenMMException("execute(): positions and forces must hold 3N values");
     double energy = 0.0;
-    if (agbnp_hip_execute_host(ctx, positions.data(), forces.data(), &energy) != AGBNP_HIP_OK)
-      throw OpenMMException(agbnp_hip_last_error(ctx));
+    check(agbnp_hip_execute_host(ctx, positions.data(), forces.data(), &energy));
     return energy;
   }
 
   // Energy-only evaluation (what OpenMM asks for with includeForces = false): the energy execute() would return at these
   // positions, without the force passes where the context allows it; no forces are written (include/agbnp_hip.h).
   double energy(const std::vector<double>& positions) {
-    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+    need();
     if ((int)positions.size() != 3 * numParticles) throw OpenMMException("energy(): positions must hold 3N values");
     double e = 0.0;
-    if (agbnp_hip_energy_host(ctx, positions.data(), &e) != AGBNP_HIP_OK) throw OpenMMException(agbnp_hip_last_error(ctx));
+    check(agbnp_hip_energy_host(ctx, positions.data(), &e));
     return e;
   }
 
@@ -127,12 +181,11 @@ class HipCalcAGBNPForceKernel {
   // AGBNP_HIP_DECOMPOSITION_TERMS planes of N doubles -- cavity, vdW, GB self, GB pair (each pair shared half and half) -- whose
   // sum over everything is the energy.  Version 0 has the cavity plane only.  No forces are written.
   double decompose(const std::vector<double>& positions, std::vector<double>& terms) {
-    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+    need();
     if ((int)positions.size() != 3 * numParticles) throw OpenMMException("decompose(): positions must hold 3N values");
     terms.assign((size_t)AGBNP_HIP_DECOMPOSITION_TERMS * numParticles, 0.0);
     double e = 0.0;
-    if (agbnp_hip_decompose_host(ctx, positions.data(), terms.data(), &e) != AGBNP_HIP_OK)
-      throw OpenMMException(agbnp_hip_last_error(ctx));
+    check(agbnp_hip_decompose_host(ctx, positions.data(), terms.data(), &e));
     return e;
   }
 
@@ -140,21 +193,11 @@ class HipCalcAGBNPForceKernel {
   // that can share them made once for all; positions[i] (3N_i) read, forces[i] accumulated, the members' energies returned.
   static std::vector<double> executeGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,
                                           const std::vector<std::vector<double>>& positions, std::vector<std::vector<double>>& forces) {
-    const size_t n = kernels.size();
-    if (n < 1 || n > AGBNP_HIP_MAX_GROUP) throw OpenMMException("executeGroup(): a group has 1 to 16 members");
-    if (positions.size() != n || forces.size() != n) throw OpenMMException("executeGroup(): one position and one force array per member");
-    std::vector<agbnp_hip_context*> ctxs(n);
-    std::vector<const double*> pos(n);
-    std::vector<double*> frc(n);
-    for (size_t i = 0; i < n; i++) {
-      if (!kernels[i] || !kernels[i]->ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
-      const size_t n3 = 3 * (size_t)kernels[i]->numParticles;
-      if (positions[i].size() != n3 || forces[i].size() != n3) throw OpenMMException("executeGroup(): arrays must hold 3N values");
-      ctxs[i] = kernels[i]->ctx, pos[i] = positions[i].data(), frc[i] = forces[i].data();
-    }
-    std::vector<double> energies(n, 0.0);
-    if (agbnp_hip_execute_group_host(ctxs.data(), (int)n, pos.data(), frc.data(), energies.data()) != AGBNP_HIP_OK)
-      throw OpenMMException(agbnp_hip_last_error(ctxs[0]));
+    auto g = detail::Group::collect("executeGroup", kernels, "a group has 1 to 16 members", "one position and one force array per member",
+                                    true, positions, &forces);
+    std::vector<double> energies(kernels.size(), 0.0);
+    detail::check(agbnp_hip_execute_group_host(g.handles.data(), (int)kernels.size(), g.pos.data(), g.frc.data(), energies.data()),
+                  g.handles[0]);
     return energies;
   }
 
@@ -162,52 +205,37 @@ class HipCalcAGBNPForceKernel {
   // on shared energy-only launches where the members allow it; no force is written anywhere.
   static std::vector<double> energyGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,
                                          const std::vector<std::vector<double>>& positions) {
-    const size_t n = kernels.size();
-    if (n < 1 || n > AGBNP_HIP_MAX_GROUP) throw OpenMMException("energyGroup(): a group has 1 to 16 members");
-    if (positions.size() != n) throw OpenMMException("energyGroup(): one position array per member");
-    std::vector<agbnp_hip_context*> ctxs(n);
-    std::vector<const double*> pos(n);
-    for (size_t i = 0; i < n; i++) {
-      if (!kernels[i] || !kernels[i]->ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
-      if (positions[i].size() != 3 * (size_t)kernels[i]->numParticles) throw OpenMMException("energyGroup(): arrays must hold 3N values");
-      ctxs[i] = kernels[i]->ctx, pos[i] = positions[i].data();
-    }
-    std::vector<double> energies(n, 0.0);
-    if (agbnp_hip_energy_group_host(ctxs.data(), (int)n, pos.data(), energies.data()) != AGBNP_HIP_OK)
-      throw OpenMMException(agbnp_hip_last_error(ctxs[0]));
+    auto g = detail::Group::collect("energyGroup", kernels, "a group has 1 to 16 members", "one position array per member", true, positions);
+    std::vector<double> energies(kernels.size(), 0.0);
+    detail::check(agbnp_hip_energy_group_host(g.handles.data(), (int)kernels.size(), g.pos.data(), energies.data()), g.handles[0]);
     return energies;
   }
 
   // The positions of the next evaluation are unrelated to the last ones (agbnp_hip_expect_jump): it lays the neighbour masks
   // down at its own positions first and is not withheld for the jump.
   void expectJump() {
-    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
-    if (agbnp_hip_expect_jump(ctx) != AGBNP_HIP_OK) throw OpenMMException(agbnp_hip_last_error(ctx));
+    need();
+    check(agbnp_hip_expect_jump(ctx));
   }
 
   void copyParametersToContext(const AGBNPForce& force) {
-    if (!ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
-    std::vector<double> r, g, a, q;
-    std::vector<int> h;
-    gather(force, r, g, a, q, h);
-    if (agbnp_hip_update_parameters(ctx, (int)r.size(), r.data(), g.data(), a.data(), q.data(), h.data()) != AGBNP_HIP_OK)
-      throw OpenMMException(agbnp_hip_last_error(ctx));
+    need();
+    const detail::Parameters p = detail::gather(force);
+    check(agbnp_hip_update_parameters(ctx, p.n(), p.r.data(), p.g.data(), p.a.data(), p.q.data(), p.h.data()));
   }
 
   agbnp_hip_context* handle() const { return ctx; }
 
  private:
-  friend class Binding;
-  static void gather(const AGBNPForce& force, std::vector<double>& r, std::vector<double>& g, std::vector<double>& a,
-                     std::vector<double>& q, std::vector<int>& h) {
-    const int n = force.getNumParticles();
-    r.resize(n), g.resize(n), a.resize(n), q.resize(n), h.resize(n);
-    for (int i = 0; i < n; i++) {
-      bool ish;
-      force.getParticleParameters(i, r[i], g[i], a[i], q[i], ish);
-      h[i] = ish ? 1 : 0;
-    }
+  friend struct detail::Group;
+  typedef agbnp_hip_context Handle;
+  static constexpr size_t maxGroup = AGBNP_HIP_MAX_GROUP;
+  static agbnp_hip_context* groupHandle(const HipCalcAGBNPForceKernel* k, const std::string&) {
+    if (!k || !k->ctx) throw OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called");
+    return k->ctx;
   }
+  void need() const { groupHandle(this, ""); }
+  void check(int rc) const { detail::check(rc, ctx); }
   agbnp_hip_context* ctx;
   int device;
   int numParticles;
@@ -223,13 +251,10 @@ class Binding {
   enum Member { Complex = 0, Receptor = 1, Ligand = 2 };
   Binding(const AGBNPForce& force, const std::vector<int>& ligandAtoms, int device = 0, int mode = AGBNP_HIP_MODE_REFERENCE)
       : b(nullptr), numParticles(force.getNumParticles()) {
-    std::vector<double> r, g, a, q;
-    std::vector<int> h;
-    HipCalcAGBNPForceKernel::gather(force, r, g, a, q, h);
-    if (agbnp_hip_binding_create(&b, numParticles, r.data(), g.data(), a.data(), q.data(), h.data(), ligandAtoms.data(),
-                                 (int)ligandAtoms.size(), (int)force.getVersion(), (int)force.getNonbondedMethod(),
-                                 force.getCutoffDistance(), device) != AGBNP_HIP_OK)
-      throw OpenMMException(agbnp_hip_last_error(nullptr));
+    const detail::Parameters p = detail::gather(force);
+    check(agbnp_hip_binding_create(&b, numParticles, p.r.data(), p.g.data(), p.a.data(), p.q.data(), p.h.data(), ligandAtoms.data(),
+                                   (int)ligandAtoms.size(), (int)force.getVersion(), (int)force.getNonbondedMethod(),
+                                   force.getCutoffDistance(), device));
     if (mode != AGBNP_HIP_MODE_REFERENCE) setMode(mode);
   }
   ~Binding() { agbnp_hip_binding_destroy(b); }
@@ -276,10 +301,8 @@ class Binding {
   void setMode(int mode) { check(agbnp_hip_binding_set_mode(b, mode)); }
   // `force` holds the parameters of the COMPLEX; every member gets its subset
   void copyParametersToContext(const AGBNPForce& force) {
-    std::vector<double> r, g, a, q;
-    std::vector<int> h;
-    HipCalcAGBNPForceKernel::gather(force, r, g, a, q, h);
-    check(agbnp_hip_binding_update_parameters(b, (int)r.size(), r.data(), g.data(), a.data(), q.data(), h.data()));
+    const detail::Parameters p = detail::gather(force);
+    check(agbnp_hip_binding_update_parameters(b, p.n(), p.r.data(), p.g.data(), p.a.data(), p.q.data(), p.h.data()));
   }
   // a member's context, for scalars, vectors, poll and wait_verdict; the binding owns it
   agbnp_hip_context* member(Member which) const { return agbnp_hip_binding_member(b, (int)which); }
@@ -287,9 +310,14 @@ class Binding {
   int getNumParticles() const { return numParticles; }
 
  private:
-  static void check(int rc) {
-    if (rc != AGBNP_HIP_OK) throw OpenMMException(agbnp_hip_last_error(nullptr));
+  friend struct detail::Group;
+  typedef agbnp_hip_binding Handle;
+  static constexpr size_t maxGroup = AGBNP_HIP_MAX_BINDING_GROUP;
+  static agbnp_hip_binding* groupHandle(const Binding* binding, const std::string& who) {
+    if (!binding) throw OpenMMException(who + "(): null binding");
+    return binding->b;
   }
+  static void check(int rc) { detail::check(rc); }  // (a binding's messages are kept with those of no context)
   agbnp_hip_binding* b;
   int numParticles;
 };
@@ -302,23 +330,12 @@ inline std::vector<double> executeBindingGroup(const std::vector<Binding*>& bind
                                                const std::vector<double>& lambdas, std::vector<std::vector<double>>& forces,
                                                std::vector<double>& bindingEnergies) {
   const size_t n = bindings.size();
-  if (n < 1 || n > AGBNP_HIP_MAX_BINDING_GROUP) throw OpenMMException("executeBindingGroup(): a binding group has 1 to 16 bindings");
-  if (positions.size() != n || forces.size() != n || lambdas.size() != n)
-    throw OpenMMException("executeBindingGroup(): one position array, one force array and one lambda per binding");
-  std::vector<agbnp_hip_binding*> bs(n);
-  std::vector<const double*> pos(n);
-  std::vector<double*> frc(n);
-  for (size_t i = 0; i < n; i++) {
-    if (!bindings[i]) throw OpenMMException("executeBindingGroup(): null binding");
-    const size_t n3 = 3 * (size_t)bindings[i]->getNumParticles();
-    if (positions[i].size() != n3 || forces[i].size() != n3) throw OpenMMException("executeBindingGroup(): arrays must hold 3N values");
-    bs[i] = bindings[i]->handle(), pos[i] = positions[i].data(), frc[i] = forces[i].data();
-  }
+  auto g = detail::Group::collect("executeBindingGroup", bindings, "a binding group has 1 to 16 bindings",
+                                  "one position array, one force array and one lambda per binding", lambdas.size() == n, positions, &forces);
   std::vector<double> energies(n, 0.0);
   bindingEnergies.assign(n, 0.0);
-  if (agbnp_hip_binding_execute_group_host(bs.data(), (int)n, pos.data(), lambdas.data(), frc.data(), energies.data(),
-                                           bindingEnergies.data()) != AGBNP_HIP_OK)
-    throw OpenMMException(agbnp_hip_last_error(nullptr));
+  detail::check(agbnp_hip_binding_execute_group_host(g.handles.data(), (int)n, g.pos.data(), lambdas.data(), g.frc.data(), energies.data(),
+                                                     bindingEnergies.data()));
   return energies;
 }
 
@@ -326,19 +343,12 @@ inline std::vector<double> executeBindingGroup(const std::vector<Binding*>& bind
 inline std::vector<double> energyBindingGroup(const std::vector<Binding*>& bindings, const std::vector<std::vector<double>>& positions,
                                               const std::vector<double>& lambdas, std::vector<double>& bindingEnergies) {
   const size_t n = bindings.size();
-  if (n < 1 || n > AGBNP_HIP_MAX_BINDING_GROUP) throw OpenMMException("energyBindingGroup(): a binding group has 1 to 16 bindings");
-  if (positions.size() != n || lambdas.size() != n) throw OpenMMException("energyBindingGroup(): one position array and one lambda per binding");
-  std::vector<agbnp_hip_binding*> bs(n);
-  std::vector<const double*> pos(n);
-  for (size_t i = 0; i < n; i++) {
-    if (!bindings[i]) throw OpenMMException("energyBindingGroup(): null binding");
-    if (positions[i].size() != 3 * (size_t)bindings[i]->getNumParticles()) throw OpenMMException("energyBindingGroup(): arrays must hold 3N values");
-    bs[i] = bindings[i]->handle(), pos[i] = positions[i].data();
-  }
+  auto g = detail::Group::collect("energyBindingGroup", bindings, "a binding group has 1 to 16 bindings",
+                                  "one position array and one lambda per binding", lambdas.size() == n, positions);
   std::vector<double> energies(n, 0.0);
   bindingEnergies.assign(n, 0.0);
-  if (agbnp_hip_binding_energy_group_host(bs.data(), (int)n, pos.data(), lambdas.data(), energies.data(), bindingEnergies.data()) != AGBNP_HIP_OK)
-    throw OpenMMException(agbnp_hip_last_error(nullptr));
+  detail::check(agbnp_hip_binding_energy_group_host(g.handles.data(), (int)n, g.pos.data(), lambdas.data(), energies.data(),
+                                                    bindingEnergies.data()));
   return energies;
 }
 

@@ -8,6 +8,9 @@ behaviour (openmmapi/include/AGBNPForce.h:39-155, openmmapi/src/AGBNPForce.cpp:1
 `AGBNPContext` is the small stand-in for the OpenMM Context + ForceImpl pair that the parity tests
 and benchmarks need (OpenMM itself is not part of this path): it owns positions and calls the kernel
 the way AGBNPForceImpl does (openmmapi/src/AGBNPForceImpl.cpp:27-46).
+
+Every call into the library is made the same way: the library is looked up when the call is made, after the
+argument checks, and a failure surfaces as an OpenMMException with the library's own message (`_Handle._call`, `_check`).
 """
 import ctypes as C
 
@@ -58,13 +61,18 @@ class AGBNPForce:
         self._version = 1
         self._solvent_radius = 1.0 * float(np.float32(0.1))  # SOLVENT_RADIUS (1.0*ANG)
         self._force_group = 0
+        self._cache = None  # the arrays of _arrays()
 
     def getNumParticles(self):
         return len(self._particles)
 
+    @staticmethod
+    def _row(radius, gamma, vdw_alpha, charge, ishydrogen):
+        return [_strip_units(radius), _strip_units(gamma), _strip_units(vdw_alpha), _strip_units(charge), bool(ishydrogen)]
+
     def addParticle(self, radius, gamma, vdw_alpha, charge, ishydrogen):
         """radius nm, gamma kJ/mol/nm^2, vdw_alpha kJ/mol nm^3... (as the reference), charge e. Returns the index."""
-        self._particles.append([_strip_units(radius), _strip_units(gamma), _strip_units(vdw_alpha), _strip_units(charge), bool(ishydrogen)])
+        self._particles.append(self._row(radius, gamma, vdw_alpha, charge, ishydrogen))
         self._cache = None
         return len(self._particles) - 1
 
@@ -74,9 +82,8 @@ class AGBNPForce:
 
     def setParticleParameters(self, index, radius, gamma, vdw_alpha, charge, ishydrogen):
         self._check_index(index)
-        row = [_strip_units(radius), _strip_units(gamma), _strip_units(vdw_alpha), _strip_units(charge), bool(ishydrogen)]
-        self._particles[index] = row
-        cache = getattr(self, "_cache", None)
+        row = self._particles[index] = self._row(radius, gamma, vdw_alpha, charge, ishydrogen)
+        cache = self._cache
         if cache is not None:  # the arrays that cross the boundary follow in place (updateParametersInContext after a sweep of these)
             for k in range(4):
                 cache[k][index] = row[k]
@@ -123,7 +130,7 @@ class AGBNPForce:
     # helpers for the engine boundary
     def _arrays(self):
         """The five parameter arrays as they cross the C ABI (built once, then kept up to date by setParticleParameters)."""
-        cache = getattr(self, "_cache", None)
+        cache = self._cache
         if cache is None:
             p = self._particles
             f = lambda k: np.ascontiguousarray([x[k] for x in p], dtype=np.float64)
@@ -139,6 +146,7 @@ class AGBNPForce:
         return force
 
 
+# ---- what crosses the C ABI -------------------------------------------------------------------------------------------------
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -147,8 +155,85 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
-class HipCalcAGBNPForceKernel:
+def _ptr(p):
+    """A raw pointer -- a device pointer, a stream -- given as an int; None and 0 are NULL."""
+    return C.c_void_p(p or 0)
+
+
+def _parameters(force):
+    """The count and the five parameter arrays of a force, as the create and update calls take them."""
+    r, g, a, q, h = force._arrays()
+    return len(r), _dp(r), _dp(g), _dp(a), _dp(q), _ip(h)
+
+
+def _forces_array(forces, n, refusal):
+    if not (isinstance(forces, np.ndarray) and forces.dtype == np.float64 and forces.flags.c_contiguous and forces.size == 3 * n):
+        raise OpenMMException(refusal)
+
+
+def _check(rc, error_handle=None):
+    """A return code of the library: a failure raises with the message the library keeps for `error_handle` (None: the message
+    of the calls that are not made on a context)."""
+    if rc != _lib.OK:
+        raise OpenMMException(_lib.last_error(error_handle))
+
+
+class _Handle:
+    """What HipCalcAGBNPForceKernel and BindingEnergy share: a library handle `_h` (None: there is none), the calls on it, the
+    log of withheld evaluations, the positions check and the release.  The symbols that differ are class data."""
+    _NEED = _WITHHELD = _DESTROY = None
+    _OWN_ERRORS = True  # the library keeps the messages of this handle's calls under the handle (else: under None)
+    _h = None
+
+    def _need(self):
+        if self._h is None:
+            raise OpenMMException(self._NEED)
+
+    def _library(self):
+        """For the calls whose result is not a return code."""
+        self._need()
+        return _lib.load()
+
+    def _call(self, symbol, *args):
+        """The one way of a method into the library: the handle is needed, `symbol` of _lib.load() is looked up now, after the
+        caller's argument checks, and called on the handle; a failure raises with the library's message for this class."""
+        if self._h is None:  # (_need() without its frame: every evaluation comes through here)
+            raise OpenMMException(self._NEED)
+        _check(getattr(_lib.load(), symbol)(self._h, *args), self._h if self._OWN_ERRORS else None)
+
+    def _positions(self, positions, who):
+        self._need()
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
+        if pos.size != 3 * self.numParticles:
+            raise OpenMMException(f"{who}(): wrong number of positions")
+        return pos
+
+    def withheld(self):
+        """Indices (enqueue order since the finish() before the last one) of the evaluations -- of a BindingEnergy: the binding
+        evaluations -- the last finish() reported as withheld."""
+        count = getattr(self._library(), self._WITHHELD)
+        n = count(self._h, None, 0)
+        idx = np.full(max(n, 1), -1, dtype=np.int32)  # the library fills as many indices as its log holds (it only COUNTS beyond bit 2047)
+        count(self._h, _ip(idx), n)
+        return [int(k) for k in idx if k >= 0]
+
+    def release(self):
+        if self._h is not None:
+            getattr(_lib.load(), self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class HipCalcAGBNPForceKernel(_Handle):
     """The 'HIP platform' implementation of CalcAGBNPForceKernel."""
+    _NEED = "HipCalcAGBNPForceKernel: initialize() has not been called"
+    _WITHHELD, _DESTROY = "agbnp_hip_withheld_evaluations", "agbnp_hip_destroy"
+    _GROUP = ("group", "members", _lib.MAX_GROUP, False)  # what a group of these is called, its bound, members distinct
 
     @staticmethod
     def Name():
@@ -165,44 +250,29 @@ class HipCalcAGBNPForceKernel:
         self.numParticles = 0
 
     def initialize(self, force):
-        lib = _lib.load()
         self.release()
-        r, g, a, q, h = force._arrays()
-        self.numParticles = len(r)
+        parameters = _parameters(force)
+        self.numParticles = parameters[0]
         handle = C.c_void_p()
-        rc = lib.agbnp_hip_create(C.byref(handle), len(r), _dp(r), _dp(g), _dp(a), _dp(q), _ip(h), force.getVersion(),
-                                  force.getNonbondedMethod(), force.getCutoffDistance(), self._device)
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(None))
+        _check(_lib.load().agbnp_hip_create(C.byref(handle), *parameters, force.getVersion(), force.getNonbondedMethod(),
+                                            force.getCutoffDistance(), self._device))
         self._h = handle
-        if self._mode and lib.agbnp_hip_set_mode(self._h, self._mode) != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        if self._mode:
+            self._call("agbnp_hip_set_mode", self._mode)
 
     def set_mode(self, mode):
         self._need()
         self._mode = self.MODES[mode]
-        if _lib.load().agbnp_hip_set_mode(self._h, self._mode) != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
-
-    def _need(self):
-        if self._h is None:
-            raise OpenMMException("HipCalcAGBNPForceKernel: initialize() has not been called")
+        self._call("agbnp_hip_set_mode", self._mode)
 
     def execute(self, positions, forces, includeForces=True, includeEnergy=True):
         """CPU-platform convention of the reference: forces (N x 3 float64 array) are accumulated in place,
         the energy is returned.  includeForces/includeEnergy are accepted and ignored, as in the reference
         (ReferenceAGBNPKernels.cpp:139-149 always computes both)."""
-        self._need()
-        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
-        if pos.size != 3 * self.numParticles:
-            raise OpenMMException("execute(): wrong number of positions")
-        if not (isinstance(forces, np.ndarray) and forces.dtype == np.float64 and forces.flags.c_contiguous
-                and forces.size == 3 * self.numParticles):
-            raise OpenMMException("execute(): forces must be a C-contiguous float64 array of 3N values")
+        pos = self._positions(positions, "execute")
+        _forces_array(forces, self.numParticles, "execute(): forces must be a C-contiguous float64 array of 3N values")
         e = C.c_double(0.0)
-        rc = _lib.load().agbnp_hip_execute_host(self._h, _dp(pos), _dp(forces), C.byref(e))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_execute_host", _dp(pos), _dp(forces), C.byref(e))
         return e.value
 
     def execute_device(self, d_positions, d_forces, d_energy, stream=None):
@@ -215,72 +285,47 @@ class HipCalcAGBNPForceKernel:
         other) cost one withheld evaluation: finish() reports it, withheld() names it, running it again is right (execute(), the
         host-buffer entry point, repeats by itself).  MD steps are two orders of magnitude below that;
         AGBNP_HIP_FIVE_LAUNCHES=0 lifts the restriction for the price of one more launch per evaluation."""
-        self._need()
-        rc = _lib.load().agbnp_hip_execute_device(self._h, C.c_void_p(d_positions), C.c_void_p(d_forces), C.c_void_p(d_energy),
-                                                  C.c_void_p(stream or 0))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_execute_device", C.c_void_p(d_positions), C.c_void_p(d_forces), C.c_void_p(d_energy), _ptr(stream))
 
     def execute_openmm(self, d_posq, posq_is_double, d_posq_correction, d_atom_index, padded_num_atoms, d_force_buffer,
                        d_energy_buffer, energy_is_double, energy_slot=0, stream=None):
         """The data conventions of an OpenMM GPU context (reference OpenCL platform): posq real4 in the context's
         atom order (+ optional float4 correction), atomIndex map, 2^32 fixed-point force planes, energy buffer slot.
         Raw device pointers (ints; 0 = NULL).  Asynchronous; call finish()."""
-        self._need()
-        rc = _lib.load().agbnp_hip_execute_openmm(self._h, C.c_void_p(d_posq), int(bool(posq_is_double)), C.c_void_p(d_posq_correction or 0),
-                                                  C.c_void_p(d_atom_index or 0), int(padded_num_atoms), C.c_void_p(d_force_buffer),
-                                                  C.c_void_p(d_energy_buffer or 0), int(bool(energy_is_double)), int(energy_slot),
-                                                  C.c_void_p(stream or 0))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_execute_openmm", C.c_void_p(d_posq), int(bool(posq_is_double)), _ptr(d_posq_correction), _ptr(d_atom_index),
+                   int(padded_num_atoms), C.c_void_p(d_force_buffer), _ptr(d_energy_buffer), int(bool(energy_is_double)),
+                   int(energy_slot), _ptr(stream))
 
     def energy(self, positions):
         """Energy-only evaluation (what OpenMM asks for with includeForces=false): the energy execute() would return at
         these positions, computed without the force passes where the context allows it (include/agbnp_hip.h).  No forces
         are written anywhere; withheld evaluations are repeated inside, like execute()."""
-        self._need()
-        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
-        if pos.size != 3 * self.numParticles:
-            raise OpenMMException("energy(): wrong number of positions")
+        pos = self._positions(positions, "energy")
         e = C.c_double(0.0)
-        rc = _lib.load().agbnp_hip_energy_host(self._h, _dp(pos), C.byref(e))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_energy_host", _dp(pos), C.byref(e))
         return e.value
 
     def energy_device(self, d_positions, d_energy, stream=None):
         """Energy-only form of execute_device(): the energy is ADDED to *d_energy on the device, nothing else is written.
         Asynchronous, counted in the same log as full evaluations (finish(), withheld(), poll(), wait_verdict()).  Refused
         (OpenMMException) inside a stream capture."""
-        self._need()
-        rc = _lib.load().agbnp_hip_energy_device(self._h, C.c_void_p(d_positions), C.c_void_p(d_energy), C.c_void_p(stream or 0))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_energy_device", C.c_void_p(d_positions), C.c_void_p(d_energy), _ptr(stream))
 
     def energy_openmm(self, d_posq, posq_is_double, d_posq_correction, d_atom_index, padded_num_atoms, d_energy_buffer,
                       energy_is_double, energy_slot=0, stream=None):
         """Energy-only form of execute_openmm(): no force buffer; the energy is ADDED to d_energy_buffer[energy_slot]."""
-        self._need()
-        rc = _lib.load().agbnp_hip_energy_openmm(self._h, C.c_void_p(d_posq), int(bool(posq_is_double)), C.c_void_p(d_posq_correction or 0),
-                                                 C.c_void_p(d_atom_index or 0), int(padded_num_atoms), C.c_void_p(d_energy_buffer),
-                                                 int(bool(energy_is_double)), int(energy_slot), C.c_void_p(stream or 0))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_energy_openmm", C.c_void_p(d_posq), int(bool(posq_is_double)), _ptr(d_posq_correction), _ptr(d_atom_index),
+                   int(padded_num_atoms), C.c_void_p(d_energy_buffer), int(bool(energy_is_double)), int(energy_slot), _ptr(stream))
 
     def decompose(self, positions):
         """Per-atom decomposition of the energy at these positions (include/agbnp_hip.h, agbnp_hip_decompose_host): returns
         (energy, terms) with terms a float64 array [4, N] in the order of DECOMPOSITION_TERMS -- cavity, vdW, GB self, GB pair
         (each pair shared half and half) -- whose sum over everything is the energy.  Version 0 has the cavity plane only.  No
         forces are written anywhere; withheld evaluations are repeated inside, like energy()."""
-        self._need()
-        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
-        if pos.size != 3 * self.numParticles:
-            raise OpenMMException("decompose(): wrong number of positions")
+        pos = self._positions(positions, "decompose")
         terms = np.zeros((len(DECOMPOSITION_TERMS), self.numParticles))
         e = C.c_double(0.0)
-        rc = _lib.load().agbnp_hip_decompose_host(self._h, _dp(pos), _dp(terms), C.byref(e))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_decompose_host", _dp(pos), _dp(terms), C.byref(e))
         return e.value, terms
 
     def decompose_device(self, d_positions, d_per_atom, d_energy=None, stream=None):
@@ -288,45 +333,33 @@ class HipCalcAGBNPForceKernel:
         order) and the total to *d_energy when it is given; raw FP64 device pointers (ints).  Asynchronous, counted in the same
         log as every other evaluation (finish(), withheld(), poll(), wait_verdict()); a withheld one adds nothing.  Refused
         (OpenMMException) inside a stream capture."""
-        self._need()
-        rc = _lib.load().agbnp_hip_decompose_device(self._h, C.c_void_p(d_positions), C.c_void_p(d_per_atom), C.c_void_p(d_energy or 0),
-                                                    C.c_void_p(stream or 0))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_decompose_device", C.c_void_p(d_positions), C.c_void_p(d_per_atom), _ptr(d_energy), _ptr(stream))
 
     def atom_order_changed(self):
         """The context has reordered its atoms (same atomIndex array, new contents): the next execute_openmm() rebuilds the
         engine's maps first instead of losing one evaluation to the check on the device."""
-        self._need()
-        _lib.load().agbnp_hip_atom_order_changed(self._h)
+        self._library().agbnp_hip_atom_order_changed(self._h)
 
     def expect_jump(self):
         """A hint: the positions of the NEXT evaluation are unrelated to the last ones (another replica's conformation, a
         restart).  That evaluation, through any entry point, lays the neighbour masks down at its own positions first -- one
         small launch, no synchronisation -- and is not withheld for the jump.  Consumed by that evaluation; does nothing where
         the context does not run the five-launch mode (include/agbnp_hip.h, agbnp_hip_expect_jump)."""
-        self._need()
-        rc = _lib.load().agbnp_hip_expect_jump(self._h)
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_expect_jump")
 
     def finish(self, stream=None):
         """Synchronise and read the device's overflow log: returns the number of evaluations enqueued since the
         previous finish() whose forces and energy were WITHHELD on the device (0 = all complete).  Those must be
         run again (see withheld()); the context has already switched to the packing / capacity variant they need."""
-        self._need()
         rep = C.c_int(0)
-        rc = _lib.load().agbnp_hip_finish(self._h, C.c_void_p(stream or 0), C.byref(rep))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_finish", _ptr(stream), C.byref(rep))
         return int(rep.value)
 
     def poll(self):
         """Non-blocking: (evaluations completed since the last finish(), how many of them were withheld), read from pinned
         host memory the device writes at the end of every evaluation (no device call)."""
-        self._need()
         done, bad = C.c_int(0), C.c_int(0)
-        if _lib.load().agbnp_hip_poll(self._h, C.byref(done), C.byref(bad)) != _lib.OK:
+        if self._library().agbnp_hip_poll(self._h, C.byref(done), C.byref(bad)) != _lib.OK:
             raise OpenMMException("agbnp_hip_poll: no pinned status memory")
         return int(done.value), int(bad.value)
 
@@ -335,37 +368,22 @@ class HipCalcAGBNPForceKernel:
         has delivered its verdict on every evaluation enqueued since the last finish() (or on `evaluations` of them) and
         returns (evaluations judged, how many were withheld).  The verdict of an evaluation is final when its tree stage
         has ended; its forces follow on the stream, gated on the device by the same words.  Raises on a timeout."""
-        self._need()
         done, bad = C.c_int(0), C.c_int(0)
-        rc = _lib.load().agbnp_hip_wait_verdict(self._h, int(evaluations), float(timeout), C.byref(done), C.byref(bad))
-        if rc == _lib.ERR_TIMEOUT:
+        verdict = self._library().agbnp_hip_wait_verdict(self._h, int(evaluations), float(timeout), C.byref(done), C.byref(bad))
+        if verdict == _lib.ERR_TIMEOUT:
             raise OpenMMException(f"agbnp_hip_wait_verdict: timed out after {timeout} s with {int(done.value)} evaluation(s) judged")
-        if rc != _lib.OK:
+        if verdict != _lib.OK:
             raise OpenMMException("agbnp_hip_wait_verdict: no pinned status memory")
         return int(done.value), int(bad.value)
-
-    def withheld(self):
-        """Indices (enqueue order since the finish() before the last one) of the evaluations the last finish()
-        reported as withheld."""
-        self._need()
-        lib = _lib.load()
-        n = lib.agbnp_hip_withheld_evaluations(self._h, None, 0)
-        idx = np.full(max(n, 1), -1, dtype=np.int32)  # the library fills as many indices as its log holds (it only COUNTS beyond bit 2047)
-        lib.agbnp_hip_withheld_evaluations(self._h, _ip(idx), n)
-        return [int(k) for k in idx if k >= 0]
 
     def generation(self):
         """Changes when a captured HIP graph of this context has gone stale (capacity variant raised; an evaluation through the
         other device-resident entry point than the graph's: include/agbnp_hip.h)."""
-        self._need()
-        return int(_lib.load().agbnp_hip_generation(self._h))
+        return int(self._library().agbnp_hip_generation(self._h))
 
     def copyParametersToContext(self, force):
         self._need()
-        r, g, a, q, h = force._arrays()
-        rc = _lib.load().agbnp_hip_update_parameters(self._h, len(r), _dp(r), _dp(g), _dp(a), _dp(q), _ip(h))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_update_parameters", *_parameters(force))
 
     # ---- diagnostics (test support) -------------------------------------------------------------
     SCALARS = dict(e_vol1=0, e_vol2=1, e_atom=2, e_gb_pair=3, max_subtree_nodes=4, total_nodes=5, variant=6, max_local_atoms=7, forests=8, rows_on=9, row_builds=10, pack_level=11, pack_age=12, row_slice=13, pack_plans=14, overflow_kinds=15, launches=16, healed_forests=17, energy_only_launches=18, group_members=19, last_evaluation_kind=20, group_block_writes=21)
@@ -374,22 +392,17 @@ class HipCalcAGBNPForceKernel:
     def scalar(self, name):
         self._need()
         v = C.c_double(0)
-        rc = _lib.load().agbnp_hip_get_scalar(self._h, self.SCALARS[name], C.byref(v))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_get_scalar", self.SCALARS[name], C.byref(v))
         return v.value
 
     def vector(self, name):
         self._need()
         out = np.zeros(self.numParticles)
-        rc = _lib.load().agbnp_hip_get_vector(self._h, self.VECTORS[name], _dp(out))
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(self._h))
+        self._call("agbnp_hip_get_vector", self.VECTORS[name], _dp(out))
         return out
 
     def tables(self):
-        self._need()
-        lib = _lib.load()
+        lib = self._library()
         ni, nj = C.c_int(0), C.c_int(0)
         lib.agbnp_hip_get_table_sizes(self._h, C.byref(ni), C.byref(nj))
         y = np.zeros(ni.value * nj.value * 16)
@@ -401,123 +414,19 @@ class HipCalcAGBNPForceKernel:
 
     def set_diagnostics(self, enabled):
         """Collect the pass-1 (enlarged radii) self volumes too (vector 'selfvol_large')."""
-        self._need()
-        _lib.load().agbnp_hip_set_diagnostics(self._h, 1 if enabled else 0)
+        self._library().agbnp_hip_set_diagnostics(self._h, 1 if enabled else 0)
 
     def set_profiling(self, enabled):
-        self._need()
-        _lib.load().agbnp_hip_set_profiling(self._h, 1 if enabled else 0)
+        self._library().agbnp_hip_set_profiling(self._h, 1 if enabled else 0)
 
     def kernel_times(self):
         """{kernel name: (total ms, launches)} accumulated since set_profiling(True)."""
-        self._need()
-        lib = _lib.load()
+        lib = self._library()
         k = lib.agbnp_hip_num_kernels()
         ms = np.zeros(k)
         cnt = np.zeros(k, dtype=np.int64)
         lib.agbnp_hip_get_kernel_times(self._h, _dp(ms), cnt.ctypes.data_as(C.POINTER(C.c_long)))
         return {lib.agbnp_hip_kernel_name(i).decode(): (float(ms[i]), int(cnt[i])) for i in range(k)}
-
-    def release(self):
-        if self._h is not None:
-            _lib.load().agbnp_hip_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-
-def _group_handles(kernels, who):
-    kernels = list(kernels)
-    if not 1 <= len(kernels) <= _lib.MAX_GROUP:
-        raise OpenMMException(f"{who}(): a group has 1 to {_lib.MAX_GROUP} members, not {len(kernels)}")
-    for k in kernels:
-        if not isinstance(k, HipCalcAGBNPForceKernel):
-            raise OpenMMException(f"{who}(): members must be HipCalcAGBNPForceKernel objects")
-        k._need()
-    return kernels, (C.c_void_p * len(kernels))(*[k._h for k in kernels])
-
-
-def execute_group(kernels, d_positions, d_forces, d_energies, stream=None):
-    """Replica groups (include/agbnp_hip.h, agbnp_hip_execute_group): one call that enqueues an evaluation of every kernel in
-    `kernels`, with the launches of the members that can share them made once for all of them.  d_positions, d_forces,
-    d_energies: lists of raw FP64 device pointers (ints), one per member; forces and energies are ADDED, as by each member's
-    execute_device().  Asynchronous; each member's finish() reports its own withheld evaluations."""
-    kernels, hs = _group_handles(kernels, "execute_group")
-    n = len(kernels)
-    for name, ptrs in (("d_positions", d_positions), ("d_forces", d_forces), ("d_energies", d_energies)):
-        if len(ptrs) != n:
-            raise OpenMMException(f"execute_group(): {name} has {len(ptrs)} entries for {n} members")
-    arr = lambda ptrs: (C.c_void_p * n)(*[int(p or 0) for p in ptrs])  # noqa: E731
-    rc = _lib.load().agbnp_hip_execute_group(hs, n, arr(d_positions), arr(d_forces), arr(d_energies), C.c_void_p(stream or 0))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(kernels[0]._h))
-
-
-def execute_group_host(kernels, positions, forces):
-    """Synchronous twin of execute_group() for host buffers: positions[i] (N_i x 3) are read, forces[i] (C-contiguous float64
-    arrays of 3 N_i values) are accumulated in place, the members' energies are returned as a list.  Withheld members are
-    repeated inside."""
-    kernels, hs = _group_handles(kernels, "execute_group_host")
-    n = len(kernels)
-    if len(positions) != n or len(forces) != n:
-        raise OpenMMException(f"execute_group_host(): {len(positions)} positions and {len(forces)} force arrays for {n} members")
-    pos = []
-    for k, p, f in zip(kernels, positions, forces):
-        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
-        if p.size != 3 * k.numParticles:
-            raise OpenMMException("execute_group_host(): wrong number of positions")
-        if not (isinstance(f, np.ndarray) and f.dtype == np.float64 and f.flags.c_contiguous and f.size == 3 * k.numParticles):
-            raise OpenMMException("execute_group_host(): forces must be C-contiguous float64 arrays of 3N values")
-        pos.append(p)
-    dpp = C.POINTER(C.c_double)
-    energies = np.zeros(n)
-    rc = _lib.load().agbnp_hip_execute_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), (dpp * n)(*[_dp(f) for f in forces]),
-                                                  _dp(energies))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(kernels[0]._h))
-    return [float(e) for e in energies]
-
-
-def energy_group(kernels, d_positions, d_energies, stream=None):
-    """Energy-only replica groups (include/agbnp_hip.h, agbnp_hip_energy_group): one call that enqueues an energy-only
-    evaluation of every kernel in `kernels`, with the launches of the members that can share them made once for all of them.
-    d_positions, d_energies: lists of raw FP64 device pointers (ints), one per member; position buffers may be shared between
-    members, the energy words must be distinct.  The energies are ADDED, as by each member's energy_device(); no force is
-    written.  Asynchronous; each member's finish() reports its own withheld evaluations."""
-    kernels, hs = _group_handles(kernels, "energy_group")
-    n = len(kernels)
-    for name, ptrs in (("d_positions", d_positions), ("d_energies", d_energies)):
-        if len(ptrs) != n:
-            raise OpenMMException(f"energy_group(): {name} has {len(ptrs)} entries for {n} members")
-    arr = lambda ptrs: (C.c_void_p * n)(*[int(p or 0) for p in ptrs])  # noqa: E731
-    rc = _lib.load().agbnp_hip_energy_group(hs, n, arr(d_positions), arr(d_energies), C.c_void_p(stream or 0))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(kernels[0]._h))
-
-
-def energy_group_host(kernels, positions):
-    """Synchronous twin of energy_group() for host buffers: positions[i] (N_i x 3) are read, the members' energies are
-    returned as a list.  Withheld members are repeated inside."""
-    kernels, hs = _group_handles(kernels, "energy_group_host")
-    n = len(kernels)
-    if len(positions) != n:
-        raise OpenMMException(f"energy_group_host(): {len(positions)} positions for {n} members")
-    pos = []
-    for k, p in zip(kernels, positions):
-        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
-        if p.size != 3 * k.numParticles:
-            raise OpenMMException("energy_group_host(): wrong number of positions")
-        pos.append(p)
-    dpp = C.POINTER(C.c_double)
-    energies = np.zeros(n)
-    rc = _lib.load().agbnp_hip_energy_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), _dp(energies))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(kernels[0]._h))
-    return [float(e) for e in energies]
 
 
 def _ligand_indices(ligand_atoms, n):
@@ -535,7 +444,7 @@ def _ligand_indices(ligand_atoms, n):
     return np.ascontiguousarray(sorted(given), dtype=np.int32)
 
 
-class BindingEnergy:
+class BindingEnergy(_Handle):
     """Binding-energy evaluations (include/agbnp_hip.h, agbnp_hip_binding_*): the complex, its receptor and its ligand in one
     call.  `force` holds the particles of the complex, `ligand_atoms` the ligand's atom indices (1 to N - 1 distinct ones, any
     order); the rest is the receptor, both in ascending complex order.  With E_RL, E_R, E_L the energies of the three systems at
@@ -546,19 +455,19 @@ class BindingEnergy:
     A binding evaluation reaches the caller's buffers only if all three members' evaluations completed (decided on the device);
     finish() and withheld() report the binding evaluations that are missing.  Do not evaluate or finish a member() directly
     between two finish() calls."""
+    _NEED = "BindingEnergy: the binding has been released"
+    _WITHHELD, _DESTROY = "agbnp_hip_binding_withheld_evaluations", "agbnp_hip_binding_destroy"
+    _OWN_ERRORS = False
+    _GROUP = ("binding group", "bindings", _lib.MAX_BINDING_GROUP, True)
 
     def __init__(self, force, ligand_atoms, device=0, mode="reference"):
         self._h = None
         n = force.getNumParticles()
         lig = _ligand_indices(ligand_atoms, n)  # (before the library is touched)
         mode_bits = HipCalcAGBNPForceKernel.MODES[mode]
-        lib = _lib.load()
-        r, g, a, q, h = force._arrays()
         handle = C.c_void_p()
-        rc = lib.agbnp_hip_binding_create(C.byref(handle), n, _dp(r), _dp(g), _dp(a), _dp(q), _ip(h), _ip(lig), len(lig),
-                                          force.getVersion(), force.getNonbondedMethod(), force.getCutoffDistance(), device)
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(None))
+        _check(_lib.load().agbnp_hip_binding_create(C.byref(handle), *_parameters(force), _ip(lig), len(lig), force.getVersion(),
+                                                    force.getNonbondedMethod(), force.getCutoffDistance(), device))
         self._h = handle
         self._device = device
         self.numParticles = n
@@ -577,83 +486,52 @@ class BindingEnergy:
     def receptor_atoms(self):
         return self._receptor.copy()
 
-    def _need(self):
-        if self._h is None:
-            raise OpenMMException("BindingEnergy: the binding has been released")
-
-    def _check(self, rc):
-        if rc != _lib.OK:
-            raise OpenMMException(_lib.last_error(None))
-
-    def _positions(self, positions, who):
-        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
-        if pos.size != 3 * self.numParticles:
-            raise OpenMMException(f"{who}(): wrong number of positions")
-        return pos
-
     def execute(self, positions, lam):
         """(E_lam, u, forces[N, 3]) at the complex's positions (N x 3, nm).  Withheld evaluations are repeated inside."""
-        self._need()
         pos = self._positions(positions, "execute")
         forces = np.zeros((self.numParticles, 3))
         e, u = C.c_double(0.0), C.c_double(0.0)
-        self._check(_lib.load().agbnp_hip_binding_execute_host(self._h, _dp(pos), float(lam), _dp(forces), C.byref(e), C.byref(u)))
+        self._call("agbnp_hip_binding_execute_host", _dp(pos), float(lam), _dp(forces), C.byref(e), C.byref(u))
         return e.value, u.value, forces
 
     def energy(self, positions, lam):
         """(E_lam, u) without forces: three energy-only evaluations.  Withheld evaluations are repeated inside."""
-        self._need()
         pos = self._positions(positions, "energy")
         e, u = C.c_double(0.0), C.c_double(0.0)
-        self._check(_lib.load().agbnp_hip_binding_energy_host(self._h, _dp(pos), float(lam), C.byref(e), C.byref(u)))
+        self._call("agbnp_hip_binding_energy_host", _dp(pos), float(lam), C.byref(e), C.byref(u))
         return e.value, u.value
 
     def execute_device(self, d_positions, lam, d_forces, d_energy=None, d_binding_energy=None, stream=None):
         """Raw FP64 device pointers (ints): F_lam is ADDED to d_forces[3N], E_lam to *d_energy, u to *d_binding_energy (either
         may be None) -- all of it or, if any member's evaluation is withheld, nothing.  Asynchronous; call finish()."""
-        self._need()
-        self._check(_lib.load().agbnp_hip_binding_execute_device(self._h, C.c_void_p(d_positions), float(lam), C.c_void_p(d_forces),
-                                                                 C.c_void_p(d_energy or 0), C.c_void_p(d_binding_energy or 0),
-                                                                 C.c_void_p(stream or 0)))
+        self._call("agbnp_hip_binding_execute_device", C.c_void_p(d_positions), float(lam), C.c_void_p(d_forces), _ptr(d_energy),
+                   _ptr(d_binding_energy), _ptr(stream))
 
     def energy_device(self, d_positions, lam, d_energy=None, d_binding_energy=None, stream=None):
         """Energy-only form of execute_device(): no force buffer is written; d_energy and d_binding_energy not both None."""
-        self._need()
-        self._check(_lib.load().agbnp_hip_binding_energy_device(self._h, C.c_void_p(d_positions), float(lam), C.c_void_p(d_energy or 0),
-                                                                C.c_void_p(d_binding_energy or 0), C.c_void_p(stream or 0)))
+        self._call("agbnp_hip_binding_energy_device", C.c_void_p(d_positions), float(lam), _ptr(d_energy), _ptr(d_binding_energy),
+                   _ptr(stream))
 
     def finish(self, stream=None):
         """Drains the stream, finishes the three members and returns the number of binding evaluations since the previous
         finish() with at least one withheld member: NOTHING of those reached the caller's buffers; run them again (withheld())."""
-        self._need()
         rep = C.c_int(0)
-        self._check(_lib.load().agbnp_hip_binding_finish(self._h, C.c_void_p(stream or 0), C.byref(rep)))
+        self._call("agbnp_hip_binding_finish", _ptr(stream), C.byref(rep))
         return int(rep.value)
-
-    def withheld(self):
-        """Indices (enqueue order since the finish() before the last one) of the binding evaluations the last finish() reported."""
-        self._need()
-        lib = _lib.load()
-        n = lib.agbnp_hip_binding_withheld_evaluations(self._h, None, 0)
-        idx = np.full(max(n, 1), -1, dtype=np.int32)
-        lib.agbnp_hip_binding_withheld_evaluations(self._h, _ip(idx), n)
-        return [int(k) for k in idx if k >= 0]
 
     def expect_jump(self):
         """The next evaluation's positions are unrelated to the last ones: forwarded to all three members."""
-        self._need()
-        self._check(_lib.load().agbnp_hip_binding_expect_jump(self._h))
+        self._call("agbnp_hip_binding_expect_jump")
 
     def set_mode(self, mode):
         self._need()
         self._mode = HipCalcAGBNPForceKernel.MODES[mode]
-        self._check(_lib.load().agbnp_hip_binding_set_mode(self._h, self._mode))
+        self._call("agbnp_hip_binding_set_mode", self._mode)
 
     def copyParametersToContext(self, force):
         """`force` holds the parameters of the COMPLEX; every member gets its subset."""
         self._need()
-        r, g, a, q, h = force._arrays()
-        self._check(_lib.load().agbnp_hip_binding_update_parameters(self._h, len(r), _dp(r), _dp(g), _dp(a), _dp(q), _ip(h)))
+        self._call("agbnp_hip_binding_update_parameters", *_parameters(force))
 
     def member(self, which):
         """A HipCalcAGBNPForceKernel view of a member -- 0 or "complex", 1 or "receptor", 2 or "ligand" -- for scalar(), vector(),
@@ -668,125 +546,6 @@ class BindingEnergy:
         view.numParticles = (self.numParticles, len(self._receptor), len(self._ligand))[which]
         return view
 
-    def release(self):
-        if self._h is not None:
-            _lib.load().agbnp_hip_binding_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-
-def _binding_handles(bindings, who):
-    bindings = list(bindings)
-    if not 1 <= len(bindings) <= _lib.MAX_BINDING_GROUP:
-        raise OpenMMException(f"{who}(): a binding group has 1 to {_lib.MAX_BINDING_GROUP} bindings, not {len(bindings)}")
-    for b in bindings:
-        if not isinstance(b, BindingEnergy):
-            raise OpenMMException(f"{who}(): members must be BindingEnergy objects")
-        b._need()
-    if len({id(b) for b in bindings}) != len(bindings):
-        raise OpenMMException(f"{who}(): the same binding twice")
-    return bindings, (C.c_void_p * len(bindings))(*[b._h for b in bindings])
-
-
-def _binding_pointers(who, n, **lists):
-    """ctypes arrays of device pointers, one entry per binding; None for a list that is None (every entry NULL)."""
-    out = []
-    for name, ptrs in lists.items():
-        if ptrs is None:
-            out.append(None)
-            continue
-        if len(ptrs) != n:
-            raise OpenMMException(f"{who}(): {name} has {len(ptrs)} entries for {n} bindings")
-        out.append((C.c_void_p * n)(*[int(p or 0) for p in ptrs]))
-    return out
-
-
-def _host_lambdas(who, lambdas, n):
-    lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
-    if lam.size != n:
-        raise OpenMMException(f"{who}(): {lam.size} lambdas for {n} bindings")
-    if not np.isfinite(lam).all():
-        raise OpenMMException(f"{who}(): lambda must be finite")
-    return lam
-
-
-def binding_execute_group(bindings, d_positions, d_lambdas, d_forces, d_energies=None, d_binding_energies=None, stream=None):
-    """Binding groups (include/agbnp_hip.h, agbnp_hip_binding_execute_group): one call that enqueues an evaluation of every
-    BindingEnergy in `bindings` -- one gather launch, the members' evaluations as replica groups, one combine launch.
-    d_positions, d_forces, d_energies, d_binding_energies: lists of raw FP64 device pointers (ints), one per binding; entries of
-    the last two may be None, and so may the lists.  d_lambdas: ONE raw device pointer to len(bindings) doubles, read by the
-    combine launch when it runs -- a kernel enqueued earlier on the stream may have written them.  F_lam, E_lam and u are ADDED,
-    per binding all or nothing.  Asynchronous; each binding's finish() reports its own withheld evaluations."""
-    who = "binding_execute_group"
-    bindings, hs = _binding_handles(bindings, who)
-    n = len(bindings)
-    pos, frc, ene, u = _binding_pointers(who, n, d_positions=d_positions, d_forces=d_forces, d_energies=d_energies,
-                                         d_binding_energies=d_binding_energies)
-    if pos is None or frc is None or not d_lambdas:
-        raise OpenMMException(f"{who}(): d_positions, d_forces and d_lambdas are needed")
-    rc = _lib.load().agbnp_hip_binding_execute_group(hs, n, pos, C.c_void_p(d_lambdas), frc, ene, u, C.c_void_p(stream or 0))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(None))
-
-
-def binding_energy_group(bindings, d_positions, d_lambdas, d_energies=None, d_binding_energies=None, stream=None):
-    """Energy-only form of binding_execute_group() (agbnp_hip_binding_energy_group): no force buffer is written; of a binding's
-    two scalar pointers at least one is given, and they are different words."""
-    who = "binding_energy_group"
-    bindings, hs = _binding_handles(bindings, who)
-    n = len(bindings)
-    pos, ene, u = _binding_pointers(who, n, d_positions=d_positions, d_energies=d_energies, d_binding_energies=d_binding_energies)
-    if pos is None or not d_lambdas:
-        raise OpenMMException(f"{who}(): d_positions and d_lambdas are needed")
-    rc = _lib.load().agbnp_hip_binding_energy_group(hs, n, pos, C.c_void_p(d_lambdas), ene, u, C.c_void_p(stream or 0))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(None))
-
-
-def binding_execute_group_host(bindings, positions, lambdas, forces):
-    """Synchronous twin of binding_execute_group() for host buffers: positions[k] (N_k x 3) are read, forces[k] (C-contiguous
-    float64 arrays of 3 N_k values) are accumulated in place; returns the lists (E_lam, u).  A binding whose evaluation was
-    withheld is repeated inside."""
-    who = "binding_execute_group_host"
-    bindings, hs = _binding_handles(bindings, who)
-    n = len(bindings)
-    if len(positions) != n or len(forces) != n:
-        raise OpenMMException(f"{who}(): {len(positions)} positions and {len(forces)} force arrays for {n} bindings")
-    lam = _host_lambdas(who, lambdas, n)
-    pos = [b._positions(p, who) for b, p in zip(bindings, positions)]
-    for b, f in zip(bindings, forces):
-        if not (isinstance(f, np.ndarray) and f.dtype == np.float64 and f.flags.c_contiguous and f.size == 3 * b.numParticles):
-            raise OpenMMException(f"{who}(): forces must be C-contiguous float64 arrays of 3N values")
-    dpp = C.POINTER(C.c_double)
-    e, u = np.zeros(n), np.zeros(n)
-    rc = _lib.load().agbnp_hip_binding_execute_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), _dp(lam),
-                                                          (dpp * n)(*[_dp(f) for f in forces]), _dp(e), _dp(u))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(None))
-    return [float(x) for x in e], [float(x) for x in u]
-
-
-def binding_energy_group_host(bindings, positions, lambdas):
-    """Synchronous twin of binding_energy_group() for host buffers: returns the lists (E_lam, u)."""
-    who = "binding_energy_group_host"
-    bindings, hs = _binding_handles(bindings, who)
-    n = len(bindings)
-    if len(positions) != n:
-        raise OpenMMException(f"{who}(): {len(positions)} positions for {n} bindings")
-    lam = _host_lambdas(who, lambdas, n)
-    pos = [b._positions(p, who) for b, p in zip(bindings, positions)]
-    dpp = C.POINTER(C.c_double)
-    e, u = np.zeros(n), np.zeros(n)
-    rc = _lib.load().agbnp_hip_binding_energy_group_host(hs, n, (dpp * n)(*[_dp(p) for p in pos]), _dp(lam), _dp(e), _dp(u))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(None))
-    return [float(x) for x in e], [float(x) for x in u]
-
 
 class _MemberView(HipCalcAGBNPForceKernel):
     """A member of a BindingEnergy: the binding owns the handle."""
@@ -798,9 +557,156 @@ class _MemberView(HipCalcAGBNPForceKernel):
         self._h = None
 
 
+# ---- groups: replica groups of kernels, binding groups of bindings --------------------------------------------------------------
+# Each of the eight entry points is: the members, checked; what crosses the C ABI, marshalled; one call; the result.
+def _members(who, members, cls):
+    """The members of a group call as a list, checked: their number, their class, each with a handle, distinct where the
+    library demands it (cls._GROUP)."""
+    members = list(members)
+    kind, noun, bound, distinct = cls._GROUP
+    if not 1 <= len(members) <= bound:
+        raise OpenMMException(f"{who}(): a {kind} has 1 to {bound} {noun}, not {len(members)}")
+    for m in members:
+        if not isinstance(m, cls):
+            raise OpenMMException(f"{who}(): members must be {cls.__name__} objects")
+        m._need()
+    if distinct and len({id(m) for m in members}) != len(members):
+        raise OpenMMException(f"{who}(): the same binding twice")
+    return members
+
+
+def _pointer_arrays(who, members, optional=False, **lists):
+    """The members' handles, then every list of device pointers (ints; None and 0 are NULL), as the ctypes arrays that cross
+    the C ABI, one entry per member.  `optional`: a list that is None stays None (every entry NULL)."""
+    n = len(members)
+    array = C.c_void_p * n
+    out = [array(*[m._h for m in members])]
+    for name, ptrs in lists.items():
+        if ptrs is None and optional:
+            out.append(None)
+        elif len(ptrs) != n:
+            raise OpenMMException(f"{who}(): {name} has {len(ptrs)} entries for {n} {members[0]._GROUP[1]}")
+        else:
+            out.append(array(*[int(p or 0) for p in ptrs]))
+    return out
+
+
+def _host_arrays(who, members, positions, forces=None, lambdas=None):
+    """The host side of a group call, checked: (handles, positions, forces, lambdas).  positions[i] is converted, forces[i]
+    must be writable as it is; both cross as arrays of pointers, one per member.  lambdas cross as one float64 array.  What
+    is not given comes back as None."""
+    n, noun = len(members), members[0]._GROUP[1]
+    if forces is None and len(positions) != n:
+        raise OpenMMException(f"{who}(): {len(positions)} positions for {n} {noun}")
+    if forces is not None and (len(positions) != n or len(forces) != n):
+        raise OpenMMException(f"{who}(): {len(positions)} positions and {len(forces)} force arrays for {n} {noun}")
+    if lambdas is not None:
+        lambdas = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
+        if lambdas.size != n:
+            raise OpenMMException(f"{who}(): {lambdas.size} lambdas for {n} {noun}")
+        if not np.isfinite(lambdas).all():
+            raise OpenMMException(f"{who}(): lambda must be finite")
+    pos = [m._positions(p, who) for m, p in zip(members, positions)]
+    for m, f in zip(members, () if forces is None else forces):
+        _forces_array(f, m.numParticles, f"{who}(): forces must be C-contiguous float64 arrays of 3N values")
+
+    def pointers(arrays):
+        out = (C.POINTER(C.c_double) * n)(*[_dp(a) for a in arrays])
+        out._arrays = arrays  # (a ctypes array does not keep alive what its entries point to: the converted positions)
+        return out
+    return _pointer_arrays(who, members)[0], pointers(pos), forces if forces is None else pointers(forces), lambdas
+
+
+def execute_group(kernels, d_positions, d_forces, d_energies, stream=None):
+    """Replica groups (include/agbnp_hip.h, agbnp_hip_execute_group): one call that enqueues an evaluation of every kernel in
+    `kernels`, with the launches of the members that can share them made once for all of them.  d_positions, d_forces,
+    d_energies: lists of raw FP64 device pointers (ints), one per member; forces and energies are ADDED, as by each member's
+    execute_device().  Asynchronous; each member's finish() reports its own withheld evaluations."""
+    kernels = _members("execute_group", kernels, HipCalcAGBNPForceKernel)
+    hs, pos, frc, ene = _pointer_arrays("execute_group", kernels, d_positions=d_positions, d_forces=d_forces, d_energies=d_energies)
+    _check(_lib.load().agbnp_hip_execute_group(hs, len(kernels), pos, frc, ene, _ptr(stream)), kernels[0]._h)
+
+
+def execute_group_host(kernels, positions, forces):
+    """Synchronous twin of execute_group() for host buffers: positions[i] (N_i x 3) are read, forces[i] (C-contiguous float64
+    arrays of 3 N_i values) are accumulated in place, the members' energies are returned as a list.  Withheld members are
+    repeated inside."""
+    kernels = _members("execute_group_host", kernels, HipCalcAGBNPForceKernel)
+    hs, pos, frc, _ = _host_arrays("execute_group_host", kernels, positions, forces)
+    energies = np.zeros(len(kernels))
+    _check(_lib.load().agbnp_hip_execute_group_host(hs, len(kernels), pos, frc, _dp(energies)), kernels[0]._h)
+    return [float(e) for e in energies]
+
+
+def energy_group(kernels, d_positions, d_energies, stream=None):
+    """Energy-only replica groups (include/agbnp_hip.h, agbnp_hip_energy_group): one call that enqueues an energy-only
+    evaluation of every kernel in `kernels`, with the launches of the members that can share them made once for all of them.
+    d_positions, d_energies: lists of raw FP64 device pointers (ints), one per member; position buffers may be shared between
+    members, the energy words must be distinct.  The energies are ADDED, as by each member's energy_device(); no force is
+    written.  Asynchronous; each member's finish() reports its own withheld evaluations."""
+    kernels = _members("energy_group", kernels, HipCalcAGBNPForceKernel)
+    hs, pos, ene = _pointer_arrays("energy_group", kernels, d_positions=d_positions, d_energies=d_energies)
+    _check(_lib.load().agbnp_hip_energy_group(hs, len(kernels), pos, ene, _ptr(stream)), kernels[0]._h)
+
+
+def energy_group_host(kernels, positions):
+    """Synchronous twin of energy_group() for host buffers: positions[i] (N_i x 3) are read, the members' energies are
+    returned as a list.  Withheld members are repeated inside."""
+    kernels = _members("energy_group_host", kernels, HipCalcAGBNPForceKernel)
+    hs, pos, _, _ = _host_arrays("energy_group_host", kernels, positions)
+    energies = np.zeros(len(kernels))
+    _check(_lib.load().agbnp_hip_energy_group_host(hs, len(kernels), pos, _dp(energies)), kernels[0]._h)
+    return [float(e) for e in energies]
+
+
+def binding_execute_group(bindings, d_positions, d_lambdas, d_forces, d_energies=None, d_binding_energies=None, stream=None):
+    """Binding groups (include/agbnp_hip.h, agbnp_hip_binding_execute_group): one call that enqueues an evaluation of every
+    BindingEnergy in `bindings` -- one gather launch, the members' evaluations as replica groups, one combine launch.
+    d_positions, d_forces, d_energies, d_binding_energies: lists of raw FP64 device pointers (ints), one per binding; entries of
+    the last two may be None, and so may the lists.  d_lambdas: ONE raw device pointer to len(bindings) doubles, read by the
+    combine launch when it runs -- a kernel enqueued earlier on the stream may have written them.  F_lam, E_lam and u are ADDED,
+    per binding all or nothing.  Asynchronous; each binding's finish() reports its own withheld evaluations."""
+    bindings = _members("binding_execute_group", bindings, BindingEnergy)
+    hs, pos, frc, ene, u = _pointer_arrays("binding_execute_group", bindings, True, d_positions=d_positions, d_forces=d_forces,
+                                           d_energies=d_energies, d_binding_energies=d_binding_energies)
+    if pos is None or frc is None or not d_lambdas:
+        raise OpenMMException("binding_execute_group(): d_positions, d_forces and d_lambdas are needed")
+    _check(_lib.load().agbnp_hip_binding_execute_group(hs, len(bindings), pos, C.c_void_p(d_lambdas), frc, ene, u, _ptr(stream)))
+
+
+def binding_energy_group(bindings, d_positions, d_lambdas, d_energies=None, d_binding_energies=None, stream=None):
+    """Energy-only form of binding_execute_group() (agbnp_hip_binding_energy_group): no force buffer is written; of a binding's
+    two scalar pointers at least one is given, and they are different words."""
+    bindings = _members("binding_energy_group", bindings, BindingEnergy)
+    hs, pos, ene, u = _pointer_arrays("binding_energy_group", bindings, True, d_positions=d_positions, d_energies=d_energies,
+                                      d_binding_energies=d_binding_energies)
+    if pos is None or not d_lambdas:
+        raise OpenMMException("binding_energy_group(): d_positions and d_lambdas are needed")
+    _check(_lib.load().agbnp_hip_binding_energy_group(hs, len(bindings), pos, C.c_void_p(d_lambdas), ene, u, _ptr(stream)))
+
+
+def binding_execute_group_host(bindings, positions, lambdas, forces):
+    """Synchronous twin of binding_execute_group() for host buffers: positions[k] (N_k x 3) are read, forces[k] (C-contiguous
+    float64 arrays of 3 N_k values) are accumulated in place; returns the lists (E_lam, u).  A binding whose evaluation was
+    withheld is repeated inside."""
+    bindings = _members("binding_execute_group_host", bindings, BindingEnergy)
+    hs, pos, frc, lam = _host_arrays("binding_execute_group_host", bindings, positions, forces, lambdas)
+    e, u = np.zeros(len(bindings)), np.zeros(len(bindings))
+    _check(_lib.load().agbnp_hip_binding_execute_group_host(hs, len(bindings), pos, _dp(lam), frc, _dp(e), _dp(u)))
+    return [float(x) for x in e], [float(x) for x in u]
+
+
+def binding_energy_group_host(bindings, positions, lambdas):
+    """Synchronous twin of binding_energy_group() for host buffers: returns the lists (E_lam, u)."""
+    bindings = _members("binding_energy_group_host", bindings, BindingEnergy)
+    hs, pos, _, lam = _host_arrays("binding_energy_group_host", bindings, positions, lambdas=lambdas)
+    e, u = np.zeros(len(bindings)), np.zeros(len(bindings))
+    _check(_lib.load().agbnp_hip_binding_energy_group_host(hs, len(bindings), pos, _dp(lam), _dp(e), _dp(u)))
+    return [float(x) for x in e], [float(x) for x in u]
+
+
 def host_tables(radius, ishydrogen):
     """I4 tables from the engine's host code (no device needed)."""
-    lib = _lib.load()
     r = np.ascontiguousarray(radius, dtype=np.float64)
     h = np.ascontiguousarray(ishydrogen, dtype=np.int32)
     n = len(r)
@@ -808,9 +714,7 @@ def host_tables(radius, ishydrogen):
     y, y2 = np.zeros(cap), np.zeros(cap)
     ti, tj = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
     ni, nj = C.c_int(0), C.c_int(0)
-    rc = lib.agbnp_hip_host_tables(n, _dp(r), _ip(h), C.byref(ni), C.byref(nj), _dp(y), _dp(y2), cap, _ip(ti), _ip(tj))
-    if rc != _lib.OK:
-        raise OpenMMException(_lib.last_error(None))
+    _check(_lib.load().agbnp_hip_host_tables(n, _dp(r), _ip(h), C.byref(ni), C.byref(nj), _dp(y), _dp(y2), cap, _ip(ti), _ip(tj)))
     k = ni.value * nj.value * 16
     return dict(y=y[:k].reshape(ni.value, nj.value, 16), y2=y2[:k].reshape(ni.value, nj.value, 16), type_screened=ti,
                 type_screener=tj)
@@ -832,13 +736,18 @@ class AGBNPContext:
     def setPositions(self, positions):
         self._positions = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
 
+    def _in_groups(self, groups):
+        """Whether the force-group mask includes this force (AGBNPForceImpl::calcForcesAndEnergy,
+        openmmapi/src/AGBNPForceImpl.cpp:32-36); positions must have been set."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        return (groups & (1 << self._force.getForceGroup())) != 0
+
     def getState(self, groups=-1):
         """Returns (potential energy, forces[N,3]).  Honours the force-group mask like
         AGBNPForceImpl::calcForcesAndEnergy (openmmapi/src/AGBNPForceImpl.cpp:32-36)."""
-        if self._positions is None:
-            raise OpenMMException("Particle positions have not been set")
         forces = np.zeros((self._kernel.numParticles, 3))
-        if (groups & (1 << self._force.getForceGroup())) == 0:
+        if not self._in_groups(groups):
             return 0.0, forces
         e = self._kernel.execute(self._positions, forces, True, True)
         return e, forces
@@ -846,18 +755,14 @@ class AGBNPContext:
     def getEnergy(self, groups=-1):
         """The potential energy alone (getState(getEnergy=True) without forces): an energy-only evaluation.  Honours the
         force-group mask like getState()."""
-        if self._positions is None:
-            raise OpenMMException("Particle positions have not been set")
-        if (groups & (1 << self._force.getForceGroup())) == 0:
+        if not self._in_groups(groups):
             return 0.0
         return self._kernel.energy(self._positions)
 
     def getEnergyDecomposition(self, groups=-1):
         """(energy, terms[4, N]) at the context's positions: the per-atom terms of DECOMPOSITION_TERMS, which sum to the energy
         (HipCalcAGBNPForceKernel.decompose).  Honours the force-group mask like getState()."""
-        if self._positions is None:
-            raise OpenMMException("Particle positions have not been set")
-        if (groups & (1 << self._force.getForceGroup())) == 0:
+        if not self._in_groups(groups):
             return 0.0, np.zeros((len(DECOMPOSITION_TERMS), self._kernel.numParticles))
         return self._kernel.decompose(self._positions)
 

@@ -13,24 +13,71 @@ MAX_GROUP = 16  # AGBNP_HIP_MAX_GROUP: members of one agbnp_hip_execute_group ca
 MAX_BINDING_GROUP = 16  # AGBNP_HIP_MAX_BINDING_GROUP: bindings of one agbnp_hip_binding_execute_group call
 DECOMPOSITION_TERMS = 4  # AGBNP_HIP_DECOMPOSITION_TERMS: planes of agbnp_hip_decompose_*
 
-# every symbol include/agbnp_hip.h declares
-SYMBOLS = [
-    "agbnp_hip_create", "agbnp_hip_update_parameters", "agbnp_hip_execute_host", "agbnp_hip_execute_device",
-    "agbnp_hip_execute_openmm", "agbnp_hip_atom_order_changed", "agbnp_hip_finish", "agbnp_hip_poll", "agbnp_hip_wait_verdict", "agbnp_hip_withheld_evaluations", "agbnp_hip_generation", "agbnp_hip_get_scalar", "agbnp_hip_get_vector", "agbnp_hip_get_table_sizes",
-    "agbnp_hip_get_tables", "agbnp_hip_host_tables", "agbnp_hip_num_particles", "agbnp_hip_version",
-    "agbnp_hip_last_error", "agbnp_hip_destroy", "agbnp_hip_device_count", "agbnp_hip_build_id",
-    "agbnp_hip_set_mode", "agbnp_hip_get_mode", "agbnp_hip_set_diagnostics", "agbnp_hip_set_profiling", "agbnp_hip_num_kernels", "agbnp_hip_kernel_name", "agbnp_hip_get_kernel_times",
-    "agbnp_hip_energy_host", "agbnp_hip_energy_device", "agbnp_hip_energy_openmm",
-    "agbnp_hip_execute_group", "agbnp_hip_execute_group_host",
-    "agbnp_hip_energy_group", "agbnp_hip_energy_group_host", "agbnp_hip_expect_jump",
-    "agbnp_hip_decompose_host", "agbnp_hip_decompose_device",
-    "agbnp_hip_binding_create", "agbnp_hip_binding_execute_device", "agbnp_hip_binding_energy_device",
-    "agbnp_hip_binding_execute_host", "agbnp_hip_binding_energy_host", "agbnp_hip_binding_finish",
-    "agbnp_hip_binding_withheld_evaluations", "agbnp_hip_binding_expect_jump", "agbnp_hip_binding_update_parameters",
-    "agbnp_hip_binding_set_mode", "agbnp_hip_binding_member", "agbnp_hip_binding_destroy",
-    "agbnp_hip_binding_execute_group", "agbnp_hip_binding_energy_group",
-    "agbnp_hip_binding_execute_group_host", "agbnp_hip_binding_energy_group_host",
-]
+_i, _d, _vp, _dp, _ip, _s = C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_char_p
+_vpp, _dpp = C.POINTER(C.c_void_p), C.POINTER(_dp)
+_create = [_i, _dp, _dp, _dp, _dp, _ip]  # the particle count and the five parameter arrays
+
+# every symbol include/agbnp_hip.h declares: name -> arguments, or (result, arguments) where the result is not an int.  load()
+# applies the table and SYMBOLS is its keys: a symbol cannot be exported without its signature (ctypes' default -- int arguments,
+# int result -- truncates a 64-bit handle).
+SIGNATURES = {
+    "agbnp_hip_create": [_vpp, *_create, _i, _i, _d, _i],
+    "agbnp_hip_update_parameters": [_vp, *_create],
+    "agbnp_hip_execute_host": [_vp, _dp, _dp, _dp],
+    "agbnp_hip_execute_device": [_vp, _vp, _vp, _vp, _vp],
+    "agbnp_hip_execute_openmm": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "agbnp_hip_energy_host": [_vp, _dp, _dp],
+    "agbnp_hip_energy_device": [_vp, _vp, _vp, _vp],
+    "agbnp_hip_energy_openmm": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "agbnp_hip_decompose_host": [_vp, _dp, _dp, _dp],
+    "agbnp_hip_decompose_device": [_vp, _vp, _vp, _vp, _vp],
+    "agbnp_hip_execute_group": [_vpp, _i, _vpp, _vpp, _vpp, _vp],
+    "agbnp_hip_execute_group_host": [_vpp, _i, _dpp, _dpp, _dp],
+    "agbnp_hip_energy_group": [_vpp, _i, _vpp, _vpp, _vp],
+    "agbnp_hip_energy_group_host": [_vpp, _i, _dpp, _dp],
+    "agbnp_hip_expect_jump": [_vp],
+    "agbnp_hip_atom_order_changed": [_vp],
+    "agbnp_hip_finish": [_vp, _vp, _ip],
+    "agbnp_hip_poll": [_vp, _ip, _ip],
+    "agbnp_hip_wait_verdict": [_vp, _i, _d, _ip, _ip],
+    "agbnp_hip_withheld_evaluations": [_vp, _ip, _i],
+    "agbnp_hip_generation": (C.c_uint, [_vp]),
+    "agbnp_hip_get_scalar": [_vp, _i, _dp],
+    "agbnp_hip_get_vector": [_vp, _i, _dp],
+    "agbnp_hip_get_table_sizes": [_vp, _ip, _ip],
+    "agbnp_hip_get_tables": [_vp, _dp, _dp, _ip, _ip],
+    "agbnp_hip_host_tables": [_i, _dp, _ip, _ip, _ip, _dp, _dp, _i, _ip, _ip],
+    "agbnp_hip_num_particles": [_vp],
+    "agbnp_hip_version": [_vp],
+    "agbnp_hip_last_error": (_s, [_vp]),
+    "agbnp_hip_destroy": (None, [_vp]),
+    "agbnp_hip_device_count": [],
+    "agbnp_hip_build_id": (_s, []),
+    "agbnp_hip_set_mode": [_vp, _i],
+    "agbnp_hip_get_mode": [_vp],
+    "agbnp_hip_set_diagnostics": [_vp, _i],
+    "agbnp_hip_set_profiling": [_vp, _i],
+    "agbnp_hip_num_kernels": [],
+    "agbnp_hip_kernel_name": (_s, [_i]),
+    "agbnp_hip_get_kernel_times": [_vp, _dp, C.POINTER(C.c_long)],
+    "agbnp_hip_binding_create": [_vpp, *_create, _ip, _i, _i, _i, _d, _i],
+    "agbnp_hip_binding_execute_device": [_vp, _vp, _d, _vp, _vp, _vp, _vp],
+    "agbnp_hip_binding_energy_device": [_vp, _vp, _d, _vp, _vp, _vp],
+    "agbnp_hip_binding_execute_host": [_vp, _dp, _d, _dp, _dp, _dp],
+    "agbnp_hip_binding_energy_host": [_vp, _dp, _d, _dp, _dp],
+    "agbnp_hip_binding_finish": [_vp, _vp, _ip],
+    "agbnp_hip_binding_withheld_evaluations": [_vp, _ip, _i],
+    "agbnp_hip_binding_expect_jump": [_vp],
+    "agbnp_hip_binding_update_parameters": [_vp, *_create],
+    "agbnp_hip_binding_set_mode": [_vp, _i],
+    "agbnp_hip_binding_member": (_vp, [_vp, _i]),
+    "agbnp_hip_binding_destroy": (None, [_vp]),
+    "agbnp_hip_binding_execute_group": [_vpp, _i, _vpp, _vp, _vpp, _vpp, _vpp, _vp],
+    "agbnp_hip_binding_energy_group": [_vpp, _i, _vpp, _vp, _vpp, _vpp, _vp],
+    "agbnp_hip_binding_execute_group_host": [_vpp, _i, _dpp, _dp, _dpp, _dp, _dp],
+    "agbnp_hip_binding_energy_group_host": [_vpp, _i, _dpp, _dp, _dp, _dp],
+}
+SYMBOLS = list(SIGNATURES)
 
 _lib = None
 
@@ -64,71 +111,9 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  openmm_agbnp_plugin_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p
-    lib.agbnp_hip_create.argtypes = [C.POINTER(vp), C.c_int, dp, dp, dp, dp, ip, C.c_int, C.c_int, C.c_double, C.c_int]
-    lib.agbnp_hip_update_parameters.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip]
-    lib.agbnp_hip_execute_host.argtypes = [vp, dp, dp, dp]
-    lib.agbnp_hip_execute_device.argtypes = [vp, vp, vp, vp, vp]
-    lib.agbnp_hip_execute_openmm.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]
-    lib.agbnp_hip_energy_host.argtypes = [vp, dp, dp]
-    lib.agbnp_hip_energy_device.argtypes = [vp, vp, vp, vp]
-    lib.agbnp_hip_energy_openmm.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
-    lib.agbnp_hip_execute_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
-    lib.agbnp_hip_execute_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), C.POINTER(dp), dp]
-    lib.agbnp_hip_energy_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), vp]
-    lib.agbnp_hip_energy_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp]
-    lib.agbnp_hip_expect_jump.argtypes = [vp]
-    lib.agbnp_hip_decompose_host.argtypes = [vp, dp, dp, dp]
-    lib.agbnp_hip_decompose_device.argtypes = [vp, vp, vp, vp, vp]
-    lib.agbnp_hip_binding_create.argtypes = [C.POINTER(vp), C.c_int, dp, dp, dp, dp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
-    lib.agbnp_hip_binding_execute_device.argtypes = [vp, vp, C.c_double, vp, vp, vp, vp]
-    lib.agbnp_hip_binding_energy_device.argtypes = [vp, vp, C.c_double, vp, vp, vp]
-    lib.agbnp_hip_binding_execute_host.argtypes = [vp, dp, C.c_double, dp, dp, dp]
-    lib.agbnp_hip_binding_energy_host.argtypes = [vp, dp, C.c_double, dp, dp]
-    lib.agbnp_hip_binding_finish.argtypes = [vp, vp, ip]
-    lib.agbnp_hip_binding_withheld_evaluations.argtypes = [vp, ip, C.c_int]
-    lib.agbnp_hip_binding_expect_jump.argtypes = [vp]
-    lib.agbnp_hip_binding_update_parameters.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip]
-    lib.agbnp_hip_binding_set_mode.argtypes = [vp, C.c_int]
-    lib.agbnp_hip_binding_member.argtypes = [vp, C.c_int]
-    lib.agbnp_hip_binding_member.restype = vp
-    lib.agbnp_hip_binding_destroy.argtypes = [vp]
-    lib.agbnp_hip_binding_destroy.restype = None
-    lib.agbnp_hip_binding_execute_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
-    lib.agbnp_hip_binding_energy_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), vp]
-    lib.agbnp_hip_binding_execute_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp, C.POINTER(dp), dp, dp]
-    lib.agbnp_hip_binding_energy_group_host.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(dp), dp, dp, dp]
-    lib.agbnp_hip_atom_order_changed.argtypes = [vp]
-    lib.agbnp_hip_finish.argtypes = [vp, vp, ip]
-    lib.agbnp_hip_poll.argtypes = [vp, ip, ip]
-    lib.agbnp_hip_wait_verdict.argtypes = [vp, C.c_int, C.c_double, ip, ip]
-    lib.agbnp_hip_withheld_evaluations.argtypes = [vp, ip, C.c_int]
-    lib.agbnp_hip_generation.argtypes = [vp]
-    lib.agbnp_hip_generation.restype = C.c_uint
-    lib.agbnp_hip_get_scalar.argtypes = [vp, C.c_int, dp]
-    lib.agbnp_hip_get_vector.argtypes = [vp, C.c_int, dp]
-    lib.agbnp_hip_get_table_sizes.argtypes = [vp, ip, ip]
-    lib.agbnp_hip_get_tables.argtypes = [vp, dp, dp, ip, ip]
-    lib.agbnp_hip_host_tables.argtypes = [C.c_int, dp, ip, ip, ip, dp, dp, C.c_int, ip, ip]
-    lib.agbnp_hip_num_particles.argtypes = [vp]
-    lib.agbnp_hip_version.argtypes = [vp]
-    lib.agbnp_hip_last_error.argtypes = [vp]
-    lib.agbnp_hip_last_error.restype = C.c_char_p
-    lib.agbnp_hip_destroy.argtypes = [vp]
-    lib.agbnp_hip_destroy.restype = None
-    lib.agbnp_hip_device_count.argtypes = []
-    lib.agbnp_hip_build_id.argtypes = []
-    lib.agbnp_hip_build_id.restype = C.c_char_p
-    lib.agbnp_hip_set_mode.argtypes = [vp, C.c_int]
-    lib.agbnp_hip_get_mode.argtypes = [vp]
-    lib.agbnp_hip_set_diagnostics.argtypes = [vp, C.c_int]
-    lib.agbnp_hip_set_profiling.argtypes = [vp, C.c_int]
-    lib.agbnp_hip_num_kernels.argtypes = []
-    lib.agbnp_hip_kernel_name.argtypes = [C.c_int]
-    lib.agbnp_hip_kernel_name.restype = C.c_char_p
-    lib.agbnp_hip_get_kernel_times.argtypes = [vp, dp, C.POINTER(C.c_long)]
-    for name in SYMBOLS:
-        getattr(lib, name)  # AttributeError if the library does not export it
+    for name, signature in SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export it
+        fn.restype, fn.argtypes = signature if isinstance(signature, tuple) else (C.c_int, signature)
     _lib = lib
     return lib
 

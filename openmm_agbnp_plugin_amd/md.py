@@ -90,6 +90,21 @@ MAX_MOVE_LIMIT = 0.02     # nm: the largest `max_move` minimise() accepts, half 
 MINIMISE_RECORD = np.dtype([("iterations", "<i8"), ("converged", "<i4"), ("fmax", "<f8"), ("energy", "<f8"), ("voids", "<i4"),
                             ("withheld", "<i8")])
 
+_vp, _gp = C.c_void_p, C.POINTER(_GroupArgs)
+# every symbol of libagbnp_md.so the drivers call: name -> arguments (every result is an int: 0, or a hipError)
+_SIGNATURES = {
+    "agbnp_md_blocks": [C.c_int],
+    "agbnp_md_group_pre": [_gp, C.c_int, _vp, _vp],
+    "agbnp_md_group_mid": [_gp, C.c_int, _vp, _vp, _vp],
+    "agbnp_md_group_post": [_gp, _vp, _vp],
+    "agbnp_md_group_tethers": [_gp, _vp, _vp],
+    "agbnp_md_exchange": [C.POINTER(_ExchangeArgs), _vp],
+    "agbnp_md_hamiltonian_exchange": [C.POINTER(_HamiltonianArgs), _vp],
+    "agbnp_md_lambda_exchange": [C.POINTER(_LambdaArgs), _vp],
+    "agbnp_md_fire_back": [_gp, C.POINTER(_FireArgs), _vp, _vp],
+    "agbnp_md_fire_front": [_gp, C.POINTER(_FireArgs), _vp, _vp],
+}
+
 _MD_LIB = None
 
 
@@ -102,17 +117,8 @@ def _md_lib():
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(path)
-        vp, gp = C.c_void_p, C.POINTER(_GroupArgs)
-        lib.agbnp_md_blocks.argtypes = [C.c_int]
-        lib.agbnp_md_group_pre.argtypes = [gp, C.c_int, vp, vp]
-        lib.agbnp_md_group_mid.argtypes = [gp, C.c_int, vp, vp, vp]
-        lib.agbnp_md_group_post.argtypes = [gp, vp, vp]
-        lib.agbnp_md_group_tethers.argtypes = [gp, vp, vp]
-        lib.agbnp_md_exchange.argtypes = [C.POINTER(_ExchangeArgs), vp]
-        lib.agbnp_md_hamiltonian_exchange.argtypes = [C.POINTER(_HamiltonianArgs), vp]
-        lib.agbnp_md_lambda_exchange.argtypes = [C.POINTER(_LambdaArgs), vp]
-        lib.agbnp_md_fire_back.argtypes = [gp, C.POINTER(_FireArgs), vp, vp]
-        lib.agbnp_md_fire_front.argtypes = [gp, C.POINTER(_FireArgs), vp, vp]
+        for name, argtypes in _SIGNATURES.items():
+            getattr(lib, name).argtypes = argtypes  # AttributeError if the library does not export it
         _MD_LIB = lib
     return _MD_LIB
 
@@ -120,6 +126,13 @@ def _md_lib():
 def _check(rc):
     if rc != 0:
         raise RuntimeError(f"libagbnp_md.so: launch failed (hipError {rc})")
+
+
+def _check_engine(rc, symbol, error_handle=None):
+    """A return code of the engine (libagbnp_hip.so) in a driver's launch sequence: a failure raises with the library's message for
+    `error_handle` behind the call's name."""
+    if rc != _lib.OK:
+        raise RuntimeError(f"{symbol}: " + _lib.last_error(error_handle))
 
 
 _KINDS = {"langevin": 0, "verlet": 1}  # the kernels' `kind`
@@ -621,9 +634,8 @@ class _GroupMD:
     # ---- launches
     def _evaluate(self, st):
         """agbnp_hip_execute_group of all members on stream `st`: forces and energies are added to frc[r], e_agbnp[r]."""
-        rc = _lib.load().agbnp_hip_execute_group(self._handles, self.R, self._pos, self._frc, self._ene, C.c_void_p(st))
-        if rc != _lib.OK:
-            raise RuntimeError("agbnp_hip_execute_group: " + _lib.last_error(self.kernels[0]._h))
+        _check_engine(_lib.load().agbnp_hip_execute_group(self._handles, self.R, self._pos, self._frc, self._ene, C.c_void_p(st)),
+                      "agbnp_hip_execute_group", self.kernels[0]._h)
 
     def _chunk(self, steps, attempt_follows):
         """run() is about to enqueue `steps` steps (as many evaluations); `attempt_follows`: an exchange attempt comes right
@@ -830,9 +842,8 @@ class HamiltonianReplicaMD(_GroupMD):
                 return
             for r in members:
                 self.kernels[r].expect_jump()
-            rc = _lib.load().agbnp_hip_energy_group(handles, len(members), pos, ene, C.c_void_p(st))
-            if rc != _lib.OK:
-                raise RuntimeError("agbnp_hip_energy_group: " + _lib.last_error(self.kernels[members[0]]._h))
+            _check_engine(_lib.load().agbnp_hip_energy_group(handles, len(members), pos, ene, C.c_void_p(st)),
+                          "agbnp_hip_energy_group", self.kernels[members[0]]._h)
             _check(self.core.lib.agbnp_md_hamiltonian_exchange(C.byref(self._h[self.core.part_read]), st))
             for r in members:
                 self.kernels[r].expect_jump()
@@ -943,10 +954,9 @@ class BindingReplicaMD(_GroupMD):
         u is added to u[r] by the last evaluation in front of an attempt alone."""
         with_u = self._u_in == 1
         self._u_in = max(self._u_in - 1, 0)
-        rc = _lib.load().agbnp_hip_binding_execute_group(self._handles, self.R, self._pos, C.c_void_p(self.lam.data_ptr()), self._frc,
-                                                         self._ene, self._u if with_u else None, C.c_void_p(st))
-        if rc != _lib.OK:
-            raise RuntimeError("agbnp_hip_binding_execute_group: " + _lib.last_error(None))
+        _check_engine(_lib.load().agbnp_hip_binding_execute_group(self._handles, self.R, self._pos, C.c_void_p(self.lam.data_ptr()),
+                                                                  self._frc, self._ene, self._u if with_u else None, C.c_void_p(st)),
+                      "agbnp_hip_binding_execute_group")
 
     def exchange(self):
         """One exchange attempt between neighbouring rungs, enqueued on the driver's stream; nothing is read and nothing waited
