@@ -82,6 +82,16 @@ __device__ unsigned long long g_wg_log[kWgLogSlots][24];
 #define PSTAMP_FLUSH()
 #endif
 
+// a local atom's gradient sums into the gradient rows of the heavy-atom table (one row per quantity: an atom's adds go to
+// different memory channels.  One 32-byte record per atom -- a quarter of the 64-byte atomic requests -- measured 1.3 us SLOWER:
+// same-line adds queue at the memory side.)
+template <class Store>
+__device__ __forceinline__ void add_gradient_rows(const TreeArgs& A, const Store& S, int la, int hj) {
+  glb_add(&A.hvat(kHvGx, hj), S.at[6][la]);
+  glb_add(&A.hvat(kHvGy, hj), S.at[7][la]);
+  glb_add(&A.hvat(kHvGz, hj), S.at[8][la]);
+}
+
 // Build + cavity passes of one forest = the subtrees of up to kMaxRoots heavy atoms (reference steps A-D of
 // platforms/reference/src/ReferenceAGBNPKernels.cpp:293-384, restated in oracle run_cavity()).  Work slot s builds the
 // work items of its row rows[kRowStride * s ..]; the packing comes from the previous evaluation's subtree sizes
@@ -115,6 +125,129 @@ constexpr int kPendCap = 4;
 #else
 constexpr int kPendCap = 16;  // work items that may wait while a forest that outgrew its store is built again in smaller sets
 #endif
+// ---- the steps of a forest's life, in the order cavity_forests takes them --------------------------------------------------------
+// (1) Fetch the row: the work items of work slot `slot` (written in slot order by the bookkeeping of the previous evaluation: no
+// slot -> forest indirection in front of it), one per lane 0..7 of every wave, -1 = no item; FIVE: and the atom (POSQ: the context's
+// slot) of each item's root.  (Counting the items with a ballot instead of reading the row's count word out of lane 8 makes
+// k_tree_cavity 1.6 us faster on 1dwc, A/B on one box -- same spill counts, different register allocation.)
+// (Slot: unsigned for the workgroup's own slot, int for one from the queue; each is widened where the address is formed.)
+template <class Slot>
+__device__ __forceinline__ int row_item(const TreeArgs& A, Slot slot, int lane) { return lane < kMaxRoots ? A.rows[slot_row_item(slot, lane)] : -1; }
+template <bool FIVE, class Slot>
+__device__ __forceinline__ int row_atom(const TreeArgs& A, Slot slot, int lane, int otherwise) {  // (otherwise: on lanes without an item)
+  return FIVE && lane < kMaxRoots ? A.row_atoms[(size_t)kMaxItems * slot + lane] : otherwise;
+}
+// the atom (POSQ: the context's slot) of root `root`, for a work item that did not come with its row
+template <bool POSQ>
+__device__ __forceinline__ int root_atom(const TreeArgs& A, int root) {
+  return (POSQ ? A.hslot : A.out.h2a)[root];
+}
+// whether local atom la is a root whose work item is part 0 of its subtree: what is counted once per subtree goes with that part
+template <class Store>
+__device__ __forceinline__ bool first_part_root(const Store& S, int la, int m) {
+  return la < m && (S.rt[kRtPart + la] & 0xff) == 0;
+}
+// a local atom's self volume: the sum over its nodes, and a root's own sphere (once per subtree)
+template <class Store>
+__device__ __forceinline__ double self_volume(const Store& S, int la, int m, bool det) {
+  return first_part_root(S, la, m) ? S.at[9][la] + quantize(S.at[4][la], kQVol, det) : S.at[9][la];
+}
+// The energy of a pass to the work slot's word (lane 0): the nodes' sum and the level-1 nodes -- volume V_i, coefficient +1
+// (gaussvol.cpp:138-141), once per subtree.  Accumulated ONTO e_sum, root by root: e_sum + (sum) rounds differently.  (Cavity
+// energies are summed per work slot of the packing: a later set of a healed row adds to its slot's word.)
+template <class Store>
+__device__ __forceinline__ void put_energy(const Store& S, double* word, bool first_set, int m, double e_sum, bool det) {
+  double e = e_sum;
+  for (int q = 0; q < m; q++) e += (S.rt[kRtPart + q] & 0xff) == 0 ? quantize(S.at[5][q] * S.at[4][q], kQEnergy, det) : 0.0;
+  if (first_set)
+    *word = e;
+  else
+    *word += e;
+}
+// (5) Topology out for the pseudo-volume pass, into work slot `out`: the atom paths (8 B/node), the membership list and the local
+// atom list are all a replay needs; fixed stride per work slot, no allocation traffic
+template <int NCAP, int ACAP, int BS>
+__device__ __forceinline__ void write_topology(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, int tid, int out, int m, int nnodes, int natoms,
+                                               int npairs) {
+  const size_t pool_off = (size_t)out * NCAP, atom_off = (size_t)out * ACAP;
+  const unsigned long long* path = reinterpret_cast<const unsigned long long*>(S.nd[6]);
+  for (int n = m + tid; n < nnodes; n += BS) A.node_pool[pool_off + n] = path[n];
+  for (int la = tid; la < natoms; la += BS) A.atom_pool[atom_off + la] = S.at_gidx[la];
+  if (TreeStore<NCAP, ACAP>::kPairGather) {
+    const size_t pair_off = (size_t)out * TreeStore<NCAP, ACAP>::PCAP;
+    for (int k = tid; k < npairs; k += BS) A.pair_pool[pair_off + k] = S.pairs[k];
+  }
+  if (tid == 0) {
+    SubtreeHeader h;
+    h.nnodes = nnodes;
+    h.natoms = natoms;
+    h.nroots = m;
+    h.npairs = npairs;
+    for (int q = 0; q < kMaxRoots; q++) h.partners[q] = q < m ? S.rt[kRtCount + q] : 0;
+    A.hdr[out] = h;
+  }
+  // per-subtree shape for the next evaluation's packing and the statistics (zeroed by k_prep; the work items
+  // of a shared subtree add their own nodes, part 0 the root and the partner count)
+  if (tid < m) {
+    const bool first = (S.rt[kRtPart + tid] & 0xff) == 0;
+    int* sz = reinterpret_cast<int*>(&A.sizes[S.rt[kRtHeavy + tid]]);  // (no global load behind the stores above)
+    atomicAdd(&sz[0], S.rt[kRtNodes + tid] + (first ? 1 : 0));
+    if (first) sz[1] = 1 + S.rt[kRtCount + tid];
+  }
+}
+// (6) Switch the local atoms to vdW radii, nu = -gamma/roffset, for pass 2, whose self volumes the Born stage needs.  One atom
+// per lane (ACAP <= BS): the parameters were requested in front of pass 1 and arrive in a_vdw / v_vdw.
+template <int NCAP, int ACAP, int BS>
+__device__ __forceinline__ void switch_to_vdw(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, int tid, int natoms, double a_vdw, double v_vdw) {
+  if (ACAP <= BS) {
+    if (tid < natoms) {
+      S.at[3][tid] = a_vdw;
+      S.at[4][tid] = v_vdw;
+      S.at[5][tid] = -S.at[5][tid];
+    }
+  } else {
+    for (int la = tid; la < natoms; la += BS) {
+      const int hj = S.at_gidx[la];
+      S.at[3][la] = A.hvat(kHvAVdw, hj);
+      S.at[4][la] = A.hvat(kHvVVdw, hj);
+      S.at[5][la] = -S.at[5][la];
+    }
+  }
+}
+
+// (4) HEALING (round 6).  A forest that outgrows its store -- the packing was planned from an earlier geometry's shapes -- used
+// to void the whole evaluation (kStatPackOverflow: withheld, repeated by the host on one subtree per slot, the packing
+// tightened for everybody).  A failed build has touched nothing outside this workgroup's store, so the workgroup simply
+// builds the row's items again in smaller SETS: the first half now, the items left over (s_pend) afterwards, each later set
+// into a SPARE work slot (numbered from max(forests, forest workgroups of the launch) on: no workgroup of either tree launch
+// has such a slot as its own; k_tree_pseudo reaches them through its queue).  Likewise a LONE item that outgrows the store
+// while its subtree is whole or shared two ways is built again as the parts of a four-way share that cover it (part p of 2 =
+// parts p and 3 - p of 4: level2_owner).  The evaluation stays complete; kStatSpareForests tells the bookkeeping to plan anew.
+// (The healing itself and the hand-over to the next set stay in cavity_forests: as functions they move `vgpr`)
+// What could not be healed is reported: the evaluation is void, work slot `out` holds nothing to replay.
+// A forest that does not fit is a packing misprediction (repeat unpacked), and so is a lone work item whose nodes
+// do not fit while its subtree can still be shared among more items (each expands a residue class of the level-2
+// branches; every item holds all level-2 atoms, so an ATOM overflow is not helped by sharing); a lone item of a
+// subtree that is shared four ways already needs the next capacity variant.  (out: the LDS word itself, read by lane 0 alone.)
+template <int NCAP>
+__device__ __forceinline__ void report_overflow(const TreeArgs& A, int tid, int m, int rc, int item0, int parts0, const int& out) {
+  if (tid == 0) {
+    const bool splittable = m == 1 && rc == kBuildNodeOverflow && parts0 < 4 && (A.split_fit & 1) != 0;
+    atomicAdd(&A.status[(m > 1 || splittable) ? kStatPackOverflow : (rc == kBuildNodeOverflow ? kStatNodeOverflow : kStatAtomOverflow)], 1);
+    if (m > 1) atomicAdd(&A.status[kStatForestOverflow], rc == kBuildNodeOverflow ? 1 : 0x10000);  // (what tightens the packing's assumed capacity)
+    if (splittable) {
+      atomicMax(&A.status[kStatSplitWanted], parts0);
+      // The device reacts by itself (evaluations may be queued behind this one long before a host sees the log): the
+      // subtree's shape is recorded as "more than four stores' worth of nodes", so that this evaluation's bookkeeping
+      // -- whose fallback packing shares to FIT -- hands the subtree to four work items in the very next evaluation
+      // (its level-2 count is left at what the other items of the subtree report, or 0: the conservative side)
+      atomicAdd(reinterpret_cast<int*>(&A.sizes[work_item_root(item0)]), 4 * NCAP);
+    }
+    A.hdr[out].nnodes = 0;
+    A.hdr[out].natoms = 0;
+  }
+  tree_barrier<NCAP>();
+}
 // SV1: the launch also collects the self volumes of pass 1 (enlarged radii; a diagnostic: agbnp_hip_set_diagnostics)
 // FIVE: the five-launch mode's instantiation (k_tree_cavity_five below): positions straight from the caller's array.
 // POSQ: FIVE with the positions in an OpenMM context's posq (TreeArgs::posq; row_atoms holds slots)
@@ -124,7 +257,7 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
   TreeStore<NCAP, ACAP> S;
   S.carve(GLOBAL ? (A.scratch + (size_t)AGBNP_WG * A.scratch_stride) : smem);
   __shared__ int s_next;  // hand-off word of the work queue (in LDS for every variant)
-  // healing (below): work items of the slot's row that wait for another set, their number, and the work slot the set in hand
+  // healing: work items of the slot's row that wait for another set, their number, and the work slot the set in hand
   // writes its topology to -- in LDS, not in registers: the build keeps ~190 scalar values live as it is
   __shared__ int s_pend[kPendCap + 2];
   int& s_npend = s_pend[kPendCap];
@@ -132,9 +265,7 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
   const int tid = threadIdx.x;
   // the row of the workgroup's own work slot is requested before anything is waited for (AGBNP_WG < slot_cap: the
   // row exists whether or not the slot is in use)
-  int first_item = -1, first_atom = 0;
-  if ((tid & 63) < kMaxRoots) first_item = A.rows[slot_row_item(AGBNP_WG, tid & 63)];
-  if (FIVE && (tid & 63) < kMaxRoots) first_atom = A.row_atoms[(size_t)kMaxItems * AGBNP_WG + (tid & 63)];
+  const int first_item = row_item(A, AGBNP_WG, tid & 63), first_atom = row_atom<FIVE>(A, AGBNP_WG, tid & 63, 0);
   const int nforests = min(A.nforests()[0], A.slot_cap);  // (never above the slots the per-slot arrays hold)
   if (AGBNP_WG == 0 && tid == 0) A.cur_nforests()[0] = nforests;
   if ((int)AGBNP_WG >= nforests && tid == 0) {  // an idle work slot: k_tree_pseudo's workgroup of the same slot finds nothing to replay
@@ -147,238 +278,143 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
   for (int slot = AGBNP_WG; slot < nforests;) {
     constexpr int kNotAsked = 0x3fffffff;  // (a forest that fails before it asks ends the workgroup's run: the evaluation is void anyway)
     int ticket = kNotAsked;  // lane 0: the queue is asked for the forest after this one ONCE per slot, however many sets it takes
-    // the slot's row of work items (written in slot order by the bookkeeping of the previous evaluation: no
-    // slot -> forest indirection in front of it): lanes 0..7 of every wave fetch one item each
-    // (-1 = no item.  Counting the items with a ballot instead of reading the row's count word out of lane 8 makes
-    // k_tree_cavity 1.6 us faster on 1dwc, A/B on one box -- same spill counts, different register allocation.)
+    // ---- (1) the slot's row of work items
     int my_item = first_item, my_atom = first_atom;
     if (slot != (int)AGBNP_WG) {  // (a forest from the queue)
       // (the lane number through an opaque move: otherwise the compiler forms the per-lane row address at the kernel's head, keeps
       // it for this path alone and -- at the register limit -- parks it in scratch: 8 bytes of stores per lane and launch)
       int lane_q = lane;
       asm volatile("" : "+v"(lane_q));
-      my_item = -1;
-      if (lane_q < kMaxRoots) my_item = A.rows[slot_row_item(slot, lane_q)];
-      if (FIVE && lane_q < kMaxRoots) my_atom = A.row_atoms[(size_t)kMaxItems * slot + lane_q];
+      my_item = row_item(A, slot, lane_q), my_atom = row_atom<FIVE>(A, slot, lane_q, my_atom);
     }
-    // HEALING (round 6).  A forest that outgrows its store -- the packing was planned from an earlier geometry's shapes -- used
-    // to void the whole evaluation (kStatPackOverflow: withheld, repeated by the host on one subtree per slot, the packing
-    // tightened for everybody).  A failed build has touched nothing outside this workgroup's store, so the workgroup simply
-    // builds the row's items again in smaller SETS: the first half now, the items left over (s_pend) afterwards, each later set
-    // into a SPARE work slot (numbered from max(forests, forest workgroups of the launch) on: no workgroup of either tree launch
-    // has such a slot as its own; k_tree_pseudo reaches them through its queue).  Likewise a LONE item that outgrows the store
-    // while its subtree is whole or shared two ways is built again as the parts of a four-way share that cover it (part p of 2 =
-    // parts p and 3 - p of 4: level2_owner).  The evaluation stays complete; kStatSpareForests tells the bookkeeping to plan anew.
     if (tid == 0) s_npend = 0, s_out = slot;  // (visible behind the barrier in front of the build)
-    for (;;) {        // the sets of the slot's row: ONE, unless a forest outgrew its store
-    const int m = __popcll(__ballot(my_item >= 0));  // 1..kMaxRoots
-    int items[kMaxRoots];
+    for (;;) {  // the sets of the slot's row (HEALING, above): ONE, unless a forest outgrew its store
+      const int m = __popcll(__ballot(my_item >= 0));  // 1..kMaxRoots
+      int items[kMaxRoots];
 #pragma unroll
-    for (int q = 0; q < kMaxRoots; q++) items[q] = __builtin_amdgcn_readlane(my_item, q);
-    for (int la = tid; la < ACAP; la += BS) {
-      S.at[6][la] = 0.0;
-      S.at[7][la] = 0.0;
-      S.at[8][la] = 0.0;
-      S.at[9][la] = 0.0;
-    }
-    tree_barrier<NCAP>();
-    CSTAMP_BEGIN();
-    int nnodes = 0, natoms = 0;
-    int rc = build_forest<NCAP, ACAP, BS, FIVE, POSQ>(S, A, tid, my_item, items, m, &nnodes, &natoms, my_atom);
-    CSTAMP(0);
-    double e_sum = 0.0;
-    int npairs = 0;
-    constexpr bool want_sv1 = SV1;
-    const bool det = A.det != 0;
-    // the vdW parameters of pass 2 are requested now and arrive underneath pass 1 (natoms <= ACAP <= BS for the
-    // LDS variants: one atom per lane)
-    const int hj_mine = (rc == kBuildOk && tid < natoms) ? S.at_gidx[tid] : work_item_root(items[0]);
-    const double a_vdw_mine = A.hvat(kHvAVdw, hj_mine), v_vdw_mine = A.hvat(kHvVVdw, hj_mine);
-    // ---- pass 1: enlarged radii, nu = +gamma/roffset (reference steps A-B, ReferenceAGBNPKernels.cpp:293-339).
-    // The node slots still hold the Gaussians of the build, so only the atom paths and the membership list are
-    // laid down before the gather.  Its gradient stays in the local accumulators and leaves with that of pass 2.
-    if (rc == kBuildOk && !volume_pass<NCAP, ACAP, BS, true, true>(S, tid, m, nnodes, natoms, want_sv1, &e_sum, &npairs, det))
-      rc = kBuildNodeOverflow;  // the membership list does not fit: same protocol as a node overflow
-    if (rc != kBuildOk) {
-      const int parts0 = work_item_parts(items[0]);
-      // ---- healed here if it can be (see above): a forest of several items in two halves, a lone splittable item as the
-      // parts of a four-way share
-      const bool refine = m == 1 && rc == kBuildNodeOverflow && (A.split_fit & 1) != 0 && parts0 <= 2;
-      const int more = (A.split_fit & 2) == 0 ? 0 : (m > 1 ? m - m / 2 : (refine ? 4 / parts0 - 1 : 0));  // items this set hands to s_pend
-      const int npend = s_npend;
-      if (more > 0 && npend + more <= kPendCap) {
-        tree_barrier<NCAP>();  // (everybody has read the count)
-        if (m > 1) {
-          // (the lane's item again from the store's root words, its root's atom again through h2a: nothing is kept alive
-          // across the build for this path)
-          const int keep = m / 2;
-          int mine = -1;
-          if (lane < m) {
-            const int pp = S.rt[kRtPart + lane];
-            mine = S.rt[kRtHeavy + lane] | ((pp & 0xff) << kWorkItemPartShift) | (((pp >> 8) - 1) << kWorkItemPartsShift);  // (make_work_item, written out: agbnp_common.h)  // (make_work_item, written out: agbnp_common.h)
-          }
-          if (tid < 64 && lane >= keep && lane < m) s_pend[npend + lane - keep] = mine;
-          my_item = lane < keep ? mine : -1;
-          if (FIVE) my_atom = my_item >= 0 ? (POSQ ? A.hslot : A.out.h2a)[work_item_root(my_item)] : 0;
-        } else {
-          const int root = work_item_root(items[0]), p = work_item_part(items[0]);
-          auto part_of_four = [&](int q) { return make_work_item(root, q, 4); };
-          if (tid == 0) {
-            if (parts0 == 1) {
-              s_pend[npend] = part_of_four(1), s_pend[npend + 1] = part_of_four(2), s_pend[npend + 2] = part_of_four(3);
-            } else {
-              s_pend[npend] = part_of_four(3 - p);
-            }
-          }
-          my_item = lane == 0 ? part_of_four(parts0 == 1 ? 0 : p) : -1;
-          if (FIVE) my_atom = lane == 0 ? (POSQ ? A.hslot : A.out.h2a)[root] : 0;
-        }
-        if (tid == 0) s_npend = npend + more;
-        continue;  // the same slot again, with the smaller set (the barrier in front of the build orders the list)
-      }
-      if (tid == 0) {
-        // a forest that does not fit is a packing misprediction (repeat unpacked), and so is a lone work item whose nodes
-        // do not fit while its subtree can still be shared among more items (each expands a residue class of the level-2
-        // branches; every item holds all level-2 atoms, so an ATOM overflow is not helped by sharing); a lone item of a
-        // subtree that is shared four ways already needs the next capacity variant
-        // (round 6: what gets here is what could not be healed above: a three-way share, the waiting list full)
-        const bool splittable = m == 1 && rc == kBuildNodeOverflow && parts0 < 4 && (A.split_fit & 1) != 0;
-        atomicAdd(&A.status[(m > 1 || splittable) ? kStatPackOverflow : (rc == kBuildNodeOverflow ? kStatNodeOverflow : kStatAtomOverflow)], 1);
-        if (m > 1) atomicAdd(&A.status[kStatForestOverflow], rc == kBuildNodeOverflow ? 1 : 0x10000);  // (what tightens the packing's assumed capacity)
-        if (splittable) {
-          atomicMax(&A.status[kStatSplitWanted], parts0);
-          // The device reacts by itself (evaluations may be queued behind this one long before a host sees the log): the
-          // subtree's shape is recorded as "more than four stores' worth of nodes", so that this evaluation's bookkeeping
-          // -- whose fallback packing shares to FIT -- hands the subtree to four work items in the very next evaluation
-          // (its level-2 count is left at what the other items of the subtree report, or 0: the conservative side)
-          atomicAdd(reinterpret_cast<int*>(&A.sizes[work_item_root(items[0])]), 4 * NCAP);
-        }
-        A.hdr[s_out].nnodes = 0;
-        A.hdr[s_out].natoms = 0;
-      }
-      tree_barrier<NCAP>();
-      break;  // on to the next forest (the evaluation is void: what waits is dropped)
-    }
-    CSTAMP(1);
-    // Take delivery of the prefetched vdW parameters HERE, while nothing else is in flight: the memory counter is in
-    // order, so a wait placed after the topology stores below would also wait for every one of them.
-    asm volatile("" ::"v"(a_vdw_mine), "v"(v_vdw_mine));
-    if (queued && tid == 0 && ticket == kNotAsked) ticket = atomicAdd(&A.status[kStatCavityQueue], 1);  // the forest AFTER this one
-    const int out = s_out;  // (== slot unless this is a later set of a healed row)
-    if (tid == 0) {
-      // level-1 nodes: volume V_i, coefficient +1 (gaussvol.cpp:138-141); once per subtree (its part 0)
-      double e1 = e_sum;
-      for (int q = 0; q < m; q++) e1 += (S.rt[kRtPart + q] & 0xff) == 0 ? quantize(S.at[5][q] * S.at[4][q], kQEnergy, det) : 0.0;
-      // (cavity energies are summed per work slot of the packing: a later set of a healed row adds to its slot's word)
-      if (out == slot)
-        A.epart[2 * slot] = e1;
-      else
-        A.epart[2 * slot] += e1;
-    }
-    if (want_sv1) {  // diagnostics: enlarged-radius self volumes
-      for (int la = tid; la < natoms; la += BS) {
-        glb_add(&A.hvat(kHvSvLarge, S.at_gidx[la]),
-                (la < m && (S.rt[kRtPart + la] & 0xff) == 0) ? S.at[9][la] + quantize(S.at[4][la], kQVol, det) : S.at[9][la]);
+      for (int q = 0; q < kMaxRoots; q++) items[q] = __builtin_amdgcn_readlane(my_item, q);
+      for (int la = tid; la < ACAP; la += BS) {
+        S.at[6][la] = 0.0;
+        S.at[7][la] = 0.0;
+        S.at[8][la] = 0.0;
         S.at[9][la] = 0.0;
       }
-    }
-    // ---- topology out for the pseudo-volume pass: the atom paths (8 B/node), the membership list and the local
-    // atom list are all a replay needs; fixed stride per work slot, no allocation traffic
-    {
-      const size_t pool_off = (size_t)out * NCAP, atom_off = (size_t)out * ACAP;
-      const unsigned long long* path = reinterpret_cast<const unsigned long long*>(S.nd[6]);
-      for (int n = m + tid; n < nnodes; n += BS) A.node_pool[pool_off + n] = path[n];
-      for (int la = tid; la < natoms; la += BS) A.atom_pool[atom_off + la] = S.at_gidx[la];
-      if (TreeStore<NCAP, ACAP>::kPairGather) {
-        const size_t pair_off = (size_t)out * TreeStore<NCAP, ACAP>::PCAP;
-        for (int k = tid; k < npairs; k += BS) A.pair_pool[pair_off + k] = S.pairs[k];
+      tree_barrier<NCAP>();
+      CSTAMP_BEGIN();
+      // ---- (2) build
+      int nnodes = 0, natoms = 0;
+      int rc = build_forest<NCAP, ACAP, BS, FIVE, POSQ>(S, A, tid, my_item, items, m, &nnodes, &natoms, my_atom);
+      CSTAMP(0);
+      double e_sum = 0.0;
+      int npairs = 0;
+      constexpr bool want_sv1 = SV1;
+      const bool det = A.det != 0;
+      // the vdW parameters of pass 2 are requested now and arrive underneath pass 1 (natoms <= ACAP <= BS for the
+      // LDS variants: one atom per lane)
+      const int hj_mine = (rc == kBuildOk && tid < natoms) ? S.at_gidx[tid] : work_item_root(items[0]);
+      const double a_vdw_mine = A.hvat(kHvAVdw, hj_mine), v_vdw_mine = A.hvat(kHvVVdw, hj_mine);
+      // ---- (3) pass 1: enlarged radii, nu = +gamma/roffset (reference steps A-B, ReferenceAGBNPKernels.cpp:293-339).
+      // The node slots still hold the Gaussians of the build, so only the atom paths and the membership list are
+      // laid down before the gather.  Its gradient stays in the local accumulators and leaves with that of pass 2.
+      if (rc == kBuildOk && !volume_pass<NCAP, ACAP, BS, true, true>(S, tid, m, nnodes, natoms, want_sv1, &e_sum, &npairs, det))
+        rc = kBuildNodeOverflow;  // the membership list does not fit: same protocol as a node overflow
+      // ---- (4) heal or report
+      if (rc != kBuildOk) {
+        // healed here if it can be: a forest of several items in two halves, a lone splittable item as the parts of a four-way
+        // share; the items this set hands to s_pend need room on the waiting list
+        const int parts0 = work_item_parts(items[0]);
+        const bool refine = m == 1 && rc == kBuildNodeOverflow && (A.split_fit & 1) != 0 && parts0 <= 2;
+        const int more = (A.split_fit & 2) == 0 ? 0 : (m > 1 ? m - m / 2 : (refine ? 4 / parts0 - 1 : 0));  // items this set hands to s_pend
+        const int npend = s_npend;
+        if (more > 0 && npend + more <= kPendCap) {
+          tree_barrier<NCAP>();  // (everybody has read the count)
+          if (m > 1) {
+            // (the lane's item again from the store's root words, its root's atom again through h2a: nothing is kept alive
+            // across the build for this path)
+            const int keep = m / 2;
+            int mine = -1;
+            if (lane < m) {
+              const int pp = S.rt[kRtPart + lane];
+              mine = S.rt[kRtHeavy + lane] | ((pp & 0xff) << kWorkItemPartShift) | (((pp >> 8) - 1) << kWorkItemPartsShift);  // (make_work_item, written out)
+            }
+            if (tid < 64 && lane >= keep && lane < m) s_pend[npend + lane - keep] = mine;
+            my_item = lane < keep ? mine : -1;
+            if (FIVE) my_atom = my_item >= 0 ? root_atom<POSQ>(A, work_item_root(my_item)) : 0;
+          } else {
+            const int root = work_item_root(items[0]), p = work_item_part(items[0]);
+            auto part_of_four = [&](int q) { return make_work_item(root, q, 4); };
+            if (tid == 0) {
+              if (parts0 == 1) {
+                s_pend[npend] = part_of_four(1), s_pend[npend + 1] = part_of_four(2), s_pend[npend + 2] = part_of_four(3);
+              } else {
+                s_pend[npend] = part_of_four(3 - p);
+              }
+            }
+            my_item = lane == 0 ? part_of_four(parts0 == 1 ? 0 : p) : -1;
+            if (FIVE) my_atom = lane == 0 ? root_atom<POSQ>(A, root) : 0;
+          }
+          if (tid == 0) s_npend = npend + more;
+          continue;  // the same slot again, with the smaller set (the barrier in front of the build orders the list)
+        }
+        report_overflow<NCAP>(A, tid, m, rc, items[0], parts0, s_out);
+        break;  // on to the next forest (the evaluation is void: what waits is dropped)
       }
-      if (tid == 0) {
-        SubtreeHeader h;
-        h.nnodes = nnodes;
-        h.natoms = natoms;
-        h.nroots = m;
-        h.npairs = npairs;
-        for (int q = 0; q < kMaxRoots; q++) h.partners[q] = q < m ? S.rt[kRtCount + q] : 0;
-        A.hdr[out] = h;
+      CSTAMP(1);
+      // Take delivery of the prefetched vdW parameters HERE, while nothing else is in flight: the memory counter is in
+      // order, so a wait placed after the topology stores below would also wait for every one of them.
+      asm volatile("" ::"v"(a_vdw_mine), "v"(v_vdw_mine));
+      if (queued && tid == 0 && ticket == kNotAsked) ticket = atomicAdd(&A.status[kStatCavityQueue], 1);  // the forest AFTER this one
+      const int out = s_out;  // (== slot unless this is a later set of a healed row)
+      if (tid == 0) put_energy(S, &A.epart[2 * slot], out == slot, m, e_sum, det);
+      if (want_sv1) {  // diagnostics: enlarged-radius self volumes
+        for (int la = tid; la < natoms; la += BS) {
+          glb_add(&A.hvat(kHvSvLarge, S.at_gidx[la]), self_volume(S, la, m, det));
+          S.at[9][la] = 0.0;
+        }
       }
-      // per-subtree shape for the next evaluation's packing and the statistics (zeroed by k_prep; the work items
-      // of a shared subtree add their own nodes, part 0 the root and the partner count)
-      if (tid < m) {
-        const bool first = (S.rt[kRtPart + tid] & 0xff) == 0;
-        int* sz = reinterpret_cast<int*>(&A.sizes[S.rt[kRtHeavy + tid]]);  // (no global load behind the stores above)
-        atomicAdd(&sz[0], S.rt[kRtNodes + tid] + (first ? 1 : 0));
-        if (first) sz[1] = 1 + S.rt[kRtCount + tid];
-      }
-    }
-    CSTAMP(2);
-    // switch the local atoms to vdW radii, nu = -gamma/roffset, for pass 2, whose self volumes the Born stage needs
-    if (ACAP <= BS) {
-      if (tid < natoms) {
-        S.at[3][tid] = a_vdw_mine;
-        S.at[4][tid] = v_vdw_mine;
-        S.at[5][tid] = -S.at[5][tid];
-      }
-    } else {
+      // ---- (5) topology out for the pseudo-volume pass
+      write_topology<NCAP, ACAP, BS>(S, A, tid, out, m, nnodes, natoms, npairs);
+      CSTAMP(2);
+      // ---- (6) vdW radii
+      switch_to_vdw<NCAP, ACAP, BS>(S, A, tid, natoms, a_vdw_mine, v_vdw_mine);
+      tree_barrier<NCAP>();  // the topology stores above keep draining underneath pass 2
+      CSTAMP(3);
+      // ---- (7) pass 2: vdW radii, nu = -gamma/roffset
+      volume_pass<NCAP, ACAP, BS, true>(S, tid, m, nnodes, natoms, true, &e_sum, &npairs, det);
+      CSTAMP(4);
+      root_gradients_from_invariance<NCAP, ACAP, BS>(S, tid, m);
+      CSTAMP(5);
+      // ---- (8) flush the per-atom sums (a root's self volume: its own sphere + every node of its tree) and the energy
       for (int la = tid; la < natoms; la += BS) {
         const int hj = S.at_gidx[la];
-        S.at[3][la] = A.hvat(kHvAVdw, hj);
-        S.at[4][la] = A.hvat(kHvVVdw, hj);
-        S.at[5][la] = -S.at[5][la];
+        add_gradient_rows(A, S, la, hj);
+        glb_add(&A.hvat(kHvSvVdw, hj), self_volume(S, la, m, det));
       }
-    }
-    tree_barrier<NCAP>();  // the topology stores above keep draining underneath pass 2
-    CSTAMP(3);
-
-    // ---- pass 2: vdW radii, nu = -gamma/roffset
-    volume_pass<NCAP, ACAP, BS, true>(S, tid, m, nnodes, natoms, true, &e_sum, &npairs, det);
-    CSTAMP(4);
-    root_gradients_from_invariance<NCAP, ACAP, BS>(S, tid, m);
-    CSTAMP(5);
-
-    // ---- flush per-atom sums (a root's self volume: its own sphere + every node of its tree)
-    // (one row per quantity: an atom's four adds go to four memory channels.  One 32-byte record per atom -- a quarter
-    // of the 64-byte atomic requests -- measured 1.3 us SLOWER: same-line adds queue at the memory side.)
-    for (int la = tid; la < natoms; la += BS) {
-      const int hj = S.at_gidx[la];
-      glb_add(&A.hvat(kHvGx, hj), S.at[6][la]);
-      glb_add(&A.hvat(kHvGy, hj), S.at[7][la]);
-      glb_add(&A.hvat(kHvGz, hj), S.at[8][la]);
-      glb_add(&A.hvat(kHvSvVdw, hj),
-              (la < m && (S.rt[kRtPart + la] & 0xff) == 0) ? S.at[9][la] + quantize(S.at[4][la], kQVol, det) : S.at[9][la]);
-    }
-    if (tid == 0) {
-      double e2 = e_sum;
-      for (int q = 0; q < m; q++) e2 += (S.rt[kRtPart + q] & 0xff) == 0 ? quantize(S.at[5][q] * S.at[4][q], kQEnergy, det) : 0.0;
-      if (out == slot)
-        A.epart[2 * slot + 1] = e2;
-      else
-        A.epart[2 * slot + 1] += e2;
-    }
-    tree_barrier<NCAP>();
-    CSTAMP(6);
-    CSTAMP_FLUSH();
-    const int npend = s_npend;
-    if (npend == 0) break;
-    // ---- the next set of a healed row: the items that wait (at most kMaxRoots of them), into a spare work slot
-    {
-      if (tid == 0) s_next = atomicAdd(&A.status[kStatSpareForests], 1);
-      lds_barrier();
-      const int spare = max(nforests, tree_blocks) + s_next;
-      lds_barrier();
-      if (spare >= A.slot_cap) {  // no spare slot left (never seen: the pools hold four slots per subtree): the evaluation is void
-        if (tid == 0) {
-          atomicAdd(&A.status[kStatPackOverflow], 1);
-          atomicAdd(&A.status[kStatForestOverflow], 1);
+      if (tid == 0) put_energy(S, &A.epart[2 * slot + 1], out == slot, m, e_sum, det);
+      tree_barrier<NCAP>();
+      CSTAMP(6);
+      CSTAMP_FLUSH();
+      // ---- (9) the next set of a healed row: the items that wait (at most kMaxRoots of them), into a spare work slot
+      const int npend = s_npend;
+      if (npend == 0) break;
+      {
+        if (tid == 0) s_next = atomicAdd(&A.status[kStatSpareForests], 1);
+        lds_barrier();
+        const int spare = max(nforests, tree_blocks) + s_next;
+        lds_barrier();
+        if (spare >= A.slot_cap) {  // no spare slot left (never seen: the pools hold four slots per subtree): the evaluation is void
+          if (tid == 0) {
+            atomicAdd(&A.status[kStatPackOverflow], 1);
+            atomicAdd(&A.status[kStatForestOverflow], 1);
+          }
+          break;
         }
-        break;
+        const int take = min(npend, kMaxRoots);
+        my_item = lane < take ? s_pend[npend - take + lane] : -1;
+        if (FIVE) my_atom = my_item >= 0 ? root_atom<POSQ>(A, work_item_root(my_item)) : 0;
+        lds_barrier();  // (the list is read: the next set may add to it)
+        if (tid == 0) s_npend = npend - take, s_out = spare;
       }
-      const int take = min(npend, kMaxRoots);
-      my_item = lane < take ? s_pend[npend - take + lane] : -1;
-      if (FIVE) my_atom = my_item >= 0 ? (POSQ ? A.hslot : A.out.h2a)[work_item_root(my_item)] : 0;
-      lds_barrier();  // (the list is read: the next set may add to it)
-      if (tid == 0) s_npend = npend - take, s_out = spare;
-    }
     }
     if (!queued) break;
     slot = __builtin_amdgcn_readfirstlane(next_forest(tid, &s_next, ticket, tree_blocks));  // (wave-uniform by construction: keeps everything derived from it in scalar registers)
@@ -457,6 +493,70 @@ __device__ __forceinline__ void outputs_role(const TreeArgs& A, int blk, int bs)
   add_force(O, i, fx, fy, fz);
 }
 
+// ---- the steps of a replay that both loops of k_tree_pseudo take ---------------------------------------------------------------
+// What a lane keeps of a stored forest between the request and the store's tables: 16-byte words of the membership list, path
+// words, its local atom.  Stores of up to 8 BS nodes and BS atoms in LDS ask for the paths and the atom together with the header.
+template <int NCAP, int ACAP, int BS, bool GLOBAL>
+struct ReplayRegs {
+  static constexpr bool kPaths = !GLOBAL && NCAP <= 8 * BS && ACAP <= BS, kPairs = TreeStore<NCAP, ACAP>::kPairGather;
+  static constexpr int kPathRegs = kPaths ? (NCAP + BS - 1) / BS : 1;
+  static constexpr int kPairWords = kPairs ? TreeStore<NCAP, ACAP>::PCAP / 8 : 1, kPairRegs = (kPairWords + BS - 1) / BS;
+};
+// Root words from the header's partner counts (lane 0; `partners`: the header's array, in registers or in memory)
+template <class Store, class Partners>
+__device__ __forceinline__ void put_root_words(const Store& S, int tid, int m, const Partners& partners) {
+  if (tid == 0) {
+    int run = m;
+    for (int q = 0; q < m; q++) {
+      const int c = partners[q];
+      S.rt[kRtCount + q] = c;
+      S.rt[kRtBase + q] = run;
+      run += c;
+    }
+  }
+}
+// the requested path words into the store's path row (the roots have none)
+template <int BS, class Store, int N>
+__device__ __forceinline__ void put_paths(const Store& S, int tid, int m, int nnodes, const unsigned long long (&pw)[N]) {
+  unsigned long long* path = reinterpret_cast<unsigned long long*>(S.nd[6]);
+#pragma unroll
+  for (int k = 0; k < N; k++)
+    if (tid + k * BS >= m && tid + k * BS < nnodes) path[tid + k * BS] = pw[k];
+}
+// Local-atom table fill: atom `la` of the store is heavy atom hj with vdW radii and nu = (W + U) / V; cleared gradient sums.
+// (The self-volume accumulators are idle in this pass: the slot carries the atom's index for the flush.)
+template <class Store>
+__device__ __forceinline__ void put_replay_atom(const Store& S, int la, int hj, double x, double y, double z, double a, double v, double nu,
+                                                bool write_forces, int atom) {
+  S.at_gidx[la] = hj;
+  put_atom(S, la, x, y, z, a, v, nu);
+  S.at[6][la] = 0.0, S.at[7][la] = 0.0, S.at[8][la] = 0.0;
+  S.at[9][la] = write_forces ? __hiloint2double(0, atom) : 0.0;
+}
+// Flush of a replayed forest's gradient sums: force = -gradient straight into the caller's buffer (nothing of an overflowed
+// evaluation: is_void() is asked only where forces are written), or into the gradient rows of the heavy-atom table
+template <int BS, class Store, class IsVoid>
+__device__ __forceinline__ void flush_replay(const TreeArgs& A, const Store& S, int tid, int natoms, bool write_forces, IsVoid is_void) {
+  if (write_forces) {
+    if (!is_void()) {
+      if (A.out.force_fixed) {
+        for (int la = tid; la < natoms; la += BS) add_force(A.out, __double2loint(S.at[9][la]), -S.at[6][la], -S.at[7][la], -S.at[8][la]);
+      } else {
+        // the caller's [n][3] array: the three components of an atom are one lane each, next to each other, so that they
+        // leave in ONE atomic request per atom.  (A lane per atom and one instruction per component sends three requests
+        // to the same line one behind the other, and same-line adds queue at the memory side: +1.9 us on 1dwc.)
+        for (int k = tid; k < 3 * natoms; k += BS) {
+          const int la = k / 3, c = k - 3 * la;
+          const double* row = c == 0 ? S.at[6] : (c == 1 ? S.at[7] : S.at[8]);
+          glb_add(&A.out.force[3 * (size_t)__double2loint(S.at[9][la]) + c], -row[la]);
+        }
+      }
+    }
+  } else {
+    for (int la = tid; la < natoms; la += BS) add_gradient_rows(A, S, la, S.at_gidx[la]);
+  }
+}
+
 // Replay of a stored forest with vdW radii: reference steps K+L (ReferenceAGBNPKernels.cpp:718-747),
 // nu_i = (W_i+U_i)/V_i formed on the fly from the chain-rule sums, gradient only.  The reference does two passes
 // (W then U); the pass is linear in nu, so one pass with the sum gives the same gradient.
@@ -486,6 +586,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
   const int nforests = nspare > 0 ? max(nplanned, grid) + nspare : nplanned;
   // The workgroup's own work slot needs no test: k_tree_cavity leaves "nothing to replay" in the header of an idle slot,
   // so the forest's topology is requested straight away.
+  using Regs = ReplayRegs<NCAP, ACAP, BS, GLOBAL>;
   constexpr bool kPipelined = PIPE && !GLOBAL && NCAP <= 8 * BS && ACAP <= BS && TreeStore<NCAP, ACAP>::kPairGather;
   if constexpr (kPipelined) {
     // Round 4: the replay of QUEUED forests is pipelined (systems with more forests than resident workgroups: the 16.6 k-atom
@@ -495,11 +596,8 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
     // in the middle of the volume pass), and its per-atom parameters behind the current forest's root gradients, in front
     // of the flush.  Lattice: k_tree_pseudo 51.5 -> 48.4-51.2 us (A/B on one box, profiles/r04): the trips were mostly hidden
     // by the other four workgroups of the CU already.  One forest per workgroup (1dwc): the same work as before.
-    constexpr int KP = (NCAP + BS - 1) / BS;
-    constexpr int kPairWordsP = TreeStore<NCAP, ACAP>::PCAP / 8;  // 16-byte words of the pair list
-    constexpr int kPairRegsP = (kPairWordsP + BS - 1) / BS;         // ... per lane
-    unsigned long long pw[KP];
-    uint4 pair_word[kPairRegsP];
+    unsigned long long pw[Regs::kPathRegs];
+    uint4 pair_word[Regs::kPairRegs];
     int hj_pre = 0;
     int h_nnodes = 0, h_natoms = 0, h_m = 0, h_npairs = 0, h_partners[kMaxRoots];  // the forest's header (wave-uniform)
     auto request_topology = [&](int slot_) {  // one round trip: header, paths, membership list, local atoms (capacity-strided
@@ -507,13 +605,13 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
       const SubtreeHeader* H = &A.hdr[slot_];  // written by k_tree_cavity's workgroup of the same slot
       const size_t pool_off = (size_t)slot_ * NCAP, atom_off = (size_t)slot_ * ACAP;
 #pragma unroll
-      for (int k = 0; k < kPairRegsP; k++) {
+      for (int k = 0; k < Regs::kPairRegs; k++) {
         pair_word[k] = make_uint4(0, 0, 0, 0);
-        if (tid + k * BS < kPairWordsP)
+        if (tid + k * BS < Regs::kPairWords)
           pair_word[k] = reinterpret_cast<const uint4*>(A.pair_pool + (size_t)slot_ * TreeStore<NCAP, ACAP>::PCAP)[tid + k * BS];
       }
 #pragma unroll
-      for (int k = 0; k < KP; k++) pw[k] = tid + k * BS < NCAP ? A.node_pool[pool_off + tid + k * BS] : 0ull;
+      for (int k = 0; k < Regs::kPathRegs; k++) pw[k] = tid + k * BS < NCAP ? A.node_pool[pool_off + tid + k * BS] : 0ull;
       hj_pre = tid < ACAP ? A.atom_pool[atom_off + tid] : 0;
       h_nnodes = H->nnodes, h_natoms = H->natoms, h_m = H->nroots, h_npairs = H->npairs;
 #pragma unroll
@@ -553,35 +651,10 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
         slot = slot_;
         continue;
       }
-      if (tid == 0) {
-        int run = m;
-        for (int q = 0; q < m; q++) {
-          S.rt[kRtCount + q] = h_partners[q];
-          S.rt[kRtBase + q] = run;
-          run += h_partners[q];
-        }
-      }
-      {
-        unsigned long long* path = reinterpret_cast<unsigned long long*>(S.nd[6]);
-#pragma unroll
-        for (int k = 0; k < KP; k++)
-          if (tid + k * BS >= m && tid + k * BS < nnodes) path[tid + k * BS] = pw[k];
-      }
+      put_root_words(S, tid, m, h_partners);
+      put_paths<BS>(S, tid, m, nnodes, pw);
       if (!have_parameters) request_parameters();
-      if (tid < natoms) {
-        S.at_gidx[tid] = hj_pre;
-        S.at[0][tid] = px;
-        S.at[1][tid] = py;
-        S.at[2][tid] = pz;
-        S.at[3][tid] = pa;
-        S.at[4][tid] = pv;
-        S.at[5][tid] = pnu;
-        S.at[6][tid] = 0.0;
-        S.at[7][tid] = 0.0;
-        S.at[8][tid] = 0.0;
-        // (the self-volume accumulators are idle in this pass: the slot carries the atom's index for the flush)
-        S.at[9][tid] = write_forces ? __hiloint2double(0, pidx) : 0.0;
-      }
+      if (tid < natoms) put_replay_atom(S, tid, hj_pre, px, py, pz, pa, pv, pnu, write_forces, pidx);
       tree_barrier<NCAP>();
       PSTAMP(0);
       // every global load of this forest has been consumed: ask for the number of the next one (see k_tree_cavity) ...
@@ -607,29 +680,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
         request_parameters();
         have_parameters = true;
       }
-      if (write_forces) {  // force = -gradient, straight into the caller's buffer (nothing of an overflowed evaluation)
-        if (!is_void) {
-          if (A.out.force_fixed) {
-            for (int la = tid; la < natoms; la += BS) add_force(A.out, __double2loint(S.at[9][la]), -S.at[6][la], -S.at[7][la], -S.at[8][la]);
-          } else {
-            // the caller's [n][3] array: the three components of an atom are one lane each, next to each other, so that they
-            // leave in ONE atomic request per atom.  (A lane per atom and one instruction per component sends three requests
-            // to the same line one behind the other, and same-line adds queue at the memory side: +1.9 us on 1dwc.)
-            for (int k = tid; k < 3 * natoms; k += BS) {
-              const int la = k / 3, c = k - 3 * la;
-              const double* row = c == 0 ? S.at[6] : (c == 1 ? S.at[7] : S.at[8]);
-              glb_add(&A.out.force[3 * (size_t)__double2loint(S.at[9][la]) + c], -row[la]);
-            }
-          }
-        }
-      } else {
-        for (int la = tid; la < natoms; la += BS) {
-          const int hj = S.at_gidx[la];
-          glb_add(&A.hvat(kHvGx, hj), S.at[6][la]);
-          glb_add(&A.hvat(kHvGy, hj), S.at[7][la]);
-          glb_add(&A.hvat(kHvGz, hj), S.at[8][la]);
-        }
-      }
+      flush_replay<BS>(A, S, tid, natoms, write_forces, [&] { return is_void; });
       tree_barrier<NCAP>();
       PSTAMP(2);
       PSTAMP_FLUSH();
@@ -647,22 +698,19 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
     // values are masked below), a second one to the per-atom parameters.
     const SubtreeHeader* H = &A.hdr[slot];  // written by k_tree_cavity's workgroup of the same slot
     const size_t pool_off = (size_t)slot * NCAP, atom_off = (size_t)slot * ACAP;
-    constexpr bool kPrefetch = !GLOBAL && NCAP <= 8 * BS && ACAP <= BS;  // topology requested together with the header
-    unsigned long long pw[kPrefetch ? (NCAP + BS - 1) / BS : 1];
+    constexpr bool kPrefetch = Regs::kPaths, kPairs = Regs::kPairs;  // (kPrefetch: topology requested together with the header)
+    unsigned long long pw[Regs::kPathRegs];
+    uint4 pair_word[Regs::kPairRegs];
     int hj_pre = 0;
-    constexpr bool kPairs = TreeStore<NCAP, ACAP>::kPairGather;
-    constexpr int kPairWords = kPairs ? TreeStore<NCAP, ACAP>::PCAP / 8 : 1;  // 16-byte words of the pair list
-    constexpr int kPairRegs = (kPairWords + BS - 1) / BS;                       // ... per lane
-    uint4 pair_word[kPairRegs];
 #pragma unroll
-    for (int k = 0; k < kPairRegs; k++) {
+    for (int k = 0; k < Regs::kPairRegs; k++) {
       pair_word[k] = make_uint4(0, 0, 0, 0);
-      if (kPairs && tid + k * BS < kPairWords)
+      if (kPairs && tid + k * BS < Regs::kPairWords)
         pair_word[k] = reinterpret_cast<const uint4*>(A.pair_pool + (size_t)slot * TreeStore<NCAP, ACAP>::PCAP)[tid + k * BS];
     }
     if (kPrefetch) {
 #pragma unroll
-      for (int k = 0; k < (NCAP + BS - 1) / BS; k++) pw[k] = tid + k * BS < NCAP ? A.node_pool[pool_off + tid + k * BS] : 0ull;
+      for (int k = 0; k < Regs::kPathRegs; k++) pw[k] = tid + k * BS < NCAP ? A.node_pool[pool_off + tid + k * BS] : 0ull;
       hj_pre = tid < ACAP ? A.atom_pool[atom_off + tid] : 0;
     }
     const int nnodes = H->nnodes, natoms = H->natoms, m = H->nroots;
@@ -672,39 +720,17 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
       if (queued && tid == 0) ticket = atomicAdd(&A.status[kStatPseudoQueue], 1);
       break;
     }
-    if (tid == 0) {
-      int run = m;
-      for (int q = 0; q < m; q++) {
-        const int c = H->partners[q];
-        S.rt[kRtCount + q] = c;
-        S.rt[kRtBase + q] = run;
-        run += c;
-      }
-    }
-    {
+    put_root_words(S, tid, m, H->partners);
+    if (!kPrefetch) {
       unsigned long long* path = reinterpret_cast<unsigned long long*>(S.nd[6]);
-      if (!kPrefetch) {
-        for (int n = m + tid; n < nnodes; n += BS) path[n] = A.node_pool[pool_off + n];
-      } else {
-#pragma unroll
-        for (int k = 0; k < (NCAP + BS - 1) / BS; k++)
-          if (tid + k * BS >= m && tid + k * BS < nnodes) path[tid + k * BS] = pw[k];
-      }
+      for (int n = m + tid; n < nnodes; n += BS) path[n] = A.node_pool[pool_off + n];
+    } else {
+      put_paths<BS>(S, tid, m, nnodes, pw);
     }
     for (int la = tid; la < natoms; la += BS) {
       const int hj = kPrefetch ? hj_pre : A.atom_pool[atom_off + la];
-      S.at_gidx[la] = hj;
-      S.at[0][la] = A.hvat(kHvX, hj);
-      S.at[1][la] = A.hvat(kHvY, hj);
-      S.at[2][la] = A.hvat(kHvZ, hj);
-      S.at[3][la] = A.hvat(kHvAVdw, hj);
-      S.at[4][la] = A.hvat(kHvVVdw, hj);
-      S.at[5][la] = A.db_wu[hj] * A.hvat(kHvInvVol, hj);
-      S.at[6][la] = 0.0;
-      S.at[7][la] = 0.0;
-      S.at[8][la] = 0.0;
-      // (the self-volume accumulators are idle in this pass: the slot carries the atom's index for the flush)
-      S.at[9][la] = write_forces ? __hiloint2double(0, A.out.h2a[hj]) : 0.0;
+      put_replay_atom(S, la, hj, A.hvat(kHvX, hj), A.hvat(kHvY, hj), A.hvat(kHvZ, hj), A.hvat(kHvAVdw, hj), A.hvat(kHvVVdw, hj),
+                      A.db_wu[hj] * A.hvat(kHvInvVol, hj), write_forces, write_forces ? A.out.h2a[hj] : 0);
     }
     tree_barrier<NCAP>();
     PSTAMP(0);
@@ -714,29 +740,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
     volume_pass<NCAP, ACAP, BS, false>(S, tid, m, nnodes, natoms, false, &e_sum, &npairs, A.det != 0, kPairs ? pair_word : nullptr);
     PSTAMP(1);
     root_gradients_from_invariance<NCAP, ACAP, BS>(S, tid, m);
-    if (write_forces) {  // force = -gradient, straight into the caller's buffer (nothing of an overflowed evaluation)
-      if (!evaluation_void(A.status)) {
-        if (A.out.force_fixed) {
-          for (int la = tid; la < natoms; la += BS) add_force(A.out, __double2loint(S.at[9][la]), -S.at[6][la], -S.at[7][la], -S.at[8][la]);
-        } else {
-          // the caller's [n][3] array: the three components of an atom are one lane each, next to each other, so that they
-          // leave in ONE atomic request per atom.  (A lane per atom and one instruction per component sends three requests
-          // to the same line one behind the other, and same-line adds queue at the memory side: +1.9 us on 1dwc.)
-          for (int k = tid; k < 3 * natoms; k += BS) {
-            const int la = k / 3, c = k - 3 * la;
-            const double* row = c == 0 ? S.at[6] : (c == 1 ? S.at[7] : S.at[8]);
-            glb_add(&A.out.force[3 * (size_t)__double2loint(S.at[9][la]) + c], -row[la]);
-          }
-        }
-      }
-    } else {
-      for (int la = tid; la < natoms; la += BS) {
-        const int hj = S.at_gidx[la];
-        glb_add(&A.hvat(kHvGx, hj), S.at[6][la]);
-        glb_add(&A.hvat(kHvGy, hj), S.at[7][la]);
-        glb_add(&A.hvat(kHvGz, hj), S.at[8][la]);
-      }
-    }
+    flush_replay<BS>(A, S, tid, natoms, write_forces, [&] { return evaluation_void(A.status); });
     tree_barrier<NCAP>();
     PSTAMP(2);
     PSTAMP_FLUSH();

@@ -163,7 +163,6 @@ __host__ __device__ inline int level2_owner(int r, int parts) {
   return m2 < parts ? m2 : 2 * parts - 1 - m2;
 }
 
-
 // ---- LDS / scratch carve-out -----------------------------------------------------------------
 template <int NCAP, int ACAP>
 struct TreeStore {
@@ -327,14 +326,13 @@ __device__ __forceinline__ double dev_merge_volume2(double x1, double y1, double
 
 // node record of an overlap whose unswitched volume is already known: exponent sum and weighted centre, no exp / sqrt
 __device__ __forceinline__ void dev_merge_known(double x1, double y1, double z1, double a1, double x2, double y2, double z2,
-                                                double a2, double gvol, double& x, double& y, double& z, double& a) {
+                                                double a2, double& x, double& y, double& z, double& a) {
   const double a12 = a1 + a2;
   const double deltai = fast_rcp(a12);
   x = (x1 * a1 + x2 * a2) * deltai;
   y = (y1 * a1 + y2 * a2) * deltai;
   z = (z1 * a1 + z2 * a2) * deltai;
   a = a12;
-  (void)gvol;
 }
 
 // ---- wave / workgroup helpers -------------------------------------------------------------------
@@ -365,7 +363,29 @@ __device__ __forceinline__ void glb_add(double* p, double v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// wave64 inclusive scan (DPP: 4 shifts inside each row of 16 lanes, then two row broadcasts)
+// The DPP controls the tree kernels use.  A wave64 scan is six steps (wave_scan_steps): four shifts inside each row of 16 lanes,
+// after which lane 15 of every row holds the row's sum, then two row broadcasts under a row mask, after which lane 63 holds the
+// wave's.  Lanes without a source (and rows outside the mask) receive the `old` operand of the step.
+constexpr int kDppWaveShl1 = 0x130, kDppWaveShr1 = 0x138;  // lane l <- lane l + 1 (lane 63: none) / lane l - 1 (lane 0: none)
+template <int CTRL, int ROW_MASK>
+struct DppStep {
+  static constexpr int kCtrl = CTRL, kRowMask = ROW_MASK;
+};
+template <class Step>
+__device__ __forceinline__ void wave_scan_steps(Step&& step) {
+  step(DppStep<0x111, 0xf>{});  // row_shr:1
+  step(DppStep<0x112, 0xf>{});  // row_shr:2
+  step(DppStep<0x114, 0xf>{});  // row_shr:4
+  step(DppStep<0x118, 0xf>{});  // row_shr:8
+  step(DppStep<0x142, 0xa>{});  // row_bcast:15 -> rows 1, 3
+  step(DppStep<0x143, 0xc>{});  // row_bcast:31 -> rows 2, 3
+}
+template <class S>
+__device__ __forceinline__ int dpp_i32(S, int old, int v) {
+  return __builtin_amdgcn_update_dpp(old, v, S::kCtrl, S::kRowMask, 0xf, false);
+}
+
+// wave64 inclusive scan (the six steps written out: through wave_scan_steps the operands of every add come out swapped)
 __device__ __forceinline__ int wave_inclusive_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
   v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
@@ -378,7 +398,7 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
 
 // sum of one double per lane over the wave, returned on every lane (DPP adds inside rows, two row broadcasts,
 // then a broadcast of lane 63): ~3x cheaper than six ds_bpermute exchanges
-template <int CTRL, int ROW_MASK>
+template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ double dpp_f64(double v) {
   const unsigned long long u = (unsigned long long)__double_as_longlong(v);
   const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, ROW_MASK, 0xf, false);
@@ -386,12 +406,7 @@ __device__ __forceinline__ double dpp_f64(double v) {
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 __device__ __forceinline__ double wave_sum_f64(double v) {
-  v += dpp_f64<0x111, 0xf>(v);  // row_shr:1   (lanes without a source add 0.0)
-  v += dpp_f64<0x112, 0xf>(v);  // row_shr:2
-  v += dpp_f64<0x114, 0xf>(v);  // row_shr:4
-  v += dpp_f64<0x118, 0xf>(v);  // row_shr:8   -> lane 15 of every row holds the row sum
-  v += dpp_f64<0x142, 0xa>(v);  // row_bcast:15 -> rows 1,3
-  v += dpp_f64<0x143, 0xc>(v);  // row_bcast:31 -> rows 2,3; lane 63 holds the wave sum
+  wave_scan_steps([&](auto s) { v += dpp_f64<decltype(s)::kCtrl, decltype(s)::kRowMask>(v); });  // (lanes without a source add 0.0)
   const unsigned long long u = (unsigned long long)__double_as_longlong(v);
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, 63);
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 63);
@@ -425,6 +440,19 @@ __device__ __forceinline__ unsigned long long kept_bits(const unsigned long long
 
 enum BuildResult { kBuildOk = 0, kBuildNodeOverflow = 1, kBuildAtomOverflow = 2 };
 
+// ---- the records of the store ----------------------------------------------------------------------------------------------
+// local atom i: centre, exponent, volume, gamma (the accumulators at[6..9] and at_gidx are the caller's)
+template <class Store>
+__device__ __forceinline__ void put_atom(const Store& S, int i, double x, double y, double z, double a, double v, double g) {
+  S.at[0][i] = x, S.at[1][i] = y, S.at[2][i] = z;
+  S.at[3][i] = a, S.at[4][i] = v, S.at[5][i] = g;
+}
+// node i: centre, exponent, unswitched volume
+template <class Store>
+__device__ __forceinline__ void put_node(const Store& S, int i, double x, double y, double z, double a, double v) {
+  S.nd[0][i] = x, S.nd[1][i] = y, S.nd[2][i] = z;
+  S.nd[3][i] = a, S.nd[4][i] = v;
+}
 // ---- build the forest of the heavy atoms roots[0..m) (large radii) -----------------------------------------
 // Node and local-atom numbering: 0..m-1 are the roots (level 1), then the level-2 nodes of root 0, of root 1, ...
 // (level-2 node k <-> local atom k), then level 3 of all trees, and so on: levels are contiguous over the whole
@@ -500,18 +528,9 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
       rx = A.hvat(kHvX, hi), ry = A.hvat(kHvY, hi), rz = A.hvat(kHvZ, hi);
     }
     const double ra = A.hvat(kHvALarge, hi), rv = A.hvat(kHvVLarge, hi), rg = A.hvat(kHvGam, hi);
-    S.at[0][tid] = rx;
-    S.at[1][tid] = ry;
-    S.at[2][tid] = rz;
-    S.at[3][tid] = ra;
-    S.at[4][tid] = rv;
-    S.at[5][tid] = rg;
+    put_atom(S, tid, rx, ry, rz, ra, rv, rg);
     S.at_gidx[tid] = hi;
-    S.nd[0][tid] = rx;
-    S.nd[1][tid] = ry;
-    S.nd[2][tid] = rz;
-    S.nd[3][tid] = ra;
-    S.nd[4][tid] = rv;
+    put_node(S, tid, rx, ry, rz, ra, rv);
     S.nla[tid] = (unsigned short)tid;
     S.npar[tid] = 0xFFFF;
     S.rt[kRtHeavy + tid] = hi;
@@ -544,11 +563,7 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
       S.cand_vol[p] = sv;
       S.cand_idx[p] = hj | (q << 24);
       const int st = NCAP - 1 - p;  // staging slot of the accepted candidates (level-2 nodes land below ACAP)
-      S.nd[0][st] = xj;
-      S.nd[1][st] = yj;
-      S.nd[2][st] = zj;
-      S.nd[3][st] = aj;
-      S.nd[4][st] = vj;
+      put_node(S, st, xj, yj, zj, aj, vj);  // (the candidate's ATOM record, parked until the ranking)
       S.at[9][p] = gj;  // (the self-volume accumulators are idle during the build; handed back as zeros below)
       S.nd[6][st] = gvol;  // unswitched overlap with the root: the level-2 node's volume
     }
@@ -626,8 +641,8 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
     S.ncs[tid] = (unsigned short)bq;  // first child
     S.ncc[tid] = (unsigned short)cq;
   }
-  // rank inside the root's candidates by switched volume (descending; exact ties by atom index) and create local
-  // atoms + level-2 nodes.  The rank is a count over all candidates: a chain of LDS round trips, four reads each.  With
+  // ---- level-2 ranking: rank inside the root's candidates by switched volume (descending; exact ties by atom index) and
+  // create local atoms + level-2 nodes.  The rank is a count over all candidates: a chain of LDS round trips, four reads each.  With
   // up to 64 candidates (the usual forest) every wave counts a share of the list for candidate `lane` and the shares meet
   // in LDS (the task-start words are idle until the expansion): a third of the trips for one barrier more.
   constexpr int kWaves = BS / 64;
@@ -640,7 +655,7 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
       const double my = S.cand_vol[c];
       const int packed = S.cand_idx[c];
       const int q = packed >> 24, hj = packed & 0xffffff;
-      auto before = [&](double vk, int ik) {
+      auto before = [&](double vk, int ik) {  // (the predicate and the count loop of the ranking below: as one function both loops move)
         return ((ik >> 24) == q && (vk > my || (vk == my && (ik & 0xffffff) < hj))) ? 1 : 0;
       };
       int k = k0;
@@ -658,16 +673,14 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
     const double my = S.cand_vol[c];
     const int packed = S.cand_idx[c];
     const int q = packed >> 24, hj = packed & 0xffffff;
-    // four independent LDS reads per trip: the loop is bound by LDS latency, not by the compares
-    int rank = 0;
-    int k = 0;
-    auto before = [&](double vk, int ik) {  // same root, larger volume; exact tie (incl. itself: never counted): atom index
-      return ((ik >> 24) == q && (vk > my || (vk == my && (ik & 0xffffff) < hj))) ? 1 : 0;
-    };
-    if (split_rank) {
+    int rank = 0, k = 0;
+    if (split_rank) {  // (the shares are in: nothing left to count)
       for (int w = 0; w < kWaves; w++) rank += S.tstart[w * 64 + c];
       k = ncand;
     }
+    auto before = [&](double vk, int ik) {  // same root, larger volume; exact tie (incl. itself: never counted): atom index
+      return ((ik >> 24) == q && (vk > my || (vk == my && (ik & 0xffffff) < hj))) ? 1 : 0;
+    };
     for (; k + 4 <= ncand; k += 4) {
       const double v0 = S.cand_vol[k], v1 = S.cand_vol[k + 1], v2 = S.cand_vol[k + 2], v3 = S.cand_vol[k + 3];
       const int i0 = S.cand_idx[k], i1 = S.cand_idx[k + 1], i2 = S.cand_idx[k + 2], i3 = S.cand_idx[k + 3];
@@ -684,21 +697,12 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
     const int st = NCAP - 1 - c;
     const double x2 = S.nd[0][st], y2 = S.nd[1][st], z2 = S.nd[2][st], a2 = S.nd[3][st], v2 = S.nd[4][st], g2 = S.at[9][c];
     S.at[9][c] = 0.0;
-    S.at[0][slot] = x2;
-    S.at[1][slot] = y2;
-    S.at[2][slot] = z2;
-    S.at[3][slot] = a2;
-    S.at[4][slot] = v2;
-    S.at[5][slot] = g2;
+    put_atom(S, slot, x2, y2, z2, a2, v2, g2);
     S.at_gidx[slot] = hj;
     const double gv2 = S.nd[6][st];  // unswitched overlap with the root, from the exact test of the search
     double cmx, cmy, cmz, cma;
-    dev_merge_known(S.at[0][q], S.at[1][q], S.at[2][q], S.at[3][q], x2, y2, z2, a2, gv2, cmx, cmy, cmz, cma);
-    S.nd[0][slot] = cmx;
-    S.nd[1][slot] = cmy;
-    S.nd[2][slot] = cmz;
-    S.nd[3][slot] = cma;
-    S.nd[4][slot] = gv2;
+    dev_merge_known(S.at[0][q], S.at[1][q], S.at[2][q], S.at[3][q], x2, y2, z2, a2, cmx, cmy, cmz, cma);
+    put_node(S, slot, cmx, cmy, cmz, cma, gv2);
     S.nla[slot] = (unsigned short)slot;
     S.npar[slot] = (unsigned short)q;
     S.ncs[slot] = (unsigned short)(bq + cq);  // until the node is expanded: end of its sibling list
@@ -735,29 +739,33 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
       // wave 0 alone; wider levels (forests, big subtrees) take all waves and one more barrier for up to BS nodes.
       const bool wide = BS > 64 && le - nb > 64;
       int nin, T;
+      // what both forms do with the lane's node k (lane tid of the batch): its tasks ...
+      auto task_count = [&](int k, bool has) { return (has && owned_level2(k)) ? (int)S.ncs[k] - k - 1 : 0; };
+      // ... and, for a node inside the batch (tasks up to `incl` fit), its task start and its tasks' bytes of the map
+      auto map_tasks = [&](int incl, int cnt) {
+        const int excl = incl - cnt;
+        S.tstart[tid] = (unsigned short)excl;
+        for (int i = 0; i < cnt; i++) tmap[excl + i] = (unsigned char)tid;
+      };
       if (!wide) {
-        // (every wave: the counts are one LDS read and a DPP scan; only wave 0 writes the map)
-        const int ln = tid & 63;
-        const int k = nb + ln;
+        // narrow: every wave scans for itself (the counts are one LDS read and a DPP scan); only wave 0 writes the map
+        const int k = nb + (tid & 63);
         const bool has = k < le;
-        const int cnt = (has && owned_level2(k)) ? (int)S.ncs[k] - k - 1 : 0;
+        const int cnt = task_count(k, has);
         const int incl = wave_inclusive_scan(cnt);
         const bool inb = has && (incl <= TCAP);  // prefix property: the batch is lanes 0..nin-1
         nin = __popcll(__ballot(inb));
         T = __builtin_amdgcn_readlane(incl, nin - 1);  // nin >= 1: a single node has < ACAP <= TCAP tasks
         if (tid < 64) {
-          if (inb) {
-            const int excl = incl - cnt;
-            S.tstart[tid] = (unsigned short)excl;
-            for (int i = 0; i < cnt; i++) tmap[excl + i] = (unsigned char)tid;
-          }
+          if (inb) map_tasks(incl, cnt);
           if (tid == 0) S.tstart[nin] = (unsigned short)T;
         }
       } else {
+        // wide: every wave scans its 64 nodes, the waves' totals meet in LDS (the extra barrier), lane 0 adds the batch up
         const int wv = tid >> 6, ln = tid & 63;
         const int k = nb + tid;
         const bool has = k < le;
-        const int cnt = (has && owned_level2(k)) ? (int)S.ncs[k] - k - 1 : 0;
+        const int cnt = task_count(k, has);
         const int local = wave_inclusive_scan(cnt);
         if (ln == 63) S.ctl[4 + wv] = local;
         tree_barrier<NCAP>();
@@ -768,11 +776,7 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
         const unsigned long long bm = __ballot(inb);
         const int nw = __popcll(bm);
         const int tw = nw > 0 ? __builtin_amdgcn_readlane(incl, nw > 0 ? nw - 1 : 0) : 0;
-        if (inb) {
-          const int excl = incl - cnt;
-          S.tstart[tid] = (unsigned short)excl;
-          for (int i = 0; i < cnt; i++) tmap[excl + i] = (unsigned char)tid;
-        }
+        if (inb) map_tasks(incl, cnt);
         if (ln == 0) {
           S.ctl[8 + wv] = nw;
           S.rt[kRtNum + 1 + wv] = tw;
@@ -863,13 +867,9 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
             const int slot = cb + rank;
             const int la = la_known >= 0 ? la_known : (int)S.nla[kk + 1 + (t - ts)];
             double mx, my, mz, ma;
-            dev_merge_known(S.nd[0][kk], S.nd[1][kk], S.nd[2][kk], S.nd[3][kk], S.at[0][la], S.at[1][la], S.at[2][la], S.at[3][la], v,
-                            mx, my, mz, ma);
-            S.nd[0][slot] = mx;
-            S.nd[1][slot] = my;
-            S.nd[2][slot] = mz;
-            S.nd[3][slot] = ma;
-            S.nd[4][slot] = v;
+            dev_merge_known(S.nd[0][kk], S.nd[1][kk], S.nd[2][kk], S.nd[3][kk], S.at[0][la], S.at[1][la], S.at[2][la], S.at[3][la], mx, my,
+                            mz, ma);
+            put_node(S, slot, mx, my, mz, ma, v);
             S.nla[slot] = (unsigned short)la;
             S.npar[slot] = (unsigned short)kk;
             S.ncs[slot] = (unsigned short)(cb + c);  // end of this child's sibling list
@@ -964,7 +964,7 @@ __device__ __forceinline__ void pair_gather(const TreeStore<NCAP, ACAP>& S, int 
   const int key = cur >= 0 ? cur : -2 - lane;
   {
     // first runs: continuation of the previous lane's last run -> that lane takes it; else it is a complete run
-    const int prev_key = __builtin_amdgcn_update_dpp(-1, key, 0x138, 0xf, 0xf, false);       // wave_shr:1 (lane 0 keeps -1)
+    const int prev_key = __builtin_amdgcn_update_dpp(-1, key, kDppWaveShr1, 0xf, 0xf, false);  // (lane 0 keeps -1)
     const bool head_cont = head_atom >= 0 && lane > 0 && prev_key == head_atom;
     if (head_atom >= 0 && !head_cont) {
       if (lane == 0)
@@ -972,17 +972,17 @@ __device__ __forceinline__ void pair_gather(const TreeStore<NCAP, ACAP>& S, int 
       else
         plain_add(head_atom, hx, hy, hz, hs);
     }
-    // lane l receives lane l+1's continuing first run (wave_shl:1; lane 63 receives nothing)
+    // lane l receives lane l+1's continuing first run (lane 63 receives nothing)
     const double sx = head_cont ? hx : 0.0, sy = head_cont ? hy : 0.0, sz = head_cont ? hz : 0.0, ss = head_cont ? hs : 0.0;
-    gx += dpp_f64<0x130, 0xf>(sx);
-    gy += dpp_f64<0x130, 0xf>(sy);
-    gz += dpp_f64<0x130, 0xf>(sz);
-    if (with_selfvol) sv += dpp_f64<0x130, 0xf>(ss);
+    gx += dpp_f64<kDppWaveShl1>(sx);
+    gy += dpp_f64<kDppWaveShl1>(sy);
+    gz += dpp_f64<kDppWaveShl1>(sz);
+    if (with_selfvol) sv += dpp_f64<kDppWaveShl1>(ss);
   }
-  // segmented inclusive scan over the lanes (4 shifts inside each row of 16 lanes, then two row broadcasts)
-  auto seg_step = [&](auto ctrl_tag, auto mask_tag) {
-    constexpr int CTRL = decltype(ctrl_tag)::value, MASK = decltype(mask_tag)::value;
-    const int src_key = __builtin_amdgcn_update_dpp(-1, key, CTRL, MASK, 0xf, false);  // lanes without a source keep -1
+  // segmented inclusive scan over the lanes
+  wave_scan_steps([&](auto s) {
+    constexpr int CTRL = decltype(s)::kCtrl, MASK = decltype(s)::kRowMask;
+    const int src_key = dpp_i32(s, -1, key);  // lanes without a source keep -1
     const bool same = src_key == key;
     const double ax = dpp_f64<CTRL, MASK>(gx), ay = dpp_f64<CTRL, MASK>(gy), az = dpp_f64<CTRL, MASK>(gz);
     gx += same ? ax : 0.0;
@@ -992,15 +992,9 @@ __device__ __forceinline__ void pair_gather(const TreeStore<NCAP, ACAP>& S, int 
       const double as = dpp_f64<CTRL, MASK>(sv);
       sv += same ? as : 0.0;
     }
-  };
-  seg_step(std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});  // row_shr:1
-  seg_step(std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});  // row_shr:2
-  seg_step(std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});  // row_shr:4
-  seg_step(std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});  // row_shr:8
-  seg_step(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});  // row_bcast:15 -> rows 1, 3
-  seg_step(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});  // row_bcast:31 -> rows 2, 3
+  });
   {
-    const int next_key = __builtin_amdgcn_update_dpp(-1, key, 0x130, 0xf, 0xf, false);  // wave_shl:1 (lane 63 keeps -1)
+    const int next_key = __builtin_amdgcn_update_dpp(-1, key, kDppWaveShl1, 0xf, 0xf, false);  // (lane 63 keeps -1)
     const bool seg_end = cur >= 0 && (lane == 63 || next_key != key);
     const int key_first = __builtin_amdgcn_readfirstlane(key), key_last = __builtin_amdgcn_readlane(key, 63);
     if (seg_end) {
@@ -1066,77 +1060,77 @@ __device__ bool volume_pass(const TreeStore<NCAP, ACAP>& S, int tid, int m, int 
     const int n = nbase + tid;
     int level = 0, rootq = -1;  // rootq < 0: no node on this lane, or an inert one
     double g = 0.0, gam = 0.0, w = 0.0;
-    do {
+    do {  // (one trip: an inert node leaves it early)
       if (n >= nnodes) break;
-    if (FRESH_BUILD) {
-      {
-        // a level-2 node that another work item owns is a sibling only: empty path = inert in every pass
-        const int par = S.npar[n];
-        if (par < m) {
-          const int pp = S.rt[kRtPart + par];
-          if (level2_owner(n - S.rt[kRtBase + par], pp >> 8) != (pp & 0xff)) {
-            path[n] = (unsigned long long)par << 56;
-            S.nd[3][n] = 0.0;
-            S.wrow[n] = 0.0;
-            break;
+      if (FRESH_BUILD) {  // ---- from the build: walk the ancestor chain, lay down the path, count the memberships
+        {
+          // a level-2 node that another work item owns is a sibling only: empty path = inert in every pass
+          const int par = S.npar[n];
+          if (par < m) {
+            const int pp = S.rt[kRtPart + par];
+            if (level2_owner(n - S.rt[kRtBase + par], pp >> 8) != (pp & 0xff)) {
+              path[n] = (unsigned long long)par << 56;
+              S.nd[3][n] = 0.0;
+              S.wrow[n] = 0.0;
+              break;
+            }
           }
         }
+        unsigned long long pw = 0ull;
+        level = 1;
+        int p = n;
+        for (; p >= m; p = S.npar[p]) {  // leaf to root: the deepest atom is met first
+          const int la = S.nla[p];
+          pw = (pw << 8) | (unsigned long long)la;
+          if (kPairs) atomicAdd(&S.pcnt[la], 1);
+          gam += S.at[5][la];  // gamma_1..i (gaussvol.cpp:224: the root's gamma plus that of every atom added)
+          level++;
+        }
+        rootq = p;
+        gam += S.at[5][rootq];
+        path[n] = pw | ((unsigned long long)rootq << 56);
+        g = S.nd[4][n];
+      } else {  // ---- from a stored path: the node's Gaussian again from its atoms
+        const unsigned long long pwr = path[n];
+        if ((pwr & kPartners) == 0ull) {  // inert (a level-2 node owned by another work item)
+          S.nd[3][n] = 0.0;
+          S.wrow[n] = 0.0;
+          break;
+        }
+        rootq = (int)(pwr >> 56);
+        double A = S.at[3][rootq], cx = S.at[0][rootq], cy = S.at[1][rootq], cz = S.at[2][rootq];
+        double pv = S.at[4][rootq], pa = A, E = 0.0;
+        gam = S.at[5][rootq];
+        level = 1;
+        for (unsigned long long pw = pwr & kPartners; pw; pw >>= 8) {
+          const int la = (int)(pw & 0xffull);
+          const double xk = S.at[0][la], yk = S.at[1][la], zk = S.at[2][la], ak = S.at[3][la];
+          const double dx = xk - cx, dy = yk - cy, dz = zk - cz;
+          const double inv = fast_rcp(A + ak);
+          const double wk = ak * inv;  // a_k / A_k
+          E = fma(A * wk, fma(dz, dz, fma(dy, dy, dx * dx)), E);
+          cx = fma(dx, wk, cx);  // (A c + a_k r_k) / (A + a_k)
+          cy = fma(dy, wk, cy);
+          cz = fma(dz, wk, cz);
+          A += ak;
+          pa *= ak;
+          pv *= S.at[4][la];
+          gam += S.at[5][la];
+          level++;
+        }
+        const double q = pa * fast_rcp(A * pi_power(level - 1));
+        g = pv * pow_three_halves(q) * exp_nonpositive(-E);
+        S.nd[0][n] = cx;
+        S.nd[1][n] = cy;
+        S.nd[2][n] = cz;
       }
-      unsigned long long pw = 0ull;
-      level = 1;
-      int p = n;
-      for (; p >= m; p = S.npar[p]) {  // leaf to root: the deepest atom is met first
-        const int la = S.nla[p];
-        pw = (pw << 8) | (unsigned long long)la;
-        if (kPairs) atomicAdd(&S.pcnt[la], 1);
-        gam += S.at[5][la];  // gamma_1..i (gaussvol.cpp:224: the root's gamma plus that of every atom added)
-        level++;
-      }
-      rootq = p;
-      gam += S.at[5][rootq];
-      path[n] = pw | ((unsigned long long)rootq << 56);
-      g = S.nd[4][n];
-    } else {
-      const unsigned long long pwr = path[n];
-      if ((pwr & kPartners) == 0ull) {  // inert (a level-2 node owned by another work item)
-        S.nd[3][n] = 0.0;
-        S.wrow[n] = 0.0;
-        break;
-      }
-      rootq = (int)(pwr >> 56);
-      double A = S.at[3][rootq], cx = S.at[0][rootq], cy = S.at[1][rootq], cz = S.at[2][rootq];
-      double pv = S.at[4][rootq], pa = A, E = 0.0;
-      gam = S.at[5][rootq];
-      level = 1;
-      for (unsigned long long pw = pwr & kPartners; pw; pw >>= 8) {
-        const int la = (int)(pw & 0xffull);
-        const double xk = S.at[0][la], yk = S.at[1][la], zk = S.at[2][la], ak = S.at[3][la];
-        const double dx = xk - cx, dy = yk - cy, dz = zk - cz;
-        const double inv = fast_rcp(A + ak);
-        const double wk = ak * inv;  // a_k / A_k
-        E = fma(A * wk, fma(dz, dz, fma(dy, dy, dx * dx)), E);
-        cx = fma(dx, wk, cx);  // (A c + a_k r_k) / (A + a_k)
-        cy = fma(dy, wk, cy);
-        cz = fma(dz, wk, cz);
-        A += ak;
-        pa *= ak;
-        pv *= S.at[4][la];
-        gam += S.at[5][la];
-        level++;
-      }
-      const double q = pa * fast_rcp(A * pi_power(level - 1));
-      g = pv * pow_three_halves(q) * exp_nonpositive(-E);
-      S.nd[0][n] = cx;
-      S.nd[1][n] = cy;
-      S.nd[2][n] = cz;
-    }
-    const double cp = ((level & 1) ? 1.0 : -1.0) / (double)level;
-    double sp;
-    const double sw = dev_switch(g, sp);
-    w = quantize(cp * sw * g, kQVol, det);  // (the self-volume sums are order-dependent: LDS atomics, list order)
-    S.nd[3][n] = -2.0 * cp * gam * (sp * g + sw) * g;
-    S.wrow[n] = w;
-    e_part += quantize(gam * (cp * sw * g), kQEnergy, det);  // (which nodes a lane sums depends on the forest's composition)
+      const double cp = ((level & 1) ? 1.0 : -1.0) / (double)level;
+      double sp;
+      const double sw = dev_switch(g, sp);
+      w = quantize(cp * sw * g, kQVol, det);  // (the self-volume sums are order-dependent: LDS atomics, list order)
+      S.nd[3][n] = -2.0 * cp * gam * (sp * g + sw) * g;
+      S.wrow[n] = w;
+      e_part += quantize(gam * (cp * sw * g), kQEnergy, det);  // (which nodes a lane sums depends on the forest's composition)
     } while (false);
     // The root is in every node of its tree: its self volume is the tree's sum of w (and its node count the count).
     // The lanes of a wave mostly share one root (levels are contiguous runs per tree): fold per root inside the wave
