@@ -211,6 +211,24 @@ class HipCalcAGBNPForceKernel {
     return energies;
   }
 
+  // Decomposition groups (agbnp_hip_decompose_group_host): the per-atom decomposition of every kernel in `kernels` at
+  // positions[i] (3N_i), the members that can share on the energy-only group's launches plus one plane launch per launch set.
+  // terms[i] receives AGBNP_HIP_DECOMPOSITION_TERMS planes of N_i doubles (as decompose()); the members' energies are returned.
+  static std::vector<double> decomposeGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,
+                                            const std::vector<std::vector<double>>& positions, std::vector<std::vector<double>>& terms) {
+    auto g = detail::Group::collect("decomposeGroup", kernels, "a group has 1 to 16 members", "one position array per member", true, positions);
+    terms.resize(kernels.size());
+    std::vector<double*> planes(kernels.size());
+    for (size_t i = 0; i < kernels.size(); i++) {
+      terms[i].assign((size_t)AGBNP_HIP_DECOMPOSITION_TERMS * kernels[i]->numParticles, 0.0);
+      planes[i] = terms[i].data();
+    }
+    std::vector<double> energies(kernels.size(), 0.0);
+    detail::check(agbnp_hip_decompose_group_host(g.handles.data(), (int)kernels.size(), g.pos.data(), planes.data(), energies.data()),
+                  g.handles[0]);
+    return energies;
+  }
+
   // The positions of the next evaluation are unrelated to the last ones (agbnp_hip_expect_jump): it lays the neighbour masks
   // down at its own positions first and is not withheld for the jump.
   void expectJump() {
@@ -275,6 +293,21 @@ class Binding {
     double e = 0.0;
     check(agbnp_hip_binding_energy_host(b, positions.data(), lambda, &e, &bindingEnergy));
     return e;
+  }
+  // Per-atom decomposition of the binding energy (agbnp_hip_binding_decompose_host): returns u; `terms` receives
+  // AGBNP_HIP_DECOMPOSITION_TERMS planes of N doubles in the complex's atom order, D[t][i] = T_RL[t][i] - T_own[t][own(i)] -- the
+  // complex's term of atom i minus the term of the same atom in its own sub-system alone -- which sum to u.  Withheld evaluations
+  // are repeated inside.
+  double decompose(const std::vector<double>& positions, std::vector<double>& terms) {
+    if ((int)positions.size() != 3 * numParticles) throw OpenMMException("Binding::decompose(): positions must hold 3N values");
+    terms.assign((size_t)AGBNP_HIP_DECOMPOSITION_TERMS * numParticles, 0.0);
+    double u = 0.0;
+    check(agbnp_hip_binding_decompose_host(b, positions.data(), terms.data(), &u));
+    return u;
+  }
+  // device pointers: the 4N terms and u are ADDED -- all of them or, if a member is withheld, nothing; asynchronous
+  void decomposeDevice(const double* dPositions, double* dPerAtom, double* dBindingEnergy, void* stream = nullptr) {
+    check(agbnp_hip_binding_decompose_device(b, dPositions, dPerAtom, dBindingEnergy, stream));
   }
   // device pointers: F_lambda, E_lambda and u are ADDED -- all of them or, if a member is withheld, nothing; asynchronous
   void executeDevice(const double* dPositions, double lambda, double* dForces, double* dEnergy, double* dBindingEnergy,

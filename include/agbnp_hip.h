@@ -182,7 +182,8 @@ int agbnp_hip_energy_openmm(agbnp_hip_context* ctx, const void* d_posq, int posq
  * fast+single mode the terms are FP64: the call computes what the FP64 fast mode gives, and the terms sum to THAT mode's energy
  * (which the call returns), not to the single-precision one.  The deterministic mode gives bit-identical planes from run to run.
  * Inside a stream capture the device call returns AGBNP_HIP_ERR_INVALID_ARGUMENT, launches nothing and leaves the capture
- * usable.  There is no OpenMM-buffer form and no group form: decomposition is analysis, not an MD step. */
+ * usable.  There is no OpenMM-buffer form: decomposition is analysis, not an MD step.  The group form is
+ * agbnp_hip_decompose_group() below, the decomposition of a binding energy agbnp_hip_binding_decompose_*(). */
 #define AGBNP_HIP_DECOMPOSITION_TERMS 4
 int agbnp_hip_decompose_host(agbnp_hip_context* ctx, const double* positions, double* per_atom /*[4][N]*/, double* energy);
 int agbnp_hip_decompose_device(agbnp_hip_context* ctx, const double* d_positions, double* d_per_atom /*[4][N]*/,
@@ -255,6 +256,39 @@ int agbnp_hip_energy_group(agbnp_hip_context* const* ctxs, int count, const doub
 /* The synchronous twin for host buffers: positions[i][3 n_i] read, energies[i] RETURNED.  Withheld members are repeated inside,
  * alone, as agbnp_hip_energy_host() does. */
 int agbnp_hip_energy_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* energies);
+
+/* Decomposition groups: the conjunction of agbnp_hip_decompose_device() and agbnp_hip_execute_group(), for per-atom tables that
+ * are averaged over replicas or frames and for the decomposition of a binding energy.  d_positions, d_per_atom and d_energies
+ * are HOST arrays of `count` DEVICE pointers; d_energies may be NULL altogether (no member's total is wanted).  For every member i
+ * the call does exactly what agbnp_hip_decompose_device(ctxs[i], d_positions[i], d_per_atom[i], d_energies[i], stream) would do:
+ * the four planes [4][n_i] ADDED to d_per_atom[i] and the total to *d_energies[i], both gated on THAT member's own verdict, ONE
+ * evaluation counted in that member's overflow log under its own enqueue index, the member left in the state an energy-only
+ * evaluation leaves, scalar 20 reporting 3 -- so agbnp_hip_finish(), _poll(), _wait_verdict(), _withheld_evaluations() and
+ * _expect_jump() work per member, a withheld member adds nothing and does not affect the others, and decomposition groups, energy
+ * groups, full groups and all single-context calls on the same contexts may be interleaved in any order.
+ * Arguments as for agbnp_hip_energy_group(): 1 .. AGBNP_HIP_MAX_GROUP distinct contexts on one device, no NULL pointer (but
+ * d_energies as a whole); the plane spans [4 n_i] and the energy words of different members must not overlap one another (a
+ * member's energy word must not lie inside its own planes either); otherwise AGBNP_HIP_ERR_INVALID_ARGUMENT -- overlapping planes
+ * with a message of their own --, nothing is launched and no member changes.  Position buffers may be shared.  A NULL `stream`, a
+ * caller stream and a device error half-way are handled as in agbnp_hip_execute_group().  Inside a stream capture the call is
+ * refused (AGBNP_HIP_ERR_INVALID_ARGUMENT, the capture stays usable).
+ * Launches.  A member SHARES under the conditions of agbnp_hip_energy_group().  A launch set runs the energy-only group's four
+ * launches (version 0: two), the cavity launch in the instantiation that also collects the enlarged-radius self volumes, and
+ * behind them ONE plane launch for all its members: FIVE launches (version 0: THREE), whatever its size, where the members'
+ * agbnp_hip_decompose_device() calls make five (three) EACH.  A set of one makes the member's own launches.  Every other member
+ * -- fast mode, fast+single with the single-precision option lifted for the call, deterministic mode, profiling, a six-launch
+ * context, a context captured into a graph before -- runs what agbnp_hip_decompose_device() runs for it on the same stream:
+ * correct, not faster.  Scalar 19 says how the last evaluation ran.
+ * Argument blocks.  The plane pointers travel with the plane launch, as the force and energy pointers do with theirs: the three
+ * kinds of group build the same block for a member's parity, and a steady run that mixes them rewrites nothing (scalar 21). */
+int agbnp_hip_decompose_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions,
+                              double* const* d_per_atom /*[count] x [4][N_m], ADDED*/,
+                              double* const* d_energies /*NULL, or [count] words, ADDED*/, void* stream);
+/* The synchronous twin for host buffers: positions[i][3 n_i] read, per_atom[i][4 n_i] OVERWRITTEN, energies[i] RETURNED (no NULL
+ * pointer; the members' per_atom arrays must not overlap).  Withheld members are repeated inside, alone, as
+ * agbnp_hip_decompose_host() does. */
+int agbnp_hip_decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions,
+                                   double* const* per_atom /*overwritten*/, double* energies /*[count]*/);
 
 /* A hint: the positions of the NEXT evaluation of this context are unrelated to those of the last one (another replica's
  * conformation in an exchange matrix, a restart, a Monte Carlo move).  In the five-launch mode the neighbour masks carry a skin,
@@ -335,6 +369,32 @@ int agbnp_hip_binding_energy_device(agbnp_hip_binding* b, const double* d_positi
 int agbnp_hip_binding_execute_host(agbnp_hip_binding* b, const double* positions, double lambda, double* forces, double* energy,
                                    double* binding_energy);
 int agbnp_hip_binding_energy_host(agbnp_hip_binding* b, const double* positions, double lambda, double* energy, double* binding_energy);
+/* Per-atom decomposition of a binding energy: which receptor and ligand atoms carry u.  With T_RL, T_R, T_L the four planes of
+ * agbnp_hip_decompose_*() of the complex, the receptor and the ligand at the complex's positions,
+ *   D[t][i] = T_RL[t][i] - T_own[t][own(i)],   t = 0..3, i an atom of the complex,
+ * T_own the receptor's plane at i's index in the receptor if i is a receptor atom, else the ligand's at i's index in the ligand.
+ * Every member's planes sum to its energy, so sum_{t,i} D[t][i] = u; plane t of D summed is that term's share of u.  There is no
+ * lambda.  Version 0 has plane 0 only.  per_atom is term-major: AGBNP_HIP_DECOMPOSITION_TERMS planes of N doubles, the
+ * complex's atom order.
+ *   agbnp_hip_binding_decompose_device  asynchronous; the 4 N terms are ADDED to d_per_atom and u to *d_binding_energy (may be
+ *                                       NULL) -- all of it or, if ANY of the three members' evaluations is withheld, nothing:
+ *                                       one verdict, read on the device
+ *   agbnp_hip_binding_decompose_host    synchronous; per_atom[4 N] OVERWRITTEN, *binding_energy RETURNED (may be NULL); withheld
+ *                                       evaluations are repeated inside, up to ten times, as agbnp_hip_binding_energy_host
+ * An evaluation is three steps on one stream: the gather launch of every binding evaluation, ONE agbnp_hip_decompose_group() over
+ * {complex, receptor, ligand} -- where the three share a launch set: five launches (version 0: three) -- into a staging buffer of
+ * the binding's own (made at the first decomposition call), and one combine launch, which reads the three verdicts, adds D and
+ * u, and clears the staging words whatever the verdict: 1 + 5 + 1 launches.  It is ONE binding evaluation of the one log above:
+ * the k-th binding evaluation is the k-th evaluation of each member whichever kind it is, agbnp_hip_binding_finish and
+ * _withheld_evaluations report it like the others, _expect_jump applies, and it may be interleaved with the other binding
+ * calls in any order on one stream.  Every mode works as the members' own decompositions do.  Inside a stream capture the call
+ * is refused before anything is launched.  If the members' group call fails, no combine launch is made and the staging buffer
+ * is cleared on the stream.  Not provided: a decomposition inside binding groups, an OpenMM-buffer form, residue bookkeeping --
+ * the planes are per atom, the caller sums them. */
+int agbnp_hip_binding_decompose_device(agbnp_hip_binding* b, const double* d_positions, double* d_per_atom /*[4][N], ADDED*/,
+                                       double* d_binding_energy /*may be NULL; u ADDED*/, void* stream);
+int agbnp_hip_binding_decompose_host(agbnp_hip_binding* b, const double* positions, double* per_atom /*overwritten*/,
+                                     double* binding_energy);
 int agbnp_hip_binding_finish(agbnp_hip_binding* b, void* stream, int* must_repeat);
 int agbnp_hip_binding_withheld_evaluations(const agbnp_hip_binding* b, int* indices, int capacity);
 int agbnp_hip_binding_expect_jump(agbnp_hip_binding* b);

@@ -512,6 +512,26 @@ class BindingEnergy(_Handle):
         self._call("agbnp_hip_binding_energy_device", C.c_void_p(d_positions), float(lam), _ptr(d_energy), _ptr(d_binding_energy),
                    _ptr(stream))
 
+    def decompose(self, positions):
+        """Per-atom decomposition of the binding energy (include/agbnp_hip.h, agbnp_hip_binding_decompose_host): returns
+        (terms, u) with terms a float64 array [4, N] in the order of DECOMPOSITION_TERMS and the complex's atom order,
+        terms[t, i] = T_RL[t, i] - T_own[t, own(i)] -- the complex's term of atom i minus the term of the same atom in its own
+        sub-system alone -- and terms.sum() = u.  Version 0 has the cavity plane only.  Withheld evaluations are repeated
+        inside."""
+        pos = self._positions(positions, "decompose")
+        terms = np.zeros((len(DECOMPOSITION_TERMS), self.numParticles))
+        u = C.c_double(0.0)
+        self._call("agbnp_hip_binding_decompose_host", _dp(pos), _dp(terms), C.byref(u))
+        return terms, u.value
+
+    def decompose_device(self, d_positions, d_per_atom, d_binding_energy=None, stream=None):
+        """Device-resident form of decompose(): the 4 N terms are ADDED to d_per_atom (term-major planes of N doubles) and u to
+        *d_binding_energy when it is given -- all of it or, if any member's evaluation is withheld, nothing; raw FP64 device
+        pointers (ints).  One binding evaluation in the binding's log; asynchronous, call finish().  Refused (OpenMMException)
+        inside a stream capture."""
+        self._call("agbnp_hip_binding_decompose_device", C.c_void_p(d_positions), C.c_void_p(d_per_atom), _ptr(d_binding_energy),
+                   _ptr(stream))
+
     def finish(self, stream=None):
         """Drains the stream, finishes the three members and returns the number of binding evaluations since the previous
         finish() with at least one withheld member: NOTHING of those reached the caller's buffers; run them again (withheld())."""
@@ -558,7 +578,7 @@ class _MemberView(HipCalcAGBNPForceKernel):
 
 
 # ---- groups: replica groups of kernels, binding groups of bindings --------------------------------------------------------------
-# Each of the eight entry points is: the members, checked; what crosses the C ABI, marshalled; one call; the result.
+# Each of the ten entry points is: the members, checked; what crosses the C ABI, marshalled; one call; the result.
 def _members(who, members, cls):
     """The members of a group call as a list, checked: their number, their class, each with a handle, distinct where the
     library demands it (cls._GROUP)."""
@@ -657,6 +677,33 @@ def energy_group_host(kernels, positions):
     energies = np.zeros(len(kernels))
     _check(_lib.load().agbnp_hip_energy_group_host(hs, len(kernels), pos, _dp(energies)), kernels[0]._h)
     return [float(e) for e in energies]
+
+
+def decompose_group(kernels, d_positions, d_per_atom, d_energies=None, stream=None):
+    """Decomposition groups (include/agbnp_hip.h, agbnp_hip_decompose_group): one call that enqueues a per-atom decomposition of
+    every kernel in `kernels`, the members that can share on the energy-only group's launches plus ONE plane launch per launch
+    set.  d_positions, d_per_atom, d_energies: lists of raw FP64 device pointers (ints), one per member; d_energies may be None
+    (no totals).  The planes [4, N_i] and the totals are ADDED, per member gated on its own verdict, as by each member's
+    decompose_device(); the members' plane buffers and energy words must not overlap.  Asynchronous; each member's finish()
+    reports its own withheld evaluations."""
+    kernels = _members("decompose_group", kernels, HipCalcAGBNPForceKernel)
+    hs, pos, planes, ene = _pointer_arrays("decompose_group", kernels, True, d_positions=d_positions, d_per_atom=d_per_atom,
+                                           d_energies=d_energies)
+    if pos is None or planes is None:
+        raise OpenMMException("decompose_group(): d_positions and d_per_atom are needed")
+    _check(_lib.load().agbnp_hip_decompose_group(hs, len(kernels), pos, planes, ene, _ptr(stream)), kernels[0]._h)
+
+
+def decompose_group_host(kernels, positions):
+    """Synchronous twin of decompose_group() for host buffers: positions[i] (N_i x 3) are read; returns the lists (energies,
+    terms) with terms[i] a float64 array [4, N_i] in the order of DECOMPOSITION_TERMS.  Withheld members are repeated inside."""
+    kernels = _members("decompose_group_host", kernels, HipCalcAGBNPForceKernel)
+    hs, pos, _, _ = _host_arrays("decompose_group_host", kernels, positions)
+    terms = [np.zeros((len(DECOMPOSITION_TERMS), k.numParticles)) for k in kernels]
+    planes = (C.POINTER(C.c_double) * len(kernels))(*[_dp(t) for t in terms])
+    energies = np.zeros(len(kernels))
+    _check(_lib.load().agbnp_hip_decompose_group_host(hs, len(kernels), pos, planes, _dp(energies)), kernels[0]._h)
+    return [float(e) for e in energies], terms
 
 
 def binding_execute_group(bindings, d_positions, d_lambdas, d_forces, d_energies=None, d_binding_energies=None, stream=None):

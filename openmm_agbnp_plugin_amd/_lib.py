@@ -35,6 +35,8 @@ SIGNATURES = {
     "agbnp_hip_execute_group_host": [_vpp, _i, _dpp, _dpp, _dp],
     "agbnp_hip_energy_group": [_vpp, _i, _vpp, _vpp, _vp],
     "agbnp_hip_energy_group_host": [_vpp, _i, _dpp, _dp],
+    "agbnp_hip_decompose_group": [_vpp, _i, _vpp, _vpp, _vpp, _vp],
+    "agbnp_hip_decompose_group_host": [_vpp, _i, _dpp, _dpp, _dp],
     "agbnp_hip_expect_jump": [_vp],
     "agbnp_hip_atom_order_changed": [_vp],
     "agbnp_hip_finish": [_vp, _vp, _ip],
@@ -65,6 +67,8 @@ SIGNATURES = {
     "agbnp_hip_binding_energy_device": [_vp, _vp, _d, _vp, _vp, _vp],
     "agbnp_hip_binding_execute_host": [_vp, _dp, _d, _dp, _dp, _dp],
     "agbnp_hip_binding_energy_host": [_vp, _dp, _d, _dp, _dp],
+    "agbnp_hip_binding_decompose_device": [_vp, _vp, _vp, _vp, _vp],
+    "agbnp_hip_binding_decompose_host": [_vp, _dp, _dp, _dp],
     "agbnp_hip_binding_finish": [_vp, _vp, _ip],
     "agbnp_hip_binding_withheld_evaluations": [_vp, _ip, _i],
     "agbnp_hip_binding_expect_jump": [_vp],

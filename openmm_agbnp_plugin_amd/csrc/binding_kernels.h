@@ -30,6 +30,13 @@ hipError_t launch_binding_combine(int n, const BindingVerdicts& v, double lambda
 hipError_t launch_binding_combine_energy(const BindingVerdicts& v, double lambda, double* e, double* d_energy, double* d_binding,
                                          hipStream_t st);
 
+// The per-atom decomposition of a binding (agbnp_hip_binding_decompose_*): one thread per atom of the complex, thread 0 the
+// scalars.  t_complex[4n] and t_sub[4 nr + 4 (n - nr)] (the receptor's planes, then the ligand's) and e[3] are the binding's own
+// staging words, which the members of one agbnp_hip_decompose_group ADDED to: read, and CLEARED whatever the verdict.
+// D[t][i] = t_complex[t][i] - t_own[t][own(i)] is ADDED to d_per_atom[4n], u to *d_binding (may be null).
+hipError_t launch_binding_decompose_combine(int n, int nr, const BindingVerdicts& v, const int* complex2sub, double* t_complex,
+                                            double* t_sub, double* e, double* d_per_atom, double* d_binding, hipStream_t st);
+
 // ---- Binding groups (agbnp_hip_binding_execute_group / _energy_group): the same two launches, made once for up to
 // kMaxBindingGroup bindings.  Every binding keeps the grid it would launch alone; the grids lie side by side and a workgroup finds
 // its binding by its number (first[]), as the workgroups of a replica group's launches do (group_args.h: GroupLaunch::first).

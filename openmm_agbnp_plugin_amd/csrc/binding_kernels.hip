@@ -104,6 +104,36 @@ __global__ __launch_bounds__(64) void k_binding_combine_energy(BindingVerdicts v
   if (threadIdx.x == 0) binding_scalars(binding_complete(v), lambda, e, d_energy, d_binding);
 }
 
+// ---- per-atom decomposition of a binding (agbnp_hip_binding_decompose_*): D[t][i] = T_RL[t][i] - T_own[t][own(i)] ----
+// Behind ONE agbnp_hip_decompose_group over {complex, receptor, ligand}, whose members ADDED their planes and energies to the
+// binding's staging buffer: one thread per atom i of the complex reads its four terms of the complex's planes [4][n] and of its
+// own sub-system's -- the receptor's [4][nr] at complex2sub[i], or the ligand's [4][n - nr] at complex2sub[i] - nr --, CLEARS the
+// eight words whatever the verdict, and adds the differences to the caller's planes if all three members are complete.  Thread 0
+// is also the role lane: binding_scalars with lambda = 1 and no E_lambda target reads and clears the three energies and adds u.
+// The per-atom words are read by the thread that clears them, through vector loads in front of its own vector stores; the
+// uniform words -- the verdicts (never cleared here) and the energies (atomic loads: vector loads, see binding_scalars) -- are
+// what the compiler hazard of DESIGN.md s.4n is about.  Elementwise: bit-identical from run to run where the members are.
+__global__ __launch_bounds__(256) void k_binding_decompose_combine(int n, int nr, BindingVerdicts v, const int* __restrict__ complex2sub,
+                                                                   double* t_complex, double* t_sub, double* __restrict__ e,
+                                                                   double* d_per_atom, double* __restrict__ d_binding) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool ok = binding_complete(v);
+  if (i == 0) binding_scalars(ok, 1.0, e, nullptr, d_binding);  // the role lane: u = E_RL - E_R - E_L
+  const int t = complex2sub[i];
+  const bool in_receptor = t < nr;
+  const size_t n_own = in_receptor ? (size_t)nr : (size_t)(n - nr);
+  double* own = in_receptor ? t_sub + t : t_sub + 4 * (size_t)nr + (t - nr);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const size_t a = (size_t)k * n + i, s = (size_t)k * n_own;
+    const double t_rl = t_complex[a], t_own = own[s];
+    t_complex[a] = 0.0;
+    own[s] = 0.0;
+    if (ok) d_per_atom[a] += t_rl - t_own;
+  }
+}
+
 // ---- binding groups: the same launches once for all bindings of a call (binding_kernels.h: BindingGroupArgs) ----
 static_assert(sizeof(BindingGroupMember) == 120 && sizeof(BindingGroupArgs) == 2000, "BindingGroupArgs: the size binding_kernels.h states");
 static_assert(sizeof(BindingGroupArgs) <= 4096, "a kernel's arguments take 4096 bytes at most");
@@ -169,6 +199,13 @@ hipError_t launch_binding_combine(int n, const BindingVerdicts& v, double lambda
 hipError_t launch_binding_combine_energy(const BindingVerdicts& v, double lambda, double* e, double* d_energy, double* d_binding,
                                          hipStream_t st) {
   hipLaunchKernelGGL(k_binding_combine_energy, dim3(1), dim3(64), 0, st, v, lambda, e, d_energy, d_binding);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_decompose_combine(int n, int nr, const BindingVerdicts& v, const int* complex2sub, double* t_complex,
+                                            double* t_sub, double* e, double* d_per_atom, double* d_binding, hipStream_t st) {
+  hipLaunchKernelGGL(k_binding_decompose_combine, dim3((n + 255) / 256), dim3(256), 0, st, n, nr, v, complex2sub, t_complex, t_sub, e,
+                     d_per_atom, d_binding);
   return hipGetLastError();
 }
 

@@ -127,13 +127,40 @@ __global__ __launch_bounds__(256) void k_decompose(PairArgs P, int version, int 
   decompose_tile<kCut>(P, (int)blockIdx.x - role_blocks, per_atom + 3 * (size_t)P.n);
 }
 
+// Decomposition groups (agbnp_hip_decompose_group; group_args.h, engine_group.hip): the plane launch of every member of a launch
+// set in one grid.  A workgroup finds its member and its number inside that member's grid (group_index) and does there what
+// k_decompose's workgroup of that number does, on the member's PairArgs out of its argument block: the member's first
+// ceil(n / 256) workgroups are role workgroups, the rest are tiles.  Gated on that member's own verdict words.  Sharing members
+// run the Reference semantics with the host-named set: no cutoff instantiation, no parity rebase.  The plane pointers travel in
+// the launch's argument (GroupPlanes): the blocks are not touched.
+__global__ __launch_bounds__(256) void k_group_decompose(GroupLaunch G, GroupPlanes O, int version) {
+  int blk;
+  const int m = group_index(G, blk);
+  const PairArgs& P = group_args(G, m).P;
+  if (evaluation_overflowed(P.estatus)) return;  // this member's evaluation was withheld: it adds nothing
+  double* __restrict__ per_atom = reinterpret_cast<double*>(O.per_atom[m]);
+  const int role_blocks = (P.n + 255) / 256;
+  if (blk < role_blocks) return decompose_atoms(P, version, blk * 256 + (int)threadIdx.x, per_atom);
+  decompose_tile<false>(P, blk - role_blocks, per_atom + 3 * (size_t)P.n);
+}
+
+// workgroups of a context's plane launch: the role workgroups, then (version 1) the tiles
+int decompose_blocks(int n, int version) {
+  const int nb = (n + 63) / 64;
+  return (n + 255) / 256 + (version == 1 ? nb * (nb + 1) / 2 : 0);
+}
+
+hipError_t launch_group_decompose(const GroupLaunch& G, const GroupPlanes& O, int version, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_decompose, dim3(G.first[G.count]), dim3(256), 0, st, G, O, version);
+  return hipGetLastError();
+}
+
 hipError_t launch_decompose(const PairArgs& P, int version, double* per_atom, hipStream_t st, Timeline* tl) {
   if (tl) {
     hipError_t m = tl->mark(kKDecompose, st);
     if (m != hipSuccess) return m;
   }
-  const int role_blocks = (P.n + 255) / 256, nb = (P.n + 63) / 64;
-  const int tiles = version == 1 ? nb * (nb + 1) / 2 : 0;
+  const int role_blocks = (P.n + 255) / 256, tiles = decompose_blocks(P.n, version) - role_blocks;
   if (P.fast)
     hipLaunchKernelGGL(k_decompose<true>, dim3(role_blocks + tiles), dim3(256), 0, st, P, version, role_blocks, per_atom);
   else

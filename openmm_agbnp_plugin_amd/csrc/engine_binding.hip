@@ -38,6 +38,11 @@ struct agbnp_hip_binding {
   // the host forms stage their lambdas in (both made on first use, by the call's first binding)
   hipEvent_t group_event = nullptr;
   DevBuf<double> d_group_lambdas;
+  // per-atom decompositions (agbnp_hip_binding_decompose_*), both made at the first call that needs them.  d_planes: [4n] the
+  // complex's planes | [4 nr + 4 nl] the receptor's and the ligand's | [3] the three energies -- what the members of the
+  // decomposition group ADD to, cleared by every combine launch.  d_decomp: the host form's staging, [3n] positions | [4n] D | u
+  DevBuf<double> d_planes, d_decomp;
+  std::vector<double> h_decomp;  // [4n + 1] D and u, read back
 
   double* sub_pos() const { return d_work.p; }
   double* f_complex() const { return d_work.p + 3 * (size_t)n; }
@@ -181,6 +186,41 @@ int binding_enqueue(agbnp_hip_binding* const* bs, int count, const double* const
   return AGBNP_HIP_OK;
 }
 
+// One per-atom decomposition of b on `stream` (NULL: the complex's own); the arguments have been checked.  The gather launch, ONE
+// agbnp_hip_decompose_group over the three members through the public entry point -- their planes and energies into d_planes --
+// and the combine launch, which reads the three verdicts and adds D and u all or nothing.
+int binding_decompose_enqueue(agbnp_hip_binding* b, const double* d_pos, double* d_per_atom, double* d_binding, void* stream,
+                              const char* who) {
+  clear_member_errors(b);
+  hipStream_t st;
+  if (enter(b->m[0], stream, &st) != AGBNP_HIP_OK) return member_fail(b, AGBNP_HIP_ERR_DEVICE, who);
+  if (is_capturing(st))
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                        std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
+  const size_t n = (size_t)b->n, nr = (size_t)b->nr, words = 8 * n + kBindingMembers;
+  if (b->d_planes.p == nullptr) {
+    BINDING_TRY(who, b->d_planes.alloc(words));
+    BINDING_TRY(who, hipMemsetAsync(b->d_planes.p, 0, sizeof(double) * words, st));
+  }
+  double* const planes = b->d_planes.p;
+  double* const e = planes + 8 * n;
+  BINDING_TRY(who, launch_binding_gather(b->n, d_pos, b->d_maps.p, b->sub_pos(), st));
+  const double* const pos[kBindingMembers] = {d_pos, b->sub_pos(), b->sub_pos() + 3 * nr};
+  double* const per_atom[kBindingMembers] = {planes, planes + 4 * n, planes + 4 * n + 4 * nr};
+  double* const ene[kBindingMembers] = {e, e + 1, e + 2};
+  // (a NULL stream is the group's first member's own: the complex's, `st`)
+  const int rc = agbnp_hip_decompose_group(b->m, kBindingMembers, pos, per_atom, ene, stream);
+  if (rc != AGBNP_HIP_OK) {
+    // no combine launch will read and clear what the members that got as far as their launches added: cleared here, as the
+    // force path does
+    (void)hipMemsetAsync(planes, 0, sizeof(double) * words, st);
+    return member_fail(b, rc, who);
+  }
+  BINDING_TRY(who, launch_binding_decompose_combine(b->n, b->nr, binding_verdicts(b), b->d_maps.p + n, planes, planes + 4 * n, e,
+                                                    d_per_atom, d_binding, st));
+  return AGBNP_HIP_OK;
+}
+
 // a device entry point has enqueued an evaluation of b on `stream`
 void binding_note(agbnp_hip_binding* b, void* stream) {
   b->enqueued++;
@@ -224,6 +264,35 @@ int binding_carry(agbnp_hip_binding* b, const char* who) {
   b->carried_seq += b->enqueued;
   b->enqueued = 0;
   return AGBNP_HIP_OK;
+}
+
+// agbnp_hip_binding_decompose_host: the device path on the binding's staging buffer and the complex's own stream; a withheld
+// evaluation is repeated here, as binding_host repeats
+int binding_decompose_host(agbnp_hip_binding* b, const double* pos, double* per_atom, double* binding_energy, const char* who) {
+  int rc = binding_carry(b, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  BINDING_TRY(who, hipSetDevice(b->device));
+  const hipStream_t st = b->m[0]->stream;
+  const size_t n3 = 3 * (size_t)b->n, n4 = 4 * (size_t)b->n;
+  if (b->d_decomp.p == nullptr) BINDING_TRY(who, b->d_decomp.alloc(n3 + n4 + 1));
+  b->h_decomp.resize(n4 + 1);
+  double* const d_out = b->d_decomp.p + n3;
+  for (int attempt = 0; attempt < 10; attempt++) {
+    BINDING_TRY(who, hipMemcpyAsync(b->d_decomp.p, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
+    BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (n4 + 1), st));
+    rc = binding_decompose_enqueue(b, b->d_decomp.p, d_out, d_out + n4, nullptr, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+    BINDING_TRY(who, hipMemcpyAsync(b->h_decomp.data(), d_out, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, st));
+    std::vector<int> bad;
+    int count = 0;
+    rc = binding_harvest(b, nullptr, bad, &count, who);  // (waits for the stream)
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (count) continue;
+    std::memcpy(per_atom, b->h_decomp.data(), sizeof(double) * n4);
+    if (binding_energy) *binding_energy = b->h_decomp[n4];
+    return AGBNP_HIP_OK;
+  }
+  return binding_fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
 }
 
 // The host entry points' evaluation, on the first complex's own stream: every binding's staging buffers made on first use, its
@@ -492,6 +561,24 @@ int agbnp_hip_binding_energy_host(agbnp_hip_binding* b, const double* positions,
   if (!positions || (!energy && !binding_energy)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
   if (!std::isfinite(lambda)) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": lambda must be finite");
   return binding_host(b, positions, lambda, nullptr, energy, binding_energy, who);
+}
+
+int agbnp_hip_binding_decompose_device(agbnp_hip_binding* b, const double* d_positions, double* d_per_atom, double* d_binding_energy,
+                                       void* stream) {
+  const char* who = "agbnp_hip_binding_decompose_device";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_positions || !d_per_atom) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  const int rc = binding_decompose_enqueue(b, d_positions, d_per_atom, d_binding_energy, stream, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  binding_note(b, stream);
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_binding_decompose_host(agbnp_hip_binding* b, const double* positions, double* per_atom, double* binding_energy) {
+  const char* who = "agbnp_hip_binding_decompose_host";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!positions || !per_atom) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  return binding_decompose_host(b, positions, per_atom, binding_energy, who);
 }
 
 int agbnp_hip_binding_execute_group(agbnp_hip_binding* const* bindings, int count, const double* const* d_positions, const double* d_lambdas,

@@ -323,6 +323,7 @@ struct EvalRequest {
   hipStream_t stream = nullptr;
   bool energy_only = false;
   bool sv_large = false;         // the cavity launch also collects the enlarged-radius self volumes (a decomposition: row kHvSvLarge)
+  double* per_atom = nullptr;    // a decomposition group's member (engine_group.hip): its planes [4][n], added to by the plane launch
   double* zero_out = nullptr;    // the host entry points' staging buffer, cleared first (PairArgs::zero_out)
   OpenmmSource in;               // agbnp_hip_execute_openmm / agbnp_hip_energy_openmm: the context's posq ...
   OpenmmTargets omm;             // ... and its fixed-point planes and energy accumulator
@@ -349,6 +350,7 @@ ENGINE_LOCAL int harvest(agbnp_hip_context* c, int* repeat, hipStream_t st);
 ENGINE_LOCAL int catch_up(agbnp_hip_context* c);
 ENGINE_LOCAL int carry_unfinished(agbnp_hip_context* c);
 ENGINE_LOCAL int host_evaluation(agbnp_hip_context* c, const double* pos, double* forces, double* energy);
+ENGINE_LOCAL int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy);
 
 // ---- engine_group.hip (what replica groups and binding groups both need)
 ENGINE_LOCAL bool spans_overlap(const double* a, size_t na, const double* b, size_t nb);  // two output spans; a null one overlaps nothing

@@ -471,6 +471,8 @@ int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int po
   r.omm.energy_slot = energy_slot;
   return enqueue(c, r);
 }
+}  // namespace
+
 // Per-atom decomposition (agbnp_hip_decompose_*): ONE evaluation in the context's overflow log -- the energy-only evaluation of the
 // context (energy_only_fast: its four / two launches; elsewhere the full evaluation with its forces sent to d_eo_force) with the
 // cavity launch's instantiation that also collects the enlarged-radius self volumes -- and behind it, on the same stream, the one
@@ -480,7 +482,7 @@ int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int po
 // fast+single: the terms are FP64 (header), so the evaluation runs with the single-precision option lifted for this call -- the
 // same lists and masks (the reach is the fast mode's), other pair-term arithmetic; kernel arguments travel by value, so nothing
 // enqueued before or after is affected.
-int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, double* d_per_atom, double* d_energy, hipStream_t st) {
+static int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, double* d_per_atom, double* d_energy, hipStream_t st) {
   EvalRequest r;
   r.pos = d_pos;
   r.force = c->d_eo_force.p;
@@ -513,6 +515,7 @@ int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, double* d_p
 }
 
 // agbnp_hip_decompose_host: the planes and the energy travel back in one buffer; withheld evaluations are repeated
+// (also how agbnp_hip_decompose_group_host repeats a member whose evaluation was withheld)
 int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy) {
   HIP_TRY(c, hipSetDevice(c->device));
   const int rc0 = carry_unfinished(c);
@@ -536,7 +539,6 @@ int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom
   }
   return c->fail(AGBNP_HIP_ERR_CAPACITY, "agbnp_hip_decompose_host: capacity negotiation did not converge");
 }
-}  // namespace
 
 extern "C" {
 

@@ -27,8 +27,11 @@ bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, const EvalRe
 // The arguments of a group call, checked before anything is launched or changed.  forces is null for an energy-only call
 // (energy_only says that this was asked for).  d_energies: the device entry points' energy words, one buffer per member, which --
 // like the force buffers [3n] -- must not overlap those of another member; the host entry points pass null.
+// planes: a decomposition group's plane buffers [4n], one per member (null for every other kind of call); they must not overlap
+// one another or an energy word -- said in a message of its own -- and the device form's energies may then be null altogether.
 int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* pos, double* const* forces, bool energy_only,
-                const void* energies, double* const* d_energies, const char* who) {
+                const void* energies, double* const* d_energies, const char* who, double* const* planes = nullptr,
+                bool planes_wanted = false, bool energies_optional = false) {
   if (!ctxs || count < 1 || count > kMaxGroup) {
     if (ctxs && count >= 1 && ctxs[0]) ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a group has 1 to 16 members");
     return AGBNP_HIP_ERR_INVALID_ARGUMENT;
@@ -36,15 +39,25 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* 
   for (int i = 0; i < count; i++)
     if (!ctxs[i]) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   agbnp_hip_context* c0 = ctxs[0];
-  if (!pos || (!forces && !energy_only) || !energies) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (!pos || (!forces && !energy_only) || (!energies && !energies_optional) || (planes_wanted && !planes))
+    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
   for (int i = 0; i < count; i++) {
     if (ctxs[i]->device != c0->device) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": members on different devices");
     for (int j = 0; j < i; j++)
       if (ctxs[j] == ctxs[i]) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the same context twice");
   }
   for (int i = 0; i < count; i++) {
-    if (!pos[i] || (forces && !forces[i]) || (d_energies && !d_energies[i]))
+    if (!pos[i] || (forces && !forces[i]) || (d_energies && !d_energies[i]) || (planes && !planes[i]))
       return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    for (int j = 0; j < i && planes; j++) {
+      const size_t ni = 4 * (size_t)ctxs[i]->n, nj = 4 * (size_t)ctxs[j]->n;
+      bool clash = spans_overlap(planes[i], ni, planes[j], nj);
+      if (d_energies) clash = clash || spans_overlap(planes[i], ni, d_energies[j], 1) || spans_overlap(d_energies[i], 1, planes[j], nj);
+      if (clash) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": plane buffers of two members overlap");
+    }
+    // (a member's own energy word inside its own planes)
+    if (planes && d_energies && spans_overlap(planes[i], 4 * (size_t)ctxs[i]->n, d_energies[i], 1))
+      return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": plane buffers of two members overlap");
     for (int j = 0; j < i && d_energies; j++) {
       const size_t ni = 3 * (size_t)ctxs[i]->n, nj = 3 * (size_t)ctxs[j]->n;
       bool clash = spans_overlap(d_energies[i], 1, d_energies[j], 1);
@@ -64,17 +77,23 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* 
 // instantiation, the three role workgroups per member --, version 0 the cavity launch and the output launch in its force-less
 // shape.  Both kinds of call build the SAME argument block for a member's parity (the block holds no output pointer, and what
 // the energy-only launches read of it a full call fills too), so a run that mixes them rewrites nothing.
+// A decomposition group (agbnp_hip_decompose_group; the requests carry sv_large and per_atom) is an energy-only set whose cavity
+// launch is the instantiation that also collects the enlarged-radius self volumes, with ONE more launch behind it: the planes of
+// every member (decompose_kernels.hip: k_group_decompose; FIVE launches, version 0 three).  The same blocks again.
 int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, const EvalRequest* reqs) {
-  const bool energy_only = reqs[set[0]].energy_only;
+  const bool energy_only = reqs[set[0]].energy_only, decomposition = reqs[set[0]].per_atom != nullptr;
   const hipStream_t st = reqs[set[0]].stream;
   agbnp_hip_context* const c0 = ctxs[set[0]];
   const int version = c0->version, variant = c0->variant;
   // version 1: cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes (energy-only: cavity, Born rows, GB tiles, roles); 0: cavity, outputs
   const int stages = version == 1 ? (energy_only ? 4 : 5) : 2;
-  GroupLaunch G[5];
+  GroupLaunch G[5], Gplanes;  // (Gplanes: the plane launch of a decomposition group, behind the energy-only stages)
   GroupOutputs out;
+  GroupPlanes planes;
   std::memset(G, 0, sizeof(G));
+  std::memset(&Gplanes, 0, sizeof(Gplanes));
   std::memset(&out, 0, sizeof(out));
+  std::memset(&planes, 0, sizeof(planes));
   size_t lds[5] = {tree_variant_lds_bytes(variant), 0, 0, 0, tree_variant_replay_bytes(variant)};
   for (int k = 0; k < m; k++) {
     const int i = set[k];
@@ -121,6 +140,9 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
     }
     out.force[k] = energy_only ? 0ull : (unsigned long long)(uintptr_t)reqs[i].force;
     out.energy[k] = (unsigned long long)(uintptr_t)reqs[i].energy;
+    Gplanes.first[k + 1] = Gplanes.first[k] + decompose_blocks(c->n, version);
+    Gplanes.args[k] = addr;
+    planes.per_atom[k] = (unsigned long long)(uintptr_t)reqs[i].per_atom;
     if (version == 1) {
       lds[1] = std::max(lds[1], sh.born_lds);
       lds[3] = std::max(lds[3], sh.chain_lds);
@@ -128,21 +150,24 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       lds[1] = std::max(lds[1], (size_t)sh.out_masks.role_bytes);
     }
     c->group_members = m;
-    c->last_kind = energy_only ? 1 : 0;
+    c->last_kind = decomposition ? 3 : energy_only ? 1 : 0;
   }
   for (int s = 0; s < stages; s++) G[s].count = m;
-  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st));
+  Gplanes.count = m;
+  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st, reqs[set[0]].sv_large));
   if (version == 0) {
     if (energy_only)
       HIP_TRY(c0, launch_group_outputs_energy(G[1], out, lds[1], st));
     else
       HIP_TRY(c0, launch_group_outputs(G[1], out, lds[1], st));
+    if (decomposition) HIP_TRY(c0, launch_group_decompose(Gplanes, planes, version, st));
     return AGBNP_HIP_OK;
   }
   HIP_TRY(c0, launch_group_born_rows(G[1], lds[1], st));
   if (energy_only) {
     HIP_TRY(c0, launch_group_gb_energy(c0->P.gb_far, G[2], st));
     HIP_TRY(c0, launch_group_energy_roles(G[3], out, lds[3], st));
+    if (decomposition) HIP_TRY(c0, launch_group_decompose(Gplanes, planes, version, st));
     return AGBNP_HIP_OK;
   }
   HIP_TRY(c0, launch_group_gb(c0->P.gb_far, G[2], st));
@@ -156,7 +181,38 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
 // reached get back the counts their enqueue_prepare advanced (enqueue index, five-launch set parity), so that host and device keep
 // counting alike; a member whose launches failed half-way is in the state a failed agbnp_hip_execute_device leaves
 // (AGBNP_HIP_ERR_DEVICE: recreate it).  A member that does not share runs what its own entry point would run for its request.
+// A decomposition group's member that runs alone -- by itself or as a launch set of one -- runs what enqueue_decomposition
+// (engine_eval.hip) runs for it: its evaluation with the sv_large cavity instantiation, then its own plane launch; fast+single
+// with the single-precision option lifted for this call (LiftSingle), as there.
+int member_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest& r) {
+  const int rc = enqueue_launch(c, plan, r);
+  if (rc != AGBNP_HIP_OK || !r.per_atom) return rc;
+  const hipError_t e = launch_decompose(c->P, c->version, r.per_atom, r.stream, c->timeline.enabled ? &c->timeline : nullptr);
+  c->last_kind = 3;
+  return e == hipSuccess ? AGBNP_HIP_OK : c->hipfail(e, "launch_decompose");
+}
+
+// the members of a decomposition group in the fast+single mode: FP64 terms, so the option is off from before their
+// enqueue_prepare until their requests have left the argument blocks (declared in front of the Unbind: destroyed behind it)
+struct LiftSingle {
+  agbnp_hip_context* lifted[kMaxGroup];
+  int count = 0;
+  void lift(agbnp_hip_context* c) {
+    if (!(c->mode & AGBNP_HIP_MODE_SINGLE)) return;
+    c->mode &= ~AGBNP_HIP_MODE_SINGLE;
+    derive_args(c);
+    lifted[count++] = c;
+  }
+  ~LiftSingle() {
+    for (int i = 0; i < count; i++) {
+      lifted[i]->mode |= AGBNP_HIP_MODE_SINGLE;
+      derive_args(lifted[i]);
+    }
+  }
+};
+
 int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* reqs) {
+  LiftSingle single;
   const Unbind unbind{ctxs, count};
   EvalPlan plans[kMaxGroup];
   bool shares[kMaxGroup], done[kMaxGroup], launched[kMaxGroup] = {};
@@ -170,6 +226,7 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* 
     agbnp_hip_context* const c = ctxs[i];
     was_enqueued[i] = c->enqueued;
     was_five_evals[i] = c->five_evals;
+    if (reqs[i].per_atom) single.lift(c);
     const int rc = enqueue_prepare(c, reqs[i], plans[i]);
     prepared = i + 1;
     if (rc != AGBNP_HIP_OK) return undo(rc);
@@ -187,14 +244,14 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* 
     for (int k = 0; k < m; k++) launched[set[k]] = true;
     // (a launch set of one makes the member's own launches: the same kernels without the look-up of its argument block, which
     // costs a dependent scalar load in front of every launch's first use of an argument)
-    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, reqs) : enqueue_launch(ctxs[set[0]], plans[set[0]], reqs[set[0]]);
+    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, reqs) : member_launch(ctxs[set[0]], plans[set[0]], reqs[set[0]]);
     if (rc != AGBNP_HIP_OK) return undo(rc);
     if (m == 1) ctxs[set[0]]->group_members = 1;
   }
   for (int i = 0; i < count; i++) {
     if (shares[i]) continue;
     launched[i] = true;
-    const int rc = enqueue_launch(ctxs[i], plans[i], reqs[i]);
+    const int rc = member_launch(ctxs[i], plans[i], reqs[i]);
     if (rc != AGBNP_HIP_OK) return undo(rc);
   }
   return AGBNP_HIP_OK;
@@ -202,9 +259,11 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* 
 
 // agbnp_hip_execute_group and -- energy_only, d_forces null: for every member what agbnp_hip_energy_device would do, the sharing
 // members on FOUR (version 0: two) launches per launch set, nothing written to a force buffer of a caller -- agbnp_hip_energy_group
+// and -- decomposition: energy_only with d_planes, d_energies may be null: for every member what agbnp_hip_decompose_device would
+// do, the sharing members on FIVE (version 0: three) launches per launch set -- agbnp_hip_decompose_group
 int group_device(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces, bool energy_only,
-                 double* const* d_energies, void* stream, const char* who) {
-  int rc = check_group(ctxs, count, d_positions, d_forces, energy_only, d_energies, d_energies, who);
+                 double* const* d_energies, void* stream, const char* who, double* const* d_planes = nullptr, bool decomposition = false) {
+  int rc = check_group(ctxs, count, d_positions, d_forces, energy_only, d_energies, d_energies, who, d_planes, decomposition, decomposition);
   if (rc != AGBNP_HIP_OK) return rc;
   agbnp_hip_context* const c0 = ctxs[0];
   hipStream_t st;
@@ -212,7 +271,8 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const double* const*
   if (rc != AGBNP_HIP_OK) return rc;
   if (is_capturing(st))
     return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream is being captured; " +
-                                                        (energy_only ? "groups and energy-only evaluations" : "groups") + " are not captured into graphs");
+                                                        (decomposition ? "groups and decompositions" : energy_only ? "groups and energy-only evaluations" : "groups") +
+                                                        " are not captured into graphs");
   EvalRequest reqs[kMaxGroup];
   for (int i = 0; i < count; i++) {
     agbnp_hip_context* const c = ctxs[i];
@@ -223,9 +283,12 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const double* const*
     if (!stream) HIP_TRY(c, join_streams(c->group_event, c->stream, st));
     reqs[i].pos = d_positions[i];
     reqs[i].force = energy_only ? c->d_eo_force.p : d_forces[i];
-    reqs[i].energy = d_energies[i];
+    // (a decomposition without energy words: into the member's spare word, as agbnp_hip_decompose_device)
+    reqs[i].energy = d_energies ? d_energies[i] : c->d_energy_tmp.p;
     reqs[i].stream = st;
     reqs[i].energy_only = energy_only;
+    reqs[i].sv_large = decomposition;
+    reqs[i].per_atom = decomposition ? d_planes[i] : nullptr;
   }
   rc = group_enqueue(ctxs, count, reqs);
   if (rc != AGBNP_HIP_OK) return rc;
@@ -278,9 +341,62 @@ int group_host(agbnp_hip_context* const* ctxs, int count, const double* const* p
   }
   return AGBNP_HIP_OK;
 }
+
+// agbnp_hip_decompose_group_host: every member's planes and energy through its own staging buffer [4n + 1], cleared first (the
+// device path ADDS); a member whose evaluation was withheld is repeated alone, as agbnp_hip_decompose_host repeats
+int decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* per_atom,
+                         double* energies, const char* who) {
+  int rc = check_group(ctxs, count, positions, nullptr, true, energies, nullptr, who, per_atom, true);
+  if (rc != AGBNP_HIP_OK) return rc;
+  const hipStream_t st = ctxs[0]->stream;
+  EvalRequest reqs[kMaxGroup];
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = carry_unfinished(c);  // (every member's streams are idle from here on)
+    if (rc != AGBNP_HIP_OK) return rc;
+    const size_t n4 = 4 * (size_t)c->n;
+    if (c->d_decomp.count != n4 + 1) HIP_TRY(c, c->d_decomp.alloc(n4 + 1));
+    c->h_decomp.resize(n4 + 1);
+    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->d_decomp.p, 0, sizeof(double) * (n4 + 1), st));
+    reqs[i].pos = c->d_pos_in.p;
+    reqs[i].force = c->d_eo_force.p;
+    reqs[i].energy = c->d_decomp.p + n4;
+    reqs[i].stream = st;
+    reqs[i].energy_only = true;
+    reqs[i].sv_large = true;
+    reqs[i].per_atom = c->d_decomp.p;
+  }
+  rc = group_enqueue(ctxs, count, reqs);
+  if (rc != AGBNP_HIP_OK) return rc;
+  for (int i = 0; i < count; i++) {
+    agbnp_hip_context* const c = ctxs[i];
+    const size_t n4 = 4 * (size_t)c->n;
+    HIP_TRY(c, hipMemcpyAsync(c->h_decomp.data(), c->d_decomp.p, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, st));
+    int repeat = 0;
+    rc = harvest(c, &repeat, st);  // (waits for the group's stream)
+    if (rc == AGBNP_HIP_OK && repeat) rc = host_decomposition(c, positions[i], per_atom[i], &energies[i]);
+    if (rc != AGBNP_HIP_OK) return rc;
+    if (repeat) continue;
+    std::memcpy(per_atom[i], c->h_decomp.data(), sizeof(double) * n4);
+    energies[i] = c->h_decomp[n4];
+  }
+  return AGBNP_HIP_OK;
+}
 }  // namespace
 
 extern "C" {
+
+int agbnp_hip_decompose_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_per_atom,
+                              double* const* d_energies, void* stream) {
+  return group_device(ctxs, count, d_positions, nullptr, true, d_energies, stream, "agbnp_hip_decompose_group", d_per_atom, true);
+}
+
+int agbnp_hip_decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* per_atom,
+                                   double* energies) {
+  return decompose_group_host(ctxs, count, positions, per_atom, energies, "agbnp_hip_decompose_group_host");
+}
 
 int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,
                             double* const* d_energies, void* stream) {

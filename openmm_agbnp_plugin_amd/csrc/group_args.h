@@ -66,7 +66,14 @@ struct GroupOutputs {
   unsigned long long force[kMaxGroup], energy[kMaxGroup];
 };
 
-hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st);
+// The members' plane buffers of a decomposition group (agbnp_hip_decompose_group): [4][N_m] each, a kernel argument of the plane
+// launch alone -- like GroupOutputs, so that the members' argument blocks stay what a full or an energy-only group writes.
+struct GroupPlanes {
+  unsigned long long per_atom[kMaxGroup];
+};
+
+// (sv_large: the instantiations that also collect the enlarged-radius self volumes -- a decomposition group's cavity launch)
+hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large = false);
 hipError_t launch_group_pseudo(int variant, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
 hipError_t launch_group_born_rows(const GroupLaunch& G, size_t lds, hipStream_t st);
 hipError_t launch_group_gb(int gb_far, const GroupLaunch& G, hipStream_t st);
@@ -77,6 +84,10 @@ hipError_t launch_group_gb_energy(int gb_far, const GroupLaunch& G, hipStream_t 
 hipError_t launch_group_energy_roles(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
 hipError_t launch_group_outputs_energy(const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
 hipError_t launch_group_put(const GroupMemberArgs& a, GroupMemberArgs* dst, hipStream_t st);
+// decomposition groups (agbnp_hip_decompose_group; decompose_kernels.hip): the ONE plane launch behind an energy-only launch set,
+// every member's grid of decompose_blocks(n, version) workgroups side by side
+int decompose_blocks(int n, int version);
+hipError_t launch_group_decompose(const GroupLaunch& G, const GroupPlanes& O, int version, hipStream_t st);
 
 #ifdef __HIP_DEVICE_COMPILE__
 typedef const __attribute__((address_space(4))) GroupMemberArgs* GroupArgsPtr;

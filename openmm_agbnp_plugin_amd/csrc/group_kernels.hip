@@ -127,11 +127,18 @@ hipError_t launch_group_put(const GroupMemberArgs& a, GroupMemberArgs* dst, hipS
 // ---- replica groups (group_args.h): the cavity and pseudo-volume launches of several contexts in one grid --------------------
 // The instantiations of the five-launch mode with the host-named set (eager launches) and, for the pseudo-volume launch, the
 // forces leaving with it: what a sharing member would launch alone.
-template <int NCAP, int ACAP, int BS>
-__global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_group_cavity_five(GroupLaunch G) {
+// SV1: the instantiations of a decomposition group (agbnp_hip_decompose_group), which also collect the enlarged-radius self
+// volumes, as k_tree_cavity_five's own SV1 instantiations do for one context
+// At four waves per SIMD (128 VGPRs) the SV1 forms of the two smallest stores park two registers in scratch, as
+// k_tree_cavity_five's do; these are asked for three (168 VGPRs) and keep everything in registers.  The 512-node store's four
+// workgroups per CU are three waves per SIMD as it is; the 432-node store then holds four workgroups per CU where the other
+// launches hold five -- a decomposition of a system with more than 1024 forests runs its cavity launch in more rounds.
+constexpr int group_cavity_waves(int ncap, bool sv1) { return sv1 && ncap <= 512 ? 3 : tree_waves_per_simd(ncap); }
+template <int NCAP, int ACAP, int BS, bool SV1>
+__global__ __launch_bounds__(BS, group_cavity_waves(NCAP, SV1)) void k_group_cavity_five(GroupLaunch G) {
   int blk;
   const GroupMemberArgs& g = group_member(G, blk);
-  k_tree_cavity_five<NCAP, ACAP, BS, false, false>(g.T, g.P, g.tree_blocks, (unsigned)blk, 0u);
+  k_tree_cavity_five<NCAP, ACAP, BS, false, false, SV1>(g.T, g.P, g.tree_blocks, (unsigned)blk, 0u);
 }
 template <int NCAP, int ACAP, int BS, bool PIPE>
 __global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_group_pseudo(GroupLaunch G, GroupOutputs O) {
@@ -154,13 +161,15 @@ static hipError_t launch_group(K kernel, const GroupLaunch& G, size_t lds, hipSt
   return hipGetLastError();
 }
 
-hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st) {
+hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large) {
   return with_tree_variant(variant, [&](auto v) {
     using V = decltype(v);
     if constexpr (V::kGlobal)
       return hipErrorInvalidValue;
+    else if (sv_large)
+      return launch_group(k_group_cavity_five<V::kNodeCap, V::kAtomCap, kBS, true>, G, lds, st);
     else
-      return launch_group(k_group_cavity_five<V::kNodeCap, V::kAtomCap, kBS>, G, lds, st);
+      return launch_group(k_group_cavity_five<V::kNodeCap, V::kAtomCap, kBS, false>, G, lds, st);
   });
 }
 
