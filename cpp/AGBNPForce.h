@@ -189,6 +189,34 @@ class HipCalcAGBNPForceKernel {
     return e;
   }
 
+  // The partition that pairMatrix() tabulates (agbnp_hip_set_atom_sets): sets[i] in 0 .. numSets - 1 is the set of atom i (its
+  // residue, its chain, receptor or ligand); numSets < 0: the largest index + 1.  Checked before the library is touched; replaces
+  // an earlier partition and survives copyParametersToContext().
+  void setAtomSets(const std::vector<int>& sets, int numSets = -1) {
+    need();
+    if ((int)sets.size() != numParticles) throw OpenMMException("setAtomSets(): one set index per atom is needed");
+    int lowest = 0, highest = -1;
+    for (int s : sets) lowest = s < lowest ? s : lowest, highest = s > highest ? s : highest;
+    if (numSets < 0) numSets = highest + 1;
+    if (numSets < 1 || numSets > AGBNP_HIP_MAX_SETS) throw OpenMMException("setAtomSets(): numSets must be 1 .. AGBNP_HIP_MAX_SETS");
+    if (lowest < 0 || highest >= numSets) throw OpenMMException("setAtomSets(): every set index must be 0 .. numSets - 1");
+    check(agbnp_hip_set_atom_sets(ctx, numParticles, sets.data(), numSets));
+  }
+  int numAtomSets() const { return ctx ? agbnp_hip_num_atom_sets(ctx) : 0; }
+
+  // Set-pair interaction matrix of the energy at these positions (agbnp_hip_pair_matrix_host): returns the energy; `matrix`
+  // receives M[S][S], row-major, over the sets of setAtomSets() -- M[a][b] = M[b][a] half the GB pair energy between sets a and b,
+  // M[a][a] what set a holds in itself -- whose sum over everything is the energy.  No forces are written.
+  double pairMatrix(const std::vector<double>& positions, std::vector<double>& matrix) {
+    need();
+    if ((int)positions.size() != 3 * numParticles) throw OpenMMException("pairMatrix(): positions must hold 3N values");
+    const size_t s = (size_t)numAtomSets();
+    matrix.assign(s * s + (s == 0), 0.0);  // (no partition: the library refuses, with its message)
+    double e = 0.0;
+    check(agbnp_hip_pair_matrix_host(ctx, positions.data(), matrix.data(), &e));
+    return e;
+  }
+
   // Replica groups (agbnp_hip_execute_group_host): one evaluation of every kernel in `kernels`, the launches of the members
   // that can share them made once for all; positions[i] (3N_i) read, forces[i] accumulated, the members' energies returned.
   static std::vector<double> executeGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,

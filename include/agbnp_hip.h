@@ -189,6 +189,48 @@ int agbnp_hip_decompose_host(agbnp_hip_context* ctx, const double* positions, do
 int agbnp_hip_decompose_device(agbnp_hip_context* ctx, const double* d_positions, double* d_per_atom /*[4][N]*/,
                                double* d_energy /*may be NULL*/, void* stream);
 
+/* Set-pair interaction matrices: the residue-by-residue (chain-by-chain, receptor-by-ligand) table of an MM-GBSA-style
+ * decomposition, which the per-atom planes cannot give -- plane 3 forgets who the partner of a pair was.  A partition assigns
+ * every atom to one of S sets; with T[t][i] the four per-atom terms above, k and f_ij as there, the matrix M[S][S] (row-major,
+ * FP64) is
+ *   a != b   M[a][b] = k sum_{i in a, j in b} q_i q_j f_ij = M[b][a]: the GB pair energy between the two sets is
+ *            M[a][b] + M[b][a], shared half and half as plane 3 shares a pair
+ *   a == b   M[a][a] = sum_{i in a} (T[0][i] + T[1][i] + T[2][i]) + k sum_{i != j, both in a} q_i q_j f_ij (ordered pairs: every
+ *            unordered pair inside the set counts twice)
+ * so that row a sums to sum_{i in a} sum_t T[t][i], the whole matrix to the energy the context returns in its mode, M[0][0] of
+ * ONE set is that energy, and with every atom its own set the off-diagonal is the bare pair matrix k q_i q_j f_ij.  Version 0
+ * fills the diagonal only (the cavity term).  Fast mode: pairs with d^2 < cutoff^2 and that mode's Born radii, exactly as
+ * plane 3; fast+single: the FP64 terms of the FP64 fast mode, as for the decomposition.
+ *   agbnp_hip_set_atom_sets      the partition: set_of_atom[N] in atom (particle) order like the planes, values 0 .. num_sets - 1,
+ *                                num_sets 1 .. AGBNP_HIP_MAX_SETS; sets may be non-contiguous and may be empty (their rows and
+ *                                columns stay 0).  A wrong N, a value out of range or a null pointer returns
+ *                                AGBNP_HIP_ERR_INVALID_ARGUMENT and the previous partition is kept.  Replaces any earlier
+ *                                partition; waits only for work that may be reading the tables it replaces (the context's
+ *                                stream and the streams the caller has enqueued on; nothing before the first partition).  It
+ *                                changes nothing an evaluation reads: agbnp_hip_generation(), scalars 16 and 18 and the overflow
+ *                                log stay as they are, and agbnp_hip_update_parameters() keeps the partition
+ *   agbnp_hip_num_atom_sets      S, or 0 when no partition has been set
+ *   agbnp_hip_pair_matrix_host   synchronous; matrix[S S] is OVERWRITTEN, *energy RETURNED; withheld evaluations are repeated
+ *   agbnp_hip_pair_matrix_device asynchronous, no host synchronisation; the S S entries are ADDED to d_matrix and the total to
+ *                                *d_energy (may be NULL): a caller accumulates frames and divides
+ * In every respect listed for agbnp_hip_decompose_host / _device above the matrix calls behave as those do: ONE evaluation in the
+ * overflow log, gated on the verdict words on the device (a withheld evaluation adds nothing to the matrix or to the energy; the
+ * host form repeats it), agbnp_hip_expect_jump() applies, the context is left as a full evaluation leaves it, the calls
+ * interleave freely with every other kind, every mode is supported, fast+single is lifted for the call, and inside a stream
+ * capture the device call is refused and the capture stays usable.  Scalar 20 reports 4.  Without a partition both return
+ * AGBNP_HIP_ERR_INVALID_ARGUMENT and the message says so.
+ * Launches: exactly those of agbnp_hip_decompose_device(), with ONE launch of the same grid (k_pair_matrix) in the place of the
+ * plane launch.  No pair goes to memory by itself: a tile sums runs of j atoms of one set in registers, the runs in an LDS
+ * accumulator by the sets of its two blocks, and leaves with two atomics per pair of sets it met.  The deterministic
+ * mode gives a bit-identical matrix from run to run.
+ * Not provided: a group form, a binding form, an OpenMM-buffer form. */
+#define AGBNP_HIP_MAX_SETS 2048
+int agbnp_hip_set_atom_sets(agbnp_hip_context* ctx, int num_particles, const int* set_of_atom /*[N], 0..num_sets-1*/, int num_sets);
+int agbnp_hip_num_atom_sets(const agbnp_hip_context* ctx); /* 0: none set */
+int agbnp_hip_pair_matrix_host(agbnp_hip_context* ctx, const double* positions, double* matrix /*[S][S] OVERWRITTEN*/, double* energy);
+int agbnp_hip_pair_matrix_device(agbnp_hip_context* ctx, const double* d_positions, double* d_matrix /*[S][S] ADDED*/,
+                                 double* d_energy /*may be NULL*/, void* stream);
+
 /* Replica groups: ONE call that enqueues an evaluation of each of `count` existing contexts (1 .. AGBNP_HIP_MAX_GROUP), for
  * replica exchange, multiple walkers and binding-energy schemes that run several small systems at once.  d_positions,
  * d_forces, d_energies are HOST arrays of `count` DEVICE pointers, one per member.  For every member i the call does exactly
@@ -576,7 +618,7 @@ enum agbnp_hip_scalar {
                                             * evaluation, like 15, 17, 18, 19 and 21): 0 a full evaluation, 1 an energy-only evaluation on
                                             * energy-only launches (alone or shared), 2 an energy-only request that ran as a full
                                             * evaluation with its forces sent to the context's own buffer, 3 a per-atom decomposition
-                                            * (agbnp_hip_decompose_*) */
+                                            * (agbnp_hip_decompose_*), 4 a set-pair interaction matrix (agbnp_hip_pair_matrix_*) */
   AGBNP_HIP_SCALAR_GROUP_BLOCK_WRITES = 21 /* how often the context's group argument blocks have been rewritten so far (one small
                                             * launch each); it stands still in a steady run of group calls with fixed position buffers */
 };

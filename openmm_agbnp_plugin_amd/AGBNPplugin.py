@@ -335,6 +335,52 @@ class HipCalcAGBNPForceKernel(_Handle):
         (OpenMMException) inside a stream capture."""
         self._call("agbnp_hip_decompose_device", C.c_void_p(d_positions), C.c_void_p(d_per_atom), _ptr(d_energy), _ptr(stream))
 
+    def set_atom_sets(self, sets, num_sets=None):
+        """The partition of the atoms that pair_matrix() tabulates (include/agbnp_hip.h, agbnp_hip_set_atom_sets): sets[i] in
+        0 .. num_sets - 1 is the set of atom i -- its residue, its chain, receptor or ligand; sets need not be contiguous and may be
+        empty.  num_sets defaults to max(sets) + 1.  Replaces an earlier partition and survives copyParametersToContext();
+        changes nothing an evaluation reads.  The input is checked here, before the library is touched."""
+        self._need()
+        try:
+            given = np.asarray(sets)
+            sets = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
+            exact = given.ndim == 1 and np.array_equal(sets, given)  # (no fraction, no wrap-around into the int)
+        except (TypeError, ValueError, OverflowError):
+            raise OpenMMException("set_atom_sets(): sets must be a list of set indices, one per atom")
+        if not exact or sets.size != self.numParticles:
+            raise OpenMMException("set_atom_sets(): sets must hold one integer set index per atom")
+        if num_sets is None:
+            num_sets = int(sets.max()) + 1 if sets.size else 0
+        num_sets = int(num_sets)
+        if not 1 <= num_sets <= _lib.MAX_SETS:
+            raise OpenMMException(f"set_atom_sets(): num_sets must be 1 .. {_lib.MAX_SETS}")
+        if sets.min() < 0 or sets.max() >= num_sets:
+            raise OpenMMException("set_atom_sets(): every set index must be 0 .. num_sets - 1")
+        self._call("agbnp_hip_set_atom_sets", int(sets.size), _ip(sets), num_sets)
+
+    def num_atom_sets(self):
+        """The number of sets of the partition in force; 0: none has been set."""
+        return int(self._library().agbnp_hip_num_atom_sets(self._h))
+
+    def pair_matrix(self, positions):
+        """Set-pair interaction matrix of the energy at these positions (include/agbnp_hip.h, agbnp_hip_pair_matrix_host):
+        returns (energy, M) with M a float64 array [S, S] over the sets of set_atom_sets().  M[a, b] = M[b, a] is half the GB pair
+        energy between sets a and b, M[a, a] what the set holds in itself (cavity, vdW, GB self, its own pairs); row a sums to
+        the set's share of decompose()'s terms and M.sum() is the energy.  Withheld evaluations are repeated inside."""
+        pos = self._positions(positions, "pair_matrix")
+        s = self.num_atom_sets()
+        matrix = np.zeros((max(s, 1), max(s, 1)))  # (no partition: the library refuses, with its message)
+        e = C.c_double(0.0)
+        self._call("agbnp_hip_pair_matrix_host", _dp(pos), _dp(matrix), C.byref(e))
+        return e.value, matrix
+
+    def pair_matrix_device(self, d_positions, d_matrix, d_energy=None, stream=None):
+        """Device-resident form of pair_matrix(): the S S entries are ADDED to d_matrix (row-major FP64) and the total to
+        *d_energy when it is given; raw device pointers (ints).  Asynchronous, counted in the same log as every other
+        evaluation (finish(), withheld(), poll(), wait_verdict()); a withheld one adds nothing.  Refused (OpenMMException)
+        inside a stream capture."""
+        self._call("agbnp_hip_pair_matrix_device", C.c_void_p(d_positions), C.c_void_p(d_matrix), _ptr(d_energy), _ptr(stream))
+
     def atom_order_changed(self):
         """The context has reordered its atoms (same atomIndex array, new contents): the next execute_openmm() rebuilds the
         engine's maps first instead of losing one evaluation to the check on the device."""
@@ -812,6 +858,17 @@ class AGBNPContext:
         if not self._in_groups(groups):
             return 0.0, np.zeros((len(DECOMPOSITION_TERMS), self._kernel.numParticles))
         return self._kernel.decompose(self._positions)
+
+    def getInteractionMatrix(self, sets, groups=-1, num_sets=None):
+        """(energy, M[S, S]) at the context's positions for the partition `sets` (one set index per atom): the set-pair
+        interaction matrix of HipCalcAGBNPForceKernel.pair_matrix(), whose entries sum to the energy.  Honours the force-group
+        mask like getEnergyDecomposition()."""
+        inside = self._in_groups(groups)
+        self._kernel.set_atom_sets(sets, num_sets)
+        if not inside:
+            s = self._kernel.num_atom_sets()
+            return 0.0, np.zeros((s, s))
+        return self._kernel.pair_matrix(self._positions)
 
     def _update_parameters(self, force):
         self._kernel.copyParametersToContext(force)

@@ -197,6 +197,7 @@ enum KernelId {
   kKGbRows,                 // row form of the GB stage (fast mode only)
   kKEnergyRoles,            // energy-only evaluations: energy, dealing and the rows' close behind the GB stage (k_energy_roles)
   kKDecompose,              // per-atom decomposition: the launch behind its evaluation (k_decompose, decompose_kernels.hip)
+  kKPairMatrix,             // set-pair interaction matrix: the launch behind its evaluation (k_pair_matrix, pair_matrix_kernels.hip)
   kKernelCount
 };
 

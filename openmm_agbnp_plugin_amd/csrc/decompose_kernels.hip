@@ -10,10 +10,10 @@
 // Version 0 has plane 0 only.  Every workgroup is gated on the evaluation's verdict words, as every other output is: a withheld
 // evaluation adds nothing.
 //
-// The shared device code (rot1, gb_pair_terms, the status words' test, the parity rebase) is read as device functions, as the
-// replica groups' unit reads it (group_args.h): this unit launches none of the kernels of pair_bodies.h.
+// The shared device code (rot1, gb_pair_terms, the status words' test, the parity rebase; the tile walk of pair_tile.h) is read as
+// device functions, as the replica groups' unit reads it (group_args.h): this unit launches none of the kernels of pair_bodies.h.
 #define AGBNP_GROUP_TU
-#include "pair_bodies.h"
+#include "pair_tile.h"
 
 namespace agbnp {
 
@@ -30,93 +30,29 @@ __device__ __forceinline__ void decompose_atoms(const PairArgs& P, int version, 
 }
 
 // ---- tile workgroups: plane 3 ------------------------------------------------------------------------------------------------
-// All 64 x 64 block pairs (I <= J) of the atoms in atom order, numbered by arithmetic from the workgroup's number (rows of the
-// upper triangle laid end to end, as neighbor_tile does): no item list -- neither the row form nor the fast mode keeps one of
-// the GB stage.  The pair step is k_gb_tiles': lane l of every wave keeps atom 64 I + l, meets a quarter of block J in cyclic
-// order from a doubled copy of the block in LDS, and the j atom's running sum travels round the wave by DPP rotation, so that a
-// pair is evaluated once and credited to both ends.  Two sums per lane where k_gb_tiles carries nine.
-// kCut (fast mode): a pair beyond the cutoff carries a zero charge product, as in k_gb_tiles<kCut>; a tile whose blocks' boxes
-// are further apart than the cutoff leaves before its walk (the boxes are formed here: the fast mode's row form keeps none).
+// The tile walk of pair_tile.h: a pair is evaluated once and credited to both ends -- to the lane's own atom, and to the j atom,
+// whose running sum travels round the wave by DPP rotation.  Two sums per lane where k_gb_tiles carries nine.
 template <bool kCut>
 __device__ __forceinline__ void decompose_tile(const PairArgs& P, int tile, double* __restrict__ plane) {
-  __shared__ double2 s_xy[128], s_zq[128], s_bb[128];  // block J twice over: entry m and m + 64 are atom 64 J + m
-  __shared__ double2 s_ixy[64], s_izq[64], s_ibc[64];  // block I: {x, y}, {z, q}, {B, -log2(e)/(4 B)}
   __shared__ double s_red[4][2][64];
-  __shared__ double s_box[2][6];
-  const int n = P.n, nb = (n + 63) >> 6;
-  if (tile >= nb * (nb + 1) / 2) return;
-  int I = (int)(0.5 * ((double)(2 * nb + 1) - sqrt((double)(2 * nb + 1) * (double)(2 * nb + 1) - 8.0 * (double)tile)));
-  I = max(0, min(I, nb - 1));
-  while (I > 0 && I * nb - I * (I - 1) / 2 > tile) I--;  // (guards against rounding)
-  while (I + 1 < nb && (I + 1) * nb - (I + 1) * I / 2 <= tile) I++;
-  const int J = I + (tile - (I * nb - I * (I - 1) / 2));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool diag = I == J;
-  if (wave < 2) {  // wave 0 prepares block J, wave 1 block I
-    const int a = 64 * (wave == 0 ? J : I) + lane;
-    const bool va = a < n;
-    const int ac = va ? a : n - 1;
-    const double4 pa = P.aposq[ac];
-    const double br = P.born[ac], inv_br = 1.0 / br;
-    const double qa = va ? pa.w : 0.0;  // zero charge switches a padded atom off
-    if (wave == 0) {
-      s_xy[lane] = s_xy[lane + 64] = make_double2(pa.x, pa.y);
-      s_zq[lane] = s_zq[lane + 64] = make_double2(pa.z, qa);
-      s_bb[lane] = s_bb[lane + 64] = make_double2(br, inv_br);
-    } else {
-      s_ixy[lane] = make_double2(pa.x, pa.y);
-      s_izq[lane] = make_double2(pa.z, qa);
-      s_ibc[lane] = make_double2(br, (-0.25 * 1.4426950408889634074) * inv_br);
-    }
-    if (kCut && !diag) {  // the block's bounding box (a padded lane repeats atom n - 1: inside the box)
-      double lo[3] = {pa.x, pa.y, pa.z}, hi[3] = {pa.x, pa.y, pa.z};
-      for (int off = 32; off > 0; off >>= 1)
-        for (int d = 0; d < 3; d++) {
-          lo[d] = fmin(lo[d], __shfl_xor(lo[d], off, 64));
-          hi[d] = fmax(hi[d], __shfl_xor(hi[d], off, 64));
-        }
-      if (lane == 0)
-        for (int d = 0; d < 3; d++) s_box[wave][d] = lo[d], s_box[wave][3 + d] = hi[d];
-    }
-  }
-  __syncthreads();
-  if (kCut && !diag) {
-    if (box_gap2(&s_box[0][0], 0, 1) >= P.gb_cut2) return;  // (the same for every lane of the workgroup)
-  }
-  // the four waves take a quarter of the cyclic distances each (diagonal tile: distances 1..32, 8 per wave)
-  const int nsteps = diag ? 8 : 16;
-  const int start = (diag ? 1 : 0) + nsteps * wave;  // cyclic offset of the first j met by lane l
-  const double2 ixy = s_ixy[lane], izq = s_izq[lane], ibc = s_ibc[lane];
-  const double xi = ixy.x, yi = ixy.y, zi = izq.x, qi = izq.y, bi = ibc.x, ci = ibc.y;
-  // diagonal tile, cyclic distance 32 (the last step of the last wave): the pair (l, l + 32) is met from the lower lane only,
-  // and that one meeting credits both of its ends
-  const int masked_step = diag ? 32 - start : -1;
-  const double qlast = lane >= 32 ? 0.0 : qi;
-  const int base = (lane + start) & 63;
-  const double2* __restrict__ jxy = s_xy + base;
-  const double2* __restrict__ jzq = s_zq + base;
-  const double2* __restrict__ jbb = s_bb + base;
+  PairTile W;
+  if (!pair_tile_of(P.n, tile, W)) return;
   double ei = 0.0, ej = 0.0;  // sum q_i q_j f_ij of the lane's own atom / of the j atom in hand
-#pragma unroll 8
-  for (int k = 0; k < nsteps; k++) {
-    const double2 xy = jxy[k], zq = jzq[k], bj = jbb[k];
-    const double dx = xy.x - xi, dy = xy.y - yi, dz = zq.x - zi;
-    const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
-    double qq = (k == masked_step ? qlast : qi) * zq.y;
-    if (kCut) qq = d2 < P.gb_cut2 ? qq : 0.0;
-    const GbPairTerms<double> t = gb_pair_terms(d2, bi * bj.x, ci * bj.y, qq);  // (only s1 is used: the rest is dropped)
-    ei += t.s1;
-    ej = rot1(ej + t.s1);
-  }
+  if (!walk_pair_tile<kCut>(P, W, [&](int, double s1) {
+        ei += s1;
+        ej = rot1(ej + s1);
+      }))
+    return;
+  const int lane = W.lane, wave = W.wave;
   s_red[wave][0][lane] = ei;
-  s_red[wave][1][(lane + start + nsteps) & 63] = ej;  // whose sum the lane holds after the rotations
+  s_red[wave][1][(lane + W.start + W.nsteps) & 63] = ej;  // whose sum the lane holds after the rotations
   __syncthreads();
   if (wave >= 2) return;
   // wave 0 adds the sums of block I, wave 1 those of block J (the deterministic mode: a tile's totals are rounded to the
   // energies' quantum, so that the order of the atomics does not matter)
-  const int a = 64 * (wave == 0 ? I : J) + lane;
+  const int a = 64 * (wave == 0 ? W.I : W.J) + lane;
   const double sum = (s_red[0][wave][lane] + s_red[1][wave][lane]) + (s_red[2][wave][lane] + s_red[3][wave][lane]);
-  if (a < n) hbm_add(&plane[a], quantize(kDielFactor * sum, kQEnergy, P.det != 0));
+  if (a < P.n) hbm_add(&plane[a], quantize(kDielFactor * sum, kQEnergy, P.det != 0));
 }
 
 template <bool kCut>

@@ -199,9 +199,15 @@ struct agbnp_hip_context {
   // (energy_role routes the energy to an OpenMM accumulator only beside a fixed-point force target); never read
   DevBuf<double> d_eo_force;
   DevBuf<unsigned long long> d_eo_fixed;
-  // per-atom decompositions (agbnp_hip_decompose_host): the four planes and the energy [4n + 1] on the device and on the host
+  // per-atom decompositions and set-pair matrices (agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host): the four planes or the
+  // matrix, and the energy behind them, [4n + 1] or [S S + 1], on the device and on the host
   DevBuf<double> d_decomp;
   std::vector<double> h_decomp;
+  // the partition of agbnp_hip_set_atom_sets as the matrix launch reads it (pair_kernels.h, AtomSets: sets.num_sets == 0: none
+  // set).  No evaluation reads it; agbnp_hip_update_parameters leaves it alone
+  DevBuf<unsigned char> d_set_rank;
+  DevBuf<int> d_set_lists, d_set_counts;
+  AtomSets sets;
   int forests_hint = 0;        // forests of the last evaluation the host has read the status of (0: none yet); reset by a fallback packing
   std::vector<int> withheld;   // evaluations (numbered from the previous finish) that the last finish found withheld
   int withheld_count = 0;
@@ -250,7 +256,7 @@ struct agbnp_hip_context {
   int group_members = 0;             // scalar 19: members of the launch set the last evaluation shared (0: it ran alone)
   int group_block_writes = 0;        // scalar 21: k_group_put launches so far
   int last_kind = 0;                 // scalar 20: 0 a full evaluation, 1 energy-only on energy-only launches, 2 energy-only run as a full one,
-                                     // 3 a per-atom decomposition
+                                     // 3 a per-atom decomposition, 4 a set-pair interaction matrix
 
   // ---- what the last harvest read (engine_report.hip reads it back to the caller)
   Timeline timeline;

@@ -482,7 +482,13 @@ int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int po
 // fast+single: the terms are FP64 (header), so the evaluation runs with the single-precision option lifted for this call -- the
 // same lists and masks (the reach is the fast mode's), other pair-term arithmetic; kernel arguments travel by value, so nothing
 // enqueued before or after is affected.
-static int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, double* d_per_atom, double* d_energy, hipStream_t st) {
+// The launch behind the evaluation is the caller's: the four planes (d_per_atom, k_decompose) or, with a partition set, the
+// set-pair interaction matrix (d_matrix, k_pair_matrix; agbnp_hip_pair_matrix_*) -- one of the two.
+struct AnalysisTarget {
+  double* per_atom = nullptr;  // [4][n]
+  double* matrix = nullptr;    // [S][S]
+};
+static int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, AnalysisTarget out, double* d_energy, hipStream_t st) {
   EvalRequest r;
   r.pos = d_pos;
   r.force = c->d_eo_force.p;
@@ -502,11 +508,13 @@ static int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, doub
     rc = enqueue_prepare(c, r, plan);
     if (rc == AGBNP_HIP_OK) rc = enqueue_launch(c, plan, r);
     if (rc == AGBNP_HIP_OK) {
-      const hipError_t e = launch_decompose(c->P, c->version, d_per_atom, st, c->timeline.enabled ? &c->timeline : nullptr);
-      if (e != hipSuccess) rc = c->hipfail(e, "launch_decompose");
+      Timeline* tl = c->timeline.enabled ? &c->timeline : nullptr;
+      const hipError_t e = out.matrix ? launch_pair_matrix(c->P, c->sets, c->version, out.matrix, st, tl)
+                                      : launch_decompose(c->P, c->version, out.per_atom, st, tl);
+      if (e != hipSuccess) rc = c->hipfail(e, out.matrix ? "launch_pair_matrix" : "launch_decompose");
     }
   }
-  c->last_kind = 3;
+  c->last_kind = out.matrix ? 4 : 3;
   if (single) {
     c->mode |= AGBNP_HIP_MODE_SINGLE;
     derive_args(c);
@@ -514,30 +522,52 @@ static int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, doub
   return rc;
 }
 
-// agbnp_hip_decompose_host: the planes and the energy travel back in one buffer; withheld evaluations are repeated
-// (also how agbnp_hip_decompose_group_host repeats a member whose evaluation was withheld)
-int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy) {
+// agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host (matrix): the `count` words of the planes or of the matrix and the energy
+// travel back in one buffer; withheld evaluations are repeated
+static int host_analysis(agbnp_hip_context* c, const double* pos, bool matrix, size_t count, double* out, double* energy, const char* who) {
   HIP_TRY(c, hipSetDevice(c->device));
   const int rc0 = carry_unfinished(c);
   if (rc0 != AGBNP_HIP_OK) return rc0;
-  const size_t n4 = 4 * (size_t)c->n;
-  if (c->d_decomp.count != n4 + 1) HIP_TRY(c, c->d_decomp.alloc(n4 + 1));
-  c->h_decomp.resize(n4 + 1);
+  if (c->d_decomp.count != count + 1) HIP_TRY(c, c->d_decomp.alloc(count + 1));
+  c->h_decomp.resize(count + 1);
   for (int attempt = 0; attempt < 10; attempt++) {
     HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, pos, sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_decomp.p, 0, sizeof(double) * (n4 + 1), c->stream));
-    int rc = enqueue_decomposition(c, c->d_pos_in.p, c->d_decomp.p, c->d_decomp.p + n4, c->stream);
+    HIP_TRY(c, hipMemsetAsync(c->d_decomp.p, 0, sizeof(double) * (count + 1), c->stream));
+    AnalysisTarget target;
+    (matrix ? target.matrix : target.per_atom) = c->d_decomp.p;
+    int rc = enqueue_decomposition(c, c->d_pos_in.p, target, c->d_decomp.p + count, c->stream);
     if (rc != AGBNP_HIP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_decomp.data(), c->d_decomp.p, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_decomp.data(), c->d_decomp.p, sizeof(double) * (count + 1), hipMemcpyDeviceToHost, c->stream));
     int repeat = 0;
     rc = harvest(c, &repeat, c->stream);  // (its own reads follow on the stream; one wait for everything)
     if (rc != AGBNP_HIP_OK) return rc;
     if (repeat) continue;
-    std::memcpy(per_atom, c->h_decomp.data(), sizeof(double) * n4);
-    *energy = c->h_decomp[n4];
+    std::memcpy(out, c->h_decomp.data(), sizeof(double) * count);
+    *energy = c->h_decomp[count];
     return AGBNP_HIP_OK;
   }
-  return c->fail(AGBNP_HIP_ERR_CAPACITY, "agbnp_hip_decompose_host: capacity negotiation did not converge");
+  return c->fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
+}
+
+// (also how agbnp_hip_decompose_group_host repeats a member whose evaluation was withheld)
+int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy) {
+  return host_analysis(c, pos, false, 4 * (size_t)c->n, per_atom, energy, "agbnp_hip_decompose_host");
+}
+
+// agbnp_hip_decompose_device, agbnp_hip_pair_matrix_device, arguments checked
+static int device_analysis(agbnp_hip_context* c, const double* d_pos, AnalysisTarget out, double* d_energy, void* stream, const char* who) {
+  hipStream_t st;
+  const int rc = enter(c, stream, &st);
+  if (rc != AGBNP_HIP_OK) return rc;
+  if (refuse_capture(c, st, who)) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  note_stream(c, stream);
+  return enqueue_decomposition(c, d_pos, out, d_energy, st);
+}
+
+// the matrix calls need a partition (agbnp_hip_set_atom_sets)
+static int need_sets(agbnp_hip_context* c, const char* who) {
+  if (c->sets.num_sets > 0) return AGBNP_HIP_OK;
+  return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": no partition has been set (agbnp_hip_set_atom_sets)");
 }
 
 extern "C" {
@@ -551,12 +581,63 @@ int agbnp_hip_decompose_host(agbnp_hip_context* c, const double* pos, double* pe
 int agbnp_hip_decompose_device(agbnp_hip_context* c, const double* d_pos, double* d_per_atom, double* d_energy, void* stream) {
   if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   if (!d_pos || !d_per_atom) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_decompose_device: null pointer");
-  hipStream_t st;
-  const int rc = enter(c, stream, &st);
+  AnalysisTarget target;
+  target.per_atom = d_per_atom;
+  return device_analysis(c, d_pos, target, d_energy, stream, "agbnp_hip_decompose_device");
+}
+
+// The partition is the matrix launch's alone (AtomSets): nothing an evaluation reads changes, so neither does
+// agbnp_hip_generation().  Its tables are replaced in place (their sizes depend on n alone), so matrix calls in flight are
+// waited for first -- the context's own stream and the streams the caller has enqueued on, as agbnp_hip_update_parameters
+// waits -- and nothing else is.  A refused partition leaves the one before it in place.
+int agbnp_hip_set_atom_sets(agbnp_hip_context* c, int n, const int* set_of_atom, int num_sets) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!set_of_atom) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_set_atom_sets: null pointer");
+  if (n != c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_set_atom_sets: the number of particles differs from the context's");
+  if (num_sets < 1 || num_sets > AGBNP_HIP_MAX_SETS)
+    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_set_atom_sets: num_sets must be 1 .. AGBNP_HIP_MAX_SETS");
+  for (int i = 0; i < n; i++)
+    if (set_of_atom[i] < 0 || set_of_atom[i] >= num_sets)
+      return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_set_atom_sets: atom " + std::to_string(i) + " names a set outside 0 .. num_sets - 1");
+  std::vector<unsigned char> rank;
+  std::vector<int> lists, counts;
+  const int depth = atom_set_tables(n, set_of_atom, rank, lists, counts);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->sets.num_sets > 0) {  // (before the first partition no launch can be reading the tables)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (void* st : c->user_streams) HIP_TRY(c, hipStreamSynchronize((hipStream_t)st));
+  }
+  c->sets = AtomSets{};  // (a failed upload leaves no partition rather than half of one)
+  HIP_TRY(c, c->d_set_rank.upload(rank));
+  HIP_TRY(c, c->d_set_lists.upload(lists));
+  HIP_TRY(c, c->d_set_counts.upload(counts));
+  c->sets.rank = c->d_set_rank.p;
+  c->sets.block_sets = c->d_set_lists.p;
+  c->sets.block_count = c->d_set_counts.p;
+  c->sets.num_sets = num_sets;
+  c->sets.depth = depth;
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_num_atom_sets(const agbnp_hip_context* c) { return c ? c->sets.num_sets : 0; }
+
+int agbnp_hip_pair_matrix_host(agbnp_hip_context* c, const double* pos, double* matrix, double* energy) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!pos || !matrix || !energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_pair_matrix_host: null pointer");
+  const int rc = need_sets(c, "agbnp_hip_pair_matrix_host");
   if (rc != AGBNP_HIP_OK) return rc;
-  if (refuse_capture(c, st, "agbnp_hip_decompose_device")) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  note_stream(c, stream);
-  return enqueue_decomposition(c, d_pos, d_per_atom, d_energy, st);
+  const size_t S = (size_t)c->sets.num_sets;
+  return host_analysis(c, pos, true, S * S, matrix, energy, "agbnp_hip_pair_matrix_host");
+}
+
+int agbnp_hip_pair_matrix_device(agbnp_hip_context* c, const double* d_pos, double* d_matrix, double* d_energy, void* stream) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_pos || !d_matrix) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_pair_matrix_device: null pointer");
+  const int rc = need_sets(c, "agbnp_hip_pair_matrix_device");
+  if (rc != AGBNP_HIP_OK) return rc;
+  AnalysisTarget target;
+  target.matrix = d_matrix;
+  return device_analysis(c, d_pos, target, d_energy, stream, "agbnp_hip_pair_matrix_device");
 }
 
 int agbnp_hip_execute_device(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, void* stream) {

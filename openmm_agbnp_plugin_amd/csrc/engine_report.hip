@@ -133,7 +133,7 @@ int agbnp_hip_num_kernels(void) { return kKernelCount; }
 const char* agbnp_hip_kernel_name(int index) {
   static const char* names[kKernelCount] = {"k_prep",        "k_tree_cavity", "k_born_tiles", "k_gb_tiles", "k_dborn_tiles",
                                             "k_tree_pseudo", "k_outputs",     "k_born_rows",  "k_dborn_rows",  "k_gb_rows",
-                                            "k_energy_roles", "k_decompose"};
+                                            "k_energy_roles", "k_decompose",  "k_pair_matrix"};
   return (index >= 0 && index < kKernelCount) ? names[index] : "";
 }
 

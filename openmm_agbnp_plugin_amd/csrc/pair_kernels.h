@@ -265,4 +265,21 @@ hipError_t launch_outputs(const PairArgs& P, const OutputShape& O, int version, 
 // adds the four term-major planes [4][n] to per_atom unless the evaluation was withheld
 hipError_t launch_decompose(const PairArgs& P, int version, double* per_atom, hipStream_t st, Timeline* tl);
 
+// set-pair interaction matrix (pair_matrix_kernels.hip; engine_eval.hip, agbnp_hip_pair_matrix_*): a partition of the atoms into
+// sets as the launch reads it, built on the host by agbnp_hip_set_atom_sets (atom_set_tables) -- every 64-block of atoms in
+// atom order lists its distinct sets, and an atom names its set by its place in its block's list
+constexpr int kSetBlock = 64;
+struct AtomSets {
+  const unsigned char* rank = nullptr;  // [64 nb] the atom's set: entry `rank` of its block's list (padding: 0)
+  const int* block_sets = nullptr;      // [nb][64] the distinct sets of a block, in the order its atoms first name them
+  const int* block_count = nullptr;     // [nb] how many
+  int num_sets = 0;                     // S: the matrix is [S][S], row-major
+  int depth = 0;                        // the largest count of a block: the tile's LDS accumulator is [depth][depth]
+};
+// the host side of AtomSets for a partition (set_of_atom[n], values checked by the caller); returns the depth
+int atom_set_tables(int n, const int* set_of_atom, std::vector<unsigned char>& rank, std::vector<int>& block_sets,
+                    std::vector<int>& block_count);
+// the one launch behind the matrix call's evaluation: adds the matrix unless the evaluation was withheld
+hipError_t launch_pair_matrix(const PairArgs& P, const AtomSets& A, int version, double* matrix, hipStream_t st, Timeline* tl);
+
 }  // namespace agbnp

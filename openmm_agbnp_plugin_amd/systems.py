@@ -120,6 +120,18 @@ def load_dms(path, name=None):
     return parse_structure(text, name=name or os.path.splitext(os.path.basename(path))[0])
 
 
+def load_sets(path):
+    """A partition of a system's atoms from a text file with one line per atom, in atom order: atoms whose lines are equal
+    (for a residue file: `resid chain resname`) form a set, and the sets are numbered in the order in which the file first names
+    them.  Returns (set_of_atom, labels): an int32 array [N] for HipCalcAGBNPForceKernel.set_atom_sets() and the label of every
+    set.  A set need not be contiguous in the file."""
+    with open(path) as f:
+        lines = [" ".join(line.split()) for line in f if line.strip()]
+    labels = list(dict.fromkeys(lines))
+    number = {label: k for k, label in enumerate(labels)}
+    return np.array([number[line] for line in lines], dtype=np.int32), labels
+
+
 def lattice(system, nx, ny, nz, pitch_nm):
     """Synthetic larger system: nx*ny*nz translated copies (stand-in for the missing hivrt file,
     SURVEY.md section 8d C4).  Copies do not overlap when pitch exceeds the molecule's extent + 2 nm... they still
