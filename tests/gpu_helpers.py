@@ -27,6 +27,22 @@ def kernel_of(params, version=1, mode="reference"):
     return k
 
 
+def freeze_packing(k, nheavy, per_forest=8):
+    """A packing frozen from the host (test hook agbnp_debug_set_packing): forest f = the whole subtrees of heavy atoms
+    per_forest f .. per_forest f + per_forest - 1, whatever their size.  `k`: a kernel, or the view of a binding's member
+    (BindingEnergy.member()): anything with the context's handle in _h.  Returns the number of forests."""
+    import ctypes as C
+
+    from openmm_agbnp_plugin_amd import _lib
+    lib = _lib.load()
+    lib.agbnp_debug_set_packing.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]
+    nf = (nheavy + per_forest - 1) // per_forest
+    order = (C.c_int * nheavy)(*range(nheavy))
+    start = (C.c_int * (nf + 1))(*[min(per_forest * f, nheavy) for f in range(nf + 1)])
+    assert lib.agbnp_debug_set_packing(k._h, order, nheavy, start, nf, 1) == _lib.OK
+    return nf
+
+
 def energy_close(e, eo, tol=TIGHT):
     assert abs(e - eo) < tol * max(1.0, abs(eo) * 1e-3), f"energy differs by {abs(e - eo):.3e}"
 

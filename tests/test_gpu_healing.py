@@ -10,6 +10,7 @@ import pytest
 
 import openmm_agbnp_plugin_amd as P
 from oracle import Oracle
+from tests.gpu_helpers import freeze_packing
 
 pytestmark = pytest.mark.gpu
 TIGHT = 1e-7
@@ -24,21 +25,6 @@ def _queue(k, torch, geoms, n):
     stream = torch.cuda.current_stream().cuda_stream
     run = lambda i: k.execute_device(pos[i].data_ptr(), frc.data_ptr(), ene.data_ptr(), stream)
     return run, frc, ene, stream
-
-
-def _freeze_eight_subtrees_per_forest(k, nheavy):
-    """A packing frozen from the host (test hook agbnp_debug_set_packing): forest f = the whole subtrees of heavy atoms
-    8 f .. 8 f + 7, whatever their size."""
-    import ctypes as C
-
-    from openmm_agbnp_plugin_amd import _lib
-    lib = _lib.load()
-    lib.agbnp_debug_set_packing.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]
-    nf = (nheavy + 7) // 8
-    order = (C.c_int * nheavy)(*range(nheavy))
-    start = (C.c_int * (nf + 1))(*[min(8 * f, nheavy) for f in range(nf + 1)])
-    assert lib.agbnp_debug_set_packing(k._h, order, nheavy, start, nf, 1) == _lib.OK
-    return nf
 
 
 @pytest.mark.parametrize("launches,version", [("six", 1), ("five", 1), ("five", 0)])
@@ -62,7 +48,7 @@ def test_overfull_forests_are_healed_inside_the_tree_launch(gpu_required, system
         run(i)
     assert k.finish(stream) == 0
     assert int(k.scalar("launches")) == ((5 if launches == "five" else 6) if version == 1 else 2)
-    nf = _freeze_eight_subtrees_per_forest(k, s.nheavy)
+    nf = freeze_packing(k, s.nheavy)
     frc.zero_()
     ene.zero_()
     gen = k.generation()

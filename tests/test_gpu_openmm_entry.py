@@ -12,10 +12,9 @@ import pytest
 
 import openmm_agbnp_plugin_amd as P
 from oracle import Oracle
-from tests.gpu_helpers import TIGHT, Buffers, close, cluster, energy_close, execute_group
+from tests.gpu_helpers import TIGHT, Buffers, close, cluster, energy_close, execute_group, freeze_packing
 from tests.gpu_helpers import five  # noqa: F401
 from tests.openmm_context import ENERGY_SLOT, OpenMMContext, protocol_geometries
-from tests.test_gpu_healing import _freeze_eight_subtrees_per_forest
 
 pytestmark = pytest.mark.gpu
 
@@ -78,7 +77,7 @@ def test_overfull_forests_are_healed_through_the_openmm_entry(gpu_required, syst
     keep = ctx.run(k, geoms[:2], expect=False)[0]  # settle on the engine's own packing
     assert k.finish(stream) == 0
     assert int(k.scalar("launches")) == 5
-    nf = _freeze_eight_subtrees_per_forest(k, s.nheavy)
+    nf = freeze_packing(k, s.nheavy)
     ctx.clear()
     gen = k.generation()
     keep, we, wf = ctx.run(k, geoms)
@@ -120,7 +119,7 @@ def test_forests_are_healed_inside_a_replayed_graph(gpu_required, systems, five)
         buf.load(s.jittered(step))
         buf.enqueue(k)
     assert k.finish(_stream(torch)) == 0
-    _freeze_eight_subtrees_per_forest(k, s.nheavy)
+    freeze_packing(k, s.nheavy)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         buf.clear()
