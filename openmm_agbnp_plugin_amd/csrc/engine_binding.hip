@@ -11,7 +11,9 @@
 // Single and group calls are ONE host path: binding_enqueue takes `count` bindings and makes, for a single call (count == 1, a
 // host lambda), the single-binding launches and otherwise the group launches, as group_enqueue makes a member's own launches
 // for a launch set of one; the host entry points of both stage and deliver through binding_stage and binding_deliver.  What
-// the single and the group entry points keep of their own is their argument checks.
+// the single and the group entry points keep of their own is their argument checks.  The per-atom decomposition is a second, single
+// enqueue (binding_decompose_enqueue) that starts as the first does (binding_enter); both single host forms repeat a withheld
+// evaluation in one loop (binding_retry).
 // Messages of failed binding calls are the calling thread's agbnp_hip_last_error(NULL).
 #include "binding_kernels.h"
 #include "engine_context.h"
@@ -94,6 +96,15 @@ BindingVerdicts binding_verdicts(const agbnp_hip_binding* b) {
   return v;
 }
 
+// what every enqueue starts with: the members' messages cleared, the first complex's device and the call's stream, no stream capture
+int binding_enter(agbnp_hip_binding* const* bs, int count, void* stream, hipStream_t* st, const char* who) {
+  for (int k = 0; k < count; k++) clear_member_errors(bs[k]);
+  if (enter(bs[0]->m[0], stream, st) != AGBNP_HIP_OK) return member_fail(bs[0], AGBNP_HIP_ERR_DEVICE, who);
+  if (!is_capturing(*st)) return AGBNP_HIP_OK;
+  return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                      std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
+}
+
 // One evaluation of every binding on `stream` (NULL: the first complex's own); the arguments have been checked.  d_forces null:
 // the energy-only form; d_energies / d_bindings null: every entry null.  One gather launch, the members' evaluations through
 // the public group entry points -- one call over all 3 count members where they fit a group, else one call per kind
@@ -103,12 +114,9 @@ BindingVerdicts binding_verdicts(const agbnp_hip_binding* b) {
 int binding_enqueue(agbnp_hip_binding* const* bs, int count, const double* const* d_pos, const Lambdas& lam, double* const* d_forces,
                     double* const* d_energies, double* const* d_bindings, void* stream, const char* who) {
   agbnp_hip_binding* const b0 = bs[0];
-  for (int k = 0; k < count; k++) clear_member_errors(bs[k]);
   hipStream_t st;
-  if (enter(b0->m[0], stream, &st) != AGBNP_HIP_OK) return member_fail(b0, AGBNP_HIP_ERR_DEVICE, who);
-  if (is_capturing(st))
-    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
-                        std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
+  const int entered = binding_enter(bs, count, stream, &st, who);
+  if (entered != AGBNP_HIP_OK) return entered;
   BindingGroupArgs G;
   std::memset(&G, 0, sizeof(G));
   G.count = count;
@@ -191,12 +199,9 @@ int binding_enqueue(agbnp_hip_binding* const* bs, int count, const double* const
 // and the combine launch, which reads the three verdicts and adds D and u all or nothing.
 int binding_decompose_enqueue(agbnp_hip_binding* b, const double* d_pos, double* d_per_atom, double* d_binding, void* stream,
                               const char* who) {
-  clear_member_errors(b);
   hipStream_t st;
-  if (enter(b->m[0], stream, &st) != AGBNP_HIP_OK) return member_fail(b, AGBNP_HIP_ERR_DEVICE, who);
-  if (is_capturing(st))
-    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
-                        std::string(who) + ": the stream is being captured; binding evaluations use group calls, which are not captured into graphs");
+  const int entered = binding_enter(&b, 1, stream, &st, who);
+  if (entered != AGBNP_HIP_OK) return entered;
   const size_t n = (size_t)b->n, nr = (size_t)b->nr, words = 8 * n + kBindingMembers;
   if (b->d_planes.p == nullptr) {
     BINDING_TRY(who, b->d_planes.alloc(words));
@@ -266,33 +271,47 @@ int binding_carry(agbnp_hip_binding* b, const char* who) {
   return AGBNP_HIP_OK;
 }
 
-// agbnp_hip_binding_decompose_host: the device path on the binding's staging buffer and the complex's own stream; a withheld
-// evaluation is repeated here, as binding_host repeats
-int binding_decompose_host(agbnp_hip_binding* b, const double* pos, double* per_atom, double* binding_energy, const char* who) {
+// The single host entry points: device evaluations still in flight are carried, then `stage` -- the device path on the binding's
+// staging buffers and the complex's own stream, the outputs on their way back -- is repeated until the harvest finds the evaluation
+// complete, and `deliver` hands out what came back
+template <class Stage, class Deliver>
+int binding_retry(agbnp_hip_binding* b, const char* who, Stage stage, Deliver deliver) {
   int rc = binding_carry(b, who);
   if (rc != AGBNP_HIP_OK) return rc;
   BINDING_TRY(who, hipSetDevice(b->device));
-  const hipStream_t st = b->m[0]->stream;
-  const size_t n3 = 3 * (size_t)b->n, n4 = 4 * (size_t)b->n;
-  if (b->d_decomp.p == nullptr) BINDING_TRY(who, b->d_decomp.alloc(n3 + n4 + 1));
-  b->h_decomp.resize(n4 + 1);
-  double* const d_out = b->d_decomp.p + n3;
   for (int attempt = 0; attempt < 10; attempt++) {
-    BINDING_TRY(who, hipMemcpyAsync(b->d_decomp.p, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
-    BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (n4 + 1), st));
-    rc = binding_decompose_enqueue(b, b->d_decomp.p, d_out, d_out + n4, nullptr, who);
+    rc = stage();
     if (rc != AGBNP_HIP_OK) return rc;
-    BINDING_TRY(who, hipMemcpyAsync(b->h_decomp.data(), d_out, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, st));
     std::vector<int> bad;
     int count = 0;
     rc = binding_harvest(b, nullptr, bad, &count, who);  // (waits for the stream)
     if (rc != AGBNP_HIP_OK) return rc;
     if (count) continue;
-    std::memcpy(per_atom, b->h_decomp.data(), sizeof(double) * n4);
-    if (binding_energy) *binding_energy = b->h_decomp[n4];
+    deliver();
     return AGBNP_HIP_OK;
   }
   return binding_fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
+}
+
+// agbnp_hip_binding_decompose_host: staged in d_decomp (made on first use), [3n] positions | [4n] D | u, the outputs cleared first
+int binding_decompose_host(agbnp_hip_binding* b, const double* pos, double* per_atom, double* binding_energy, const char* who) {
+  const size_t n3 = 3 * (size_t)b->n, n4 = 4 * (size_t)b->n;
+  auto stage = [&]() -> int {
+    const hipStream_t st = b->m[0]->stream;
+    if (b->d_decomp.p == nullptr) BINDING_TRY(who, b->d_decomp.alloc(n3 + n4 + 1));
+    b->h_decomp.resize(n4 + 1);
+    double* const d_out = b->d_decomp.p + n3;
+    BINDING_TRY(who, hipMemcpyAsync(b->d_decomp.p, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
+    BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (n4 + 1), st));
+    const int rc = binding_decompose_enqueue(b, b->d_decomp.p, d_out, d_out + n4, nullptr, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+    BINDING_TRY(who, hipMemcpyAsync(b->h_decomp.data(), d_out, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, st));
+    return AGBNP_HIP_OK;
+  };
+  return binding_retry(b, who, stage, [&] {
+    std::memcpy(per_atom, b->h_decomp.data(), sizeof(double) * n4);
+    if (binding_energy) *binding_energy = b->h_decomp[n4];
+  });
 }
 
 // The host entry points' evaluation, on the first complex's own stream: every binding's staging buffers made on first use, its
@@ -330,25 +349,11 @@ void binding_deliver(const agbnp_hip_binding* b, double* forces, double* energy,
   if (binding_energy) *binding_energy = b->h_host[n3 + 1];
 }
 
-// agbnp_hip_binding_execute_host and (forces null) agbnp_hip_binding_energy_host: the device path on the binding's staging
-// buffers and the complex's own stream; a withheld evaluation is repeated here
+// agbnp_hip_binding_execute_host and (forces null) agbnp_hip_binding_energy_host
 int binding_host(agbnp_hip_binding* b, const double* pos, double lambda, double* forces, double* energy, double* binding_energy,
                  const char* who) {
-  int rc = binding_carry(b, who);
-  if (rc != AGBNP_HIP_OK) return rc;
-  BINDING_TRY(who, hipSetDevice(b->device));
-  for (int attempt = 0; attempt < 10; attempt++) {
-    rc = binding_stage(&b, 1, &pos, Lambdas{lambda, nullptr}, forces == nullptr, who);
-    if (rc != AGBNP_HIP_OK) return rc;
-    std::vector<int> bad;
-    int count = 0;
-    rc = binding_harvest(b, nullptr, bad, &count, who);  // (waits for the stream)
-    if (rc != AGBNP_HIP_OK) return rc;
-    if (count) continue;
-    binding_deliver(b, forces, energy, binding_energy);
-    return AGBNP_HIP_OK;
-  }
-  return binding_fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
+  return binding_retry(b, who, [&] { return binding_stage(&b, 1, &pos, Lambdas{lambda, nullptr}, forces == nullptr, who); },
+                       [&] { binding_deliver(b, forces, energy, binding_energy); });
 }
 
 // agbnp_hip_binding_execute_device and (energy_only, d_forces null) agbnp_hip_binding_energy_device: the single entry points'

@@ -322,22 +322,55 @@ ENGINE_LOCAL int mark_rows_stale(agbnp_hip_context* c);
 // What a caller asks of one evaluation.  It is written into the argument blocks by bind_request (inside enqueue_prepare) and taken
 // out again by Unbind, on every return path of enqueue / group_enqueue: between evaluations P and T name no caller's buffer to clear
 // and no OpenMM context.
+// An analysis (agbnp_hip_decompose_*, agbnp_hip_pair_matrix_*, a decomposition group's member) is a property of the request: ONE
+// evaluation in the context's overflow log -- the energy-only evaluation of the context (energy_only_fast: its four / two launches;
+// elsewhere the full evaluation with its forces sent to d_eo_force) with the cavity launch's instantiation that also collects the
+// enlarged-radius self volumes (sv_large(): row kHvSvLarge) -- and behind it, on the same stream, the one launch that adds to the
+// caller's target: the four planes (k_decompose, decompose_kernels.hip; a launch set's members share k_group_decompose) or, with a
+// partition set, the set-pair interaction matrix (k_pair_matrix) -- one of the two.  enqueue_launch makes that launch and names the
+// kind in last_kind; launch_set makes the shared one.  The energy leaves with the evaluation's own energy role (energy_request:
+// no energy word: into the context's spare word), the target is gated on the same verdict words.  Nothing of the context's state
+// differs from what the evaluation alone leaves: the request selects the instantiation, c->diagnostics is not touched.
+// fast+single: the terms are FP64 (header), so the evaluation runs with the single-precision option lifted for this call
+// (LiftSingle) -- the same lists and masks (the reach is the fast mode's), other pair-term arithmetic; kernel arguments travel by
+// value, so nothing enqueued before or after is affected.
+enum class Analysis { none, planes, matrix };
 struct EvalRequest {
   const double* pos = nullptr;   // [3n] FP64 positions on the device
   double* force = nullptr;       // [3n] FP64 forces, added to (energy-only: where a full evaluation's would go, d_eo_force)
   double* energy = nullptr;      // [1]
   hipStream_t stream = nullptr;
   bool energy_only = false;
-  bool sv_large = false;         // the cavity launch also collects the enlarged-radius self volumes (a decomposition: row kHvSvLarge)
-  double* per_atom = nullptr;    // a decomposition group's member (engine_group.hip): its planes [4][n], added to by the plane launch
+  Analysis analysis = Analysis::none;  // what follows the evaluation, and ...
+  double* target = nullptr;      // ... what it adds to: the planes [4][n] or the matrix [S][S]
   double* zero_out = nullptr;    // the host entry points' staging buffer, cleared first (PairArgs::zero_out)
   OpenmmSource in;               // agbnp_hip_execute_openmm / agbnp_hip_energy_openmm: the context's posq ...
   OpenmmTargets omm;             // ... and its fixed-point planes and energy accumulator
+  bool sv_large() const { return analysis != Analysis::none; }  // an analysis is exactly what needs the enlarged-radius self volumes
 };
 struct ENGINE_LOCAL Unbind {
   agbnp_hip_context* const* ctxs;
   int count;
   ~Unbind();
+};
+// The requests that carry an analysis in the fast+single mode: the option is off from before the member's enqueue_prepare
+// (host_set_only there reads P.single) until its request has left the argument blocks -- declared in front of the Unbind, destroyed
+// behind it.  The generation is not touched: the mode is what it was when the call returns.
+struct ENGINE_LOCAL LiftSingle {
+  agbnp_hip_context* lifted[kMaxGroup];
+  int count = 0;
+  void lift(agbnp_hip_context* c, const EvalRequest& r) {
+    if (!r.sv_large() || !(c->mode & AGBNP_HIP_MODE_SINGLE)) return;
+    c->mode &= ~AGBNP_HIP_MODE_SINGLE;
+    derive_args(c);
+    lifted[count++] = c;
+  }
+  ~LiftSingle() {
+    for (int i = 0; i < count; i++) {
+      lifted[i]->mode |= AGBNP_HIP_MODE_SINGLE;
+      derive_args(lifted[i]);
+    }
+  }
 };
 // What enqueue() decides before its launches (enqueue_prepare) and hands to them (enqueue_launch)
 struct EvalPlan {
@@ -357,6 +390,11 @@ ENGINE_LOCAL int catch_up(agbnp_hip_context* c);
 ENGINE_LOCAL int carry_unfinished(agbnp_hip_context* c);
 ENGINE_LOCAL int host_evaluation(agbnp_hip_context* c, const double* pos, double* forces, double* energy);
 ENGINE_LOCAL int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy);
+// the energy-only request with its analysis (d_energy null: the context's spare word); a host form's analysis through d_decomp [count + 1]
+ENGINE_LOCAL EvalRequest energy_request(agbnp_hip_context* c, const double* d_pos, double* d_energy, hipStream_t st, Analysis kind = Analysis::none, double* target = nullptr);
+ENGINE_LOCAL int stage_analysis(agbnp_hip_context* c, const double* pos, Analysis kind, size_t count, hipStream_t st, EvalRequest* r);
+ENGINE_LOCAL hipError_t fetch_analysis(agbnp_hip_context* c, size_t count, hipStream_t st);
+ENGINE_LOCAL void deliver_analysis(const agbnp_hip_context* c, size_t count, double* out, double* energy);
 
 // ---- engine_group.hip (what replica groups and binding groups both need)
 ENGINE_LOCAL bool spans_overlap(const double* a, size_t na, const double* b, size_t nb);  // two output spans; a null one overlaps nothing

@@ -1,5 +1,6 @@
 // One evaluation of one context (engine_context.h): the request and how it enters and leaves the argument blocks, the
-// per-evaluation host logic and the launches, the harvest behind them, and every single-context entry point that computes.
+// per-evaluation host logic and the launches -- the analysis that a request carries among them --, the harvest behind them, and
+// every single-context entry point that computes.
 #include "engine_context.h"
 
 // set the context's device and pick the stream of a call: the caller's, or the context's own
@@ -190,24 +191,30 @@ void set_outputs(agbnp_hip_context* c, double* d_force, bool fused) {
   O.gb_rows = c->P.gb_rows;
 }
 
-// The launches of an evaluation that enqueue_prepare has prepared
+// The launches of an evaluation that enqueue_prepare has prepared, and behind them -- on every way out -- the request's analysis
 int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest& r) {
   const hipStream_t st = r.stream;
   Timeline* tl = c->timeline.enabled ? &c->timeline : nullptr;
   const int tree_grid = plan.tree_grid;
   const PairLaunchShape shape = pair_launch_shape(c->P, c->version);
-  c->last_kind = !r.energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
+  const bool matrix = r.analysis == Analysis::matrix;
+  c->last_kind = matrix ? 4 : r.sv_large() ? 3 : !r.energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
+  auto analysis = [&]() -> int {
+    if (!r.sv_large()) return AGBNP_HIP_OK;
+    const hipError_t e = matrix ? launch_pair_matrix(c->P, c->sets, c->version, r.target, st, tl) : launch_decompose(c->P, c->version, r.target, st, tl);
+    return e == hipSuccess ? AGBNP_HIP_OK : c->hipfail(e, matrix ? "launch_pair_matrix" : "launch_decompose");
+  };
   if (c->five_active) {
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
-    HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st, r.sv_large));
+    HIP_TRY(c, launch_tree_cavity_five(c->variant, tree_grid, c->T, c->P, st, r.sv_large()));
     if (r.energy_only && energy_only_fast(c)) {
       HIP_TRY(c, launch_energy_only_stages(c->P, shape, c->version, r.energy, c->d_components.p, st, tl));
-      return AGBNP_HIP_OK;
+      return analysis();
     }
   } else {
     HIP_TRY(c, launch_prep(c->P, st, tl));
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
-    HIP_TRY(c, launch_tree_cavity(c->variant, kGlobalGrid, tree_grid, c->T, st, r.sv_large));
+    HIP_TRY(c, launch_tree_cavity(c->variant, kGlobalGrid, tree_grid, c->T, st, r.sv_large()));
   }
   if (c->version == 1) {
     HIP_TRY(c, launch_pair_stages(c->P, shape, r.energy, c->d_components.p, st, tl));
@@ -218,17 +225,19 @@ int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest
     HIP_TRY(c, launch_tree_pseudo(c->variant, kGlobalGrid, tree_grid, c->T, st));
     if (fused) {
       if (tl) HIP_TRY(c, tl->mark(-1, st));
-      return AGBNP_HIP_OK;
+      return analysis();
     }
   }
   // (version 0 in the five-launch mode: the renewal of the level-2 neighbour masks rides at the tail of this launch)
   HIP_TRY(c, launch_outputs(c->P, c->five_active && c->version == 0 ? shape.out_masks : shape.out, c->version, r.force, r.energy, c->d_components.p, st, tl));
-  return AGBNP_HIP_OK;
+  return analysis();
 }
 
 namespace {
 int enqueue(agbnp_hip_context* c, const EvalRequest& r) {
+  LiftSingle single;  // (in front of the Unbind: the option comes back behind it)
   const Unbind unbind{&c, 1};
+  single.lift(c, r);
   EvalPlan plan;
   const int rc = enqueue_prepare(c, r, plan);
   if (rc != AGBNP_HIP_OK) return rc;
@@ -473,77 +482,56 @@ int agbnp_hip_execute_openmm_to(agbnp_hip_context* c, const void* d_posq, int po
 }
 }  // namespace
 
-// Per-atom decomposition (agbnp_hip_decompose_*): ONE evaluation in the context's overflow log -- the energy-only evaluation of the
-// context (energy_only_fast: its four / two launches; elsewhere the full evaluation with its forces sent to d_eo_force) with the
-// cavity launch's instantiation that also collects the enlarged-radius self volumes -- and behind it, on the same stream, the one
-// launch that adds the planes (decompose_kernels.hip).  The energy leaves with the evaluation's own energy role (d_energy == NULL:
-// into the context's spare word), the planes are gated on the same verdict words.  Nothing of the context's state differs from
-// what the evaluation alone leaves: the request selects the instantiation, c->diagnostics is not touched.
-// fast+single: the terms are FP64 (header), so the evaluation runs with the single-precision option lifted for this call -- the
-// same lists and masks (the reach is the fast mode's), other pair-term arithmetic; kernel arguments travel by value, so nothing
-// enqueued before or after is affected.
-// The launch behind the evaluation is the caller's: the four planes (d_per_atom, k_decompose) or, with a partition set, the
-// set-pair interaction matrix (d_matrix, k_pair_matrix; agbnp_hip_pair_matrix_*) -- one of the two.
-struct AnalysisTarget {
-  double* per_atom = nullptr;  // [4][n]
-  double* matrix = nullptr;    // [S][S]
-};
-static int enqueue_decomposition(agbnp_hip_context* c, const double* d_pos, AnalysisTarget out, double* d_energy, hipStream_t st) {
+// The energy-only request -- the context's own force target, for where it runs as a full evaluation -- and with it the analysis that
+// follows, if any (engine_context.h, above EvalRequest), set together.  d_energy null: the energy goes to the context's spare word.
+EvalRequest energy_request(agbnp_hip_context* c, const double* d_pos, double* d_energy, hipStream_t st, Analysis kind, double* target) {
   EvalRequest r;
   r.pos = d_pos;
   r.force = c->d_eo_force.p;
   r.energy = d_energy ? d_energy : c->d_energy_tmp.p;
   r.stream = st;
   r.energy_only = true;
-  r.sv_large = true;
-  const bool single = (c->mode & AGBNP_HIP_MODE_SINGLE) != 0;
-  if (single) {
-    c->mode &= ~AGBNP_HIP_MODE_SINGLE;
-    derive_args(c);
-  }
-  int rc;
-  {
-    const Unbind unbind{&c, 1};
-    EvalPlan plan;
-    rc = enqueue_prepare(c, r, plan);
-    if (rc == AGBNP_HIP_OK) rc = enqueue_launch(c, plan, r);
-    if (rc == AGBNP_HIP_OK) {
-      Timeline* tl = c->timeline.enabled ? &c->timeline : nullptr;
-      const hipError_t e = out.matrix ? launch_pair_matrix(c->P, c->sets, c->version, out.matrix, st, tl)
-                                      : launch_decompose(c->P, c->version, out.per_atom, st, tl);
-      if (e != hipSuccess) rc = c->hipfail(e, out.matrix ? "launch_pair_matrix" : "launch_decompose");
-    }
-  }
-  c->last_kind = out.matrix ? 4 : 3;
-  if (single) {
-    c->mode |= AGBNP_HIP_MODE_SINGLE;
-    derive_args(c);
-  }
-  return rc;
+  r.analysis = kind;
+  r.target = target;
+  return r;
 }
 
-// agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host (matrix): the `count` words of the planes or of the matrix and the energy
-// travel back in one buffer; withheld evaluations are repeated
-static int host_analysis(agbnp_hip_context* c, const double* pos, bool matrix, size_t count, double* out, double* energy, const char* who) {
+// A host form's analysis (agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host, a member of agbnp_hip_decompose_group_host): the
+// `count` words of the planes or of the matrix and the energy travel through one buffer [count + 1], cleared first (the device path
+// ADDS).  stage_analysis: the buffers, the positions up, the clear, the request; fetch_analysis: the read-back, in front of the
+// harvest's wait; deliver_analysis: what came back OVERWRITES the caller's
+int stage_analysis(agbnp_hip_context* c, const double* pos, Analysis kind, size_t count, hipStream_t st, EvalRequest* r) {
+  if (c->d_decomp.count != count + 1) HIP_TRY(c, c->d_decomp.alloc(count + 1));
+  c->h_decomp.resize(count + 1);
+  HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, pos, sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(c->d_decomp.p, 0, sizeof(double) * (count + 1), st));
+  *r = energy_request(c, c->d_pos_in.p, c->d_decomp.p + count, st, kind, c->d_decomp.p);
+  return AGBNP_HIP_OK;
+}
+hipError_t fetch_analysis(agbnp_hip_context* c, size_t count, hipStream_t st) {
+  return hipMemcpyAsync(c->h_decomp.data(), c->d_decomp.p, sizeof(double) * (count + 1), hipMemcpyDeviceToHost, st);
+}
+void deliver_analysis(const agbnp_hip_context* c, size_t count, double* out, double* energy) {
+  std::memcpy(out, c->h_decomp.data(), sizeof(double) * count);
+  *energy = c->h_decomp[count];
+}
+
+// agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host: withheld evaluations are repeated
+static int host_analysis(agbnp_hip_context* c, const double* pos, Analysis kind, size_t count, double* out, double* energy, const char* who) {
   HIP_TRY(c, hipSetDevice(c->device));
   const int rc0 = carry_unfinished(c);
   if (rc0 != AGBNP_HIP_OK) return rc0;
-  if (c->d_decomp.count != count + 1) HIP_TRY(c, c->d_decomp.alloc(count + 1));
-  c->h_decomp.resize(count + 1);
   for (int attempt = 0; attempt < 10; attempt++) {
-    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, pos, sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_decomp.p, 0, sizeof(double) * (count + 1), c->stream));
-    AnalysisTarget target;
-    (matrix ? target.matrix : target.per_atom) = c->d_decomp.p;
-    int rc = enqueue_decomposition(c, c->d_pos_in.p, target, c->d_decomp.p + count, c->stream);
+    EvalRequest r;
+    int rc = stage_analysis(c, pos, kind, count, c->stream, &r);
+    if (rc == AGBNP_HIP_OK) rc = enqueue(c, r);
     if (rc != AGBNP_HIP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_decomp.data(), c->d_decomp.p, sizeof(double) * (count + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, fetch_analysis(c, count, c->stream));
     int repeat = 0;
     rc = harvest(c, &repeat, c->stream);  // (its own reads follow on the stream; one wait for everything)
     if (rc != AGBNP_HIP_OK) return rc;
     if (repeat) continue;
-    std::memcpy(out, c->h_decomp.data(), sizeof(double) * count);
-    *energy = c->h_decomp[count];
+    deliver_analysis(c, count, out, energy);
     return AGBNP_HIP_OK;
   }
   return c->fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
@@ -551,17 +539,18 @@ static int host_analysis(agbnp_hip_context* c, const double* pos, bool matrix, s
 
 // (also how agbnp_hip_decompose_group_host repeats a member whose evaluation was withheld)
 int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom, double* energy) {
-  return host_analysis(c, pos, false, 4 * (size_t)c->n, per_atom, energy, "agbnp_hip_decompose_host");
+  return host_analysis(c, pos, Analysis::planes, 4 * (size_t)c->n, per_atom, energy, "agbnp_hip_decompose_host");
 }
 
-// agbnp_hip_decompose_device, agbnp_hip_pair_matrix_device, arguments checked
-static int device_analysis(agbnp_hip_context* c, const double* d_pos, AnalysisTarget out, double* d_energy, void* stream, const char* who) {
+// agbnp_hip_energy_device (no analysis), agbnp_hip_decompose_device, agbnp_hip_pair_matrix_device, arguments checked (the kernel
+// files' comments know this path by its earlier name, enqueue_decomposition)
+static int device_energy(agbnp_hip_context* c, const double* d_pos, Analysis kind, double* target, double* d_energy, void* stream, const char* who) {
   hipStream_t st;
   const int rc = enter(c, stream, &st);
   if (rc != AGBNP_HIP_OK) return rc;
   if (refuse_capture(c, st, who)) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   note_stream(c, stream);
-  return enqueue_decomposition(c, d_pos, out, d_energy, st);
+  return enqueue(c, energy_request(c, d_pos, d_energy, st, kind, target));
 }
 
 // the matrix calls need a partition (agbnp_hip_set_atom_sets)
@@ -581,9 +570,7 @@ int agbnp_hip_decompose_host(agbnp_hip_context* c, const double* pos, double* pe
 int agbnp_hip_decompose_device(agbnp_hip_context* c, const double* d_pos, double* d_per_atom, double* d_energy, void* stream) {
   if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   if (!d_pos || !d_per_atom) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_decompose_device: null pointer");
-  AnalysisTarget target;
-  target.per_atom = d_per_atom;
-  return device_analysis(c, d_pos, target, d_energy, stream, "agbnp_hip_decompose_device");
+  return device_energy(c, d_pos, Analysis::planes, d_per_atom, d_energy, stream, "agbnp_hip_decompose_device");
 }
 
 // The partition is the matrix launch's alone (AtomSets): nothing an evaluation reads changes, so neither does
@@ -627,7 +614,7 @@ int agbnp_hip_pair_matrix_host(agbnp_hip_context* c, const double* pos, double* 
   const int rc = need_sets(c, "agbnp_hip_pair_matrix_host");
   if (rc != AGBNP_HIP_OK) return rc;
   const size_t S = (size_t)c->sets.num_sets;
-  return host_analysis(c, pos, true, S * S, matrix, energy, "agbnp_hip_pair_matrix_host");
+  return host_analysis(c, pos, Analysis::matrix, S * S, matrix, energy, "agbnp_hip_pair_matrix_host");
 }
 
 int agbnp_hip_pair_matrix_device(agbnp_hip_context* c, const double* d_pos, double* d_matrix, double* d_energy, void* stream) {
@@ -635,9 +622,7 @@ int agbnp_hip_pair_matrix_device(agbnp_hip_context* c, const double* d_pos, doub
   if (!d_pos || !d_matrix) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_pair_matrix_device: null pointer");
   const int rc = need_sets(c, "agbnp_hip_pair_matrix_device");
   if (rc != AGBNP_HIP_OK) return rc;
-  AnalysisTarget target;
-  target.matrix = d_matrix;
-  return device_analysis(c, d_pos, target, d_energy, stream, "agbnp_hip_pair_matrix_device");
+  return device_energy(c, d_pos, Analysis::matrix, d_matrix, d_energy, stream, "agbnp_hip_pair_matrix_device");
 }
 
 int agbnp_hip_execute_device(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, void* stream) {
@@ -656,16 +641,7 @@ int agbnp_hip_execute_device(agbnp_hip_context* c, const double* d_pos, double* 
 int agbnp_hip_energy_device(agbnp_hip_context* c, const double* d_pos, double* d_energy, void* stream) {
   if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   if (!d_pos || !d_energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_energy_device: null pointer");
-  EvalRequest r;
-  const int rc = enter(c, stream, &r.stream);
-  if (rc != AGBNP_HIP_OK) return rc;
-  if (refuse_capture(c, r.stream, "agbnp_hip_energy_device")) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  note_stream(c, stream);
-  r.pos = d_pos;
-  r.force = c->d_eo_force.p;
-  r.energy = d_energy;
-  r.energy_only = true;
-  return enqueue(c, r);
+  return device_energy(c, d_pos, Analysis::none, nullptr, d_energy, stream, "agbnp_hip_energy_device");
 }
 
 int agbnp_hip_execute_openmm(agbnp_hip_context* c, const void* d_posq, int posq_is_double, const void* d_posq_correction,

@@ -1,4 +1,6 @@
 // Replica groups (engine_context.h; agbnp_hip_execute_group, group_args.h): the evaluations of several contexts on one set of launches.
+// The three kinds of group call -- full, energy-only, decomposition -- are one description (GroupCall), one check, one device form
+// and one host form; what a kind does differently is in the requests it builds and in the host form's three named steps.
 #include "engine_context.h"
 
 // (shared with the binding groups, engine_binding.hip, whose output pointers may be null: a null span overlaps nothing)
@@ -24,14 +26,26 @@ bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, const EvalRe
   return c->version == 0 || plan.fused || r.energy_only;
 }
 
-// The arguments of a group call, checked before anything is launched or changed.  forces is null for an energy-only call
-// (energy_only says that this was asked for).  d_energies: the device entry points' energy words, one buffer per member, which --
-// like the force buffers [3n] -- must not overlap those of another member; the host entry points pass null.
-// planes: a decomposition group's plane buffers [4n], one per member (null for every other kind of call); they must not overlap
-// one another or an energy word -- said in a message of its own -- and the device form's energies may then be null altogether.
-int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* pos, double* const* forces, bool energy_only,
-                const void* energies, double* const* d_energies, const char* who, double* const* planes = nullptr,
-                bool planes_wanted = false, bool energies_optional = false) {
+// A group call: its kind, and the buffers its entry point was given.  host: the host form -- positions, forces and planes are host
+// arrays and the energies come back in `energies`; the device form has one energy word per member in d_energies.
+enum class GroupKind { full, energy_only, decomposition };
+struct GroupCall {
+  GroupKind kind;
+  const char* who;
+  bool host;
+  const double* const* pos;  // every kind
+  double* const* forces;     // a full call's, [3n] per member
+  double* const* planes;     // a decomposition's, [4n] per member
+  double* const* d_energies;
+  double* energies;
+};
+
+// The arguments of a group call, checked before anything is launched or changed.  Every kind needs positions, a full call forces,
+// a decomposition planes; the energies are the host form's array or the device form's words, which a decomposition alone may leave
+// out altogether.  The device form's outputs -- energy words, force buffers [3n], plane buffers [4n] -- must not overlap those of
+// another member; the planes' clashes, with one another or with an energy word, are said in a message of their own.
+int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
+  const char* const who = g.who;
   if (!ctxs || count < 1 || count > kMaxGroup) {
     if (ctxs && count >= 1 && ctxs[0]) ctxs[0]->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": a group has 1 to 16 members");
     return AGBNP_HIP_ERR_INVALID_ARGUMENT;
@@ -39,7 +53,13 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* 
   for (int i = 0; i < count; i++)
     if (!ctxs[i]) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   agbnp_hip_context* c0 = ctxs[0];
-  if (!pos || (!forces && !energy_only) || (!energies && !energies_optional) || (planes_wanted && !planes))
+  const bool full = g.kind == GroupKind::full, decomposition = g.kind == GroupKind::decomposition;
+  // (what this kind and form read of the description; null below: not theirs)
+  const double* const* pos = g.pos;
+  double* const* forces = full ? g.forces : nullptr;
+  double* const* planes = decomposition ? g.planes : nullptr;
+  double* const* d_energies = g.host ? nullptr : g.d_energies;
+  if (!pos || (full && !forces) || (decomposition && !planes) || (g.host ? !g.energies : !d_energies && !decomposition))
     return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
   for (int i = 0; i < count; i++) {
     if (ctxs[i]->device != c0->device) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": members on different devices");
@@ -77,11 +97,11 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const double* const* 
 // instantiation, the three role workgroups per member --, version 0 the cavity launch and the output launch in its force-less
 // shape.  Both kinds of call build the SAME argument block for a member's parity (the block holds no output pointer, and what
 // the energy-only launches read of it a full call fills too), so a run that mixes them rewrites nothing.
-// A decomposition group (agbnp_hip_decompose_group; the requests carry sv_large and per_atom) is an energy-only set whose cavity
+// A decomposition group (agbnp_hip_decompose_group; the requests carry the planes as their analysis) is an energy-only set whose cavity
 // launch is the instantiation that also collects the enlarged-radius self volumes, with ONE more launch behind it: the planes of
 // every member (decompose_kernels.hip: k_group_decompose; FIVE launches, version 0 three).  The same blocks again.
 int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, const EvalRequest* reqs) {
-  const bool energy_only = reqs[set[0]].energy_only, decomposition = reqs[set[0]].per_atom != nullptr;
+  const bool energy_only = reqs[set[0]].energy_only, decomposition = reqs[set[0]].sv_large();  // (no group entry point asks for a matrix)
   const hipStream_t st = reqs[set[0]].stream;
   agbnp_hip_context* const c0 = ctxs[set[0]];
   const int version = c0->version, variant = c0->variant;
@@ -142,7 +162,7 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
     out.energy[k] = (unsigned long long)(uintptr_t)reqs[i].energy;
     Gplanes.first[k + 1] = Gplanes.first[k] + decompose_blocks(c->n, version);
     Gplanes.args[k] = addr;
-    planes.per_atom[k] = (unsigned long long)(uintptr_t)reqs[i].per_atom;
+    planes.per_atom[k] = (unsigned long long)(uintptr_t)reqs[i].target;
     if (version == 1) {
       lds[1] = std::max(lds[1], sh.born_lds);
       lds[3] = std::max(lds[3], sh.chain_lds);
@@ -154,7 +174,7 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
   }
   for (int s = 0; s < stages; s++) G[s].count = m;
   Gplanes.count = m;
-  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st, reqs[set[0]].sv_large));
+  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st, decomposition));
   if (version == 0) {
     if (energy_only)
       HIP_TRY(c0, launch_group_outputs_energy(G[1], out, lds[1], st));
@@ -181,36 +201,8 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
 // reached get back the counts their enqueue_prepare advanced (enqueue index, five-launch set parity), so that host and device keep
 // counting alike; a member whose launches failed half-way is in the state a failed agbnp_hip_execute_device leaves
 // (AGBNP_HIP_ERR_DEVICE: recreate it).  A member that does not share runs what its own entry point would run for its request.
-// A decomposition group's member that runs alone -- by itself or as a launch set of one -- runs what enqueue_decomposition
-// (engine_eval.hip) runs for it: its evaluation with the sv_large cavity instantiation, then its own plane launch; fast+single
-// with the single-precision option lifted for this call (LiftSingle), as there.
-int member_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest& r) {
-  const int rc = enqueue_launch(c, plan, r);
-  if (rc != AGBNP_HIP_OK || !r.per_atom) return rc;
-  const hipError_t e = launch_decompose(c->P, c->version, r.per_atom, r.stream, c->timeline.enabled ? &c->timeline : nullptr);
-  c->last_kind = 3;
-  return e == hipSuccess ? AGBNP_HIP_OK : c->hipfail(e, "launch_decompose");
-}
-
-// the members of a decomposition group in the fast+single mode: FP64 terms, so the option is off from before their
-// enqueue_prepare until their requests have left the argument blocks (declared in front of the Unbind: destroyed behind it)
-struct LiftSingle {
-  agbnp_hip_context* lifted[kMaxGroup];
-  int count = 0;
-  void lift(agbnp_hip_context* c) {
-    if (!(c->mode & AGBNP_HIP_MODE_SINGLE)) return;
-    c->mode &= ~AGBNP_HIP_MODE_SINGLE;
-    derive_args(c);
-    lifted[count++] = c;
-  }
-  ~LiftSingle() {
-    for (int i = 0; i < count; i++) {
-      lifted[i]->mode |= AGBNP_HIP_MODE_SINGLE;
-      derive_args(lifted[i]);
-    }
-  }
-};
-
+// A decomposition group's member that runs alone -- by itself or as a launch set of one -- runs what agbnp_hip_decompose_device runs
+// for it: enqueue_launch makes its own plane launch; fast+single with the single-precision option lifted for this call (LiftSingle).
 int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* reqs) {
   LiftSingle single;
   const Unbind unbind{ctxs, count};
@@ -226,7 +218,7 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* 
     agbnp_hip_context* const c = ctxs[i];
     was_enqueued[i] = c->enqueued;
     was_five_evals[i] = c->five_evals;
-    if (reqs[i].per_atom) single.lift(c);
+    single.lift(c, reqs[i]);
     const int rc = enqueue_prepare(c, reqs[i], plans[i]);
     prepared = i + 1;
     if (rc != AGBNP_HIP_OK) return undo(rc);
@@ -244,34 +236,34 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* 
     for (int k = 0; k < m; k++) launched[set[k]] = true;
     // (a launch set of one makes the member's own launches: the same kernels without the look-up of its argument block, which
     // costs a dependent scalar load in front of every launch's first use of an argument)
-    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, reqs) : member_launch(ctxs[set[0]], plans[set[0]], reqs[set[0]]);
+    const int rc = m > 1 ? launch_set(ctxs, set, m, plans, reqs) : enqueue_launch(ctxs[set[0]], plans[set[0]], reqs[set[0]]);
     if (rc != AGBNP_HIP_OK) return undo(rc);
     if (m == 1) ctxs[set[0]]->group_members = 1;
   }
   for (int i = 0; i < count; i++) {
     if (shares[i]) continue;
     launched[i] = true;
-    const int rc = member_launch(ctxs[i], plans[i], reqs[i]);
+    const int rc = enqueue_launch(ctxs[i], plans[i], reqs[i]);
     if (rc != AGBNP_HIP_OK) return undo(rc);
   }
   return AGBNP_HIP_OK;
 }
 
-// agbnp_hip_execute_group and -- energy_only, d_forces null: for every member what agbnp_hip_energy_device would do, the sharing
-// members on FOUR (version 0: two) launches per launch set, nothing written to a force buffer of a caller -- agbnp_hip_energy_group
-// and -- decomposition: energy_only with d_planes, d_energies may be null: for every member what agbnp_hip_decompose_device would
-// do, the sharing members on FIVE (version 0: three) launches per launch set -- agbnp_hip_decompose_group
-int group_device(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces, bool energy_only,
-                 double* const* d_energies, void* stream, const char* who, double* const* d_planes = nullptr, bool decomposition = false) {
-  int rc = check_group(ctxs, count, d_positions, d_forces, energy_only, d_energies, d_energies, who, d_planes, decomposition, decomposition);
+// The device forms.  agbnp_hip_execute_group; agbnp_hip_energy_group: for every member what agbnp_hip_energy_device would do, the
+// sharing members on FOUR (version 0: two) launches per launch set, nothing written to a force buffer of a caller;
+// agbnp_hip_decompose_group: for every member what agbnp_hip_decompose_device would do (d_energies may be null), the sharing
+// members on FIVE (version 0: three) launches per launch set
+int group_device(agbnp_hip_context* const* ctxs, int count, const GroupCall& g, void* stream) {
+  int rc = check_group(ctxs, count, g);
   if (rc != AGBNP_HIP_OK) return rc;
   agbnp_hip_context* const c0 = ctxs[0];
   hipStream_t st;
   rc = enter(c0, stream, &st);
   if (rc != AGBNP_HIP_OK) return rc;
+  const bool full = g.kind == GroupKind::full, decomposition = g.kind == GroupKind::decomposition;
   if (is_capturing(st))
-    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream is being captured; " +
-                                                        (decomposition ? "groups and decompositions" : energy_only ? "groups and energy-only evaluations" : "groups") +
+    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(g.who) + ": the stream is being captured; " +
+                                                        (decomposition ? "groups and decompositions" : full ? "groups" : "groups and energy-only evaluations") +
                                                         " are not captured into graphs");
   EvalRequest reqs[kMaxGroup];
   for (int i = 0; i < count; i++) {
@@ -281,14 +273,15 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const double* const*
     // stream is joined to it on both sides instead, so that the member's agbnp_hip_finish(NULL) drains the group's work)
     note_stream(c, stream);
     if (!stream) HIP_TRY(c, join_streams(c->group_event, c->stream, st));
-    reqs[i].pos = d_positions[i];
-    reqs[i].force = energy_only ? c->d_eo_force.p : d_forces[i];
-    // (a decomposition without energy words: into the member's spare word, as agbnp_hip_decompose_device)
-    reqs[i].energy = d_energies ? d_energies[i] : c->d_energy_tmp.p;
+    if (!full) {  // (a decomposition without energy words: into the member's spare word, as agbnp_hip_decompose_device)
+      reqs[i] = energy_request(c, g.pos[i], g.d_energies ? g.d_energies[i] : nullptr, st, decomposition ? Analysis::planes : Analysis::none,
+                               decomposition ? g.planes[i] : nullptr);
+      continue;
+    }
+    reqs[i].pos = g.pos[i];
+    reqs[i].force = g.forces[i];
+    reqs[i].energy = g.d_energies[i];
     reqs[i].stream = st;
-    reqs[i].energy_only = energy_only;
-    reqs[i].sv_large = decomposition;
-    reqs[i].per_atom = decomposition ? d_planes[i] : nullptr;
   }
   rc = group_enqueue(ctxs, count, reqs);
   if (rc != AGBNP_HIP_OK) return rc;
@@ -296,57 +289,41 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const double* const*
   return AGBNP_HIP_OK;
 }
 
-// agbnp_hip_execute_group_host and -- energy_only, forces null -- agbnp_hip_energy_group_host
-int group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces, bool energy_only,
-               double* energies, const char* who) {
-  int rc = check_group(ctxs, count, positions, forces, energy_only, energies, nullptr, who);
-  if (rc != AGBNP_HIP_OK) return rc;
-  const hipStream_t st = ctxs[0]->stream;
-  EvalRequest reqs[kMaxGroup];
-  for (int i = 0; i < count; i++) {
-    agbnp_hip_context* const c = ctxs[i];
-    HIP_TRY(c, hipSetDevice(c->device));
-    rc = carry_unfinished(c);  // (every member's streams are idle from here on)
-    if (rc != AGBNP_HIP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
-    reqs[i].pos = c->d_pos_in.p;
-    reqs[i].force = energy_only ? c->d_eo_force.p : c->d_force_tmp.p;
-    reqs[i].energy = c->d_force_tmp.p + 3 * (size_t)c->n;
-    reqs[i].stream = st;
-    reqs[i].energy_only = energy_only;
-    // (cleared by the cavity launch's trailing workgroups, as in agbnp_hip_execute_host; the staging buffer's energy word with it)
-    reqs[i].zero_out = c->d_force_tmp.p;
-  }
-  rc = group_enqueue(ctxs, count, reqs);
-  if (rc != AGBNP_HIP_OK) return rc;
-  for (int i = 0; i < count; i++) {
-    agbnp_hip_context* const c = ctxs[i];
-    int repeat = 0;
-    rc = harvest(c, &repeat, st);  // (waits for the group's stream)
-    if (rc != AGBNP_HIP_OK) return rc;
-    if (repeat) {  // withheld: repeated alone, as agbnp_hip_execute_host / agbnp_hip_energy_host repeats
-      rc = host_evaluation(c, positions[i], energy_only ? nullptr : forces[i], &energies[i]);
-      if (rc != AGBNP_HIP_OK) return rc;
-      continue;
-    }
-    if (energy_only) {
-      HIP_TRY(c, hipMemcpy(&energies[i], reqs[i].energy, sizeof(double), hipMemcpyDeviceToHost));
-      continue;
-    }
-    const size_t n3 = 3 * (size_t)c->n;
-    c->h_force_tmp.resize(n3 + 1);
-    HIP_TRY(c, hipMemcpy(c->h_force_tmp.data(), c->d_force_tmp.p, sizeof(double) * (n3 + 1), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n3; k++) forces[i][k] += c->h_force_tmp[k];
-    energies[i] = c->h_force_tmp[n3];
-  }
+// The host forms' per-kind steps.  A member stages in d_force_tmp [3n + 1] -- forces and energy in one buffer, cleared by the cavity
+// launch's trailing workgroups as in agbnp_hip_execute_host -- or, a decomposition, in d_decomp [4n + 1] (stage_analysis) ...
+int stage_member(agbnp_hip_context* c, const GroupCall& g, int i, hipStream_t st, EvalRequest* r) {
+  if (g.kind == GroupKind::decomposition) return stage_analysis(c, g.pos[i], Analysis::planes, 4 * (size_t)c->n, st, r);
+  HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, g.pos[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
+  r->pos = c->d_pos_in.p;
+  r->force = g.kind == GroupKind::full ? c->d_force_tmp.p : c->d_eo_force.p;
+  r->energy = c->d_force_tmp.p + 3 * (size_t)c->n;
+  r->stream = st;
+  r->energy_only = g.kind != GroupKind::full;
+  r->zero_out = c->d_force_tmp.p;
+  return AGBNP_HIP_OK;
+}
+// ... a member whose evaluation was withheld is repeated alone, as its own host entry point repeats ...
+int repeat_member(agbnp_hip_context* c, const GroupCall& g, int i) {
+  if (g.kind == GroupKind::decomposition) return host_decomposition(c, g.pos[i], g.planes[i], &g.energies[i]);
+  return host_evaluation(c, g.pos[i], g.kind == GroupKind::full ? g.forces[i] : nullptr, &g.energies[i]);
+}
+// ... and what came back is delivered once the stream is idle: forces ADDED and the energy stored, the energy alone, or the planes
+// OVERWRITTEN (read back in front of the harvest: fetch_analysis; the other two with blocking copies here)
+int deliver_member(agbnp_hip_context* c, const GroupCall& g, int i, const EvalRequest& r) {
+  const size_t n3 = 3 * (size_t)c->n;
+  if (g.kind == GroupKind::decomposition) deliver_analysis(c, 4 * (size_t)c->n, g.planes[i], &g.energies[i]);
+  if (g.kind == GroupKind::energy_only) HIP_TRY(c, hipMemcpy(&g.energies[i], r.energy, sizeof(double), hipMemcpyDeviceToHost));
+  if (g.kind != GroupKind::full) return AGBNP_HIP_OK;
+  c->h_force_tmp.resize(n3 + 1);
+  HIP_TRY(c, hipMemcpy(c->h_force_tmp.data(), c->d_force_tmp.p, sizeof(double) * (n3 + 1), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < n3; k++) g.forces[i][k] += c->h_force_tmp[k];
+  g.energies[i] = c->h_force_tmp[n3];
   return AGBNP_HIP_OK;
 }
 
-// agbnp_hip_decompose_group_host: every member's planes and energy through its own staging buffer [4n + 1], cleared first (the
-// device path ADDS); a member whose evaluation was withheld is repeated alone, as agbnp_hip_decompose_host repeats
-int decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* per_atom,
-                         double* energies, const char* who) {
-  int rc = check_group(ctxs, count, positions, nullptr, true, energies, nullptr, who, per_atom, true);
+// agbnp_hip_execute_group_host, agbnp_hip_energy_group_host, agbnp_hip_decompose_group_host: one skeleton over the kind
+int group_host(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
+  int rc = check_group(ctxs, count, g);
   if (rc != AGBNP_HIP_OK) return rc;
   const hipStream_t st = ctxs[0]->stream;
   EvalRequest reqs[kMaxGroup];
@@ -354,33 +331,18 @@ int decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double
     agbnp_hip_context* const c = ctxs[i];
     HIP_TRY(c, hipSetDevice(c->device));
     rc = carry_unfinished(c);  // (every member's streams are idle from here on)
+    if (rc == AGBNP_HIP_OK) rc = stage_member(c, g, i, st, &reqs[i]);
     if (rc != AGBNP_HIP_OK) return rc;
-    const size_t n4 = 4 * (size_t)c->n;
-    if (c->d_decomp.count != n4 + 1) HIP_TRY(c, c->d_decomp.alloc(n4 + 1));
-    c->h_decomp.resize(n4 + 1);
-    HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, positions[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->d_decomp.p, 0, sizeof(double) * (n4 + 1), st));
-    reqs[i].pos = c->d_pos_in.p;
-    reqs[i].force = c->d_eo_force.p;
-    reqs[i].energy = c->d_decomp.p + n4;
-    reqs[i].stream = st;
-    reqs[i].energy_only = true;
-    reqs[i].sv_large = true;
-    reqs[i].per_atom = c->d_decomp.p;
   }
   rc = group_enqueue(ctxs, count, reqs);
   if (rc != AGBNP_HIP_OK) return rc;
   for (int i = 0; i < count; i++) {
     agbnp_hip_context* const c = ctxs[i];
-    const size_t n4 = 4 * (size_t)c->n;
-    HIP_TRY(c, hipMemcpyAsync(c->h_decomp.data(), c->d_decomp.p, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, st));
+    if (g.kind == GroupKind::decomposition) HIP_TRY(c, fetch_analysis(c, 4 * (size_t)c->n, st));
     int repeat = 0;
     rc = harvest(c, &repeat, st);  // (waits for the group's stream)
-    if (rc == AGBNP_HIP_OK && repeat) rc = host_decomposition(c, positions[i], per_atom[i], &energies[i]);
+    if (rc == AGBNP_HIP_OK) rc = repeat ? repeat_member(c, g, i) : deliver_member(c, g, i, reqs[i]);
     if (rc != AGBNP_HIP_OK) return rc;
-    if (repeat) continue;
-    std::memcpy(per_atom[i], c->h_decomp.data(), sizeof(double) * n4);
-    energies[i] = c->h_decomp[n4];
   }
   return AGBNP_HIP_OK;
 }
@@ -390,31 +352,31 @@ extern "C" {
 
 int agbnp_hip_decompose_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_per_atom,
                               double* const* d_energies, void* stream) {
-  return group_device(ctxs, count, d_positions, nullptr, true, d_energies, stream, "agbnp_hip_decompose_group", d_per_atom, true);
+  return group_device(ctxs, count, {GroupKind::decomposition, "agbnp_hip_decompose_group", false, d_positions, nullptr, d_per_atom, d_energies, nullptr}, stream);
 }
 
 int agbnp_hip_decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* per_atom,
                                    double* energies) {
-  return decompose_group_host(ctxs, count, positions, per_atom, energies, "agbnp_hip_decompose_group_host");
+  return group_host(ctxs, count, {GroupKind::decomposition, "agbnp_hip_decompose_group_host", true, positions, nullptr, per_atom, nullptr, energies});
 }
 
 int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,
                             double* const* d_energies, void* stream) {
-  return group_device(ctxs, count, d_positions, d_forces, false, d_energies, stream, "agbnp_hip_execute_group");
+  return group_device(ctxs, count, {GroupKind::full, "agbnp_hip_execute_group", false, d_positions, d_forces, nullptr, d_energies, nullptr}, stream);
 }
 
 int agbnp_hip_execute_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* forces,
                                  double* energies) {
-  return group_host(ctxs, count, positions, forces, false, energies, "agbnp_hip_execute_group_host");
+  return group_host(ctxs, count, {GroupKind::full, "agbnp_hip_execute_group_host", true, positions, forces, nullptr, nullptr, energies});
 }
 
 int agbnp_hip_energy_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_energies,
                            void* stream) {
-  return group_device(ctxs, count, d_positions, nullptr, true, d_energies, stream, "agbnp_hip_energy_group");
+  return group_device(ctxs, count, {GroupKind::energy_only, "agbnp_hip_energy_group", false, d_positions, nullptr, nullptr, d_energies, nullptr}, stream);
 }
 
 int agbnp_hip_energy_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* energies) {
-  return group_host(ctxs, count, positions, nullptr, true, energies, "agbnp_hip_energy_group_host");
+  return group_host(ctxs, count, {GroupKind::energy_only, "agbnp_hip_energy_group_host", true, positions, nullptr, nullptr, nullptr, energies});
 }
 
 }  // extern "C"
