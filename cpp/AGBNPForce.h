@@ -257,6 +257,27 @@ class HipCalcAGBNPForceKernel {
     return energies;
   }
 
+  // Pair-matrix groups (agbnp_hip_pair_matrix_group_host): the set-pair matrix of every kernel in `kernels` at positions[i]
+  // (3N_i), each over its own partition (setAtomSets(); checked here), the members that can share on the energy-only group's
+  // launches plus one matrix launch per launch set.  matrices[i] receives M[S_i][S_i], row-major (as pairMatrix()); the members'
+  // energies are returned.
+  static std::vector<double> pairMatrixGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,
+                                             const std::vector<std::vector<double>>& positions, std::vector<std::vector<double>>& matrices) {
+    auto g = detail::Group::collect("pairMatrixGroup", kernels, "a group has 1 to 16 members", "one position array per member", true, positions);
+    matrices.resize(kernels.size());
+    std::vector<double*> targets(kernels.size());
+    for (size_t i = 0; i < kernels.size(); i++) {
+      const size_t s = (size_t)kernels[i]->numAtomSets();
+      if (s == 0) throw OpenMMException("pairMatrixGroup(): a member has no partition (setAtomSets())");
+      matrices[i].assign(s * s, 0.0);
+      targets[i] = matrices[i].data();
+    }
+    std::vector<double> energies(kernels.size(), 0.0);
+    detail::check(agbnp_hip_pair_matrix_group_host(g.handles.data(), (int)kernels.size(), g.pos.data(), targets.data(), energies.data()),
+                  g.handles[0]);
+    return energies;
+  }
+
   // The positions of the next evaluation are unrelated to the last ones (agbnp_hip_expect_jump): it lays the neighbour masks
   // down at its own positions first and is not withheld for the jump.
   void expectJump() {
@@ -336,6 +357,34 @@ class Binding {
   // device pointers: the 4N terms and u are ADDED -- all of them or, if a member is withheld, nothing; asynchronous
   void decomposeDevice(const double* dPositions, double* dPerAtom, double* dBindingEnergy, void* stream = nullptr) {
     check(agbnp_hip_binding_decompose_device(b, dPositions, dPerAtom, dBindingEnergy, stream));
+  }
+  // The partition that pairMatrix() tabulates (agbnp_hip_binding_set_atom_sets): sets[i] in 0 .. numSets - 1 is the set of atom i
+  // of the COMPLEX (a set may mix receptor and ligand atoms); numSets < 0: the largest index + 1.  Checked before the library is
+  // touched, as HipCalcAGBNPForceKernel::setAtomSets() checks; a refused partition leaves the earlier one in force.
+  void setAtomSets(const std::vector<int>& sets, int numSets = -1) {
+    if ((int)sets.size() != numParticles) throw OpenMMException("Binding::setAtomSets(): one set index per atom is needed");
+    int lowest = 0, highest = -1;
+    for (int s : sets) lowest = s < lowest ? s : lowest, highest = s > highest ? s : highest;
+    if (numSets < 0) numSets = highest + 1;
+    if (numSets < 1 || numSets > AGBNP_HIP_MAX_SETS) throw OpenMMException("Binding::setAtomSets(): numSets must be 1 .. AGBNP_HIP_MAX_SETS");
+    if (lowest < 0 || highest >= numSets) throw OpenMMException("Binding::setAtomSets(): every set index must be 0 .. numSets - 1");
+    check(agbnp_hip_binding_set_atom_sets(b, numParticles, sets.data(), numSets));
+  }
+  int numAtomSets() const { return agbnp_hip_binding_num_atom_sets(b); }
+  // Set-pair matrix of the binding energy (agbnp_hip_binding_pair_matrix_host): returns u; `matrix` receives D[S][S], row-major,
+  // D = M_RL - M_R - M_L of the members' pairMatrix() tables over the sets of setAtomSets(), which sums to u.  Withheld
+  // evaluations are repeated inside.
+  double pairMatrix(const std::vector<double>& positions, std::vector<double>& matrix) {
+    if ((int)positions.size() != 3 * numParticles) throw OpenMMException("Binding::pairMatrix(): positions must hold 3N values");
+    const size_t s = (size_t)numAtomSets();
+    matrix.assign(s * s + (s == 0), 0.0);  // (no partition: the library refuses, with its message)
+    double u = 0.0;
+    check(agbnp_hip_binding_pair_matrix_host(b, positions.data(), matrix.data(), &u));
+    return u;
+  }
+  // device pointers: the S S entries of D and u are ADDED -- all of them or, if a member is withheld, nothing; asynchronous
+  void pairMatrixDevice(const double* dPositions, double* dMatrix, double* dBindingEnergy, void* stream = nullptr) {
+    check(agbnp_hip_binding_pair_matrix_device(b, dPositions, dMatrix, dBindingEnergy, stream));
   }
   // device pointers: F_lambda, E_lambda and u are ADDED -- all of them or, if a member is withheld, nothing; asynchronous
   void executeDevice(const double* dPositions, double lambda, double* dForces, double* dEnergy, double* dBindingEnergy,

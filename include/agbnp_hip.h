@@ -223,7 +223,8 @@ int agbnp_hip_decompose_device(agbnp_hip_context* ctx, const double* d_positions
  * plane launch.  No pair goes to memory by itself: a tile sums runs of j atoms of one set in registers, the runs in an LDS
  * accumulator by the sets of its two blocks, and leaves with two atomics per pair of sets it met.  The deterministic
  * mode gives a bit-identical matrix from run to run.
- * Not provided: a group form, a binding form, an OpenMM-buffer form. */
+ * Not provided: a group form, a binding form, an OpenMM-buffer form.  (Those of the first two were added later, further down:
+ * agbnp_hip_pair_matrix_group() and agbnp_hip_binding_pair_matrix_*(); there is still no OpenMM-buffer form.) */
 #define AGBNP_HIP_MAX_SETS 2048
 int agbnp_hip_set_atom_sets(agbnp_hip_context* ctx, int num_particles, const int* set_of_atom /*[N], 0..num_sets-1*/, int num_sets);
 int agbnp_hip_num_atom_sets(const agbnp_hip_context* ctx); /* 0: none set */
@@ -332,6 +333,36 @@ int agbnp_hip_decompose_group(agbnp_hip_context* const* ctxs, int count, const d
 int agbnp_hip_decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions,
                                    double* const* per_atom /*overwritten*/, double* energies /*[count]*/);
 
+/* Pair-matrix groups: the conjunction of agbnp_hip_pair_matrix_device() and agbnp_hip_decompose_group(), for set-pair tables that
+ * are averaged over replicas or frames and for the pairwise table of a binding energy.  The contract is that of
+ * agbnp_hip_decompose_group() with the matrix in the place of the planes.  d_positions, d_matrices and d_energies are HOST arrays
+ * of `count` DEVICE pointers; d_energies may be NULL altogether.  For every member i the call does exactly what
+ * agbnp_hip_pair_matrix_device(ctxs[i], d_positions[i], d_matrices[i], d_energies[i], stream) would do: the member's OWN partition
+ * (S_m may differ between members), its S_m S_m entries ADDED to d_matrices[i] and the total to *d_energies[i], both gated on THAT
+ * member's own verdict, ONE evaluation counted in that member's overflow log, scalar 20 reporting 4 and scalar 19 the launch set's
+ * size -- so agbnp_hip_finish(), _poll(), _wait_verdict(), _withheld_evaluations() and _expect_jump() work per member, a withheld
+ * member adds nothing and does not affect the others, and the call interleaves freely with every other kind of call.
+ * Arguments, all checked on the host before anything is launched or any member changes: those of agbnp_hip_decompose_group(); the
+ * matrix spans [S_m S_m] and the energy words must not overlap one another, and a member's energy word must not lie inside its own
+ * matrix (overlap has a message of its own); a member without a partition is refused with AGBNP_HIP_ERR_INVALID_ARGUMENT and
+ * the message says that no partition has been set.  Position buffers may be shared.  Inside a stream capture the call is refused
+ * (AGBNP_HIP_ERR_INVALID_ARGUMENT, the capture stays usable).
+ * Launches.  A member SHARES under the conditions of agbnp_hip_energy_group(); nothing is added to them.  A launch set runs the
+ * decomposition group's first stages -- the energy-only launches with the cavity launch that also collects the enlarged-radius
+ * self volumes -- and behind them ONE matrix launch for all its members (k_group_pair_matrix): FIVE launches (version 0: THREE),
+ * whatever its size.  A set of one, and every member that cannot share (fast, fast+single, deterministic, profiling, six-launch,
+ * captured before), runs what agbnp_hip_pair_matrix_device() runs for it on the same stream.
+ * Argument blocks.  The matrix pointers and the members' partitions travel with the matrix launch alone: all four kinds of group
+ * build the same block for a member's parity, and a steady run that mixes them rewrites nothing (scalar 21). */
+int agbnp_hip_pair_matrix_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions,
+                                double* const* d_matrices /*[count] x [S_m][S_m], ADDED*/,
+                                double* const* d_energies /*NULL, or [count] words, ADDED*/, void* stream);
+/* The synchronous twin for host buffers: positions[i][3 n_i] read, matrices[i][S_i S_i] OVERWRITTEN, energies[i] RETURNED (no NULL
+ * pointer; the members' matrices must not overlap).  Withheld members are repeated inside, alone, as agbnp_hip_pair_matrix_host()
+ * does. */
+int agbnp_hip_pair_matrix_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions,
+                                     double* const* matrices /*overwritten*/, double* energies /*[count]*/);
+
 /* A hint: the positions of the NEXT evaluation of this context are unrelated to those of the last one (another replica's
  * conformation in an exchange matrix, a restart, a Monte Carlo move).  In the five-launch mode the neighbour masks carry a skin,
  * and a heavy atom that has moved more than 0.04 nm since they were laid down makes the evaluation a jump: withheld, reported
@@ -437,6 +468,43 @@ int agbnp_hip_binding_decompose_device(agbnp_hip_binding* b, const double* d_pos
                                        double* d_binding_energy /*may be NULL; u ADDED*/, void* stream);
 int agbnp_hip_binding_decompose_host(agbnp_hip_binding* b, const double* positions, double* per_atom /*overwritten*/,
                                      double* binding_energy);
+/* Set-pair matrix of a binding energy: which receptor set pays how much against which ligand set, and how much the ligand's
+ * arrival changes the interaction of two receptor sets -- the pairwise table of an MM-GBSA decomposition, which the per-atom
+ * planes above cannot give.  A partition over the atoms of the COMPLEX (S sets, 1 .. AGBNP_HIP_MAX_SETS; sets may mix receptor
+ * and ligand atoms) is restricted to each member through the binding's index maps, with the SAME set numbering and the SAME S:
+ * a set with no atom in a member is an empty set there.  With M_RL, M_R, M_L the members' matrices of agbnp_hip_pair_matrix_*()
+ * at the complex's positions, each S x S,
+ *   D[a][b] = M_RL[a][b] - M_R[a][b] - M_L[a][b],   sum_{a,b} D[a][b] = u = E_RL - E_R - E_L.
+ * D is symmetric; row a sums to sum_{i in a} sum_t D[t][i] of agbnp_hip_binding_decompose_*(); for a set a wholly in the receptor
+ * and a set b wholly in the ligand D[a][b] = M_RL[a][b], the direct GB interaction; for two receptor sets D[a][b] is what the
+ * ligand's presence changes of their interaction.  Version 0 fills the diagonal only.  There is no lambda.
+ *   agbnp_hip_binding_set_atom_sets      the partition, set_of_atom[N] in the complex's atom order, validated entirely on the
+ *                                        host first: a refused one (wrong N, a value outside 0 .. num_sets - 1, num_sets out of
+ *                                        range, a null pointer) leaves the previous partition in force in all three members.
+ *                                        agbnp_hip_binding_update_parameters() keeps the partition
+ *   agbnp_hip_binding_num_atom_sets      S, or 0 when none has been set
+ *   agbnp_hip_binding_pair_matrix_device asynchronous; the S S entries of D are ADDED to d_matrix and u to *d_binding_energy
+ *                                        (may be NULL) -- all of it or, if ANY member's evaluation is withheld, nothing
+ *   agbnp_hip_binding_pair_matrix_host   synchronous; matrix[S S] OVERWRITTEN, *binding_energy RETURNED (may be NULL); withheld
+ *                                        evaluations are repeated inside, up to ten times
+ * An evaluation is the three steps of the binding decomposition on one stream: the gather launch, ONE
+ * agbnp_hip_pair_matrix_group() over {complex, receptor, ligand} -- where the three share a launch set: five launches (version
+ * 0: three) -- into a staging buffer of the binding's own, and one combine launch (one thread per cell), which reads the three
+ * verdicts, adds D and u only if all three completed, and clears the staging words whatever the verdict: 1 + 5 + 1 launches.
+ * The staging buffer holds [3][S][S] doubles and three energy words: 24 S^2 bytes -- 1.6 MB for 258 residues, 100 MB at 2048
+ * sets.  It is made at the first matrix call and remade when S changes, after the streams that may read it have drained.
+ * It is ONE binding evaluation of the one log above: agbnp_hip_binding_finish, _withheld_evaluations and _expect_jump apply, and
+ * the call may be interleaved with the other binding calls in any order on one stream.  The combine is elementwise: in the
+ * deterministic mode D is bit-identical from run to run.  Without a partition both forms return
+ * AGBNP_HIP_ERR_INVALID_ARGUMENT and the message says that no partition has been set.  Inside a stream capture the call is
+ * refused before anything is launched.  If the members' group call fails, no combine launch is made and the staging buffer is
+ * cleared on the stream.  Not provided: a matrix inside binding groups, an OpenMM-buffer form. */
+int agbnp_hip_binding_set_atom_sets(agbnp_hip_binding* b, int num_particles, const int* set_of_atom /*[N] complex order*/, int num_sets);
+int agbnp_hip_binding_num_atom_sets(const agbnp_hip_binding* b); /* 0: none set */
+int agbnp_hip_binding_pair_matrix_device(agbnp_hip_binding* b, const double* d_positions, double* d_matrix /*[S][S], ADDED*/,
+                                         double* d_binding_energy /*may be NULL; u ADDED*/, void* stream);
+int agbnp_hip_binding_pair_matrix_host(agbnp_hip_binding* b, const double* positions, double* matrix /*overwritten*/,
+                                       double* binding_energy /*may be NULL*/);
 int agbnp_hip_binding_finish(agbnp_hip_binding* b, void* stream, int* must_repeat);
 int agbnp_hip_binding_withheld_evaluations(const agbnp_hip_binding* b, int* indices, int capacity);
 int agbnp_hip_binding_expect_jump(agbnp_hip_binding* b);

@@ -171,6 +171,27 @@ def _forces_array(forces, n, refusal):
         raise OpenMMException(refusal)
 
 
+def _partition(sets, num_sets, n):
+    """A partition of n atoms as set_atom_sets() takes it (a kernel's, a BindingEnergy's), checked as the library checks it:
+    (sets as an int32 array, num_sets); num_sets None: max(sets) + 1."""
+    try:
+        given = np.asarray(sets)
+        sets = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
+        exact = given.ndim == 1 and np.array_equal(sets, given)  # (no fraction, no wrap-around into the int)
+    except (TypeError, ValueError, OverflowError):
+        raise OpenMMException("set_atom_sets(): sets must be a list of set indices, one per atom")
+    if not exact or sets.size != n:
+        raise OpenMMException("set_atom_sets(): sets must hold one integer set index per atom")
+    if num_sets is None:
+        num_sets = int(sets.max()) + 1 if sets.size else 0
+    num_sets = int(num_sets)
+    if not 1 <= num_sets <= _lib.MAX_SETS:
+        raise OpenMMException(f"set_atom_sets(): num_sets must be 1 .. {_lib.MAX_SETS}")
+    if sets.min() < 0 or sets.max() >= num_sets:
+        raise OpenMMException("set_atom_sets(): every set index must be 0 .. num_sets - 1")
+    return sets, num_sets
+
+
 def _check(rc, error_handle=None):
     """A return code of the library: a failure raises with the message the library keeps for `error_handle` (None: the message
     of the calls that are not made on a context)."""
@@ -257,6 +278,7 @@ class HipCalcAGBNPForceKernel(_Handle):
         _check(_lib.load().agbnp_hip_create(C.byref(handle), *parameters, force.getVersion(), force.getNonbondedMethod(),
                                             force.getCutoffDistance(), self._device))
         self._h = handle
+        self._num_sets = 0  # (a new context has no partition)
         if self._mode:
             self._call("agbnp_hip_set_mode", self._mode)
 
@@ -341,22 +363,11 @@ class HipCalcAGBNPForceKernel(_Handle):
         empty.  num_sets defaults to max(sets) + 1.  Replaces an earlier partition and survives copyParametersToContext();
         changes nothing an evaluation reads.  The input is checked here, before the library is touched."""
         self._need()
-        try:
-            given = np.asarray(sets)
-            sets = np.ascontiguousarray(given, dtype=np.int32).reshape(-1)
-            exact = given.ndim == 1 and np.array_equal(sets, given)  # (no fraction, no wrap-around into the int)
-        except (TypeError, ValueError, OverflowError):
-            raise OpenMMException("set_atom_sets(): sets must be a list of set indices, one per atom")
-        if not exact or sets.size != self.numParticles:
-            raise OpenMMException("set_atom_sets(): sets must hold one integer set index per atom")
-        if num_sets is None:
-            num_sets = int(sets.max()) + 1 if sets.size else 0
-        num_sets = int(num_sets)
-        if not 1 <= num_sets <= _lib.MAX_SETS:
-            raise OpenMMException(f"set_atom_sets(): num_sets must be 1 .. {_lib.MAX_SETS}")
-        if sets.min() < 0 or sets.max() >= num_sets:
-            raise OpenMMException("set_atom_sets(): every set index must be 0 .. num_sets - 1")
+        sets, num_sets = _partition(sets, num_sets, self.numParticles)
         self._call("agbnp_hip_set_atom_sets", int(sets.size), _ip(sets), num_sets)
+        self._num_sets = num_sets
+
+    _num_sets = 0  # S of the partition set through THIS object (pair_matrix_group() checks it before the library is reached)
 
     def num_atom_sets(self):
         """The number of sets of the partition in force; 0: none has been set."""
@@ -578,6 +589,45 @@ class BindingEnergy(_Handle):
         self._call("agbnp_hip_binding_decompose_device", C.c_void_p(d_positions), C.c_void_p(d_per_atom), _ptr(d_binding_energy),
                    _ptr(stream))
 
+    _num_sets = 0
+
+    def set_atom_sets(self, sets, num_sets=None):
+        """The partition that pair_matrix() tabulates (include/agbnp_hip.h, agbnp_hip_binding_set_atom_sets): sets[i] in
+        0 .. num_sets - 1 is the set of atom i of the COMPLEX -- its residue, say; a set may mix receptor and ligand atoms.
+        Every member gets the restriction to its atoms with the same numbering and the same S.  num_sets defaults to
+        max(sets) + 1.  Replaces an earlier partition and survives copyParametersToContext(); a refused one leaves the earlier
+        one in force.  The input is checked here as a kernel's set_atom_sets() checks it, before the library is touched."""
+        self._need()
+        sets, num_sets = _partition(sets, num_sets, self.numParticles)
+        self._call("agbnp_hip_binding_set_atom_sets", int(sets.size), _ip(sets), num_sets)
+        self._num_sets = num_sets
+
+    def num_atom_sets(self):
+        """The number of sets of the partition in force; 0: none has been set."""
+        return int(self._library().agbnp_hip_binding_num_atom_sets(self._h))
+
+    def pair_matrix(self, positions):
+        """Set-pair matrix of the binding energy (include/agbnp_hip.h, agbnp_hip_binding_pair_matrix_host): returns (D, u) with D
+        a float64 array [S, S] over the sets of set_atom_sets(), D = M_RL - M_R - M_L of the members' pair_matrix() tables at the
+        complex's positions.  D is symmetric, D.sum() = u, row a sums to the share of set a in decompose()'s terms; for a
+        receptor set a and a ligand set b D[a, b] is their direct GB interaction (half of it: D[b, a] is the other half), for
+        two receptor sets what the ligand's presence changes between them.  Version 0 fills the diagonal only.  Withheld
+        evaluations are repeated inside."""
+        pos = self._positions(positions, "pair_matrix")
+        s = max(self.num_atom_sets(), 1)  # (no partition: the library refuses, with its message)
+        matrix = np.zeros((s, s))
+        u = C.c_double(0.0)
+        self._call("agbnp_hip_binding_pair_matrix_host", _dp(pos), _dp(matrix), C.byref(u))
+        return matrix, u.value
+
+    def pair_matrix_device(self, d_positions, d_matrix, d_binding_energy=None, stream=None):
+        """Device-resident form of pair_matrix(): the S S entries of D are ADDED to d_matrix (row-major FP64) and u to
+        *d_binding_energy when it is given -- all of it or, if any member's evaluation is withheld, nothing; raw device pointers
+        (ints).  One binding evaluation in the binding's log; asynchronous, call finish().  Refused (OpenMMException) inside a
+        stream capture and without a partition."""
+        self._call("agbnp_hip_binding_pair_matrix_device", C.c_void_p(d_positions), C.c_void_p(d_matrix), _ptr(d_binding_energy),
+                   _ptr(stream))
+
     def finish(self, stream=None):
         """Drains the stream, finishes the three members and returns the number of binding evaluations since the previous
         finish() with at least one withheld member: NOTHING of those reached the caller's buffers; run them again (withheld())."""
@@ -609,6 +659,7 @@ class BindingEnergy(_Handle):
         view = _MemberView(self._device)
         view._h = C.c_void_p(_lib.load().agbnp_hip_binding_member(self._h, which))
         view._mode = self._mode
+        view._num_sets = self._num_sets
         view.numParticles = (self.numParticles, len(self._receptor), len(self._ligand))[which]
         return view
 
@@ -624,7 +675,7 @@ class _MemberView(HipCalcAGBNPForceKernel):
 
 
 # ---- groups: replica groups of kernels, binding groups of bindings --------------------------------------------------------------
-# Each of the ten entry points is: the members, checked; what crosses the C ABI, marshalled; one call; the result.
+# Each of the twelve entry points is: the members, checked; what crosses the C ABI, marshalled; one call; the result.
 def _members(who, members, cls):
     """The members of a group call as a list, checked: their number, their class, each with a handle, distinct where the
     library demands it (cls._GROUP)."""
@@ -750,6 +801,54 @@ def decompose_group_host(kernels, positions):
     energies = np.zeros(len(kernels))
     _check(_lib.load().agbnp_hip_decompose_group_host(hs, len(kernels), pos, planes, _dp(energies)), kernels[0]._h)
     return [float(e) for e in energies], terms
+
+
+def _matrix_members(who, kernels):
+    """The members of a pair-matrix group, checked, and their S: every member needs a partition set through set_atom_sets()."""
+    kernels = _members(who, kernels, HipCalcAGBNPForceKernel)
+    for i, k in enumerate(kernels):
+        if k._num_sets < 1:
+            raise OpenMMException(f"{who}(): member {i}: no partition has been set (set_atom_sets())")
+    return kernels, [k._num_sets for k in kernels]
+
+
+def pair_matrix_group(kernels, d_positions, d_matrices, d_energies=None, stream=None):
+    """Pair-matrix groups (include/agbnp_hip.h, agbnp_hip_pair_matrix_group): one call that enqueues a set-pair matrix of every
+    kernel in `kernels`, the members that can share on the energy-only group's launches plus ONE matrix launch per launch set.
+    d_positions, d_matrices, d_energies: lists of raw FP64 device
+    pointers (ints), one per member; d_energies may be None (no totals).  Every member uses its own partition: its matrix
+    [S_i, S_i] and its total are ADDED, gated on its own verdict, as by its pair_matrix_device().  Position buffers may be
+    shared; the matrices and energy words must not overlap, which is checked here -- like the members' partitions -- before the
+    library is reached.  Asynchronous; each member's finish() reports its own withheld evaluations."""
+    who = "pair_matrix_group"
+    kernels, sizes = _matrix_members(who, kernels)
+    hs, pos, mats, ene = _pointer_arrays(who, kernels, True, d_positions=d_positions, d_matrices=d_matrices, d_energies=d_energies)
+    if pos is None or mats is None:
+        raise OpenMMException(f"{who}(): d_positions and d_matrices are needed")
+    # the output spans in bytes: every member's matrix, then (where given) its energy word
+    spans = [(int(p or 0), 8 * s * s) for p, s in zip(d_matrices, sizes)]
+    spans += [(int(p or 0), 8) for p in (d_energies or ())]
+    if any(a == 0 for a, _ in spans) or any(not p for p in d_positions):
+        raise OpenMMException(f"{who}(): null pointer")
+    for i, (a, na) in enumerate(spans):
+        for j, (b, nb) in enumerate(spans[:i]):
+            if a < b + nb and b < a + na:
+                words = j >= len(kernels)  # (both are energy words: the library's own message for those)
+                raise OpenMMException(f"{who}(): " + ("energy words" if words else "matrices") + " of two members overlap")
+    _check(_lib.load().agbnp_hip_pair_matrix_group(hs, len(kernels), pos, mats, ene, _ptr(stream)), kernels[0]._h)
+
+
+def pair_matrix_group_host(kernels, positions):
+    """Synchronous twin of pair_matrix_group() for host buffers: positions[i] (N_i x 3) are read; returns the lists (energies,
+    matrices) with matrices[i] a float64 array [S_i, S_i] over member i's own partition.  Withheld members are repeated inside."""
+    who = "pair_matrix_group_host"
+    kernels, sizes = _matrix_members(who, kernels)
+    hs, pos, _, _ = _host_arrays(who, kernels, positions)
+    matrices = [np.zeros((s, s)) for s in sizes]
+    mats = (C.POINTER(C.c_double) * len(kernels))(*[_dp(m) for m in matrices])
+    energies = np.zeros(len(kernels))
+    _check(_lib.load().agbnp_hip_pair_matrix_group_host(hs, len(kernels), pos, mats, _dp(energies)), kernels[0]._h)
+    return [float(e) for e in energies], matrices
 
 
 def binding_execute_group(bindings, d_positions, d_lambdas, d_forces, d_energies=None, d_binding_energies=None, stream=None):

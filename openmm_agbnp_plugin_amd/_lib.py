@@ -42,6 +42,8 @@ SIGNATURES = {
     "agbnp_hip_energy_group_host": [_vpp, _i, _dpp, _dp],
     "agbnp_hip_decompose_group": [_vpp, _i, _vpp, _vpp, _vpp, _vp],
     "agbnp_hip_decompose_group_host": [_vpp, _i, _dpp, _dpp, _dp],
+    "agbnp_hip_pair_matrix_group": [_vpp, _i, _vpp, _vpp, _vpp, _vp],
+    "agbnp_hip_pair_matrix_group_host": [_vpp, _i, _dpp, _dpp, _dp],
     "agbnp_hip_expect_jump": [_vp],
     "agbnp_hip_atom_order_changed": [_vp],
     "agbnp_hip_finish": [_vp, _vp, _ip],
@@ -74,6 +76,10 @@ SIGNATURES = {
     "agbnp_hip_binding_energy_host": [_vp, _dp, _d, _dp, _dp],
     "agbnp_hip_binding_decompose_device": [_vp, _vp, _vp, _vp, _vp],
     "agbnp_hip_binding_decompose_host": [_vp, _dp, _dp, _dp],
+    "agbnp_hip_binding_set_atom_sets": [_vp, _i, _ip, _i],
+    "agbnp_hip_binding_num_atom_sets": [_vp],
+    "agbnp_hip_binding_pair_matrix_device": [_vp, _vp, _vp, _vp, _vp],
+    "agbnp_hip_binding_pair_matrix_host": [_vp, _dp, _dp, _dp],
     "agbnp_hip_binding_finish": [_vp, _vp, _ip],
     "agbnp_hip_binding_withheld_evaluations": [_vp, _ip, _i],
     "agbnp_hip_binding_expect_jump": [_vp],

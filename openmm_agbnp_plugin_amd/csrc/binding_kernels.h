@@ -37,6 +37,13 @@ hipError_t launch_binding_combine_energy(const BindingVerdicts& v, double lambda
 hipError_t launch_binding_decompose_combine(int n, int nr, const BindingVerdicts& v, const int* complex2sub, double* t_complex,
                                             double* t_sub, double* e, double* d_per_atom, double* d_binding, hipStream_t st);
 
+// The set-pair matrix of a binding (agbnp_hip_binding_pair_matrix_*): one thread per cell of the S x S matrix, thread 0 the
+// scalars.  m[3][S S] (the complex's, the receptor's and the ligand's matrix, one set numbering) and e[3] are the binding's own
+// staging words, which the members of one agbnp_hip_pair_matrix_group ADDED to: read, and CLEARED whatever the verdict.
+// D[a][b] = m[0][a][b] - m[1][a][b] - m[2][a][b] is ADDED to d_matrix[S S], u to *d_binding (may be null).
+hipError_t launch_binding_matrix_combine(int num_sets, const BindingVerdicts& v, double* m, double* e, double* d_matrix, double* d_binding,
+                                         hipStream_t st);
+
 // ---- Binding groups (agbnp_hip_binding_execute_group / _energy_group): the same two launches, made once for up to
 // kMaxBindingGroup bindings.  Every binding keeps the grid it would launch alone; the grids lie side by side and a workgroup finds
 // its binding by its number (first[]), as the workgroups of a replica group's launches do (group_args.h: GroupLaunch::first).

@@ -134,6 +134,25 @@ __global__ __launch_bounds__(256) void k_binding_decompose_combine(int n, int nr
   }
 }
 
+// ---- set-pair matrix of a binding (agbnp_hip_binding_pair_matrix_*): D[a][b] = M_RL[a][b] - M_R[a][b] - M_L[a][b] ----
+// Behind ONE agbnp_hip_pair_matrix_group over {complex, receptor, ligand}, whose members ADDED their matrices -- all three [S][S],
+// one set numbering -- and energies to the binding's staging buffer m[3][cells] | e[3]: one thread per cell reads its three words,
+// CLEARS them whatever the verdict, and adds the difference to the caller's matrix if all three members are complete.  Thread 0
+// is also the role lane, as in k_binding_decompose_combine.  Every cell is read by the thread that clears it, through vector loads
+// in front of its own vector stores.  Elementwise: bit-identical from run to run where the members are.
+__global__ __launch_bounds__(256) void k_binding_matrix_combine(size_t cells, BindingVerdicts v, double* m, double* __restrict__ e,
+                                                                double* d_matrix, double* __restrict__ d_binding) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= cells) return;
+  const bool ok = binding_complete(v);
+  if (c == 0) binding_scalars(ok, 1.0, e, nullptr, d_binding);  // the role lane: u = E_RL - E_R - E_L
+  const double m_rl = m[c], m_r = m[cells + c], m_l = m[2 * cells + c];
+  m[c] = 0.0;
+  m[cells + c] = 0.0;
+  m[2 * cells + c] = 0.0;
+  if (ok) d_matrix[c] += m_rl - m_r - m_l;
+}
+
 // ---- binding groups: the same launches once for all bindings of a call (binding_kernels.h: BindingGroupArgs) ----
 static_assert(sizeof(BindingGroupMember) == 120 && sizeof(BindingGroupArgs) == 2000, "BindingGroupArgs: the size binding_kernels.h states");
 static_assert(sizeof(BindingGroupArgs) <= 4096, "a kernel's arguments take 4096 bytes at most");
@@ -206,6 +225,13 @@ hipError_t launch_binding_decompose_combine(int n, int nr, const BindingVerdicts
                                             double* t_sub, double* e, double* d_per_atom, double* d_binding, hipStream_t st) {
   hipLaunchKernelGGL(k_binding_decompose_combine, dim3((n + 255) / 256), dim3(256), 0, st, n, nr, v, complex2sub, t_complex, t_sub, e,
                      d_per_atom, d_binding);
+  return hipGetLastError();
+}
+
+hipError_t launch_binding_matrix_combine(int num_sets, const BindingVerdicts& v, double* m, double* e, double* d_matrix, double* d_binding,
+                                         hipStream_t st) {
+  const size_t cells = (size_t)num_sets * (size_t)num_sets;  // (at most 2048^2: 16384 workgroups)
+  hipLaunchKernelGGL(k_binding_matrix_combine, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, cells, v, m, e, d_matrix, d_binding);
   return hipGetLastError();
 }
 

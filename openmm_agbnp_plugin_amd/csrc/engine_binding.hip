@@ -12,8 +12,8 @@
 // host lambda), the single-binding launches and otherwise the group launches, as group_enqueue makes a member's own launches
 // for a launch set of one; the host entry points of both stage and deliver through binding_stage and binding_deliver.  What
 // the single and the group entry points keep of their own is their argument checks.  The per-atom decomposition is a second, single
-// enqueue (binding_decompose_enqueue) that starts as the first does (binding_enter); both single host forms repeat a withheld
-// evaluation in one loop (binding_retry).
+// enqueue (binding_decompose_enqueue) that starts as the first does (binding_enter), the set-pair matrix a third of the same shape
+// (binding_matrix_enqueue); all single host forms repeat a withheld evaluation in one loop (binding_retry).
 // Messages of failed binding calls are the calling thread's agbnp_hip_last_error(NULL).
 #include "binding_kernels.h"
 #include "engine_context.h"
@@ -45,6 +45,14 @@ struct agbnp_hip_binding {
   // decomposition group ADD to, cleared by every combine launch.  d_decomp: the host form's staging, [3n] positions | [4n] D | u
   DevBuf<double> d_planes, d_decomp;
   std::vector<double> h_decomp;  // [4n + 1] D and u, read back
+  // set-pair matrices (agbnp_hip_binding_pair_matrix_*).  set_of_atom: the partition over the complex's atoms, [n], num_sets
+  // sets (0: none set); every member holds its restriction, same numbering, same S.  d_matrices: [3][S][S] the members'
+  // matrices | [3] the three energies -- what the members of the matrix group ADD to, cleared by every combine launch; made at the
+  // first matrix call, released when S changes.  d_matrix_host: the host form's staging, [3n] positions | [S S] D | u
+  std::vector<int> set_of_atom;
+  int num_sets = 0;
+  DevBuf<double> d_matrices, d_matrix_host;
+  std::vector<double> h_matrix;  // [S S + 1] D and u, read back
 
   double* sub_pos() const { return d_work.p; }
   double* f_complex() const { return d_work.p + 3 * (size_t)n; }
@@ -226,6 +234,42 @@ int binding_decompose_enqueue(agbnp_hip_binding* b, const double* d_pos, double*
   return AGBNP_HIP_OK;
 }
 
+// the matrix calls need a partition (agbnp_hip_binding_set_atom_sets)
+int binding_need_sets(const agbnp_hip_binding* b, const char* who) {
+  if (b->num_sets > 0) return AGBNP_HIP_OK;
+  return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": no partition has been set (agbnp_hip_binding_set_atom_sets)");
+}
+
+// One set-pair matrix of b on `stream` (NULL: the complex's own); the arguments have been checked and a partition is set.  The
+// gather launch, ONE agbnp_hip_pair_matrix_group over the three members through the public entry point -- their matrices and
+// energies into d_matrices -- and the combine launch, which reads the three verdicts and adds D and u all or nothing.
+int binding_matrix_enqueue(agbnp_hip_binding* b, const double* d_pos, double* d_matrix, double* d_binding, void* stream, const char* who) {
+  hipStream_t st;
+  const int entered = binding_enter(&b, 1, stream, &st, who);
+  if (entered != AGBNP_HIP_OK) return entered;
+  const size_t cells = (size_t)b->num_sets * (size_t)b->num_sets, words = kBindingMembers * cells + kBindingMembers;
+  if (b->d_matrices.p == nullptr) {  // (the first matrix call, or the first since S changed: agbnp_hip_binding_set_atom_sets)
+    BINDING_TRY(who, b->d_matrices.alloc(words));
+    BINDING_TRY(who, hipMemsetAsync(b->d_matrices.p, 0, sizeof(double) * words, st));
+  }
+  double* const m = b->d_matrices.p;
+  double* const e = m + kBindingMembers * cells;
+  BINDING_TRY(who, launch_binding_gather(b->n, d_pos, b->d_maps.p, b->sub_pos(), st));
+  const double* const pos[kBindingMembers] = {d_pos, b->sub_pos(), b->sub_pos() + 3 * (size_t)b->nr};
+  double* const matrices[kBindingMembers] = {m, m + cells, m + 2 * cells};
+  double* const ene[kBindingMembers] = {e, e + 1, e + 2};
+  // (a NULL stream is the group's first member's own: the complex's, `st`)
+  const int rc = agbnp_hip_pair_matrix_group(b->m, kBindingMembers, pos, matrices, ene, stream);
+  if (rc != AGBNP_HIP_OK) {
+    // no combine launch will read and clear what the members that got as far as their launches added: cleared here, as the
+    // decomposition does
+    (void)hipMemsetAsync(m, 0, sizeof(double) * words, st);
+    return member_fail(b, rc, who);
+  }
+  BINDING_TRY(who, launch_binding_matrix_combine(b->num_sets, binding_verdicts(b), m, e, d_matrix, d_binding, st));
+  return AGBNP_HIP_OK;
+}
+
 // a device entry point has enqueued an evaluation of b on `stream`
 void binding_note(agbnp_hip_binding* b, void* stream) {
   b->enqueued++;
@@ -311,6 +355,28 @@ int binding_decompose_host(agbnp_hip_binding* b, const double* pos, double* per_
   return binding_retry(b, who, stage, [&] {
     std::memcpy(per_atom, b->h_decomp.data(), sizeof(double) * n4);
     if (binding_energy) *binding_energy = b->h_decomp[n4];
+  });
+}
+
+// agbnp_hip_binding_pair_matrix_host: staged in d_matrix_host (remade when S changes: the complex's stream is idle between host
+// calls), [3n] positions | [S S] D | u, the outputs cleared first
+int binding_matrix_host(agbnp_hip_binding* b, const double* pos, double* matrix, double* binding_energy, const char* who) {
+  const size_t n3 = 3 * (size_t)b->n, cells = (size_t)b->num_sets * (size_t)b->num_sets;
+  auto stage = [&]() -> int {
+    const hipStream_t st = b->m[0]->stream;
+    if (b->d_matrix_host.count != n3 + cells + 1) BINDING_TRY(who, b->d_matrix_host.alloc(n3 + cells + 1));
+    b->h_matrix.resize(cells + 1);
+    double* const d_out = b->d_matrix_host.p + n3;
+    BINDING_TRY(who, hipMemcpyAsync(b->d_matrix_host.p, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
+    BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (cells + 1), st));
+    const int rc = binding_matrix_enqueue(b, b->d_matrix_host.p, d_out, d_out + cells, nullptr, who);
+    if (rc != AGBNP_HIP_OK) return rc;
+    BINDING_TRY(who, hipMemcpyAsync(b->h_matrix.data(), d_out, sizeof(double) * (cells + 1), hipMemcpyDeviceToHost, st));
+    return AGBNP_HIP_OK;
+  };
+  return binding_retry(b, who, stage, [&] {
+    std::memcpy(matrix, b->h_matrix.data(), sizeof(double) * cells);
+    if (binding_energy) *binding_energy = b->h_matrix[cells];
   });
 }
 
@@ -584,6 +650,64 @@ int agbnp_hip_binding_decompose_host(agbnp_hip_binding* b, const double* positio
   if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   if (!positions || !per_atom) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
   return binding_decompose_host(b, positions, per_atom, binding_energy, who);
+}
+
+// The partition is checked here, entirely, before any member is touched: what a member's agbnp_hip_set_atom_sets could refuse of
+// its restriction has been refused already, so a refused partition leaves the previous one in force in all three.  Each member
+// gets the restriction to its atoms in its own atom order, with the complex's set numbers and S (a set without an atom in a member
+// is an empty set there).  The members wait for what may be reading the tables they replace; the staging buffer of another S is
+// released behind them, once the caller streams the binding has noted have drained too.
+int agbnp_hip_binding_set_atom_sets(agbnp_hip_binding* b, int n, const int* set_of_atom, int num_sets) {
+  const char* who = "agbnp_hip_binding_set_atom_sets";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!set_of_atom) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (n != b->n) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the number of particles differs from the complex's");
+  if (num_sets < 1 || num_sets > AGBNP_HIP_MAX_SETS)
+    return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": num_sets must be 1 .. AGBNP_HIP_MAX_SETS");
+  for (int i = 0; i < n; i++)
+    if (set_of_atom[i] < 0 || set_of_atom[i] >= num_sets)
+      return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                          std::string(who) + ": atom " + std::to_string(i) + " names a set outside 0 .. num_sets - 1");
+  clear_member_errors(b);
+  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {b->n, b->nr, b->nl};
+  for (int k = 0; k < kBindingMembers; k++) {
+    std::vector<int> own(count[k]);
+    for (int t = 0; t < count[k]; t++) own[t] = set_of_atom[k == 0 ? t : b->sub2complex[first[k] + t]];
+    const int rc = agbnp_hip_set_atom_sets(b->m[k], count[k], own.data(), num_sets);
+    if (rc != AGBNP_HIP_OK) return member_fail(b, rc, who);  // (a device error: nothing the checks above could have found)
+  }
+  if (num_sets != b->num_sets && b->d_matrices.p) {
+    BINDING_TRY(who, hipSetDevice(b->device));
+    BINDING_TRY(who, hipStreamSynchronize(b->m[0]->stream));
+    for (void* s : b->streams) BINDING_TRY(who, hipStreamSynchronize((hipStream_t)s));
+    b->d_matrices.release();
+  }
+  b->set_of_atom.assign(set_of_atom, set_of_atom + n);
+  b->num_sets = num_sets;
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_binding_num_atom_sets(const agbnp_hip_binding* b) { return b ? b->num_sets : 0; }
+
+int agbnp_hip_binding_pair_matrix_device(agbnp_hip_binding* b, const double* d_positions, double* d_matrix, double* d_binding_energy,
+                                         void* stream) {
+  const char* who = "agbnp_hip_binding_pair_matrix_device";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_positions || !d_matrix) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  int rc = binding_need_sets(b, who);
+  if (rc == AGBNP_HIP_OK) rc = binding_matrix_enqueue(b, d_positions, d_matrix, d_binding_energy, stream, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  binding_note(b, stream);
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_binding_pair_matrix_host(agbnp_hip_binding* b, const double* positions, double* matrix, double* binding_energy) {
+  const char* who = "agbnp_hip_binding_pair_matrix_host";
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!positions || !matrix) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  const int rc = binding_need_sets(b, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  return binding_matrix_host(b, positions, matrix, binding_energy, who);
 }
 
 int agbnp_hip_binding_execute_group(agbnp_hip_binding* const* bindings, int count, const double* const* d_positions, const double* d_lambdas,

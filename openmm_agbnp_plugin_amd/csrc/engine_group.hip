@@ -1,5 +1,5 @@
 // Replica groups (engine_context.h; agbnp_hip_execute_group, group_args.h): the evaluations of several contexts on one set of launches.
-// The three kinds of group call -- full, energy-only, decomposition -- are one description (GroupCall), one check, one device form
+// The four kinds of group call -- full, energy-only, decomposition, pair matrix -- are one description (GroupCall), one check, one device form
 // and one host form; what a kind does differently is in the requests it builds and in the host form's three named steps.
 #include "engine_context.h"
 
@@ -28,22 +28,29 @@ bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, const EvalRe
 
 // A group call: its kind, and the buffers its entry point was given.  host: the host form -- positions, forces and planes are host
 // arrays and the energies come back in `energies`; the device form has one energy word per member in d_energies.
-enum class GroupKind { full, energy_only, decomposition };
+enum class GroupKind { full, energy_only, decomposition, matrix };
 struct GroupCall {
   GroupKind kind;
   const char* who;
   bool host;
   const double* const* pos;  // every kind
   double* const* forces;     // a full call's, [3n] per member
-  double* const* planes;     // a decomposition's, [4n] per member
+  double* const* planes;     // a decomposition's, [4n] per member; a pair-matrix call's matrices, [S_m S_m] per member
   double* const* d_energies;
   double* energies;
 };
 
+// words of a member's analysis target: the four planes, or the matrix of its own partition
+size_t target_words(const agbnp_hip_context* c, GroupKind kind) {
+  const size_t S = (size_t)c->sets.num_sets;
+  return kind == GroupKind::matrix ? S * S : 4 * (size_t)c->n;
+}
+
 // The arguments of a group call, checked before anything is launched or changed.  Every kind needs positions, a full call forces,
-// a decomposition planes; the energies are the host form's array or the device form's words, which a decomposition alone may leave
-// out altogether.  The device form's outputs -- energy words, force buffers [3n], plane buffers [4n] -- must not overlap those of
-// another member; the planes' clashes, with one another or with an energy word, are said in a message of their own.
+// a decomposition planes, a pair-matrix call matrices -- and a partition in every member; the energies are the host form's array
+// or the device form's words, which the two analyses alone may leave out altogether.  The device form's outputs -- energy words,
+// force buffers [3n], plane buffers [4n], matrices [S_m S_m] -- must not overlap those of another member; the planes' and the
+// matrices' clashes, with one another or with an energy word, are said in a message of their own.
 int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
   const char* const who = g.who;
   if (!ctxs || count < 1 || count > kMaxGroup) {
@@ -53,31 +60,38 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
   for (int i = 0; i < count; i++)
     if (!ctxs[i]) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   agbnp_hip_context* c0 = ctxs[0];
-  const bool full = g.kind == GroupKind::full, decomposition = g.kind == GroupKind::decomposition;
+  const bool full = g.kind == GroupKind::full, matrix = g.kind == GroupKind::matrix;
+  const bool analysis = matrix || g.kind == GroupKind::decomposition;
+  const std::string clash_message = std::string(who) + (matrix ? ": matrices of two members overlap" : ": plane buffers of two members overlap");
   // (what this kind and form read of the description; null below: not theirs)
   const double* const* pos = g.pos;
   double* const* forces = full ? g.forces : nullptr;
-  double* const* planes = decomposition ? g.planes : nullptr;
+  double* const* planes = analysis ? g.planes : nullptr;
   double* const* d_energies = g.host ? nullptr : g.d_energies;
-  if (!pos || (full && !forces) || (decomposition && !planes) || (g.host ? !g.energies : !d_energies && !decomposition))
+  if (!pos || (full && !forces) || (analysis && !planes) || (g.host ? !g.energies : !d_energies && !analysis))
     return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
   for (int i = 0; i < count; i++) {
     if (ctxs[i]->device != c0->device) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": members on different devices");
     for (int j = 0; j < i; j++)
       if (ctxs[j] == ctxs[i]) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the same context twice");
   }
+  for (int i = 0; i < count && matrix; i++)
+    if (ctxs[i]->sets.num_sets < 1)
+      return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                      std::string(who) + ": member " + std::to_string(i) + ": no partition has been set (agbnp_hip_set_atom_sets)");
   for (int i = 0; i < count; i++) {
     if (!pos[i] || (forces && !forces[i]) || (d_energies && !d_energies[i]) || (planes && !planes[i]))
       return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    // (the host form's targets are host arrays, each OVERWRITTEN by its own member's result: they are held to the same rule)
     for (int j = 0; j < i && planes; j++) {
-      const size_t ni = 4 * (size_t)ctxs[i]->n, nj = 4 * (size_t)ctxs[j]->n;
+      const size_t ni = target_words(ctxs[i], g.kind), nj = target_words(ctxs[j], g.kind);
       bool clash = spans_overlap(planes[i], ni, planes[j], nj);
       if (d_energies) clash = clash || spans_overlap(planes[i], ni, d_energies[j], 1) || spans_overlap(d_energies[i], 1, planes[j], nj);
-      if (clash) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": plane buffers of two members overlap");
+      if (clash) return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, clash_message);
     }
-    // (a member's own energy word inside its own planes)
-    if (planes && d_energies && spans_overlap(planes[i], 4 * (size_t)ctxs[i]->n, d_energies[i], 1))
-      return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": plane buffers of two members overlap");
+    // (a member's own energy word inside its own planes or matrix)
+    if (planes && d_energies && spans_overlap(planes[i], target_words(ctxs[i], g.kind), d_energies[i], 1))
+      return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, clash_message);
     for (int j = 0; j < i && d_energies; j++) {
       const size_t ni = 3 * (size_t)ctxs[i]->n, nj = 3 * (size_t)ctxs[j]->n;
       bool clash = spans_overlap(d_energies[i], 1, d_energies[j], 1);
@@ -100,20 +114,27 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
 // A decomposition group (agbnp_hip_decompose_group; the requests carry the planes as their analysis) is an energy-only set whose cavity
 // launch is the instantiation that also collects the enlarged-radius self volumes, with ONE more launch behind it: the planes of
 // every member (decompose_kernels.hip: k_group_decompose; FIVE launches, version 0 three).  The same blocks again.
+// A pair-matrix group (agbnp_hip_pair_matrix_group; the requests carry the matrices) is the same set with the matrix launch of every
+// member in the place of the plane launch (pair_matrix_kernels.hip: k_group_pair_matrix), on the same grids; the members'
+// partitions and matrix pointers travel in that launch's argument (GroupMatrices), so the blocks are the same once more.
 int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, const EvalRequest* reqs) {
-  const bool energy_only = reqs[set[0]].energy_only, decomposition = reqs[set[0]].sv_large();  // (no group entry point asks for a matrix)
+  const bool energy_only = reqs[set[0]].energy_only, decomposition = reqs[set[0]].sv_large();  // (either analysis)
+  const bool matrix = reqs[set[0]].analysis == Analysis::matrix;
   const hipStream_t st = reqs[set[0]].stream;
   agbnp_hip_context* const c0 = ctxs[set[0]];
   const int version = c0->version, variant = c0->variant;
   // version 1: cavity, Born rows, GB tiles, chain-rule rows, pseudo volumes (energy-only: cavity, Born rows, GB tiles, roles); 0: cavity, outputs
   const int stages = version == 1 ? (energy_only ? 4 : 5) : 2;
-  GroupLaunch G[5], Gplanes;  // (Gplanes: the plane launch of a decomposition group, behind the energy-only stages)
+  GroupLaunch G[5], Gplanes;  // (Gplanes: the plane or matrix launch of an analysis group, behind the energy-only stages)
   GroupOutputs out;
   GroupPlanes planes;
+  GroupMatrices matrices;
+  size_t matrix_lds = 0;
   std::memset(G, 0, sizeof(G));
   std::memset(&Gplanes, 0, sizeof(Gplanes));
   std::memset(&out, 0, sizeof(out));
   std::memset(&planes, 0, sizeof(planes));
+  std::memset(&matrices, 0, sizeof(matrices));
   size_t lds[5] = {tree_variant_lds_bytes(variant), 0, 0, 0, tree_variant_replay_bytes(variant)};
   for (int k = 0; k < m; k++) {
     const int i = set[k];
@@ -163,6 +184,11 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
     Gplanes.first[k + 1] = Gplanes.first[k] + decompose_blocks(c->n, version);
     Gplanes.args[k] = addr;
     planes.per_atom[k] = (unsigned long long)(uintptr_t)reqs[i].target;
+    if (matrix) {
+      matrices.sets[k] = c->sets;
+      matrices.matrix[k] = planes.per_atom[k];
+      matrix_lds = std::max(matrix_lds, sizeof(double) * (size_t)c->sets.depth * (size_t)c->sets.depth);
+    }
     if (version == 1) {
       lds[1] = std::max(lds[1], sh.born_lds);
       lds[3] = std::max(lds[3], sh.chain_lds);
@@ -170,24 +196,28 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       lds[1] = std::max(lds[1], (size_t)sh.out_masks.role_bytes);
     }
     c->group_members = m;
-    c->last_kind = decomposition ? 3 : energy_only ? 1 : 0;
+    c->last_kind = matrix ? 4 : decomposition ? 3 : energy_only ? 1 : 0;
   }
   for (int s = 0; s < stages; s++) G[s].count = m;
   Gplanes.count = m;
+  // the launch behind an analysis set's energy-only stages: the members' matrices, or their planes
+  auto analysis = [&]() -> hipError_t {
+    return matrix ? launch_group_pair_matrix(Gplanes, matrices, version, matrix_lds, st) : launch_group_decompose(Gplanes, planes, version, st);
+  };
   HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st, decomposition));
   if (version == 0) {
     if (energy_only)
       HIP_TRY(c0, launch_group_outputs_energy(G[1], out, lds[1], st));
     else
       HIP_TRY(c0, launch_group_outputs(G[1], out, lds[1], st));
-    if (decomposition) HIP_TRY(c0, launch_group_decompose(Gplanes, planes, version, st));
+    if (decomposition) HIP_TRY(c0, analysis());
     return AGBNP_HIP_OK;
   }
   HIP_TRY(c0, launch_group_born_rows(G[1], lds[1], st));
   if (energy_only) {
     HIP_TRY(c0, launch_group_gb_energy(c0->P.gb_far, G[2], st));
     HIP_TRY(c0, launch_group_energy_roles(G[3], out, lds[3], st));
-    if (decomposition) HIP_TRY(c0, launch_group_decompose(Gplanes, planes, version, st));
+    if (decomposition) HIP_TRY(c0, analysis());
     return AGBNP_HIP_OK;
   }
   HIP_TRY(c0, launch_group_gb(c0->P.gb_far, G[2], st));
@@ -252,7 +282,8 @@ int group_enqueue(agbnp_hip_context* const* ctxs, int count, const EvalRequest* 
 // The device forms.  agbnp_hip_execute_group; agbnp_hip_energy_group: for every member what agbnp_hip_energy_device would do, the
 // sharing members on FOUR (version 0: two) launches per launch set, nothing written to a force buffer of a caller;
 // agbnp_hip_decompose_group: for every member what agbnp_hip_decompose_device would do (d_energies may be null), the sharing
-// members on FIVE (version 0: three) launches per launch set
+// members on FIVE (version 0: three) launches per launch set; agbnp_hip_pair_matrix_group: for every member what
+// agbnp_hip_pair_matrix_device would do, on as many launches
 int group_device(agbnp_hip_context* const* ctxs, int count, const GroupCall& g, void* stream) {
   int rc = check_group(ctxs, count, g);
   if (rc != AGBNP_HIP_OK) return rc;
@@ -260,11 +291,13 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const GroupCall& g, 
   hipStream_t st;
   rc = enter(c0, stream, &st);
   if (rc != AGBNP_HIP_OK) return rc;
-  const bool full = g.kind == GroupKind::full, decomposition = g.kind == GroupKind::decomposition;
+  const bool full = g.kind == GroupKind::full, decomposition = g.kind == GroupKind::decomposition, matrix = g.kind == GroupKind::matrix;
+  const Analysis analysis = matrix ? Analysis::matrix : decomposition ? Analysis::planes : Analysis::none;
   if (is_capturing(st))
-    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(g.who) + ": the stream is being captured; " +
-                                                        (decomposition ? "groups and decompositions" : full ? "groups" : "groups and energy-only evaluations") +
-                                                        " are not captured into graphs");
+    return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                    std::string(g.who) + ": the stream is being captured; " +
+                        (matrix ? "groups and pair matrices" : decomposition ? "groups and decompositions" : full ? "groups" : "groups and energy-only evaluations") +
+                        " are not captured into graphs");
   EvalRequest reqs[kMaxGroup];
   for (int i = 0; i < count; i++) {
     agbnp_hip_context* const c = ctxs[i];
@@ -273,9 +306,8 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const GroupCall& g, 
     // stream is joined to it on both sides instead, so that the member's agbnp_hip_finish(NULL) drains the group's work)
     note_stream(c, stream);
     if (!stream) HIP_TRY(c, join_streams(c->group_event, c->stream, st));
-    if (!full) {  // (a decomposition without energy words: into the member's spare word, as agbnp_hip_decompose_device)
-      reqs[i] = energy_request(c, g.pos[i], g.d_energies ? g.d_energies[i] : nullptr, st, decomposition ? Analysis::planes : Analysis::none,
-                               decomposition ? g.planes[i] : nullptr);
+    if (!full) {  // (an analysis without energy words: into the member's spare word, as agbnp_hip_decompose_device)
+      reqs[i] = energy_request(c, g.pos[i], g.d_energies ? g.d_energies[i] : nullptr, st, analysis, analysis != Analysis::none ? g.planes[i] : nullptr);
       continue;
     }
     reqs[i].pos = g.pos[i];
@@ -290,9 +322,11 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const GroupCall& g, 
 }
 
 // The host forms' per-kind steps.  A member stages in d_force_tmp [3n + 1] -- forces and energy in one buffer, cleared by the cavity
-// launch's trailing workgroups as in agbnp_hip_execute_host -- or, a decomposition, in d_decomp [4n + 1] (stage_analysis) ...
+// launch's trailing workgroups as in agbnp_hip_execute_host -- or, an analysis, in d_decomp [4n + 1] or [S S + 1] (stage_analysis) ...
+bool is_analysis(GroupKind kind) { return kind == GroupKind::decomposition || kind == GroupKind::matrix; }
 int stage_member(agbnp_hip_context* c, const GroupCall& g, int i, hipStream_t st, EvalRequest* r) {
-  if (g.kind == GroupKind::decomposition) return stage_analysis(c, g.pos[i], Analysis::planes, 4 * (size_t)c->n, st, r);
+  if (is_analysis(g.kind))
+    return stage_analysis(c, g.pos[i], g.kind == GroupKind::matrix ? Analysis::matrix : Analysis::planes, target_words(c, g.kind), st, r);
   HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, g.pos[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
   r->pos = c->d_pos_in.p;
   r->force = g.kind == GroupKind::full ? c->d_force_tmp.p : c->d_eo_force.p;
@@ -305,13 +339,14 @@ int stage_member(agbnp_hip_context* c, const GroupCall& g, int i, hipStream_t st
 // ... a member whose evaluation was withheld is repeated alone, as its own host entry point repeats ...
 int repeat_member(agbnp_hip_context* c, const GroupCall& g, int i) {
   if (g.kind == GroupKind::decomposition) return host_decomposition(c, g.pos[i], g.planes[i], &g.energies[i]);
+  if (g.kind == GroupKind::matrix) return agbnp_hip_pair_matrix_host(c, g.pos[i], g.planes[i], &g.energies[i]);
   return host_evaluation(c, g.pos[i], g.kind == GroupKind::full ? g.forces[i] : nullptr, &g.energies[i]);
 }
 // ... and what came back is delivered once the stream is idle: forces ADDED and the energy stored, the energy alone, or the planes
-// OVERWRITTEN (read back in front of the harvest: fetch_analysis; the other two with blocking copies here)
+// or the matrix OVERWRITTEN (read back in front of the harvest: fetch_analysis; the other two with blocking copies here)
 int deliver_member(agbnp_hip_context* c, const GroupCall& g, int i, const EvalRequest& r) {
   const size_t n3 = 3 * (size_t)c->n;
-  if (g.kind == GroupKind::decomposition) deliver_analysis(c, 4 * (size_t)c->n, g.planes[i], &g.energies[i]);
+  if (is_analysis(g.kind)) deliver_analysis(c, target_words(c, g.kind), g.planes[i], &g.energies[i]);
   if (g.kind == GroupKind::energy_only) HIP_TRY(c, hipMemcpy(&g.energies[i], r.energy, sizeof(double), hipMemcpyDeviceToHost));
   if (g.kind != GroupKind::full) return AGBNP_HIP_OK;
   c->h_force_tmp.resize(n3 + 1);
@@ -321,7 +356,8 @@ int deliver_member(agbnp_hip_context* c, const GroupCall& g, int i, const EvalRe
   return AGBNP_HIP_OK;
 }
 
-// agbnp_hip_execute_group_host, agbnp_hip_energy_group_host, agbnp_hip_decompose_group_host: one skeleton over the kind
+// agbnp_hip_execute_group_host, agbnp_hip_energy_group_host, agbnp_hip_decompose_group_host, agbnp_hip_pair_matrix_group_host: one
+// skeleton over the kind
 int group_host(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
   int rc = check_group(ctxs, count, g);
   if (rc != AGBNP_HIP_OK) return rc;
@@ -338,7 +374,7 @@ int group_host(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
   if (rc != AGBNP_HIP_OK) return rc;
   for (int i = 0; i < count; i++) {
     agbnp_hip_context* const c = ctxs[i];
-    if (g.kind == GroupKind::decomposition) HIP_TRY(c, fetch_analysis(c, 4 * (size_t)c->n, st));
+    if (is_analysis(g.kind)) HIP_TRY(c, fetch_analysis(c, target_words(c, g.kind), st));
     int repeat = 0;
     rc = harvest(c, &repeat, st);  // (waits for the group's stream)
     if (rc == AGBNP_HIP_OK) rc = repeat ? repeat_member(c, g, i) : deliver_member(c, g, i, reqs[i]);
@@ -358,6 +394,16 @@ int agbnp_hip_decompose_group(agbnp_hip_context* const* ctxs, int count, const d
 int agbnp_hip_decompose_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* per_atom,
                                    double* energies) {
   return group_host(ctxs, count, {GroupKind::decomposition, "agbnp_hip_decompose_group_host", true, positions, nullptr, per_atom, nullptr, energies});
+}
+
+int agbnp_hip_pair_matrix_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_matrices,
+                                double* const* d_energies, void* stream) {
+  return group_device(ctxs, count, {GroupKind::matrix, "agbnp_hip_pair_matrix_group", false, d_positions, nullptr, d_matrices, d_energies, nullptr}, stream);
+}
+
+int agbnp_hip_pair_matrix_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* matrices,
+                                     double* energies) {
+  return group_host(ctxs, count, {GroupKind::matrix, "agbnp_hip_pair_matrix_group_host", true, positions, nullptr, matrices, nullptr, energies});
 }
 
 int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,

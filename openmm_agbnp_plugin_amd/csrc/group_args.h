@@ -72,6 +72,14 @@ struct GroupPlanes {
   unsigned long long per_atom[kMaxGroup];
 };
 
+// The members' matrices and partitions of a pair-matrix group (agbnp_hip_pair_matrix_group): [S_m][S_m] each and the AtomSets
+// its own matrix launch would take, a kernel argument of the matrix launch alone -- again so that the blocks stay what the other
+// three kinds write.  16 x (32 + 8) bytes beside GroupLaunch's 200: far inside the 4096 bytes a kernel's arguments may take.
+struct GroupMatrices {
+  AtomSets sets[kMaxGroup];
+  unsigned long long matrix[kMaxGroup];
+};
+
 // (sv_large: the instantiations that also collect the enlarged-radius self volumes -- a decomposition group's cavity launch)
 hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large = false);
 hipError_t launch_group_pseudo(int variant, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
@@ -88,6 +96,9 @@ hipError_t launch_group_put(const GroupMemberArgs& a, GroupMemberArgs* dst, hipS
 // every member's grid of decompose_blocks(n, version) workgroups side by side
 int decompose_blocks(int n, int version);
 hipError_t launch_group_decompose(const GroupLaunch& G, const GroupPlanes& O, int version, hipStream_t st);
+// pair-matrix groups (agbnp_hip_pair_matrix_group; pair_matrix_kernels.hip): the ONE matrix launch behind an energy-only launch
+// set, on the same grids; lds: the largest depth^2 x 8 bytes over the members
+hipError_t launch_group_pair_matrix(const GroupLaunch& G, const GroupMatrices& O, int version, size_t lds, hipStream_t st);
 
 #ifdef __HIP_DEVICE_COMPILE__
 typedef const __attribute__((address_space(4))) GroupMemberArgs* GroupArgsPtr;

@@ -101,6 +101,32 @@ __global__ __launch_bounds__(256) void k_pair_matrix(PairArgs P, AtomSets A, int
   matrix_tile<kCut>(P, A, (int)blockIdx.x - role_blocks, matrix);
 }
 
+// Pair-matrix groups (agbnp_hip_pair_matrix_group; group_args.h, engine_group.hip): the matrix launch of every member of a launch
+// set in one grid, as k_group_decompose is the plane launch of every member.  A workgroup finds its member and its number inside
+// that member's grid (group_index) and does there what k_pair_matrix's workgroup of that number does, on the member's PairArgs
+// out of its argument block and on the member's own partition and matrix out of the launch's argument (GroupMatrices: the blocks
+// are not touched).  Gated on that member's own verdict words.  Sharing members run the Reference semantics with the host-named
+// set: no cutoff instantiation, no parity rebase.  The dynamic LDS is sized for the deepest partition of the set; a tile uses
+// the first nI nJ words of it, by its own member's counts.
+__global__ __launch_bounds__(256) void k_group_pair_matrix(GroupLaunch G, GroupMatrices O, int version) {
+  int blk;
+  const int m = group_index(G, blk);
+  const PairArgs& P = group_args(G, m).P;
+  if (evaluation_overflowed(P.estatus)) return;  // this member's evaluation was withheld: it adds nothing
+  const AtomSets& A = O.sets[m];
+  double* __restrict__ matrix = reinterpret_cast<double*>(O.matrix[m]);
+  const int role_blocks = (P.n + 255) / 256;
+  if (blk < role_blocks) return matrix_atoms(P, A, version, 4 * blk, matrix);
+  matrix_tile<false>(P, A, blk - role_blocks, matrix);
+}
+
+static_assert(sizeof(GroupLaunch) + sizeof(GroupMatrices) + sizeof(int) <= 4096, "a kernel's arguments take 4096 bytes at most");
+
+hipError_t launch_group_pair_matrix(const GroupLaunch& G, const GroupMatrices& O, int version, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(k_group_pair_matrix, dim3(G.first[G.count]), dim3(256), lds, st, G, O, version);
+  return hipGetLastError();
+}
+
 int atom_set_tables(int n, const int* set_of_atom, std::vector<unsigned char>& rank, std::vector<int>& block_sets,
                     std::vector<int>& block_count) {
   const int nb = (n + kSetBlock - 1) / kSetBlock;
