@@ -102,6 +102,18 @@ inline Parameters gather(const AGBNPForce& force) {
   return p;
 }
 
+// A partition as both setAtomSets() check it before the library is touched (`who`: the method's name, for the messages): one
+// index per atom, 0 .. numSets - 1; returns numSets, a negative one resolved to the largest index + 1
+inline int checkAtomSets(const std::string& who, const std::vector<int>& sets, int numParticles, int numSets) {
+  if ((int)sets.size() != numParticles) throw OpenMMException(who + "(): one set index per atom is needed");
+  int lowest = 0, highest = -1;
+  for (int s : sets) lowest = s < lowest ? s : lowest, highest = s > highest ? s : highest;
+  if (numSets < 0) numSets = highest + 1;
+  if (numSets < 1 || numSets > AGBNP_HIP_MAX_SETS) throw OpenMMException(who + "(): numSets must be 1 .. AGBNP_HIP_MAX_SETS");
+  if (lowest < 0 || highest >= numSets) throw OpenMMException(who + "(): every set index must be 0 .. numSets - 1");
+  return numSets;
+}
+
 // The arrays of a group call: the members' handles, their positions and, where `forces` is given, their forces.  `bound` and
 // `each` are the refusals of a wrong member count and of per-member arguments that are not one per member (`counted`: what the
 // caller has counted itself).  A member class names its handle type, its bound and its particle count, and hands out a member's
@@ -194,12 +206,7 @@ class HipCalcAGBNPForceKernel {
   // an earlier partition and survives copyParametersToContext().
   void setAtomSets(const std::vector<int>& sets, int numSets = -1) {
     need();
-    if ((int)sets.size() != numParticles) throw OpenMMException("setAtomSets(): one set index per atom is needed");
-    int lowest = 0, highest = -1;
-    for (int s : sets) lowest = s < lowest ? s : lowest, highest = s > highest ? s : highest;
-    if (numSets < 0) numSets = highest + 1;
-    if (numSets < 1 || numSets > AGBNP_HIP_MAX_SETS) throw OpenMMException("setAtomSets(): numSets must be 1 .. AGBNP_HIP_MAX_SETS");
-    if (lowest < 0 || highest >= numSets) throw OpenMMException("setAtomSets(): every set index must be 0 .. numSets - 1");
+    numSets = detail::checkAtomSets("setAtomSets", sets, numParticles, numSets);
     check(agbnp_hip_set_atom_sets(ctx, numParticles, sets.data(), numSets));
   }
   int numAtomSets() const { return ctx ? agbnp_hip_num_atom_sets(ctx) : 0; }
@@ -362,12 +369,7 @@ class Binding {
   // of the COMPLEX (a set may mix receptor and ligand atoms); numSets < 0: the largest index + 1.  Checked before the library is
   // touched, as HipCalcAGBNPForceKernel::setAtomSets() checks; a refused partition leaves the earlier one in force.
   void setAtomSets(const std::vector<int>& sets, int numSets = -1) {
-    if ((int)sets.size() != numParticles) throw OpenMMException("Binding::setAtomSets(): one set index per atom is needed");
-    int lowest = 0, highest = -1;
-    for (int s : sets) lowest = s < lowest ? s : lowest, highest = s > highest ? s : highest;
-    if (numSets < 0) numSets = highest + 1;
-    if (numSets < 1 || numSets > AGBNP_HIP_MAX_SETS) throw OpenMMException("Binding::setAtomSets(): numSets must be 1 .. AGBNP_HIP_MAX_SETS");
-    if (lowest < 0 || highest >= numSets) throw OpenMMException("Binding::setAtomSets(): every set index must be 0 .. numSets - 1");
+    numSets = detail::checkAtomSets("Binding::setAtomSets", sets, numParticles, numSets);
     check(agbnp_hip_binding_set_atom_sets(b, numParticles, sets.data(), numSets));
   }
   int numAtomSets() const { return agbnp_hip_binding_num_atom_sets(b); }

@@ -201,10 +201,12 @@ def _check(rc, error_handle=None):
 
 class _Handle:
     """What HipCalcAGBNPForceKernel and BindingEnergy share: a library handle `_h` (None: there is none), the calls on it, the
-    log of withheld evaluations, the positions check and the release.  The symbols that differ are class data."""
-    _NEED = _WITHHELD = _DESTROY = None
+    log of withheld evaluations, the partition of the matrix calls, the positions check and the release.  The symbols that
+    differ are class data."""
+    _NEED = _WITHHELD = _DESTROY = _SET_SETS = _NUM_SETS = None
     _OWN_ERRORS = True  # the library keeps the messages of this handle's calls under the handle (else: under None)
     _h = None
+    _num_sets = 0  # S of the partition set through THIS object (pair_matrix_group() checks it before the library is reached)
 
     def _need(self):
         if self._h is None:
@@ -238,6 +240,21 @@ class _Handle:
         count(self._h, _ip(idx), n)
         return [int(k) for k in idx if k >= 0]
 
+    def set_atom_sets(self, sets, num_sets=None):
+        """The partition of the atoms that pair_matrix() tabulates (include/agbnp_hip.h, agbnp_hip_set_atom_sets and
+        agbnp_hip_binding_set_atom_sets): sets[i] in 0 .. num_sets - 1 is the set of atom i; sets need not be contiguous and may
+        be empty; what a set is of is in the class's own text.  num_sets defaults to max(sets) + 1.  Replaces an earlier
+        partition and survives copyParametersToContext(); changes nothing an evaluation reads.  The input is checked here,
+        before the library is touched."""
+        self._need()
+        sets, num_sets = _partition(sets, num_sets, self.numParticles)
+        self._call(self._SET_SETS, int(sets.size), _ip(sets), num_sets)
+        self._num_sets = num_sets
+
+    def num_atom_sets(self):
+        """The number of sets of the partition in force; 0: none has been set."""
+        return int(getattr(self._library(), self._NUM_SETS)(self._h))
+
     def release(self):
         if self._h is not None:
             getattr(_lib.load(), self._DESTROY)(self._h)
@@ -251,9 +268,12 @@ class _Handle:
 
 
 class HipCalcAGBNPForceKernel(_Handle):
-    """The 'HIP platform' implementation of CalcAGBNPForceKernel."""
+    """The 'HIP platform' implementation of CalcAGBNPForceKernel.
+
+    set_atom_sets(): a set is whatever pair_matrix() is to tabulate by -- an atom's residue, its chain, receptor or ligand."""
     _NEED = "HipCalcAGBNPForceKernel: initialize() has not been called"
     _WITHHELD, _DESTROY = "agbnp_hip_withheld_evaluations", "agbnp_hip_destroy"
+    _SET_SETS, _NUM_SETS = "agbnp_hip_set_atom_sets", "agbnp_hip_num_atom_sets"
     _GROUP = ("group", "members", _lib.MAX_GROUP, False)  # what a group of these is called, its bound, members distinct
 
     @staticmethod
@@ -356,22 +376,6 @@ class HipCalcAGBNPForceKernel(_Handle):
         log as every other evaluation (finish(), withheld(), poll(), wait_verdict()); a withheld one adds nothing.  Refused
         (OpenMMException) inside a stream capture."""
         self._call("agbnp_hip_decompose_device", C.c_void_p(d_positions), C.c_void_p(d_per_atom), _ptr(d_energy), _ptr(stream))
-
-    def set_atom_sets(self, sets, num_sets=None):
-        """The partition of the atoms that pair_matrix() tabulates (include/agbnp_hip.h, agbnp_hip_set_atom_sets): sets[i] in
-        0 .. num_sets - 1 is the set of atom i -- its residue, its chain, receptor or ligand; sets need not be contiguous and may be
-        empty.  num_sets defaults to max(sets) + 1.  Replaces an earlier partition and survives copyParametersToContext();
-        changes nothing an evaluation reads.  The input is checked here, before the library is touched."""
-        self._need()
-        sets, num_sets = _partition(sets, num_sets, self.numParticles)
-        self._call("agbnp_hip_set_atom_sets", int(sets.size), _ip(sets), num_sets)
-        self._num_sets = num_sets
-
-    _num_sets = 0  # S of the partition set through THIS object (pair_matrix_group() checks it before the library is reached)
-
-    def num_atom_sets(self):
-        """The number of sets of the partition in force; 0: none has been set."""
-        return int(self._library().agbnp_hip_num_atom_sets(self._h))
 
     def pair_matrix(self, positions):
         """Set-pair interaction matrix of the energy at these positions (include/agbnp_hip.h, agbnp_hip_pair_matrix_host):
@@ -511,9 +515,14 @@ class BindingEnergy(_Handle):
 
     A binding evaluation reaches the caller's buffers only if all three members' evaluations completed (decided on the device);
     finish() and withheld() report the binding evaluations that are missing.  Do not evaluate or finish a member() directly
-    between two finish() calls."""
+    between two finish() calls.
+
+    set_atom_sets(): sets[i] is the set of atom i of the COMPLEX -- its residue, say; a set may mix receptor and ligand atoms.
+    Every member gets the restriction to its atoms with the same numbering and the same S; a refused partition leaves the
+    earlier one in force."""
     _NEED = "BindingEnergy: the binding has been released"
     _WITHHELD, _DESTROY = "agbnp_hip_binding_withheld_evaluations", "agbnp_hip_binding_destroy"
+    _SET_SETS, _NUM_SETS = "agbnp_hip_binding_set_atom_sets", "agbnp_hip_binding_num_atom_sets"
     _OWN_ERRORS = False
     _GROUP = ("binding group", "bindings", _lib.MAX_BINDING_GROUP, True)
 
@@ -588,23 +597,6 @@ class BindingEnergy(_Handle):
         inside a stream capture."""
         self._call("agbnp_hip_binding_decompose_device", C.c_void_p(d_positions), C.c_void_p(d_per_atom), _ptr(d_binding_energy),
                    _ptr(stream))
-
-    _num_sets = 0
-
-    def set_atom_sets(self, sets, num_sets=None):
-        """The partition that pair_matrix() tabulates (include/agbnp_hip.h, agbnp_hip_binding_set_atom_sets): sets[i] in
-        0 .. num_sets - 1 is the set of atom i of the COMPLEX -- its residue, say; a set may mix receptor and ligand atoms.
-        Every member gets the restriction to its atoms with the same numbering and the same S.  num_sets defaults to
-        max(sets) + 1.  Replaces an earlier partition and survives copyParametersToContext(); a refused one leaves the earlier
-        one in force.  The input is checked here as a kernel's set_atom_sets() checks it, before the library is touched."""
-        self._need()
-        sets, num_sets = _partition(sets, num_sets, self.numParticles)
-        self._call("agbnp_hip_binding_set_atom_sets", int(sets.size), _ip(sets), num_sets)
-        self._num_sets = num_sets
-
-    def num_atom_sets(self):
-        """The number of sets of the partition in force; 0: none has been set."""
-        return int(self._library().agbnp_hip_binding_num_atom_sets(self._h))
 
     def pair_matrix(self, positions):
         """Set-pair matrix of the binding energy (include/agbnp_hip.h, agbnp_hip_binding_pair_matrix_host): returns (D, u) with D

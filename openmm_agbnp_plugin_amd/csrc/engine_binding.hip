@@ -11,9 +11,10 @@
 // Single and group calls are ONE host path: binding_enqueue takes `count` bindings and makes, for a single call (count == 1, a
 // host lambda), the single-binding launches and otherwise the group launches, as group_enqueue makes a member's own launches
 // for a launch set of one; the host entry points of both stage and deliver through binding_stage and binding_deliver.  What
-// the single and the group entry points keep of their own is their argument checks.  The per-atom decomposition is a second, single
-// enqueue (binding_decompose_enqueue) that starts as the first does (binding_enter), the set-pair matrix a third of the same shape
-// (binding_matrix_enqueue); all single host forms repeat a withheld evaluation in one loop (binding_retry).
+// the single and the group entry points keep of their own is their argument checks.  The binding analyses -- the per-atom
+// decomposition (Analysis::planes) and the set-pair matrix (Analysis::matrix) -- are ONE second, single enqueue
+// (binding_analysis_enqueue) that starts as the first does (binding_enter) and ONE host form (binding_analysis_host); what a kind
+// needs of either is said once (analysis_shape).  All single host forms repeat a withheld evaluation in one loop (binding_retry).
 // Messages of failed binding calls are the calling thread's agbnp_hip_last_error(NULL).
 #include "binding_kernels.h"
 #include "engine_context.h"
@@ -40,24 +41,28 @@ struct agbnp_hip_binding {
   // the host forms stage their lambdas in (both made on first use, by the call's first binding)
   hipEvent_t group_event = nullptr;
   DevBuf<double> d_group_lambdas;
-  // per-atom decompositions (agbnp_hip_binding_decompose_*), both made at the first call that needs them.  d_planes: [4n] the
-  // complex's planes | [4 nr + 4 nl] the receptor's and the ligand's | [3] the three energies -- what the members of the
-  // decomposition group ADD to, cleared by every combine launch.  d_decomp: the host form's staging, [3n] positions | [4n] D | u
-  DevBuf<double> d_planes, d_decomp;
-  std::vector<double> h_decomp;  // [4n + 1] D and u, read back
-  // set-pair matrices (agbnp_hip_binding_pair_matrix_*).  set_of_atom: the partition over the complex's atoms, [n], num_sets
-  // sets (0: none set); every member holds its restriction, same numbering, same S.  d_matrices: [3][S][S] the members'
-  // matrices | [3] the three energies -- what the members of the matrix group ADD to, cleared by every combine launch; made at the
-  // first matrix call, released when S changes.  d_matrix_host: the host form's staging, [3n] positions | [S S] D | u
+  // The binding analyses (agbnp_hip_binding_decompose_*: Analysis::planes, the result D [4][n]; agbnp_hip_binding_pair_matrix_*:
+  // Analysis::matrix, D [S][S]), one buffer set per kind (of()), each buffer made at the first call that needs it.  members: the
+  // complex's target | the receptor's | the ligand's | [3] the three energies -- [4n] | [4 nr] | [4 nl] planes, or [3][S][S]
+  // matrices; what the members of the analysis group ADD to, cleared by every combine launch; the matrix kind's is released when S
+  // changes.  host: the host form's staging, [3n] positions | D | u, remade when D's size changes (the matrix kind's S)
+  struct AnalysisBuffers {
+    DevBuf<double> members, host;
+    std::vector<double> back;  // D and u, read back
+  } analysis[2];
+  AnalysisBuffers& of(Analysis kind) { return analysis[kind == Analysis::matrix]; }
+  // set-pair matrices: set_of_atom the partition over the complex's atoms, [n], num_sets sets (0: none set); every member holds
+  // its restriction, same numbering, same S
   std::vector<int> set_of_atom;
   int num_sets = 0;
-  DevBuf<double> d_matrices, d_matrix_host;
-  std::vector<double> h_matrix;  // [S S + 1] D and u, read back
 
   double* sub_pos() const { return d_work.p; }
   double* f_complex() const { return d_work.p + 3 * (size_t)n; }
   double* f_sub() const { return d_work.p + 6 * (size_t)n; }
   double* energies() const { return d_work.p + 9 * (size_t)n; }
+  // the complex atom that member k's atom t is (k = 0: itself): restricts any per-atom array of the complex to a member
+  int member_atom(int k, int t) const { return k == 0 ? t : sub2complex[(k == 2 ? nr : 0) + t]; }
+  int member_size(int k) const { return k == 0 ? n : k == 1 ? nr : nl; }
 };
 
 namespace {
@@ -202,71 +207,68 @@ int binding_enqueue(agbnp_hip_binding* const* bs, int count, const double* const
   return AGBNP_HIP_OK;
 }
 
-// One per-atom decomposition of b on `stream` (NULL: the complex's own); the arguments have been checked.  The gather launch, ONE
-// agbnp_hip_decompose_group over the three members through the public entry point -- their planes and energies into d_planes --
-// and the combine launch, which reads the three verdicts and adds D and u all or nothing.
-int binding_decompose_enqueue(agbnp_hip_binding* b, const double* d_pos, double* d_per_atom, double* d_binding, void* stream,
-                              const char* who) {
-  hipStream_t st;
-  const int entered = binding_enter(&b, 1, stream, &st, who);
-  if (entered != AGBNP_HIP_OK) return entered;
-  const size_t n = (size_t)b->n, nr = (size_t)b->nr, words = 8 * n + kBindingMembers;
-  if (b->d_planes.p == nullptr) {
-    BINDING_TRY(who, b->d_planes.alloc(words));
-    BINDING_TRY(who, hipMemsetAsync(b->d_planes.p, 0, sizeof(double) * words, st));
-  }
-  double* const planes = b->d_planes.p;
-  double* const e = planes + 8 * n;
-  BINDING_TRY(who, launch_binding_gather(b->n, d_pos, b->d_maps.p, b->sub_pos(), st));
-  const double* const pos[kBindingMembers] = {d_pos, b->sub_pos(), b->sub_pos() + 3 * nr};
-  double* const per_atom[kBindingMembers] = {planes, planes + 4 * n, planes + 4 * n + 4 * nr};
-  double* const ene[kBindingMembers] = {e, e + 1, e + 2};
-  // (a NULL stream is the group's first member's own: the complex's, `st`)
-  const int rc = agbnp_hip_decompose_group(b->m, kBindingMembers, pos, per_atom, ene, stream);
-  if (rc != AGBNP_HIP_OK) {
-    // no combine launch will read and clear what the members that got as far as their launches added: cleared here, as the
-    // force path does
-    (void)hipMemsetAsync(planes, 0, sizeof(double) * words, st);
-    return member_fail(b, rc, who);
-  }
-  BINDING_TRY(who, launch_binding_decompose_combine(b->n, b->nr, binding_verdicts(b), b->d_maps.p + n, planes, planes + 4 * n, e,
-                                                    d_per_atom, d_binding, st));
-  return AGBNP_HIP_OK;
-}
-
 // the matrix calls need a partition (agbnp_hip_binding_set_atom_sets)
 int binding_need_sets(const agbnp_hip_binding* b, const char* who) {
   if (b->num_sets > 0) return AGBNP_HIP_OK;
   return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": no partition has been set (agbnp_hip_binding_set_atom_sets)");
 }
 
-// One set-pair matrix of b on `stream` (NULL: the complex's own); the arguments have been checked and a partition is set.  The
-// gather launch, ONE agbnp_hip_pair_matrix_group over the three members through the public entry point -- their matrices and
-// energies into d_matrices -- and the combine launch, which reads the three verdicts and adds D and u all or nothing.
-int binding_matrix_enqueue(agbnp_hip_binding* b, const double* d_pos, double* d_matrix, double* d_binding, void* stream, const char* who) {
+// what the four analysis entry points check, in this order (a null binding: the code alone)
+int binding_analysis_check(const agbnp_hip_binding* b, Analysis kind, const double* pos, const double* out, const char* who) {
+  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!pos || !out) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  return kind == Analysis::matrix ? binding_need_sets(b, who) : AGBNP_HIP_OK;
+}
+
+// What a binding analysis of a kind needs: the words of each member's target and of the result D.  (Which public group call
+// runs the members and which combine launch follows are the two places binding_analysis_enqueue asks for the kind.)
+struct AnalysisShape {
+  size_t member[kBindingMembers];  // planes: 4n | 4nr | 4nl; matrix: S S each
+  size_t out;                      // D: 4n | S S
+  size_t words() const { return member[0] + member[1] + member[2] + kBindingMembers; }  // ... and the three energies
+};
+AnalysisShape analysis_shape(const agbnp_hip_binding* b, Analysis kind) {
+  const size_t cells = (size_t)b->num_sets * (size_t)b->num_sets;
+  if (kind == Analysis::matrix) return {{cells, cells, cells}, cells};
+  return {{4 * (size_t)b->n, 4 * (size_t)b->nr, 4 * (size_t)b->nl}, 4 * (size_t)b->n};
+}
+
+// One analysis of b on `stream` (NULL: the complex's own); the arguments have been checked and, for a matrix, a partition is set.
+// The gather launch, ONE agbnp_hip_decompose_group / agbnp_hip_pair_matrix_group over the three members through the public entry
+// point -- their targets and energies into the kind's members' buffer -- and the combine launch, which reads the three verdicts
+// and adds D and u all or nothing.
+int binding_analysis_enqueue(agbnp_hip_binding* b, Analysis kind, const double* d_pos, double* d_out, double* d_binding, void* stream,
+                             const char* who) {
   hipStream_t st;
   const int entered = binding_enter(&b, 1, stream, &st, who);
   if (entered != AGBNP_HIP_OK) return entered;
-  const size_t cells = (size_t)b->num_sets * (size_t)b->num_sets, words = kBindingMembers * cells + kBindingMembers;
-  if (b->d_matrices.p == nullptr) {  // (the first matrix call, or the first since S changed: agbnp_hip_binding_set_atom_sets)
-    BINDING_TRY(who, b->d_matrices.alloc(words));
-    BINDING_TRY(who, hipMemsetAsync(b->d_matrices.p, 0, sizeof(double) * words, st));
+  const AnalysisShape shape = analysis_shape(b, kind);
+  const size_t words = shape.words();
+  DevBuf<double>& members = b->of(kind).members;
+  if (members.p == nullptr) {  // (the first call of the kind, or the first matrix since S changed: agbnp_hip_binding_set_atom_sets)
+    BINDING_TRY(who, members.alloc(words));
+    BINDING_TRY(who, hipMemsetAsync(members.p, 0, sizeof(double) * words, st));
   }
-  double* const m = b->d_matrices.p;
-  double* const e = m + kBindingMembers * cells;
+  double* const t = members.p;
+  double* const target[kBindingMembers] = {t, t + shape.member[0], t + shape.member[0] + shape.member[1]};
+  double* const e = t + words - kBindingMembers;
+  double* const ene[kBindingMembers] = {e, e + 1, e + 2};
   BINDING_TRY(who, launch_binding_gather(b->n, d_pos, b->d_maps.p, b->sub_pos(), st));
   const double* const pos[kBindingMembers] = {d_pos, b->sub_pos(), b->sub_pos() + 3 * (size_t)b->nr};
-  double* const matrices[kBindingMembers] = {m, m + cells, m + 2 * cells};
-  double* const ene[kBindingMembers] = {e, e + 1, e + 2};
   // (a NULL stream is the group's first member's own: the complex's, `st`)
-  const int rc = agbnp_hip_pair_matrix_group(b->m, kBindingMembers, pos, matrices, ene, stream);
+  const int rc = kind == Analysis::matrix ? agbnp_hip_pair_matrix_group(b->m, kBindingMembers, pos, target, ene, stream)
+                                          : agbnp_hip_decompose_group(b->m, kBindingMembers, pos, target, ene, stream);
   if (rc != AGBNP_HIP_OK) {
     // no combine launch will read and clear what the members that got as far as their launches added: cleared here, as the
-    // decomposition does
-    (void)hipMemsetAsync(m, 0, sizeof(double) * words, st);
+    // force path does
+    (void)hipMemsetAsync(t, 0, sizeof(double) * words, st);
     return member_fail(b, rc, who);
   }
-  BINDING_TRY(who, launch_binding_matrix_combine(b->num_sets, binding_verdicts(b), m, e, d_matrix, d_binding, st));
+  if (kind == Analysis::matrix)
+    BINDING_TRY(who, launch_binding_matrix_combine(b->num_sets, binding_verdicts(b), t, e, d_out, d_binding, st));
+  else
+    BINDING_TRY(who, launch_binding_decompose_combine(b->n, b->nr, binding_verdicts(b), b->d_maps.p + b->n, t, target[1], e, d_out,
+                                                      d_binding, st));
   return AGBNP_HIP_OK;
 }
 
@@ -274,6 +276,16 @@ int binding_matrix_enqueue(agbnp_hip_binding* b, const double* d_pos, double* d_
 void binding_note(agbnp_hip_binding* b, void* stream) {
   b->enqueued++;
   if (stream && std::find(b->streams.begin(), b->streams.end(), stream) == b->streams.end()) b->streams.push_back(stream);
+}
+
+// agbnp_hip_binding_decompose_device / agbnp_hip_binding_pair_matrix_device
+int binding_analysis_device(agbnp_hip_binding* b, Analysis kind, const double* d_pos, double* d_out, double* d_binding, void* stream,
+                            const char* who) {
+  int rc = binding_analysis_check(b, kind, d_pos, d_out, who);
+  if (rc == AGBNP_HIP_OK) rc = binding_analysis_enqueue(b, kind, d_pos, d_out, d_binding, stream, who);
+  if (rc != AGBNP_HIP_OK) return rc;
+  binding_note(b, stream);
+  return AGBNP_HIP_OK;
 }
 
 // drains `stream`, finishes the three members and forms the union of their logs: `out` the indices (ascending), *count their
@@ -337,46 +349,29 @@ int binding_retry(agbnp_hip_binding* b, const char* who, Stage stage, Deliver de
   return binding_fail(AGBNP_HIP_ERR_CAPACITY, std::string(who) + ": capacity negotiation did not converge");
 }
 
-// agbnp_hip_binding_decompose_host: staged in d_decomp (made on first use), [3n] positions | [4n] D | u, the outputs cleared first
-int binding_decompose_host(agbnp_hip_binding* b, const double* pos, double* per_atom, double* binding_energy, const char* who) {
-  const size_t n3 = 3 * (size_t)b->n, n4 = 4 * (size_t)b->n;
+// agbnp_hip_binding_decompose_host / agbnp_hip_binding_pair_matrix_host: staged in the kind's host buffer, [3n] positions | D | u
+// (made on first use, and remade when D's size -- the matrix kind's S -- changes: the complex's stream is idle between host
+// calls), the outputs cleared first
+int binding_analysis_host(agbnp_hip_binding* b, Analysis kind, const double* pos, double* out, double* binding_energy, const char* who) {
+  const int checked = binding_analysis_check(b, kind, pos, out, who);
+  if (checked != AGBNP_HIP_OK) return checked;
+  const size_t n3 = 3 * (size_t)b->n, cells = analysis_shape(b, kind).out;
+  agbnp_hip_binding::AnalysisBuffers& buf = b->of(kind);
   auto stage = [&]() -> int {
     const hipStream_t st = b->m[0]->stream;
-    if (b->d_decomp.p == nullptr) BINDING_TRY(who, b->d_decomp.alloc(n3 + n4 + 1));
-    b->h_decomp.resize(n4 + 1);
-    double* const d_out = b->d_decomp.p + n3;
-    BINDING_TRY(who, hipMemcpyAsync(b->d_decomp.p, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
-    BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (n4 + 1), st));
-    const int rc = binding_decompose_enqueue(b, b->d_decomp.p, d_out, d_out + n4, nullptr, who);
-    if (rc != AGBNP_HIP_OK) return rc;
-    BINDING_TRY(who, hipMemcpyAsync(b->h_decomp.data(), d_out, sizeof(double) * (n4 + 1), hipMemcpyDeviceToHost, st));
-    return AGBNP_HIP_OK;
-  };
-  return binding_retry(b, who, stage, [&] {
-    std::memcpy(per_atom, b->h_decomp.data(), sizeof(double) * n4);
-    if (binding_energy) *binding_energy = b->h_decomp[n4];
-  });
-}
-
-// agbnp_hip_binding_pair_matrix_host: staged in d_matrix_host (remade when S changes: the complex's stream is idle between host
-// calls), [3n] positions | [S S] D | u, the outputs cleared first
-int binding_matrix_host(agbnp_hip_binding* b, const double* pos, double* matrix, double* binding_energy, const char* who) {
-  const size_t n3 = 3 * (size_t)b->n, cells = (size_t)b->num_sets * (size_t)b->num_sets;
-  auto stage = [&]() -> int {
-    const hipStream_t st = b->m[0]->stream;
-    if (b->d_matrix_host.count != n3 + cells + 1) BINDING_TRY(who, b->d_matrix_host.alloc(n3 + cells + 1));
-    b->h_matrix.resize(cells + 1);
-    double* const d_out = b->d_matrix_host.p + n3;
-    BINDING_TRY(who, hipMemcpyAsync(b->d_matrix_host.p, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
+    if (buf.host.p == nullptr || buf.host.count != n3 + cells + 1) BINDING_TRY(who, buf.host.alloc(n3 + cells + 1));
+    buf.back.resize(cells + 1);
+    double* const d_out = buf.host.p + n3;
+    BINDING_TRY(who, hipMemcpyAsync(buf.host.p, pos, sizeof(double) * n3, hipMemcpyHostToDevice, st));
     BINDING_TRY(who, hipMemsetAsync(d_out, 0, sizeof(double) * (cells + 1), st));
-    const int rc = binding_matrix_enqueue(b, b->d_matrix_host.p, d_out, d_out + cells, nullptr, who);
+    const int rc = binding_analysis_enqueue(b, kind, buf.host.p, d_out, d_out + cells, nullptr, who);
     if (rc != AGBNP_HIP_OK) return rc;
-    BINDING_TRY(who, hipMemcpyAsync(b->h_matrix.data(), d_out, sizeof(double) * (cells + 1), hipMemcpyDeviceToHost, st));
+    BINDING_TRY(who, hipMemcpyAsync(buf.back.data(), d_out, sizeof(double) * (cells + 1), hipMemcpyDeviceToHost, st));
     return AGBNP_HIP_OK;
   };
   return binding_retry(b, who, stage, [&] {
-    std::memcpy(matrix, b->h_matrix.data(), sizeof(double) * cells);
-    if (binding_energy) *binding_energy = b->h_matrix[cells];
+    std::memcpy(out, buf.back.data(), sizeof(double) * cells);
+    if (binding_energy) *binding_energy = buf.back[cells];
   });
 }
 
@@ -535,10 +530,9 @@ struct MemberParams {
 };
 MemberParams member_params(const agbnp_hip_binding* b, int k, const double* radius, const double* gamma, const double* vdw_alpha,
                            const double* charge, const int* ishydrogen) {
-  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {b->n, b->nr, b->nl};
   MemberParams p;
-  for (int t = 0; t < count[k]; t++) {
-    const int i = k == 0 ? t : b->sub2complex[first[k] + t];
+  for (int t = 0; t < b->member_size(k); t++) {
+    const int i = b->member_atom(k, t);
     p.r.push_back(radius[i]), p.g.push_back(gamma[i]), p.a.push_back(vdw_alpha[i]), p.q.push_back(charge[i]), p.h.push_back(ishydrogen[i]);
   }
   return p;
@@ -636,20 +630,11 @@ int agbnp_hip_binding_energy_host(agbnp_hip_binding* b, const double* positions,
 
 int agbnp_hip_binding_decompose_device(agbnp_hip_binding* b, const double* d_positions, double* d_per_atom, double* d_binding_energy,
                                        void* stream) {
-  const char* who = "agbnp_hip_binding_decompose_device";
-  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!d_positions || !d_per_atom) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-  const int rc = binding_decompose_enqueue(b, d_positions, d_per_atom, d_binding_energy, stream, who);
-  if (rc != AGBNP_HIP_OK) return rc;
-  binding_note(b, stream);
-  return AGBNP_HIP_OK;
+  return binding_analysis_device(b, Analysis::planes, d_positions, d_per_atom, d_binding_energy, stream, "agbnp_hip_binding_decompose_device");
 }
 
 int agbnp_hip_binding_decompose_host(agbnp_hip_binding* b, const double* positions, double* per_atom, double* binding_energy) {
-  const char* who = "agbnp_hip_binding_decompose_host";
-  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!positions || !per_atom) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-  return binding_decompose_host(b, positions, per_atom, binding_energy, who);
+  return binding_analysis_host(b, Analysis::planes, positions, per_atom, binding_energy, "agbnp_hip_binding_decompose_host");
 }
 
 // The partition is checked here, entirely, before any member is touched: what a member's agbnp_hip_set_atom_sets could refuse of
@@ -669,18 +654,18 @@ int agbnp_hip_binding_set_atom_sets(agbnp_hip_binding* b, int n, const int* set_
       return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
                           std::string(who) + ": atom " + std::to_string(i) + " names a set outside 0 .. num_sets - 1");
   clear_member_errors(b);
-  const int first[kBindingMembers] = {0, 0, b->nr}, count[kBindingMembers] = {b->n, b->nr, b->nl};
   for (int k = 0; k < kBindingMembers; k++) {
-    std::vector<int> own(count[k]);
-    for (int t = 0; t < count[k]; t++) own[t] = set_of_atom[k == 0 ? t : b->sub2complex[first[k] + t]];
-    const int rc = agbnp_hip_set_atom_sets(b->m[k], count[k], own.data(), num_sets);
+    std::vector<int> own(b->member_size(k));
+    for (size_t t = 0; t < own.size(); t++) own[t] = set_of_atom[b->member_atom(k, (int)t)];
+    const int rc = agbnp_hip_set_atom_sets(b->m[k], (int)own.size(), own.data(), num_sets);
     if (rc != AGBNP_HIP_OK) return member_fail(b, rc, who);  // (a device error: nothing the checks above could have found)
   }
-  if (num_sets != b->num_sets && b->d_matrices.p) {
+  DevBuf<double>& matrices = b->of(Analysis::matrix).members;
+  if (num_sets != b->num_sets && matrices.p) {
     BINDING_TRY(who, hipSetDevice(b->device));
     BINDING_TRY(who, hipStreamSynchronize(b->m[0]->stream));
     for (void* s : b->streams) BINDING_TRY(who, hipStreamSynchronize((hipStream_t)s));
-    b->d_matrices.release();
+    matrices.release();
   }
   b->set_of_atom.assign(set_of_atom, set_of_atom + n);
   b->num_sets = num_sets;
@@ -691,23 +676,11 @@ int agbnp_hip_binding_num_atom_sets(const agbnp_hip_binding* b) { return b ? b->
 
 int agbnp_hip_binding_pair_matrix_device(agbnp_hip_binding* b, const double* d_positions, double* d_matrix, double* d_binding_energy,
                                          void* stream) {
-  const char* who = "agbnp_hip_binding_pair_matrix_device";
-  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!d_positions || !d_matrix) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-  int rc = binding_need_sets(b, who);
-  if (rc == AGBNP_HIP_OK) rc = binding_matrix_enqueue(b, d_positions, d_matrix, d_binding_energy, stream, who);
-  if (rc != AGBNP_HIP_OK) return rc;
-  binding_note(b, stream);
-  return AGBNP_HIP_OK;
+  return binding_analysis_device(b, Analysis::matrix, d_positions, d_matrix, d_binding_energy, stream, "agbnp_hip_binding_pair_matrix_device");
 }
 
 int agbnp_hip_binding_pair_matrix_host(agbnp_hip_binding* b, const double* positions, double* matrix, double* binding_energy) {
-  const char* who = "agbnp_hip_binding_pair_matrix_host";
-  if (!b) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
-  if (!positions || !matrix) return binding_fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-  const int rc = binding_need_sets(b, who);
-  if (rc != AGBNP_HIP_OK) return rc;
-  return binding_matrix_host(b, positions, matrix, binding_energy, who);
+  return binding_analysis_host(b, Analysis::matrix, positions, matrix, binding_energy, "agbnp_hip_binding_pair_matrix_host");
 }
 
 int agbnp_hip_binding_execute_group(agbnp_hip_binding* const* bindings, int count, const double* const* d_positions, const double* d_lambdas,

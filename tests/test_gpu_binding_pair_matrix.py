@@ -329,6 +329,28 @@ def test_a_replaced_partition_with_another_size_and_a_refused_one(gpu_required, 
     check(b.pair_matrix(s.pos), reference(s, ligand, sets, S, "file", s.pos), what="after the refusals")
 
 
+def test_the_host_forms_across_partitions_of_another_size(gpu_required, systems, five_groups):
+    """One binding through the HOST forms alone: the matrix with 20 sets, the planes, the matrix with 3 sets, the planes, the
+    matrix with 20 again.  The matrix's host staging is remade for every S (its positions, its S S cells and u lie elsewhere each
+    time), the planes' is made once and is not the matrix's; every result is the restatement's and nothing is withheld."""
+    from tests.test_gpu_binding_decomposition import check as check_planes
+    from tests.test_gpu_binding_decomposition import reference as plane_reference
+    s = systems("trpcage")
+    sets, S = residues("trpcage")
+    mod3 = np.arange(s.n) % 3
+    ligand = list(range(16))
+    b = _binding(s, ligand, sets, S)
+    planes = plane_reference(s, ligand, "file", s.pos)
+    check(b.pair_matrix(s.pos), reference(s, ligand, sets, S, "file", s.pos), what="host, 20 sets")
+    check_planes(b.decompose(s.pos), planes, what="host, after 20 sets")
+    b.set_atom_sets(mod3)
+    check(b.pair_matrix(s.pos), reference(s, ligand, mod3, 3, "file", s.pos), what="host, 3 sets")
+    check_planes(b.decompose(s.pos), planes, what="host, after 3 sets")
+    b.set_atom_sets(sets, S)
+    check(b.pair_matrix(s.pos), reference(s, ligand, sets, S, "file", s.pos), what="host, 20 sets again")
+    assert b.finish() == 0 and b.withheld() == []
+
+
 def test_update_parameters_keeps_the_partition(gpu_required, systems, five_groups):
     s = systems("trpcage")
     sets, S = residues("trpcage")
