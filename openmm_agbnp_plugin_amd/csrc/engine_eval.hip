@@ -199,6 +199,9 @@ int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest
   const PairLaunchShape shape = pair_launch_shape(c->P, c->version);
   const bool matrix = r.analysis == Analysis::matrix;
   c->last_kind = matrix ? 4 : r.sv_large() ? 3 : !r.energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
+  // the form of the cavity launch and, with it, the replay's weights (tree_single_gather; the self volumes of pass 1 -- an
+  // analysis, the diagnostics -- come out of that pass's own gather: both gathers there)
+  c->T.single_gather = tree_single_gather(c->variant, c->version) && !r.sv_large() && !c->T.want_sv_large ? 1 : 0;
   auto analysis = [&]() -> int {
     if (!r.sv_large()) return AGBNP_HIP_OK;
     const hipError_t e = matrix ? launch_pair_matrix(c->P, c->sets, c->version, r.target, st, tl) : launch_decompose(c->P, c->version, r.target, st, tl);

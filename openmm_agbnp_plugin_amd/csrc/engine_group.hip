@@ -146,6 +146,8 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
     std::memset(&a, 0, sizeof(a));
     a.P = c->P;
     a.T = c->T;
+    // (the replay's weights; whatever the kind of request, so that the blocks stay the same: a set without a replay does not read it)
+    a.T.single_gather = tree_single_gather(variant, version) ? 1 : 0;
     a.T.out.forest_blocks = plan.tree_grid;
     a.T.out.force = nullptr;  // (the caller's outputs travel in the launch argument: the block stays what it was)
     a.components = c->d_components.p;
@@ -204,7 +206,8 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
   auto analysis = [&]() -> hipError_t {
     return matrix ? launch_group_pair_matrix(Gplanes, matrices, version, matrix_lds, st) : launch_group_decompose(Gplanes, planes, version, st);
   };
-  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st, decomposition));
+  // (an analysis set collects the self volumes of pass 1 and has no replay: both gathers)
+  HIP_TRY(c0, launch_group_cavity_five(variant, G[0], lds[0], st, decomposition, tree_single_gather(variant, version) && !decomposition));
   if (version == 0) {
     if (energy_only)
       HIP_TRY(c0, launch_group_outputs_energy(G[1], out, lds[1], st));

@@ -80,8 +80,9 @@ struct GroupMatrices {
   unsigned long long matrix[kMaxGroup];
 };
 
-// (sv_large: the instantiations that also collect the enlarged-radius self volumes -- a decomposition group's cavity launch)
-hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large = false);
+// (sv_large: the instantiations that also collect the enlarged-radius self volumes -- a decomposition group's cavity launch;
+// single_gather: the forests' single-gather form, as the members' TreeArgs::single_gather says -- never both)
+hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large = false, bool single_gather = false);
 hipError_t launch_group_pseudo(int variant, const GroupLaunch& G, const GroupOutputs& O, size_t lds, hipStream_t st);
 hipError_t launch_group_born_rows(const GroupLaunch& G, size_t lds, hipStream_t st);
 hipError_t launch_group_gb(int gb_far, const GroupLaunch& G, hipStream_t st);

@@ -134,11 +134,12 @@ hipError_t launch_group_put(const GroupMemberArgs& a, GroupMemberArgs* dst, hipS
 // workgroups per CU are three waves per SIMD as it is; the 432-node store then holds four workgroups per CU where the other
 // launches hold five -- a decomposition of a system with more than 1024 forests runs its cavity launch in more rounds.
 constexpr int group_cavity_waves(int ncap, bool sv1) { return sv1 && ncap <= 512 ? 3 : tree_waves_per_simd(ncap); }
-template <int NCAP, int ACAP, int BS, bool SV1>
+// SINGLE: the forests' single-gather form (tree_bodies.h), what a version-1 member would launch alone
+template <int NCAP, int ACAP, int BS, bool SV1, bool SINGLE = false>
 __global__ __launch_bounds__(BS, group_cavity_waves(NCAP, SV1)) void k_group_cavity_five(GroupLaunch G) {
   int blk;
   const GroupMemberArgs& g = group_member(G, blk);
-  k_tree_cavity_five<NCAP, ACAP, BS, false, false, SV1>(g.T, g.P, g.tree_blocks, (unsigned)blk, 0u);
+  k_tree_cavity_five<NCAP, ACAP, BS, false, false, SV1, SINGLE>(g.T, g.P, g.tree_blocks, (unsigned)blk, 0u);
 }
 template <int NCAP, int ACAP, int BS, bool PIPE>
 __global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_group_pseudo(GroupLaunch G, GroupOutputs O) {
@@ -161,12 +162,17 @@ static hipError_t launch_group(K kernel, const GroupLaunch& G, size_t lds, hipSt
   return hipGetLastError();
 }
 
-hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large) {
+hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large, bool single_gather) {
   return with_tree_variant(variant, [&](auto v) {
     using V = decltype(v);
-    if constexpr (V::kGlobal)
+    if constexpr (V::kGlobal) {
       return hipErrorInvalidValue;
-    else if (sv_large)
+    } else if (single_gather) {
+      if constexpr (TreeStore<V::kNodeCap, V::kAtomCap>::kPairGather) {
+        if (!sv_large) return launch_group(k_group_cavity_five<V::kNodeCap, V::kAtomCap, kBS, false, true>, G, lds, st);
+      }
+      return hipErrorInvalidValue;
+    } else if (sv_large)
       return launch_group(k_group_cavity_five<V::kNodeCap, V::kAtomCap, kBS, true>, G, lds, st);
     else
       return launch_group(k_group_cavity_five<V::kNodeCap, V::kAtomCap, kBS, false>, G, lds, st);

@@ -197,10 +197,14 @@ __device__ __forceinline__ void write_topology(const TreeStore<NCAP, ACAP>& S, c
 }
 // (6) Switch the local atoms to vdW radii, nu = -gamma/roffset, for pass 2, whose self volumes the Born stage needs.  One atom
 // per lane (ACAP <= BS): the parameters were requested in front of pass 1 and arrive in a_vdw / v_vdw.
-template <int NCAP, int ACAP, int BS>
+// KEEP_EXPONENTS (the single-gather form): the enlarged exponents, which the one gather behind node step 2 still needs, move to
+// cand_vol -- idle since the counting sort of the membership list, whose cursors were its last tenants.
+template <int NCAP, int ACAP, int BS, bool KEEP_EXPONENTS = false>
 __device__ __forceinline__ void switch_to_vdw(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, int tid, int natoms, double a_vdw, double v_vdw) {
+  static_assert(!KEEP_EXPONENTS || ACAP <= BS, "one atom per lane");
   if (ACAP <= BS) {
     if (tid < natoms) {
+      if (KEEP_EXPONENTS) S.cand_vol[tid] = S.at[3][tid];
       S.at[3][tid] = a_vdw;
       S.at[4][tid] = v_vdw;
       S.at[5][tid] = -S.at[5][tid];
@@ -251,8 +255,17 @@ __device__ __forceinline__ void report_overflow(const TreeArgs& A, int tid, int 
 // SV1: the launch also collects the self volumes of pass 1 (enlarged radii; a diagnostic: agbnp_hip_set_diagnostics)
 // FIVE: the five-launch mode's instantiation (k_tree_cavity_five below): positions straight from the caller's array.
 // POSQ: FIVE with the positions in an OpenMM context's posq (TreeArgs::posq; row_atoms holds slots)
-template <int NCAP, int ACAP, int BS, bool GLOBAL, bool SV1, bool FIVE, bool POSQ = false>
+// SINGLE: the single-gather form, for evaluations that end in a replay (version 1, the membership-list stores, no pass-1 self
+// volumes; TreeArgs::single_gather says so to both tree launches).  The gradient of pass 2 is the replay's gradient form at the
+// same Gaussians with per-atom weights -gamma/roffset, and the gather is linear in those weights: k_tree_pseudo takes it along
+// with weights nu - gamma/roffset (replay_weight), and nothing between the two launches reads it.  What is left of pass 2 -- the
+// self volumes and E2 -- needs one word per node, so the rows of pass 1 stay where they are (volume_pass, kGatherLater /
+// kGatherFused) and ONE walk over the membership list serves both passes: the gradient from the rows of pass 1, the self volumes
+// from the w row of pass 2.  A list walk, a segmented scan, a set of LDS atomics with their barriers and four stores per node less
+// in every forest's life.  The verdict on the store (steps 3-4) is known before any gather, as before.
+template <int NCAP, int ACAP, int BS, bool GLOBAL, bool SV1, bool FIVE, bool POSQ = false, bool SINGLE = false>
 __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree_blocks AGBNP_WG_PARAM) {  // tree_blocks: forest workgroups of the launch
+  static_assert(!SINGLE || (TreeStore<NCAP, ACAP>::kPairGather && !SV1 && !GLOBAL), "single-gather form: membership-list stores, no pass-1 self volumes");
   extern __shared__ __align__(16) char smem[];
   TreeStore<NCAP, ACAP> S;
   S.carve(GLOBAL ? (A.scratch + (size_t)AGBNP_WG * A.scratch_stride) : smem);
@@ -316,7 +329,8 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
       // ---- (3) pass 1: enlarged radii, nu = +gamma/roffset (reference steps A-B, ReferenceAGBNPKernels.cpp:293-339).
       // The node slots still hold the Gaussians of the build, so only the atom paths and the membership list are
       // laid down before the gather.  Its gradient stays in the local accumulators and leaves with that of pass 2.
-      if (rc == kBuildOk && !volume_pass<NCAP, ACAP, BS, true, true>(S, tid, m, nnodes, natoms, want_sv1, &e_sum, &npairs, det))
+      // (SINGLE: node step and list only; the gather is the one behind node step 2.)
+      if (rc == kBuildOk && !volume_pass<NCAP, ACAP, BS, true, true, SINGLE ? kGatherLater : kGatherOwn>(S, tid, m, nnodes, natoms, want_sv1, &e_sum, &npairs, det))
         rc = kBuildNodeOverflow;  // the membership list does not fit: same protocol as a node overflow
       // ---- (4) heal or report
       if (rc != kBuildOk) {
@@ -376,11 +390,11 @@ __device__ __forceinline__ void cavity_forests(const TreeArgs& A, const int tree
       write_topology<NCAP, ACAP, BS>(S, A, tid, out, m, nnodes, natoms, npairs);
       CSTAMP(2);
       // ---- (6) vdW radii
-      switch_to_vdw<NCAP, ACAP, BS>(S, A, tid, natoms, a_vdw_mine, v_vdw_mine);
+      switch_to_vdw<NCAP, ACAP, BS, SINGLE>(S, A, tid, natoms, a_vdw_mine, v_vdw_mine);
       tree_barrier<NCAP>();  // the topology stores above keep draining underneath pass 2
       CSTAMP(3);
-      // ---- (7) pass 2: vdW radii, nu = -gamma/roffset
-      volume_pass<NCAP, ACAP, BS, true>(S, tid, m, nnodes, natoms, true, &e_sum, &npairs, det);
+      // ---- (7) pass 2: vdW radii, nu = -gamma/roffset (SINGLE: self volumes and E2; its walk also takes the gradient of pass 1)
+      volume_pass<NCAP, ACAP, BS, true, false, SINGLE ? kGatherFused : kGatherOwn>(S, tid, m, nnodes, natoms, true, &e_sum, &npairs, det);
       CSTAMP(4);
       root_gradients_from_invariance<NCAP, ACAP, BS>(S, tid, m);
       CSTAMP(5);
@@ -432,7 +446,8 @@ static_assert(kPrepHvGx == kHvGx && kPrepHvGx + 3 == kHvSvVdw && kPrepHvSvLarge 
 // every particle's entry against atomIndex (kStatOrderStale: the context has reordered its atoms, the evaluation is void)
 // SV1: the instantiation of the per-atom decomposition (agbnp_hip_decompose_*), which also collects the enlarged-radius self
 // volumes (row kHvSvLarge; the trailing workgroups clear the next evaluation's row in every instantiation)
-template <int NCAP, int ACAP, int BS, bool DEVPAR = false, bool POSQ = false, bool SV1 = false>
+// SINGLE: the forests' single-gather form (cavity_forests), what version 1 launches; version 0 has no replay and keeps both gathers
+template <int NCAP, int ACAP, int BS, bool DEVPAR = false, bool POSQ = false, bool SV1 = false, bool SINGLE = false>
 AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity_five(TreeArgs A, PairArgs P, int tree_blocks AGBNP_WG_PARAM) {
   if ((int)AGBNP_WG >= tree_blocks) {
     const int b = (int)AGBNP_WG - tree_blocks;
@@ -440,7 +455,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity_five
     return prep_atoms(P, b * BS + (int)threadIdx.x, b == 0, true);
   }
   if (DEVPAR) rebase_tree_for_parity(A, 0);
-  cavity_forests<NCAP, ACAP, BS, false, SV1, true, POSQ>(A, tree_blocks AGBNP_WG_ARG);
+  cavity_forests<NCAP, ACAP, BS, false, SV1, true, POSQ, SINGLE>(A, tree_blocks AGBNP_WG_ARG);
 }
 
 // ---- the forces leave with the last tree launch (TreeOutputs) ------------------------------------------------------
@@ -523,7 +538,21 @@ __device__ __forceinline__ void put_paths(const Store& S, int tid, int m, int nn
   for (int k = 0; k < N; k++)
     if (tid + k * BS >= m && tid + k * BS < nnodes) path[tid + k * BS] = pw[k];
 }
-// Local-atom table fill: atom `la` of the store is heavy atom hj with vdW radii and nu = (W + U) / V; cleared gradient sums.
+// A replay's weight of heavy atom hj: nu = (W + U) / V -- and, behind a cavity launch in its single-gather form, minus
+// gamma/roffset: the vdW-radius cavity gradient, which that launch has left to this one (cavity_forests, SINGLE).  The gamma row
+// is the context's own, asked for in the same trip as the other parameters whichever form ran.  (Store: the stores without a
+// membership list have no such form, and their replays read nothing more than before.)
+template <class Store>
+__device__ __forceinline__ double replay_weight(const TreeArgs& A, int hj) {
+  const double nu = A.db_wu[hj] * A.hvat(kHvInvVol, hj);
+  if constexpr (!Store::kPairGather) {
+    return nu;
+  } else {
+    const double gam = A.hvat(kHvGam, hj);
+    return A.single_gather ? nu - gam : nu;
+  }
+}
+// Local-atom table fill: atom `la` of the store is heavy atom hj with vdW radii and the replay's weight; cleared gradient sums.
 // (The self-volume accumulators are idle in this pass: the slot carries the atom's index for the flush.)
 template <class Store>
 __device__ __forceinline__ void put_replay_atom(const Store& S, int la, int hj, double x, double y, double z, double a, double v, double nu,
@@ -559,7 +588,8 @@ __device__ __forceinline__ void flush_replay(const TreeArgs& A, const Store& S, 
 
 // Replay of a stored forest with vdW radii: reference steps K+L (ReferenceAGBNPKernels.cpp:718-747),
 // nu_i = (W_i+U_i)/V_i formed on the fly from the chain-rule sums, gradient only.  The reference does two passes
-// (W then U); the pass is linear in nu, so one pass with the sum gives the same gradient.
+// (W then U); the pass is linear in nu, so one pass with the sum gives the same gradient -- and, behind a cavity launch in its
+// single-gather form, the vdW-radius cavity gradient as well (replay_weight).
 // PIPE: the instantiation whose replay of QUEUED forests is pipelined (round 4); it keeps the next forest's registers live
 // across the volume pass and spills one at the 128-register bound.  Launches whose forests fit one round (TreeOutputs::enabled:
 // the engine's own rule for fusing the forces) take the lean one; either handles any number of forests.
@@ -624,7 +654,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
         const int hj = hj_pre;
         px = A.hvat(kHvX, hj), py = A.hvat(kHvY, hj), pz = A.hvat(kHvZ, hj);
         pa = A.hvat(kHvAVdw, hj), pv = A.hvat(kHvVVdw, hj);
-        pnu = A.db_wu[hj] * A.hvat(kHvInvVol, hj);
+        pnu = replay_weight<TreeStore<NCAP, ACAP>>(A, hj);
         pidx = write_forces ? A.out.h2a[hj] : 0;
       }
     };
@@ -730,7 +760,7 @@ AGBNP_KERNEL AGBNP_BOUNDS(BS, tree_waves_per_simd(NCAP)) void k_tree_pseudo(Tree
     for (int la = tid; la < natoms; la += BS) {
       const int hj = kPrefetch ? hj_pre : A.atom_pool[atom_off + la];
       put_replay_atom(S, la, hj, A.hvat(kHvX, hj), A.hvat(kHvY, hj), A.hvat(kHvZ, hj), A.hvat(kHvAVdw, hj), A.hvat(kHvVVdw, hj),
-                      A.db_wu[hj] * A.hvat(kHvInvVol, hj), write_forces, write_forces ? A.out.h2a[hj] : 0);
+                      replay_weight<TreeStore<NCAP, ACAP>>(A, hj), write_forces, write_forces ? A.out.h2a[hj] : 0);
     }
     tree_barrier<NCAP>();
     PSTAMP(0);

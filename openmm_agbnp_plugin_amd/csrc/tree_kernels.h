@@ -5,7 +5,9 @@
 // (or one residue class of the level-2 branches of a big subtree) -- and keeps it in LDS for its whole life: build
 // (large radii) -> volume pass 1 on the build's Gaussians -> topology out -> vdW radii -> volume pass 2, all inside
 // one launch.  Only per-atom sums (gradients, self volumes), one energy pair per forest and the stored topology
-// (8-byte atom path per node + 2-byte (atom, node) memberships) leave the CU.
+// (8-byte atom path per node + 2-byte (atom, node) memberships) leave the CU.  (Where a replay follows -- version 1 -- pass 2
+// keeps its self volumes and energy and leaves its gradient to the replay, and the forest walks its memberships once for both
+// passes: cavity_forests' single-gather form, tree_bodies.h.)
 //
 // What is computed (reference restated in oracle/agbnp_oracle.cpp):
 //   build      : gaussvol/gaussvol.cpp:197-250 (child scan over YOUNGER siblings), :154-192 (children sorted
@@ -88,6 +90,8 @@ struct TreeArgs {
   int det;                     // deterministic mode: order-dependent sums only take quantized terms (device_math.h)
   int split_fit;               // bit 0: a lone work item that outgrows the store asks for its subtree to be shared (kStatSplitWanted);
                                // bit 1: a forest that outgrows its store is healed inside the launch (cavity_forests, tree_bodies.h)
+  int single_gather;           // the cavity launch walks the membership list ONCE (cavity_forests, SINGLE) and leaves the vdW-radius
+                               // gradient to the replay, whose per-atom weights are then nu - gamma/roffset (replay_weight)
   const int* rows;             // [kRowStride * slots] the work slots' rows (slot_row_item / slot_row_count, agbnp_common.h)
   const int* packing;          // the packing block (PackingWord, agbnp_common.h)
   int slot_cap;
@@ -895,7 +899,15 @@ __device__ int build_forest(const TreeStore<NCAP, ACAP>& S, const TreeArgs& A, i
 }
 
 // ---- (3) of a volume pass: gather over the (atom, node) membership list, sorted by atom -------------------------------
-template <int NCAP, int ACAP, int BS>
+// What a volume pass does about its gather (the membership-list variants; cavity_forests' single-gather form, tree_bodies.h):
+//   kGatherOwn    the pass gathers what its own node step laid down: gradient, and self volumes if asked
+//   kGatherLater  (a FRESH_BUILD pass) node step and membership list only: its rows nd[0..3] wait for a later pass's gather
+//   kGatherFused  the node step forms w_n and the energy alone and leaves nd[0..3] -- the rows of the pass before -- as they
+//                 are; ONE walk then takes the gradient from those rows, with the exponents that pass worked with (kept in
+//                 cand_vol: the local atom table holds this pass's by now), and the self volumes from this pass's w row
+enum PassGather { kGatherOwn = 0, kGatherLater, kGatherFused };
+// KEPT_EXPONENTS: the atoms' exponents come from cand_vol, not from the local atom table (kGatherFused)
+template <int NCAP, int ACAP, int BS, bool KEPT_EXPONENTS = false>
 __device__ __forceinline__ void pair_gather(const TreeStore<NCAP, ACAP>& S, int tid, int total, bool with_selfvol, bool det) {
   // (3) gather over the pair list.  Every lane takes an equal, contiguous piece of the list (sorted by atom) and sums
   // the terms of every run of the same atom in registers: work proportional to the memberships (about three per
@@ -945,7 +957,7 @@ __device__ __forceinline__ void pair_gather(const TreeStore<NCAP, ACAP>& S, int 
         in_first = false;
       }
       cur = a;
-      xa = S.at[0][a], ya = S.at[1][a], za = S.at[2][a], ea = S.at[3][a];
+      xa = S.at[0][a], ya = S.at[1][a], za = S.at[2][a], ea = (KEPT_EXPONENTS ? S.cand_vol : S.at[3])[a];
       gx = gy = gz = sv = 0.0;
     }
     const double am = cf * ea;
@@ -1038,12 +1050,16 @@ struct NoHook {
 };
 // after_pairs: called by every thread once the node step is done and the replayed pair list (pair_word) has been moved
 // from registers into LDS -- the point from which a replay's registers are free for the NEXT forest's loads (k_tree_pseudo)
-template <int NCAP, int ACAP, int BS, bool WITH_ENERGY, bool FRESH_BUILD = false, class AfterPairs = NoHook>
+// GATHER: what the pass does about its gather (PassGather, above)
+template <int NCAP, int ACAP, int BS, bool WITH_ENERGY, bool FRESH_BUILD = false, int GATHER = kGatherOwn, class AfterPairs = NoHook>
 __device__ bool volume_pass(const TreeStore<NCAP, ACAP>& S, int tid, int m, int nnodes, int natoms, bool with_selfvol,
                             double* e_sum, int* npairs, bool det, const uint4* pair_word = nullptr, AfterPairs after_pairs = AfterPairs()) {
   static_assert(ACAP <= 256, "atom path stores one byte per level");
   static_assert(BS % 64 == 0 && BS >= 64, "whole waves");
   constexpr bool kPairs = TreeStore<NCAP, ACAP>::kPairGather;
+  constexpr bool kOwnRows = GATHER != kGatherFused;  // the node step lays down centres and coefficients (nd[0..3])
+  static_assert(GATHER == kGatherOwn || kPairs, "the single-gather form walks the membership list");
+  static_assert(GATHER == kGatherOwn || FRESH_BUILD == (GATHER == kGatherLater), "the build's pass waits, the pass behind it gathers for both");
   constexpr int PCAP = TreeStore<NCAP, ACAP>::PCAP;
   unsigned long long* path = reinterpret_cast<unsigned long long*>(S.nd[6]);
   AGBNP_BUILD_STAMP_BEGIN();
@@ -1093,7 +1109,7 @@ __device__ bool volume_pass(const TreeStore<NCAP, ACAP>& S, int tid, int m, int 
       } else {  // ---- from a stored path: the node's Gaussian again from its atoms
         const unsigned long long pwr = path[n];
         if ((pwr & kPartners) == 0ull) {  // inert (a level-2 node owned by another work item)
-          S.nd[3][n] = 0.0;
+          if (kOwnRows) S.nd[3][n] = 0.0;
           S.wrow[n] = 0.0;
           break;
         }
@@ -1120,15 +1136,17 @@ __device__ bool volume_pass(const TreeStore<NCAP, ACAP>& S, int tid, int m, int 
         }
         const double q = pa * fast_rcp(A * pi_power(level - 1));
         g = pv * pow_three_halves(q) * exp_nonpositive(-E);
-        S.nd[0][n] = cx;
-        S.nd[1][n] = cy;
-        S.nd[2][n] = cz;
+        if (kOwnRows) {
+          S.nd[0][n] = cx;
+          S.nd[1][n] = cy;
+          S.nd[2][n] = cz;
+        }
       }
       const double cp = ((level & 1) ? 1.0 : -1.0) / (double)level;
       double sp;
       const double sw = dev_switch(g, sp);
       w = quantize(cp * sw * g, kQVol, det);  // (the self-volume sums are order-dependent: LDS atomics, list order)
-      S.nd[3][n] = -2.0 * cp * gam * (sp * g + sw) * g;
+      if (kOwnRows) S.nd[3][n] = -2.0 * cp * gam * (sp * g + sw) * g;
       S.wrow[n] = w;
       e_part += quantize(gam * (cp * sw * g), kQEnergy, det);  // (which nodes a lane sums depends on the forest's composition)
     } while (false);
@@ -1190,8 +1208,10 @@ __device__ bool volume_pass(const TreeStore<NCAP, ACAP>& S, int tid, int m, int 
       tree_barrier<NCAP>();
       after_pairs();
     }
-    pair_gather<NCAP, ACAP, BS>(S, tid, *npairs, with_selfvol, det);
-    tree_barrier<NCAP>();
+    if (GATHER != kGatherLater) {
+      pair_gather<NCAP, ACAP, BS, GATHER == kGatherFused>(S, tid, *npairs, with_selfvol, det);
+      tree_barrier<NCAP>();
+    }
     AGBNP_BUILD_STAMP(14);
     return true;
   }
@@ -1296,6 +1316,7 @@ size_t tree_variant_scratch_bytes(int variant);  // the per-workgroup HBM slab o
 int tree_variant_node_cap(int variant);
 int tree_variant_atom_cap(int variant);
 int tree_variant_wgs_per_cu(int variant);
+bool tree_single_gather(int variant, int version);  // the evaluations whose cavity launch walks the membership list once (TreeArgs::single_gather)
 // workgroups of the five-launch mode's cavity launch and of the pseudo-volume launch, as the launchers below make them
 int tree_five_grid(int slots, const PairArgs& P);
 int tree_pseudo_grid(int variant, int global_grid, int slots, const TreeArgs& A);

@@ -5,9 +5,10 @@
 namespace agbnp {
 
 // the cavity launch of the six-launch mode (behind k_prep): every workgroup is a forest workgroup
-template <int NCAP, int ACAP, int BS, bool GLOBAL, bool SV1>
+// (SINGLE: the forests' single-gather form, tree_bodies.h)
+template <int NCAP, int ACAP, int BS, bool GLOBAL, bool SV1, bool SINGLE = false>
 __global__ __launch_bounds__(BS, tree_waves_per_simd(NCAP)) void k_tree_cavity(TreeArgs A) {
-  cavity_forests<NCAP, ACAP, BS, GLOBAL, SV1, false>(A, (int)gridDim.x);
+  cavity_forests<NCAP, ACAP, BS, GLOBAL, SV1, false, false, SINGLE>(A, (int)gridDim.x);
 }
 
 // ---- host-side launchers (the capacity variants: tree_bodies.h) -----------------------------------
@@ -25,6 +26,13 @@ int tree_variant_node_cap(int variant) {
 }
 int tree_variant_atom_cap(int variant) {
   return with_tree_variant(variant, [](auto v) { return decltype(v)::kAtomCap; });
+}
+// Which evaluations take the cavity launch in its single-gather form (cavity_forests, SINGLE) and so the replay with the combined
+// weights: those that end in a replay (version 1) on a store that gathers over the membership list.  (A launch that is to collect
+// the self volumes of pass 1 -- an analysis' request, the diagnostics -- needs that pass's own gather: the engine asks for both
+// gathers there, TreeArgs::single_gather = 0.)
+bool tree_single_gather(int variant, int version) {
+  return version == 1 && with_tree_variant(variant, [](auto v) { return TreeStore<decltype(v)::kNodeCap, decltype(v)::kAtomCap>::kPairGather; });
 }
 // workgroups of the build kernel that a CU holds: LDS granules of 1280 B (128 per CU), 32 waves, the register budget
 int tree_variant_wgs_per_cu(int variant) {
@@ -67,7 +75,15 @@ hipError_t launch_tree_cavity(int variant, int global_grid, int slots, const Tre
   const int grid = tree_forest_blocks(variant, global_grid, slots, A);
   return with_tree_variant(variant, [&](auto v) {
     using V = decltype(v);
-    if (A.want_sv_large || sv_large)  // (the self volumes of pass 1, a diagnostic or a decomposition's request: a kernel of their own)
+    constexpr bool kPairs = TreeStore<V::kNodeCap, V::kAtomCap>::kPairGather;
+    const bool sv1 = A.want_sv_large || sv_large;
+    if (A.single_gather) {  // (the replay behind this launch takes the vdW-radius gradient along: the form that leaves it out)
+      if constexpr (kPairs) {
+        if (!sv1) return launch_tree(k_tree_cavity<V::kNodeCap, V::kAtomCap, kBS, false, false, true>, grid, V::kLdsBytes, st, A);
+      }
+      return hipErrorInvalidValue;
+    }
+    if (sv1)  // (the self volumes of pass 1, a diagnostic or a decomposition's request: a kernel of their own)
       return launch_tree(k_tree_cavity<V::kNodeCap, V::kAtomCap, kBS, V::kGlobal, true>, grid, V::kLdsBytes, st, A);
     return launch_tree(k_tree_cavity<V::kNodeCap, V::kAtomCap, kBS, V::kGlobal, false>, grid, V::kLdsBytes, st, A);
   });
@@ -87,6 +103,16 @@ hipError_t launch_tree_cavity_five(int variant, int slots, const TreeArgs& A, co
       return hipErrorInvalidValue;
     } else {
       constexpr int N = V::kNodeCap, AC = V::kAtomCap;
+      if (A.single_gather) {  // (as in launch_tree_cavity)
+        if constexpr (TreeStore<N, AC>::kPairGather) {
+          if (sv_large) return hipErrorInvalidValue;
+          if (dev && posq) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, true, false, true>, grid, V::kLdsBytes, st, A, P, slots);
+          if (dev) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, false, false, true>, grid, V::kLdsBytes, st, A, P, slots);
+          if (posq) return launch_tree(k_tree_cavity_five<N, AC, kBS, false, true, false, true>, grid, V::kLdsBytes, st, A, P, slots);
+          return launch_tree(k_tree_cavity_five<N, AC, kBS, false, false, false, true>, grid, V::kLdsBytes, st, A, P, slots);
+        }
+        return hipErrorInvalidValue;
+      }
       if (sv_large && dev) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, false, true>, grid, V::kLdsBytes, st, A, P, slots);
       if (sv_large) return launch_tree(k_tree_cavity_five<N, AC, kBS, false, false, true>, grid, V::kLdsBytes, st, A, P, slots);
       if (dev && posq) return launch_tree(k_tree_cavity_five<N, AC, kBS, true, true>, grid, V::kLdsBytes, st, A, P, slots);
