@@ -285,6 +285,50 @@ class HipCalcAGBNPForceKernel {
     return energies;
   }
 
+  // The parameter sets that perturbedEnergies() scores (agbnp_hip_set_parameter_sets): gamma, vdwAlpha and charge hold M sets of N
+  // values each, set-major, M 1 .. AGBNP_HIP_MAX_PARAMETER_SETS; radii and hydrogen flags are the kernel's own.  Checked before the
+  // library is touched; replaces earlier sets and survives copyParametersToContext().
+  void setParameterSets(const std::vector<double>& gamma, const std::vector<double>& vdwAlpha, const std::vector<double>& charge) {
+    need();
+    const size_t n = (size_t)numParticles, m = n ? gamma.size() / n : 0;
+    if (m < 1 || m > AGBNP_HIP_MAX_PARAMETER_SETS || gamma.size() != m * n || vdwAlpha.size() != m * n || charge.size() != m * n)
+      throw OpenMMException("setParameterSets(): gamma, vdwAlpha and charge must each hold M x N values, M 1 .. 16");
+    check(agbnp_hip_set_parameter_sets(ctx, numParticles, (int)m, gamma.data(), vdwAlpha.data(), charge.data()));
+  }
+  int numParameterSets() const { return ctx ? agbnp_hip_num_parameter_sets(ctx) : 0; }
+
+  // The energy of these positions under every set of setParameterSets(), from one evaluation (agbnp_hip_perturbed_energies_host):
+  // returns the kernel's own energy; energies[m] receives what a kernel initialised with set m would return.  No forces are written.
+  double perturbedEnergies(const std::vector<double>& positions, std::vector<double>& energies) {
+    need();
+    if ((int)positions.size() != 3 * numParticles) throw OpenMMException("perturbedEnergies(): positions must hold 3N values");
+    const size_t m = (size_t)numParameterSets();
+    energies.assign(m + (m == 0), 0.0);  // (no sets: the library refuses, with its message)
+    double e = 0.0;
+    check(agbnp_hip_perturbed_energies_host(ctx, positions.data(), energies.data(), &e));
+    return e;
+  }
+
+  // Perturbation groups (agbnp_hip_perturbed_energies_group_host): the perturbation energies of every kernel in `kernels` at
+  // positions[i] (3N_i), each over its own sets (setParameterSets(); checked here), the members that can share on the energy-only
+  // group's launches plus one perturbation launch per launch set.  energies[i] receives [M_i]; the members' own energies are returned.
+  static std::vector<double> perturbedEnergiesGroup(const std::vector<HipCalcAGBNPForceKernel*>& kernels,
+                                                    const std::vector<std::vector<double>>& positions, std::vector<std::vector<double>>& energies) {
+    auto g = detail::Group::collect("perturbedEnergiesGroup", kernels, "a group has 1 to 16 members", "one position array per member", true, positions);
+    energies.resize(kernels.size());
+    std::vector<double*> targets(kernels.size());
+    for (size_t i = 0; i < kernels.size(); i++) {
+      const size_t m = (size_t)kernels[i]->numParameterSets();
+      if (m == 0) throw OpenMMException("perturbedEnergiesGroup(): a member has no parameter sets (setParameterSets())");
+      energies[i].assign(m, 0.0);
+      targets[i] = energies[i].data();
+    }
+    std::vector<double> own(kernels.size(), 0.0);
+    detail::check(agbnp_hip_perturbed_energies_group_host(g.handles.data(), (int)kernels.size(), g.pos.data(), targets.data(), own.data()),
+                  g.handles[0]);
+    return own;
+  }
+
   // The positions of the next evaluation are unrelated to the last ones (agbnp_hip_expect_jump): it lays the neighbour masks
   // down at its own positions first and is not withheld for the jump.
   void expectJump() {

@@ -232,6 +232,51 @@ int agbnp_hip_pair_matrix_host(agbnp_hip_context* ctx, const double* positions, 
 int agbnp_hip_pair_matrix_device(agbnp_hip_context* ctx, const double* d_positions, double* d_matrix /*[S][S] ADDED*/,
                                  double* d_energy /*may be NULL*/, void* stream);
 
+/* Perturbation energies: what THIS conformation would cost under THOSE parameters -- the cross energies of Hamiltonian replica
+ * exchange over gamma / vdw_alpha / charge ladders, the rows of an MBAR / FEP reweighting matrix, a force-field scan -- for up to
+ * AGBNP_HIP_MAX_PARAMETER_SETS parameter sets from ONE evaluation.  agbnp_hip_update_parameters() may change only gamma, vdw_alpha
+ * and charge; the overlap trees, both sets of self volumes and the Born radii depend on the geometry and the radii alone, and
+ * the energy is an explicit function of the three vectors over them (nu, k, B_i and f_ij as for the decomposition above):
+ *   E_m = sum_i nu_i^m (sv_large_i - sv_vdw_i)  +  sum_i alpha_i^m / (B_i + 0.14 nm)^3
+ *       + k sum_i (q_i^m)^2 / B_i  +  2k sum_{i<j} q_i^m q_j^m f_ij
+ * energies[m] is the energy that a context created with (radius, gamma^m, vdw_alpha^m, charge^m, ishydrogen) of this context --
+ * the same version, nonbonded method and cutoff -- would return from agbnp_hip_energy_*() at the same positions IN THIS CONTEXT'S
+ * MODE.  A hydrogen's gamma counts as 0, as everywhere else; per-atom gammas inside a set are allowed, as
+ * agbnp_hip_update_parameters() allows them.  Version 0 gives the cavity term only.
+ *   agbnp_hip_set_parameter_sets         the sets: gamma, vdw_alpha, charge are [M][N] row-major, atom (particle) order, M = num_sets
+ *                                        1 .. AGBNP_HIP_MAX_PARAMETER_SETS.  A wrong N, M out of range or a null pointer returns
+ *                                        AGBNP_HIP_ERR_INVALID_ARGUMENT and the previous sets are kept.  Replaces any earlier sets;
+ *                                        waits only for work that may be reading the tables it replaces (the context's stream and
+ *                                        the streams the caller has enqueued on; nothing before the first sets).  The sets are
+ *                                        independent of the context's own parameters.  It changes nothing an evaluation reads:
+ *                                        agbnp_hip_generation(), scalars 16 and 18 and the overflow log stay as they are, and
+ *                                        agbnp_hip_update_parameters() keeps the sets
+ *   agbnp_hip_num_parameter_sets         M, or 0 when no sets have been set
+ *   agbnp_hip_perturbed_energies_host    synchronous; energies[M] is OVERWRITTEN, *energy -- the context's own, under its own
+ *                                        parameters -- RETURNED; withheld evaluations are repeated
+ *   agbnp_hip_perturbed_energies_device  asynchronous, no host synchronisation; the M energies are ADDED to d_energies and the
+ *                                        context's own to *d_energy (may be NULL)
+ * In every respect listed for agbnp_hip_decompose_host / _device above the perturbation calls behave as those do: ONE evaluation in
+ * the overflow log, gated on the verdict words on the device (a withheld evaluation adds nothing to the energies or to the energy;
+ * the host form repeats it), agbnp_hip_expect_jump() applies, the context is left as a full evaluation leaves it, the calls
+ * interleave freely with every other kind, every mode is supported, fast+single is lifted for the call, and inside a stream
+ * capture the device call is refused and the capture stays usable.  Scalar 20 reports 5.  Without sets both return
+ * AGBNP_HIP_ERR_INVALID_ARGUMENT and the message says so.  Fast mode: pairs with d^2 < cutoff^2 and that mode's Born radii;
+ * fast+single: the FP64 fast mode's numbers; the deterministic mode gives bit-identical energies from run to run.
+ * Launches: exactly those of agbnp_hip_decompose_device(), with ONE launch of the same grid (k_perturb) in the place of the plane
+ * launch.  A pair's f_ij -- the FP64 exponential and reciprocal square root -- is formed once and multiplied by M charge products;
+ * M is rounded up to a compiled tier (4, 8, 16) whose surplus sets carry zero charges.  The call runs at the context's own
+ * positions: no second context, no jump, no hint.
+ * Not provided: forces under the other sets, a binding form, an OpenMM-buffer form. */
+#define AGBNP_HIP_MAX_PARAMETER_SETS 16
+int agbnp_hip_set_parameter_sets(agbnp_hip_context* ctx, int num_particles, int num_sets, const double* gamma /*[M][N]*/,
+                                 const double* vdw_alpha /*[M][N]*/, const double* charge /*[M][N]*/);
+int agbnp_hip_num_parameter_sets(const agbnp_hip_context* ctx); /* 0: none set */
+int agbnp_hip_perturbed_energies_host(agbnp_hip_context* ctx, const double* positions, double* energies /*[M] OVERWRITTEN*/,
+                                      double* energy /*the context's own, RETURNED*/);
+int agbnp_hip_perturbed_energies_device(agbnp_hip_context* ctx, const double* d_positions, double* d_energies /*[M] ADDED*/,
+                                        double* d_energy /*may be NULL*/, void* stream);
+
 /* Replica groups: ONE call that enqueues an evaluation of each of `count` existing contexts (1 .. AGBNP_HIP_MAX_GROUP), for
  * replica exchange, multiple walkers and binding-energy schemes that run several small systems at once.  d_positions,
  * d_forces, d_energies are HOST arrays of `count` DEVICE pointers, one per member.  For every member i the call does exactly
@@ -362,6 +407,36 @@ int agbnp_hip_pair_matrix_group(agbnp_hip_context* const* ctxs, int count, const
  * does. */
 int agbnp_hip_pair_matrix_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions,
                                      double* const* matrices /*overwritten*/, double* energies /*[count]*/);
+
+/* Perturbation groups: the conjunction of agbnp_hip_perturbed_energies_device() and agbnp_hip_decompose_group(), for the energy
+ * matrices of Hamiltonian replica exchange and of MBAR over several replicas or frames at once.  The contract is that of
+ * agbnp_hip_decompose_group() with the energies under the member's sets in the place of the planes.  d_positions, d_energies and
+ * d_own_energies are HOST arrays of `count` DEVICE pointers; d_own_energies may be NULL altogether.  For every member i the call
+ * does exactly what agbnp_hip_perturbed_energies_device(ctxs[i], d_positions[i], d_energies[i], d_own_energies[i], stream) would
+ * do: the member's OWN sets (M_i may differ between members), its M_i energies ADDED to d_energies[i] and its own energy to
+ * *d_own_energies[i], both gated on THAT member's own verdict, ONE evaluation counted in that member's overflow log, scalar 20
+ * reporting 5 and scalar 19 the launch set's size -- so agbnp_hip_finish(), _poll(), _wait_verdict(), _withheld_evaluations() and
+ * _expect_jump() work per member, a withheld member adds nothing and does not affect the others, and the call interleaves freely
+ * with every other kind of call.
+ * Arguments, all checked on the host before anything is launched or any member changes: those of agbnp_hip_decompose_group() --
+ * 1 .. AGBNP_HIP_MAX_GROUP distinct contexts on one device --; the spans [M_i] and the own-energy words must not overlap one
+ * another (overlap has a message of its own); a member without sets is refused with AGBNP_HIP_ERR_INVALID_ARGUMENT and the message
+ * says that no parameter sets have been set.  Position buffers may be shared.  Inside a stream capture the call is refused
+ * (AGBNP_HIP_ERR_INVALID_ARGUMENT, the capture stays usable).
+ * Launches.  A member SHARES under the conditions of agbnp_hip_energy_group(); nothing is added to them.  A launch set runs the
+ * decomposition group's first stages and behind them ONE perturbation launch for all its members (k_group_perturb, in the tier of
+ * the member with the most sets): FIVE launches (version 0: THREE), whatever its size.  A set of one, and every member that cannot
+ * share, runs what agbnp_hip_perturbed_energies_device() runs for it on the same stream.
+ * Argument blocks.  The members' tables and output pointers travel with the perturbation launch alone: all five kinds of group build
+ * the same block for a member's parity, and a steady run that mixes them rewrites nothing (scalar 21). */
+int agbnp_hip_perturbed_energies_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions,
+                                       double* const* d_energies /*[count] x [M_i], ADDED*/,
+                                       double* const* d_own_energies /*NULL, or [count] words, ADDED*/, void* stream);
+/* The synchronous twin for host buffers: positions[i][3 n_i] read, energies[i][M_i] OVERWRITTEN, own_energies[i] RETURNED (no NULL
+ * pointer; the members' arrays must not overlap).  Withheld members are repeated inside, alone, as
+ * agbnp_hip_perturbed_energies_host() does. */
+int agbnp_hip_perturbed_energies_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions,
+                                            double* const* energies /*overwritten*/, double* own_energies /*[count]*/);
 
 /* A hint: the positions of the NEXT evaluation of this context are unrelated to those of the last one (another replica's
  * conformation in an exchange matrix, a restart, a Monte Carlo move).  In the five-launch mode the neighbour masks carry a skin,
@@ -686,7 +761,8 @@ enum agbnp_hip_scalar {
                                             * evaluation, like 15, 17, 18, 19 and 21): 0 a full evaluation, 1 an energy-only evaluation on
                                             * energy-only launches (alone or shared), 2 an energy-only request that ran as a full
                                             * evaluation with its forces sent to the context's own buffer, 3 a per-atom decomposition
-                                            * (agbnp_hip_decompose_*), 4 a set-pair interaction matrix (agbnp_hip_pair_matrix_*) */
+                                            * (agbnp_hip_decompose_*), 4 a set-pair interaction matrix (agbnp_hip_pair_matrix_*),
+                                            * 5 perturbation energies (agbnp_hip_perturbed_energies_*) */
   AGBNP_HIP_SCALAR_GROUP_BLOCK_WRITES = 21 /* how often the context's group argument blocks have been rewritten so far (one small
                                             * launch each); it stands still in a steady run of group calls with fixed position buffers */
 };

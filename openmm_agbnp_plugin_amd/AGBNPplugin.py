@@ -192,6 +192,30 @@ def _partition(sets, num_sets, n):
     return sets, num_sets
 
 
+def _parameter_sets(gamma, vdw_alpha, charge, n):
+    """The parameter sets of set_parameter_sets() as they cross the C ABI, checked as the library checks them: three float64
+    arrays [M, n] (a [n] array is one set), M 1 .. MAX_PARAMETER_SETS.  Returns (M, gamma, vdw_alpha, charge)."""
+    tables = []
+    for name, given in (("gamma", gamma), ("vdw_alpha", vdw_alpha), ("charge", charge)):
+        try:
+            a = np.ascontiguousarray(given, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise OpenMMException(f"set_parameter_sets(): {name} must be an array of numbers, [M, N] or [N]")
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2 or a.shape[1] != n:
+            raise OpenMMException(f"set_parameter_sets(): {name} must be [M, N] or [N] with N = {n} particles")
+        if not np.isfinite(a).all():
+            raise OpenMMException(f"set_parameter_sets(): {name} must be finite")
+        tables.append(a)
+    m = tables[0].shape[0]
+    if any(a.shape[0] != m for a in tables):
+        raise OpenMMException("set_parameter_sets(): gamma, vdw_alpha and charge must hold the same number of sets")
+    if not 1 <= m <= _lib.MAX_PARAMETER_SETS:
+        raise OpenMMException(f"set_parameter_sets(): the number of sets must be 1 .. {_lib.MAX_PARAMETER_SETS}")
+    return (m, *tables)
+
+
 def _check(rc, error_handle=None):
     """A return code of the library: a failure raises with the message the library keeps for `error_handle` (None: the message
     of the calls that are not made on a context)."""
@@ -298,7 +322,7 @@ class HipCalcAGBNPForceKernel(_Handle):
         _check(_lib.load().agbnp_hip_create(C.byref(handle), *parameters, force.getVersion(), force.getNonbondedMethod(),
                                             force.getCutoffDistance(), self._device))
         self._h = handle
-        self._num_sets = 0  # (a new context has no partition)
+        self._num_sets = self._num_parameter_sets = 0  # (a new context has no partition and no parameter sets)
         if self._mode:
             self._call("agbnp_hip_set_mode", self._mode)
 
@@ -395,6 +419,40 @@ class HipCalcAGBNPForceKernel(_Handle):
         evaluation (finish(), withheld(), poll(), wait_verdict()); a withheld one adds nothing.  Refused (OpenMMException)
         inside a stream capture."""
         self._call("agbnp_hip_pair_matrix_device", C.c_void_p(d_positions), C.c_void_p(d_matrix), _ptr(d_energy), _ptr(stream))
+
+    _num_parameter_sets = 0  # M of the sets set through THIS object (perturbed_energies_group() checks it before the library is reached)
+
+    def set_parameter_sets(self, gamma, vdw_alpha, charge):
+        """The parameter sets that perturbed_energies() scores (include/agbnp_hip.h, agbnp_hip_set_parameter_sets): float64
+        arrays [M, N] -- or [N] for one set -- of gamma, vdw_alpha and charge, M 1 .. 16.  Radii and hydrogen flags are the
+        kernel's own; a hydrogen's gamma counts as 0.  Replaces earlier sets and survives copyParametersToContext(); changes
+        nothing an evaluation reads.  The shapes are checked here, before the library is touched."""
+        self._need()
+        m, g, a, q = _parameter_sets(gamma, vdw_alpha, charge, self.numParticles)
+        self._call("agbnp_hip_set_parameter_sets", self.numParticles, m, _dp(g), _dp(a), _dp(q))
+        self._num_parameter_sets = m
+
+    def num_parameter_sets(self):
+        """The number of parameter sets in force; 0: none have been set."""
+        return int(self._library().agbnp_hip_num_parameter_sets(self._h))
+
+    def perturbed_energies(self, positions):
+        """The energy of these positions under every parameter set of set_parameter_sets(), from ONE evaluation
+        (include/agbnp_hip.h, agbnp_hip_perturbed_energies_host): returns (energy, energies) with energy the kernel's own --
+        what energy() returns -- and energies a float64 array [M], energies[m] what a kernel initialised with set m would
+        return at these positions in this kernel's mode.  Withheld evaluations are repeated inside."""
+        pos = self._positions(positions, "perturbed_energies")
+        energies = np.zeros(max(self.num_parameter_sets(), 1))  # (no sets: the library refuses, with its message)
+        e = C.c_double(0.0)
+        self._call("agbnp_hip_perturbed_energies_host", _dp(pos), _dp(energies), C.byref(e))
+        return e.value, energies
+
+    def perturbed_energies_device(self, d_positions, d_energies, d_energy=None, stream=None):
+        """Device-resident form of perturbed_energies(): the M energies are ADDED to d_energies and the kernel's own to *d_energy
+        when it is given; raw FP64 device pointers (ints).  Asynchronous, counted in the same log as every other evaluation
+        (finish(), withheld(), poll(), wait_verdict()); a withheld one adds nothing.  Refused (OpenMMException) inside a stream
+        capture and without sets."""
+        self._call("agbnp_hip_perturbed_energies_device", C.c_void_p(d_positions), C.c_void_p(d_energies), _ptr(d_energy), _ptr(stream))
 
     def atom_order_changed(self):
         """The context has reordered its atoms (same atomIndex array, new contents): the next execute_openmm() rebuilds the
@@ -667,7 +725,7 @@ class _MemberView(HipCalcAGBNPForceKernel):
 
 
 # ---- groups: replica groups of kernels, binding groups of bindings --------------------------------------------------------------
-# Each of the twelve entry points is: the members, checked; what crosses the C ABI, marshalled; one call; the result.
+# Each of the fourteen entry points is: the members, checked; what crosses the C ABI, marshalled; one call; the result.
 def _members(who, members, cls):
     """The members of a group call as a list, checked: their number, their class, each with a handle, distinct where the
     library demands it (cls._GROUP)."""
@@ -843,6 +901,44 @@ def pair_matrix_group_host(kernels, positions):
     return [float(e) for e in energies], matrices
 
 
+def _perturbed_members(who, kernels):
+    """The members of a perturbation group, checked, and their M: every member needs sets set through set_parameter_sets()."""
+    kernels = _members(who, kernels, HipCalcAGBNPForceKernel)
+    for i, k in enumerate(kernels):
+        if k._num_parameter_sets < 1:
+            raise OpenMMException(f"{who}(): member {i}: no parameter sets have been set (set_parameter_sets())")
+    return kernels, [k._num_parameter_sets for k in kernels]
+
+
+def perturbed_energies_group(kernels, d_positions, d_energies, d_own_energies=None, stream=None):
+    """Perturbation groups (include/agbnp_hip.h, agbnp_hip_perturbed_energies_group): one call that enqueues the perturbation
+    energies of every kernel in `kernels`, the members that can share on the energy-only group's launches plus ONE perturbation
+    launch per launch set.  d_positions, d_energies, d_own_energies: lists of raw FP64 device pointers (ints), one per member;
+    d_own_energies may be None.  Every member uses its own sets: its [M_i] energies and its own energy are ADDED, gated on its
+    own verdict, as by its perturbed_energies_device().  Position buffers may be shared; the outputs must not overlap.
+    Asynchronous; each member's finish() reports its own withheld evaluations."""
+    who = "perturbed_energies_group"
+    kernels, _ = _perturbed_members(who, kernels)
+    hs, pos, ene, own = _pointer_arrays(who, kernels, True, d_positions=d_positions, d_energies=d_energies, d_own_energies=d_own_energies)
+    if pos is None or ene is None:
+        raise OpenMMException(f"{who}(): d_positions and d_energies are needed")
+    _check(_lib.load().agbnp_hip_perturbed_energies_group(hs, len(kernels), pos, ene, own, _ptr(stream)), kernels[0]._h)
+
+
+def perturbed_energies_group_host(kernels, positions):
+    """Synchronous twin of perturbed_energies_group() for host buffers: positions[i] (N_i x 3) are read; returns the lists
+    (own energies, energies) with energies[i] a float64 array [M_i] over member i's own sets.  Withheld members are repeated
+    inside."""
+    who = "perturbed_energies_group_host"
+    kernels, _ = _perturbed_members(who, kernels)
+    hs, pos, _, _ = _host_arrays(who, kernels, positions)
+    energies = [np.zeros(max(k.num_parameter_sets(), 1)) for k in kernels]  # (sized by the library's own count, as perturbed_energies())
+    out = (C.POINTER(C.c_double) * len(kernels))(*[_dp(e) for e in energies])
+    own = np.zeros(len(kernels))
+    _check(_lib.load().agbnp_hip_perturbed_energies_group_host(hs, len(kernels), pos, out, _dp(own)), kernels[0]._h)
+    return [float(e) for e in own], energies
+
+
 def binding_execute_group(bindings, d_positions, d_lambdas, d_forces, d_energies=None, d_binding_energies=None, stream=None):
     """Binding groups (include/agbnp_hip.h, agbnp_hip_binding_execute_group): one call that enqueues an evaluation of every
     BindingEnergy in `bindings` -- one gather launch, the members' evaluations as replica groups, one combine launch.
@@ -960,6 +1056,16 @@ class AGBNPContext:
             s = self._kernel.num_atom_sets()
             return 0.0, np.zeros((s, s))
         return self._kernel.pair_matrix(self._positions)
+
+    def getPerturbedEnergies(self, gamma, vdw_alpha, charge, groups=-1):
+        """(energy, energies[M]) at the context's positions: the context's own energy and the energy under each of the M
+        parameter sets gamma, vdw_alpha, charge ([M, N], or [N] for one) -- HipCalcAGBNPForceKernel.perturbed_energies().
+        Honours the force-group mask like getEnergyDecomposition()."""
+        inside = self._in_groups(groups)
+        self._kernel.set_parameter_sets(gamma, vdw_alpha, charge)
+        if not inside:
+            return 0.0, np.zeros(self._kernel.num_parameter_sets())
+        return self._kernel.perturbed_energies(self._positions)
 
     def _update_parameters(self, force):
         self._kernel.copyParametersToContext(force)

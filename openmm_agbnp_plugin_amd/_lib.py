@@ -13,6 +13,7 @@ MAX_GROUP = 16  # AGBNP_HIP_MAX_GROUP: members of one agbnp_hip_execute_group ca
 MAX_BINDING_GROUP = 16  # AGBNP_HIP_MAX_BINDING_GROUP: bindings of one agbnp_hip_binding_execute_group call
 DECOMPOSITION_TERMS = 4  # AGBNP_HIP_DECOMPOSITION_TERMS: planes of agbnp_hip_decompose_*
 MAX_SETS = 2048  # AGBNP_HIP_MAX_SETS: sets of a partition (agbnp_hip_set_atom_sets)
+MAX_PARAMETER_SETS = 16  # AGBNP_HIP_MAX_PARAMETER_SETS: parameter sets of agbnp_hip_set_parameter_sets
 
 _i, _d, _vp, _dp, _ip, _s = C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_char_p
 _vpp, _dpp = C.POINTER(C.c_void_p), C.POINTER(_dp)
@@ -36,6 +37,12 @@ SIGNATURES = {
     "agbnp_hip_num_atom_sets": [_vp],
     "agbnp_hip_pair_matrix_host": [_vp, _dp, _dp, _dp],
     "agbnp_hip_pair_matrix_device": [_vp, _vp, _vp, _vp, _vp],
+    "agbnp_hip_set_parameter_sets": [_vp, _i, _i, _dp, _dp, _dp],
+    "agbnp_hip_num_parameter_sets": [_vp],
+    "agbnp_hip_perturbed_energies_host": [_vp, _dp, _dp, _dp],
+    "agbnp_hip_perturbed_energies_device": [_vp, _vp, _vp, _vp, _vp],
+    "agbnp_hip_perturbed_energies_group": [_vpp, _i, _vpp, _vpp, _vpp, _vp],
+    "agbnp_hip_perturbed_energies_group_host": [_vpp, _i, _dpp, _dpp, _dp],
     "agbnp_hip_execute_group": [_vpp, _i, _vpp, _vpp, _vpp, _vp],
     "agbnp_hip_execute_group_host": [_vpp, _i, _dpp, _dpp, _dp],
     "agbnp_hip_energy_group": [_vpp, _i, _vpp, _vpp, _vp],

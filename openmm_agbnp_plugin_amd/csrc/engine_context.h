@@ -208,6 +208,10 @@ struct agbnp_hip_context {
   DevBuf<unsigned char> d_set_rank;
   DevBuf<int> d_set_lists, d_set_counts;
   AtomSets sets;
+  // the parameter sets of agbnp_hip_set_parameter_sets as the perturbation launch reads them (pair_kernels.h, ParamSets: three [M][n]
+  // tables; psets.num_sets == 0: none set).  No evaluation reads them; agbnp_hip_update_parameters leaves them alone
+  DevBuf<double> d_pset_nu, d_pset_alpha, d_pset_charge;
+  ParamSets psets;
   int forests_hint = 0;        // forests of the last evaluation the host has read the status of (0: none yet); reset by a fallback packing
   std::vector<int> withheld;   // evaluations (numbered from the previous finish) that the last finish found withheld
   int withheld_count = 0;
@@ -256,7 +260,7 @@ struct agbnp_hip_context {
   int group_members = 0;             // scalar 19: members of the launch set the last evaluation shared (0: it ran alone)
   int group_block_writes = 0;        // scalar 21: k_group_put launches so far
   int last_kind = 0;                 // scalar 20: 0 a full evaluation, 1 energy-only on energy-only launches, 2 energy-only run as a full one,
-                                     // 3 a per-atom decomposition, 4 a set-pair interaction matrix
+                                     // 3 a per-atom decomposition, 4 a set-pair interaction matrix, 5 perturbation energies
 
   // ---- what the last harvest read (engine_report.hip reads it back to the caller)
   Timeline timeline;
@@ -322,19 +326,20 @@ ENGINE_LOCAL int mark_rows_stale(agbnp_hip_context* c);
 // What a caller asks of one evaluation.  It is written into the argument blocks by bind_request (inside enqueue_prepare) and taken
 // out again by Unbind, on every return path of enqueue / group_enqueue: between evaluations P and T name no caller's buffer to clear
 // and no OpenMM context.
-// An analysis (agbnp_hip_decompose_*, agbnp_hip_pair_matrix_*, a decomposition group's member) is a property of the request: ONE
+// An analysis (agbnp_hip_decompose_*, agbnp_hip_pair_matrix_*, agbnp_hip_perturbed_energies_*, a group's member) is a property of the request: ONE
 // evaluation in the context's overflow log -- the energy-only evaluation of the context (energy_only_fast: its four / two launches;
 // elsewhere the full evaluation with its forces sent to d_eo_force) with the cavity launch's instantiation that also collects the
 // enlarged-radius self volumes (sv_large(): row kHvSvLarge) -- and behind it, on the same stream, the one launch that adds to the
 // caller's target: the four planes (k_decompose, decompose_kernels.hip; a launch set's members share k_group_decompose) or, with a
-// partition set, the set-pair interaction matrix (k_pair_matrix) -- one of the two.  enqueue_launch makes that launch and names the
+// partition set, the set-pair interaction matrix (k_pair_matrix), or, with parameter sets set, the energies under those sets
+// (k_perturb, perturb_kernels.hip) -- one of the three.  enqueue_launch makes that launch and names the
 // kind in last_kind; launch_set makes the shared one.  The energy leaves with the evaluation's own energy role (energy_request:
 // no energy word: into the context's spare word), the target is gated on the same verdict words.  Nothing of the context's state
 // differs from what the evaluation alone leaves: the request selects the instantiation, c->diagnostics is not touched.
 // fast+single: the terms are FP64 (header), so the evaluation runs with the single-precision option lifted for this call
 // (LiftSingle) -- the same lists and masks (the reach is the fast mode's), other pair-term arithmetic; kernel arguments travel by
 // value, so nothing enqueued before or after is affected.
-enum class Analysis { none, planes, matrix };
+enum class Analysis { none, planes, matrix, perturb };
 struct EvalRequest {
   const double* pos = nullptr;   // [3n] FP64 positions on the device
   double* force = nullptr;       // [3n] FP64 forces, added to (energy-only: where a full evaluation's would go, d_eo_force)
@@ -342,7 +347,7 @@ struct EvalRequest {
   hipStream_t stream = nullptr;
   bool energy_only = false;
   Analysis analysis = Analysis::none;  // what follows the evaluation, and ...
-  double* target = nullptr;      // ... what it adds to: the planes [4][n] or the matrix [S][S]
+  double* target = nullptr;      // ... what it adds to: the planes [4][n], the matrix [S][S] or the energies [M]
   double* zero_out = nullptr;    // the host entry points' staging buffer, cleared first (PairArgs::zero_out)
   OpenmmSource in;               // agbnp_hip_execute_openmm / agbnp_hip_energy_openmm: the context's posq ...
   OpenmmTargets omm;             // ... and its fixed-point planes and energy accumulator

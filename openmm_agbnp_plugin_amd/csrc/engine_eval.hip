@@ -197,15 +197,17 @@ int enqueue_launch(agbnp_hip_context* c, const EvalPlan& plan, const EvalRequest
   Timeline* tl = c->timeline.enabled ? &c->timeline : nullptr;
   const int tree_grid = plan.tree_grid;
   const PairLaunchShape shape = pair_launch_shape(c->P, c->version);
-  const bool matrix = r.analysis == Analysis::matrix;
-  c->last_kind = matrix ? 4 : r.sv_large() ? 3 : !r.energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
+  const bool matrix = r.analysis == Analysis::matrix, perturb = r.analysis == Analysis::perturb;
+  c->last_kind = perturb ? 5 : matrix ? 4 : r.sv_large() ? 3 : !r.energy_only ? 0 : (energy_only_fast(c) ? 1 : 2);
   // the form of the cavity launch and, with it, the replay's weights (tree_single_gather; the self volumes of pass 1 -- an
   // analysis, the diagnostics -- come out of that pass's own gather: both gathers there)
   c->T.single_gather = tree_single_gather(c->variant, c->version) && !r.sv_large() && !c->T.want_sv_large ? 1 : 0;
   auto analysis = [&]() -> int {
     if (!r.sv_large()) return AGBNP_HIP_OK;
-    const hipError_t e = matrix ? launch_pair_matrix(c->P, c->sets, c->version, r.target, st, tl) : launch_decompose(c->P, c->version, r.target, st, tl);
-    return e == hipSuccess ? AGBNP_HIP_OK : c->hipfail(e, matrix ? "launch_pair_matrix" : "launch_decompose");
+    const hipError_t e = perturb  ? launch_perturb(c->P, c->psets, c->version, r.target, st)
+                         : matrix ? launch_pair_matrix(c->P, c->sets, c->version, r.target, st, tl)
+                                  : launch_decompose(c->P, c->version, r.target, st, tl);
+    return e == hipSuccess ? AGBNP_HIP_OK : c->hipfail(e, perturb ? "launch_perturb" : matrix ? "launch_pair_matrix" : "launch_decompose");
   };
   if (c->five_active) {
     if (tl) HIP_TRY(c, tl->mark(kKTreeCavity, st));
@@ -499,8 +501,8 @@ EvalRequest energy_request(agbnp_hip_context* c, const double* d_pos, double* d_
   return r;
 }
 
-// A host form's analysis (agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host, a member of agbnp_hip_decompose_group_host): the
-// `count` words of the planes or of the matrix and the energy travel through one buffer [count + 1], cleared first (the device path
+// A host form's analysis (agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host, agbnp_hip_perturbed_energies_host, a member of a
+// group's host form): the `count` words of the planes, of the matrix or of the energies under the sets, and the energy travel through one buffer [count + 1], cleared first (the device path
 // ADDS).  stage_analysis: the buffers, the positions up, the clear, the request; fetch_analysis: the read-back, in front of the
 // harvest's wait; deliver_analysis: what came back OVERWRITES the caller's
 int stage_analysis(agbnp_hip_context* c, const double* pos, Analysis kind, size_t count, hipStream_t st, EvalRequest* r) {
@@ -519,7 +521,7 @@ void deliver_analysis(const agbnp_hip_context* c, size_t count, double* out, dou
   *energy = c->h_decomp[count];
 }
 
-// agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host: withheld evaluations are repeated
+// agbnp_hip_decompose_host, agbnp_hip_pair_matrix_host, agbnp_hip_perturbed_energies_host: withheld evaluations are repeated
 static int host_analysis(agbnp_hip_context* c, const double* pos, Analysis kind, size_t count, double* out, double* energy, const char* who) {
   HIP_TRY(c, hipSetDevice(c->device));
   const int rc0 = carry_unfinished(c);
@@ -545,7 +547,8 @@ int host_decomposition(agbnp_hip_context* c, const double* pos, double* per_atom
   return host_analysis(c, pos, Analysis::planes, 4 * (size_t)c->n, per_atom, energy, "agbnp_hip_decompose_host");
 }
 
-// agbnp_hip_energy_device (no analysis), agbnp_hip_decompose_device, agbnp_hip_pair_matrix_device, arguments checked (the kernel
+// agbnp_hip_energy_device (no analysis), agbnp_hip_decompose_device, agbnp_hip_pair_matrix_device,
+// agbnp_hip_perturbed_energies_device, arguments checked (the kernel
 // files' comments know this path by its earlier name, enqueue_decomposition)
 static int device_energy(agbnp_hip_context* c, const double* d_pos, Analysis kind, double* target, double* d_energy, void* stream, const char* who) {
   hipStream_t st;
@@ -560,6 +563,12 @@ static int device_energy(agbnp_hip_context* c, const double* d_pos, Analysis kin
 static int need_sets(agbnp_hip_context* c, const char* who) {
   if (c->sets.num_sets > 0) return AGBNP_HIP_OK;
   return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": no partition has been set (agbnp_hip_set_atom_sets)");
+}
+
+// the perturbation calls need parameter sets (agbnp_hip_set_parameter_sets)
+static int need_parameter_sets(agbnp_hip_context* c, const char* who) {
+  if (c->psets.num_sets > 0) return AGBNP_HIP_OK;
+  return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": no parameter sets have been set (agbnp_hip_set_parameter_sets)");
 }
 
 extern "C" {
@@ -626,6 +635,54 @@ int agbnp_hip_pair_matrix_device(agbnp_hip_context* c, const double* d_pos, doub
   const int rc = need_sets(c, "agbnp_hip_pair_matrix_device");
   if (rc != AGBNP_HIP_OK) return rc;
   return device_energy(c, d_pos, Analysis::matrix, d_matrix, d_energy, stream, "agbnp_hip_pair_matrix_device");
+}
+
+// The sets are the perturbation launch's alone (ParamSets), as the partition is the matrix launch's: nothing an evaluation reads
+// changes, so neither does agbnp_hip_generation().  The tables are replaced (their sizes depend on M), so perturbation calls in
+// flight are waited for first -- the context's own stream and the streams the caller has enqueued on -- and nothing else is.
+// Refused sets leave the ones before them in place.
+int agbnp_hip_set_parameter_sets(agbnp_hip_context* c, int n, int num_sets, const double* gamma, const double* vdw_alpha, const double* charge) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!gamma || !vdw_alpha || !charge) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_set_parameter_sets: null pointer");
+  if (n != c->n) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_set_parameter_sets: the number of particles differs from the context's");
+  if (num_sets < 1 || num_sets > AGBNP_HIP_MAX_PARAMETER_SETS)
+    return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_set_parameter_sets: num_sets must be 1 .. AGBNP_HIP_MAX_PARAMETER_SETS");
+  const size_t words = (size_t)num_sets * (size_t)n;
+  std::vector<double> nu(words);
+  for (size_t k = 0; k < words; k++) nu[k] = c->ish[k % (size_t)n] ? 0.0 : gamma[k] / kRadiusIncrement;  // (as gam_cav: engine_setup.hip)
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->d_pset_nu.p || c->d_pset_alpha.p || c->d_pset_charge.p) {  // (before the first tables no launch can be reading them; after a
+                                                                    // failed upload they may stand without sets: still waited for)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (void* st : c->user_streams) HIP_TRY(c, hipStreamSynchronize((hipStream_t)st));
+  }
+  c->psets = ParamSets{};  // (a failed upload leaves no sets rather than half of them)
+  HIP_TRY(c, c->d_pset_nu.upload(nu));
+  HIP_TRY(c, c->d_pset_alpha.upload(std::vector<double>(vdw_alpha, vdw_alpha + words)));
+  HIP_TRY(c, c->d_pset_charge.upload(std::vector<double>(charge, charge + words)));
+  c->psets.nu = c->d_pset_nu.p;
+  c->psets.alpha = c->d_pset_alpha.p;
+  c->psets.charge = c->d_pset_charge.p;
+  c->psets.num_sets = num_sets;
+  return AGBNP_HIP_OK;
+}
+
+int agbnp_hip_num_parameter_sets(const agbnp_hip_context* c) { return c ? c->psets.num_sets : 0; }
+
+int agbnp_hip_perturbed_energies_host(agbnp_hip_context* c, const double* pos, double* energies, double* energy) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!pos || !energies || !energy) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_perturbed_energies_host: null pointer");
+  const int rc = need_parameter_sets(c, "agbnp_hip_perturbed_energies_host");
+  if (rc != AGBNP_HIP_OK) return rc;
+  return host_analysis(c, pos, Analysis::perturb, (size_t)c->psets.num_sets, energies, energy, "agbnp_hip_perturbed_energies_host");
+}
+
+int agbnp_hip_perturbed_energies_device(agbnp_hip_context* c, const double* d_pos, double* d_energies, double* d_energy, void* stream) {
+  if (!c) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
+  if (!d_pos || !d_energies) return c->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, "agbnp_hip_perturbed_energies_device: null pointer");
+  const int rc = need_parameter_sets(c, "agbnp_hip_perturbed_energies_device");
+  if (rc != AGBNP_HIP_OK) return rc;
+  return device_energy(c, d_pos, Analysis::perturb, d_energies, d_energy, stream, "agbnp_hip_perturbed_energies_device");
 }
 
 int agbnp_hip_execute_device(agbnp_hip_context* c, const double* d_pos, double* d_force, double* d_energy, void* stream) {

@@ -1,5 +1,5 @@
 // Replica groups (engine_context.h; agbnp_hip_execute_group, group_args.h): the evaluations of several contexts on one set of launches.
-// The four kinds of group call -- full, energy-only, decomposition, pair matrix -- are one description (GroupCall), one check, one device form
+// The five kinds of group call -- full, energy-only, decomposition, pair matrix, perturbation -- are one description (GroupCall), one check, one device form
 // and one host form; what a kind does differently is in the requests it builds and in the host form's three named steps.
 #include "engine_context.h"
 
@@ -28,27 +28,35 @@ bool group_shares(const agbnp_hip_context* c, const EvalPlan& plan, const EvalRe
 
 // A group call: its kind, and the buffers its entry point was given.  host: the host form -- positions, forces and planes are host
 // arrays and the energies come back in `energies`; the device form has one energy word per member in d_energies.
-enum class GroupKind { full, energy_only, decomposition, matrix };
+enum class GroupKind { full, energy_only, decomposition, matrix, perturb };
 struct GroupCall {
   GroupKind kind;
   const char* who;
   bool host;
   const double* const* pos;  // every kind
   double* const* forces;     // a full call's, [3n] per member
-  double* const* planes;     // a decomposition's, [4n] per member; a pair-matrix call's matrices, [S_m S_m] per member
+  double* const* planes;     // a decomposition's, [4n] per member; a pair-matrix call's matrices, [S_m S_m] per member; a
+                             // perturbation call's energies under the member's sets, [M_m] per member
   double* const* d_energies;
   double* energies;
 };
 
-// words of a member's analysis target: the four planes, or the matrix of its own partition
+// the analysis that a kind's requests carry
+Analysis analysis_of(GroupKind kind) {
+  return kind == GroupKind::perturb ? Analysis::perturb : kind == GroupKind::matrix ? Analysis::matrix : kind == GroupKind::decomposition ? Analysis::planes : Analysis::none;
+}
+bool is_analysis(GroupKind kind) { return analysis_of(kind) != Analysis::none; }
+
+// words of a member's analysis target: the four planes, the matrix of its own partition, or one energy per set of its own
 size_t target_words(const agbnp_hip_context* c, GroupKind kind) {
   const size_t S = (size_t)c->sets.num_sets;
-  return kind == GroupKind::matrix ? S * S : 4 * (size_t)c->n;
+  return kind == GroupKind::perturb ? (size_t)c->psets.num_sets : kind == GroupKind::matrix ? S * S : 4 * (size_t)c->n;
 }
 
 // The arguments of a group call, checked before anything is launched or changed.  Every kind needs positions, a full call forces,
-// a decomposition planes, a pair-matrix call matrices -- and a partition in every member; the energies are the host form's array
-// or the device form's words, which the two analyses alone may leave out altogether.  The device form's outputs -- energy words,
+// a decomposition planes, a pair-matrix call matrices -- and a partition in every member --, a perturbation call energy words [M_m]
+// -- and parameter sets in every member; the energies are the host form's array or the device form's words, which the analyses
+// alone may leave out altogether.  The device form's outputs -- energy words,
 // force buffers [3n], plane buffers [4n], matrices [S_m S_m] -- must not overlap those of another member; the planes' and the
 // matrices' clashes, with one another or with an energy word, are said in a message of their own.
 int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
@@ -60,9 +68,11 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
   for (int i = 0; i < count; i++)
     if (!ctxs[i]) return AGBNP_HIP_ERR_INVALID_ARGUMENT;
   agbnp_hip_context* c0 = ctxs[0];
-  const bool full = g.kind == GroupKind::full, matrix = g.kind == GroupKind::matrix;
-  const bool analysis = matrix || g.kind == GroupKind::decomposition;
-  const std::string clash_message = std::string(who) + (matrix ? ": matrices of two members overlap" : ": plane buffers of two members overlap");
+  const bool full = g.kind == GroupKind::full, matrix = g.kind == GroupKind::matrix, perturb = g.kind == GroupKind::perturb;
+  const bool analysis = is_analysis(g.kind);
+  const std::string clash_message = std::string(who) + (perturb  ? ": energy arrays of two members overlap"
+                                                        : matrix ? ": matrices of two members overlap"
+                                                                 : ": plane buffers of two members overlap");
   // (what this kind and form read of the description; null below: not theirs)
   const double* const* pos = g.pos;
   double* const* forces = full ? g.forces : nullptr;
@@ -79,6 +89,10 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
     if (ctxs[i]->sets.num_sets < 1)
       return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
                       std::string(who) + ": member " + std::to_string(i) + ": no partition has been set (agbnp_hip_set_atom_sets)");
+  for (int i = 0; i < count && perturb; i++)
+    if (ctxs[i]->psets.num_sets < 1)
+      return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
+                      std::string(who) + ": member " + std::to_string(i) + ": no parameter sets have been set (agbnp_hip_set_parameter_sets)");
   for (int i = 0; i < count; i++) {
     if (!pos[i] || (forces && !forces[i]) || (d_energies && !d_energies[i]) || (planes && !planes[i]))
       return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
@@ -117,9 +131,11 @@ int check_group(agbnp_hip_context* const* ctxs, int count, const GroupCall& g) {
 // A pair-matrix group (agbnp_hip_pair_matrix_group; the requests carry the matrices) is the same set with the matrix launch of every
 // member in the place of the plane launch (pair_matrix_kernels.hip: k_group_pair_matrix), on the same grids; the members'
 // partitions and matrix pointers travel in that launch's argument (GroupMatrices), so the blocks are the same once more.
+// A perturbation group (agbnp_hip_perturbed_energies_group) likewise, with the perturbation launch of every member in that place
+// (perturb_kernels.hip: k_group_perturb; the members' tables and output words in GroupPerturb).
 int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const EvalPlan* plans, const EvalRequest* reqs) {
   const bool energy_only = reqs[set[0]].energy_only, decomposition = reqs[set[0]].sv_large();  // (either analysis)
-  const bool matrix = reqs[set[0]].analysis == Analysis::matrix;
+  const bool matrix = reqs[set[0]].analysis == Analysis::matrix, perturb = reqs[set[0]].analysis == Analysis::perturb;
   const hipStream_t st = reqs[set[0]].stream;
   agbnp_hip_context* const c0 = ctxs[set[0]];
   const int version = c0->version, variant = c0->variant;
@@ -129,12 +145,14 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
   GroupOutputs out;
   GroupPlanes planes;
   GroupMatrices matrices;
+  GroupPerturb perturbed;
   size_t matrix_lds = 0;
   std::memset(G, 0, sizeof(G));
   std::memset(&Gplanes, 0, sizeof(Gplanes));
   std::memset(&out, 0, sizeof(out));
   std::memset(&planes, 0, sizeof(planes));
   std::memset(&matrices, 0, sizeof(matrices));
+  std::memset(&perturbed, 0, sizeof(perturbed));
   size_t lds[5] = {tree_variant_lds_bytes(variant), 0, 0, 0, tree_variant_replay_bytes(variant)};
   for (int k = 0; k < m; k++) {
     const int i = set[k];
@@ -191,6 +209,10 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       matrices.matrix[k] = planes.per_atom[k];
       matrix_lds = std::max(matrix_lds, sizeof(double) * (size_t)c->sets.depth * (size_t)c->sets.depth);
     }
+    if (perturb) {
+      perturbed.sets[k] = c->psets;
+      perturbed.energies[k] = planes.per_atom[k];
+    }
     if (version == 1) {
       lds[1] = std::max(lds[1], sh.born_lds);
       lds[3] = std::max(lds[3], sh.chain_lds);
@@ -198,12 +220,13 @@ int launch_set(agbnp_hip_context* const* ctxs, const int* set, int m, const Eval
       lds[1] = std::max(lds[1], (size_t)sh.out_masks.role_bytes);
     }
     c->group_members = m;
-    c->last_kind = matrix ? 4 : decomposition ? 3 : energy_only ? 1 : 0;
+    c->last_kind = perturb ? 5 : matrix ? 4 : decomposition ? 3 : energy_only ? 1 : 0;
   }
   for (int s = 0; s < stages; s++) G[s].count = m;
   Gplanes.count = m;
-  // the launch behind an analysis set's energy-only stages: the members' matrices, or their planes
+  // the launch behind an analysis set's energy-only stages: the members' energies under their sets, their matrices, or their planes
   auto analysis = [&]() -> hipError_t {
+    if (perturb) return launch_group_perturb(Gplanes, perturbed, version, st);
     return matrix ? launch_group_pair_matrix(Gplanes, matrices, version, matrix_lds, st) : launch_group_decompose(Gplanes, planes, version, st);
   };
   // (an analysis set collects the self volumes of pass 1 and has no replay: both gathers)
@@ -295,11 +318,11 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const GroupCall& g, 
   rc = enter(c0, stream, &st);
   if (rc != AGBNP_HIP_OK) return rc;
   const bool full = g.kind == GroupKind::full, decomposition = g.kind == GroupKind::decomposition, matrix = g.kind == GroupKind::matrix;
-  const Analysis analysis = matrix ? Analysis::matrix : decomposition ? Analysis::planes : Analysis::none;
+  const Analysis analysis = analysis_of(g.kind);
   if (is_capturing(st))
     return c0->fail(AGBNP_HIP_ERR_INVALID_ARGUMENT,
                     std::string(g.who) + ": the stream is being captured; " +
-                        (matrix ? "groups and pair matrices" : decomposition ? "groups and decompositions" : full ? "groups" : "groups and energy-only evaluations") +
+                        (g.kind == GroupKind::perturb ? "groups and perturbation energies" : matrix ? "groups and pair matrices" : decomposition ? "groups and decompositions" : full ? "groups" : "groups and energy-only evaluations") +
                         " are not captured into graphs");
   EvalRequest reqs[kMaxGroup];
   for (int i = 0; i < count; i++) {
@@ -326,10 +349,9 @@ int group_device(agbnp_hip_context* const* ctxs, int count, const GroupCall& g, 
 
 // The host forms' per-kind steps.  A member stages in d_force_tmp [3n + 1] -- forces and energy in one buffer, cleared by the cavity
 // launch's trailing workgroups as in agbnp_hip_execute_host -- or, an analysis, in d_decomp [4n + 1] or [S S + 1] (stage_analysis) ...
-bool is_analysis(GroupKind kind) { return kind == GroupKind::decomposition || kind == GroupKind::matrix; }
 int stage_member(agbnp_hip_context* c, const GroupCall& g, int i, hipStream_t st, EvalRequest* r) {
   if (is_analysis(g.kind))
-    return stage_analysis(c, g.pos[i], g.kind == GroupKind::matrix ? Analysis::matrix : Analysis::planes, target_words(c, g.kind), st, r);
+    return stage_analysis(c, g.pos[i], analysis_of(g.kind), target_words(c, g.kind), st, r);
   HIP_TRY(c, hipMemcpyAsync(c->d_pos_in.p, g.pos[i], sizeof(double) * 3 * (size_t)c->n, hipMemcpyHostToDevice, st));
   r->pos = c->d_pos_in.p;
   r->force = g.kind == GroupKind::full ? c->d_force_tmp.p : c->d_eo_force.p;
@@ -343,6 +365,7 @@ int stage_member(agbnp_hip_context* c, const GroupCall& g, int i, hipStream_t st
 int repeat_member(agbnp_hip_context* c, const GroupCall& g, int i) {
   if (g.kind == GroupKind::decomposition) return host_decomposition(c, g.pos[i], g.planes[i], &g.energies[i]);
   if (g.kind == GroupKind::matrix) return agbnp_hip_pair_matrix_host(c, g.pos[i], g.planes[i], &g.energies[i]);
+  if (g.kind == GroupKind::perturb) return agbnp_hip_perturbed_energies_host(c, g.pos[i], g.planes[i], &g.energies[i]);
   return host_evaluation(c, g.pos[i], g.kind == GroupKind::full ? g.forces[i] : nullptr, &g.energies[i]);
 }
 // ... and what came back is delivered once the stream is idle: forces ADDED and the energy stored, the energy alone, or the planes
@@ -407,6 +430,16 @@ int agbnp_hip_pair_matrix_group(agbnp_hip_context* const* ctxs, int count, const
 int agbnp_hip_pair_matrix_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions, double* const* matrices,
                                      double* energies) {
   return group_host(ctxs, count, {GroupKind::matrix, "agbnp_hip_pair_matrix_group_host", true, positions, nullptr, matrices, nullptr, energies});
+}
+
+int agbnp_hip_perturbed_energies_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions,
+                                       double* const* d_energies, double* const* d_own_energies, void* stream) {
+  return group_device(ctxs, count, {GroupKind::perturb, "agbnp_hip_perturbed_energies_group", false, d_positions, nullptr, d_energies, d_own_energies, nullptr}, stream);
+}
+
+int agbnp_hip_perturbed_energies_group_host(agbnp_hip_context* const* ctxs, int count, const double* const* positions,
+                                            double* const* energies, double* own_energies) {
+  return group_host(ctxs, count, {GroupKind::perturb, "agbnp_hip_perturbed_energies_group_host", true, positions, nullptr, energies, nullptr, own_energies});
 }
 
 int agbnp_hip_execute_group(agbnp_hip_context* const* ctxs, int count, const double* const* d_positions, double* const* d_forces,

@@ -80,6 +80,14 @@ struct GroupMatrices {
   unsigned long long matrix[kMaxGroup];
 };
 
+// The members' parameter sets and output words of a perturbation group (agbnp_hip_perturbed_energies_group): the ParamSets its own
+// perturbation launch would take and its [M_m] words, a kernel argument of that launch alone -- once more so that the blocks stay
+// what the other kinds write.  16 x (32 + 8) bytes.
+struct GroupPerturb {
+  ParamSets sets[kMaxGroup];
+  unsigned long long energies[kMaxGroup];
+};
+
 // (sv_large: the instantiations that also collect the enlarged-radius self volumes -- a decomposition group's cavity launch;
 // single_gather: the forests' single-gather form, as the members' TreeArgs::single_gather says -- never both)
 hipError_t launch_group_cavity_five(int variant, const GroupLaunch& G, size_t lds, hipStream_t st, bool sv_large = false, bool single_gather = false);
@@ -100,6 +108,9 @@ hipError_t launch_group_decompose(const GroupLaunch& G, const GroupPlanes& O, in
 // pair-matrix groups (agbnp_hip_pair_matrix_group; pair_matrix_kernels.hip): the ONE matrix launch behind an energy-only launch
 // set, on the same grids; lds: the largest depth^2 x 8 bytes over the members
 hipError_t launch_group_pair_matrix(const GroupLaunch& G, const GroupMatrices& O, int version, size_t lds, hipStream_t st);
+// perturbation groups (agbnp_hip_perturbed_energies_group; perturb_kernels.hip): the ONE perturbation launch behind an energy-only
+// launch set, on the same grids, in the tier of the member with the most sets
+hipError_t launch_group_perturb(const GroupLaunch& G, const GroupPerturb& O, int version, hipStream_t st);
 
 #ifdef __HIP_DEVICE_COMPILE__
 typedef const __attribute__((address_space(4))) GroupMemberArgs* GroupArgsPtr;

@@ -282,4 +282,17 @@ int atom_set_tables(int n, const int* set_of_atom, std::vector<unsigned char>& r
 // the one launch behind the matrix call's evaluation: adds the matrix unless the evaluation was withheld
 hipError_t launch_pair_matrix(const PairArgs& P, const AtomSets& A, int version, double* matrix, hipStream_t st, Timeline* tl);
 
+// perturbation energies (perturb_kernels.hip; engine_eval.hip, agbnp_hip_perturbed_energies_*): the parameter sets of
+// agbnp_hip_set_parameter_sets as the launch reads them, three [M][n] tables in atom order owned by the context
+constexpr int kMaxParamSets = 16;  // AGBNP_HIP_MAX_PARAMETER_SETS (include/agbnp_hip.h)
+struct ParamSets {
+  const double* nu = nullptr;      // [M][n] gamma / roffset, 0 for a hydrogen
+  const double* alpha = nullptr;   // [M][n]
+  const double* charge = nullptr;  // [M][n]
+  int num_sets = 0;                // M; 0: none set
+};
+// the one launch behind the perturbation call's evaluation (k_decompose's grid): adds the M energies unless the evaluation was
+// withheld.  (No timeline id: the profiling table ends with k_decompose, k_pair_matrix.)
+hipError_t launch_perturb(const PairArgs& P, const ParamSets& S, int version, double* energies, hipStream_t st);
+
 }  // namespace agbnp

@@ -1,5 +1,5 @@
 // The all-pairs 64 x 64 tile walk of the analysis launches (k_decompose, decompose_kernels.hip; k_pair_matrix,
-// pair_matrix_kernels.hip): which pair of blocks a workgroup has, and the GB pair step over it.  What a launch does with a met
+// pair_matrix_kernels.hip; k_perturb, perturb_kernels.hip): which pair of blocks a workgroup has, and the GB pair step over it.  What a launch does with a met
 // pair's value is its own (the `met` argument): the walk is said once.
 //
 // All 64 x 64 block pairs (I <= J) of the atoms in atom order, numbered by arithmetic from the workgroup's number (rows of the
@@ -43,7 +43,9 @@ __device__ __forceinline__ bool pair_tile_of(int n, int tile, PairTile& W) {
 // The walk of a workgroup of 256 over its tile: met(k, s1) at step k of the lane's walk, s1 = q_i q_j f_ij of the pair met there
 // (0 for a padded atom, for a pair beyond the cutoff, and for the pair that the other lane credits).  Holds one barrier, which
 // every thread of the workgroup reaches; false (for the whole workgroup): the tile lies beyond the cutoff, nothing was met.
-template <bool kCut, class Met>
+// kUnit (k_perturb, perturb_kernels.hip: many charge tables over one walk): every real atom carries the charge 1, so that the
+// product is the pair's 0/1 weight -- 0 in exactly the three cases above -- and s1 = w f_ij.
+template <bool kCut, bool kUnit = false, class Met>
 __device__ __forceinline__ bool walk_pair_tile(const PairArgs& P, const PairTile& W, Met&& met) {
   __shared__ double2 s_xy[128], s_zq[128], s_bb[128];  // block J twice over: entry m and m + 64 are atom 64 J + m
   __shared__ double2 s_ixy[64], s_izq[64], s_ibc[64];  // block I: {x, y}, {z, q}, {B, -log2(e)/(4 B)}
@@ -55,7 +57,7 @@ __device__ __forceinline__ bool walk_pair_tile(const PairArgs& P, const PairTile
     const int ac = va ? a : n - 1;
     const double4 pa = P.aposq[ac];
     const double br = P.born[ac], inv_br = 1.0 / br;
-    const double qa = va ? pa.w : 0.0;  // zero charge switches a padded atom off
+    const double qa = va ? (kUnit ? 1.0 : pa.w) : 0.0;  // zero charge switches a padded atom off
     if (wave == 0) {
       s_xy[lane] = s_xy[lane + 64] = make_double2(pa.x, pa.y);
       s_zq[lane] = s_zq[lane + 64] = make_double2(pa.z, qa);
